@@ -10,14 +10,20 @@ enumerates), inputs resident in HBM, acceleration-structure build included.  The
 N_SETS distinct input sets (different deformed grids, queries and gradients) so that no step finds
 its inputs in the 256 MiB Infinity Cache left by the previous one.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config {1,2,3,4}]
+    python bench.py [--gpus N --steps K --warmup W] [--config {1,2,3,4,5}] [--full] [--dump-outputs DIR]
 
 --gpus N > 1 without a torch.distributed environment re-launches itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N` (one rank per GPU, RCCL);
 when the driver has already launched it that way (WORLD_SIZE set) it just runs as a rank.
 --config picks the BASELINE.json configuration that is timed as the main line (default 2 =
-configs[2], the one the metric is quoted on); at N=1 the other configurations are measured after the
-timed region and reported under "other_configs" in the same JSON line.
+configs[2], the one the metric is quoted on).
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full also measures, after
+the timed region, what the headline does not need: the median / maximum step from a second region
+with an event per step, the bandwidth probe and, at N=1, the other pipelining setting, hipGraph
+replay, the brute-force comparator, the CPU baseline and the other configurations ("other_configs");
+the --no-* options skip single parts of it.
+--dump-outputs DIR writes what the last timed step computed (rank 0's shapes) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -40,6 +46,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0                         # MI355X_MICROARCH.md: 8 TB/s HBM3E spec
 N_SETS = 3                                    # distinct input sets the steps rotate over
+DUMP_BUDGET_BYTES = 64_000_000               # --dump-outputs: at most 64 MB of .npy files in all
+DUMP_SEED = 0                                 # --dump-outputs: seed of the element sample of outputs that do not fit
 
 # BASELINE.json configs[i] -> workload.  configs[3] is "batch=64 sharded 8 shapes/GPU across 8 GPUs":
 # 8 shapes per GPU, so `--gpus 8 --config 3` IS that configuration and `--gpus 1 --config 3` one GPU's share.
@@ -150,6 +158,7 @@ class PitWorkload:
         self._side = None
         self._pq = {}
         self.last = None
+        self.last_gathered = None
         from deftet_amd import hip_ops
         if self.order_mode == "sorted":
             self.order = hip_ops.tet_spatial_order(self.sets[0]["tet"][0])
@@ -199,12 +208,18 @@ class PitWorkload:
         if self.world > 1:
             # the only collective (RCCL over xGMI): enqueued asynchronously, consumed one step later
             loss = self.gather.submit(loss.cpu() if torch.distributed.get_backend() == "gloo" else loss)
-        self.last = (cond, w, g_tet, g_pred, loss)
+        self.last = (cond, w, occ, g_tet, g_pred, loss)
 
     def drain(self):
         self._pq = {}
         if self.world > 1 and self.gather is not None:
-            self.gather.flush()                           # the last step's all-gather belongs to the timed region
+            self.last_gathered = self.gather.flush()      # the last step's all-gather belongs to the timed region
+
+    def outputs(self):
+        """what a caller of the step receives from the last one (all ranks' loss scalars when world > 1)"""
+        cond, w, occ, g_tet, g_pred, loss = self.last
+        return {"tet_index": cond, "bary_weights": w, "occ": occ, "grad_tet": g_tet, "grad_pred": g_pred,
+                "loss": self.last_gathered if self.world > 1 else loss}
 
     def _tracker_counts(self):
         from deftet_amd import hip_ops
@@ -263,6 +278,10 @@ class RasterWorkload:
     def drain(self):
         pass
 
+    def outputs(self):
+        feat, face, gxy, gff = self.last
+        return {"features": feat, "face_index": face, "grad_face_vertices_image": gxy, "grad_face_features": gff}
+
     def describe(self):
         return {"workload": "%s: %d rays x %d faces, k=%d (%s saturation policy), fwd+bwd, tile binning included; PARITY UNPINNED "
                             "(Kaolin absent)" % (self.cfg["name"], self.P, self.F, self.k, ["nearest-k", "first-k"][self.policy]),
@@ -303,6 +322,12 @@ class GeometryWorkload:
 
     def drain(self):
         pass
+
+    def outputs(self):
+        loss, boundary = self.last
+        out = {"loss": loss, "grad_pos": self.pos.grad, "grad_pred": self.pred.grad}
+        out.update({"boundary_%d" % b: f for b, f in enumerate(boundary)})      # one face list per shape (ragged)
+        return out
 
     def describe(self):
         return {"workload": "%s: T=%d tets, %d GT points and %d queries per shape, DefTet.forward_surface_align (gather, check_sign, boundary "
@@ -572,6 +597,39 @@ def summarize(wl, elapsed, per_step, kern_ms_tot, kern_cnt, steps, world, peak_m
     }
 
 
+def dump_outputs(arrays, out_dir, budget=DUMP_BUDGET_BYTES, seed=DUMP_SEED):
+    """Writes every tensor of `arrays` as out_dir/<name>.npy: floating-point outputs as float32 (float64 ones as float64),
+    integer and boolean ones as float64 (exact below 2^53).  When the files would exceed `budget` bytes, the budget is shared
+    out smallest array first and an array that does not fit its share is replaced by a fixed sample: the elements of the
+    flattened array at the sorted positions np.random.default_rng(seed).choice(numel, k, replace=False).  The sample depends
+    on the array's size only, so two builds of the project write the same positions.  Returns {name: record} for the line."""
+    items = []
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = t.detach()
+        dt = torch.float64 if (t.dtype == torch.float64 or not t.is_floating_point()) else torch.float32
+        items.append((name, t, dt))
+    header = 256                                          # bytes allowed per .npy header (numpy writes 128 for a few dimensions)
+    left, todo = budget - header * len(items), len(items)
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t, dt in sorted(items, key=lambda x: x[1].numel() * x[2].itemsize):
+        n = t.numel()
+        k = min(n, max(0, left // todo) // dt.itemsize)
+        flat = t.reshape(-1)
+        if k < n:
+            pos = np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+            flat = flat[torch.from_numpy(pos).to(flat.device)]
+        a = flat.to(dt).cpu().numpy()
+        a = a.reshape(tuple(t.shape)) if k == n else a
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = {"shape": list(t.shape), "dtype": str(a.dtype), "sampled": k < n, "elements": int(k)}
+        left -= a.nbytes
+        todo -= 1
+    return written
+
+
 def pin_to_gpu_numa_node(dev_index):
     """Best effort: restrict this rank's CPU threads to the cores of its GPU's NUMA node (eight ranks that all start on node 0
     share its memory controllers while they build their inputs and launch).  Returns a short description for the line."""
@@ -617,12 +675,18 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", type=int, default=2, choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline after the timed region (median / "
+                    "maximum step, bandwidth probe; at N=1 pipelining, hipGraph replay, brute force, CPU baseline, other configurations)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32 / "
+                    "float64, at most 64 MB in all: a fixed, seeded sample of the elements of outputs that do not fit)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true")
     ap.add_argument("--no-brute-force", action="store_true", help="skip the brute-force HIP comparator (one shape, ~50 ms at configs[2])")
     ap.add_argument("--no-unpipelined", action="store_true", help="skip the extra un-overlapped timing loop (profiling runs: every traversal launch in the kernel table is then a timed-region launch)")
     ap.add_argument("--no-bandwidth-probe", action="store_true", help="skip the 1 GiB copy/read probe (profiling runs: keeps its launches out of the kernel table)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -680,8 +744,13 @@ def main():
     gather = sharding.LossGather()
     wl = make_workload(args.config, rank, device, world, gather)
     elapsed, _, kms, kcnt = timed(wl, lib, args.steps, args.warmup, world)
-    # median / maximum step: a second region of the same K steps with an event after every step (not the headline)
-    _, per_step, _, _ = timed(wl, lib, args.steps, 2, world, step_events=True)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(wl.outputs(), args.dump_outputs)
+    per_step = []
+    if args.full:
+        # median / maximum step: a second region of the same K steps with an event after every step (not the headline)
+        _, per_step, _, _ = timed(wl, lib, args.steps, 2, world, step_events=True)
     rank_ms = None
     if world > 1:
         # the job's time is the slowest rank's; every rank's own time is kept beside it so that a straggler is visible
@@ -692,21 +761,24 @@ def main():
         elapsed = float(allt.max().item())
 
     if rank == 0:
-        peak = measure_bandwidth(device) if (world == 1 and not args.no_bandwidth_probe) else None
+        peak = measure_bandwidth(device) if (args.full and world == 1 and not args.no_bandwidth_probe) else None
         main_line = summarize(wl, elapsed, per_step, kms, kcnt, args.steps, world, peak)
         line = {
             "metric": ("M tet-point tests/s (fwd+bwd) at res=70, 100k queries" if args.config == 2 else
                        "%s (fwd+bwd), %s" % (wl.unit, CONFIGS[args.config]["name"])),
             "value": main_line["value"], "unit": main_line["unit"],
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": main_line["ms_per_step"], "ms_per_step_median": main_line["ms_per_step_median"],
-            "ms_per_step_max": main_line["ms_per_step_max"],
-            "median_max_from": "a second region of the same K steps with a HIP event after every step",
+            "ms_per_step": main_line["ms_per_step"],
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "config": wl.describe(),
             "roofline": main_line["roofline"],
         }
+        if args.full:
+            line.update({"ms_per_step_median": main_line["ms_per_step_median"], "ms_per_step_max": main_line["ms_per_step_max"],
+                         "median_max_from": "a second region of the same K steps with a HIP event after every step"})
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         if world > 1:
             line["rccl_ranks"] = torch.distributed.get_world_size()
             if line["rccl_ranks"] != args.gpus:
@@ -715,7 +787,7 @@ def main():
             line["ranks"] = identities                    # rank -> (host, device, PCI address, NUMA node its threads were pinned to)
             line["distinct_devices"] = len({(i["host"], i["device"]) for i in identities})
             line["ms_per_step_by_rank"] = {"min": min(rank_ms), "max": max(rank_ms), "all": rank_ms}
-        if world == 1:
+        if world == 1 and args.full:
             if isinstance(wl, PitWorkload) and not args.no_unpipelined:
                 # the same K steps with the other setting of the cross-step overlap (not the headline; printed beside it)
                 wl.pipeline = not wl.pipeline

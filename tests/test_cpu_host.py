@@ -381,43 +381,6 @@ def test_overlay_installs_and_reference_shaped_callers_resolve_to_hip_ops():
         sys.modules.update({k: v for k, v in saved.items() if k not in sys.modules})
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/layers"), reason="needs the reference checkout (authoring container only)")
-def test_unchanged_reference_modules_import_through_the_overlay():
-    """The reference's own layers/DefTet/deftet.py, utils/mesh_utils.py and utils/tet_utils.py — unmodified, from
-    /root/reference — import with the overlay installed (no nvcc, no THC, no cv2, no kaolin, no run.so in the CWD)
-    and end up holding this repository's operators."""
-    import deftet_amd.overlay as overlay
-    saved, saved_path = dict(sys.modules), list(sys.path)
-    _clean_overlay_names()
-    try:
-        names = overlay.install(kaolin=True)
-        sys.path.insert(0, "/root/reference")
-        import importlib
-        ref_deftet = importlib.import_module("layers.DefTet.deftet")
-        ref_mesh = importlib.import_module("utils.mesh_utils")
-        ref_tet = importlib.import_module("utils.tet_utils")
-        assert ref_deftet.__file__.startswith("/root/reference/") and ref_tet.__file__.startswith("/root/reference/")
-        import deftet_amd.layers.DefTet.check_condition_tetrahedron_base.utils as a
-        import deftet_amd.layers.DefTet.tet_face_adj_m_idx.utils as b
-        import deftet_amd.layers.DefTet.tet_analytic_distance_batch.utils as c
-        import deftet_amd.layers.nearest_neighbor as d
-        assert ref_deftet.check_condition_f_base is a.check_condition_f_base
-        assert ref_mesh.tet_face_adj_m_f_idx is b.tet_face_adj_m_f_idx
-        assert ref_mesh.tet_analytic_distance_f_batch is c.tet_analytic_distance_f_batch
-        assert ref_mesh.NearestNeighbor is d.NearestNeighbor
-        assert type(ref_tet.c_tet_point_adj).__module__ == "deftet_amd.utils.lib.tet_point_adj.interface"
-        assert type(ref_tet.c_tet_face_adj).__module__ == "deftet_amd.utils.lib.tet_face_adj.interface"
-        assert type(ref_tet.c_obj_tet_adj_share).__module__ == "deftet_amd.utils.lib.tet_adj_share.interface"
-        assert getattr(ref_deftet.kal, "__deftet_amd_shim__", False)
-        m = ref_deftet.DefTet()                                  # the reference's module object, our operators underneath
-        assert hasattr(m, "forward_surface_align")
-        overlay.uninstall(names)
-    finally:
-        sys.path[:] = saved_path
-        _clean_overlay_names()
-        sys.modules.update({k: v for k, v in saved.items() if k not in sys.modules})
-
-
 def test_bench_self_launch_command(monkeypatch):
     """`python bench.py --gpus N` with no torch.distributed environment must become the launcher the driver would
     otherwise be: torch.distributed.run, one node, N ranks, loopback rendezvous, the original arguments passed on."""
@@ -440,6 +403,31 @@ def test_bench_self_launch_command(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
     # every BASELINE configuration has a workload definition (5 = the full geometry step, not a BASELINE entry)
     assert sorted(bench.CONFIGS) == [1, 2, 3, 4, 5] and bench.CONFIGS[2]["res"] == 70 and bench.CONFIGS[2]["n_query"] == 100_000
+
+
+def test_bench_dump_outputs_within_budget_and_reproducible(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 files only, within the byte budget, small outputs written whole and exact,
+    an output too large for its share replaced by a seeded sample of its elements that is the same from call to call."""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    arrays = {"index": torch.arange(-1, 999, dtype=torch.int32).reshape(10, 100, 1), "w": torch.rand(10, 100, 4, generator=g),
+              "w64": torch.rand(7, dtype=torch.float64, generator=g), "big": torch.rand(400, 300, generator=g), "absent": None}
+    budget = 200_000
+    runs = []
+    for k in range(2):
+        out = tmp_path / str(k)
+        rec = bench.dump_outputs(arrays, str(out), budget=budget)
+        files = {p.stem: np.load(p) for p in out.glob("*.npy")}
+        assert set(files) == {"index", "w", "w64", "big"} and set(rec) == set(files)
+        assert sum(p.stat().st_size for p in out.glob("*.npy")) <= budget
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert files["index"].dtype == np.float64 and np.array_equal(files["index"], arrays["index"].numpy())
+        assert np.array_equal(files["w"], arrays["w"].numpy()) and np.array_equal(files["w64"], arrays["w64"].numpy())
+        big = files["big"]
+        assert rec["big"]["sampled"] and rec["big"]["shape"] == [400, 300] and 0 < big.size == rec["big"]["elements"] < 120_000
+        assert np.isin(big, arrays["big"].numpy().reshape(-1)).all()
+        runs.append(files)
+    assert all(np.array_equal(runs[0][n], runs[1][n]) for n in runs[0])
 
 
 def test_profiles_readme_quotes_what_the_evidence_files_hold():

@@ -1,6 +1,6 @@
 """CPU tests (no GPU): the oracle against the golden vectors generated from the reference's
-Python code (tests/golden/gen_golden.py) and against the reference's native builders
-compiled into oracle/_ref."""
+Python code (tests/golden/gen_golden.py) and against what the reference's native builders
+returned (tests/golden/ref_native_builders.npz, from oracle/_ref; live as well where it is built)."""
 import hashlib
 import os
 
@@ -91,39 +91,40 @@ def _random_mesh(rng, res):
     return tets[keep].astype(np.int32), verts.shape[0]
 
 
+def _native(key):
+    """what the reference's run.cpp builders returned (tests/golden/ref_native_builders.npz, written by gen_ref_native.py from
+    oracle/_ref); where oracle/_ref is built, the live native library is checked against the same rows as well"""
+    return load("ref_native_builders.npz")[key]
+
+
 @pytest.mark.parametrize("seed", range(6))
 def test_builders_match_reference_native(oracle, seed):
-    """row-for-row equality with the reference's run.cpp compiled into oracle/_ref"""
-    if not oracle.RefBuilders.available():
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    ref = oracle.RefBuilders()
-    rng = np.random.default_rng(seed)
-    tets, n_point = _random_mesh(rng, 4 + 2 * (seed % 3))
-    assert np.array_equal(oracle.tet_adj_share(tets, n_point), ref.tet_adj_share(tets, n_point))
-    assert np.array_equal(oracle.tet_face_adj(tets, n_point, wrap32=True), ref.tet_face_adj(tets, n_point))
-    assert np.array_equal(oracle.tet_point_adj(tets, n_point), lexsorted(ref.tet_point_adj(tets, n_point)))
-    pts = rng.uniform(-1, 1, (500, 3)).astype(np.float32)
-    pts[100:200] = pts[:100] + rng.choice([0, 1e-7, 4e-6, 1e-5], (100, 3)).astype(np.float32)
-    pts[200:220] = np.round(pts[200:220], 5) + np.float32(5e-6)        # rounding ties of %.5f
-    pts[220] = 0.0
-    pts[221] = -0.0                                                     # "-0.00000" != "0.00000"
-    pts[222] = -1e-7
-    a, b = oracle.colaps_v(pts), ref.colaps_v(pts)
-    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    """row-for-row equality with the reference's run.cpp (stored outputs; live from oracle/_ref when it is built)"""
+    s = "s%d_" % seed
+    tets, n_point, pts = _native(s + "tets"), int(_native(s + "n_point")), _native(s + "pts")
+    want = {k: _native(s + k) for k in ("adj_share", "face_adj", "point_adj", "colaps_m", "colaps_inv")}
+    assert np.array_equal(oracle.tet_adj_share(tets, n_point), want["adj_share"])
+    assert np.array_equal(oracle.tet_face_adj(tets, n_point, wrap32=True), want["face_adj"])
+    assert np.array_equal(oracle.tet_point_adj(tets, n_point), lexsorted(want["point_adj"]))
+    a = oracle.colaps_v(pts)
+    assert np.array_equal(a[0], want["colaps_m"]) and np.array_equal(a[1], want["colaps_inv"])
+    if oracle.RefBuilders.available():
+        ref = oracle.RefBuilders()
+        assert np.array_equal(ref.tet_adj_share(tets, n_point), want["adj_share"])
+        assert np.array_equal(ref.tet_face_adj(tets, n_point), want["face_adj"])
+        assert np.array_equal(ref.tet_point_adj(tets, n_point), want["point_adj"])
+        b = ref.colaps_v(pts)
+        assert np.array_equal(b[0], want["colaps_m"]) and np.array_equal(b[1], want["colaps_inv"])
 
 
 def test_face_adj_int32_wrap_matches_native(oracle):
     """the native tet_face_adj keys edges with a 32-bit int (run.cpp:39): with n_point > 46340
     the key wraps; the oracle's wrap32 mode must still equal the native output row for row"""
-    if not oracle.RefBuilders.available():
-        pytest.skip("oracle/_ref not built")
-    ref = oracle.RefBuilders()
-    rng = np.random.default_rng(3)
-    tets, n_small = _random_mesh(rng, 4)
-    n_point = 70000
-    remap = np.sort(rng.choice(n_point, n_small, replace=False)).astype(np.int32)
-    tets = remap[tets]
-    assert np.array_equal(oracle.tet_face_adj(tets, n_point, wrap32=True), ref.tet_face_adj(tets, n_point))
+    tets, n_point, want = _native("wrap_tets"), int(_native("wrap_n_point")), _native("wrap_face_adj")
+    assert n_point > 46340
+    assert np.array_equal(oracle.tet_face_adj(tets, n_point, wrap32=True), want)
+    if oracle.RefBuilders.available():
+        assert np.array_equal(oracle.RefBuilders().tet_face_adj(tets, n_point), want)
     # and the Python-twin mode (exact keys) gives the same adjacency as on the un-remapped mesh
     a = lexsorted(oracle.tet_face_adj(tets, n_point, wrap32=False))
     b = lexsorted(oracle.tet_face_adj(tets, n_point, wrap32=True))

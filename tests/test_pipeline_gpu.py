@@ -155,14 +155,16 @@ def test_overlay_reference_shaped_callers_run_on_gpu(cuda, oracle):
 
 def test_bench_self_launches_two_ranks(cuda):
     """`python bench.py --gpus 2` with no torch.distributed environment re-launches itself under torch.distributed.run
-    and rank 0 prints the JSON line (the driver's command).  Single-GPU box: both ranks share cuda:0 and the collectives
-    are staged over gloo (DEFTET_BENCH_TEST_SHARED_GPU=1); on a multi-GPU node the same command runs over RCCL."""
+    and rank 0 prints the JSON line (the driver's command; --full for the median / maximum step).  Single-GPU box: both
+    ranks share cuda:0 and the collectives are staged over gloo (DEFTET_BENCH_TEST_SHARED_GPU=1); on a multi-GPU node the
+    same command runs over RCCL."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, DEFTET_BENCH_TEST_SHARED_GPU="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "1"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "1",
+                          "--full"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -198,6 +200,40 @@ def test_bench_eight_ranks_config3_shared_gpu(cuda):
     # test run has ONE distinct device; a real run asserts eight), the transport probe passed before the timed region
     assert rec["config"]["inputs_generated_on"] == "gpu"
     assert [r["rank"] for r in rec["ranks"]] == list(range(8)) and rec["distinct_devices"] == 1 and rec["backend"] == "gloo"
+
+
+def test_bench_plain_run_dumps_the_same_outputs_twice(cuda, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the line holds the headline fields and nothing that
+    --full measures; the dumped outputs of the last timed step are float32 / float64, within 64 MB, consistent (weights of a
+    hit sum to one) and identical in a second run with the same arguments."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                              "--config", "1", "--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 4 and rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["higher_is_better"] is True
+        assert rec["unit"] == "M tet-point tests/s" and rec["dtype"] == "f32" and rec["roofline"]["launches_timed"] == 4
+        for moved in ("ms_per_step_median", "cpu_baseline", "brute_force_hip", "other_configs", "ms_per_step_hipgraph"):
+            assert moved not in rec, moved
+        assert "peak_measured" not in rec["roofline"]
+        files = {p.stem: np.load(p) for p in d.glob("*.npy")}
+        assert set(files) == {"tet_index", "bary_weights", "occ", "grad_tet", "grad_pred", "loss"} == set(rec["dumped_outputs"])
+        assert sum(p.stat().st_size for p in d.glob("*.npy")) <= 64_000_000
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        idx, w = files["tet_index"], files["bary_weights"]
+        assert idx.shape == (8, 50_000, 1) and w.shape == (8, 50_000, 4) and files["loss"].shape == (8,)
+        hit = idx[..., 0] >= 0
+        assert 0.5 < hit.mean() < 1 and np.allclose(w[hit].sum(-1), 1.0, atol=1e-5) and np.isfinite(files["grad_tet"]).all()
+        dumps.append(files)
+    for name, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][name]), name
 
 
 def test_forward_surface_align_save_writes_the_reference_obj_files(cuda, oracle, tmp_path):

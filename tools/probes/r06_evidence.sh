@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 O=gpurun_out/r06; mkdir -p $O
 parts="${*:-pmc bench prof ab host tol}"
-B="python $PWD/bench.py"
+B="python $PWD/bench.py --full"      # (--full: the lines below quote the median step, hipGraph replay and the other configurations)
 Q="--no-cpu-baseline --no-other-configs --no-bandwidth-probe --no-brute-force"
 has() { case " $parts " in *" $1 "*) return 0;; esac; return 1; }
 
