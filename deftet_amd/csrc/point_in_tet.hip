@@ -888,8 +888,116 @@ struct CellBox {
     int cx0, cx1, cy0, cy1, cz0, cz1;
 };
 
+// ------------------------------------------------------------------------------------
+// Tet sources.  Every kernel that reads tets takes its tets through one of these (a template parameter): what follows the
+// load is the same code for both, so the two give the same bits.
+//   DenseTets    the gathered [B,T,4,3] tensor: three 16-byte loads per tet (the kernels of rounds 1-6, unchanged).
+//   IndexedTets  vertices [B,V,3] + index list [idx_batch,T,4] (idx_batch 1: shared by the shapes): one 16-byte index load,
+//                then four 12-byte vertex loads.  An index outside [0, V) (one unsigned compare per corner) reads as
+//                (NaN, NaN, NaN) — what deftet_tet_gather_fwd_f32 writes for it.  (The bad-index flag is raised by a separate
+//                pass over the list, k_idx_check: a flag pointer carried into the loads cost the ordered wave kernel a spill.)
+// `Arg` is the kernel parameter (for DenseTets the __restrict__ pointer of before, so the dense kernels see the same
+// aliasing facts), `Ref` names one tet (for DenseTets the pointer to its record), get* load it.
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ float4 ld_f4_hint(const float4 *p, bool nt)
+{
+    if (!nt) return *p;
+    typedef float f4v __attribute__((ext_vector_type(4)));
+    const f4v x = __builtin_nontemporal_load(reinterpret_cast<const f4v *>(p));
+    return make_float4(x[0], x[1], x[2], x[3]);
+}
+struct DenseTets {
+    typedef const float *__restrict__ Arg;
+    typedef const float *Ref;
+    typedef const float *__restrict__ RefArg;          // (parameter of the out-of-line helpers, as before)
+    const float *tet;
+    __host__ __device__ __forceinline__ DenseTets(const float *p) : tet(p) {}
+    __device__ __forceinline__ Ref at(int b, int T, int t) const { return tet + ((size_t)b * T + t) * 12; }
+    __device__ __forceinline__ Ref at_flat(long long i, int /*T*/) const { return tet + i * 12; }
+    template <bool NT = false>
+    __device__ __forceinline__ static void get3(Ref r, float4 &a, float4 &bq, float4 &c)
+    {
+        const float4 *src = reinterpret_cast<const float4 *>(r);
+        a = ld_f4_hint(src, NT); bq = ld_f4_hint(src + 1, NT); c = ld_f4_hint(src + 2, NT);
+    }
+    template <bool NT = false>
+    __device__ __forceinline__ static void get4(Ref r, float (&v)[12])         // three 16-byte loads
+    {
+        float4 a, bq, c;
+        get3<NT>(r, a, bq, c);
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+        v[4] = bq.x; v[5] = bq.y; v[6] = bq.z; v[7] = bq.w;
+        v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w;
+    }
+    __device__ __forceinline__ static void get(Ref r, float (&v)[12])          // twelve 4-byte loads (the out-of-line helpers)
+    {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) v[k] = r[k];
+    }
+};
+struct IndexedTets {
+    const float *pos;       // [B, V, 3], 4-byte aligned
+    const int *idx;         // [idx_batch, T, 4], 16-byte aligned
+    long long idxStride;    // ints between the lists of two shapes: 0 (shared list) or 4 T
+    int V;
+    typedef IndexedTets Arg;
+    struct Ref {
+        const float *p;     // the shape's vertices
+        const int *ix;      // the tet's four indices
+        unsigned V;
+    };
+    typedef Ref RefArg;
+    __device__ __forceinline__ Ref at(int b, int T, int t) const
+    {
+        (void)T;
+        return Ref{pos + (size_t)b * (size_t)V * 3, idx + (size_t)b * idxStride + (size_t)t * 4, (unsigned)V};
+    }
+    __device__ __forceinline__ Ref at_flat(long long i, int T) const { return at((int)(i / T), T, (int)(i % T)); }
+    template <bool NT = false>
+    __device__ __forceinline__ static void get4(const Ref &r, float (&v)[12])
+    {
+        const int4 c = *reinterpret_cast<const int4 *>(r.ix);
+        const int ci[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned u = (unsigned)ci[k];
+            if (u < r.V) {
+                const float *p = r.p + (size_t)u * 3;
+                v[3 * k] = p[0]; v[3 * k + 1] = p[1]; v[3 * k + 2] = p[2];
+            } else {
+                v[3 * k] = v[3 * k + 1] = v[3 * k + 2] = __int_as_float(0x7FC00000);   // deftet_tet_gather_fwd_f32's fill
+            }
+        }
+    }
+    template <bool NT = false>
+    __device__ __forceinline__ static void get3(const Ref &r, float4 &a, float4 &bq, float4 &c)
+    {
+        float v[12];
+        get4(r, v);
+        a = make_float4(v[0], v[1], v[2], v[3]); bq = make_float4(v[4], v[5], v[6], v[7]); c = make_float4(v[8], v[9], v[10], v[11]);
+    }
+    __device__ __forceinline__ static void get(const Ref &r, float (&v)[12]) { get4(r, v); }
+};
+// *bad = 1 when an index of the list is outside [0, V) (n = idx_batch * T tets; benign race: all write 1)
+__global__ __launch_bounds__(256) void k_idx_check(const int4 *__restrict__ idx, long long n, unsigned V, int *bad)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int4 c = idx[i];
+    if ((unsigned)c.x >= V || (unsigned)c.y >= V || (unsigned)c.z >= V || (unsigned)c.w >= V) *bad = 1;
+}
+
+// one template argument for kernels that have two (DEFTET_LAUNCH splits its arguments at commas): the tet source and a flag
+// (ORD of the traversal kernels, SPARSE of k_bary_bwd_hits)
+template <class TS_, bool F>
+struct TetCfg {
+    typedef TS_ TS;
+    static constexpr bool flag = F;
+};
+
 // The round-1 kernel (DEFTET_PIT_EXACT): one lane per tet, box test + the exact predicate on every candidate.
-__global__ __launch_bounds__(256, PIT_WAVES) void k_tet_scan(const float *__restrict__ tet, int T, int Q,
+template <class TS>
+__global__ __launch_bounds__(256, PIT_WAVES) void k_tet_scan(typename TS::Arg tet, int T, int Q,
                                                   const float *__restrict__ gparam, int G, int Gx, const int *__restrict__ table,
                                                   long long cellStride, const float4 *__restrict__ sortedQ, int *result, int *counters,
                                                   int *irregT, int2 *hits, const float *__restrict__ pts,
@@ -915,13 +1023,18 @@ __global__ __launch_bounds__(256, PIT_WAVES) void k_tet_scan(const float *__rest
     const int vb = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
     const int t = vb * blockDim.x + threadIdx.x;
     if (vb >= nblk || t >= T) return;
+    const TS ts(tet);
     float v[12];
-    {
+    if constexpr (std::is_same<TS, DenseTets>::value) {
+        // (the dense load spelled out as before: through TS::get4 the compiler gave this kernel one more register, 65, and seven
+        // waves per SIMD instead of eight)
         const float4 *src = reinterpret_cast<const float4 *>(tet + ((size_t)b * T + t) * 12);
         float4 a = src[0], bq = src[1], c = src[2];
         v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
         v[4] = bq.x; v[5] = bq.y; v[6] = bq.z; v[7] = bq.w;
         v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w;
+    } else {
+        TS::get4(ts.at(b, T, t), v);
     }
     Planes P;
     make_planes(v, P);
@@ -1087,6 +1200,7 @@ __device__ __forceinline__ void stream_store(float4 *p, const float4 v)
 }
 __device__ __forceinline__ void stream_store(float *p, float v) { __builtin_nontemporal_store(v, p); }
 // probe switches (tools/probes/build_variant.sh): the tet records of a launch are read once — do they belong in the L2s?
+// (the tet sources' get3 / get4<NT> issue the streaming form, ld_f4_hint)
 #ifndef PIT_SCAN_TET_NT
 #define PIT_SCAN_TET_NT 0
 #endif
@@ -1099,13 +1213,6 @@ __device__ __forceinline__ void stream_store(float *p, float v) { __builtin_nont
 #ifndef PIT_REC_NT
 #define PIT_REC_NT 1        // hit records of the wave kernel leave with the streaming hint: the backward is their only reader, and
 #endif                      // k_finalize, which runs in between, finds more of the tets it gathers in the caches (28.2 -> 26.8 us)
-template <bool NT>
-__device__ __forceinline__ float4 load_f4(const float4 *p)
-{
-    if (!NT) return *p;
-    const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(p));
-    return make_float4(x[0], x[1], x[2], x[3]);
-}
 __device__ __forceinline__ void store_rec(int2 *p, const int2 v)
 {
     if (PIT_REC_NT) {
@@ -1140,13 +1247,13 @@ __device__ __forceinline__ void store_b64_off(void *base, unsigned byte_off, int
 // the very rare tets that met the filter's undecided band more than twice.  Out of line and called
 // AFTER the traversal loop, so that nothing of it is scheduled (or kept in registers) inside the loop.  Publishes every
 // accepted query with atomicMin (idempotent w.r.t. the ones the filter already accepted) and writes the hit record.
-__device__ __noinline__ void exact_rescan(const float *__restrict__ tv, int t, const int *__restrict__ tb, const float4 *__restrict__ sq,
+template <class TS>
+__device__ __noinline__ void exact_rescan(typename TS::RefArg tv, int t, const int *__restrict__ tb, const float4 *__restrict__ sq,
                                           int *res, int G, int Gx, int cx0, int cx1, int cy0, int cy1, int cz0, int cz1,
                                           float m, int *counters, int nB, int b, int2 *hits, int4 *spill, size_t idx)
 {
     float vv[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) vv[k] = tv[k];
+    TS::get(tv, vv);
     Planes P;
     make_planes(vv, P);
     float elo[3], ehi[3];
@@ -1181,11 +1288,11 @@ __device__ __noinline__ void exact_rescan(const float *__restrict__ tv, int t, c
 // filter's undecided band.  Out of line and re-loading the tet, so that neither the exact planes nor the vertices are
 // kept in registers by the traversal loop.  (For a regular tet the predicate itself is the reference's decision: every
 // point it accepts lies in the enlarged box, DESIGN.md section 3, so no box test is needed.)
-__device__ __noinline__ float exact_accept(const float *__restrict__ tv, float x, float y, float z)
+template <class TS>
+__device__ __noinline__ float exact_accept(typename TS::RefArg tv, float x, float y, float z)
 {
     float vv[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) vv[k] = tv[k];
+    TS::get(tv, vv);
     Planes P;
     make_planes(vv, P);
     return accept(P, x, y, z) ? 1.0f : -1.0f;
@@ -1193,21 +1300,21 @@ __device__ __noinline__ float exact_accept(const float *__restrict__ tv, float x
 
 // irregular queries (NaN / Inf / huge; normally none): re-load the tet so that its vertices need not stay in
 // registers across the traversal loop
-__device__ __noinline__ void irregular_tail_slow(const float *__restrict__ tet, int t, int b, int T, int Q, const float *__restrict__ pts,
+template <class TS>
+__device__ __noinline__ void irregular_tail_slow(typename TS::Arg tet, int t, int b, int T, int Q, const float *__restrict__ pts,
                                                  const int *__restrict__ counters, const int *__restrict__ irregQ, int *result)
 {
     float v[12];
-    const float *src = tet + ((size_t)b * T + t) * 12;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) v[k] = src[k];
+    TS::get(TS(tet).at(b, T, t), v);
     Planes P;
     make_planes(v, P);
     irregular_queries_tail(P, t, b, Q, pts, counters, irregQ, result);
 }
-__device__ __forceinline__ void irregular_tail(const float *__restrict__ tet, int t, int b, int T, int Q, const float *__restrict__ pts,
+template <class TS>
+__device__ __forceinline__ void irregular_tail(typename TS::Arg tet, int t, int b, int T, int Q, const float *__restrict__ pts,
                                                const int *__restrict__ counters, const int *__restrict__ irregQ, int *result)
 {
-    if (counters[b * 4 + 1] > 0) irregular_tail_slow(tet, t, b, T, Q, pts, counters, irregQ, result);
+    if (counters[b * 4 + 1] > 0) irregular_tail_slow<TS>(tet, t, b, T, Q, pts, counters, irregQ, result);
 }
 
 #ifndef PIT_BATCH
@@ -1219,8 +1326,8 @@ __device__ __forceinline__ void irregular_tail(const float *__restrict__ tet, in
 // ORD: the lane at position p of the launch works on tet order[p] (a permutation of [0, T) shared by the shapes of the batch,
 // deftet_tet_spatial_order_f32) and publishes / records under that ORIGINAL index, so every output is the same as without
 // the permutation; a template argument, so that the unordered instance is the round-4 kernel unchanged.
-template <bool ORD>
-__global__ __launch_bounds__(256, PIT_WAVES) void k_tet_scan_slab(const float *__restrict__ tet, int T, int Q,
+template <class C>
+__global__ __launch_bounds__(256, PIT_WAVES) void k_tet_scan_slab(typename C::TS::Arg tet, int T, int Q,
                                                   const float *__restrict__ gparam, int G, int Gx, const int *__restrict__ table,
                                                   long long cellStride, const float4 *__restrict__ sortedQ, int *result, int *counters,
                                                   int *irregT, int2 *hits, const float *__restrict__ pts,
@@ -1236,6 +1343,8 @@ __global__ __launch_bounds__(256, PIT_WAVES) void k_tet_scan_slab(const float *_
         ucount[hpad + blockIdx.y] = 0;
         ucount[2 * hpad + blockIdx.y] = 0;
     }
+    typedef typename C::TS TS;
+    constexpr bool ORD = C::flag;
     const int b = blockIdx.y;
     const int nblk = gridDim.x;
     const int per = (nblk + 7) >> 3;
@@ -1244,14 +1353,9 @@ __global__ __launch_bounds__(256, PIT_WAVES) void k_tet_scan_slab(const float *_
     if (vb >= nblk || pos >= T) return;
     const int t = ORD ? order[pos] : pos;
     PHASE_DECL;
+    const TS ts(tet);
     float v[12];
-    {
-        const float4 *src = reinterpret_cast<const float4 *>(tet + ((size_t)b * T + t) * 12);
-        float4 a = src[0], bq = src[1], c = src[2];
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-        v[4] = bq.x; v[5] = bq.y; v[6] = bq.z; v[7] = bq.w;
-        v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w;
-    }
+    TS::get4(ts.at(b, T, t), v);
     Filter F;
     TetBox bx;
     const Grid g = load_grid(gparam + b * kGridWords);
@@ -1293,7 +1397,7 @@ __global__ __launch_bounds__(256, PIT_WAVES) void k_tet_scan_slab(const float *_
     }
     if (ehi[0] < g.lo[0] || elo[0] > g.hi[0] || ehi[1] < g.lo[1] || elo[1] > g.hi[1] || ehi[2] < g.lo[2] || elo[2] > g.hi[2]) {
         if (hits) hits[(size_t)b * T + t] = make_int2(-1, -1);
-        irregular_tail(tet, t, b, T, Q, pts, counters, irregQ, result);
+        irregular_tail<TS>(tet, t, b, T, Q, pts, counters, irregQ, result);
         return;
     }
     const int cx0 = cell_of(elo[0], g.o[0], g.inv[0], Gx), cx1 = cell_of(ehi[0], g.o[0], g.inv[0], Gx);
@@ -1303,7 +1407,7 @@ __global__ __launch_bounds__(256, PIT_WAVES) void k_tet_scan_slab(const float *_
         int k = atomicAdd(&counters[b * 4 + 0], 1);
         irregT[(size_t)b * T + k] = t;
         if (hits) hits[(size_t)b * T + t] = make_int2(-1, kHitOverflow);
-        irregular_tail(tet, t, b, T, Q, pts, counters, irregQ, result);
+        irregular_tail<TS>(tet, t, b, T, Q, pts, counters, irregQ, result);
         return;
     }
     const int Gp = table_pitch(G);
@@ -1443,16 +1547,16 @@ __global__ __launch_bounds__(256, PIT_WAVES) void k_tet_scan_slab(const float *_
     }
     PHASE_MARK(1);                                                       // [1] traversal loop
     if (npend > 0) {                                                      // undecided candidates (rare)
-        const float *tv = tet + ((size_t)b * T + t) * 12;
+        const typename TS::Ref tv = ts.at(b, T, t);
         atomicAdd(&counters[gridDim.y * 4 + b * 4 + 1], npend);              // statistics: candidates decided exactly
         if (npend > 2) {
-            exact_rescan(tv, t, tb, sq, result + (size_t)b * Q, G, Gx, cx0, cx1, cy0, cy1, cz0, cz1, m, counters, gridDim.y, b, hits, spill, (size_t)b * T + t);
-            irregular_tail(tet, t, b, T, Q, pts, counters, irregQ, result);
+            exact_rescan<TS>(tv, t, tb, sq, result + (size_t)b * Q, G, Gx, cx0, cx1, cy0, cy1, cz0, cz1, m, counters, gridDim.y, b, hits, spill, (size_t)b * T + t);
+            irregular_tail<TS>(tet, t, b, T, Q, pts, counters, irregQ, result);
             return;
         }
         for (int k = 0; k < npend; ++k) {
             const float4 q = sq[k == 0 ? pend0 : pend1];
-            if (exact_accept(tv, q.x, q.y, q.z) > 0.f) {
+            if (exact_accept<TS>(tv, q.x, q.y, q.z) > 0.f) {
                 const int qi = __float_as_int(q.w);
                 atomicMin(&result[(size_t)b * Q + qi], t);
                 if (hcnt >= cap) {                                           // (the held ones are not published yet)
@@ -1491,7 +1595,7 @@ __global__ __launch_bounds__(256, PIT_WAVES) void k_tet_scan_slab(const float *_
             store_b64_off(uniform_ptr(hits + (size_t)b * T), (unsigned)t * 8u, -1, kHitOverflow);
         }
     }
-    irregular_tail(tet, t, b, T, Q, pts, counters, irregQ, result);
+    irregular_tail<TS>(tet, t, b, T, Q, pts, counters, irregQ, result);
     PHASE_MARK(2);                                                       // [2] publish (atomics, record store) / re-scan
 }
 
@@ -1661,13 +1765,14 @@ __device__ __forceinline__ void cross_fma(float ax, float ay, float az, float bx
 }
 
 // irregular tet (flat / needle / non-finite / huge): listed for k_finalize, its hits are not recorded
-__device__ __noinline__ void irregular_tet_slow(const float *__restrict__ tet, int t, int b, int T, int Q, const float *__restrict__ pts,
+template <class TS>
+__device__ __noinline__ void irregular_tet_slow(typename TS::Arg tet, int t, int b, int T, int Q, const float *__restrict__ pts,
                                                 int *counters, int *irregT, const int *__restrict__ irregQ, int *result, int2 *hits)
 {
     const int k = atomicAdd(&counters[b * 4 + 0], 1);
     irregT[(size_t)b * T + k] = t;
     if (hits) hits[(size_t)b * T + t] = make_int2(-1, kHitOverflow);
-    if (counters[b * 4 + 1] > 0) irregular_tail_slow(tet, t, b, T, Q, pts, counters, irregQ, result);
+    if (counters[b * 4 + 1] > 0) irregular_tail_slow<TS>(tet, t, b, T, Q, pts, counters, irregQ, result);
 }
 
 // The cell box of a regular tet, from its vertices: the same operations, in the same order, as the setup of
@@ -1691,12 +1796,12 @@ __device__ __forceinline__ void tet_cell_box(const float *__restrict__ tv, const
 
 // exact re-scan of one tet (more than two undecided candidates, or more acceptances than slots: practically never): every
 // accepted query is published and the lane's LDS slots are refilled from scratch; returns the number of accepted queries
-__device__ __noinline__ int exact_rescan_slots(const float *__restrict__ tv, int t, const int *__restrict__ tb, const float4 *__restrict__ sq,
+template <class TS>
+__device__ __noinline__ int exact_rescan_slots(typename TS::RefArg tv, int t, const int *__restrict__ tb, const float4 *__restrict__ sq,
                                                int *res, const float *__restrict__ gp, int G, int Gx, int *slotCol)
 {
     float vv[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) vv[k] = tv[k];
+    TS::get(tv, vv);
     Planes P;
     make_planes(vv, P);
     const Grid g = load_grid(gp);
@@ -1763,8 +1868,8 @@ __device__ __forceinline__ float4 bary_weights(const float4 t0, const float4 t1,
 // the lane's footprint is the union of its two cell boxes, every staged candidate is tested against both filters (one LDS
 // read, 2 x 6 packed FMAs), each tet has its own slots, record and publish.  A tet of the pair that has nothing to traverse
 // (irregular, outside the query box, past the end of the list) gets a filter that rejects everything.
-template <bool ORD, int NT>                                             // ORD: see k_tet_scan_slab
-__device__ __forceinline__ void tet_scan_wave_body(const float *__restrict__ tet, int T, int Q,
+template <class TS, bool ORD, int NT>                                  // ORD: see k_tet_scan_slab
+__device__ __forceinline__ void tet_scan_wave_body(typename TS::Arg tet, int T, int Q,
                                                   const float *__restrict__ gparam, int G, int Gx, const int *__restrict__ table,
                                                   long long cellStride, const float4 *__restrict__ sortedQ, int *result, int *counters,
                                                   int *irregT, int2 *hits, const float *__restrict__ pts,
@@ -1791,6 +1896,7 @@ __device__ __forceinline__ void tet_scan_wave_body(const float *__restrict__ tet
         ucount[2 * hpad + PIT_BLK_B] = 0;                              // per lane = 16 MB of HBM writes per launch; so: 76, none)
     }
     const int b = PIT_BLK_B, tid = threadIdx.x, lane = tid & 63;
+    const TS ts(tet);
     Stage &W = s_w[tid >> 6];
     const int nblk = gridDim.x;
 #if PIT_PIN_SHAPES
@@ -1825,13 +1931,7 @@ __device__ __forceinline__ void tet_scan_wave_body(const float *__restrict__ tet
 #pragma unroll
     for (int k = 0; k < NT; ++k) {
         float v[12];
-        {
-            const float4 *src = reinterpret_cast<const float4 *>(tet + ((size_t)b * T + tet_id(k)) * 12);
-            float4 a = load_f4<PIT_SCAN_TET_NT != 0>(src), bq = load_f4<PIT_SCAN_TET_NT != 0>(src + 1), c = load_f4<PIT_SCAN_TET_NT != 0>(src + 2);
-            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
-            v[4] = bq.x; v[5] = bq.y; v[6] = bq.z; v[7] = bq.w;
-            v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w;
-        }
+        TS::template get4<PIT_SCAN_TET_NT != 0>(ts.at(b, T, tet_id(k)), v);
         float mN[4][3], det;
         {
             const float e1x = v[3] - v[0], e1y = v[4] - v[1], e1z = v[5] - v[2];
@@ -2195,9 +2295,7 @@ __device__ __forceinline__ void tet_scan_wave_body(const float *__restrict__ tet
             for (int k = 0; k < NT; ++k) {
                 if (NT > 1 && !works[k]) continue;
                 float tv[12], mrg2;
-                const float *src = tet + ((size_t)b * T + tet_id(k)) * 12;
-#pragma unroll
-                for (int j = 0; j < 12; ++j) tv[j] = src[j];
+                TS::get(ts.at(b, T, tet_id(k)), tv);
                 CellBox c1;
                 tet_cell_box(tv, g, G, Gx, c1, mrg2);
                 cb.cx0 = min(cb.cx0, c1.cx0); cb.cx1 = max(cb.cx1, c1.cx1); cb.cy0 = min(cb.cy0, c1.cy0); cb.cy1 = max(cb.cy1, c1.cy1);
@@ -2255,7 +2353,7 @@ __device__ __forceinline__ void tet_scan_wave_body(const float *__restrict__ tet
             for (int k = 0; k < NT; ++k)
                 if (works[k]) {
                     const int te = tet_id(k);
-                    hcnt[k] = exact_rescan_slots(tet + ((size_t)b * T + te) * 12, te, tb, sq, result + (size_t)b * Q, gparam + b * kGridWords, G, Gx,
+                    hcnt[k] = exact_rescan_slots<TS>(ts.at(b, T, te), te, tb, sq, result + (size_t)b * Q, gparam + b * kGridWords, G, Gx,
                                                  &s_hit[k][0][tid]);
                 }
         } else {
@@ -2264,7 +2362,7 @@ __device__ __forceinline__ void tet_scan_wave_body(const float *__restrict__ tet
                 const int k = NT == 1 ? 0 : (pq >> 30) & 1, qi = pq & 0x3FFFFFFF;
                 const int te = tet_id(k);
                 const float *pp = pts + ((size_t)b * Q + qi) * 3;
-                if (exact_accept(tet + ((size_t)b * T + te) * 12, pp[0], pp[1], pp[2]) > 0.f) {
+                if (exact_accept<TS>(ts.at(b, T, te), pp[0], pp[1], pp[2]) > 0.f) {
                     atomicMin(&result[(size_t)b * Q + qi], te);
                     if (NT == 1 || k == 0) { s_hit[0][min(hcnt[0], kWvSlots)][tid] = qi; ++hcnt[0]; }
                     else { s_hit[NT - 1][min(hcnt[NT - 1], kWvSlots)][tid] = qi; ++hcnt[NT - 1]; }
@@ -2280,13 +2378,13 @@ __device__ __forceinline__ void tet_scan_wave_body(const float *__restrict__ tet
         int te = tet_id(k);
         asm volatile("" : "+v"(te));
         if (!regular[k]) {                                               // (out-of-line call placed where almost nothing is live)
-            irregular_tet_slow(tet, te, b, T, Q, pts, counters, irregT, irregQ, result, hits);
+            irregular_tet_slow<TS>(tet, te, b, T, Q, pts, counters, irregT, irregQ, result, hits);
             continue;
         }
         int hc = hcnt[k];
         if (hc > kWvSlots) {                                             // more acceptances than slots (dense queries): the out-of-line exact
-            const float *tv = tet + ((size_t)b * T + te) * 12;           // walk publishes every one of them
-            hc = exact_rescan_slots(tv, te, tb, sq, result + (size_t)b * Q, gparam + b * kGridWords, G, Gx, &s_hit[k][0][tid]);
+            const typename TS::Ref tv = ts.at(b, T, te);                 // walk publishes every one of them
+            hc = exact_rescan_slots<TS>(tv, te, tb, sq, result + (size_t)b * Q, gparam + b * kGridWords, G, Gx, &s_hit[k][0][tid]);
         }
 #pragma unroll 1
         for (int i = 0; i < kWvSlots; ++i) {                             // publish: one atomic instruction per slot level in use
@@ -2303,9 +2401,10 @@ __device__ __forceinline__ void tet_scan_wave_body(const float *__restrict__ tet
                 if (PIT_PROBE_SCATTER == 1) atomic_smin_off_nh(resb, (unsigned)qi * 4u, te);
                 else win = atomicMin(&result[iq], te) > te;
                 if (win && PIT_PROBE_SCATTER == 3) {
-                    const float4 *src = reinterpret_cast<const float4 *>(tet + ((size_t)b * T + te) * 12);
+                    float4 s0, s1, s2;
+                    TS::get3(ts.at(b, T, te), s0, s1, s2);
                     const float *pp = pts + iq * 3;
-                    *reinterpret_cast<float4 *>(pb + iq * 16) = bary_weights(src[0], src[1], src[2], pp[0], pp[1], pp[2]);
+                    *reinterpret_cast<float4 *>(pb + iq * 16) = bary_weights(s0, s1, s2, pp[0], pp[1], pp[2]);
                     *reinterpret_cast<float *>(pb + nq * 16 + iq * 4) = (float)te;
                     *reinterpret_cast<float *>(pb + nq * 20 + iq * 4) = (float)qi;
                 } else if (win) {
@@ -2337,26 +2436,26 @@ __device__ __forceinline__ void tet_scan_wave_body(const float *__restrict__ tet
             if (over) note_overflow(counters, gridDim.y, b, te);
             if (!(PIT_PROBE_SKIP & 2)) store_rec(hits + (size_t)b * T + te, over ? make_int2(-1, kHitOverflow) : make_int2(h[0], h[1]));
         }
-        irregular_tail(tet, te, b, T, Q, pts, counters, irregQ, result);
+        irregular_tail<TS>(tet, te, b, T, Q, pts, counters, irregQ, result);
     }
     PHASE_MARK(3);                                                       // [3] exact decisions, records
     SPAN_MARK(1);
 }
 
 #define PIT_SCAN_PARAMS                                                                                                               \
-    const float *__restrict__ tet, int T, int Q, const float *__restrict__ gparam, int G, int Gx, const int *__restrict__ table,      \
+    typename C::TS::Arg tet, int T, int Q, const float *__restrict__ gparam, int G, int Gx, const int *__restrict__ table,      \
         long long cellStride, const float4 *__restrict__ sortedQ, int *result, int *counters, int *irregT, int2 *hits,                \
         const float *__restrict__ pts, const int *__restrict__ irregQ, int *ucount, int hpad, int4 *spill, const int *__restrict__ order
 #define PIT_SCAN_FWD tet, T, Q, gparam, G, Gx, table, cellStride, sortedQ, result, counters, irregT, hits, pts, irregQ, ucount, hpad, spill, order
-template <bool ORD>
+template <class C>
 __global__ __launch_bounds__(kWvThreads, PIT_WAVES2) void k_tet_scan_wave(PIT_SCAN_PARAMS)
 {
-    tet_scan_wave_body<ORD, 1>(PIT_SCAN_FWD);
+    tet_scan_wave_body<typename C::TS, C::flag, 1>(PIT_SCAN_FWD);
 }
-template <bool ORD>
+template <class C>
 __global__ __launch_bounds__(kWvThreads, PIT_WAVES_PAIR) void k_tet_scan_pair(PIT_SCAN_PARAMS)
 {
-    tet_scan_wave_body<ORD, 2>(PIT_SCAN_FWD);
+    tet_scan_wave_body<typename C::TS, C::flag, 2>(PIT_SCAN_FWD);
 }
 #undef PIT_SCAN_PARAMS
 #undef PIT_SCAN_FWD
@@ -2370,8 +2469,8 @@ __global__ __launch_bounds__(kWvThreads, PIT_WAVES_PAIR) void k_tet_scan_pair(PI
 #ifndef PIT_FIN_QPT
 #define PIT_FIN_QPT 1
 #endif
-template <int QPT>
-__global__ __launch_bounds__(256) void k_finalize(const float *__restrict__ tet, const float *__restrict__ pts, int T,
+template <class TS, int QPT = PIT_FIN_QPT>
+__global__ __launch_bounds__(256) void k_finalize(typename TS::Arg tet, const float *__restrict__ pts, int T,
                                                   int Q, const int *__restrict__ result, float *cond, float *bary,
                                                   const float *__restrict__ pred, float *occ, const int2 *__restrict__ hits,
                                                   int *ucount, int *ulist, const int *__restrict__ counters,
@@ -2380,6 +2479,7 @@ __global__ __launch_bounds__(256) void k_finalize(const float *__restrict__ tet,
     __shared__ int s_cnt[4], s_base;
     const int2 sb = shape_block(pin);                                  // shape-per-XCD placement
     const int b = sb.x;
+    const TS ts(tet);
     int q[QPT], r[QPT];
     bool live[QPT];                                                 // (no early return: the append below has barriers)
     size_t i[QPT];
@@ -2403,9 +2503,7 @@ __global__ __launch_bounds__(256) void k_finalize(const float *__restrict__ tet,
         for (int k = 0; k < nIrregT; ++k) {
             const int t = irregT[(size_t)b * T + k];
             float v[12];
-            const float *src = tet + ((size_t)b * T + t) * 12;
-#pragma unroll
-            for (int jj = 0; jj < 12; ++jj) v[jj] = src[jj];
+            TS::get(ts.at(b, T, t), v);
             Planes P;
             make_planes(v, P);
 #pragma unroll
@@ -2420,8 +2518,8 @@ __global__ __launch_bounds__(256) void k_finalize(const float *__restrict__ tet,
 #pragma unroll
     for (int j = 0; j < QPT; ++j) {
         hit[j] = r[j] != kMiss;
-        const float4 *src = reinterpret_cast<const float4 *>(tet + ((size_t)b * T + (hit[j] ? r[j] : 0)) * 12);
-        if (bary && hit[j]) { t0[j] = src[0]; t1[j] = src[1]; t2[j] = src[2]; }
+        const typename TS::Ref tr = ts.at(b, T, hit[j] ? r[j] : 0);
+        if (bary && hit[j]) TS::get3(tr, t0[j], t1[j], t2[j]);
         pr[j] = (occ && live[j]) ? pred[(size_t)b * T + (hit[j] ? r[j] : 0)] : 0.f;    // paste_occ: misses alias tet 0 (deftet.py:133-135)
     }
 #pragma unroll
@@ -2496,15 +2594,13 @@ __global__ __launch_bounds__(256) void k_finalize(const float *__restrict__ tet,
 // computed once per tet, read through the scalar cache as wave-uniform operands, one
 // query per lane, wave-wide early exit once all 64 lanes have their first hit.
 // ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_prep_records(const float *__restrict__ tet, long long n, float *rec)
+template <class TS>
+__global__ __launch_bounds__(256) void k_prep_records(typename TS::Arg tet, long long n, float *rec, int T)
 {
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float v[12];
-    const float4 *src = reinterpret_cast<const float4 *>(tet + i * 12);
-    float4 a = src[0], bq = src[1], c = src[2];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = bq.x; v[5] = bq.y; v[6] = bq.z; v[7] = bq.w;
-    v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w;
+    TS::get4(TS(tet).at_flat(i, T), v);
     Planes P;
     make_planes(v, P);
     float4 *dst = reinterpret_cast<float4 *>(rec + i * 32);
@@ -2556,7 +2652,8 @@ __device__ __forceinline__ void cross3(const float *a, const float *b, float *o)
     o[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-__global__ __launch_bounds__(256) void k_bary_bwd(const float *__restrict__ tet, const float *__restrict__ pts,
+template <class TS>
+__global__ __launch_bounds__(256) void k_bary_bwd(typename TS::Arg tet, const float *__restrict__ pts,
                                                   const float *__restrict__ cond, const float *__restrict__ grad_w, int T,
                                                   int Q, float *grad_tet, float *grad_pts)
 {
@@ -2569,8 +2666,8 @@ __global__ __launch_bounds__(256) void k_bary_bwd(const float *__restrict__ tet,
     float G3[3] = {0.f, 0.f, 0.f};
     if (hit) {
         const int t = (int)cf;
-        const float4 *src = reinterpret_cast<const float4 *>(tet + ((size_t)b * T + t) * 12);
-        float4 t0 = src[0], t1 = src[1], t2 = src[2];
+        float4 t0, t1, t2;
+        TS::get3(TS(tet).at(b, T, t), t0, t1, t2);
         const float A[3] = {t0.x, t0.y, t0.z}, Bv[3] = {t0.w, t1.x, t1.y}, Cv[3] = {t1.z, t1.w, t2.x}, D[3] = {t2.y, t2.z, t2.w};
         const float *pp = pts + i * 3;
         float vap[3], vbp[3], vab[3], vac[3], vad[3], vbc[3], vbd[3];
@@ -2653,7 +2750,8 @@ __global__ __launch_bounds__(256) void k_hit_link(const float *__restrict__ cond
     }
 }
 
-__global__ __launch_bounds__(256) void k_bary_bwd_gather(const float *__restrict__ tet, const float *__restrict__ pts,
+template <class TS>
+__global__ __launch_bounds__(256) void k_bary_bwd_gather(typename TS::Arg tet, const float *__restrict__ pts,
                                                          const float *__restrict__ grad_w, const int *__restrict__ head,
                                                          const int *__restrict__ next, int T, int Q, float *grad_tet,
                                                          float *grad_pts, int accumulate, const float *__restrict__ gocc,
@@ -2668,8 +2766,8 @@ __global__ __launch_bounds__(256) void k_bary_bwd_gather(const float *__restrict
     int q = head[(size_t)b * T + t];
     float gp = (grad_pred && t == 0) ? missSum[b] : 0.f;             // clamped misses paste from tet 0
     if (q >= 0) {
-        const float4 *src = reinterpret_cast<const float4 *>(tet + ((size_t)b * T + t) * 12);
-        float4 t0 = src[0], t1 = src[1], t2 = src[2];
+        float4 t0, t1, t2;
+        TS::get3(TS(tet).at(b, T, t), t0, t1, t2);
         const float A[3] = {t0.x, t0.y, t0.z}, Bv[3] = {t0.w, t1.x, t1.y}, Cv[3] = {t1.z, t1.w, t2.x}, D[3] = {t2.y, t2.z, t2.w};
         float vab[3], vac[3], vad[3], vbc[3], vbd[3];
 #pragma unroll
@@ -2730,10 +2828,11 @@ struct TetGrad {
     float na[3], nb[3], nc[3], nd[3];
     float v6;
 };
-__device__ __forceinline__ void tet_grad_setup(const float *__restrict__ tet, size_t i, TetGrad &g)
+template <class TS>
+__device__ __forceinline__ void tet_grad_setup(typename TS::Ref r, TetGrad &g)
 {
-    const float4 *src = reinterpret_cast<const float4 *>(tet + i * 12);
-    const float4 t0 = load_f4<PIT_BWD_TET_NT != 0>(src), t1 = load_f4<PIT_BWD_TET_NT != 0>(src + 1), t2 = load_f4<PIT_BWD_TET_NT != 0>(src + 2);
+    float4 t0, t1, t2;
+    TS::template get3<PIT_BWD_TET_NT != 0>(r, t0, t1, t2);
     const float C[3] = {t1.z, t1.w, t2.x}, D[3] = {t2.y, t2.z, t2.w};
     g.A[0] = t0.x; g.A[1] = t0.y; g.A[2] = t0.z; g.Bv[0] = t0.w; g.Bv[1] = t1.x; g.Bv[2] = t1.y;
     float vab[3], vac[3], vad[3], vbc[3], vbd[3];
@@ -2803,7 +2902,8 @@ constexpr int kMissStride = 80;    // floats of workspace per shape: kMissParts 
 // One pass over the list per hit is affordable while (hits of the tet) x (64-entry steps of the list) stays below this; beyond
 // it (thousands of queries inside one tet) the matching lanes evaluate one hit each and a butterfly adds the lanes up
 constexpr long long kRescanOrderedSteps = 16384;
-__device__ __forceinline__ bool bwd_rescan(const float *__restrict__ tet, const float *__restrict__ pts, const float *__restrict__ cond,
+template <class TS>
+__device__ __forceinline__ bool bwd_rescan(typename TS::Arg tet, const float *__restrict__ pts, const float *__restrict__ cond,
                                         const float *__restrict__ grad_w, const float *__restrict__ gocc, float *grad_pts,
                                         bool want_pred, const int *__restrict__ ulist, int b, int T, int Q, int nU,
                                         unsigned long long need, int t, float (*park)[256])
@@ -2839,7 +2939,7 @@ __device__ __forceinline__ bool bwd_rescan(const float *__restrict__ tet, const 
 #pragma unroll
         for (int k = 0; k < 13; ++k) part[k] = 0.f;
         TetGrad g;
-        tet_grad_setup(tet, (size_t)b * T + tL, g);
+        tet_grad_setup<TS>(TS(tet).at(b, T, tL), g);
         // ONE instance of the evaluation for both modes.  ordered: the whole wave evaluates hit `best` (wave-uniform values: every
         // lane holds the same sums), then looks for the next; otherwise: every lane evaluates its own entry of the next 64
         for (int base = 0;;) {
@@ -2891,8 +2991,8 @@ __device__ __forceinline__ bool bwd_rescan(const float *__restrict__ tet, const 
 // only the rows of the tets that accepted something, COMPACTED to the start of its 64-row block in lane order, and one 64-bit
 // word per wave (rowMask[b][t / 64], the ballot of those lanes) tells the reader which tets they belong to: rank = popcount of
 // the mask below the tet's bit.  29 MB of contiguous stores instead of 99 MB, and the reader fetches a third of the lines.
-template <bool SPARSE>
-__global__ __launch_bounds__(256, PIT_BWD_WAVES) void k_bary_bwd_hits(const float *__restrict__ tet, const float *__restrict__ pts,
+template <class C>
+__global__ __launch_bounds__(256, PIT_BWD_WAVES) void k_bary_bwd_hits(typename C::TS::Arg tet, const float *__restrict__ pts,
                                                        const float *__restrict__ cond, const float *__restrict__ grad_w,
                                                        const int2 *__restrict__ hits, int T, int Q, float *grad_tet,
                                                        float *grad_pts, int accumulate, const float *__restrict__ gocc,
@@ -2911,6 +3011,8 @@ __global__ __launch_bounds__(256, PIT_BWD_WAVES) void k_bary_bwd_hits(const floa
     __shared__ __attribute__((aligned(16))) float s_buf[13 * 256];
     float4(*s_rows)[192] = reinterpret_cast<float4(*)[192]>(s_buf);   // [4][192] float4 = 12 KB of the 13 KB
     float(*s_park)[256] = reinterpret_cast<float(*)[256]>(s_buf);     // [13][256] float
+    typedef typename C::TS TS;
+    constexpr bool SPARSE = C::flag;
     const int2 sb = shape_block(pin);                                  // shape-per-XCD placement
     const int b = sb.x, bx = PIT_BWD_REV ? (int)gridDim.x - 1 - sb.y : sb.y, tid = threadIdx.x, lane = tid & 63;
     const bool side = grad_pred && bx < nMissParts;                // block-uniform
@@ -2938,7 +3040,7 @@ __global__ __launch_bounds__(256, PIT_BWD_WAVES) void k_bary_bwd_hits(const floa
     if (nU > 0) {                                                  // wave-uniform (scalar load)
         const bool anyQ = hitWords[2 * pad + b] != 0;              // entries of irregular queries: their tets' records look complete
         const unsigned long long need = __ballot(live && (h.y == kHitOverflow || anyQ));
-        if (need) parked = bwd_rescan(tet, pts, cond, grad_w, gocc, grad_pts, grad_pred != nullptr, ulist, b, T, Q, nU, need, t, s_park);
+        if (need) parked = bwd_rescan<TS>(tet, pts, cond, grad_w, gocc, grad_pts, grad_pred != nullptr, ulist, b, T, Q, nU, need, t, s_park);
     }
     float acc[12];
 #pragma unroll
@@ -2946,7 +3048,7 @@ __global__ __launch_bounds__(256, PIT_BWD_WAVES) void k_bary_bwd_hits(const floa
     float gp = 0.f;
     if (h.x >= 0 && h.y != kHitOverflow) {                         // slots fill in order: x < 0 means no accepted query
         TetGrad g;
-        tet_grad_setup(tet, (size_t)b * T + t, g);
+        tet_grad_setup<TS>(TS(tet).at(b, T, t), g);
         // the records list the accepted queries in traversal order, which depends on the (arbitrary)
         // order of queries inside a grid cell: sort the ids so that the fp32 sums below are
         // added in the same order on every run (empty slots, -1, go last)
@@ -3274,8 +3376,11 @@ static int pit_prepare(const Layout &L, const float *pts, int B, int Q, hipStrea
     return DEFTET_OK;
 }
 
-// tet side: traversal + finalize; consumes the prepared state (result sentinels, counters)
-static int pit_scan(const Layout &L, const float *tet, const float *pts, float *cond, float *bary, const float *pred, float *occ,
+// tet side: traversal + finalize; consumes the prepared state (result sentinels, counters).  TS: the tet source (DenseTets /
+// IndexedTets); the kernels of both are launched under the same names, "k_tet_scan_wave<WaveP>" etc. (deftet_profile_select
+// ("k_tet_scan_wave") times either: the match stops at '<').
+template <class TS>
+static int pit_scan(const Layout &L, typename TS::Arg tet, const float *pts, float *cond, float *bary, const float *pred, float *occ,
                     int32_t *hit_buf, int B, int T, int Q, int algo, hipStream_t st, const int32_t *order = nullptr)
 {
     const dim3 blk(256);
@@ -3283,7 +3388,7 @@ static int pit_scan(const Layout &L, const float *tet, const float *pts, float *
     int *ucount = hit_buf ? hit_buf + hit_cnt_off(B, T) : nullptr;
     if (T > 0) {
         if (algo == DEFTET_PIT_EXACT) {
-            DEFTET_LAUNCH(k_tet_scan, gt, blk, st, tet, T, Q, L.gparam, L.G, L.Gx, L.table, L.cellStride, L.sortedQ, L.result,
+            DEFTET_LAUNCH(k_tet_scan<TS>, gt, blk, st, tet, T, Q, L.gparam, L.G, L.Gx, L.table, L.cellStride, L.sortedQ, L.result,
                           L.counters, L.irregT, (int2 *)hit_buf, pts, L.irregQ, ucount, hit_pad(B), hit_buf ? (int4 *)(hit_buf + hit_spill_off(B, T, Q)) : (int4 *)nullptr);
         } else {
             int4 *spill = hit_buf ? (int4 *)(hit_buf + hit_spill_off(B, T, Q)) : (int4 *)nullptr;
@@ -3298,28 +3403,30 @@ static int pit_scan(const Layout &L, const float *tet, const float *pts, float *
             const dim3 gp(((((T + 1) / 2 + kWvThreads - 1) / kWvThreads + 7) / 8) * 8, B);       // two tets per lane
 #define PIT_SCAN_ARGS tet, T, Q, L.gparam, L.G, L.Gx, L.table, L.cellStride, L.sortedQ, L.result, L.counters, L.irregT, (int2 *)hit_buf, pts, \
                       L.irregQ, ucount, hit_pad(B), spill, (const int *)order
-            if (slab && order) DEFTET_LAUNCH(k_tet_scan_slab<true>, gt, blk, st, PIT_SCAN_ARGS);
-            else if (slab) DEFTET_LAUNCH(k_tet_scan_slab<false>, gt, blk, st, PIT_SCAN_ARGS);
-            else if (kern == DEFTET_PIT_PAIR && order) DEFTET_LAUNCH(k_tet_scan_pair<true>, gp, bw, st, PIT_SCAN_ARGS);
-            else if (kern == DEFTET_PIT_PAIR) DEFTET_LAUNCH(k_tet_scan_pair<false>, gp, bw, st, PIT_SCAN_ARGS);
-            else if (order) DEFTET_LAUNCH(k_tet_scan_wave<true>, gw, bw, st, PIT_SCAN_ARGS);
-            else DEFTET_LAUNCH(k_tet_scan_wave<false>, gw, bw, st, PIT_SCAN_ARGS);
+            typedef TetCfg<TS, true> Ord;                                                       // walks the tets in `order`
+            typedef TetCfg<TS, false> Plain;
+            if (slab && order) DEFTET_LAUNCH(k_tet_scan_slab<Ord>, gt, blk, st, PIT_SCAN_ARGS);
+            else if (slab) DEFTET_LAUNCH(k_tet_scan_slab<Plain>, gt, blk, st, PIT_SCAN_ARGS);
+            else if (kern == DEFTET_PIT_PAIR && order) DEFTET_LAUNCH(k_tet_scan_pair<Ord>, gp, bw, st, PIT_SCAN_ARGS);
+            else if (kern == DEFTET_PIT_PAIR) DEFTET_LAUNCH(k_tet_scan_pair<Plain>, gp, bw, st, PIT_SCAN_ARGS);
+            else if (order) DEFTET_LAUNCH(k_tet_scan_wave<Ord>, gw, bw, st, PIT_SCAN_ARGS);
+            else DEFTET_LAUNCH(k_tet_scan_wave<Plain>, gw, bw, st, PIT_SCAN_ARGS);
 #undef PIT_SCAN_ARGS
         }
     } else if (ucount) {
         DEFTET_HIP(hipMemsetAsync(ucount, 0, (size_t)3 * hit_pad(B) * 4, st));
     }
-    DEFTET_LAUNCH(k_finalize<PIT_FIN_QPT>, gf, blk, st, tet, pts, T, Q, L.result, cond, bary, pred, occ, (const int2 *)hit_buf, ucount,
+    DEFTET_LAUNCH(k_finalize<TS>, gf, blk, st, tet, pts, T, Q, L.result, cond, bary, pred, occ, (const int2 *)hit_buf, ucount,
                   hit_buf ? hit_buf + hit_list_off(B, T) : nullptr, L.counters, L.irregT, hit_pad(B), pin_shapes(Q), (const float *)L.gparam);
     return DEFTET_OK;
 }
 
-static int pit_forward(const float *tet, const float *pts, float *cond, float *bary, const float *pred, float *occ, int32_t *hit_buf,
-                       int B, int T, int Q, int algo, void *workspace, size_t workspace_bytes, void *stream_, const int32_t *order,
-                       const float *boxIn = nullptr, float *boxOut = nullptr, int32_t *missOut = nullptr)
+// (the caller has checked the arguments: pit_check, or pit_check_indexed)
+template <class TS>
+static int pit_forward_checked(typename TS::Arg tet, const float *pts, float *cond, float *bary, const float *pred, float *occ,
+                               int32_t *hit_buf, int B, int T, int Q, int algo, void *workspace, size_t workspace_bytes, void *stream_,
+                               const int32_t *order, const float *boxIn, float *boxOut, int32_t *missOut)
 {
-    int rc = pit_check(tet, pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo, workspace);
-    if (rc != DEFTET_OK || B == 0 || Q == 0) return rc;
     Layout L = make_layout(B, T, Q, algo, workspace, workspace_bytes);
     DEFTET_CHECK_ARG(L.bytes <= workspace_bytes, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
     hipStream_t st = as_stream(stream_);
@@ -3327,16 +3434,25 @@ static int pit_forward(const float *tet, const float *pts, float *cond, float *b
         const dim3 blk(256), gq((Q + 255) / 256, B);
         if (T > 0) {
             long long n = (long long)B * T;
-            DEFTET_LAUNCH(k_prep_records, dim3((unsigned)((n + 255) / 256)), blk, st, tet, n, L.rec);
+            DEFTET_LAUNCH(k_prep_records<TS>, dim3((unsigned)((n + 255) / 256)), blk, st, tet, n, L.rec, T);
         }
         DEFTET_LAUNCH(k_brute, gq, blk, st, L.rec, pts, T, Q, L.result);
-        DEFTET_LAUNCH(k_finalize<PIT_FIN_QPT>, dim3((Q + 256 * PIT_FIN_QPT - 1) / (256 * PIT_FIN_QPT), B), blk, st, tet, pts, T, Q, L.result, cond, bary, pred, occ, (const int2 *)nullptr, (int *)nullptr,
+        DEFTET_LAUNCH(k_finalize<TS>, dim3((Q + 256 * PIT_FIN_QPT - 1) / (256 * PIT_FIN_QPT), B), blk, st, tet, pts, T, Q, L.result, cond, bary, pred, occ, (const int2 *)nullptr, (int *)nullptr,
                       (int *)nullptr, (const int *)nullptr, L.irregT, 0, pin_shapes(Q), (const float *)nullptr);
         return DEFTET_OK;
     }
-    rc = pit_prepare(L, pts, B, Q, st, boxIn, boxOut, missOut);
+    const int rc = pit_prepare(L, pts, B, Q, st, boxIn, boxOut, missOut);
     if (rc != DEFTET_OK) return rc;
-    return pit_scan(L, tet, pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo, st, order);
+    return pit_scan<TS>(L, tet, pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo, st, order);
+}
+static int pit_forward(const float *tet, const float *pts, float *cond, float *bary, const float *pred, float *occ, int32_t *hit_buf,
+                       int B, int T, int Q, int algo, void *workspace, size_t workspace_bytes, void *stream_, const int32_t *order,
+                       const float *boxIn = nullptr, float *boxOut = nullptr, int32_t *missOut = nullptr)
+{
+    int rc = pit_check(tet, pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo, workspace);
+    if (rc != DEFTET_OK || B == 0 || Q == 0) return rc;
+    return pit_forward_checked<DenseTets>(tet, pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo, workspace, workspace_bytes, stream_, order,
+                                          boxIn, boxOut, missOut);
 }
 
 extern "C" int deftet_point_in_tet_f32(const float *tet, const float *pts, float *cond, float *bary, const float *pred,
@@ -3409,7 +3525,7 @@ static int pit_scan_entry(const float *tet, const float *pts, float *cond, float
     if (rc != DEFTET_OK || B == 0 || Q == 0) return rc;
     Layout L = make_layout(B, T, Q, algo, workspace, workspace_bytes);
     DEFTET_CHECK_ARG(L.bytes <= workspace_bytes, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
-    return pit_scan(L, tet, pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo, as_stream(stream_), order);
+    return pit_scan<DenseTets>(L, tet, pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo, as_stream(stream_), order);
 }
 
 extern "C" int deftet_point_in_tet_scan_f32(const float *tet, const float *pts, float *cond, float *bary, const float *pred,
@@ -3453,11 +3569,11 @@ extern "C" int deftet_point_in_tet_read_stats(const void *workspace, size_t work
 extern "C" int deftet_debug_occupancy(int *out8)
 {
     int n = 0;
-    DEFTET_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)deftet::pit::k_tet_scan_wave<false>, 256, 0)); out8[0] = n;
-    DEFTET_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)deftet::pit::k_tet_scan_pair<false>, 256, 0)); out8[1] = n;
-    DEFTET_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)deftet::pit::k_tet_scan_slab<false>, 256, 0)); out8[2] = n;
+    DEFTET_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)deftet::pit::k_tet_scan_wave<deftet::pit::TetCfg<deftet::pit::DenseTets, false>>, 256, 0)); out8[0] = n;
+    DEFTET_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)deftet::pit::k_tet_scan_pair<deftet::pit::TetCfg<deftet::pit::DenseTets, false>>, 256, 0)); out8[1] = n;
+    DEFTET_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void *)deftet::pit::k_tet_scan_slab<deftet::pit::TetCfg<deftet::pit::DenseTets, false>>, 256, 0)); out8[2] = n;
     hipFuncAttributes a;
-    DEFTET_HIP(hipFuncGetAttributes(&a, (const void *)deftet::pit::k_tet_scan_wave<false>));
+    DEFTET_HIP(hipFuncGetAttributes(&a, (const void *)deftet::pit::k_tet_scan_wave<deftet::pit::TetCfg<deftet::pit::DenseTets, false>>));
     out8[3] = (int)a.sharedSizeBytes; out8[4] = a.numRegs; out8[5] = (int)a.maxDynamicSharedSizeBytes;
     hipDeviceProp_t pr;
     DEFTET_HIP(hipGetDeviceProperties(&pr, 0));
@@ -3503,10 +3619,15 @@ extern "C" size_t deftet_point_in_tet_bwd_workspace_bytes(int B, int T, int Q)
     return lists > miss ? lists : miss;
 }
 
-extern "C" int deftet_point_in_tet_bwd_f32(const float *tet, const float *pts, const float *cond, const float *grad_w,
-                                           float *grad_tet, float *grad_pts, const float *grad_occ, float *grad_pred,
-                                           const int32_t *hit_buf, int B, int T, int Q, int accumulate, void *workspace,
-                                           size_t workspace_bytes, void *stream_)
+static bool tets_null(const float *tet) { return tet == nullptr; }
+static bool tets_null(const IndexedTets &s) { return s.pos == nullptr || s.idx == nullptr; }
+static bool tets_misaligned(const float *tet) { return ((uintptr_t)tet & 15) != 0; }
+static bool tets_misaligned(const IndexedTets &s) { return ((uintptr_t)s.idx & 15) != 0 || ((uintptr_t)s.pos & 3) != 0; }
+
+template <class TS>
+static int pit_bwd(typename TS::Arg tet, const float *pts, const float *cond, const float *grad_w, float *grad_tet, float *grad_pts,
+                   const float *grad_occ, float *grad_pred, const int32_t *hit_buf, int B, int T, int Q, int accumulate, void *workspace,
+                   size_t workspace_bytes, void *stream_)
 {
     DEFTET_CHECK_ARG(B >= 0 && T >= 0 && Q >= 0, "negative size");
     DEFTET_CHECK_ARG(B <= 65535, "n_batch=%d exceeds 65535", B);
@@ -3523,8 +3644,8 @@ extern "C" int deftet_point_in_tet_bwd_f32(const float *tet, const float *pts, c
         }
         return DEFTET_OK;
     }
-    DEFTET_CHECK_ARG(tet && pts && cond && grad_w, "null pointer");
-    DEFTET_CHECK_ARG(((uintptr_t)tet & 15) == 0 && ((uintptr_t)grad_w & 15) == 0, "tet/grad_w must be 16-byte aligned");
+    DEFTET_CHECK_ARG(!tets_null(tet) && pts && cond && grad_w, "null pointer");
+    DEFTET_CHECK_ARG(!tets_misaligned(tet) && ((uintptr_t)grad_w & 15) == 0, "tet/grad_w must be 16-byte aligned");
     // More than kDenseQueriesPerTet queries per tet: more and more tets accept more queries than a record and its spill record
     // hold (six to eight), every one of them scans the shape's list of unrecorded hits, and that is quadratic — 111 ms against
     // 0.055 ms for the per-tet lists at 100,000 queries on 6,000 tets; the crossover is measured (tools/probes/
@@ -3543,7 +3664,8 @@ extern "C" int deftet_point_in_tet_bwd_f32(const float *tet, const float *pts, c
         }
         const int tblocks = (T + 255) / 256, nMissParts = tblocks < kMissParts ? tblocks : kMissParts;
         int32_t *words = const_cast<int32_t *>(hit_buf) + hit_cnt_off(B, T);    // counters / ticket / flag: the buffer is this library's own
-        DEFTET_LAUNCH(k_bary_bwd_hits<false>, dim3(tblocks, B), dim3(256), st, tet, pts, cond, grad_w, (const int2 *)hit_buf, T, Q,
+        typedef TetCfg<TS, false> Dense;                             // (grad_tet: every row written)
+        DEFTET_LAUNCH(k_bary_bwd_hits<Dense>, dim3(tblocks, B), dim3(256), st, tet, pts, cond, grad_w, (const int2 *)hit_buf, T, Q,
                       grad_tet, grad_pts, accumulate, grad_occ, grad_pred, missPart, nMissParts, words,
                       (const int *)(hit_buf + hit_list_off(B, T)), hit_pad(B), (const int4 *)(hit_buf + hit_spill_off(B, T, Q)), pin_shapes(Q),
                       (unsigned long long *)nullptr);
@@ -3559,12 +3681,12 @@ extern "C" int deftet_point_in_tet_bwd_f32(const float *tet, const float *pts, c
         if (grad_pred) DEFTET_HIP(hipMemsetAsync(missSum, 0, (size_t)B * 4, st));
         DEFTET_LAUNCH(k_hit_link, dim3((Q + 256 * kLinkPer - 1) / (256 * kLinkPer), B), dim3(256), st, cond, T, Q, head, next,
                       grad_occ, missSum);
-        DEFTET_LAUNCH(k_bary_bwd_gather, dim3((T + 255) / 256, B), dim3(256), st, tet, pts, grad_w, head, next, T, Q,
+        DEFTET_LAUNCH(k_bary_bwd_gather<TS>, dim3((T + 255) / 256, B), dim3(256), st, tet, pts, grad_w, head, next, T, Q,
                       grad_tet, grad_pts, accumulate, grad_occ, missSum, grad_pred);
     } else {
         // no workspace: atomic scatter (slow on this chip; kept for callers that cannot provide one)
         if (!accumulate) DEFTET_HIP(hipMemsetAsync(grad_tet, 0, (size_t)B * T * 48, st));
-        DEFTET_LAUNCH(k_bary_bwd, dim3((Q + 255) / 256, B), dim3(256), st, tet, pts, cond, grad_w, T, Q, grad_tet,
+        DEFTET_LAUNCH(k_bary_bwd<TS>, dim3((Q + 255) / 256, B), dim3(256), st, tet, pts, cond, grad_w, T, Q, grad_tet,
                       grad_pts);
         if (grad_pred) {
             if (!accumulate) DEFTET_HIP(hipMemsetAsync(grad_pred, 0, (size_t)B * T * 4, st));
@@ -3572,6 +3694,14 @@ extern "C" int deftet_point_in_tet_bwd_f32(const float *tet, const float *pts, c
         }
     }
     return DEFTET_OK;
+}
+extern "C" int deftet_point_in_tet_bwd_f32(const float *tet, const float *pts, const float *cond, const float *grad_w,
+                                           float *grad_tet, float *grad_pts, const float *grad_occ, float *grad_pred,
+                                           const int32_t *hit_buf, int B, int T, int Q, int accumulate, void *workspace,
+                                           size_t workspace_bytes, void *stream_)
+{
+    return pit_bwd<DenseTets>(tet, pts, cond, grad_w, grad_tet, grad_pts, grad_occ, grad_pred, hit_buf, B, T, Q, accumulate, workspace,
+                              workspace_bytes, stream_);
 }
 
 // A1b backward fused with the backward of the vertex -> tet gather (N2): dL/dpos [B,V,3] without the dense dL/dtet.
@@ -3588,11 +3718,11 @@ extern "C" size_t deftet_point_in_tet_bwd_to_vertices_workspace_bytes(int B, int
            align_up(deftet_point_in_tet_bwd_workspace_bytes(B, T, Q), 256);
 }
 
-extern "C" int deftet_point_in_tet_bwd_to_vertices_f32(const float *tet, const float *pts, const float *cond, const float *grad_w,
-                                                       const float *grad_occ, const int32_t *hit_buf, const int32_t *csr_offsets,
-                                                       const int32_t *csr_slots, int idx_batch, float *grad_pos, float *grad_pts,
-                                                       float *grad_pred, int B, int V, int T, int Q, int accumulate, void *workspace,
-                                                       size_t workspace_bytes, void *stream_)
+template <class TS>
+static int pit_bwd_to_vertices(typename TS::Arg tet, const float *pts, const float *cond, const float *grad_w, const float *grad_occ,
+                               const int32_t *hit_buf, const int32_t *csr_offsets, const int32_t *csr_slots, int idx_batch,
+                               float *grad_pos, float *grad_pts, float *grad_pred, int B, int V, int T, int Q, int accumulate,
+                               void *workspace, size_t workspace_bytes, void *stream_)
 {
     DEFTET_CHECK_ARG(B >= 0 && V >= 0 && T >= 0 && Q >= 0, "negative size");
     DEFTET_CHECK_ARG(B <= 65535, "n_batch=%d exceeds 65535", B);
@@ -3609,8 +3739,8 @@ extern "C" int deftet_point_in_tet_bwd_to_vertices_f32(const float *tet, const f
         }
         return DEFTET_OK;
     }
-    DEFTET_CHECK_ARG(tet && pts && cond && grad_w && csr_offsets && csr_slots, "null pointer");
-    DEFTET_CHECK_ARG(((uintptr_t)tet & 15) == 0 && ((uintptr_t)grad_w & 15) == 0, "tet/grad_w must be 16-byte aligned");
+    DEFTET_CHECK_ARG(!tets_null(tet) && pts && cond && grad_w && csr_offsets && csr_slots, "null pointer");
+    DEFTET_CHECK_ARG(!tets_misaligned(tet) && ((uintptr_t)grad_w & 15) == 0, "tet/grad_w must be 16-byte aligned");
     const size_t need = deftet_point_in_tet_bwd_to_vertices_workspace_bytes(B, T, Q);
     DEFTET_CHECK_ARG(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 255) == 0,
                      "workspace null, misaligned or too small (%zu < %zu)", workspace_bytes, need);
@@ -3625,7 +3755,8 @@ extern "C" int deftet_point_in_tet_bwd_to_vertices_f32(const float *tet, const f
         if (grad_pts) DEFTET_HIP(hipMemsetAsync(grad_pts, 0, (size_t)B * Q * 12, st));
         const int tblocks = (T + 255) / 256, nMissParts = tblocks < kMissParts ? tblocks : kMissParts;
         int32_t *words = const_cast<int32_t *>(hit_buf) + hit_cnt_off(B, T);
-        DEFTET_LAUNCH(k_bary_bwd_hits<true>, dim3(tblocks, B), dim3(256), st, tet, pts, cond, grad_w, (const int2 *)hit_buf, T, Q,
+        typedef TetCfg<TS, true> Sparse;                             // (rows: compacted per wave + mask words)
+        DEFTET_LAUNCH(k_bary_bwd_hits<Sparse>, dim3(tblocks, B), dim3(256), st, tet, pts, cond, grad_w, (const int2 *)hit_buf, T, Q,
                       rows, grad_pts, accumulate, grad_occ, grad_pred, static_cast<float *>(inner), nMissParts, words,
                       (const int *)(hit_buf + hit_list_off(B, T)), hit_pad(B), (const int4 *)(hit_buf + hit_spill_off(B, T, Q)), pin_shapes(Q),
                       rowMask);
@@ -3634,10 +3765,103 @@ extern "C" int deftet_point_in_tet_bwd_to_vertices_f32(const float *tet, const f
     // no records (the forward was asked for none), or the dense case where the records are not the fast path: the per-tet lists
     // into dense rows, then the dense gather
     if (accumulate) DEFTET_HIP(hipMemsetAsync(rows, 0, (size_t)B * T * 48, st));     // (the inner call's `accumulate` covers grad_pred too)
-    const int rc = deftet_point_in_tet_bwd_f32(tet, pts, cond, grad_w, rows, grad_pts, grad_occ, grad_pred, hit_buf, B, T, Q, accumulate, inner,
-                                               innerBytes, stream_);
+    const int rc = pit_bwd<TS>(tet, pts, cond, grad_w, rows, grad_pts, grad_occ, grad_pred, hit_buf, B, T, Q, accumulate, inner,
+                               innerBytes, stream_);
     if (rc != DEFTET_OK) return rc;
     return vtx::gather_bwd_rows(rows, nullptr, csr_offsets, csr_slots, grad_pos, B, V, T, idx_batch, accumulate, st);
+}
+extern "C" int deftet_point_in_tet_bwd_to_vertices_f32(const float *tet, const float *pts, const float *cond, const float *grad_w,
+                                                       const float *grad_occ, const int32_t *hit_buf, const int32_t *csr_offsets,
+                                                       const int32_t *csr_slots, int idx_batch, float *grad_pos, float *grad_pts,
+                                                       float *grad_pred, int B, int V, int T, int Q, int accumulate, void *workspace,
+                                                       size_t workspace_bytes, void *stream_)
+{
+    return pit_bwd_to_vertices<DenseTets>(tet, pts, cond, grad_w, grad_occ, hit_buf, csr_offsets, csr_slots, idx_batch, grad_pos, grad_pts,
+                                          grad_pred, B, V, T, Q, accumulate, workspace, workspace_bytes, stream_);
+}
+
+// ------------------------------------------------------------------------------------
+// Indexed input (version 230): the same operator straight from vertices [B,V,3] and an index list [idx_batch,T,4] — corner c
+// of tet t of shape b is pos[b, idx[ib, t, c]], ib = 0 when idx_batch == 1, else b.  Every output, hit records included, is
+// the one the dense entry points give on the tensor deftet_tet_gather_fwd_f32 makes from the same inputs (the kernels are the
+// dense ones with the IndexedTets source; see the top of the kernels section).  An index outside [0, V) reads as a NaN corner,
+// as in that gather, and sets *bad_flag (device int32, may be NULL) to 1.
+// ------------------------------------------------------------------------------------
+static int pit_check_indexed(const float *pos, const int32_t *tet_idx, int idx_batch, int B, int V, int T)
+{
+    DEFTET_CHECK_ARG(B >= 0 && V >= 0 && T >= 0, "negative size (B=%d V=%d T=%d)", B, V, T);
+    DEFTET_CHECK_ARG(idx_batch == 1 || idx_batch == B, "idx_batch must be 1 or n_batch (got %d, n_batch %d)", idx_batch, B);
+    DEFTET_CHECK_ARG(((uintptr_t)tet_idx & 15) == 0, "tet_idx must be 16-byte aligned");
+    DEFTET_CHECK_ARG(((uintptr_t)pos & 3) == 0, "pos must be 4-byte aligned");
+    if ((long long)V * 3 >= (1ll << 31)) return set_error(DEFTET_ELIMIT, "n_vertex=%d: vertex offsets exceed 2^31", V);
+    if (B > 0 && T > 0) DEFTET_CHECK_ARG(tet_idx && (pos || V == 0), "null pos/tet_idx pointer");
+    return DEFTET_OK;
+}
+static IndexedTets make_indexed(const float *pos, const int32_t *tet_idx, int idx_batch, int V, int T)
+{
+    IndexedTets s;
+    s.pos = pos;
+    s.idx = tet_idx;
+    s.idxStride = idx_batch == 1 ? 0 : (long long)T * 4;
+    s.V = V;
+    return s;
+}
+static int flag_bad_indices(const int32_t *tet_idx, int idx_batch, int V, int T, int32_t *bad_flag, hipStream_t st)
+{
+    const long long n = (long long)idx_batch * T;
+    if (!bad_flag || n == 0) return DEFTET_OK;
+    DEFTET_LAUNCH(k_idx_check, dim3((unsigned)((n + 255) / 256)), dim3(256), st, reinterpret_cast<const int4 *>(tet_idx), n, (unsigned)V, bad_flag);
+    return DEFTET_OK;
+}
+
+extern "C" int deftet_point_in_tet_indexed_f32(const float *pos, const int32_t *tet_idx, int idx_batch, const float *pts, float *cond,
+                                               float *bary, const float *pred, float *occ, int32_t *hit_buf, int B, int V, int T, int Q,
+                                               int algo, const int32_t *tet_order, const float *query_box_in, float *query_box_out,
+                                               int32_t *query_box_misses, int32_t *bad_flag, void *workspace, size_t workspace_bytes,
+                                               void *stream_)
+{
+    int rc = pit_check_indexed(pos, tet_idx, idx_batch, B, V, T);
+    if (rc != DEFTET_OK) return rc;
+    DEFTET_CHECK_ARG(!query_box_in || query_box_in != query_box_out, "query_box_in and query_box_out must not alias");
+    // (pit_check's tet tests see the aligned index list)
+    rc = pit_check(reinterpret_cast<const float *>(tet_idx), pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo, workspace);
+    if (rc != DEFTET_OK || B == 0) return rc;
+    rc = flag_bad_indices(tet_idx, idx_batch, V, T, bad_flag, as_stream(stream_));
+    if (rc != DEFTET_OK || Q == 0) return rc;
+    return pit_forward_checked<IndexedTets>(make_indexed(pos, tet_idx, idx_batch, V, T), pts, cond, bary, pred, occ, hit_buf, B, T,
+                                            Q, algo, workspace, workspace_bytes, stream_, tet_order, query_box_in, query_box_out,
+                                            query_box_misses);
+}
+
+extern "C" int deftet_point_in_tet_indexed_scan_f32(const float *pos, const int32_t *tet_idx, int idx_batch, const float *pts, float *cond,
+                                                    float *bary, const float *pred, float *occ, int32_t *hit_buf, int B, int V, int T,
+                                                    int Q, int algo, const int32_t *tet_order, int32_t *bad_flag, void *workspace,
+                                                    size_t workspace_bytes, void *stream_)
+{
+    int rc = pit_check_indexed(pos, tet_idx, idx_batch, B, V, T);
+    if (rc != DEFTET_OK) return rc;
+    DEFTET_CHECK_ARG(algo != DEFTET_PIT_BRUTE, "scan needs a binned algo");
+    rc = pit_check(reinterpret_cast<const float *>(tet_idx), pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo, workspace);
+    if (rc != DEFTET_OK || B == 0) return rc;
+    rc = flag_bad_indices(tet_idx, idx_batch, V, T, bad_flag, as_stream(stream_));
+    if (rc != DEFTET_OK || Q == 0) return rc;
+    Layout L = make_layout(B, T, Q, algo, workspace, workspace_bytes);
+    DEFTET_CHECK_ARG(L.bytes <= workspace_bytes, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
+    return pit_scan<IndexedTets>(L, make_indexed(pos, tet_idx, idx_batch, V, T), pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo,
+                                 as_stream(stream_), tet_order);
+}
+
+extern "C" int deftet_point_in_tet_indexed_bwd_to_vertices_f32(const float *pos, const int32_t *tet_idx, int idx_batch, const float *pts,
+                                                               const float *cond, const float *grad_w, const float *grad_occ,
+                                                               const int32_t *hit_buf, const int32_t *csr_offsets, const int32_t *csr_slots,
+                                                               float *grad_pos, float *grad_pts, float *grad_pred, int B, int V, int T, int Q,
+                                                               int accumulate, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    const int rc = pit_check_indexed(pos, tet_idx, idx_batch, B, V, T);
+    if (rc != DEFTET_OK) return rc;
+    return pit_bwd_to_vertices<IndexedTets>(make_indexed(pos, tet_idx, idx_batch, V, T), pts, cond, grad_w, grad_occ, hit_buf,
+                                            csr_offsets, csr_slots, idx_batch, grad_pos, grad_pts, grad_pred, B, V, T, Q, accumulate, workspace,
+                                            workspace_bytes, stream_);
 }
 
 extern "C" int deftet_paste_occ_fwd_f32(const float *pred, float *cond, float *out, int B, int T, int Q,

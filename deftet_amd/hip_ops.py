@@ -449,6 +449,114 @@ def point_in_tet(tet_bxtx4x3, pts_bxqx3, want_bary=False, algo=PIT_AUTO, pred_bx
     return out if len(out) > 1 else cond
 
 
+def _idx32(tet_idx):
+    """int32 [Bi,T,4] contiguous copy of an index list ([T,4] or [Bi,T,4]); a TetTopology hands in its own (built once)."""
+    idx = tet_idx if tet_idx.dim() == 3 else tet_idx[None]
+    if idx.dtype != torch.int32:
+        if idx.numel() and (int(idx.min()) < -(1 << 31) or int(idx.max()) >= (1 << 31)):
+            raise RuntimeError("tet_idx: index does not fit int32")
+        idx = idx.to(torch.int32)
+    return idx.contiguous()
+
+
+def _indexed_inputs(pos_bxvx3, tet_idx, pts_bxqx3, topology):
+    _lib.require_gpu(pos_bxvx3, tet_idx, pts_bxqx3)
+    pos, pts = _f32c(pos_bxvx3), _f32c(pts_bxqx3)
+    idx = getattr(topology, "tet_idx32", None)
+    if idx is None or (tet_idx is not getattr(topology, "tet_idx", None) and tet_idx is not idx):
+        idx = tet_idx
+    idx = _idx32(idx)
+    if pos.dim() != 3 or pos.shape[2] != 3:
+        raise RuntimeError("pos must be [B,V,3], got %s" % (tuple(pos.shape),))
+    if idx.dim() != 3 or idx.shape[2] != 4 or idx.shape[0] not in (1, pos.shape[0]):
+        raise RuntimeError("tet_idx must be [T,4] or [B,T,4] with B matching pos, got %s" % (tuple(idx.shape),))
+    if pts.dim() != 3 or pts.shape[2] != 3 or pts.shape[0] != pos.shape[0]:
+        raise RuntimeError("point_pos_bxnx3 must be [B,Q,3] with the same B, got %s" % (tuple(pts.shape),))
+    if idx.device != pos.device or pts.device != pos.device:
+        raise RuntimeError("pos, tet_idx and pts must be on one device")
+    return pos, idx, pts
+
+
+def _auto_order_indexed(pos, idx, pts, algo, topology):
+    """auto_tet_order for the indexed path: the per-topology decision when it is cached, else decided once on shape 0's tets
+    (gathered for that only).  The index list itself is the topology key when the caller gives none."""
+    if topology is None:
+        topology = idx
+    T, Q = idx.shape[1], pts.shape[1]
+    dev = pos.device
+    if pos.shape[0] and T >= 4096 and Q:
+        kernel = int(_lib.load().deftet_point_in_tet_resolve_algo(int(algo), T, Q))
+        key = (dev.index if dev.index is not None else torch.cuda.current_device(), T, kernel, _topology_key(topology))
+        with _order_lock:
+            entry = _order_cache.get(key)
+        if entry is not None:
+            return entry.choice
+    if torch.cuda.is_current_stream_capturing():                     # (auto_tet_order decides nothing inside a capture either)
+        return None
+    return auto_tet_order(tet_gather(pos[:1], idx[:1]), pts, algo, topology)
+
+
+def point_in_tet_indexed(pos_bxvx3, tet_idx, pts_bxqx3, want_bary=False, algo=PIT_AUTO, pred_bxt=None, want_hits=False, prepared=None,
+                         order=None, query_box=None, query_box_misses=None, topology=None, check=False):
+    """point_in_tet on the tets (pos_bxvx3, tet_idx) without gathering them: corner c of tet t of shape b is
+    pos[b, tet_idx[b or 0, t, c]].  tet_idx: [T,4] (shared by the shapes) or [B,T,4], any integer dtype (a TetTopology's int32
+    copy is used when `topology` is one).  Returns exactly what point_in_tet(tet_gather(pos, tet_idx), pts, ...) returns, bit
+    for bit, including the hit records (either backward takes them).  An index outside [0, V) reads as a NaN corner, as in
+    tet_gather; check=True synchronises and raises on one."""
+    pos, idx, pts = _indexed_inputs(pos_bxvx3, tet_idx, pts_bxqx3, topology)
+    _lib.require_gpu(pred_bxt)
+    lib = _lib.load()
+    B, V, T, Q, Bi = pos.shape[0], pos.shape[1], idx.shape[1], pts.shape[1], idx.shape[0]
+    dev = pts.device
+    cond = torch.empty(B, Q, 1, device=dev, dtype=torch.float32)
+    bary = torch.empty(B, Q, 4, device=dev, dtype=torch.float32) if want_bary else None
+    pred = _f32c(pred_bxt) if pred_bxt is not None else None
+    if pred is not None and pred.shape != (B, T):
+        raise RuntimeError("pred_tet_occ must be [B,T], got %s" % (tuple(pred.shape),))
+    occ = torch.empty(B, Q, device=dev, dtype=torch.float32) if pred is not None else None
+    hits = None
+    if want_hits and algo != PIT_BRUTE:
+        hits = torch.empty(max(lib.deftet_point_in_tet_hits_ints(B, T, Q), 4), device=dev, dtype=torch.int32)
+    if isinstance(order, str):
+        if order != "auto":
+            raise RuntimeError("order must be None, 'auto' or an int32 [T] permutation")
+        order = _auto_order_indexed(pos, idx, pts, algo, topology) if algo in (PIT_AUTO, PIT_SLAB, PIT_WAVE, PIT_PAIR) else None
+    if order is not None:
+        _lib.require_gpu(order)
+        if order.dtype != torch.int32 or order.shape != (T,) or not order.is_contiguous() or order.device != dev:
+            raise RuntimeError("order must be a contiguous int32 [T] tensor on the tets' device")
+        _check_order(order, T)
+    bad = torch.zeros(1, device=dev, dtype=torch.int32) if check else None
+    with _lib.on_device(dev):
+        if prepared is not None:
+            if prepared.consumed or prepared.algo != algo or prepared.n_tet != T or prepared.pts.data_ptr() != pts.data_ptr() \
+                    or prepared.pts.shape != pts.shape:
+                raise RuntimeError("point_in_tet_indexed: `prepared` was made for other points / sizes / algo, or was already used")
+            if prepared.version != pts._version:
+                raise RuntimeError("point_in_tet_indexed: the points were modified in place after prepare_queries (stale sorted copy)")
+            cur = torch.cuda.current_stream(dev)
+            cur.wait_event(prepared.event)
+            ws = prepared.workspace
+            ws.record_stream(cur)
+            prepared.consumed = True
+            _lib.check(lib.deftet_point_in_tet_indexed_scan_f32(_lib.ptr(pos), _lib.ptr(idx), Bi, _lib.ptr(pts), _lib.ptr(cond), _lib.ptr(bary),
+                                                                _lib.ptr(pred), _lib.ptr(occ), _lib.ptr(hits), B, V, T, Q, algo, _lib.ptr(order),
+                                                                _lib.ptr(bad), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
+                       "deftet_point_in_tet_indexed_scan_f32")
+        else:
+            ws = _lib.workspace(dev, lib.deftet_point_in_tet_workspace_bytes(B, T, Q, algo))
+            box_in, box_out, box_miss = _resolve_query_box(query_box, dev, B, Q, algo, query_box_misses)
+            _lib.check(lib.deftet_point_in_tet_indexed_f32(_lib.ptr(pos), _lib.ptr(idx), Bi, _lib.ptr(pts), _lib.ptr(cond), _lib.ptr(bary),
+                                                           _lib.ptr(pred), _lib.ptr(occ), _lib.ptr(hits), B, V, T, Q, algo, _lib.ptr(order),
+                                                           _lib.ptr(box_in), _lib.ptr(box_out), _lib.ptr(box_miss), _lib.ptr(bad),
+                                                           _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
+                       "deftet_point_in_tet_indexed_f32")
+    if check and int(bad.item()):
+        raise RuntimeError("point_in_tet_indexed: index out of range [0, %d)" % V)
+    out = (cond,) + ((bary,) if want_bary else ()) + ((occ,) if pred is not None else ()) + ((hits,) if want_hits else ())
+    return out if len(out) > 1 else cond
+
+
 def point_in_tet_grid(n_tet, n_query):
     """(y/z cells per axis, x cells) of the query grid the binned algos build for this problem size."""
     import ctypes
@@ -531,6 +639,41 @@ def point_in_tet_bwd_to_vertices(tet_bxtx4x3, pts_bxqx3, cond, grad_w, csr, n_ve
                                                                _lib.ptr(grad_pts), _lib.ptr(grad_pred), B, V, T, Q, 1 if acc else 0,
                                                                _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
                    "deftet_point_in_tet_bwd_to_vertices_f32")
+    if go is not None:
+        return grad_pos, grad_pts, grad_pred
+    return grad_pos, grad_pts
+
+
+def point_in_tet_indexed_bwd_to_vertices(pos, tet_idx, pts, cond, grad_w, csr, want_grad_pts=False, grad_occ=None, hits=None, out=None):
+    """point_in_tet_bwd_to_vertices for the indexed forward: the tets are read from (pos, tet_idx) instead of a gathered tensor.
+    csr = tet_vertex_csr(tet_idx, V) of the same list (same idx_batch).  Returns and `out=` as point_in_tet_bwd_to_vertices, bit
+    for bit the same values on the same inputs; hits from either forward."""
+    pos, idx, pts = _indexed_inputs(pos, tet_idx, pts, None)
+    _lib.require_gpu(cond, grad_w, grad_occ)
+    lib = _lib.load()
+    cond, gw = _f32c(cond), _f32c(grad_w)
+    B, V, T, Q, Bi = pos.shape[0], pos.shape[1], idx.shape[1], pts.shape[1], idx.shape[0]
+    offsets, slots, Bc = csr
+    if Bc != Bi:
+        raise RuntimeError("point_in_tet_indexed_bwd_to_vertices: the CSR was built over %d index list(s), tet_idx has %d" % (Bc, Bi))
+    if slots.numel() != Bi * T * 4 or offsets.numel() != Bi * V + 1:
+        raise RuntimeError("point_in_tet_indexed_bwd_to_vertices: CSR does not match tet_idx / n_vertex")
+    dev = pts.device
+    acc = out is not None
+    if acc and (out.shape != (B, V, 3) or out.dtype != torch.float32 or not out.is_contiguous()):
+        raise RuntimeError("point_in_tet_indexed_bwd_to_vertices: out must be contiguous f32 [B,V,3]")
+    grad_pos = out if acc else torch.empty(B, V, 3, device=dev, dtype=torch.float32)
+    grad_pts = torch.empty_like(pts) if want_grad_pts else None
+    go = _f32c(grad_occ) if grad_occ is not None else None
+    grad_pred = (torch.zeros if acc else torch.empty)(B, T, device=dev, dtype=torch.float32) if go is not None else None
+    with _lib.on_device(dev):
+        ws = _lib.workspace(dev, lib.deftet_point_in_tet_bwd_to_vertices_workspace_bytes(B, T, Q))
+        _lib.check(lib.deftet_point_in_tet_indexed_bwd_to_vertices_f32(_lib.ptr(pos), _lib.ptr(idx), Bi, _lib.ptr(pts), _lib.ptr(cond),
+                                                                       _lib.ptr(gw), _lib.ptr(go), _lib.ptr(hits), _lib.ptr(offsets),
+                                                                       _lib.ptr(slots), _lib.ptr(grad_pos), _lib.ptr(grad_pts),
+                                                                       _lib.ptr(grad_pred), B, V, T, Q, 1 if acc else 0, _lib.ptr(ws),
+                                                                       ws.numel(), _lib.current_stream(dev)),
+                   "deftet_point_in_tet_indexed_bwd_to_vertices_f32")
     if go is not None:
         return grad_pos, grad_pts, grad_pred
     return grad_pos, grad_pts

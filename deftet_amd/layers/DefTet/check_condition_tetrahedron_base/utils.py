@@ -124,6 +124,36 @@ class PointInTetOccVertices(Function):
 point_in_tet_occ_vertices = PointInTetOccVertices.apply
 
 
+class PointInTetOccIndexed(Function):
+    """PointInTetOccVertices without the gathered tensor: (vertice_pos [B,V,3], pts [B,Q,3], pred_tet_occ [B,T], topology) ->
+    (condition, weights, occ).  The forward and the backward read the tets through the topology's index list
+    (hip_ops.point_in_tet_indexed / point_in_tet_indexed_bwd_to_vertices), so no [B,T,4,3] tensor exists at any time; what is
+    kept for the backward is vertice_pos itself (saved for backward: an in-place change to it before the backward raises
+    torch's usual error instead of giving a wrong gradient).  The same bits as PointInTetOccVertices."""
+
+    @staticmethod
+    def forward(ctx, vertice_pos, point_pos_bxnx3, pred_tet_occ, topology):
+        rec = hip_ops.bwd_uses_records(topology.tet_idx32.shape[1], point_pos_bxnx3.shape[1])
+        out = hip_ops.point_in_tet_indexed(vertice_pos, topology.tet_idx32, point_pos_bxnx3, want_bary=True, pred_bxt=pred_tet_occ,
+                                           want_hits=rec, order="auto", query_box="track", topology=topology)
+        cond, w, occ, hits = out if rec else (out + (None,))
+        ctx.save_for_backward(vertice_pos, point_pos_bxnx3, cond, hits)
+        ctx.topology = topology
+        ctx.mark_non_differentiable(cond)
+        return cond, w, occ
+
+    @staticmethod
+    def backward(ctx, _grad_cond, grad_w, grad_occ):
+        pos, pts, cond, hits = ctx.saved_tensors
+        g_pos, g_pts, g_pred = hip_ops.point_in_tet_indexed_bwd_to_vertices(pos.detach(), ctx.topology.tet_idx32, pts, cond, grad_w,
+                                                                            ctx.topology.csr, want_grad_pts=ctx.needs_input_grad[1],
+                                                                            grad_occ=grad_occ, hits=hits)
+        return (g_pos if ctx.needs_input_grad[0] else None), g_pts, (g_pred if ctx.needs_input_grad[2] else None), None
+
+
+point_in_tet_occ_indexed = PointInTetOccIndexed.apply
+
+
 class PasteOcc(Function):
     """DefTet.paste_occ (layers/DefTet/deftet.py:132-136) as one fused gather with its
     scatter-add backward; `condition` is clamped in place like the reference does."""

@@ -22,7 +22,8 @@ import torch
 import torch.nn as nn
 
 from deftet_amd import hip_ops, surface_losses
-from deftet_amd.layers.DefTet.check_condition_tetrahedron_base.utils import check_condition_f_base, paste_occ, point_in_tet_occ_vertices
+from deftet_amd.layers.DefTet.check_condition_tetrahedron_base.utils import (check_condition_f_base, paste_occ, point_in_tet_occ_indexed,
+                                                                             point_in_tet_occ_vertices)
 
 EPS = 1e-10
 
@@ -57,7 +58,8 @@ class TetTopology:
             idx = idx[:1]
         self.tet_idx = idx.contiguous()
         self.n_vertex = int(n_vertex)
-        self.csr = hip_ops.tet_vertex_csr(self.tet_idx, self.n_vertex)
+        self.csr = hip_ops.tet_vertex_csr(self.tet_idx, self.n_vertex)     # (raises on an index outside [0, n_vertex))
+        self.tet_idx32 = self.tet_idx.to(torch.int32).contiguous()         # what the indexed query reads (hip_ops.point_in_tet_indexed)
 
     def gather(self, vertice_pos):
         return _TetGather.apply(vertice_pos, self.tet_idx, self.csr)
@@ -160,10 +162,14 @@ class DefTet(nn.Module):
 
     # --- A1 + A1b + paste_occ for a caller that holds the VERTICES (build-defined, like point_in_tet_occ): the gradient of the
     #     weights lands on vertice_pos without the dense per-tet gradient in between
-    def occupancy_query(self, vertice_pos, tetrahedron_bxfx4, point_pos_bxpx3, pred_tet_occ, tet_bxfx4x3=None):
+    def occupancy_query(self, vertice_pos, tetrahedron_bxfx4, point_pos_bxpx3, pred_tet_occ, tet_bxfx4x3=None, indexed=False):
         """(condition [B,Q,1], weights [B,Q,4], occ [B,Q]) of the query points in the mesh (vertice_pos, tetrahedron_bxfx4);
-        tet_bxfx4x3 = self.gather_tet_pos(vertice_pos, tetrahedron_bxfx4) when the caller has it already."""
+        tet_bxfx4x3 = self.gather_tet_pos(vertice_pos, tetrahedron_bxfx4) when the caller has it already.
+        indexed=True (and no tet_bxfx4x3): the query reads the vertices through the index list and never materialises the
+        [B,T,4,3] tensor, neither as a temporary nor as memory kept for the backward; the same bits either way."""
         topo = _topology_for(tetrahedron_bxfx4, vertice_pos.shape[1])
+        if indexed and tet_bxfx4x3 is None:
+            return point_in_tet_occ_indexed(vertice_pos, point_pos_bxpx3, pred_tet_occ, topo)
         return point_in_tet_occ_vertices(vertice_pos, point_pos_bxpx3, pred_tet_occ, topo, tet_bxfx4x3)
 
     # --- A11 (each call evaluates the fused kernel and returns its own component)

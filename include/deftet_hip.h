@@ -42,7 +42,10 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
-/* 220: round 6 — deftet_tet_order_coherence_f32 (what the traversal-order decision is made on); the rasterizer bins into at most
+/* 230: the indexed point-in-tet query — deftet_point_in_tet_indexed_f32, _indexed_scan_f32, _indexed_bwd_to_vertices_f32 take
+ *      vertices + a tet index list instead of the gathered [B,T,4,3] tensor (outputs bit-identical to the dense entry points).
+ * 221: round 6, second half — 8-byte hit records, deftet_point_in_tet_bwd_to_vertices_f32, deftet_put_host_ints.
+ * 220: round 6 — deftet_tet_order_coherence_f32 (what the traversal-order decision is made on); the rasterizer bins into at most
  *      90 x 90 tiles and gives sliver faces a certified box (no interface change).
  * 210: round 5 — the *_ex_* point-in-tet entry points (traversal order, query box with its miss counts),
  * deftet_tet_spatial_order_f32, DEFTET_PIT_PAIR; the backward takes per-tet lists above 2 queries per tet.
@@ -373,6 +376,32 @@ int deftet_point_in_tet_bwd_to_vertices_f32(const float *tet, const float *pts, 
                                             const int32_t *csr_slots, int idx_batch, float *grad_pos, float *grad_pts,
                                             float *grad_pred, int n_batch, int n_vertex, int n_tet, int n_query,
                                             int accumulate, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Indexed input (230): the occupancy query straight from vertex positions and a tet index list.  Corner c of tet t of shape b
+ * is pos[b, tet_idx[ib, t, c]], ib = 0 when idx_batch == 1, else b.  pos: f32 [B,V,3], contiguous, 4-byte aligned (a slice of
+ * a vertex tensor works); tet_idx: int32 [idx_batch,T,4], contiguous, 16-byte aligned, idx_batch 1 or B.  Every output — cond,
+ * bary, occ, hit_buf records, query box — is bit-identical to deftet_point_in_tet_ex_f32 / _scan_ex_f32 /
+ * _bwd_to_vertices_f32 run on the tensor deftet_tet_gather_fwd_f32 makes from the same pos and list, for every algo, with and
+ * without tet_order and a query box; the records of either forward feed either backward.  An index outside [0, V) reads as a
+ * (NaN, NaN, NaN) corner, as in that gather, and sets *bad_flag (device int32, may be NULL) to 1; pos is never read out of
+ * range.  Workspaces: deftet_point_in_tet_workspace_bytes and deftet_point_in_tet_bwd_to_vertices_workspace_bytes.
+ * The scan form consumes a deftet_point_in_tet_prepare[_ex]_f32 exactly as deftet_point_in_tet_scan_ex_f32 does.  The CSR
+ * (deftet_tet_vertex_csr_i32) must be built over the same list, with the same idx_batch. */
+int deftet_point_in_tet_indexed_f32(const float *pos, const int32_t *tet_idx, int idx_batch, const float *pts, float *cond,
+                                    float *bary, const float *pred, float *occ, int32_t *hit_buf, int n_batch, int n_vertex,
+                                    int n_tet, int n_query, int algo, const int32_t *tet_order, const float *query_box_in,
+                                    float *query_box_out, int32_t *query_box_misses, int32_t *bad_flag, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+int deftet_point_in_tet_indexed_scan_f32(const float *pos, const int32_t *tet_idx, int idx_batch, const float *pts, float *cond,
+                                         float *bary, const float *pred, float *occ, int32_t *hit_buf, int n_batch, int n_vertex,
+                                         int n_tet, int n_query, int algo, const int32_t *tet_order, int32_t *bad_flag,
+                                         void *workspace, size_t workspace_bytes, void *stream);
+int deftet_point_in_tet_indexed_bwd_to_vertices_f32(const float *pos, const int32_t *tet_idx, int idx_batch, const float *pts,
+                                                    const float *cond, const float *grad_w, const float *grad_occ,
+                                                    const int32_t *hit_buf, const int32_t *csr_offsets, const int32_t *csr_slots,
+                                                    float *grad_pos, float *grad_pts, float *grad_pred, int n_batch, int n_vertex,
+                                                    int n_tet, int n_query, int accumulate, void *workspace,
+                                                    size_t workspace_bytes, void *stream);
 
 /* A11 fused per-tet energies, layers/DefTet/deftet.py:239-338: out f32 [B,3] =
  * {volume_variance(pow_v), amips_energy(inv_v f32 [T,3,3]; 0 when NULL), edge_length(pow_e)};
