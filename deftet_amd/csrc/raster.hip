@@ -713,14 +713,46 @@ __global__ __launch_bounds__(256) void k_pix_raster(const float *__restrict__ pi
     if (live) nhit[p] = (nearest && RAST_PROBE_NOSTORE) ? 0 : nh;      // (probe builds wrote no records: nothing for k_pix_emit to read)
 }
 
+// The rank of hit `me` (record i0 + lane of the pixel's n records h[]) in the output order (z descending, face ascending): the
+// number of the pixel's hits that come before it.  The (face, z) keys are parked in LDS (s_key: this wave's 64 entries), 64 at a
+// time, and every lane ranks its own hit against them with wave-uniform 8-byte reads (LDS broadcasts, all in flight together).
+// Rounds 2-5 read them through the scalar cache with a wait after every pair of loads: 32 dependent scalar-cache latencies per
+// wave (round 6: 0.30 -> 0.245 ms at configs[4]).  Called by the whole wave (n wave-uniform).
+__device__ __forceinline__ int pix_rank(const int4 *h, int n, int i0, int lane, int wv, int4 me, float zi, int2 (*s_key)[64])
+{
+    int r = 0;
+    for (int j0 = 0; j0 < n; j0 += 64) {                          // the pixel's hits, 64 keys per round
+        __builtin_amdgcn_wave_barrier();
+        const int jl = j0 + lane;
+        if (jl < n) s_key[wv][lane] = (jl >= i0 && jl < i0 + 64) ? make_int2(me.x, me.y) : *reinterpret_cast<const int2 *>(h + jl);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const int m = min(64, n - j0);
+        int j = 0;
+        for (; j + 8 <= m; j += 8) {
+            int2 o[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) o[u] = s_key[wv][j + u];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const float zj = __int_as_float(o[u].y);
+                r += (zj > zi || (zj == zi && o[u].x < me.x)) ? 1 : 0;
+            }
+        }
+        for (; j < m; ++j) {
+            const int2 o = s_key[wv][j];
+            const float zj = __int_as_float(o.y);
+            r += (zj > zi || (zj == zi && o.x < me.x)) ? 1 : 0;
+        }
+    }
+    return r;
+}
+
 // one wave per pixel: rank by (z descending, face ascending), write the sorted outputs
 __global__ __launch_bounds__(256) void k_pix_emit(const int4 *__restrict__ hits, const int *__restrict__ nhit,
                                                   const float *__restrict__ feat, int P, int D, int knum, float *out_feat,
                                                   long long *out_face, float *out_w)
 {
-    // The (face, z) keys of the pixel's hits are parked in LDS, 64 at a time, and every lane ranks its own hit against them with
-    // wave-uniform 8-byte reads (LDS broadcasts, all in flight together).  Rounds 2-5 read them through the scalar cache with a
-    // wait after every pair of loads: 32 dependent scalar-cache latencies per wave (round 6: 0.30 -> 0.245 ms at configs[4]).
     __shared__ int2 s_key[4][64];
     const int p = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -734,31 +766,7 @@ __global__ __launch_bounds__(256) void k_pix_emit(const int4 *__restrict__ hits,
         int4 me = make_int4(0, 0, 0, 0);
         if (mine) me = h[i];
         const float zi = __int_as_float(me.y);
-        int r = 0;
-        for (int j0 = 0; j0 < n; j0 += 64) {                          // the pixel's hits, 64 keys per round
-            __builtin_amdgcn_wave_barrier();
-            const int jl = j0 + lane;
-            if (jl < n) s_key[wv][lane] = (jl >= i0 && jl < i0 + 64) ? make_int2(me.x, me.y) : *reinterpret_cast<const int2 *>(h + jl);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            const int m = min(64, n - j0);
-            int j = 0;
-            for (; j + 8 <= m; j += 8) {
-                int2 o[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) o[u] = s_key[wv][j + u];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const float zj = __int_as_float(o[u].y);
-                    r += (zj > zi || (zj == zi && o[u].x < me.x)) ? 1 : 0;
-                }
-            }
-            for (; j < m; ++j) {
-                const int2 o = s_key[wv][j];
-                const float zj = __int_as_float(o.y);
-                r += (zj > zi || (zj == zi && o.x < me.x)) ? 1 : 0;
-            }
-        }
+        const int r = pix_rank(h, n, i0, lane, wv, me, zi, s_key);
         if (mine) {
             const size_t o = (size_t)p * knum + r;
             const float w1 = __int_as_float(me.z), w2 = __int_as_float(me.w), w0 = 1 - w1 - w2;
@@ -1197,6 +1205,237 @@ __global__ __launch_bounds__(kRunWaves * 64) void k_bwd_runs(const float *__rest
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Fused rasterize-and-composite (240): the ranked layers of a pixel are composited front to back where they are made, as
+// alpha_composite (deftet_amd/render/compositing.py) composites the [B,P,knum,D] stack: opacity alpha_i = clamp(channel a, 1e-10,
+// 1 - 1e-10) (a = 1 with a depth channel 0, else 0), T_i = prod_{j<i} (1 - alpha_j), w_i = alpha_i T_i, colour = sum_i w_i c_i +
+// background (1 - coverage), coverage = sum_i w_i, depth = sum_i w_i d_i + far (1 - coverage).  The knum - n empty slots of a pixel
+// with n hits are zero layers at opacity 1e-10: 1 - 1e-10 is 1.0f, so they leave T unchanged and add (knum - n) 1e-10 T to the
+// coverage (closed form).  One wave per pixel, 64 ranked slots per window; every sum has a fixed order.
+constexpr float kAlphaLo = 1e-10f, kAlphaHi = 1.0f;          // torch's clamp(alpha, 1e-10, 1 - 1e-10) in fp32
+
+__device__ __forceinline__ float clamp_alpha(float x) { return x < kAlphaLo ? kAlphaLo : (x > kAlphaHi ? kAlphaHi : x); }   // NaN stays NaN
+
+// sum over the wave by a butterfly: every lane ends with the same bits (a + b == b + a)
+__device__ __forceinline__ float wave_sum(float x)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+    return x;
+}
+
+// Exclusive product scan over the wave (lane 0 receives 1) in a fixed order — DPP row_shr 1, 2, 4, 8 inside the rows, row_bcast
+// 15 and 31 across them (as seg_scan), then one lane up — and the product of all 64 in `total`.
+__device__ __forceinline__ float wave_excl_prod(float x, int lane, float &total)
+{
+    const int r = lane & 15;
+    float t;
+    t = __int_as_float(dpp_mov<0x111, 0xf>(__float_as_int(x))); x *= r >= 1 ? t : 1.f;
+    t = __int_as_float(dpp_mov<0x112, 0xf>(__float_as_int(x))); x *= r >= 2 ? t : 1.f;
+    t = __int_as_float(dpp_mov<0x114, 0xf>(__float_as_int(x))); x *= r >= 4 ? t : 1.f;
+    t = __int_as_float(dpp_mov<0x118, 0xf>(__float_as_int(x))); x *= r >= 8 ? t : 1.f;
+    t = __int_as_float(dpp_mov<0x142, 0xa>(__float_as_int(x))); x *= (lane & 16) ? t : 1.f;
+    t = __int_as_float(dpp_mov<0x143, 0xc>(__float_as_int(x))); x *= (lane & 32) ? t : 1.f;
+    total = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
+    const float e = lane_below(x);
+    return lane == 0 ? 1.f : e;
+}
+
+// One ranked slot: its face and barycentric weights, and channel d of its layer — k_pix_emit's expression.
+struct Slot {
+    const float *ff;
+    float w0, w1, w2;
+    int D;
+    __device__ __forceinline__ float layer(int d) const { return (w0 * ff[d] + w1 * ff[D + d]) + w2 * ff[2 * D + d]; }
+};
+
+// The transmittance before every slot of a window: the window's slots (alpha of the used ones, 1 - alpha = 1 for the others) are
+// scanned in lane order and T carries the product of everything before the window.  The forward and the backward call this.
+__device__ __forceinline__ float window_T(float alpha, bool used, int lane, float &T)
+{
+    float tot;
+    const float Ti = T * wave_excl_prod(used ? 1.f - alpha : 1.f, lane, tot);
+    T = T * tot;
+    return Ti;
+}
+
+// Forward: rank (pix_rank, as k_pix_emit), then composite.  The rank pass parks each hit's record index in its ranked slot of
+// out_face; the compositing pass reads it back slot by slot (64 ranked slots per window) and overwrites it with the face.
+__global__ __launch_bounds__(256) void k_pix_composite(const int4 *__restrict__ hits, const int *__restrict__ nhit,
+                                                       const float *__restrict__ feat, int P, int D, int knum, int depthCh,
+                                                       float background, float farDepth, float *out_colour, float *out_cov,
+                                                       float *out_depth, int *out_face)
+{
+    __shared__ int2 s_key[4][64];
+    const int p = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (p >= P) return;
+    const int n = nhit[p];
+    const int4 *h = hits + (size_t)p * knum;
+    int *of = out_face + (size_t)p * knum;
+    for (int i0 = 0; i0 < n; i0 += 64) {                             // (wave-uniform trip count)
+        const int i = i0 + lane;
+        const bool mine = i < n;
+        int4 me = make_int4(0, 0, 0, 0);
+        if (mine) me = h[i];
+        const int r = pix_rank(h, n, i0, lane, wv, me, __int_as_float(me.y), s_key);
+        if (mine) of[r] = i;
+    }
+    // the slots were written by other lanes of this wave: make the stores visible before they are read back
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    const int a = depthCh ? 1 : 0, c0 = a + 1, Dc = D - c0;
+    float *oc = out_colour + (size_t)p * Dc;
+    float T = 1.f, cov = 0.f, dep = 0.f;
+    for (int r0 = 0; r0 < n; r0 += 64) {
+        const int sl = r0 + lane;
+        const bool used = sl < n;
+        Slot S{feat, 0.f, 0.f, 0.f, D};
+        if (used) {
+            int i = of[sl];
+            i = (unsigned)i < (unsigned)n ? i : 0;                   // (a permutation: always true)
+            const int4 rec = h[i];
+            of[sl] = rec.x;
+            S.ff = feat + (size_t)rec.x * 3 * D;
+            S.w1 = __int_as_float(rec.z); S.w2 = __int_as_float(rec.w);
+            S.w0 = 1 - S.w1 - S.w2;
+        }
+        const float alpha = clamp_alpha(used ? S.layer(a) : 0.f);
+        const float Ti = window_T(alpha, used, lane, T);
+        const float w = used ? alpha * Ti : 0.f;
+        cov += wave_sum(w);
+        if (depthCh) dep += wave_sum(used ? w * S.layer(0) : 0.f);
+        for (int c = 0; c < Dc; ++c) {
+            const float sc = wave_sum(used ? w * S.layer(c0 + c) : 0.f);
+            if (lane == 0) oc[c] = r0 == 0 ? sc : oc[c] + sc;         // (the lane's own earlier store)
+        }
+    }
+    cov += (float)(knum - n) * (kAlphaLo * T);                       // the empty slots, in closed form
+    if (lane == 0) {
+        out_cov[p] = cov;
+        for (int c = 0; c < Dc; ++c) oc[c] = (n > 0 ? oc[c] : 0.f) + background * (1.f - cov);
+        if (depthCh) out_depth[p] = dep + farDepth * (1.f - cov);
+    }
+    for (int sl = n + lane; sl < knum; sl += 64) of[sl] = -1;
+}
+
+// Backward of the compositing onto the layers, one wave per pixel.  With v_i = sum_c g_col,c (c_i,c - background) + g_cov +
+// g_dep (d_i - far) (what dL/dw_i is), dL/dalpha_i = T_i (v_i - R_i), R_i = alpha_{i+1} v_{i+1} + (1 - alpha_{i+1}) R_{i+1}:
+// no division by 1 - alpha (alpha = 1 is reachable).  The empty slots seed R_{n-1} = (knum - n) 1e-10 v_empty.  The recurrence
+// is run on Q_i = v_i - R_i (below) as a reverse scan of affine maps, 64 slots per window from the last window to the first
+// (fixed order).
+// Writes the layer gradient [D] of every used slot into gout (slot = pixel * knum + rank, as the unfused backward reads it):
+// opacity channel dL/dalpha masked by the clamp (passes for 1e-10 <= alpha <= 1, as torch's clamp), colour w_i g_col,c, depth
+// w_i g_dep.  The first pass parks T_i in the slot's opacity channel; the lane that owns the slot reads it back in the second.
+__global__ __launch_bounds__(256) void k_pix_composite_bwd(const float *__restrict__ pix, const float *__restrict__ fxy,
+                                                           const float *__restrict__ feat, const int *__restrict__ face,
+                                                           const float *__restrict__ gcol, const float *__restrict__ gcov,
+                                                           const float *__restrict__ gdep, int P, int F, int D, int knum, float eps,
+                                                           int depthCh, float background, float farDepth, float *gout)
+{
+    const int p = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    if (p >= P) return;
+    const int *fr = face + (size_t)p * knum;
+    int n = knum;                                                    // used slots: the ranked faces fill 0..n-1
+    for (int s0 = 0; s0 < knum; s0 += 64) {
+        const int sl = s0 + lane;
+        const int f = sl < knum ? fr[sl] : -1;
+        const unsigned long long m = __ballot(f >= 0 && f < F);
+        if (m != ~0ull) { n = min(knum, s0 + __ffsll((long long)~m) - 1); break; }
+    }
+    const int a = depthCh ? 1 : 0, c0 = a + 1, Dc = D - c0;
+    const float2 px = reinterpret_cast<const float2 *>(pix)[p];
+    const float gv = gcov ? gcov[p] : 0.f, gd = (depthCh && gdep) ? gdep[p] : 0.f;
+    const float *gc = gcol ? gcol + (size_t)p * Dc : nullptr;
+    float *go = gout + (size_t)p * knum * D;
+    auto slot = [&](int sl) __attribute__((always_inline)) {          // the forward's weights, recomputed bit for bit (k_bwd_sorted)
+        Slot S{feat, 0.f, 0.f, 0.f, D};
+        const int f = fr[sl];
+        const float2 pa = reinterpret_cast<const float2 *>(fxy)[f * 3], pb = reinterpret_cast<const float2 *>(fxy)[f * 3 + 1],
+                     pc = reinterpret_cast<const float2 *>(fxy)[f * 3 + 2];
+        const float m = pb.x - pa.x, pp = pb.y - pa.y, nn = pc.x - pa.x, q = pc.y - pa.y, s = px.x - pa.x, t = px.y - pa.y;
+        const float k1 = s * q - nn * t, k2 = m * t - s * pp, k3 = m * q - nn * pp;
+        const float den = k3 + eps;
+        S.ff = feat + (size_t)f * 3 * D;
+        S.w1 = k1 / den; S.w2 = k2 / den; S.w0 = 1 - S.w1 - S.w2;
+        return S;
+    };
+    // pass 1: T_i of every used slot (the forward's scan, same code and order)
+    float T = 1.f;
+    for (int r0 = 0; r0 < n; r0 += 64) {
+        const int sl = r0 + lane;
+        const bool used = sl < n;
+        float alpha = 0.f;
+        if (used) alpha = slot(sl).layer(a);
+        alpha = clamp_alpha(alpha);
+        const float Ti = window_T(alpha, used, lane, T);
+        if (used) go[(size_t)sl * D + a] = Ti;
+    }
+    // pass 2: the reverse recurrence, windows from last to first, on Q_i = v_i - R_i: Q_i = (v_i - v_{i+1}) + (1 - alpha_{i+1})
+    // Q_{i+1}, Q_{n-1} = v_{n-1} - R_{n-1}.  (The same numbers as R, without the cancellation of v_i - R_i: with coverage alone
+    // v is one constant and R_i approaches it as the layers behind become opaque.)
+    float vEmpty = gv;                                               // v of an empty slot (all its channels are 0)
+    if (depthCh) vEmpty += gd * (0.f - farDepth);
+    if (gc)
+        for (int c = 0; c < Dc; ++c) vEmpty += gc[c] * (0.f - background);
+    const float Rseed = (float)(knum - n) * (kAlphaLo * vEmpty);
+    float Q = 0.f, vNext = 0.f, aNext = 0.f;                         // Q, v and alpha of the slot after the window
+    for (int r0 = (n - 1) & ~63; r0 >= 0 && n > 0; r0 -= 64) {
+        const int sl = r0 + lane;
+        const bool used = sl < n;
+        float v = 0.f, alpha = 0.f, araw = 0.f, Ti = 0.f, w = 0.f;
+        if (used) {
+            const Slot S = slot(sl);
+            araw = S.layer(a);
+            alpha = clamp_alpha(araw);
+            Ti = go[(size_t)sl * D + a];
+            w = alpha * Ti;
+            v = gv;
+            if (depthCh) v += gd * (S.layer(0) - farDepth);
+            if (gc)
+                for (int c = 0; c < Dc; ++c) v += gc[c] * (S.layer(c0 + c) - background);
+        }
+        // lane l holds the map Q_{l+1} -> Q_l: (A, B) = (v_l - v_{l+1}, 1 - alpha_{l+1}); the last used slot's ignores its
+        // argument, unused lanes are the identity
+        float v1 = __shfl_down(v, 1), a1 = __shfl_down(alpha, 1);
+        if (lane == 63) { v1 = vNext; a1 = aNext; }
+        float A = 0.f, Bm = 1.f;
+        if (used) {
+            const bool last = sl == n - 1;
+            A = last ? v - Rseed : v - v1;
+            Bm = last ? 0.f : 1.f - a1;
+        }
+        // inclusive suffix scan of the maps: (A, B) o (A', B') = (A + B A', B B'), fixed order
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const float oA = __shfl_down(A, d), oB = __shfl_down(Bm, d);
+            if (lane + d < 64) { A = A + Bm * oA; Bm = Bm * oB; }
+        }
+        const float Qi = A + Bm * Q;
+        Q = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Qi), 0));
+        vNext = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
+        aNext = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(alpha), 0));
+        if (used) {
+            float *g = go + (size_t)sl * D;
+            g[a] = (araw >= kAlphaLo && araw <= kAlphaHi) ? Ti * Qi : 0.f;
+            if (depthCh) g[0] = w * gd;
+            for (int c = 0; c < Dc; ++c) g[c0 + c] = gc ? w * gc[c] : 0.f;
+        }
+    }
+}
+
+// first-pass key loader of the hit sort for the fused operator: the ranked int32 face ids (empty slots: the padding key F)
+struct FaceKeyLoad32 {
+    const int *face;
+    int F;
+    __device__ __forceinline__ unsigned operator()(size_t i) const
+    {
+        const int f = face[i];
+        return (f >= 0 && f < F) ? (unsigned)f : (unsigned)F;
+    }
+};
+
 struct BwdLayout {
     size_t bytes, tmpBytes;
     unsigned *skey, *sval;
@@ -1296,6 +1535,64 @@ extern "C" int deftet_debug_rast_stats(unsigned long long *out8, int reset)
 }
 #endif
 
+// Everything of the forward up to and including k_pix_raster for one batch entry: the pixel's hit records (face, z, w1, w2) in
+// L.hits (knum per pixel, unordered) and their count in L.nhit.  Shared by the layer-returning and the compositing operator.
+static int raster_hits(const float *pb, const float *rb, const float *zb, const float *xb, int P, int F, int knum, float eps,
+                       int policy, const Layout &L, hipStream_t st)
+{
+    DEFTET_LAUNCH(k_pix_bbox, dim3(kBoxBlocks), dim3(256), st, pb, P, L.part);
+    DEFTET_LAUNCH(k_face_stats, dim3(kBoxBlocks), dim3(256), st, xb, zb, F, L.fpart);
+    DEFTET_LAUNCH(k_pix_grid, dim3(1), dim3(64), st, L.part, L.fpart, L.grid, L.zAbsMax);
+#define RAST_TRY(call)                     \
+    do {                                   \
+        const int rc_ = (call);            \
+        if (rc_ != DEFTET_OK) return rc_;  \
+    } while (0)
+    const bool nearest = policy == DEFTET_RASTER_NEAREST;
+    const unsigned *perm = nullptr;
+    if (F > 0 && nearest) {
+        DEFTET_LAUNCH(k_face_depth_keys, dim3((F + 255) / 256), dim3(256), st, zb, F, L.pkey, L.pval);
+        RAST_TRY((prims::radix_sort<unsigned, unsigned>(L.pkey, L.skey, L.pval, L.perm, (size_t)F, 24, L.tmp, L.tmpBytes, st)));
+        perm = L.perm;
+    }
+    if (F > 0) {
+        DEFTET_LAUNCH(k_face_span, dim3((F + 255) / 256), dim3(256), st, xb, F, L.grid, eps, perm, L.span, L.isWide);
+        DEFTET_HIP(hipMemsetAsync(L.span + F, 0, 4, st));
+        DEFTET_HIP(hipMemsetAsync(L.isWide + F, 0, 4, st));
+        RAST_TRY((prims::scan<int, prims::Plus, true>(L.span, L.pairOff, (size_t)F + 1, 0, prims::Plus(), L.tmp, L.tmpBytes, st)));
+        RAST_TRY((prims::scan<int, prims::Plus, true>(L.isWide, L.wideOff, (size_t)F + 1, 0, prims::Plus(), L.tmp, L.tmpBytes, st)));
+        DEFTET_LAUNCH(k_face_pairs, dim3((unsigned)((L.cap + 255) / 256)), dim3(256), st, xb, F, L.grid, eps, L.pairOff, L.wideOff, L.pkey,
+                      L.pval, L.wide, L.nWide, L.cap, perm, L.wideBox);
+        // stable sort of the (tile, face) pairs by tile — of the pairs really produced (pairOff[F], known on the device
+        // only): the workgroups beyond that count find nothing to do (rounds 1-2 sorted the whole F * 16 capacity)
+        RAST_TRY((prims::radix_sort<unsigned, unsigned>(L.pkey, L.skey, L.pval, L.list, (size_t)L.cap, 13, L.tmp, L.tmpBytes, st,
+                                                        (const int *)(L.pairOff + F))));
+        DEFTET_LAUNCH(k_tile_starts, dim3((L.nTiles + 256) / 256), dim3(256), st, (const unsigned *)L.skey, (const int *)(L.pairOff + F), L.nTiles,
+                      L.tileStart);
+    } else {
+        DEFTET_HIP(hipMemsetAsync(L.tileStart, 0, ((size_t)L.nTiles + 2) * 4, st));
+        DEFTET_HIP(hipMemsetAsync(L.nWide, 0, 16, st));
+    }
+    DEFTET_LAUNCH(k_pix_keys, dim3((P + 255) / 256), dim3(256), st, pb, P, L.grid, L.xkey, L.xval);
+    RAST_TRY((prims::radix_sort<unsigned, unsigned>(L.xkey, L.xskey, L.xval, L.pixOrder, (size_t)P, 15, L.tmp, L.tmpBytes, st)));
+    DEFTET_LAUNCH(k_pix_chunks, dim3((L.nTiles + 2 + 255) / 256), dim3(256), st, (const unsigned *)L.xskey, P, L.nTiles, L.pixStart,
+                  L.chunkCount);
+    RAST_TRY((prims::scan<int, prims::Plus, true>(L.chunkCount, L.chunkStart, (size_t)L.nTiles + 2, 0, prims::Plus(), L.tmp, L.tmpBytes, st)));
+#undef RAST_TRY
+    {
+        const long long maxChunks = (long long)(P + 63) / 64 + L.nTiles + 1;     // every tile may end with a partial chunk
+        if (nearest)
+            DEFTET_LAUNCH(k_pix_raster<true>, dim3((unsigned)((maxChunks + 3) / 4)), dim3(256), st, pb, rb, zb, xb, P, L.nTiles, L.tileStart,
+                          (const int *)L.list, L.wide, L.nWide, F, knum, eps, L.hits, L.nhit, (const unsigned *)L.pixOrder,
+                          (const int *)L.pixStart, (const int *)L.chunkStart, (const unsigned *)L.zAbsMax, (const float4 *)L.wideBox);
+        else
+            DEFTET_LAUNCH(k_pix_raster<false>, dim3((unsigned)((maxChunks + 3) / 4)), dim3(256), st, pb, rb, zb, xb, P, L.nTiles, L.tileStart,
+                          (const int *)L.list, L.wide, L.nWide, F, knum, eps, L.hits, L.nhit, (const unsigned *)L.pixOrder,
+                          (const int *)L.pixStart, (const int *)L.chunkStart, (const unsigned *)L.zAbsMax, (const float4 *)L.wideBox);
+    }
+    return DEFTET_OK;
+}
+
 extern "C" size_t deftet_sparse_render_workspace_bytes(int B, int P, int F, int knum)
 {
     if (P < 0 || F < 0 || knum < 0) return 0;
@@ -1320,55 +1617,9 @@ extern "C" int deftet_sparse_render_fwd_policy_f32(const float *pix, const float
     for (int b = 0; b < B; ++b) {
         const float *pb = pix + (size_t)b * P * 2, *rb = rng + (size_t)b * P * 2;
         const float *zb = fz + (size_t)b * F * 3, *xb = fxy + (size_t)b * F * 6, *fb = feat + (size_t)b * F * 3 * D;
-        DEFTET_LAUNCH(k_pix_bbox, dim3(kBoxBlocks), dim3(256), st, pb, P, L.part);
-        DEFTET_LAUNCH(k_face_stats, dim3(kBoxBlocks), dim3(256), st, xb, zb, F, L.fpart);
-        DEFTET_LAUNCH(k_pix_grid, dim3(1), dim3(64), st, L.part, L.fpart, L.grid, L.zAbsMax);
-#define RAST_TRY(call)                     \
-    do {                                   \
-        const int rc_ = (call);            \
-        if (rc_ != DEFTET_OK) return rc_;  \
-    } while (0)
-        const bool nearest = policy == DEFTET_RASTER_NEAREST;
-        const unsigned *perm = nullptr;
-        if (F > 0 && nearest) {
-            DEFTET_LAUNCH(k_face_depth_keys, dim3((F + 255) / 256), dim3(256), st, zb, F, L.pkey, L.pval);
-            RAST_TRY((prims::radix_sort<unsigned, unsigned>(L.pkey, L.skey, L.pval, L.perm, (size_t)F, 24, L.tmp, L.tmpBytes, st)));
-            perm = L.perm;
-        }
-        if (F > 0) {
-            DEFTET_LAUNCH(k_face_span, dim3((F + 255) / 256), dim3(256), st, xb, F, L.grid, eps, perm, L.span, L.isWide);
-            DEFTET_HIP(hipMemsetAsync(L.span + F, 0, 4, st));
-            DEFTET_HIP(hipMemsetAsync(L.isWide + F, 0, 4, st));
-            RAST_TRY((prims::scan<int, prims::Plus, true>(L.span, L.pairOff, (size_t)F + 1, 0, prims::Plus(), L.tmp, L.tmpBytes, st)));
-            RAST_TRY((prims::scan<int, prims::Plus, true>(L.isWide, L.wideOff, (size_t)F + 1, 0, prims::Plus(), L.tmp, L.tmpBytes, st)));
-            DEFTET_LAUNCH(k_face_pairs, dim3((unsigned)((L.cap + 255) / 256)), dim3(256), st, xb, F, L.grid, eps, L.pairOff, L.wideOff, L.pkey,
-                          L.pval, L.wide, L.nWide, L.cap, perm, L.wideBox);
-            // stable sort of the (tile, face) pairs by tile — of the pairs really produced (pairOff[F], known on the device
-            // only): the workgroups beyond that count find nothing to do (rounds 1-2 sorted the whole F * 16 capacity)
-            RAST_TRY((prims::radix_sort<unsigned, unsigned>(L.pkey, L.skey, L.pval, L.list, (size_t)L.cap, 13, L.tmp, L.tmpBytes, st,
-                                                            (const int *)(L.pairOff + F))));
-            DEFTET_LAUNCH(k_tile_starts, dim3((L.nTiles + 256) / 256), dim3(256), st, (const unsigned *)L.skey, (const int *)(L.pairOff + F), L.nTiles,
-                          L.tileStart);
-        } else {
-            DEFTET_HIP(hipMemsetAsync(L.tileStart, 0, ((size_t)L.nTiles + 2) * 4, st));
-            DEFTET_HIP(hipMemsetAsync(L.nWide, 0, 16, st));
-        }
-        DEFTET_LAUNCH(k_pix_keys, dim3((P + 255) / 256), dim3(256), st, pb, P, L.grid, L.xkey, L.xval);
-        RAST_TRY((prims::radix_sort<unsigned, unsigned>(L.xkey, L.xskey, L.xval, L.pixOrder, (size_t)P, 15, L.tmp, L.tmpBytes, st)));
-        DEFTET_LAUNCH(k_pix_chunks, dim3((L.nTiles + 2 + 255) / 256), dim3(256), st, (const unsigned *)L.xskey, P, L.nTiles, L.pixStart,
-                      L.chunkCount);
-        RAST_TRY((prims::scan<int, prims::Plus, true>(L.chunkCount, L.chunkStart, (size_t)L.nTiles + 2, 0, prims::Plus(), L.tmp, L.tmpBytes, st)));
-#undef RAST_TRY
         {
-            const long long maxChunks = (long long)(P + 63) / 64 + L.nTiles + 1;     // every tile may end with a partial chunk
-            if (nearest)
-                DEFTET_LAUNCH(k_pix_raster<true>, dim3((unsigned)((maxChunks + 3) / 4)), dim3(256), st, pb, rb, zb, xb, P, L.nTiles, L.tileStart,
-                              (const int *)L.list, L.wide, L.nWide, F, knum, eps, L.hits, L.nhit, (const unsigned *)L.pixOrder,
-                              (const int *)L.pixStart, (const int *)L.chunkStart, (const unsigned *)L.zAbsMax, (const float4 *)L.wideBox);
-            else
-                DEFTET_LAUNCH(k_pix_raster<false>, dim3((unsigned)((maxChunks + 3) / 4)), dim3(256), st, pb, rb, zb, xb, P, L.nTiles, L.tileStart,
-                              (const int *)L.list, L.wide, L.nWide, F, knum, eps, L.hits, L.nhit, (const unsigned *)L.pixOrder,
-                              (const int *)L.pixStart, (const int *)L.chunkStart, (const unsigned *)L.zAbsMax, (const float4 *)L.wideBox);
+            const int rc = raster_hits(pb, rb, zb, xb, P, F, knum, eps, policy, L, st);
+            if (rc != DEFTET_OK) return rc;
         }
         DEFTET_LAUNCH(k_pix_emit, dim3((P + 3) / 4), dim3(256), st, L.hits, L.nhit, fb, P, D, knum,
                       out_feat + (size_t)b * P * knum * D, (long long *)out_face + (size_t)b * P * knum,
@@ -1383,6 +1634,33 @@ extern "C" int deftet_sparse_render_fwd_f32(const float *pix, const float *rng, 
 {
     return deftet_sparse_render_fwd_policy_f32(pix, rng, fz, fxy, feat, out_feat, out_face, out_w, B, P, F, D, knum, eps,
                                                DEFTET_RASTER_NEAREST, workspace, wsb, stream_);
+}
+
+// The gradients of one batch entry's faces from the per-slot layer gradients gout [n = P * knum, D]: the hit sort by face (its
+// first pass reads the face of every slot through `keys`; empty slots get the padding key F) and k_bwd_runs / k_bwd_sorted.
+// gxy and gfeat must be cleared (faces whose hits straddle blocks add into them).
+template <class KeyLoad>
+static int reduce_by_face(KeyLoad keys, const float *pix, const float *fxy, const float *feat, const float *gout, float *gxy,
+                          float *gfeat, long long n, int F, int D, int knum, float eps, const BwdLayout &L, hipStream_t st)
+{
+    {
+        const int rc = prims::radix_sort_from<unsigned, unsigned>(keys, L.skey, prims::IotaLoad(), L.sval, (size_t)n, L.bits, L.tmp,
+                                                                  L.tmpBytes, st);
+        if (rc != DEFTET_OK) return rc;
+    }
+#define RAST_BWD(DT)                                                                                                                  \
+    DEFTET_LAUNCH(k_bwd_sorted<DT>, dim3((unsigned)((n + kBwdWaves * 64 - 1) / (kBwdWaves * 64))), dim3(kBwdWaves * 64), st, pix, fxy, \
+                  feat, gout, (const unsigned *)L.skey, (const unsigned *)L.sval, n, F, D, knum, eps, gxy, gfeat)
+    // DEFTET_RAST_BWD=sorted: the round-5 kernel for D = 4 as well (A/B runs)
+    static const bool runs = [] { const char *e = getenv("DEFTET_RAST_BWD"); return !(e && e[0] == 's'); }();
+    const bool d4 = D == 4 && (((uintptr_t)feat | (uintptr_t)gout | (uintptr_t)gfeat) & 15) == 0;
+    if (d4 && runs)
+        DEFTET_LAUNCH(k_bwd_runs, dim3((unsigned)((n + kRunBlock - 1) / kRunBlock)), dim3(kRunWaves * 64), st, pix, fxy, feat, gout,
+                      (const unsigned *)L.skey, (const unsigned *)L.sval, n, F, knum, eps, gxy, gfeat);
+    else if (d4) RAST_BWD(4);
+    else RAST_BWD(0);
+#undef RAST_BWD
+    return DEFTET_OK;
 }
 
 extern "C" size_t deftet_sparse_render_bwd_workspace_bytes(int B, int P, int F, int knum)
@@ -1411,25 +1689,130 @@ extern "C" int deftet_sparse_render_bwd_f32(const float *pix, const float *fxy, 
     BwdLayout L = make_bwd_layout(P, F, knum, workspace, wsb);
     DEFTET_CHECK_ARG(L.bytes <= wsb, "backward workspace too small: need %zu bytes, got %zu", L.bytes, wsb);
     for (int b = 0; b < B; ++b) {
-        {
-            const int rc = prims::radix_sort_from<unsigned, unsigned>(FaceKeyLoad{(const long long *)face_idx + (size_t)b * n, F}, L.skey,
-                                                                      prims::IotaLoad(), L.sval, (size_t)n, L.bits, L.tmp, L.tmpBytes, st);
+        const int rc = reduce_by_face(FaceKeyLoad{(const long long *)face_idx + (size_t)b * n, F}, pix + (size_t)b * P * 2,
+                                      fxy + (size_t)b * F * 6, feat + (size_t)b * F * 3 * D, gout + (size_t)b * n * D,
+                                      gxy + (size_t)b * F * 6, gfeat + (size_t)b * F * 3 * D, n, F, D, knum, eps, L, st);
+        if (rc != DEFTET_OK) return rc;
+    }
+    return DEFTET_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Fused rasterize-and-composite (240).  Nothing of size P * knum * D is written by the forward; the backward's layer gradients
+// (P * knum * D floats of one batch entry) live in its workspace only.
+static int composite_sizes_ok(int B, int P, int F, int D, int knum, int depth_channel)
+{
+    DEFTET_CHECK_ARG(B >= 0 && P >= 0 && F >= 0 && D >= 0 && knum >= 0, "negative size");
+    DEFTET_CHECK_ARG(D >= (depth_channel ? 3 : 2), "D = %d feature channels: need opacity and colour%s", D,
+                     depth_channel ? " after the depth channel (D >= 3)" : " (D >= 2)");
+    DEFTET_CHECK_ARG((long long)P * knum < 2147483647LL && (long long)F * kMaxTiles < 2147483647LL, "P*knum or F too large");
+    return DEFTET_OK;
+}
+
+extern "C" size_t deftet_sparse_render_composite_workspace_bytes(int B, int P, int F, int D, int knum)
+{
+    (void)D;
+    if (P < 0 || F < 0 || knum < 0) return 0;
+    return make_layout(P, F, knum, nullptr, 0).bytes;      // shapes are processed one after another
+}
+
+extern "C" int deftet_sparse_render_composite_fwd_f32(const float *pix, const float *rng, const float *fz, const float *fxy,
+                                                      const float *feat, int B, int P, int F, int D, int knum, float eps, int policy,
+                                                      int depth_channel, float background, float far_depth, float *out_colour,
+                                                      float *out_coverage, float *out_depth, int32_t *out_face, void *workspace,
+                                                      size_t wsb, void *stream_)
+{
+    {
+        const int rc = composite_sizes_ok(B, P, F, D, knum, depth_channel);
+        if (rc != DEFTET_OK) return rc;
+    }
+    DEFTET_CHECK_ARG(policy == DEFTET_RASTER_NEAREST || policy == DEFTET_RASTER_FIRST, "unknown saturation policy %d", policy);
+    if (B == 0 || P == 0) return DEFTET_OK;
+    DEFTET_CHECK_ARG(pix && rng && out_colour && out_coverage && (!depth_channel || out_depth) && (knum == 0 || out_face) &&
+                         (F == 0 || (fz && fxy && feat)),
+                     "null pointer");
+    DEFTET_CHECK_ARG(((uintptr_t)fxy & 7) == 0, "face_vertices_image must be 8-byte aligned");
+    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0, "workspace null or misaligned");
+    Layout L = make_layout(P, F, knum, workspace, wsb);
+    DEFTET_CHECK_ARG(L.bytes <= wsb, "workspace too small: need %zu bytes, got %zu", L.bytes, wsb);
+    hipStream_t st = as_stream(stream_);
+    const int Dc = D - (depth_channel ? 2 : 1);
+    for (int b = 0; b < B; ++b) {
+        const float *pb = pix + (size_t)b * P * 2, *rb = rng + (size_t)b * P * 2;
+        const float *zb = fz + (size_t)b * F * 3, *xb = fxy + (size_t)b * F * 6, *fb = feat + (size_t)b * F * 3 * D;
+        if (knum > 0) {
+            const int rc = raster_hits(pb, rb, zb, xb, P, F, knum, eps, policy, L, st);
             if (rc != DEFTET_OK) return rc;
+        } else {
+            DEFTET_HIP(hipMemsetAsync(L.nhit, 0, (size_t)P * sizeof(int), st));       // no slots: every pixel is background
         }
-#define RAST_BWD(DT)                                                                                                                  \
-    DEFTET_LAUNCH(k_bwd_sorted<DT>, dim3((unsigned)((n + kBwdWaves * 64 - 1) / (kBwdWaves * 64))), dim3(kBwdWaves * 64), st, pix + (size_t)b * P * 2, fxy + (size_t)b * F * 6, \
-                  feat + (size_t)b * F * 3 * D, gout + (size_t)b * n * D, (const unsigned *)L.skey, (const unsigned *)L.sval, n, F, D,   \
-                  knum, eps, gxy + (size_t)b * F * 6, gfeat + (size_t)b * F * 3 * D)
-        // DEFTET_RAST_BWD=sorted: the round-5 kernel for D = 4 as well (A/B runs)
-        static const bool runs = [] { const char *e = getenv("DEFTET_RAST_BWD"); return !(e && e[0] == 's'); }();
-        const bool d4 = D == 4 && (((uintptr_t)feat | (uintptr_t)gout | (uintptr_t)gfeat) & 15) == 0;
-        if (d4 && runs)
-            DEFTET_LAUNCH(k_bwd_runs, dim3((unsigned)((n + kRunBlock - 1) / kRunBlock)), dim3(kRunWaves * 64), st, pix + (size_t)b * P * 2,
-                          fxy + (size_t)b * F * 6, feat + (size_t)b * F * 3 * D, gout + (size_t)b * n * D, (const unsigned *)L.skey,
-                          (const unsigned *)L.sval, n, F, knum, eps, gxy + (size_t)b * F * 6, gfeat + (size_t)b * F * 3 * D);
-        else if (d4) RAST_BWD(4);
-        else RAST_BWD(0);
-#undef RAST_BWD
+        DEFTET_LAUNCH(k_pix_composite, dim3((P + 3) / 4), dim3(256), st, L.hits, L.nhit, fb, P, D, knum, depth_channel ? 1 : 0,
+                      background, far_depth, out_colour + (size_t)b * P * Dc, out_coverage + (size_t)b * P,
+                      depth_channel ? out_depth + (size_t)b * P : nullptr, out_face + (size_t)b * P * knum);
+    }
+    return DEFTET_OK;
+}
+
+struct CompositeBwdLayout {
+    size_t bytes;
+    float *gout;
+    BwdLayout sort;
+};
+
+static CompositeBwdLayout make_composite_bwd_layout(int P, int F, int D, int knum, void *ws, size_t wsb)
+{
+    CompositeBwdLayout L{};
+    Arena A(ws, wsb);
+    L.gout = A.take<float>((size_t)P * knum * D + 4);
+    char *rest = ws ? static_cast<char *>(ws) + align_up(A.off, 256) : nullptr;
+    const size_t off = align_up(A.off, 256);
+    L.sort = make_bwd_layout(P, F, knum, rest, wsb > off ? wsb - off : 0);
+    L.bytes = off + L.sort.bytes;
+    return L;
+}
+
+extern "C" size_t deftet_sparse_render_composite_bwd_workspace_bytes(int B, int P, int F, int D, int knum)
+{
+    (void)B;
+    if (P < 0 || F < 0 || D < 0 || knum < 0 || (long long)P * knum >= 2147483647LL) return 0;
+    return make_composite_bwd_layout(P, F, D, knum, nullptr, 0).bytes;     // shapes are processed one after another
+}
+
+extern "C" int deftet_sparse_render_composite_bwd_f32(const float *pix, const float *fxy, const float *feat, const int32_t *face,
+                                                      const float *g_colour, const float *g_coverage, const float *g_depth, int B,
+                                                      int P, int F, int D, int knum, float eps, int depth_channel, float background,
+                                                      float far_depth, float *gxy, float *gfeat, void *workspace, size_t wsb,
+                                                      void *stream_)
+{
+    {
+        const int rc = composite_sizes_ok(B, P, F, D, knum, depth_channel);
+        if (rc != DEFTET_OK) return rc;
+    }
+    if (B == 0 || F == 0) return DEFTET_OK;
+    DEFTET_CHECK_ARG(fxy && feat && gxy && gfeat, "null pointer");
+    const long long n = (long long)P * knum;
+    if (n > 0) {
+        DEFTET_CHECK_ARG(pix && face, "null pointer");
+        DEFTET_CHECK_ARG(((uintptr_t)fxy & 7) == 0 && ((uintptr_t)pix & 7) == 0, "face_vertices_image and pixel_coords must be 8-byte aligned");
+        DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0, "backward workspace null or misaligned");
+    }
+    CompositeBwdLayout L = make_composite_bwd_layout(P, F, D, knum, n > 0 ? workspace : nullptr, wsb);
+    DEFTET_CHECK_ARG(n == 0 || L.bytes <= wsb, "backward workspace too small: need %zu bytes, got %zu", L.bytes, wsb);
+    hipStream_t st = as_stream(stream_);
+    DEFTET_HIP(hipMemsetAsync(gxy, 0, (size_t)B * F * 6 * sizeof(float), st));
+    DEFTET_HIP(hipMemsetAsync(gfeat, 0, (size_t)B * F * 3 * D * sizeof(float), st));
+    if (n == 0 || (!g_colour && !g_coverage && !(depth_channel && g_depth))) return DEFTET_OK;
+    const int Dc = D - (depth_channel ? 2 : 1);
+    for (int b = 0; b < B; ++b) {
+        const float *pb = pix + (size_t)b * P * 2, *xb = fxy + (size_t)b * F * 6, *fb = feat + (size_t)b * F * 3 * D;
+        const int32_t *face_b = face + (size_t)b * n;
+        DEFTET_LAUNCH(k_pix_composite_bwd, dim3((P + 3) / 4), dim3(256), st, pb, xb, fb, (const int *)face_b,
+                      g_colour ? g_colour + (size_t)b * P * Dc : nullptr, g_coverage ? g_coverage + (size_t)b * P : nullptr,
+                      (depth_channel && g_depth) ? g_depth + (size_t)b * P : nullptr, P, F, D, knum, eps, depth_channel ? 1 : 0,
+                      background, far_depth, L.gout);
+        const int rc = reduce_by_face(FaceKeyLoad32{(const int *)face_b, F}, pb, xb, fb, L.gout, gxy + (size_t)b * F * 6,
+                                      gfeat + (size_t)b * F * 3 * D, n, F, D, knum, eps, L.sort, st);
+        if (rc != DEFTET_OK) return rc;
     }
     return DEFTET_OK;
 }

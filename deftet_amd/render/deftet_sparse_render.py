@@ -70,6 +70,82 @@ class _SparseRender(Function):
         return None, None, None, gxy, gff, None, None, None
 
 
+class _SparseRenderComposite(Function):
+    @staticmethod
+    def forward(ctx, pixel_coords, render_ranges, face_vertices_z, face_vertices_image, face_features, knum, eps, policy, depth,
+                background, far_depth):
+        _lib.require_gpu(pixel_coords, render_ranges, face_vertices_z, face_vertices_image, face_features)
+        lib = _lib.load()
+        pix, rng = _f32c(pixel_coords), _f32c(render_ranges)
+        fz, fxy, ff = _f32c(face_vertices_z), _f32c(face_vertices_image), _f32c(face_features)
+        B, P = pix.shape[0], pix.shape[1]
+        F, D = fz.shape[1], ff.shape[3]
+        if fxy.shape != (B, F, 3, 2) or ff.shape[:3] != (B, F, 3) or rng.shape != (B, P, 2):
+            raise RuntimeError("deftet_sparse_render_composite: inconsistent shapes")
+        if D < (3 if depth else 2):
+            raise RuntimeError("deftet_sparse_render_composite: D = %d feature channels, need at least %d (%s)"
+                               % (D, 3 if depth else 2, "depth, opacity, colour" if depth else "opacity, colour"))
+        dev = pix.device
+        Dc = D - (2 if depth else 1)
+        colour = torch.empty(B, P, Dc, device=dev, dtype=torch.float32)
+        coverage = torch.empty(B, P, 1, device=dev, dtype=torch.float32)
+        dep = torch.empty(B, P, 1, device=dev, dtype=torch.float32) if depth else None
+        face = torch.empty(B, P, knum, device=dev, dtype=torch.int32)
+        with _lib.on_device(dev):
+            ws = _lib.workspace(dev, lib.deftet_sparse_render_composite_workspace_bytes(B, P, F, D, knum))
+            _lib.check(lib.deftet_sparse_render_composite_fwd_f32(
+                _lib.ptr(pix), _lib.ptr(rng), _lib.ptr(fz), _lib.ptr(fxy), _lib.ptr(ff), B, P, F, D, knum, eps, int(policy), int(depth),
+                background, far_depth, _lib.ptr(colour), _lib.ptr(coverage), _lib.ptr(dep), _lib.ptr(face), _lib.ptr(ws), ws.numel(),
+                _lib.current_stream(dev)), "deftet_sparse_render_composite_fwd_f32")
+        ctx.save_for_backward(pix, fxy, ff, face)              # the inputs and the int32 faces: nothing of size P * knum * D
+        ctx.eps, ctx.depth, ctx.background, ctx.far_depth = eps, depth, background, far_depth
+        ctx.mark_non_differentiable(face)
+        ctx.set_materialize_grads(False)
+        return colour, coverage, dep, face
+
+    @staticmethod
+    def backward(ctx, g_colour, g_coverage, g_depth, _g_face):
+        pix, fxy, ff, face = ctx.saved_tensors
+        if not ctx.depth:
+            g_depth = None
+        if g_colour is None and g_coverage is None and g_depth is None:
+            return (None,) * 11
+        lib = _lib.load()
+        B, P, knum = face.shape
+        F, D = fxy.shape[1], ff.shape[3]
+        gc, gv, gd = (None if g is None else _f32c(g) for g in (g_colour, g_coverage, g_depth))
+        gxy = torch.empty_like(fxy)
+        gff = torch.empty_like(ff)
+        dev = pix.device
+        with _lib.on_device(dev):
+            ws = _lib.workspace(dev, lib.deftet_sparse_render_composite_bwd_workspace_bytes(B, P, F, D, knum))
+            _lib.check(lib.deftet_sparse_render_composite_bwd_f32(
+                _lib.ptr(pix), _lib.ptr(fxy), _lib.ptr(ff), _lib.ptr(face), _lib.ptr(gc), _lib.ptr(gv), _lib.ptr(gd), B, P, F, D, knum,
+                ctx.eps, int(ctx.depth), ctx.background, ctx.far_depth, _lib.ptr(gxy), _lib.ptr(gff), _lib.ptr(ws), ws.numel(),
+                _lib.current_stream(dev)), "deftet_sparse_render_composite_bwd_f32")
+        return None, None, None, gxy, gff, None, None, None, None, None, None
+
+
+def deftet_sparse_render_composite(pixel_coords, render_ranges, face_vertices_z, face_vertices_image, face_features, knum=300,
+                                   eps=1e-8, policy=NEAREST, depth=False, background=1.0, far_depth=-6.0):
+    """Rasterize and composite in one operator: (colour [B,P,Dc], coverage [B,P,1], depth [B,P,1] or None, face int32 [B,P,knum])
+    equal up to fp32 rounding to
+
+        layers, face64 = deftet_sparse_render(..., knum=knum, eps=eps, policy=policy)
+        alpha_composite(layers[..., 1:], layers[..., :1], background, far_depth) if depth else alpha_composite(layers, None, ...)
+
+    without the [B,P,knum,D] layer stack: opacity is feature channel 0 (1 with depth=True, channel 0 then being the layer depth),
+    clamped as alpha_composite clamps it, and the colour is the remaining channels (Dc = D - 1, or D - 2 with depth).  `face`
+    equals face64 (same faces, same nearest-first order; -1 = empty) and is not differentiable.  Gradients flow to
+    face_vertices_image and face_features.  `policy` must be NEAREST or FIRST (no saturation probe here)."""
+    if policy not in (NEAREST, FIRST):
+        raise ValueError("deftet_sparse_render_composite: policy must be NEAREST (0) or FIRST (1), got %r" % (policy,))
+    colour, coverage, dep, face = _SparseRenderComposite.apply(pixel_coords, render_ranges, face_vertices_z, face_vertices_image,
+                                                               face_features, int(knum), float(eps), int(policy), bool(depth),
+                                                               float(background), float(far_depth))
+    return colour, coverage, dep, face
+
+
 _warned_saturation = False
 _default_calls = 0
 

@@ -42,7 +42,8 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
-/* 230: the indexed point-in-tet query — deftet_point_in_tet_indexed_f32, _indexed_scan_f32, _indexed_bwd_to_vertices_f32 take
+/* 240: the fused rasterize-and-composite operator — deftet_sparse_render_composite_fwd_f32 / _bwd_f32 and their workspace sizes.
+ * 230: the indexed point-in-tet query — deftet_point_in_tet_indexed_f32, _indexed_scan_f32, _indexed_bwd_to_vertices_f32 take
  *      vertices + a tet index list instead of the gathered [B,T,4,3] tensor (outputs bit-identical to the dense entry points).
  * 221: round 6, second half — 8-byte hit records, deftet_point_in_tet_bwd_to_vertices_f32, deftet_put_host_ints.
  * 220: round 6 — deftet_tet_order_coherence_f32 (what the traversal-order decision is made on); the rasterizer bins into at most
@@ -553,6 +554,30 @@ int deftet_sparse_render_bwd_f32(const float *pixel_bxpx2, const float *face_xy_
                                  float *grad_face_xy, float *grad_face_feat,
                                  int n_batch, int n_pixel, int n_face, int n_feat, int knum, float eps,
                                  void *workspace, size_t workspace_bytes, void *stream);
+
+/* Fused rasterize-and-composite (240): the same faces in the same order as deftet_sparse_render_fwd_policy_f32, composited front
+ * to back where they are made — alpha_composite (deftet_amd/render/compositing.py) of the layer stack, which is never written.
+ * Opacity is feature channel 0, or 1 with depth_channel != 0 (channel 0 is then the layer depth), clamped to [1e-10, 1 - 1e-10];
+ * the colour is the remaining D - 1 (D - 2) channels.  Empty slots are zero layers at opacity 1e-10.  Outputs: colour
+ * [B,P,Dc] over `background`, coverage [B,P], depth [B,P] over `far_depth` (only with depth_channel; NULL otherwise) and the
+ * ranked faces as int32 [B,P,knum] (-1 = empty), which the backward reads.  D >= 2 (>= 3 with depth_channel). */
+size_t deftet_sparse_render_composite_workspace_bytes(int n_batch, int n_pixel, int n_face, int n_feat, int knum);
+int deftet_sparse_render_composite_fwd_f32(const float *pixel_bxpx2, const float *range_bxpx2,
+                                           const float *face_z_bxfx3, const float *face_xy_bxfx3x2,
+                                           const float *face_feat_bxfx3xd, int n_batch, int n_pixel, int n_face, int n_feat,
+                                           int knum, float eps, int policy, int depth_channel, float background, float far_depth,
+                                           float *out_colour_bxpxc, float *out_coverage_bxp, float *out_depth_bxp,
+                                           int32_t *out_face_bxpxk, void *workspace, size_t workspace_bytes, void *stream);
+/* backward: gradients to face_xy [B,F,3,2] and face_feat [B,F,3,D] (both fully overwritten), none to z.  Any of the three output
+ * gradients may be NULL (absent = zero).  No division by 1 - alpha: opacities of exactly 1 are fine. */
+size_t deftet_sparse_render_composite_bwd_workspace_bytes(int n_batch, int n_pixel, int n_face, int n_feat, int knum);
+int deftet_sparse_render_composite_bwd_f32(const float *pixel_bxpx2, const float *face_xy_bxfx3x2,
+                                           const float *face_feat_bxfx3xd, const int32_t *face_bxpxk,
+                                           const float *grad_colour_bxpxc, const float *grad_coverage_bxp,
+                                           const float *grad_depth_bxp, int n_batch, int n_pixel, int n_face, int n_feat,
+                                           int knum, float eps, int depth_channel, float background, float far_depth,
+                                           float *grad_face_xy, float *grad_face_feat, void *workspace, size_t workspace_bytes,
+                                           void *stream);
 
 #ifdef __cplusplus
 }
