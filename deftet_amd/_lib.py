@@ -118,6 +118,11 @@ SIGNATURES = {
     "deftet_sparse_render_composite_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "deftet_sparse_render_composite_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _f, _f, _vp, _vp,
                                                      _vp, _sz, _vp]),
+    "deftet_vertex_adjacency_workspace_bytes": (_sz, [_i, _i]),
+    "deftet_vertex_adjacency_csr_i32": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "deftet_vertex_laplacian_workspace_bytes": (_sz, [_i, _i]),
+    "deftet_vertex_laplacian_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "deftet_vertex_laplacian_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
 }
 
 _lock = threading.Lock()

@@ -1408,6 +1408,157 @@ def tet_gather_bwd(grad_tet_bxtx4x3, csr, n_vertex, out=None):
     return gp
 
 
+# --------------------------------------------------------------------------------- vertex Laplacian
+VLAP_VALUES, VLAP_ROW_DIVISOR = 0, 1               # include/deftet_hip.h DEFTET_VLAP_*
+VLAP_NONE, VLAP_SHAPE = 0, 1
+_VADJ_ROW_COL, _VADJ_ROW_INPUT = 0, 1
+_VLAP_REDUCTIONS = {"none": VLAP_NONE, "shape": VLAP_SHAPE}
+
+
+class VertexAdjacency:
+    """A sparse vertex adjacency M [V,V] for vertex_laplacian, built once per topology and reused (like TetTopology): the CSR
+    (offsets, cols, vals) and its transpose (t_offsets, t_rows, t_vals), int32 / f32 on the GPU.  `weighting` is VLAP_VALUES
+    (nei = Σ v_ij x_j) or VLAP_ROW_DIVISOR (nei = (Σ_j x_j) / row_weights[i]).  The object is a snapshot: it holds its own
+    copies and does not follow later changes of the tensors it was built from — build a new one when the topology changes."""
+
+    def __init__(self, n_vertex, weighting, offsets, cols, vals, t_offsets, t_rows, t_vals, row_weights=None):
+        self.n_vertex, self.weighting = int(n_vertex), int(weighting)
+        self.offsets, self.cols, self.vals = offsets, cols, vals
+        self.t_offsets, self.t_rows, self.t_vals = t_offsets, t_rows, t_vals
+        self.row_weights = row_weights
+        self.nnz = int(cols.numel())
+        self.device = offsets.device
+
+    @classmethod
+    def _build(cls, rows, cols, values, n_vertex, order, weighting, row_weights=None):
+        _lib.require_gpu(rows, cols, values, row_weights)
+        lib = _lib.load()
+        V, nnz, dev = int(n_vertex), int(rows.numel()), rows.device
+        if rows.dtype not in (torch.int32, torch.int64) or cols.dtype != rows.dtype or cols.numel() != nnz:
+            raise RuntimeError("VertexAdjacency: rows and cols must be int32 or int64 of one dtype and one length")
+        rows, cols = rows.contiguous(), cols.contiguous()
+        if values is not None:
+            values = values.to(torch.float32).contiguous()
+            if values.numel() != nnz:
+                raise RuntimeError("VertexAdjacency: one value per entry expected")
+        want_vals = weighting == VLAP_VALUES
+        offsets = torch.empty(V + 1, device=dev, dtype=torch.int32)
+        t_offsets = torch.empty(V + 1, device=dev, dtype=torch.int32)
+        out_cols = torch.empty(nnz, device=dev, dtype=torch.int32)
+        t_rows = torch.empty(nnz, device=dev, dtype=torch.int32)
+        vals = torch.empty(nnz, device=dev, dtype=torch.float32) if want_vals else None
+        t_vals = torch.empty(nnz, device=dev, dtype=torch.float32) if want_vals else None
+        bad = torch.empty(1, device=dev, dtype=torch.int32)
+        with _lib.on_device(dev):
+            ws = _lib.workspace(dev, lib.deftet_vertex_adjacency_workspace_bytes(nnz, V))
+            _lib.check(lib.deftet_vertex_adjacency_csr_i32(_lib.ptr(rows), _lib.ptr(cols), rows.element_size(), _lib.ptr(values), nnz, V,
+                                                           order, _lib.ptr(offsets), _lib.ptr(out_cols), _lib.ptr(vals),
+                                                           _lib.ptr(t_offsets), _lib.ptr(t_rows), _lib.ptr(t_vals), _lib.ptr(bad),
+                                                           _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
+                       "deftet_vertex_adjacency_csr_i32")
+        if int(bad.item()):                                 # (the one host sync: build time only)
+            raise RuntimeError("VertexAdjacency: vertex index out of range [0, %d)" % V)
+        return cls(V, weighting, offsets, out_cols, vals, t_offsets, t_rows, t_vals, row_weights)
+
+    @classmethod
+    def from_sparse(cls, adj):
+        """From a torch sparse COO [V,V] on the GPU, coalesced or not (duplicates are summed, as torch.sparse.mm does): e.g.
+        Tet_point_adj().run(V, tets, normalize=True) moved to the GPU, or the reference's MySparse.construct()."""
+        if not adj.is_sparse or adj.dim() != 2 or adj.shape[0] != adj.shape[1]:
+            raise RuntimeError("VertexAdjacency.from_sparse: a sparse COO [V,V] tensor expected")
+        idx = adj._indices()                                # (uncoalesced input: its entries as stored)
+        return cls._build(idx[0], idx[1], adj._values(), adj.shape[0], _VADJ_ROW_COL, VLAP_VALUES)
+
+    @classmethod
+    def from_tets(cls, tet_tx4, n_vertex, normalize=True):
+        """The vertex adjacency of a tet mesh (tet_point_adj): ones, or D⁻¹A with `normalize` — the matrix
+        Tet_point_adj().run(n_vertex, tets, normalize) gives, without going through torch sparse."""
+        _lib.require_gpu(tet_tx4)
+        V = int(n_vertex)
+        pairs = tet_point_adj(tet_tx4, V, tet_tx4.device)               # sorted unique directed pairs, int32 [n,2]
+        rows, cols = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
+        vals = None
+        if normalize:
+            # 1/deg(row) rounded once from fp64, as utils/lib/tet_point_adj/interface.py does on the host
+            deg = torch.bincount(rows.long(), minlength=V).double()
+            vals = (1.0 / deg)[rows.long()].float()
+        return cls._build(rows, cols, vals, V, _VADJ_ROW_COL, VLAP_VALUES)
+
+    @classmethod
+    def from_table(cls, point_adj_idx_pxm, point_adj_weights_px1, index_base=0):
+        """From a padded neighbour table [P,m] and row weights [P,1] (Deftet.get_featlap): index_base=0 for this repository's
+        table (point_adj_idx: ascending neighbours, -1 padding), index_base=1 for the reference's stored table (+1, 0 padding).
+        Each row sums its neighbours in table order, then divides by its weight."""
+        _lib.require_gpu(point_adj_idx_pxm, point_adj_weights_px1)
+        if index_base not in (0, 1):
+            raise ValueError("from_table: index_base must be 0 or 1")
+        table = point_adj_idx_pxm
+        if table.dim() != 2:
+            raise RuntimeError("from_table: a [P,m] table expected")
+        P, m = table.shape
+        w = point_adj_weights_px1.reshape(-1).to(torch.float32).contiguous().clone()
+        if w.numel() != P:
+            raise RuntimeError("from_table: one weight per table row expected")
+        t = table.long() - index_base
+        keep = t != -1                                      # the padding; anything else outside [0, P) raises in the build
+        rows = torch.arange(P, device=t.device).unsqueeze(1).expand(P, m)[keep]      # (row-major: table order)
+        return cls._build(rows, t[keep], None, P, _VADJ_ROW_INPUT, VLAP_ROW_DIVISOR, w)
+
+
+class _VertexLaplacian(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, adjacency, reduction):
+        ctx.set_materialize_grads(False)
+        lib = _lib.load()
+        adj = adjacency
+        B, V, C = x.shape
+        dev = x.device
+        r = torch.empty(B, V, C, device=dev, dtype=torch.float32)
+        out = torch.empty((B,) if reduction == VLAP_SHAPE else (B, V, C), device=dev, dtype=torch.float32)
+        with _lib.on_device(dev):
+            ws = _lib.workspace(dev, lib.deftet_vertex_laplacian_workspace_bytes(B, V)) if reduction == VLAP_SHAPE else None
+            _lib.check(lib.deftet_vertex_laplacian_fwd_f32(_lib.ptr(x), _lib.ptr(adj.offsets), _lib.ptr(adj.cols), _lib.ptr(adj.vals),
+                                                           _lib.ptr(adj.row_weights), adj.weighting, reduction, B, V, C, adj.nnz,
+                                                           _lib.ptr(r), _lib.ptr(out), _lib.ptr(ws), ws.numel() if ws is not None else 0,
+                                                           _lib.current_stream(dev)), "deftet_vertex_laplacian_fwd_f32")
+        ctx.save_for_backward(r)
+        ctx.adj, ctx.reduction = adj, reduction
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if grad_out is None or not ctx.needs_input_grad[0]:
+            return None, None, None
+        (r,) = ctx.saved_tensors
+        adj, reduction = ctx.adj, ctx.reduction
+        lib = _lib.load()
+        g = _f32c(grad_out)
+        B, V, C = r.shape
+        dx = torch.empty_like(r)
+        with _lib.on_device(r.device):
+            _lib.check(lib.deftet_vertex_laplacian_bwd_f32(_lib.ptr(r), _lib.ptr(g), _lib.ptr(adj.t_offsets), _lib.ptr(adj.t_rows),
+                                                           _lib.ptr(adj.t_vals), _lib.ptr(adj.row_weights), adj.weighting, reduction,
+                                                           B, V, C, adj.nnz, _lib.ptr(dx), _lib.current_stream(r.device)),
+                       "deftet_vertex_laplacian_bwd_f32")
+        return dx, None, None
+
+
+def vertex_laplacian(x, adjacency, reduction="shape"):
+    """r = M·x − x over a VertexAdjacency M, x f32 [B,V,C] with 1 <= C <= 16 (differentiable w.r.t. x); returns
+    Σ_{i,c} r² per shape, f32 [B] (reduction="shape": DefTet.laplacian_sparse) or r², f32 [B,V,C] (reduction="none":
+    Deftet.get_featlap).  No host synchronisation: the call can be captured in a graph."""
+    _lib.require_gpu(x)
+    if not isinstance(adjacency, VertexAdjacency):
+        raise TypeError("vertex_laplacian: a hip_ops.VertexAdjacency expected, got %s" % type(adjacency).__name__)
+    if reduction not in _VLAP_REDUCTIONS:
+        raise ValueError("vertex_laplacian: reduction must be 'shape' or 'none', got %r" % (reduction,))
+    if x.dim() != 3 or x.shape[1] != adjacency.n_vertex:
+        raise RuntimeError("vertex_laplacian: x [B,%d,C] expected, got %s" % (adjacency.n_vertex, tuple(x.shape)))
+    if x.device != adjacency.device:
+        raise RuntimeError("vertex_laplacian: x is on %s, the adjacency on %s" % (x.device, adjacency.device))
+    return _VertexLaplacian.apply(_f32c(x), adjacency, _VLAP_REDUCTIONS[reduction])
+
+
 # --------------------------------------------------------------------------------- A7 / A11
 def boundary_index(tet_face_fx3, tet_idx_fx2, occ_bxn, mode=1):
     """list of B int64 [Fb_i,3] tensors — DefTet.get_boundary_index (mode 1) /

@@ -14,7 +14,9 @@
     forward_surface_align / forward           (:51-184)   composed from the operators above plus the surface
                                                              terms in deftet_amd/surface_losses.py (A8/A9/A10); same
                                                              arguments, same tuple order as the reference
-    laplacian_sparse                          (:340-343)  torch.sparse.mm (vendor SpMM)
+    laplacian_sparse                          (:340-343)  adj a hip_ops.VertexAdjacency -> deftet_vertex_laplacian_*_f32
+                                                             (fused, atomic-free backward); adj a torch sparse tensor ->
+                                                             torch.sparse.mm (vendor SpMM), unchanged
 """
 import collections
 import threading
@@ -60,9 +62,25 @@ class TetTopology:
         self.n_vertex = int(n_vertex)
         self.csr = hip_ops.tet_vertex_csr(self.tet_idx, self.n_vertex)     # (raises on an index outside [0, n_vertex))
         self.tet_idx32 = self.tet_idx.to(torch.int32).contiguous()         # what the indexed query reads (hip_ops.point_in_tet_indexed)
+        self._vertex_adjacency = {}                                         # normalize -> hip_ops.VertexAdjacency (vertex_adjacency)
 
     def gather(self, vertice_pos):
         return _TetGather.apply(vertice_pos, self.tet_idx, self.csr)
+
+    def vertex_adjacency(self, normalize=True):
+        """hip_ops.VertexAdjacency of this tet list (D⁻¹A with `normalize`, else A), for DefTet.laplacian_sparse; built on the
+        first call per `normalize` and kept."""
+        key = bool(normalize)
+        adj = self._vertex_adjacency.get(key)
+        if adj is None:
+            tets = self.tet_idx32
+            if tets.dim() == 3:
+                if tets.shape[0] != 1:
+                    raise RuntimeError("TetTopology.vertex_adjacency: the shapes of this batch have different tet lists")
+                tets = tets[0]
+            adj = hip_ops.VertexAdjacency.from_tets(tets, self.n_vertex, normalize=key)
+            self._vertex_adjacency[key] = adj
+        return adj
 
 
 # Cache of the incidence CSR, per device and index shape, at MODULE level: nn.DataParallel (train_multigpu.py:138)
@@ -259,7 +277,11 @@ class DefTet(nn.Module):
 
     def laplacian_sparse(self, offset, adj):
         """sum over vertices and coordinates of (mean of the neighbours' offsets - own offset)^2, per shape;
-        adj = row-normalised vertex adjacency [V,V] (c_tet_to_adj_sparse(normalize=True))."""
+        adj = row-normalised vertex adjacency [V,V] (c_tet_to_adj_sparse(normalize=True)).  A hip_ops.VertexAdjacency adj
+        (e.g. TetTopology.vertex_adjacency()) takes the fused HIP operator, hip_ops.vertex_laplacian; a torch sparse adj
+        takes torch.sparse.mm as before."""
+        if isinstance(adj, hip_ops.VertexAdjacency):
+            return hip_ops.vertex_laplacian(offset, adj, reduction="shape")
         n_shape, n_vertex, width = offset.shape
         flat = offset.permute(1, 0, 2).reshape(n_vertex, n_shape * width)
         nei = torch.sparse.mm(adj, flat).reshape(n_vertex, n_shape, width).permute(1, 0, 2)

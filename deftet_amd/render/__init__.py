@@ -1,3 +1,4 @@
 from .deftet_sparse_render import deftet_sparse_render, deftet_sparse_render_composite  # noqa: F401
 from .compositing import alpha_composite  # noqa: F401
 from .camera import perspective, face_attributes, render_mesh_color  # noqa: F401
+from .laplacian import get_featlap  # noqa: F401

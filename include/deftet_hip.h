@@ -42,7 +42,9 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
-/* 240: the fused rasterize-and-composite operator — deftet_sparse_render_composite_fwd_f32 / _bwd_f32 and their workspace sizes.
+/* 250: the vertex Laplacian regulariser — deftet_vertex_adjacency_csr_i32 (an adjacency and its transpose as CSRs) with its
+ *      workspace size, deftet_vertex_laplacian_fwd_f32 / _bwd_f32 and the forward's workspace size.
+ * 240: the fused rasterize-and-composite operator — deftet_sparse_render_composite_fwd_f32 / _bwd_f32 and their workspace sizes.
  * 230: the indexed point-in-tet query — deftet_point_in_tet_indexed_f32, _indexed_scan_f32, _indexed_bwd_to_vertices_f32 take
  *      vertices + a tet index list instead of the gathered [B,T,4,3] tensor (outputs bit-identical to the dense entry points).
  * 221: round 6, second half — 8-byte hit records, deftet_point_in_tet_bwd_to_vertices_f32, deftet_put_host_ints.
@@ -578,6 +580,46 @@ int deftet_sparse_render_composite_bwd_f32(const float *pixel_bxpx2, const float
                                            int knum, float eps, int depth_channel, float background, float far_depth,
                                            float *grad_face_xy, float *grad_face_feat, void *workspace, size_t workspace_bytes,
                                            void *stream);
+
+/* Vertex Laplacian (250): r = M·x − x over a sparse vertex adjacency M, then r².  Training form: DefTet.laplacian_sparse
+ * (layers/DefTet/deftet.py:340-343), M = D⁻¹A, Σ_{i,c} r² per shape.  Render form: Deftet.get_featlap
+ * (diff_render/diftet_6_subdiv/3_model/deftet.py:221-241), M = (sum over a padded neighbour table) / w, r² per entry.
+ *
+ * deftet_vertex_adjacency_csr_i32: nnz (row, col) pairs, int32 or int64 (index_bytes 4 / 8), with optional f32 values (NULL = 1),
+ *   to a CSR — offsets int32 [V+1], cols int32 [nnz], vals f32 [nnz] — and its transpose — t_offsets int32 [V+1], t_rows int32
+ *   [nnz], t_vals f32 [nnz] (the row of each entry and its value, grouped by column).  vals / t_vals may be NULL (not written).
+ *   The entries of a row are ordered by column (DEFTET_VADJ_ROW_COL) or kept in input order (DEFTET_VADJ_ROW_INPUT: a padded
+ *   neighbour table read row-major, pads removed); those of a transposed row by row.  Ties keep their input order: duplicate
+ *   pairs are kept and summed, as torch.sparse.mm sums an uncoalesced tensor.  An index outside [0, V) sets *bad_flag
+ *   (device int32, required, cleared by the call) to 1; such entries are never referenced by the offsets.
+ *   Stable radix sorts of this library, no atomics.  Workspace: deftet_vertex_adjacency_workspace_bytes(nnz, V).
+ * deftet_vertex_laplacian_fwd_f32: x f32 [B,V,C], 1 <= C <= 16, and the CSR above (nnz entries).
+ *   nei = Σ_k vals_k x[cols_k] in CSR order (DEFTET_VLAP_VALUES), or (Σ_k x[cols_k]) / row_weights[i], adds in CSR order then
+ *   one IEEE division (DEFTET_VLAP_ROW_DIVISOR; row_weights f32 [V], vals unused).  r = nei − x is written to r f32 [B,V,C];
+ *   out f32 [B,V,C] = r² (DEFTET_VLAP_NONE) or out f32 [B] = Σ_{i,c} r² (DEFTET_VLAP_SHAPE, a fixed-order two-stage
+ *   reduction through the workspace: deftet_vertex_laplacian_workspace_bytes(B, V); NONE needs none).
+ * deftet_vertex_laplacian_bwd_f32: grad_x f32 [B,V,C] (overwritten) = Σ_{i: j ∈ row i} a_ij u_i − u_j, u = 2·g·r, from the
+ *   saved r, the upstream gradient grad_out (f32 [B] for SHAPE, [B,V,C] for NONE) and the TRANSPOSED CSR; a_ij = t_vals or
+ *   1 / row_weights[i] (applied as a division).  One gather per vertex in transposed-CSR order: no atomics, bit-reproducible.
+ * The CSRs must come from deftet_vertex_adjacency_csr_i32 with *bad_flag == 0: the kernels do not re-check their indices. */
+#define DEFTET_VADJ_ROW_COL 0
+#define DEFTET_VADJ_ROW_INPUT 1
+#define DEFTET_VLAP_VALUES 0
+#define DEFTET_VLAP_ROW_DIVISOR 1
+#define DEFTET_VLAP_NONE 0
+#define DEFTET_VLAP_SHAPE 1
+size_t deftet_vertex_adjacency_workspace_bytes(int nnz, int n_vertex);
+int deftet_vertex_adjacency_csr_i32(const void *row_idx, const void *col_idx, int index_bytes, const float *values, int nnz,
+                                    int n_vertex, int order, int32_t *offsets, int32_t *cols, float *vals, int32_t *t_offsets,
+                                    int32_t *t_rows, float *t_vals, int32_t *bad_flag, void *workspace, size_t workspace_bytes,
+                                    void *stream);
+size_t deftet_vertex_laplacian_workspace_bytes(int n_batch, int n_vertex);
+int deftet_vertex_laplacian_fwd_f32(const float *x, const int32_t *offsets, const int32_t *cols, const float *vals,
+                                    const float *row_weights, int weighting, int reduction, int n_batch, int n_vertex, int n_chan,
+                                    int nnz, float *r, float *out, void *workspace, size_t workspace_bytes, void *stream);
+int deftet_vertex_laplacian_bwd_f32(const float *r, const float *grad_out, const int32_t *t_offsets, const int32_t *t_rows,
+                                    const float *t_vals, const float *row_weights, int weighting, int reduction, int n_batch,
+                                    int n_vertex, int n_chan, int nnz, float *grad_x, void *stream);
 
 #ifdef __cplusplus
 }
