@@ -15,6 +15,8 @@ every import the hot path goes through:
     utils.lib.{tet_point_adj,tet_face_adj,tet_adj_share,colaps_v}.interface
     kaolin.ops.mesh.check_sign, kaolin.render.mesh.deftet_sparse_render   (only when Kaolin itself is not
                                                            importable, or with kaolin=True; parity unpinned)
+    kaolin.ops.mesh.{sample_points,index_vertices_by_faces}, kaolin.metrics.pointcloud.sided_distance,
+    kaolin.metrics.trianglemesh.point_to_mesh_distance    (the evaluation metrics, same condition)
     cv2                                                    empty stub (imported, never used: check_condition.../utils.py:14)
 
 With `deftet_module=True` also `layers.DefTet.deftet` (the `DefTet` nn.Module built on the fused
@@ -46,8 +48,9 @@ def _kaolin_check_sign(verts, faces, points, hash_resolution=512):
 
 
 def kaolin_shim():
-    """A module tree exposing exactly the two Kaolin entry points the hot path calls
-    (layers/DefTet/deftet.py:46, diff_render/diftet_6_subdiv/5_rendereq/deftetrneder.py:97-100)."""
+    """A module tree exposing the two Kaolin entry points the hot path calls
+    (layers/DefTet/deftet.py:46, diff_render/diftet_6_subdiv/5_rendereq/deftetrneder.py:97-100) and the four the evaluation
+    metrics call."""
     from deftet_amd.render.deftet_sparse_render import deftet_sparse_render
     kal = types.ModuleType("kaolin")
     kal.__path__ = []                                  # a package, so `import kaolin.ops.mesh` resolves through sys.modules
@@ -57,9 +60,19 @@ def kaolin_shim():
     ops_mesh.check_sign = _kaolin_check_sign
     render_mesh.deftet_sparse_render = deftet_sparse_render
     kal.ops, kal.render, ops.mesh, render.mesh = ops, render, ops_mesh, render_mesh
+    # the evaluation metrics (eval.py:237-260, utils/point_cloud_utils.py, dataloader.py:76-99)
+    from deftet_amd import metrics
+    ops_mesh.sample_points = metrics.sample_points
+    ops_mesh.index_vertices_by_faces = metrics.index_vertices_by_faces
+    met, met_pc, met_tm = (types.ModuleType(n) for n in ("kaolin.metrics", "kaolin.metrics.pointcloud", "kaolin.metrics.trianglemesh"))
+    met.__path__ = []
+    met_pc.sided_distance = metrics.sided_distance
+    met_tm.point_to_mesh_distance = metrics.point_to_mesh_distance
+    kal.metrics, met.pointcloud, met.trianglemesh = met, met_pc, met_tm
     kal.__deftet_amd_shim__ = True
     return {"kaolin": kal, "kaolin.ops": ops, "kaolin.render": render, "kaolin.ops.mesh": ops_mesh,
-            "kaolin.render.mesh": render_mesh}
+            "kaolin.render.mesh": render_mesh, "kaolin.metrics": met, "kaolin.metrics.pointcloud": met_pc,
+            "kaolin.metrics.trianglemesh": met_tm}
 
 
 def install(kaolin=None, deftet_module=False, stub_cv2=True):

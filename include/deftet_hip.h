@@ -42,7 +42,9 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
-/* 250: the vertex Laplacian regulariser — deftet_vertex_adjacency_csr_i32 (an adjacency and its transpose as CSRs) with its
+/* 260: the evaluation metrics — deftet_point_mesh_distance_f32 / _scan_f32, deftet_sample_points_f32, deftet_nn_distance_f32,
+ *      deftet_surface_metrics_f32 and their workspace sizes.
+ * 250: the vertex Laplacian regulariser — deftet_vertex_adjacency_csr_i32 (an adjacency and its transpose as CSRs) with its
  *      workspace size, deftet_vertex_laplacian_fwd_f32 / _bwd_f32 and the forward's workspace size.
  * 240: the fused rasterize-and-composite operator — deftet_sparse_render_composite_fwd_f32 / _bwd_f32 and their workspace sizes.
  * 230: the indexed point-in-tet query — deftet_point_in_tet_indexed_f32, _indexed_scan_f32, _indexed_bwd_to_vertices_f32 take
@@ -620,6 +622,46 @@ int deftet_vertex_laplacian_fwd_f32(const float *x, const int32_t *offsets, cons
 int deftet_vertex_laplacian_bwd_f32(const float *r, const float *grad_out, const int32_t *t_offsets, const int32_t *t_rows,
                                     const float *t_vals, const float *row_weights, int weighting, int reduction, int n_batch,
                                     int n_vertex, int n_chan, int nnz, float *grad_x, void *stream);
+
+/* Evaluation metrics (260): what eval.py:237-260 and utils/point_cloud_utils.py compute with Kaolin, forward only.
+ *
+ * deftet_point_mesh_distance_f32: points f32 [B,P,3] against face_vertices f32 [B,F,3,3]; n_face (device int32 [B], NULL = F
+ *   faces each) limits shape b to its first n_face[b] faces.  dist f32 [B,P] = the squared Euclidean distance to the closest
+ *   face, fp32 Ericson (Real-Time Collision Detection §5.1.5) in its branch order; face_idx int64 [B,P] = the first face, in
+ *   index order, with the strictly smallest distance; dist_type int32 [B,P]: 0 inside the face, 1/2/3 vertex 0/1/2, 4/5/6 edge
+ *   0-1/1-2/2-0.  A zero-area face whose evaluation reaches the interior branch takes the minimum over its three segments; a
+ *   face with a non-finite corner never wins; no face gives (+inf, -1, -1); a non-finite point gives (NaN, -1, -1).
+ *   The grid search needs deftet_point_mesh_distance_workspace_bytes(B, P, F); _scan_f32 is the streaming scan over every
+ *   face with the same evaluation (no workspace).  Both give bit-identical outputs.
+ * deftet_sample_points_f32: N points per shape on faces f32 [B,F,3,3] chosen with probability proportional to area (fp32
+ *   0.5·|cross(v1−v0, v2−v0)|, or the caller's areas f32 [B,F]) through an exact integer CDF; uniforms f32 [B,N,3] = (u0
+ *   face choice, u1, u2 position).  points f32 [B,N,3], face_choice int64 [B,N].  A shape with no faces or zero total area
+ *   gets NaN points, face -1 and empty_flag[b] = 1 (device int32 [B], cleared by the call).  Workspace:
+ *   deftet_sample_points_workspace_bytes(B, F).
+ * deftet_nn_distance_f32: dist f32 [B,N] = A10's distance ((dx·dx + dy·dy) + dz·dz) from query n to points[idx[n]] (idx
+ *   int32 [B,N], e.g. from deftet_nn_index_f32), and idx64 (int64 [B,N], optional) = idx.  An index outside [0, M) gives NaN.
+ * deftet_surface_metrics_f32: per shape, from the clouds p1 f32 [B,N1,3] (ground truth) and p2 f32 [B,N2,3] (prediction), their
+ *   NN indices idx12 int32 [B,N1] (into p2) and idx21 int32 [B,N2] (into p1), and optionally the squared point-to-mesh
+ *   distances dist_a f32 [B,Nh] (p1 to the predicted mesh) and dist_b f32 [B,Nh] (p2 to the ground-truth mesh): out f32 [B,5]
+ *   = chamfer, chamfer-L1, F-score (radius, extend=True form), mean and max Hausdorff (NaN without dist_a / dist_b).  A
+ *   fixed-order two-stage reduction: bit-identical from run to run.  Workspace: deftet_surface_metrics_workspace_bytes(B). */
+size_t deftet_point_mesh_distance_workspace_bytes(int n_batch, int n_point, int n_face);
+int deftet_point_mesh_distance_f32(const float *points_bxpx3, const float *face_bxfx3x3, const int32_t *n_face_b, int n_batch,
+                                   int n_point, int n_face, float *dist_bxp, int64_t *face_idx_bxp, int32_t *dist_type_bxp,
+                                   void *workspace, size_t workspace_bytes, void *stream);
+int deftet_point_mesh_distance_scan_f32(const float *points_bxpx3, const float *face_bxfx3x3, const int32_t *n_face_b, int n_batch,
+                                        int n_point, int n_face, float *dist_bxp, int64_t *face_idx_bxp, int32_t *dist_type_bxp,
+                                        void *stream);
+size_t deftet_sample_points_workspace_bytes(int n_batch, int n_face);
+int deftet_sample_points_f32(const float *face_bxfx3x3, const float *areas_bxf, const int32_t *n_face_b, const float *uniforms_bxnx3,
+                             int n_batch, int n_face, int n_sample, float *points_bxnx3, int64_t *face_choice_bxn, int32_t *empty_flag_b,
+                             void *workspace, size_t workspace_bytes, void *stream);
+int deftet_nn_distance_f32(const float *queries_bxnx3, const float *points_bxmx3, const int32_t *idx_bxn, int n_batch, int n_query,
+                           int n_point, float *dist_bxn, int64_t *idx64_bxn, void *stream);
+size_t deftet_surface_metrics_workspace_bytes(int n_batch);
+int deftet_surface_metrics_f32(const float *p1_bxn1x3, const float *p2_bxn2x3, const int32_t *idx12_bxn1, const int32_t *idx21_bxn2,
+                               const float *dist_a_bxnh, const float *dist_b_bxnh, int n_batch, int n1, int n2, int nh, float radius,
+                               float *out_bx5, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
