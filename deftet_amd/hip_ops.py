@@ -6,6 +6,10 @@ reference's names and signatures) lives in deftet_amd/layers/ and deftet_amd/uti
 """
 from __future__ import annotations
 
+import collections
+import os
+import threading
+
 import numpy as np
 import torch
 
@@ -13,6 +17,7 @@ from . import _lib
 
 PIT_AUTO, PIT_BRUTE, PIT_EXACT, PIT_SLAB, PIT_WAVE, PIT_PAIR = 0, 1, 2, 3, 4, 5        # include/deftet_hip.h DEFTET_PIT_*
 _PIT_KERNEL = {PIT_WAVE: "k_tet_scan_wave", PIT_EXACT: "k_tet_scan", PIT_BRUTE: "k_brute", PIT_SLAB: "k_tet_scan_slab", PIT_PAIR: "k_tet_scan_pair"}
+_ORDERED = (PIT_AUTO, PIT_SLAB, PIT_WAVE, PIT_PAIR)     # the algos whose traversal takes an order (PIT_AUTO resolves to one of them)
 
 
 def pit_kernel_name(algo, n_tet=None, n_query=None):
@@ -26,6 +31,39 @@ def pit_kernel_name(algo, n_tet=None, n_query=None):
 
 def _f32c(t):
     return t.contiguous().float()
+
+
+class _LRU(collections.OrderedDict):
+    """At most `maxsize` entries, the least recently used dropped first (like _TOPOLOGIES in layers/DefTet/deftet.py); every
+    access holds `lock`.  An entry that leaves is retire()d: the GPU may still be writing into pinned host memory it owns, and
+    torch hands a freed pinned block out again at once."""
+
+    def __init__(self, maxsize):
+        super().__init__()
+        self.maxsize, self.lock = maxsize, threading.RLock()
+
+    def lookup(self, key):
+        with self.lock:
+            value = self.get(key)
+            if value is not None:
+                self.move_to_end(key)
+            return value
+
+    def add(self, key, value):
+        with self.lock:
+            self[key] = value
+            self.move_to_end(key)
+            gone = [self.popitem(last=False)[1] for _ in range(len(self) - self.maxsize)]
+        for old in gone:
+            old.retire()
+        return value
+
+    def clear(self):
+        with self.lock:
+            gone = list(self.values())
+            super().clear()
+        for old in gone:
+            old.retire()
 
 
 # --------------------------------------------------------------------------------- A1
@@ -47,6 +85,18 @@ class PreparedQueries:
         self.event = None
         self.consumed = False
 
+    def consume(self, caller, pts, n_tet, algo):
+        """The workspace for `caller`'s one call on these points, ordered after the sort on the current stream."""
+        if self.consumed or self.algo != algo or self.n_tet != n_tet or self.pts.data_ptr() != pts.data_ptr() or self.pts.shape != pts.shape:
+            raise RuntimeError("%s: `prepared` was made for other points / sizes / algo, or was already used" % caller)
+        if self.version != pts._version:
+            raise RuntimeError("%s: the points were modified in place after prepare_queries (stale sorted copy)" % caller)
+        cur = torch.cuda.current_stream(pts.device)
+        cur.wait_event(self.event)                     # the sort may have run on another stream
+        self.workspace.record_stream(cur)
+        self.consumed = True
+        return self.workspace
+
 
 # Query boxes tracked from call to call (query_box="track"): per (device, STREAM, B, Q) two [B,6] tensors used in turns — a call
 # hands the box the PREVIOUS call measured to the library (query_box_in: the grid spans it, the measuring launch is skipped) and
@@ -61,10 +111,10 @@ class PreparedQueries:
 # The stream is part of the key (round 6): call N+1 reads the box call N's k_slab_sort wrote, and only the
 # order of ONE stream makes that read come after the write — two streams sharing a tracker (bench.py's pipelined path: one
 # prepare on the main stream, the next on a side stream) raced, and a box that changes while k_slab_local runs gives its
-# workgroups different grids.  Calls on different streams now never share a box; inside the library every workgroup takes
-# the grid from the snapshot its own launch sequence published (k_slab_local<true>: see there).
-_box_cache = {}
-_box_lock = __import__("threading").Lock()
+# workgroups different grids.  Every workgroup of k_slab_local<true> reads the caller's box directly, so this per-stream key is
+# what keeps calls on different streams from sharing one.  At most _CACHE_MAX trackers are kept.
+_CACHE_MAX = 32
+_box_cache = _LRU(_CACHE_MAX)
 
 
 class _BoxTracker:
@@ -97,6 +147,10 @@ class _BoxTracker:
             self.backoff, self.clean = self.backoff // 4, 0
         return box_in, box_out, self.misses
 
+    def retire(self):
+        if self.box[0].is_cuda:                              # tracked calls in flight write `misses`
+            torch.cuda.synchronize(self.box[0].device)
+
 
 def query_box_key(dev, B, Q):
     """Key of the tracker a query_box="track" call on `dev`'s CURRENT stream uses (see query_box_trackers)."""
@@ -108,30 +162,26 @@ def query_box_key(dev, B, Q):
 
 def _tracked_boxes(dev, B, Q):
     """(query_box_in | None, query_box_out, query_box_misses | None) for this call."""
-    import os
     if os.environ.get("DEFTET_PIT_BOX", "track") == "off":
         return None, None, None
     # A call that is being captured into a graph measures its own box and touches no tracker: a tracked call would bake ONE
     # (box_in, box_out, misses) triple into the graph — replays would never alternate the buffers nor ever fall back to
     # measuring (the misses are only polled by eager calls), and the Python phase would no longer describe what the graph does.
-    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+    if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
         return None, None, None
     key = query_box_key(dev, B, Q)
-    with _box_lock:
-        st = _box_cache.get(key)
-        if st is None:
-            st = _box_cache[key] = _BoxTracker(dev, B, Q)
+    with _box_cache.lock:
+        st = _box_cache.lookup(key) or _box_cache.add(key, _BoxTracker(dev, B, Q))
         return st.step()
 
 
 def clear_query_box_cache():
-    with _box_lock:
-        _box_cache.clear()
+    _box_cache.clear()
 
 
 def query_box_trackers():
     """{(device, stream, B, Q): {"tracked", "measured", "backoffs", "hold", "backoff"}} — what query_box="track" has been doing."""
-    with _box_lock:
+    with _box_cache.lock:
         return {k: dict(v.counts, hold=v.hold, backoff=v.backoff) for k, v in _box_cache.items()}
 
 
@@ -173,6 +223,25 @@ def prepare_queries(pts_bxqx3, n_tet, algo=PIT_AUTO, query_box=None, query_box_m
     return pq
 
 
+# An `order` indexes the tet array and the hit records: a duplicate silently skips tets, an entry outside [0, T) reads and writes
+# out of bounds (ADVICE rounds 5 and 6).  A caller's order is checked once per tensor OBJECT and version, and the verdict is kept
+# on the tensor itself: a view, or a new tensor the caching allocator placed where a checked one was freed, is another object
+# and is checked again.  (A write that bypasses the version counter — through .data, or by a kernel — is not seen.)  The orders
+# tet_spatial_order computes are permutations by construction (a stable sort of 0..T-1) and are marked without the check.
+def _check_order(order, T, dev=None):
+    if order.dtype != torch.int32 or order.shape != (T,) or not order.is_contiguous() or (dev is not None and order.device != dev):
+        raise RuntimeError("order must be a contiguous int32 [T] tensor on the tets' device")
+    if getattr(order, "_deftet_permutation", None) == order._version:
+        return
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("order: a permutation must be validated by an eager call before it is used inside a graph capture")
+    o = order.to(torch.int64)
+    ok = T == 0 or (int(o.min()) >= 0 and int(o.max()) < T and bool((torch.bincount(o, minlength=T) == 1).all()))
+    if not ok:
+        raise RuntimeError("order must be a permutation of 0..T-1 (duplicates would skip tets, entries outside the range index out of bounds)")
+    order._deftet_permutation = order._version
+
+
 def tet_spatial_order(tet_tx4x3, want_breaks=False):
     """int32 [T] permutation that walks the tets of ONE shape column by column ((x, y) columns one mean tet extent wide,
     ascending z inside a column): the traversal order the *_ex_* entry points take (tet_order).  Static topology => computed once
@@ -190,7 +259,7 @@ def tet_spatial_order(tet_tx4x3, want_breaks=False):
         ws = _lib.workspace(dev, max(lib.deftet_tet_spatial_order_workspace_bytes(T), 256))
         _lib.check(lib.deftet_tet_spatial_order_f32(_lib.ptr(tet), T, _lib.ptr(order), _lib.ptr(breaks), _lib.ptr(ws), ws.numel(),
                                                     _lib.current_stream(dev)), "deftet_tet_spatial_order_f32")
-    _orders_checked[_order_id(order, T)] = True                       # a stable sort of 0..T-1: a permutation by construction
+    order._deftet_permutation = order._version                          # a permutation by construction (see _check_order)
     return (order, breaks) if want_breaks else order
 
 
@@ -205,8 +274,8 @@ def tet_order_coherence(tet_tx4x3, order=None, out=None):
     if tet.dim() != 3 or tet.shape[1:] != (4, 3):
         raise RuntimeError("tet_tx4x3 must be [T,4,3] (one shape), got %s" % (tuple(tet.shape),))
     T, dev = tet.shape[0], tet.device
-    if order is not None and (order.dtype != torch.int32 or order.shape != (T,) or not order.is_contiguous() or order.device != dev):
-        raise RuntimeError("order must be a contiguous int32 [T] tensor on the tets' device")
+    if order is not None:
+        _check_order(order, T, dev)
     if out is None:
         out = torch.empty(2, device=dev, dtype=torch.int32)
     elif out.dtype != torch.int32 or out.numel() < 2 or not out.is_contiguous():
@@ -230,23 +299,25 @@ def tet_order_coherence(tet_tx4x3, order=None, out=None):
 # QuarTet grid by 13 %: a permutation costs gathers of 48-byte records, profiles/r05_scan_ab_orders.jsonl).  A stale or unlucky
 # choice can never change a result.
 #   topology: what identifies the tet LIST (static during training, layers/DefTet/deftet.py:65-68) — a TetTopology (its serial), any
-# hashable key, or the index tensor itself (fingerprinted once by content).  Callers that only have positions
-# (check_condition_f_base's reference signature) pass None: their entry is keyed by the sizes alone and is WATCHED — every
-# _WATCH_EVERY-th call the coherence of the caller's numbering (and of the permutation in use) is measured asynchronously into
-# pinned host memory and read by a later call without synchronising; when it no longer matches what the decision was made on (a
-# second mesh with the same number of tets and another numbering) the entry is dropped and decided again.
-# DEFTET_PIT_ORDER=off|force overrides the decision.
+# hashable key, or the index tensor itself (fingerprinted by content once per tensor object and version, kept on the tensor).
+# Callers that only have positions (check_condition_f_base's reference signature) pass None: their entry is keyed by the sizes
+# alone and is WATCHED — every _WATCH_EVERY-th call the coherence of the caller's numbering (and of the permutation in use) is
+# measured asynchronously into pinned host memory and read by a later call without synchronising; when it no longer matches what
+# the decision was made on (a second mesh with the same number of tets and another numbering) the entry is dropped and decided
+# again.  At most _CACHE_MAX decisions are kept.  DEFTET_PIT_ORDER=off|force overrides the decision.
 _FAR_LIMIT = 0.02
 _WATCH_EVERY = 64
-_order_cache = {}
-_order_lock = __import__("threading").Lock()
-_topology_prints = {}
+_order_cache = _LRU(_CACHE_MAX)
 
 
 class _OrderEntry:
     def __init__(self, choice, fractions):
         self.choice, self.fractions = choice, fractions      # fractions: (far fraction of the caller's numbering, of the computed order) | None
         self.calls, self.mail, self.event = 0, None, None
+
+    def retire(self):
+        if self.event is not None:                           # a watch measurement in flight writes `mail`
+            self.event.synchronize()
 
 
 def _far_fraction(pair):
@@ -265,18 +336,15 @@ def _topology_key(topology):
     if serial is not None:
         return ("topology", int(serial))
     if isinstance(topology, torch.Tensor):
-        k = (topology.data_ptr(), topology._version, tuple(topology.shape), str(topology.dtype), str(topology.device))
-        fp = _topology_prints.get(k)
-        if fp is None:
-            # content fingerprint (one reduction + sync, once per tensor version): two index lists with the same content share
-            # a decision, two numberings of one mesh do not
+        fp = getattr(topology, "_deftet_fingerprint", None)
+        if fp is None or fp[0] != topology._version:
+            # content fingerprint (one reduction + sync, once per tensor object and version): two index lists with the same
+            # content share a decision, two numberings of one mesh do not
             flat = topology.reshape(-1).to(torch.int64)
             w = (torch.arange(flat.numel(), device=flat.device, dtype=torch.int64) * 2654435761 + 40503) & 0xFFFFFFFF
-            fp = (int(((flat + 1) * w).sum().item()) & ((1 << 62) - 1), int(flat.numel()))
-            if len(_topology_prints) > 64:
-                _topology_prints.clear()
-            _topology_prints[k] = fp
-        return ("tensor",) + fp
+            fp = (topology._version, int(((flat + 1) * w).sum().item()) & ((1 << 62) - 1), int(flat.numel()))
+            topology._deftet_fingerprint = fp
+        return ("tensor",) + fp[1:]
     raise RuntimeError("topology must be None, a hashable key, a TetTopology or the index tensor")
 
 
@@ -284,11 +352,12 @@ def _moved(now, then):
     return abs(now - then) > max(0.01, 0.5 * then)
 
 
-def _watch_order(entry, key, tet0):
+def _watch_order(entry, key, tets0):
     """Position-only callers: now and then measure what is being traversed, asynchronously, and compare with what the decision
     was made on — the far-step fraction of the caller's numbering, and of the permutation in use if there is one.  Both are
     properties of the tet LIST (a training step deforms the grid by a fraction of a tet: they move in the third digit), so a
-    value that moved means another list is being handed in under the same sizes: the entry is dropped and decided again."""
+    value that moved means another list is being handed in under the same sizes: the entry is dropped and decided again.
+    tets0() returns shape 0's tets."""
     entry.calls += 1
     if entry.fractions is None or entry.calls % _WATCH_EVERY or torch.cuda.is_current_stream_capturing():
         return
@@ -298,13 +367,14 @@ def _watch_order(entry, key, tet0):
         m = entry.mail.tolist()
         stale = _moved(_far_fraction(m[0:2]), entry.fractions[0]) or (entry.choice is not None and _moved(_far_fraction(m[2:4]), entry.fractions[1]))
         if stale:
-            with _order_lock:
+            with _order_cache.lock:
                 if _order_cache.get(key) is entry:
                     del _order_cache[key]
             return
     if entry.mail is None:
         entry.mail = torch.zeros(4, dtype=torch.int32, pin_memory=True)
         entry.mail[1] = entry.mail[3] = 1
+    tet0 = tets0()
     tet_order_coherence(tet0, None, out=entry.mail[0:2])
     if entry.choice is not None:
         tet_order_coherence(tet0, entry.choice, out=entry.mail[2:4])
@@ -314,71 +384,80 @@ def _watch_order(entry, key, tet0):
 
 def auto_tet_order(tet_bxtx4x3, pts_bxqx3, algo=PIT_AUTO, topology=None):
     """The cached traversal order for this grid, or None when its own numbering is coherent enough (or the grid is tiny)."""
-    import os
+    return _auto_order(tet_bxtx4x3.device, tet_bxtx4x3.shape[0], tet_bxtx4x3.shape[1], pts_bxqx3.shape[1], algo, topology,
+                       lambda: tet_bxtx4x3[0])
+
+
+def _auto_order(dev, B, T, Q, algo, topology, tets0):
+    """auto_tet_order from the sizes; tets0() returns shape 0's [T,4,3] tets and is only called when they are read (a decision
+    or a watch measurement), so the indexed query gathers them for that alone."""
     mode = os.environ.get("DEFTET_PIT_ORDER", "auto")
-    B, T, dev = tet_bxtx4x3.shape[0], tet_bxtx4x3.shape[1], tet_bxtx4x3.device
-    Q = pts_bxqx3.shape[1]
     if mode == "off" or T < 4096 or B == 0 or Q == 0:
         return None
     kernel = int(_lib.load().deftet_point_in_tet_resolve_algo(int(algo), T, Q))
-    if kernel not in (PIT_SLAB, PIT_WAVE, PIT_PAIR):
+    if kernel not in _ORDERED:
         return None
     tkey = _topology_key(topology)
     key = (dev.index if dev.index is not None else torch.cuda.current_device(), T, kernel, tkey)
-    with _order_lock:
-        entry = _order_cache.get(key)
+    entry = _order_cache.lookup(key)
     if entry is not None:
         if tkey is None:
-            _watch_order(entry, key, tet_bxtx4x3[0])
+            _watch_order(entry, key, tets0)
         return entry.choice
     if torch.cuda.is_current_stream_capturing():                     # the decision reads two counters back: not inside a graph capture
         return None
-    order = tet_spatial_order(tet_bxtx4x3[0])
+    tet0 = tets0()
+    order = tet_spatial_order(tet0)
     if mode == "force":
         choice, fractions = order, None
     else:
-        fractions = (_far_fraction(tet_order_coherence(tet_bxtx4x3[0]).tolist()), _far_fraction(tet_order_coherence(tet_bxtx4x3[0], order).tolist()))
+        fractions = (_far_fraction(tet_order_coherence(tet0).tolist()), _far_fraction(tet_order_coherence(tet0, order).tolist()))
         choice = order if _decide_order(*fractions) else None
-    with _order_lock:
-        _order_cache[key] = _OrderEntry(choice, fractions)
+    _order_cache.add(key, _OrderEntry(choice, fractions))
     return choice
 
 
 def tet_order_decisions():
     """{(device, n_tet, kernel id, topology key): (chosen "sorted" | "native", (far fraction of the caller's numbering, of the
     computed order) | None)} — what auto_tet_order decided."""
-    with _order_lock:
+    with _order_cache.lock:
         return {k: ("native" if v.choice is None else "sorted", v.fractions) for k, v in _order_cache.items()}
 
 
 def clear_tet_order_cache():
-    with _order_lock:
-        _order_cache.clear()
+    _order_cache.clear()
 
 
-# Permutations handed in by the caller are checked ONCE per tensor (version): a duplicate silently skips tets, an entry outside
-# [0, T) indexes the tet array and the hit records out of bounds (ADVICE round 5).  The orders this module computes are
-# permutations by construction (a stable sort of 0..T-1) and are registered without the check.
-_orders_checked = {}
+def _pit_begin(caller, lib, pts, T, want_bary, algo, pred_bxt, want_hits, prepared, order, query_box, query_box_misses, auto_order):
+    """What point_in_tet and point_in_tet_indexed do before their one library call, on the queries' device: the outputs, the
+    traversal order (order="auto" asks auto_order()), and the workspace — `prepared`'s, or the cached one with the query box.
+    Returns (cond, bary, pred, occ, hits, order, workspace, (query_box_in, query_box_out, query_box_misses))."""
+    B, Q, dev = pts.shape[0], pts.shape[1], pts.device
+    cond = torch.empty(B, Q, 1, device=dev, dtype=torch.float32)
+    bary = torch.empty(B, Q, 4, device=dev, dtype=torch.float32) if want_bary else None
+    pred = _f32c(pred_bxt) if pred_bxt is not None else None
+    if pred is not None and pred.shape != (B, T):
+        raise RuntimeError("pred_tet_occ must be [B,T], got %s" % (tuple(pred.shape),))
+    occ = torch.empty(B, Q, device=dev, dtype=torch.float32) if pred is not None else None
+    hits = None
+    if want_hits and algo != PIT_BRUTE:
+        hits = torch.empty(max(lib.deftet_point_in_tet_hits_ints(B, T, Q), 4), device=dev, dtype=torch.int32)
+    if isinstance(order, str):
+        if order != "auto":
+            raise RuntimeError("order must be None, 'auto' or an int32 [T] permutation")
+        order = auto_order() if algo in _ORDERED else None
+    if order is not None:
+        _lib.require_gpu(order)
+        _check_order(order, T, dev)
+    if prepared is not None:
+        return cond, bary, pred, occ, hits, order, prepared.consume(caller, pts, T, algo), (None, None, None)
+    ws = _lib.workspace(dev, lib.deftet_point_in_tet_workspace_bytes(B, T, Q, algo))
+    return cond, bary, pred, occ, hits, order, ws, _resolve_query_box(query_box, dev, B, Q, algo, query_box_misses)
 
 
-def _order_id(order, T):
-    return (order.data_ptr(), order._version, int(T), str(order.device))
-
-
-def _check_order(order, T):
-    k = _order_id(order, T)
-    if k in _orders_checked:
-        return
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError("order: a permutation must be validated by an eager call before it is used inside a graph capture")
-    o = order.to(torch.int64)
-    ok = T == 0 or (int(o.min()) >= 0 and int(o.max()) < T and bool((torch.bincount(o, minlength=T) == 1).all()))
-    if not ok:
-        raise RuntimeError("order must be a permutation of 0..T-1 (duplicates would skip tets, entries outside the range index out of bounds)")
-    if len(_orders_checked) > 256:
-        _orders_checked.clear()
-    _orders_checked[k] = True
+def _pit_result(cond, bary, occ, hits, want_hits):
+    out = (cond,) + ((bary,) if bary is not None else ()) + ((occ,) if occ is not None else ()) + ((hits,) if want_hits else ())
+    return out if len(out) > 1 else cond
 
 
 def point_in_tet(tet_bxtx4x3, pts_bxqx3, want_bary=False, algo=PIT_AUTO, pred_bxt=None, want_hits=False, prepared=None, order=None,
@@ -403,50 +482,21 @@ def point_in_tet(tet_bxtx4x3, pts_bxqx3, want_bary=False, algo=PIT_AUTO, pred_bx
         raise RuntimeError("point_pos_bxnx3 must be [B,Q,3] with the same B, got %s" % (tuple(pts.shape),))
     B, T, Q = tet.shape[0], tet.shape[1], pts.shape[1]
     dev = pts.device
-    cond = torch.empty(B, Q, 1, device=dev, dtype=torch.float32)
-    bary = torch.empty(B, Q, 4, device=dev, dtype=torch.float32) if want_bary else None
-    pred = _f32c(pred_bxt) if pred_bxt is not None else None
-    if pred is not None and pred.shape != (B, T):
-        raise RuntimeError("pred_tet_occ must be [B,T], got %s" % (tuple(pred.shape),))
-    occ = torch.empty(B, Q, device=dev, dtype=torch.float32) if pred is not None else None
-    hits = None
-    if want_hits and algo != PIT_BRUTE:
-        hits = torch.empty(max(lib.deftet_point_in_tet_hits_ints(B, T, Q), 4), device=dev, dtype=torch.int32)
-    if isinstance(order, str):
-        if order != "auto":
-            raise RuntimeError("order must be None, 'auto' or an int32 [T] permutation")
-        order = auto_tet_order(tet, pts, algo, topology) if algo in (PIT_AUTO, PIT_SLAB, PIT_WAVE, PIT_PAIR) else None
-    if order is not None:
-        _lib.require_gpu(order)
-        if order.dtype != torch.int32 or order.shape != (T,) or not order.is_contiguous() or order.device != dev:
-            raise RuntimeError("order must be a contiguous int32 [T] tensor on the tets' device")
-        _check_order(order, T)
     with _lib.on_device(dev):
+        cond, bary, pred, occ, hits, order, ws, box = _pit_begin("point_in_tet", lib, pts, T, want_bary, algo, pred_bxt, want_hits, prepared,
+                                                                 order, query_box, query_box_misses,
+                                                                 lambda: _auto_order(dev, B, T, Q, algo, topology, lambda: tet[0]))
         if prepared is not None:
-            if prepared.consumed or prepared.algo != algo or prepared.n_tet != T or prepared.pts.data_ptr() != pts.data_ptr() \
-                    or prepared.pts.shape != pts.shape:
-                raise RuntimeError("point_in_tet: `prepared` was made for other points / sizes / algo, or was already used")
-            if prepared.version != pts._version:
-                raise RuntimeError("point_in_tet: the points were modified in place after prepare_queries (stale sorted copy)")
-            cur = torch.cuda.current_stream(dev)
-            cur.wait_event(prepared.event)                             # the sort may have run on another stream
-            ws = prepared.workspace
-            ws.record_stream(cur)
-            prepared.consumed = True
             _lib.check(lib.deftet_point_in_tet_scan_ex_f32(_lib.ptr(tet), _lib.ptr(pts), _lib.ptr(cond), _lib.ptr(bary), _lib.ptr(pred),
                                                            _lib.ptr(occ), _lib.ptr(hits), B, T, Q, algo, _lib.ptr(order), _lib.ptr(ws),
                                                            ws.numel(), _lib.current_stream(dev)), "deftet_point_in_tet_scan_ex_f32")
         else:
-            nbytes = lib.deftet_point_in_tet_workspace_bytes(B, T, Q, algo)
-            ws = _lib.workspace(dev, nbytes)
-            box_in, box_out, box_miss = _resolve_query_box(query_box, dev, B, Q, algo, query_box_misses)
             _lib.check(lib.deftet_point_in_tet_ex_f32(_lib.ptr(tet), _lib.ptr(pts), _lib.ptr(cond), _lib.ptr(bary), _lib.ptr(pred),
-                                                      _lib.ptr(occ), _lib.ptr(hits), B, T, Q, algo, _lib.ptr(order), _lib.ptr(box_in),
-                                                      _lib.ptr(box_out), _lib.ptr(box_miss), _lib.ptr(ws), ws.numel(),
+                                                      _lib.ptr(occ), _lib.ptr(hits), B, T, Q, algo, _lib.ptr(order), _lib.ptr(box[0]),
+                                                      _lib.ptr(box[1]), _lib.ptr(box[2]), _lib.ptr(ws), ws.numel(),
                                                       _lib.current_stream(dev)),
                        "deftet_point_in_tet_ex_f32")
-    out = (cond,) + ((bary,) if want_bary else ()) + ((occ,) if pred is not None else ()) + ((hits,) if want_hits else ())
-    return out if len(out) > 1 else cond
+    return _pit_result(cond, bary, occ, hits, want_hits)
 
 
 def _idx32(tet_idx):
@@ -477,84 +527,38 @@ def _indexed_inputs(pos_bxvx3, tet_idx, pts_bxqx3, topology):
     return pos, idx, pts
 
 
-def _auto_order_indexed(pos, idx, pts, algo, topology):
-    """auto_tet_order for the indexed path: the per-topology decision when it is cached, else decided once on shape 0's tets
-    (gathered for that only).  The index list itself is the topology key when the caller gives none."""
-    if topology is None:
-        topology = idx
-    T, Q = idx.shape[1], pts.shape[1]
-    dev = pos.device
-    if pos.shape[0] and T >= 4096 and Q:
-        kernel = int(_lib.load().deftet_point_in_tet_resolve_algo(int(algo), T, Q))
-        key = (dev.index if dev.index is not None else torch.cuda.current_device(), T, kernel, _topology_key(topology))
-        with _order_lock:
-            entry = _order_cache.get(key)
-        if entry is not None:
-            return entry.choice
-    if torch.cuda.is_current_stream_capturing():                     # (auto_tet_order decides nothing inside a capture either)
-        return None
-    return auto_tet_order(tet_gather(pos[:1], idx[:1]), pts, algo, topology)
-
-
 def point_in_tet_indexed(pos_bxvx3, tet_idx, pts_bxqx3, want_bary=False, algo=PIT_AUTO, pred_bxt=None, want_hits=False, prepared=None,
                          order=None, query_box=None, query_box_misses=None, topology=None, check=False):
     """point_in_tet on the tets (pos_bxvx3, tet_idx) without gathering them: corner c of tet t of shape b is
     pos[b, tet_idx[b or 0, t, c]].  tet_idx: [T,4] (shared by the shapes) or [B,T,4], any integer dtype (a TetTopology's int32
     copy is used when `topology` is one).  Returns exactly what point_in_tet(tet_gather(pos, tet_idx), pts, ...) returns, bit
     for bit, including the hit records (either backward takes them).  An index outside [0, V) reads as a NaN corner, as in
-    tet_gather; check=True synchronises and raises on one."""
+    tet_gather; check=True synchronises and raises on one.  order="auto" without a topology keys the decision by tet_idx."""
     pos, idx, pts = _indexed_inputs(pos_bxvx3, tet_idx, pts_bxqx3, topology)
     _lib.require_gpu(pred_bxt)
     lib = _lib.load()
     B, V, T, Q, Bi = pos.shape[0], pos.shape[1], idx.shape[1], pts.shape[1], idx.shape[0]
     dev = pts.device
-    cond = torch.empty(B, Q, 1, device=dev, dtype=torch.float32)
-    bary = torch.empty(B, Q, 4, device=dev, dtype=torch.float32) if want_bary else None
-    pred = _f32c(pred_bxt) if pred_bxt is not None else None
-    if pred is not None and pred.shape != (B, T):
-        raise RuntimeError("pred_tet_occ must be [B,T], got %s" % (tuple(pred.shape),))
-    occ = torch.empty(B, Q, device=dev, dtype=torch.float32) if pred is not None else None
-    hits = None
-    if want_hits and algo != PIT_BRUTE:
-        hits = torch.empty(max(lib.deftet_point_in_tet_hits_ints(B, T, Q), 4), device=dev, dtype=torch.int32)
-    if isinstance(order, str):
-        if order != "auto":
-            raise RuntimeError("order must be None, 'auto' or an int32 [T] permutation")
-        order = _auto_order_indexed(pos, idx, pts, algo, topology) if algo in (PIT_AUTO, PIT_SLAB, PIT_WAVE, PIT_PAIR) else None
-    if order is not None:
-        _lib.require_gpu(order)
-        if order.dtype != torch.int32 or order.shape != (T,) or not order.is_contiguous() or order.device != dev:
-            raise RuntimeError("order must be a contiguous int32 [T] tensor on the tets' device")
-        _check_order(order, T)
+    key = topology if topology is not None else tet_idx
     bad = torch.zeros(1, device=dev, dtype=torch.int32) if check else None
     with _lib.on_device(dev):
+        cond, bary, pred, occ, hits, order, ws, box = _pit_begin("point_in_tet_indexed", lib, pts, T, want_bary, algo, pred_bxt, want_hits,
+                                                                 prepared, order, query_box, query_box_misses,
+                                                                 lambda: _auto_order(dev, B, T, Q, algo, key, lambda: tet_gather(pos[:1], idx[:1])[0]))
         if prepared is not None:
-            if prepared.consumed or prepared.algo != algo or prepared.n_tet != T or prepared.pts.data_ptr() != pts.data_ptr() \
-                    or prepared.pts.shape != pts.shape:
-                raise RuntimeError("point_in_tet_indexed: `prepared` was made for other points / sizes / algo, or was already used")
-            if prepared.version != pts._version:
-                raise RuntimeError("point_in_tet_indexed: the points were modified in place after prepare_queries (stale sorted copy)")
-            cur = torch.cuda.current_stream(dev)
-            cur.wait_event(prepared.event)
-            ws = prepared.workspace
-            ws.record_stream(cur)
-            prepared.consumed = True
             _lib.check(lib.deftet_point_in_tet_indexed_scan_f32(_lib.ptr(pos), _lib.ptr(idx), Bi, _lib.ptr(pts), _lib.ptr(cond), _lib.ptr(bary),
                                                                 _lib.ptr(pred), _lib.ptr(occ), _lib.ptr(hits), B, V, T, Q, algo, _lib.ptr(order),
                                                                 _lib.ptr(bad), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
                        "deftet_point_in_tet_indexed_scan_f32")
         else:
-            ws = _lib.workspace(dev, lib.deftet_point_in_tet_workspace_bytes(B, T, Q, algo))
-            box_in, box_out, box_miss = _resolve_query_box(query_box, dev, B, Q, algo, query_box_misses)
             _lib.check(lib.deftet_point_in_tet_indexed_f32(_lib.ptr(pos), _lib.ptr(idx), Bi, _lib.ptr(pts), _lib.ptr(cond), _lib.ptr(bary),
                                                            _lib.ptr(pred), _lib.ptr(occ), _lib.ptr(hits), B, V, T, Q, algo, _lib.ptr(order),
-                                                           _lib.ptr(box_in), _lib.ptr(box_out), _lib.ptr(box_miss), _lib.ptr(bad),
+                                                           _lib.ptr(box[0]), _lib.ptr(box[1]), _lib.ptr(box[2]), _lib.ptr(bad),
                                                            _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
                        "deftet_point_in_tet_indexed_f32")
     if check and int(bad.item()):
         raise RuntimeError("point_in_tet_indexed: index out of range [0, %d)" % V)
-    out = (cond,) + ((bary,) if want_bary else ()) + ((occ,) if pred is not None else ()) + ((hits,) if want_hits else ())
-    return out if len(out) > 1 else cond
+    return _pit_result(cond, bary, occ, hits, want_hits)
 
 
 def point_in_tet_grid(n_tet, n_query):
@@ -610,6 +614,26 @@ def point_in_tet_bwd(tet_bxtx4x3, pts_bxqx3, cond, grad_w, want_grad_pts=False, 
     return grad_tet, grad_pts
 
 
+def _to_vertices_begin(caller, lib, csr, Bi, B, V, T, pts, want_grad_pts, grad_occ, out):
+    """The checks, outputs and workspace of the two *_bwd_to_vertices, on the queries' device (Bi: the index lists the tets come
+    from, None = the CSR's).  Returns (offsets, slots, Bi, grad_pos, grad_pts, grad_occ as f32, grad_pred, workspace)."""
+    offsets, slots, Bc = csr
+    if Bi is not None and Bc != Bi:
+        raise RuntimeError("%s: the CSR was built over %d index list(s), tet_idx has %d" % (caller, Bc, Bi))
+    if slots.numel() != Bc * T * 4 or offsets.numel() != Bc * V + 1:
+        raise RuntimeError("%s: CSR does not match the tets / n_vertex" % caller)
+    if out is not None and (out.shape != (B, V, 3) or out.dtype != torch.float32 or not out.is_contiguous()):
+        raise RuntimeError("%s: out must be contiguous f32 [B,V,3]" % caller)
+    dev = pts.device
+    grad_pos = out if out is not None else torch.empty(B, V, 3, device=dev, dtype=torch.float32)
+    grad_pts = torch.empty_like(pts) if want_grad_pts else None
+    go = _f32c(grad_occ) if grad_occ is not None else None
+    # (`accumulate` of the C entry covers grad_pos AND grad_pred: a fresh grad_pred must then start from zero)
+    grad_pred = (torch.zeros if out is not None else torch.empty)(B, T, device=dev, dtype=torch.float32) if go is not None else None
+    ws = _lib.workspace(dev, lib.deftet_point_in_tet_bwd_to_vertices_workspace_bytes(B, T, pts.shape[1]))
+    return offsets, slots, Bc, grad_pos, grad_pts, go, grad_pred, ws
+
+
 def point_in_tet_bwd_to_vertices(tet_bxtx4x3, pts_bxqx3, cond, grad_w, csr, n_vertex, want_grad_pts=False, grad_occ=None, hits=None,
                                  out=None):
     """(grad_pos [B,V,3], grad_pts [B,Q,3] | None[, grad_pred [B,T]]): point_in_tet_bwd followed by tet_gather_bwd in one call
@@ -620,28 +644,16 @@ def point_in_tet_bwd_to_vertices(tet_bxtx4x3, pts_bxqx3, cond, grad_w, csr, n_ve
     lib = _lib.load()
     tet, pts, cond, gw = _f32c(tet_bxtx4x3), _f32c(pts_bxqx3), _f32c(cond), _f32c(grad_w)
     B, T, Q, V = tet.shape[0], tet.shape[1], pts.shape[1], int(n_vertex)
-    offsets, slots, Bi = csr
-    if slots.numel() != Bi * T * 4 or offsets.numel() != Bi * V + 1:
-        raise RuntimeError("point_in_tet_bwd_to_vertices: CSR does not match tet / n_vertex")
     dev = pts.device
-    acc = out is not None
-    if acc and (out.shape != (B, V, 3) or out.dtype != torch.float32 or not out.is_contiguous()):
-        raise RuntimeError("point_in_tet_bwd_to_vertices: out must be contiguous f32 [B,V,3]")
-    grad_pos = out if acc else torch.empty(B, V, 3, device=dev, dtype=torch.float32)
-    grad_pts = torch.empty_like(pts) if want_grad_pts else None
-    go = _f32c(grad_occ) if grad_occ is not None else None
-    # (`accumulate` of the C entry covers grad_pos AND grad_pred: a fresh grad_pred must then start from zero)
-    grad_pred = (torch.zeros if acc else torch.empty)(B, T, device=dev, dtype=torch.float32) if go is not None else None
     with _lib.on_device(dev):
-        ws = _lib.workspace(dev, lib.deftet_point_in_tet_bwd_to_vertices_workspace_bytes(B, T, Q))
+        offsets, slots, Bi, grad_pos, grad_pts, go, grad_pred, ws = _to_vertices_begin("point_in_tet_bwd_to_vertices", lib, csr, None, B, V, T,
+                                                                                       pts, want_grad_pts, grad_occ, out)
         _lib.check(lib.deftet_point_in_tet_bwd_to_vertices_f32(_lib.ptr(tet), _lib.ptr(pts), _lib.ptr(cond), _lib.ptr(gw), _lib.ptr(go),
                                                                _lib.ptr(hits), _lib.ptr(offsets), _lib.ptr(slots), Bi, _lib.ptr(grad_pos),
-                                                               _lib.ptr(grad_pts), _lib.ptr(grad_pred), B, V, T, Q, 1 if acc else 0,
+                                                               _lib.ptr(grad_pts), _lib.ptr(grad_pred), B, V, T, Q, 1 if out is not None else 0,
                                                                _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
                    "deftet_point_in_tet_bwd_to_vertices_f32")
-    if go is not None:
-        return grad_pos, grad_pts, grad_pred
-    return grad_pos, grad_pts
+    return (grad_pos, grad_pts) if grad_pred is None else (grad_pos, grad_pts, grad_pred)
 
 
 def point_in_tet_indexed_bwd_to_vertices(pos, tet_idx, pts, cond, grad_w, csr, want_grad_pts=False, grad_occ=None, hits=None, out=None):
@@ -653,30 +665,17 @@ def point_in_tet_indexed_bwd_to_vertices(pos, tet_idx, pts, cond, grad_w, csr, w
     lib = _lib.load()
     cond, gw = _f32c(cond), _f32c(grad_w)
     B, V, T, Q, Bi = pos.shape[0], pos.shape[1], idx.shape[1], pts.shape[1], idx.shape[0]
-    offsets, slots, Bc = csr
-    if Bc != Bi:
-        raise RuntimeError("point_in_tet_indexed_bwd_to_vertices: the CSR was built over %d index list(s), tet_idx has %d" % (Bc, Bi))
-    if slots.numel() != Bi * T * 4 or offsets.numel() != Bi * V + 1:
-        raise RuntimeError("point_in_tet_indexed_bwd_to_vertices: CSR does not match tet_idx / n_vertex")
     dev = pts.device
-    acc = out is not None
-    if acc and (out.shape != (B, V, 3) or out.dtype != torch.float32 or not out.is_contiguous()):
-        raise RuntimeError("point_in_tet_indexed_bwd_to_vertices: out must be contiguous f32 [B,V,3]")
-    grad_pos = out if acc else torch.empty(B, V, 3, device=dev, dtype=torch.float32)
-    grad_pts = torch.empty_like(pts) if want_grad_pts else None
-    go = _f32c(grad_occ) if grad_occ is not None else None
-    grad_pred = (torch.zeros if acc else torch.empty)(B, T, device=dev, dtype=torch.float32) if go is not None else None
     with _lib.on_device(dev):
-        ws = _lib.workspace(dev, lib.deftet_point_in_tet_bwd_to_vertices_workspace_bytes(B, T, Q))
+        offsets, slots, _, grad_pos, grad_pts, go, grad_pred, ws = _to_vertices_begin("point_in_tet_indexed_bwd_to_vertices", lib, csr, Bi, B, V,
+                                                                                      T, pts, want_grad_pts, grad_occ, out)
         _lib.check(lib.deftet_point_in_tet_indexed_bwd_to_vertices_f32(_lib.ptr(pos), _lib.ptr(idx), Bi, _lib.ptr(pts), _lib.ptr(cond),
                                                                        _lib.ptr(gw), _lib.ptr(go), _lib.ptr(hits), _lib.ptr(offsets),
                                                                        _lib.ptr(slots), _lib.ptr(grad_pos), _lib.ptr(grad_pts),
-                                                                       _lib.ptr(grad_pred), B, V, T, Q, 1 if acc else 0, _lib.ptr(ws),
+                                                                       _lib.ptr(grad_pred), B, V, T, Q, 1 if out is not None else 0, _lib.ptr(ws),
                                                                        ws.numel(), _lib.current_stream(dev)),
                    "deftet_point_in_tet_indexed_bwd_to_vertices_f32")
-    if go is not None:
-        return grad_pos, grad_pts, grad_pred
-    return grad_pos, grad_pts
+    return (grad_pos, grad_pts) if grad_pred is None else (grad_pos, grad_pts, grad_pred)
 
 
 def paste_occ_fwd(pred_bxt, cond_bxqx1, clamp_inplace=True):

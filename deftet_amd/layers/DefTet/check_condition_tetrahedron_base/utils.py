@@ -102,6 +102,10 @@ class PointInTetOccVertices(Function):
 
     @staticmethod
     def forward(ctx, vertice_pos, point_pos_bxnx3, pred_tet_occ, topology, tet_bxfx4x3=None):
+        want = (vertice_pos.shape[0], topology.tet_idx.shape[-2], 4, 3)
+        if tet_bxfx4x3 is not None and tuple(tet_bxfx4x3.shape) != want:
+            raise RuntimeError("tet_bxfx4x3 must be the [B,T,4,3] = %s tets gathered from vertice_pos with this topology, got %s"
+                               % (want, tuple(tet_bxfx4x3.shape)))
         tet = tet_bxfx4x3.detach() if tet_bxfx4x3 is not None else hip_ops.tet_gather(vertice_pos, topology.tet_idx)
         rec = hip_ops.bwd_uses_records(tet.shape[1], point_pos_bxnx3.shape[1])
         out = hip_ops.point_in_tet(tet, point_pos_bxnx3, want_bary=True, pred_bxt=pred_tet_occ, want_hits=rec, order="auto",

@@ -127,6 +127,45 @@ def test_tracked_query_boxes_fall_back_to_measuring_when_queries_miss_the_box():
     hip_ops.clear_query_box_cache()
 
 
+def test_tracked_query_boxes_are_bounded():
+    """the trackers live in a bounded cache: more distinct (B, Q) keys than the bound leave at most the bound, the least recently
+    used dropped first."""
+    from deftet_amd import hip_ops
+    hip_ops.clear_query_box_cache()
+    dev = torch.device("cpu", 0)
+    n = hip_ops._CACHE_MAX
+    for q in range(n + 5):
+        hip_ops._tracked_boxes(dev, 1, 100 + q)
+        hip_ops._tracked_boxes(dev, 1, 100)                      # the first key, used again every time: never the oldest
+    keys = hip_ops.query_box_trackers()
+    assert len(keys) == n
+    assert hip_ops.query_box_key(dev, 1, 100 + n + 4) in keys and hip_ops.query_box_key(dev, 1, 100) in keys
+    assert hip_ops.query_box_key(dev, 1, 101) not in keys
+    hip_ops.clear_query_box_cache()
+    assert hip_ops.query_box_trackers() == {}
+
+
+def test_order_check_is_keyed_by_the_tensor_not_its_address():
+    """a caller's order is validated once per tensor object and version: a view of a checked tensor, or a checked
+    tensor changed in place, is checked again — an address key let a recycled block (same data_ptr, version 0) skip the check."""
+    from deftet_amd import hip_ops
+    a = torch.randperm(16).to(torch.int32)
+    hip_ops._check_order(a, 16)
+    a.data[0] = a.data[1]                                        # the content changes, the version counter does not
+    with pytest.raises(RuntimeError, match="permutation"):
+        hip_ops._check_order(a.view(-1), 16)                     # another object at the same address and version
+    b = torch.randperm(16).to(torch.int32)
+    hip_ops._check_order(b, 16)
+    hip_ops._check_order(b.view(-1), 16)                         # a view of a permutation is one
+    b[0] = b[1]                                                  # in place: the version moves
+    with pytest.raises(RuntimeError, match="permutation"):
+        hip_ops._check_order(b, 16)
+    with pytest.raises(RuntimeError, match="int32"):
+        hip_ops._check_order(torch.arange(16), 16)               # int64
+    with pytest.raises(RuntimeError, match="int32"):
+        hip_ops._check_order(torch.arange(15, dtype=torch.int32), 16)
+
+
 @pytest.mark.parametrize("res", [2, 4, 20])
 def test_kuhn_grid_counts_and_orientation(res):
     verts, tets = grids.kuhn_grid(res)

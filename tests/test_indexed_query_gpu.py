@@ -283,6 +283,23 @@ def test_occupancy_query_indexed_inplace_change_raises(cuda):
         (w.sum() + occ.sum()).backward()
 
 
+def test_occupancy_query_rejects_tets_of_another_shape(cuda):
+    """tet_bxfx4x3 handed to occupancy_query must have the [B,T,4,3] shape of (vertice_pos, tetrahedron): its values are used and
+    the gradient goes to vertice_pos, so a tensor of other tets would give wrong gradients silently."""
+    from deftet_amd import hip_ops
+    from deftet_amd.layers.DefTet.deftet import DefTet
+    pos, idx = _mesh(6, 2, cuda)
+    q = torch.from_numpy(grids.random_queries(2, 300)).to(cuda)
+    pred = torch.rand(2, idx.shape[0], device=cuda)
+    m = DefTet(device=cuda)
+    tet = hip_ops.tet_gather(pos, idx)
+    want = m.occupancy_query(pos, idx, q, pred)
+    assert all(torch.equal(a, b) for a, b in zip(m.occupancy_query(pos, idx, q, pred, tet_bxfx4x3=tet), want))
+    for bad in (tet[:1], tet[:, :-1], tet[..., :2].contiguous(), tet.reshape(-1, 4, 3)):
+        with pytest.raises(RuntimeError, match="tet_bxfx4x3"):
+            m.occupancy_query(pos, idx, q, pred, tet_bxfx4x3=bad)
+
+
 def test_occupancy_query_indexed_keeps_no_gathered_tensor(cuda):
     """res 40, B = 8: across a forward with grad enabled the allocated memory rises by less than one [B,T,4,3] tensor (the
     default path keeps exactly that tensor for its backward)."""

@@ -681,6 +681,23 @@ def test_auto_order_without_a_topology_notices_another_mesh(cuda):
     hip_ops.clear_tet_order_cache()
 
 
+def test_auto_order_decisions_are_bounded(cuda):
+    """order="auto" keeps at most _CACHE_MAX decisions (each may hold an int32 [T] order and a pinned mailbox), the least recently
+    used dropped first; a dropped decision is simply decided again."""
+    from deftet_amd import grids, hip_ops
+    tet, pts, _, _ = grids.make_case(20, 3000, 1)
+    t, p = torch.from_numpy(tet).to(cuda), torch.from_numpy(pts).to(cuda)
+    assert t.shape[1] >= 4096                                           # (smaller grids are never ordered)
+    hip_ops.clear_tet_order_cache()
+    n = hip_ops._CACHE_MAX
+    for i in range(n + 3):
+        assert hip_ops.auto_tet_order(t, p, topology="mesh%d" % i) is None
+        hip_ops.auto_tet_order(t, p, topology="mesh0")                  # used again every time: never the oldest
+    keys = [k[3] for k in hip_ops.tet_order_decisions()]
+    assert len(keys) == n and "mesh%d" % (n + 2) in keys and "mesh0" in keys and "mesh1" not in keys
+    hip_ops.clear_tet_order_cache()
+
+
 def test_order_argument_must_be_a_permutation(cuda):
     """A caller's `order` is validated once per tensor: duplicates would skip tets, entries outside [0, T) index the
     tet array and the hit records out of bounds."""
@@ -695,6 +712,8 @@ def test_order_argument_must_be_a_permutation(cuda):
                 good.clone().index_fill_(0, torch.tensor([T - 1], device=cuda), -1)):           # negative
         with pytest.raises(RuntimeError, match="permutation"):
             hip_ops.point_in_tet(t, p, order=bad)
+        with pytest.raises(RuntimeError, match="permutation"):
+            hip_ops.tet_order_coherence(t[0], bad)                      # public, and its kernel dereferences the order too
     good[0], good[1] = int(good[1]), int(good[0])                       # modified in place: checked again, still a permutation
     assert torch.equal(hip_ops.point_in_tet(t, p, order=good), hip_ops.point_in_tet(t, p))
 
