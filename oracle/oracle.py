@@ -44,6 +44,7 @@ def lib():
         build()
         _lib = C.CDLL(LIB_PATH)
         _lib.oracle_point_in_tet_f32_omp.restype = C.c_int
+        _lib.oracle_sparse_render_fwd_policy_f32_omp.restype = C.c_int
     return _lib
 
 
@@ -305,7 +306,9 @@ RASTER_NEAREST, RASTER_FIRST = 0, 1     # which kept faces a saturated pixel rec
 
 
 def sparse_render_fwd(pixel_bxpx2, range_bxpx2, face_z_bxfx3, face_xy_bxfx3x2, face_feat_bxfx3xd, knum=300, eps=1e-8,
-                      policy=RASTER_NEAREST):
+                      policy=RASTER_NEAREST, omp=False):
+    """The rasterizer contract on the CPU.  omp=True splits the pixels across OpenMP threads (as many as OMP_NUM_THREADS says):
+    the same per-pixel code, hence the same bits as the serial entry (tests/test_render_oracle_cpu.py)."""
     pix, rng = _c(pixel_bxpx2, np.float32), _c(range_bxpx2, np.float32)
     fz, fxy, ff = _c(face_z_bxfx3, np.float32), _c(face_xy_bxfx3x2, np.float32), _c(face_feat_bxfx3xd, np.float32)
     B, P = pix.shape[:2]
@@ -313,9 +316,13 @@ def sparse_render_fwd(pixel_bxpx2, range_bxpx2, face_z_bxfx3, face_xy_bxfx3x2, f
     feat = np.zeros((B, P, knum, D), np.float32)
     face = np.zeros((B, P, knum), np.int64)
     w = np.zeros((B, P, knum, 3), np.float32)
-    lib().oracle_sparse_render_fwd_policy_f32(_p(pix, _f32p), _p(rng, _f32p), _p(fz, _f32p), _p(fxy, _f32p), _p(ff, _f32p),
-                                              _p(feat, _f32p), _p(face, _i64p), _p(w, _f32p), B, P, F, D, int(knum), C.c_float(eps),
-                                              int(policy))
+    args = (_p(pix, _f32p), _p(rng, _f32p), _p(fz, _f32p), _p(fxy, _f32p), _p(ff, _f32p),
+            _p(feat, _f32p), _p(face, _i64p), _p(w, _f32p), B, P, F, D, int(knum), C.c_float(eps), int(policy))
+    if omp:
+        if lib().oracle_sparse_render_fwd_policy_f32_omp(*args) != 0:
+            raise MemoryError("the render oracle could not allocate its per-thread hit buffers")
+    else:
+        lib().oracle_sparse_render_fwd_policy_f32(*args)
     return feat, face, w
 
 

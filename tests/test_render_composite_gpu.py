@@ -263,6 +263,41 @@ def test_baseline_config(cuda, oracle, policy):
         assert e_fus <= 1.5 * e_unf + 1e-7, (k, e_fus, e_unf)
 
 
+@pytest.mark.parametrize("depth", [False, True])
+@pytest.mark.parametrize("policy", [NEAREST, FIRST])
+def test_baseline_forward_vs_oracle_layers(cuda, oracle, policy, depth):
+    """test_baseline_config proves fused == unfused, and both start from the kernel's own faces.  Here the fused forward at
+    BASELINE configs[4] is held against the CPU oracle on the 16,384 chosen pixels of tests/raster_scene.py: the same faces in the
+    same order, and colour / coverage / depth against alpha_composite evaluated in fp64 on the ORACLE's fp32 layers.  The error
+    bound is the unfused path's own error against that value (deftet_sparse_render + alpha_composite in fp32) times 1.5 plus
+    1e-7 — the rule test_baseline_config uses for the gradients — and 1e-5 absolute on colour and coverage, which lie in
+    [0, 1]; the depth (up to |far_depth| = 6 in magnitude) gets 1e-5 of its largest entry."""
+    from deftet_amd.render import alpha_composite
+    from tests import raster_scene as RS
+    from tests.tol import check_close
+    pix, rngs, fz, fxy, ff = RS.scene("baseline")
+    sel = RS.selection("baseline").sel
+    wfeat, wface, _ = RS.oracle_rows("baseline", 64, policy)
+    assert len(sel) >= 16384 and (wface[0, :, -1] >= 0).mean() > 0.5 and (wface[0, :, 0] < 0).any()      # full rows and empty ones
+    layers = torch.from_numpy(wfeat).double()
+    want = alpha_composite(layers[..., 1:], layers[..., :1]) if depth else alpha_composite(layers)
+    rows = torch.from_numpy(sel).to(cuda)
+    t = to_dev(cuda, pix, rngs, fz, fxy, ff)
+    with torch.no_grad():
+        c0, v0, d0, _ = unfused(*t, 64, policy, depth)
+        c1, v1, d1, face = fused(*t, 64, policy, depth)
+    assert np.array_equal(face[0, rows].cpu().numpy(), wface[0])
+    tag = "configs[4] 16 k chosen pixels k64 policy %d depth %d vs fp64 composite of the oracle's layers" % (policy, int(depth))
+    for nm, w64, unf, fus in (("colour", want[0], c0, c1), ("coverage", want[1], v0, v1)) + ((("depth", want[2], d0, d1),) if depth else ()):
+        scale = w64.abs().max().item()
+        assert 0.5 < scale <= (1.0 if nm != "depth" else 6.0) + 1e-6
+        bound = 1e-5 / scale if nm != "depth" else 1e-5                        # check_close measures relative to the largest entry
+        e_unf = check_close("unfused %s, %s" % (nm, tag), unf[:, rows], w64, bound)[0] * scale
+        e_fus = check_close("fused %s, %s" % (nm, tag), fus[:, rows], w64, bound)[0] * scale
+        print("%s: fused %.3g, unfused %.3g (absolute, policy %d depth %d)" % (nm, e_fus, e_unf, policy, int(depth)))
+        assert e_fus <= 1.5 * e_unf + 1e-7, (nm, e_fus, e_unf)
+
+
 # ---------------------------------------------------------------------------------------------------------------- 6
 def test_memory_without_the_layer_stack(cuda):
     fz, fxy, ff = projected_grid(70)
