@@ -437,8 +437,8 @@ static inline int pin_shapes(int Q) { return (size_t)Q * 36 <= ((size_t)4 << 20)
 // (Round-1 history: one returning global atomicAdd per query = 800 k fabric transactions = 41 us;
 // random-address global atomics run at ~23-26 G/s chip-wide at ANY scope, tools/probes/.)
 // Two levels, both with LDS atomics only, two launches:
-//   k_slab_local: every workgroup sorts ITS chunk of <= kRowTile queries by first-level bin (slab cz, y-eighth) into its
-//         own segment of `localQ` and publishes the exclusive bin prefix of the chunk (pre[bin][block]);
+//   k_slab_local: every workgroup sorts ITS chunk of <= kRowTile queries by first-level bin (slab cz, y-quarter) into its
+//         own segment of `localQ` and publishes the exclusive bin prefix of the chunk (pre[block][bin]);
 //   k_slab_sort:  one workgroup per (slab, shape) gathers the slab's runs from all chunk segments (a run per chunk,
 //         contiguous), counts per (cy, cx) cell in LDS, scans, writes its plane of the transposed cell-start table with
 //         coalesced stores and places the queries.
@@ -454,15 +454,25 @@ constexpr int kMaxRowBlocks = 256;   // chunks per shape (k_slab_sort handles on
 #define PIT_ROWTILE 2048
 #endif
 constexpr int kRowTile = PIT_ROWTILE;  // smallest query chunk per workgroup
-constexpr int kLocalKeep = kRowTile / 256;   // queries a thread keeps in registers between the two passes
-// First-level bins: (slab, y-eighth of the cell rows).  The second level works on y-quarters of a slab (two adjacent
-// sub-bins = one contiguous run per chunk): a quarter's (cy, cx) counters need ~10 KB of LDS, so several workgroups
-// share a compute unit (a whole slab needs 40 KB at configs[2], and only 64 KB per CU are handed out to kernels that do
-// not opt into the large-LDS mode: one workgroup per CU, 17 us instead of 6).
-constexpr int kSub = 8;
+#ifndef PIT_LOCAL_THREADS
+#define PIT_LOCAL_THREADS 512
+#endif
+// threads of a k_slab_local workgroup: 392 chunks of configs[2] are 1.5 workgroups per compute unit, so a chunk's chain (loads ->
+// LDS atomics -> scan -> stores) is what the launch waits for; eight waves walk it with four queries per thread instead of eight
+// (256 / 512 / 1024 threads: 12.7 / 11.9 / 13.8 us beside the other changes of that commit)
+constexpr int kLocalThreads = PIT_LOCAL_THREADS;
+constexpr int kLocalWaves = kLocalThreads / 64;
+constexpr int kLocalKeep = kRowTile / kLocalThreads;   // queries a thread keeps in registers between the two passes
+static_assert(kLocalThreads % 64 == 0 && kLocalKeep * kLocalThreads == kRowTile, "whole waves, whole trips over a chunk");
+// First-level bins: (slab, y-quarter of the cell rows) — the granularity the second level consumes: one workgroup per bin, its
+// run in a chunk's segment contiguous.  A quarter's (cy, cx) counters need ~10 KB of LDS, so several workgroups share a compute
+// unit (a whole slab needs 40 KB at configs[2]: one workgroup per CU, 17 us instead of 6).  (Until the row-major `pre` the
+// first level binned y-eighths, two per second-level workgroup: twice the prefixes to scan and store for nothing — 14.3 -> 12.9 us
+// for k_slab_local at configs[2].)
+constexpr int kSub = 4;
 constexpr int kParts = 4;                  // second-level workgroups per slab
 constexpr int kSubPerPart = kSub / kParts;
-constexpr int kMaxBin1 = kMaxG * kSub;     // 896
+constexpr int kMaxBin1 = kMaxG * kSub;     // 448
 
 // HINT (query_box_in given): the grid comes from the box the caller handed in (hint_grid) and k_query_bbox is not launched,
 // so this kernel also does what that launch did besides measuring — the result sentinels of its chunk — and measures for
@@ -471,15 +481,15 @@ constexpr int kMaxBin1 = kMaxG * kSub;     // 896
 // counter (nobody has zeroed one): irregQ[q0 + i], i < irrCnt[chunk]; k_slab_sort compacts the lists and sets the counters.
 // irrCnt[nShapes * kMaxRowBlocks + chunk] counts the chunk's regular queries OUTSIDE the hint on their own (query_box_misses).
 template <bool HINT>
-__global__ __launch_bounds__(256) void k_slab_local(const float *__restrict__ pts, int Q, const float *__restrict__ bboxPart,
-                                                    float *gparam, int G, int Gx, int nblk, int nblkPad, int chunkQ,
+__global__ __launch_bounds__(kLocalThreads) void k_slab_local(const float *__restrict__ pts, int Q, const float *__restrict__ bboxPart,
+                                                    float *gparam, int G, int Gx, int nblk, int prePitch, int chunkQ,
                                                     float4 *localQ, int *pre, int *counters, int *irregQ,
                                                     const float *__restrict__ boxIn, float *partOut, int *irrCnt, int *result)
 {
     __shared__ int hist[kMaxBin1 + 1];
-    __shared__ int wtot[4];
+    __shared__ int wtot[kLocalWaves];
     __shared__ int s_irr, s_out;
-    __shared__ float s_box[4][6];
+    __shared__ float s_box[kLocalWaves][6];
     const int b = blockIdx.y, blk = blockIdx.x, R1 = G * kSub, tid = threadIdx.x;
     const int q0 = blk * chunkQ, q1 = min(Q, q0 + chunkQ);
     const bool keep = chunkQ <= kRowTile;                          // launch-uniform: the chunk fits the register file
@@ -487,12 +497,12 @@ __global__ __launch_bounds__(256) void k_slab_local(const float *__restrict__ pt
     if (keep) {                                                    // issued BEFORE the box reduction: its loads and shuffles wait
 #pragma unroll                                                     // on nothing these need
         for (int k = 0; k < kLocalKeep; ++k) {                     // unconditional (clamped) loads: all in flight at once
-            const float *p = pts + ((size_t)b * Q + max(min(q0 + tid + k * 256, q1 - 1), 0)) * 3;
+            const float *p = pts + ((size_t)b * Q + max(min(q0 + tid + k * kLocalThreads, q1 - 1), 0)) * 3;
             kp[k] = make_float3(p[0], p[1], p[2]);
         }
     }
     if (HINT) {
-        for (int q = q0 + tid; q < q1; q += 256) result[(size_t)b * Q + q] = kMiss;
+        for (int q = q0 + tid; q < q1; q += kLocalThreads) result[(size_t)b * Q + q] = kMiss;
         if (tid == 0) { s_irr = 0; s_out = 0; }
     }
     const Grid g = HINT ? hint_grid(boxIn + (size_t)b * 6, G, Gx) : reduce_grid(bboxPart + (size_t)b * kBoxBlocks * 6, kBoxBlocks, G, Gx);
@@ -520,18 +530,18 @@ __global__ __launch_bounds__(256) void k_slab_local(const float *__restrict__ pt
         gp[18] = __int_as_float(wide_cells(g, Q, G, Gx));
         gp[19] = HINT ? 1.0f : 0.f;                                  // k_finalize: with a measured box every regular query is binned (no test needed)
     }
-    for (int i = tid; i <= R1; i += 256) hist[i] = 0;
+    for (int i = tid; i <= R1; i += kLocalThreads) hist[i] = 0;
     __syncthreads();
     const float rcpG = 1.0f / (float)G;
     int kbin[kLocalKeep], krank[kLocalKeep];
-    auto bin_of = [&](float x, float y, float z) {                 // (cz, y-eighth of the CELL row: sub = (cy * 8) / G exactly,
+    auto bin_of = [&](float x, float y, float z) {                 // (cz, y-quarter of the CELL row: sub = (cy * kSub) / G exactly,
         const int cy = cell_of(y, g.o[1], g.inv[1], G);            //  +0.5 keeps the quotient away from the integers)
         return cell_of(z, g.o[2], g.inv[2], G) * kSub + (int)(((float)(cy * kSub) + 0.5f) * rcpG);
     };
     if (keep) {
 #pragma unroll
         for (int k = 0; k < kLocalKeep; ++k) {
-            const int q = q0 + tid + k * 256;
+            const int q = q0 + tid + k * kLocalThreads;
             kbin[k] = -1;
             if (q < q1) {
                 box_add(kp[k].x, kp[k].y, kp[k].z);
@@ -544,7 +554,7 @@ __global__ __launch_bounds__(256) void k_slab_local(const float *__restrict__ pt
             }
         }
     } else {
-        for (int q = q0 + tid; q < q1; q += 256) {
+        for (int q = q0 + tid; q < q1; q += kLocalThreads) {
             const float *p = pts + ((size_t)b * Q + q) * 3;
             const float x = p[0], y = p[1], z = p[2];
             box_add(x, y, z);
@@ -570,7 +580,7 @@ __global__ __launch_bounds__(256) void k_slab_local(const float *__restrict__ pt
     if (HINT) {
         if (tid < 6) {
             float v = s_box[0][tid];
-            for (int i = 1; i < 4; ++i) v = tid < 3 ? fminf(v, s_box[i][tid]) : fmaxf(v, s_box[i][tid]);
+            for (int i = 1; i < kLocalWaves; ++i) v = tid < 3 ? fminf(v, s_box[i][tid]) : fmaxf(v, s_box[i][tid]);
             partOut[((size_t)b * kMaxRowBlocks + blk) * 6 + tid] = v;
         }
         if (tid == 0) {
@@ -579,8 +589,8 @@ __global__ __launch_bounds__(256) void k_slab_local(const float *__restrict__ pt
         }
     }
     {   // exclusive scan of the R1 counts (<= 4 consecutive bins per thread); hist[R1] = number of regular queries
-        constexpr int kPer = (kMaxBin1 + 255) / 256;               // 4
-        const int per = (R1 + 255) / 256, i0 = tid * per;
+        constexpr int kPer = (kMaxBin1 + kLocalThreads - 1) / kLocalThreads;
+        const int per = (R1 + kLocalThreads - 1) / kLocalThreads, i0 = tid * per;
         int n[kPer], sum = 0;
 #pragma unroll
         for (int j = 0; j < kPer; ++j) {
@@ -598,26 +608,26 @@ __global__ __launch_bounds__(256) void k_slab_local(const float *__restrict__ pt
         __syncthreads();
         int run = incl - sum;
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
+        for (int k = 0; k < kLocalWaves; ++k)
             if (k < w) run += wtot[k];
-        int *col = pre + (size_t)b * (R1 + 1) * nblkPad + blk;     // pre[bin][chunk]: a slab workgroup reads rows of it
+        int *row = pre + ((size_t)b * nblk + blk) * prePitch;      // pre[chunk][bin]: the chunk's prefixes leave as one contiguous store stream
 #pragma unroll
         for (int j = 0; j < kPer; ++j)
             if (j < per && i0 + j < R1) {
                 hist[i0 + j] = run;
-                col[(size_t)(i0 + j) * nblkPad] = run;
+                row[i0 + j] = run;
                 run += n[j];
             }
-        if (tid == 255) col[(size_t)R1 * nblkPad] = run;           // thread 255 holds the grand total after its own bins
+        if (tid == kLocalThreads - 1) row[R1] = run;               // the last thread holds the grand total after its own bins
     }
     __syncthreads();
     float4 *dst = localQ + (size_t)b * Q + q0;
     if (keep) {
 #pragma unroll
         for (int k = 0; k < kLocalKeep; ++k)
-            if (kbin[k] >= 0) dst[hist[kbin[k]] + krank[k]] = make_float4(kp[k].x, kp[k].y, kp[k].z, __int_as_float(q0 + tid + k * 256));
+            if (kbin[k] >= 0) dst[hist[kbin[k]] + krank[k]] = make_float4(kp[k].x, kp[k].y, kp[k].z, __int_as_float(q0 + tid + k * kLocalThreads));
     } else {
-        for (int q = q0 + tid; q < q1; q += 256) {
+        for (int q = q0 + tid; q < q1; q += kLocalThreads) {
             const float *p = pts + ((size_t)b * Q + q) * 3;
             const float x = p[0], y = p[1], z = p[2];
             if (binned(x, y, z)) dst[atomicAdd(&hist[bin_of(x, y, z)], 1)] = make_float4(x, y, z, __int_as_float(q));
@@ -625,7 +635,7 @@ __global__ __launch_bounds__(256) void k_slab_local(const float *__restrict__ pt
     }
 }
 
-// One workgroup per (slab, y-quarter, shape).  Thread k < nblk owns the part's run in chunk k (pre[.][k] gives its offset
+// One workgroup per (slab, y-quarter, shape).  Thread k < nblk owns the part's run in chunk k (pre[k][.] gives its offset
 // and length); the block sums the offsets (= queries in lower bins = the part's start in sortedQ) and scans the lengths.
 // Then: gather, count per (cy, cx) cell in LDS, exclusive scan in (cy, cx) order, placement, and the part's rows of the
 // slab's plane of the transposed cell-start table.  Parts of up to kSortThreads * kSortKeep queries (the usual case) keep
@@ -637,18 +647,18 @@ constexpr int kSortThreads = PIT_SORT_THREADS;
 constexpr int kSortKeep = 1024 / kSortThreads;                        // queries a thread keeps in registers
 constexpr int kRunsPer = kMaxRowBlocks / kSortThreads;               // chunk runs per thread (consecutive chunks)
 static_assert(kRunsPer * kSortThreads == kMaxRowBlocks && kSortThreads % 64 == 0, "every chunk run has a thread");
-// boxPart / boxOut (query_box_out): the workgroup of a shape's first slab part also reduces the nPart per-block boxes of the
-// queries (k_query_bbox's, or k_slab_local<true>'s) into the box the caller gets back.  hint: k_slab_local<true> ran instead
+// boxPart / boxOut (query_box_out): block 0 of a shape (the grid has one workgroup more than slab parts) reduces the nPart per-block
+// boxes of the queries (k_query_bbox's, or k_slab_local<true>'s) into the box the caller gets back.  hint: k_slab_local<true> ran instead
 // of k_query_bbox — the same workgroup compacts the chunks' lists of unbinned queries (forward copy: a list's place in the
 // compact list never lies behind its own segment) and sets the counters the traversal and k_finalize read.
 __global__ __launch_bounds__(kSortThreads) void k_slab_sort(const float4 *__restrict__ localQ, int Q, const float *__restrict__ gparam,
-                                                            int G, int Gx, const int *__restrict__ pre, int nblk, int nblkPad,
+                                                            int G, int Gx, const int *__restrict__ pre, int nblk, int prePitch,
                                                             int chunkQ, long long cellStride, int *table, float4 *sortedQ, int pin,
                                                             const float *__restrict__ boxPart, int nPart, int partStride, float *boxOut,
                                                             int hint, const int *__restrict__ irrCnt, int *irregQ, int *counters,
                                                             int *missOut)
 {
-    if (shape_block(pin).y == 0 && (boxOut || hint)) {               // (block-uniform; before the sort proper: nothing below depends on it)
+    if (shape_block(pin).y == 0) {                                   // a workgroup of its own per shape, dispatched first: no sorting workgroup is lengthened by this
         const int b0 = shape_block(pin).x, nB = gridDim.y;
         if (boxOut && threadIdx.x < 64) {
             float lo[3], hi[3];
@@ -680,16 +690,18 @@ __global__ __launch_bounds__(kSortThreads) void k_slab_sort(const float4 *__rest
                 if (missOut) missOut[b0] = nOut;                     // (may be host-mapped memory: one posted store per shape)
             }
         }
+        return;
     }
     extern __shared__ __attribute__((aligned(16))) int cnt[];       // [rows of the part][GxP] counts -> starts (-> placement cursors)
     __shared__ int wsum[kSortThreads / 64], wsum2[kSortThreads / 64];
     __shared__ int runStart[kMaxRowBlocks + 1], runSrc[kMaxRowBlocks];
-    const int2 sb = shape_block(pin);                               // the runs are gathered from all over the shape's localQ
+    const int2 sb0 = shape_block(pin);                              // the runs are gathered from all over the shape's localQ
+    const int2 sb = make_int2(sb0.x, sb0.y - 1);                    // (block 0 of the shape is the one above)
     const int b = sb.x, cz = sb.y / kParts, part = sb.y % kParts, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int GxP = Gx | 1;                                         // odd pitch: the transposed read below is conflict-free
     // cell rows of this part: (cy * kSub) / G in [part * kSubPerPart, (part + 1) * kSubPerPart)
     const int cyLo = (part * kSubPerPart * G + kSub - 1) / kSub, cyHi = ((part + 1) * kSubPerPart * G + kSub - 1) / kSub;
-    const int nb = (cyHi - cyLo) * GxP, R1 = G * kSub;
+    const int nb = (cyHi - cyLo) * GxP;
     const int binLo = cz * kSub + part * kSubPerPart;
     PHASE_DECL;
     SPAN_MARK(0);
@@ -700,9 +712,9 @@ __global__ __launch_bounds__(kSortThreads) void k_slab_sort(const float4 *__rest
         const int r = tid * kRunsPer + j;
         a[j] = 0; len[j] = 0;
         if (r < nblk) {
-            const int *row = pre + (size_t)b * (R1 + 1) * nblkPad;
-            a[j] = row[(size_t)binLo * nblkPad + r];
-            len[j] = row[(size_t)(binLo + kSubPerPart) * nblkPad + r] - a[j];
+            const int *row = pre + ((size_t)b * nblk + r) * prePitch + binLo;   // two neighbouring words of the chunk's row
+            a[j] = row[0];
+            len[j] = row[kSubPerPart] - a[j];
         }
         asum += a[j];
         lsum += len[j];
@@ -757,7 +769,9 @@ __global__ __launch_bounds__(kSortThreads) void k_slab_sort(const float4 *__rest
     int kbin[kSortKeep], krank[kSortKeep];
     if (keep) {
 #pragma unroll
-        for (int k = 0; k < kSortKeep; ++k) kq[k] = src[source_of(max(min(tid + k * kSortThreads, n - 1), 0))];   // clamped, unconditional
+        for (int k = 0; k < kSortKeep; ++k)                         // clamped, unconditional within the trips the part reaches (block-uniform
+            if (k == 0 || k * kSortThreads < n)                     // test): a part of configs[2] holds ~360 queries, two of the four trips —
+                kq[k] = src[source_of(max(min(tid + k * kSortThreads, n - 1), 0))];   // the other two were binary searches and loads for nothing
     }
     PHASE_MARK(8);                                                  // [8] runs + loads issued + LDS cleared
     if (keep) {
@@ -3270,7 +3284,7 @@ struct Layout {
     size_t bytes;
     float *bboxPart, *chunkBox;
     int *irrCnt;
-    int nblkPad;
+    int prePitch;
     int *counters, *table, *pre, *result, *irregT, *irregQ;
     float4 *localQ, *sortedQ;
     float *rec, *gparam;
@@ -3297,8 +3311,8 @@ static Layout make_layout(int B, int T, int Q, int algo, void *ws, size_t wsByte
         L.counters = A.take<int>((size_t)B * (8 + kOvfCap));  // 4 counters + 4 statistics words per shape, then the overflowed-tet lists
         L.gparam = A.take<float>((size_t)B * kGridWords);
         L.table = A.take<int>((size_t)B * L.cellStride);
-        L.nblkPad = (L.nRowBlk + 15) / 16 * 16;
-        L.pre = A.take<int>((size_t)B * (L.G * kSub + 1) * L.nblkPad);
+        L.prePitch = (L.G * kSub + 1 + 31) / 32 * 32;               // words between two chunks' rows of pre (whole 128-byte lines)
+        L.pre = A.take<int>((size_t)B * L.nRowBlk * L.prePitch);
         L.localQ = A.take<float4>((size_t)B * Q);
         L.sortedQ = A.take<float4>((size_t)B * Q);
         L.irregT = A.take<int>((size_t)B * T);
@@ -3359,17 +3373,17 @@ static int pit_check(const float *tet, const float *pts, const float *cond, cons
 static int pit_prepare(const Layout &L, const float *pts, int B, int Q, hipStream_t st, const float *boxIn = nullptr, float *boxOut = nullptr,
                        int32_t *missOut = nullptr)
 {
-    const dim3 blk(256);
+    const dim3 blk(256), lblk(kLocalThreads);
     if (boxIn) {                                                         // two launches: the grid spans the box handed in
-        DEFTET_LAUNCH(k_slab_local<true>, dim3(L.nRowBlk, B), blk, st, pts, Q, L.bboxPart, L.gparam, L.G, L.Gx, L.nRowBlk, L.nblkPad, L.chunkQ,
+        DEFTET_LAUNCH(k_slab_local<true>, dim3(L.nRowBlk, B), lblk, st, pts, Q, L.bboxPart, L.gparam, L.G, L.Gx, L.nRowBlk, L.prePitch, L.chunkQ,
                       L.localQ, L.pre, L.counters, L.irregQ, boxIn, L.chunkBox, L.irrCnt, L.result);
     } else {
         DEFTET_LAUNCH(k_query_bbox, dim3(kBoxBlocks, B), blk, st, pts, Q, L.bboxPart, L.counters, L.result, B, (long long)B * Q);
-        DEFTET_LAUNCH(k_slab_local<false>, dim3(L.nRowBlk, B), blk, st, pts, Q, L.bboxPart, L.gparam, L.G, L.Gx, L.nRowBlk, L.nblkPad, L.chunkQ,
+        DEFTET_LAUNCH(k_slab_local<false>, dim3(L.nRowBlk, B), lblk, st, pts, Q, L.bboxPart, L.gparam, L.G, L.Gx, L.nRowBlk, L.prePitch, L.chunkQ,
                       L.localQ, L.pre, L.counters, L.irregQ, (const float *)nullptr, (float *)nullptr, (int *)nullptr, (int *)nullptr);
     }
     const size_t shm = align_up((size_t)((L.G + kParts - 1) / kParts + 1) * (L.Gx | 1) * sizeof(int), 16);   // rows of a y-quarter
-    DEFTET_LAUNCH_SHM(k_slab_sort, dim3(L.G * kParts, B), dim3(kSortThreads), shm, st, L.localQ, Q, L.gparam, L.G, L.Gx, L.pre, L.nRowBlk, L.nblkPad,
+    DEFTET_LAUNCH_SHM(k_slab_sort, dim3(L.G * kParts + 1, B), dim3(kSortThreads), shm, st, L.localQ, Q, L.gparam, L.G, L.Gx, L.pre, L.nRowBlk, L.prePitch,
                       L.chunkQ, L.cellStride, L.table, L.sortedQ, (size_t)Q * 16 <= ((size_t)4 << 20),
                       (const float *)(boxIn ? L.chunkBox : L.bboxPart), boxIn ? L.nRowBlk : kBoxBlocks, boxIn ? kMaxRowBlocks : kBoxBlocks, boxOut,
                       boxIn ? 1 : 0, (const int *)L.irrCnt, L.irregQ, L.counters, (int *)(boxIn ? missOut : nullptr));
@@ -3561,6 +3575,20 @@ extern "C" int deftet_point_in_tet_read_stats(const void *workspace, size_t work
             out_host[b * 8 + k] = tmp[(size_t)b * 4 + k];
             out_host[b * 8 + 4 + k] = tmp[(size_t)B * 4 + (size_t)b * 4 + k];
         }
+    return DEFTET_OK;
+}
+
+// Tests: where a prepared workspace keeps the sorted queries.  out8 = G, Gx, table words per shape, then the byte offsets of
+// the grid parameters (kGridWords floats per shape: origin xyz, cells per unit xyz, ...), the cell-start table, sortedQ
+// (float4: x, y, z, query index as bits), the counters (4 ints per shape; [1] = unbinned queries) and the unbinned list.
+// Not part of the public header: the layout is the library's own.
+extern "C" int deftet_debug_point_in_tet_layout(int B, int T, int Q, int algo, long long *out8)
+{
+    DEFTET_CHECK_ARG(out8 && B > 0 && T >= 0 && Q >= 0 && algo != DEFTET_PIT_BRUTE, "bad argument");
+    const Layout L = make_layout(B, T, Q, algo, nullptr, 0);
+    auto off = [](const void *p) { return (long long)reinterpret_cast<uintptr_t>(p); };
+    out8[0] = L.G; out8[1] = L.Gx; out8[2] = L.cellStride;
+    out8[3] = off(L.gparam); out8[4] = off(L.table); out8[5] = off(L.sortedQ); out8[6] = off(L.counters); out8[7] = off(L.irregQ);
     return DEFTET_OK;
 }
 
