@@ -131,6 +131,12 @@ SIGNATURES = {
     "deftet_nn_distance_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "deftet_surface_metrics_workspace_bytes": (_sz, [_i]),
     "deftet_surface_metrics_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
+    "deftet_tet_face_neighbours_i64": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "deftet_surface_extract_workspace_bytes": (_sz, [_i, _i, _i]),
+    "deftet_surface_extract_count_f32": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, C.c_double, _vp, _vp, _sz, _vp]),
+    "deftet_surface_extract_fill_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, C.c_double, _ll, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "deftet_surface_weld_workspace_bytes": (_sz, [_i]),
+    "deftet_surface_weld_f32": (_i, [_vp, _ll, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lock = threading.Lock()

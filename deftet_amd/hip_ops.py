@@ -1622,3 +1622,198 @@ class _TetEnergies(torch.autograd.Function):
 def tet_energies(tet_bxfx4x3, inverse_v=None, pow_v=4, pow_e=4, scale=20.0):
     """f32 [B,3] = (volume_variance, amips_energy, edge_length) — differentiable w.r.t. tet."""
     return _TetEnergies.apply(tet_bxfx4x3, inverse_v, pow_v, pow_e, scale)
+
+
+# --------------------------------------------------------------------------------- surface extraction (DESIGN.md §6g)
+SX_BINARY, SX_THRESHOLD = 0, 1                          # include/deftet_hip.h DEFTET_SX_*
+_SX_MODES = {"binary": SX_BINARY, "threshold": SX_THRESHOLD, SX_BINARY: SX_BINARY, SX_THRESHOLD: SX_THRESHOLD}
+SurfaceSoup = collections.namedtuple("SurfaceSoup", "face face_attr index faces")
+
+
+class TetFaceNeighbours:
+    """nbr[t][i] = the tet across LOCAL FACE i of tet t, -1 where no other tet owns the face: `table` int64 [T,4] for torch
+    indexing, `table32` int32 [T,4] for the kernels (16 bytes per tet).  Built once per topology."""
+    __slots__ = ("table", "table32", "n_tet", "device")
+
+    def __init__(self, table, table32):
+        self.table, self.table32 = table, table32
+        self.n_tet, self.device = int(table32.shape[0]), table32.device
+
+
+def tet_face_neighbours(tet_list, n_point, device):
+    """TetFaceNeighbours of a tet list — row t of the i-th matrix of tet_adj_share (utils/lib/tet_adj_share/run.cpp:40-97,
+    diff_render/diftet_6_subdiv/3_model/utils_tetsv.py:16-75) as one table.  Raises ValueError when a face has more than two
+    owners, as both reference functions do."""
+    lib = _lib.load()
+    dev = torch.device(device)
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise _lib.DefTetHipError("deftet_amd operators need a GPU (got device %s); there is no CPU fallback" % dev)
+    _f3, t2, tf2, _b3, n_multi = tet_to_face(tet_list, n_point, dev, with_boundary=True)
+    if n_multi:
+        raise ValueError("%d faces are shared by more than two tetrahedra" % n_multi)
+    T = int(torch.as_tensor(tet_list).shape[0])
+    if T == 0:
+        raise ValueError("tet_face_neighbours: empty tet list")
+    n64 = torch.empty(T, 4, dtype=torch.int64, device=dev)
+    n32 = torch.empty(T, 4, dtype=torch.int32, device=dev)
+    with _lib.on_device(dev):
+        _lib.check(lib.deftet_tet_face_neighbours_i64(_lib.ptr(t2), _lib.ptr(tf2), int(t2.shape[0]), T, _lib.ptr(n64), _lib.ptr(n32),
+                                                      _lib.current_stream(dev)), "deftet_tet_face_neighbours_i64")
+    return TetFaceNeighbours(n64, n32)
+
+
+def adj_list_table(adj_list):
+    """numpy int64 [T,4] neighbour table by local face from the reference's list of four [T,T] sparse matrices (scipy, or torch
+    sparse COO).  A row holds at most one nonzero (a local face has one partner) and its value is 1; anything else raises."""
+    if len(adj_list) != 4:
+        raise ValueError("tet_adj: four sparse matrices expected, got %d" % len(adj_list))
+    T = int(adj_list[0].shape[0])
+    table = -np.ones((T, 4), np.int64)
+    for i, adj in enumerate(adj_list):
+        if tuple(adj.shape) != (T, T):
+            raise ValueError("tet_adj[%d] is %s, expected (%d, %d)" % (i, tuple(adj.shape), T, T))
+        if isinstance(adj, torch.Tensor):
+            adj = (adj if adj.layout == torch.sparse_coo else adj.to_sparse()).coalesce()
+            row, col = (x.cpu().numpy() for x in adj.indices())
+            val = adj.values().cpu().numpy()
+        else:
+            adj = adj.tocoo(copy=True)
+            adj.sum_duplicates()
+            row, col, val = adj.row, adj.col, adj.data
+        keep = val != 0
+        row, col, val = row[keep], col[keep], val[keep]
+        if row.size and np.bincount(row, minlength=T).max() > 1:
+            raise ValueError("tet_adj[%d]: a row holds more than one nonzero" % i)
+        if not (val == 1).all():
+            raise ValueError("tet_adj[%d]: values other than 1" % i)
+        table[row, i] = col
+    return table
+
+
+def neighbours_from_adj_list(adj_list, device):
+    """TetFaceNeighbours from a TetFaceNeighbours (returned as it is) or the reference's list of four sparse matrices
+    (adj_list_table + one upload).  Nothing is cached behind the caller's back: convert once per topology and hand the returned
+    object to the drop-ins as `tet_adj` — a list is converted again on every call."""
+    if isinstance(adj_list, TetFaceNeighbours):
+        return adj_list
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.DefTetHipError("deftet_amd operators need GPU tensors (got device %s); there is no CPU fallback" % dev)
+    t64 = torch.from_numpy(adj_list_table(adj_list)).to(dev)
+    return TetFaceNeighbours(t64, t64.to(torch.int32))
+
+
+def surface_extract(tet_bxfx4x3, occ, nbr, mode, thres=None, attr=None, vertex_weights=None, tet_idx=None, return_index=False,
+                    return_faces=False):
+    """Triangle soup of a per-tet occupancy: SurfaceSoup(face, face_attr, index, faces), each a list of B tensors (or None) with
+    rows in ascending (tet, local face) order — face f32 [F_b,3,3]; face_attr f32 [F_b,3,C] with attr f32 [B,T,4,C];
+    index int64 [F_b,2] = (tet, local face); faces int64 [F_b,3] = vertex ids through tet_idx [T,4].
+    mode "binary": utils/tet_utils.py:427-471; mode "threshold" with thres = htres: utils_tetsv.py:79-128, 145-225.
+    occ f32 [B,T] / [B,T,1], or None with vertex_weights f32 [B,V] (or [V] for one shape) and tet_idx: occ = max of the four
+    corner weights (3_model/deftet.py:522-523).  No gradient: gather with `index` for one.  One read-back (the offsets)."""
+    lib = _lib.load()
+    if mode not in _SX_MODES:
+        raise ValueError("surface_extract: mode %r is neither 'binary' nor 'threshold'" % (mode,))
+    mode = _SX_MODES[mode]
+    if mode == SX_THRESHOLD and thres is None:
+        raise ValueError("surface_extract: mode 'threshold' needs thres")
+    if not isinstance(nbr, TetFaceNeighbours):
+        raise TypeError("surface_extract: nbr must be a TetFaceNeighbours (tet_face_neighbours / neighbours_from_adj_list)")
+    if attr is not None and (attr.dim() != 4 or not 1 <= int(attr.shape[3]) <= 8):
+        raise _lib.DefTetHipError("surface_extract: attr [B,T,4,C] with 1 <= C <= 8 expected, got %s (DEFTET_EINVAL)" % (tuple(attr.shape),))
+    _lib.require_gpu(tet_bxfx4x3, occ, attr, vertex_weights, nbr.table32)
+    if (occ is None) == (vertex_weights is None):
+        raise ValueError("surface_extract: exactly one of occ and vertex_weights")
+    tet = _f32c(tet_bxfx4x3)
+    if tet.dim() != 4 or tuple(tet.shape[2:]) != (4, 3):
+        raise RuntimeError("surface_extract: tet [B,T,4,3] expected, got %s" % (tuple(tet.shape),))
+    B, T = int(tet.shape[0]), int(tet.shape[1])
+    dev = tet.device
+    if nbr.n_tet != T or nbr.device != dev:
+        raise RuntimeError("surface_extract: the neighbour table has %d tets on %s, the input %d on %s" % (nbr.n_tet, nbr.device, T, dev))
+    idx32, V = None, 0
+    if tet_idx is not None:
+        idx32 = torch.as_tensor(tet_idx).to(device=dev, dtype=torch.int32).contiguous()
+        if tuple(idx32.shape) != (T, 4):
+            raise RuntimeError("surface_extract: tet_idx [%d,4] on %s expected" % (T, dev))
+    if (vertex_weights is not None or return_faces) and idx32 is None:
+        raise ValueError("surface_extract: vertex_weights / return_faces need tet_idx")
+    w = None
+    if vertex_weights is not None:
+        w = _f32c(vertex_weights)
+        w = w.reshape(1, -1) if w.dim() == 1 or (w.dim() == 2 and w.shape[1] == 1 and B == 1) else w.reshape(w.shape[0], -1)
+        if w.shape[0] != B:
+            raise RuntimeError("surface_extract: vertex_weights for %d shapes, tets for %d" % (w.shape[0], B))
+        V = int(w.shape[1])
+    else:
+        occ = _f32c(occ)
+        if occ.numel() != B * T:
+            raise RuntimeError("surface_extract: occ [%d,%d] expected, got %s" % (B, T, tuple(occ.shape)))
+        occ = occ.reshape(B, T)
+    C = 0
+    if attr is not None:
+        attr = _f32c(attr)
+        if attr.dim() != 4 or tuple(attr.shape[:3]) != (B, T, 4):
+            raise RuntimeError("surface_extract: attr [%d,%d,4,C] expected, got %s" % (B, T, tuple(attr.shape)))
+        C = int(attr.shape[3])
+    h = float(thres) if thres is not None else 0.0
+    offs = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    with _lib.on_device(dev):
+        st = _lib.current_stream(dev)
+        # the count pass leaves the row bases in its workspace for the fill pass: a tensor of this call, not the shared one
+        wsb = lib.deftet_surface_extract_workspace_bytes(B, T, int(w is not None))
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        _lib.check(lib.deftet_surface_extract_count_f32(_lib.ptr(occ), _lib.ptr(w), _lib.ptr(idx32), V, _lib.ptr(nbr.table32), B, T, mode,
+                                                        h, _lib.ptr(offs), _lib.ptr(ws), wsb, st), "deftet_surface_extract_count_f32")
+        o = offs.tolist()                               # the one sync (the reference syncs per shape and per local face)
+        if o[B] < 0:
+            raise RuntimeError("surface_extract: a neighbour or vertex index is out of range")
+        F = o[B]
+        face = torch.empty(F, 3, 3, dtype=torch.float32, device=dev)
+        fattr = torch.empty(F, 3, C, dtype=torch.float32, device=dev) if attr is not None else None
+        index = torch.empty(F, 2, dtype=torch.int64, device=dev) if return_index else None
+        faces = torch.empty(F, 3, dtype=torch.int64, device=dev) if return_faces else None
+        _lib.check(lib.deftet_surface_extract_fill_f32(_lib.ptr(tet), _lib.ptr(attr), C, _lib.ptr(occ) if w is None else None,
+                                                       _lib.ptr(idx32), _lib.ptr(nbr.table32), B, T, mode, h, F, _lib.ptr(face),
+                                                       _lib.ptr(fattr), _lib.ptr(index), _lib.ptr(faces), _lib.ptr(ws), wsb, st),
+                   "deftet_surface_extract_fill_f32")
+
+    def split(x):
+        return None if x is None else [x[o[b]:o[b + 1]] for b in range(B)]
+    return SurfaceSoup(split(face), split(fattr), split(index), split(faces))
+
+
+def surface_weld(verts_vx3, faces_fx3, attrs=None):
+    """Indexed mesh on the vertices its faces use, renumbered in ascending original id: (verts [V',3], attrs [V',C] or None,
+    faces int64 [F,3] with the new ids, old_id int64 [V']).  verts[faces] is unchanged bit for bit."""
+    _lib.require_gpu(verts_vx3, faces_fx3, attrs)
+    lib = _lib.load()
+    verts = _f32c(verts_vx3)
+    faces = faces_fx3.contiguous().long()
+    if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError("surface_weld: verts [V,3] and faces [F,3] expected, got %s and %s" % (tuple(verts.shape), tuple(faces.shape)))
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    dev = verts.device
+    C = 0
+    if attrs is not None:
+        attrs = _f32c(attrs)
+        if attrs.dim() != 2 or attrs.shape[0] != V:
+            raise RuntimeError("surface_weld: attrs [%d,C] expected, got %s" % (V, tuple(attrs.shape)))
+        C = int(attrs.shape[1])
+        if not 1 <= C <= 8:
+            raise _lib.DefTetHipError("surface_weld: attrs has C = %d channels, 1..8 supported (DEFTET_EINVAL)" % C)
+    cap = min(V, 3 * F)
+    n = torch.empty(2, dtype=torch.int32, device=dev)
+    old = torch.empty(cap, dtype=torch.int64, device=dev)
+    vout = torch.empty(cap, 3, dtype=torch.float32, device=dev)
+    aout = torch.empty(cap, C, dtype=torch.float32, device=dev) if attrs is not None else None
+    fout = torch.empty(F, 3, dtype=torch.int64, device=dev)
+    with _lib.on_device(dev):
+        ws = _lib.workspace(dev, lib.deftet_surface_weld_workspace_bytes(V))
+        _lib.check(lib.deftet_surface_weld_f32(_lib.ptr(faces), F, _lib.ptr(verts), _lib.ptr(attrs), C, V, cap, _lib.ptr(n), _lib.ptr(old),
+                                               _lib.ptr(vout), _lib.ptr(aout), _lib.ptr(fout), _lib.ptr(ws), ws.numel(),
+                                               _lib.current_stream(dev)), "deftet_surface_weld_f32")
+    n_used, bad = n.tolist()
+    if bad:
+        raise RuntimeError("surface_weld: a face index is outside [0, %d)" % V)
+    return vout[:n_used], (aout[:n_used] if aout is not None else None), fout, old[:n_used]

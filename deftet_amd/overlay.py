@@ -21,6 +21,8 @@ every import the hot path goes through:
 
 With `deftet_module=True` also `layers.DefTet.deftet` (the `DefTet` nn.Module built on the fused
 operators) — otherwise the reference's own module runs on top of the replaced L1 operators.
+With `render_model=True` also the flat module name `utils_tetsv` (a render-side checkout puts
+diff_render/diftet_6_subdiv/3_model on sys.path and imports it by that name): the surface extraction and its OBJ writers.
 Nothing here touches a CPU fallback: every replaced entry point raises on non-GPU tensors.
 """
 import importlib
@@ -75,7 +77,7 @@ def kaolin_shim():
             "kaolin.metrics.trianglemesh": met_tm}
 
 
-def install(kaolin=None, deftet_module=False, stub_cv2=True):
+def install(kaolin=None, deftet_module=False, stub_cv2=True, render_model=False):
     """Register the overlay in sys.modules; returns the list of names it registered.
     kaolin: True = always shim, False = never, None = shim only if `import kaolin` would fail."""
     done = []
@@ -85,6 +87,9 @@ def install(kaolin=None, deftet_module=False, stub_cv2=True):
     if deftet_module:
         sys.modules["layers.DefTet.deftet"] = importlib.import_module("deftet_amd.layers.DefTet.deftet")
         done.append("layers.DefTet.deftet")
+    if render_model:
+        sys.modules["utils_tetsv"] = importlib.import_module("deftet_amd.render.utils_tetsv")
+        done.append("utils_tetsv")
     if kaolin is None:
         kaolin = "kaolin" not in sys.modules and importlib.util.find_spec("kaolin") is None
     if kaolin:

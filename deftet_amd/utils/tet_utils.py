@@ -71,3 +71,25 @@ def tet_neighbour_table(tet_list_tx4, n_point, device="cuda"):
     """The T x 4 `tet_neighbour_idx` that diff_render/diftet_6_subdiv/3_model/utils_tetsv.py:16-75 returns next to
     the four adjacency matrices (consumed at 3_model/deftet.py:152,327)."""
     return hip_ops.tet_neighbours(np.asarray(tet_list_tx4), n_point, device).cpu().numpy()
+
+
+def get_tet_adj(tetrahedron_fx4, n_point, device="cuda"):
+    """utils/tet_utils.py:420-424: what get_face_use_occ takes as `tet_adj` — here the neighbour table by local face on the GPU
+    (hip_ops.TetFaceNeighbours) instead of four sparse matrices."""
+    tet = tetrahedron_fx4.cpu().numpy() if isinstance(tetrahedron_fx4, torch.Tensor) else np.asarray(tetrahedron_fx4)
+    return hip_ops.tet_face_neighbours(tet, n_point, device)
+
+
+def get_face_use_occ(tet_bxfx4x3, center_occ_cuda, tet_adj):
+    """utils/tet_utils.py:427-471: list of B [F_b,3,3] tensors, the faces between an occupied tet (occ == 1) and a neighbour of
+    another occupancy, in (tet, local face) order.  tet_adj: get_tet_adj(), or the reference's list of four sparse matrices."""
+    hip_ops._lib.require_gpu(tet_bxfx4x3, center_occ_cuda)
+    nbr = hip_ops.neighbours_from_adj_list(tet_adj, tet_bxfx4x3.device)
+    return hip_ops.surface_extract(tet_bxfx4x3, center_occ_cuda, nbr, "binary").face
+
+
+def save_tet_face(tet_fx3x3, f_name):
+    """utils/tet_utils.py:473-482, the same bytes."""
+    from deftet_amd.render import export
+    with open(f_name, "w") as f:
+        f.write(export.soup_obj_text(tet_fx3x3))

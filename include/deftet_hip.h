@@ -42,7 +42,9 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
-/* 260: the evaluation metrics — deftet_point_mesh_distance_f32 / _scan_f32, deftet_sample_points_f32, deftet_nn_distance_f32,
+/* 270: surface extraction from a per-tet occupancy — deftet_tet_face_neighbours_i64, deftet_surface_extract_count_f32 / _fill_f32,
+ *      deftet_surface_weld_f32 and their workspace sizes.
+ * 260: the evaluation metrics — deftet_point_mesh_distance_f32 / _scan_f32, deftet_sample_points_f32, deftet_nn_distance_f32,
  *      deftet_surface_metrics_f32 and their workspace sizes.
  * 250: the vertex Laplacian regulariser — deftet_vertex_adjacency_csr_i32 (an adjacency and its transpose as CSRs) with its
  *      workspace size, deftet_vertex_laplacian_fwd_f32 / _bwd_f32 and the forward's workspace size.
@@ -275,6 +277,51 @@ size_t deftet_boundary_index_workspace_bytes(int n_batch, int n_face);
 int deftet_boundary_index_i64(const int64_t *face_fx3, const int64_t *tetidx_fx2, const float *occ_bxt,
                               int64_t *out_rows, int32_t *offsets, int n_batch, int n_tet, int n_face, int mode,
                               void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * Surface extraction: the triangle surface of a per-tet occupancy.
+ * Local face i of tet (A,B,C,D) has the corners (a,b,c) = ([A,B,C,D][i], [B,A,D,C][i], [C,D,A,B][i]); rows come in ascending
+ * (tet, local face) order per shape, shapes back to back.
+ *
+ * deftet_tet_face_neighbours_i64: nbr[t][i] = the tet across LOCAL FACE i of t, -1 when no other tet owns the face — what row t
+ * of the i-th sparse matrix of tet_adj_share holds (utils/lib/tet_adj_share/run.cpp:40-97,
+ * diff_render/diftet_6_subdiv/3_model/utils_tetsv.py:16-75).  Inputs: the tetidx / tetfaceidx tables of
+ * deftet_tet_to_face_i32(with_boundary=1).  Either output may be NULL; the int32 table is what the kernels below read
+ * (16 bytes per tet, 16-byte aligned).  Needs no workspace. */
+int deftet_tet_face_neighbours_i64(const int64_t *tetidx_fx2, const int64_t *tetfaceidx_fx2, int n_face, int n_tet,
+                                   int64_t *nbr_tx4, int32_t *nbr32_tx4, void *stream);
+
+#define DEFTET_SX_BINARY 0     /* utils/tet_utils.py:427-471: n >= 0 && occ[n] != occ[t] && occ[t] == 1 (fp32; grid-boundary faces never) */
+#define DEFTET_SX_THRESHOLD 1  /* utils_tetsv.py:79-128: fabs((double)no - (double)occ[t]) > htres && occ[t] > (float)(2 htres), no = 0 at the boundary */
+
+/* Count pass (replaces the masks of utils/tet_utils.py:434-444 and utils_tetsv.py:88-101, 158-171).  The occupancy is either
+ * occ_bxt f32 [B,T], or — occ_bxt NULL — the maximum of the four corner weights of weights_bxv f32 [B,n_vertex] through
+ * tet_idx_tx4 int32 [T,4] (3_model/deftet.py:522-523; NaN propagates as in np.max).  offsets int32 [B+1] (device): first row of
+ * every shape, offsets[B] = rows of the batch; all -1 if a neighbour or vertex index is out of range.  The workspace keeps the
+ * per-workgroup row bases (and the fused occupancy): hand the SAME, untouched workspace to the fill pass. */
+size_t deftet_surface_extract_workspace_bytes(int n_batch, int n_tet, int with_vertex_weights);
+int deftet_surface_extract_count_f32(const float *occ_bxt, const float *weights_bxv, const int32_t *tet_idx_tx4, int n_vertex,
+                                     const int32_t *nbr32_tx4, int n_batch, int n_tet, int mode, double htres, int32_t *offsets,
+                                     void *workspace, size_t workspace_bytes, void *stream);
+/* Fill pass (replaces the boolean-mask gathers of utils/tet_utils.py:447-470 and utils_tetsv.py:103-126, 173-223), same mode,
+ * htres, neighbours and occupancy as the count pass (occ_bxt NULL = the occupancy the count pass fused from the vertex weights).
+ * The count pass records in the workspace which of the two occupancies it ran on; a fill pass asked for the OTHER one (or handed a
+ * workspace no count pass wrote) writes no row.
+ * capacity = rows the outputs hold (offsets[B]).  face f32 [F,3,3]; with attr_bxtx4xc f32 [B,T,4,n_attr] (1 <= n_attr <= 8) also
+ * face_attr f32 [F,3,n_attr]; index int64 [F,2] = (tet, local face) or NULL; faces int64 [F,3] = the corners' vertex ids from
+ * tet_idx_tx4 or NULL. */
+int deftet_surface_extract_fill_f32(const float *tet_bxtx4x3, const float *attr_bxtx4xc, int n_attr, const float *occ_bxt,
+                                    const int32_t *tet_idx_tx4, const int32_t *nbr32_tx4, int n_batch, int n_tet, int mode,
+                                    double htres, long long capacity, float *face, float *face_attr, int64_t *index, int64_t *faces,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+/* Welded mesh of one shape (no reference counterpart: utils/tet_utils.py:474 leaves it to trimesh): the vertices some face uses,
+ * renumbered in ascending original id.  n_out int32 [2] (device) = {n_used, 1 if a face id is outside [0, n_vertex)};
+ * old_id int64, verts_out f32 [.,3], attr_out f32 [.,n_attr] (with attr_vxc) hold capacity >= min(n_vertex, 3 n_face) rows;
+ * faces_out int64 [n_face,3] = the new ids. */
+size_t deftet_surface_weld_workspace_bytes(int n_vertex);
+int deftet_surface_weld_f32(const int64_t *faces_fx3, long long n_face, const float *verts_vx3, const float *attr_vxc, int n_attr,
+                            int n_vertex, int capacity, int32_t *n_out, int64_t *old_id, float *verts_out, float *attr_out,
+                            int64_t *faces_out, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------
  * N1  ground-truth occupancy by ray parity:

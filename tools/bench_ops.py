@@ -243,6 +243,15 @@ def main():
          torch_same_gpu_ms=round(tt_ * 1e3, 3), speedup_vs_torch=round(tt_ / tf_, 1),
          **roof(Be * T * (48 + 48 + 48) + T * 36 * 2, tfe, "hbm"))
 
+    # ---- surface extraction (utils/tet_utils.py:427-471): soup of the sphere occupancy, whole batch; the A/B against
+    # the reference's torch route is tools/surface_extract_ab.py
+    nbr_s = hip_ops.tet_face_neighbours(tets, n_point, dev)
+    occ_s = (tete.detach().mean(2).norm(dim=-1) < 0.3).float()
+    tsx = gpu_time(lambda: hip_ops.surface_extract(tete.detach(), occ_s, nbr_s, "binary"), reps=10)
+    rows_s = sum(int(f.shape[0]) for f in hip_ops.surface_extract(tete.detach(), occ_s, nbr_s, "binary").face)
+    emit(op="surface_extract binary", res=res, batch=Be, n_tet=T, rows=rows_s, gpu_ms=round(tsx * 1e3, 3),
+         **roof(2 * Be * T * 20 + rows_s * 72, tsx, "latency (two small passes and one read-back of the offsets)"))
+
     # ---- A1 forward: the binned path against the brute-force HIP formulation (the algorithmic equivalent of the
     # reference kernel: every query meets every tet in index order), BASELINE configs[2]
     Bp, Qp = (2, 20000) if quick else (8, 100000)
