@@ -137,6 +137,12 @@ SIGNATURES = {
     "deftet_surface_extract_fill_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, C.c_double, _ll, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "deftet_surface_weld_workspace_bytes": (_sz, [_i]),
     "deftet_surface_weld_f32": (_i, [_vp, _ll, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "deftet_face_vertex_csr_workspace_bytes": (_sz, [_i, _i]),
+    "deftet_face_vertex_csr_i32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "deftet_project_vertices_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "deftet_project_vertices_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "deftet_face_gather_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "deftet_face_gather_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
 }
 
 _lock = threading.Lock()

@@ -92,6 +92,12 @@ int ticket_slot_for_stream(hipStream_t st, int n_slots);
 namespace vtx {
 int gather_bwd_rows(const float *rows, const unsigned long long *rowMask, const int32_t *offsets, const int32_t *slots, float *grad_pos,
                     int B, int V, int T, int idx_batch, int accumulate, hipStream_t st);
+// vertex_ops.hip: the incidence CSR of an index list int64 [idx_batch,E,corners] over V vertices — offsets int32 [idx_batch*V+1],
+// slots int32 [idx_batch*corners*E] holding corners*e + corner in ascending order per vertex; *bad_flag = 1 for an index outside
+// [0,V).  corners = 4 is deftet_tet_vertex_csr_i32, corners = 3 is deftet_face_vertex_csr_i32 (render_vertices.hip).
+size_t incidence_csr_workspace_bytes(int idx_batch, int V, int E, int corners);
+int incidence_csr(const int64_t *idx, int32_t *offsets, int32_t *slots, int32_t *bad_flag, int idx_batch, int V, int E, int corners,
+                  void *workspace, size_t workspace_bytes, hipStream_t st);
 }
 
 }  // namespace deftet

@@ -155,27 +155,28 @@ extern "C" int deftet_tet_gather_fwd_f32(const float *pos, const int64_t *tet_id
     return DEFTET_OK;
 }
 
-extern "C" size_t deftet_tet_vertex_csr_workspace_bytes(int idx_batch, int V, int T)
+// The incidence CSR of an index list with `corners` indices per element (4: tets, 3: faces — render_vertices.hip): slot
+// corners*e + corner, ascending per vertex.
+size_t deftet::vtx::incidence_csr_workspace_bytes(int idx_batch, int V, int E, int corners)
 {
-    if (idx_batch <= 0 || V < 0 || T < 0) return 0;
-    const size_t n = (size_t)idx_batch * T * 4;
+    if (idx_batch <= 0 || V < 0 || E < 0) return 0;
+    const size_t n = (size_t)idx_batch * E * corners;
     return 3 * align_up(n * 4, 256) + align_up(vtx::sort_tmp_bytes(n), 256) + 256;
 }
 
-extern "C" int deftet_tet_vertex_csr_i32(const int64_t *tet_idx, int32_t *offsets, int32_t *slots, int32_t *bad_flag,
-                                         int idx_batch, int V, int T, void *workspace, size_t workspace_bytes, void *stream_)
+int deftet::vtx::incidence_csr(const int64_t *idx, int32_t *offsets, int32_t *slots, int32_t *bad_flag, int idx_batch, int V, int E,
+                               int corners, void *workspace, size_t workspace_bytes, hipStream_t st)
 {
-    DEFTET_CHECK_ARG(idx_batch >= 1 && V >= 0 && T >= 0, "bad size");
-    DEFTET_CHECK_ARG((long long)idx_batch * V < 0xFFFFFFFFLL && (long long)idx_batch * T * 4 < 0x7FFFFFFFLL, "topology too large for 32-bit keys");
-    DEFTET_CHECK_ARG(offsets && bad_flag && (T == 0 || (tet_idx && slots)), "null pointer");
-    hipStream_t st = as_stream(stream_);
-    const long long n = (long long)idx_batch * T * 4, nKeys = (long long)idx_batch * V;
+    DEFTET_CHECK_ARG(idx_batch >= 1 && V >= 0 && E >= 0, "bad size");
+    DEFTET_CHECK_ARG((long long)idx_batch * V < 0xFFFFFFFFLL && (long long)idx_batch * E * corners < 0x7FFFFFFFLL, "topology too large for 32-bit keys");
+    DEFTET_CHECK_ARG(offsets && bad_flag && (E == 0 || (idx && slots)), "null pointer");
+    const long long n = (long long)idx_batch * E * corners, nKeys = (long long)idx_batch * V;
     DEFTET_HIP(hipMemsetAsync(bad_flag, 0, 4, st));
     if (n == 0) {
         DEFTET_HIP(hipMemsetAsync(offsets, 0, (size_t)(nKeys + 1) * 4, st));
         return DEFTET_OK;
     }
-    DEFTET_CHECK_ARG(workspace && workspace_bytes >= deftet_tet_vertex_csr_workspace_bytes(idx_batch, V, T) &&
+    DEFTET_CHECK_ARG(workspace && workspace_bytes >= incidence_csr_workspace_bytes(idx_batch, V, E, corners) &&
                          ((uintptr_t)workspace & 255) == 0,
                      "workspace null, misaligned or too small");
     Arena A(workspace, workspace_bytes);
@@ -183,12 +184,23 @@ extern "C" int deftet_tet_vertex_csr_i32(const int64_t *tet_idx, int32_t *offset
     size_t tmpBytes = vtx::sort_tmp_bytes((size_t)n);
     void *tmp = A.take<char>(tmpBytes);
     const unsigned gb = (unsigned)((n + 255) / 256);
-    DEFTET_LAUNCH(vtx::k_csr_keys, dim3(gb), dim3(256), st, tet_idx, n, (long long)T * 4, V, key, val, bad_flag);
+    DEFTET_LAUNCH(vtx::k_csr_keys, dim3(gb), dim3(256), st, idx, n, (long long)E * corners, V, key, val, bad_flag);
     // all 32 key bits: invalid incidences carry the key 0xFFFFFFFF and must sort behind every vertex
     const int rc = prims::radix_sort<unsigned, unsigned>(key, skey, val, reinterpret_cast<unsigned *>(slots), (size_t)n, 32, tmp, tmpBytes, st);
     if (rc != DEFTET_OK) return rc;
     DEFTET_LAUNCH(vtx::k_csr_offsets, dim3((unsigned)((n + 256) / 256)), dim3(256), st, skey, n, nKeys, offsets);
     return DEFTET_OK;
+}
+
+extern "C" size_t deftet_tet_vertex_csr_workspace_bytes(int idx_batch, int V, int T)
+{
+    return vtx::incidence_csr_workspace_bytes(idx_batch, V, T, 4);
+}
+
+extern "C" int deftet_tet_vertex_csr_i32(const int64_t *tet_idx, int32_t *offsets, int32_t *slots, int32_t *bad_flag,
+                                         int idx_batch, int V, int T, void *workspace, size_t workspace_bytes, void *stream_)
+{
+    return vtx::incidence_csr(tet_idx, offsets, slots, bad_flag, idx_batch, V, T, 4, workspace, workspace_bytes, as_stream(stream_));
 }
 
 int deftet::vtx::gather_bwd_rows(const float *rows, const unsigned long long *rowMask, const int32_t *offsets, const int32_t *slots,

@@ -1817,3 +1817,153 @@ def surface_weld(verts_vx3, faces_fx3, attrs=None):
     if bad:
         raise RuntimeError("surface_weld: a face index is outside [0, %d)" % V)
     return vout[:n_used], (aout[:n_used] if aout is not None else None), fout, old[:n_used]
+
+
+# --------------------------------------------------------------------------------- rendering from the vertices
+class FaceTopology:
+    """A face list for face_gather, built once and reused (like TetTopology / VertexAdjacency): `faces` int64 [F,3] on the GPU
+    and the CSR of its (face, corner) incidences per vertex — `offsets` int32 [V+1], `slots` int32 [3F] holding 3*f+corner in
+    ascending order per vertex.  Raises on an index outside [0, n_vertex).  The object is a snapshot of the list it was built
+    from: a new face list (after a subdivision or a deletion) means a new object.  `device`: where to put a host list."""
+
+    def __init__(self, faces_fx3, n_vertex, device=None):
+        faces = torch.as_tensor(faces_fx3)
+        if device is not None:
+            faces = faces.to(device)
+        _lib.require_gpu(faces)
+        if faces.dim() != 2 or faces.shape[1] != 3:
+            raise RuntimeError("FaceTopology: faces [F,3] expected")
+        lib = _lib.load()
+        faces = faces.to(dtype=torch.int64, copy=True).contiguous()   # ours: later in-place edits of the caller's list do not reach it
+        F, V, dev = faces.shape[0], int(n_vertex), faces.device
+        offsets = torch.empty(V + 1, device=dev, dtype=torch.int32)
+        slots = torch.empty(3 * F, device=dev, dtype=torch.int32)
+        bad = torch.zeros(1, device=dev, dtype=torch.int32)
+        with _lib.on_device(dev):
+            ws = _lib.workspace(dev, lib.deftet_face_vertex_csr_workspace_bytes(V, F))
+            _lib.check(lib.deftet_face_vertex_csr_i32(_lib.ptr(faces), _lib.ptr(offsets), _lib.ptr(slots), _lib.ptr(bad), V, F,
+                                                      _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)), "deftet_face_vertex_csr_i32")
+        if int(bad.item()):
+            raise RuntimeError("FaceTopology: face index out of range [0, %d)" % V)
+        self.faces, self.n_vertex, self.n_face = faces, V, F
+        self.offsets, self.slots, self.device = offsets, slots, dev
+
+
+def _batched(t, last, what):
+    """[V,last] -> [1,V,last]; [B,V,last] stays"""
+    if t.dim() == 2:
+        t = t[None]
+    if t.dim() != 3 or t.shape[2] != last:
+        raise RuntimeError("project_vertices: %s [V,%d] or [B,V,%d] expected" % (what, last, last))
+    return _f32c(t)
+
+
+class _ProjectVertices(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, features, rot, cam_pos, proj, multiplier, depth):
+        _lib.require_gpu(points, features, rot, cam_pos, proj)
+        lib = _lib.load()
+        rot, cam_pos, proj = _f32c(rot), _f32c(cam_pos), _f32c(proj).reshape(-1)
+        B = rot.shape[0]
+        if rot.shape != (B, 3, 3) or cam_pos.shape != (B, 3) or proj.numel() != 3:
+            raise RuntimeError("project_vertices: cameras (rotation [B,3,3], position [B,3], projection [3]) expected")
+        pos = _batched(points, 3, "points")
+        feat = _batched(features, features.shape[-1], "features")
+        V, D = pos.shape[1], feat.shape[2]
+        if feat.shape[1] != V or pos.shape[0] not in (1, B) or feat.shape[0] not in (1, B) or D < 1:
+            raise RuntimeError("project_vertices: points and features must share V and have batch 1 or %d" % B)
+        dev, Do = pos.device, D + (1 if depth else 0)
+        z = torch.empty(B, V, device=dev, dtype=torch.float32)
+        xy = torch.empty(B, V, 2, device=dev, dtype=torch.float32)
+        act = torch.empty(B, V, Do, device=dev, dtype=torch.float32)
+        with _lib.on_device(dev):
+            _lib.check(lib.deftet_project_vertices_fwd_f32(_lib.ptr(pos), _lib.ptr(feat), _lib.ptr(rot), _lib.ptr(cam_pos), _lib.ptr(proj),
+                                                           multiplier, int(depth), _lib.ptr(z), _lib.ptr(xy), _lib.ptr(act), B, V, D,
+                                                           pos.shape[0], feat.shape[0], _lib.current_stream(dev)),
+                       "deftet_project_vertices_fwd_f32")
+        ctx.save_for_backward(pos, feat, rot, cam_pos, proj)   # the inputs: the backward recomputes the camera space in fp64
+        ctx.args = (multiplier, bool(depth), points.shape, features.shape)
+        ctx.mark_non_differentiable(z)                          # z reaches the loss through the depth channel of `act` only
+        ctx.set_materialize_grads(False)
+        return z, xy, act
+
+    @staticmethod
+    def backward(ctx, _g_z, g_xy, g_act):
+        pos, feat, rot, cam_pos, proj = ctx.saved_tensors
+        multiplier, depth, pshape, fshape = ctx.args
+        want_p, want_f = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if (g_xy is None and g_act is None) or not (want_p or want_f):
+            return (None,) * 7
+        lib = _lib.load()
+        B, Bp, Bf, V, D, dev = rot.shape[0], pos.shape[0], feat.shape[0], pos.shape[1], feat.shape[2], pos.device
+        g_xy, g_act = (None if g is None else _f32c(g) for g in (g_xy, g_act))
+        gp = torch.empty(Bp, V, 3, device=dev, dtype=torch.float32) if want_p else None
+        gf = torch.empty(Bf, V, D, device=dev, dtype=torch.float32) if want_f else None
+        with _lib.on_device(dev):
+            _lib.check(lib.deftet_project_vertices_bwd_f32(_lib.ptr(g_xy), _lib.ptr(g_act), _lib.ptr(pos), _lib.ptr(feat), _lib.ptr(rot),
+                                                           _lib.ptr(cam_pos), _lib.ptr(proj), multiplier, int(depth), _lib.ptr(gp), _lib.ptr(gf),
+                                                           B, V, D, Bp, Bf, _lib.current_stream(dev)), "deftet_project_vertices_bwd_f32")
+        return (gp.reshape(pshape) if want_p else None, gf.reshape(fshape) if want_f else None, None, None, None, None, None)
+
+
+def project_vertices(points, features, cameras, multiplier=1.0, depth=False):
+    """(z [B,V], xy [B,V,2], act [B,V,Do]) of points [V,3] | [B,V,3] and features [V,D] | [B,V,D] under cameras = (rotation
+    [B,3,3], position [B,3], projection [3] or [3,1]): camera-space depth, image coordinates times `multiplier` (`perspective`,
+    3_model/cameraop.py:19-33, 3_model/deftet.py:468) and sigmoid(features); with depth=True Do = D + 1 and act[..., 0] is the
+    camera-space z, not squashed (3_model/deftet.py:452-455, deftetrneder.py:78-89).  A [V,*] or [1,V,*] input is shared by the B
+    views without being repeated; its gradient is the sum over the views in ascending b.  Differentiable in points and features
+    (through xy and act; z is not differentiable — the rasterizer has no gradient for it); cameras get no gradient."""
+    rot, cam_pos, proj = cameras
+    return _ProjectVertices.apply(points, features, rot, cam_pos, proj, float(multiplier), bool(depth))
+
+
+class _FaceGather(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, xy, act, topology):
+        _lib.require_gpu(z, xy, act)
+        lib = _lib.load()
+        z, xy, act = _f32c(z), _f32c(xy), _f32c(act)
+        B, V = z.shape[0], topology.n_vertex
+        F, Do = topology.n_face, act.shape[-1]
+        if z.shape != (B, V) or xy.shape != (B, V, 2) or act.shape != (B, V, Do) or Do < 1 or z.device != topology.device:
+            raise RuntimeError("face_gather: z [B,V], xy [B,V,2], act [B,V,Do] on the topology's device with V = %d expected" % V)
+        dev = z.device
+        face_z = torch.empty(B, F, 3, device=dev, dtype=torch.float32)
+        face_xy = torch.empty(B, F, 3, 2, device=dev, dtype=torch.float32)
+        face_feat = torch.empty(B, F, 3, Do, device=dev, dtype=torch.float32)
+        with _lib.on_device(dev):
+            # (no flag: the topology checked its indices when it was built)
+            _lib.check(lib.deftet_face_gather_fwd_f32(_lib.ptr(z), _lib.ptr(xy), _lib.ptr(act), _lib.ptr(topology.faces), _lib.ptr(face_z),
+                                                      _lib.ptr(face_xy), _lib.ptr(face_feat), None, B, V, F, Do,
+                                                      _lib.current_stream(dev)), "deftet_face_gather_fwd_f32")
+        ctx.topology, ctx.sizes = topology, (B, V, F, Do)
+        ctx.mark_non_differentiable(face_z)
+        ctx.set_materialize_grads(False)
+        return face_z, face_xy, face_feat
+
+    @staticmethod
+    def backward(ctx, _g_face_z, g_face_xy, g_face_feat):
+        if g_face_xy is None and g_face_feat is None:
+            return None, None, None, None
+        lib = _lib.load()
+        top = ctx.topology
+        B, V, F, Do = ctx.sizes
+        dev = top.device
+        g_face_xy, g_face_feat = (None if g is None else _f32c(g) for g in (g_face_xy, g_face_feat))
+        g_xy = torch.empty(B, V, 2, device=dev, dtype=torch.float32)
+        g_act = torch.empty(B, V, Do, device=dev, dtype=torch.float32)
+        with _lib.on_device(dev):
+            _lib.check(lib.deftet_face_gather_bwd_f32(_lib.ptr(g_face_xy), _lib.ptr(g_face_feat), _lib.ptr(top.offsets), _lib.ptr(top.slots),
+                                                      _lib.ptr(g_xy), _lib.ptr(g_act), B, V, F, Do, _lib.current_stream(dev)),
+                       "deftet_face_gather_bwd_f32")
+        return None, g_xy, g_act, None
+
+
+def face_gather(z, xy, act, topology):
+    """(face_z [B,F,3], face_xy [B,F,3,2], face_feat [B,F,3,Do]): the rows of z [B,V], xy [B,V,2], act [B,V,Do] at the corners of
+    `topology` (a FaceTopology) — the rasterizer's three dense inputs, written by one launch (the three `vertex2face` gathers of
+    5_rendereq/deftetrneder.py:93-95).  The backward sums the per-corner gradients of face_xy and face_feat per vertex through the
+    topology's CSR, one after the other in slot order: no atomics, the same bits on every run.  face_z is not differentiable."""
+    if not isinstance(topology, FaceTopology):
+        raise TypeError("face_gather: topology must be a hip_ops.FaceTopology")
+    return _FaceGather.apply(z, xy, act, topology)

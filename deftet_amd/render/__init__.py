@@ -2,3 +2,4 @@ from .deftet_sparse_render import deftet_sparse_render, deftet_sparse_render_com
 from .compositing import alpha_composite  # noqa: F401
 from .camera import perspective, face_attributes, render_mesh_color  # noqa: F401
 from .laplacian import get_featlap  # noqa: F401
+from .vertices import render_vertices, model_forward  # noqa: F401

@@ -42,7 +42,9 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
-/* 270: surface extraction from a per-tet occupancy — deftet_tet_face_neighbours_i64, deftet_surface_extract_count_f32 / _fill_f32,
+/* 280: rendering straight from the vertices — deftet_face_vertex_csr_i32 (+ workspace size), deftet_project_vertices_fwd_f32 /
+ *      _bwd_f32, deftet_face_gather_fwd_f32 / _bwd_f32 (render_vertices.hip).
+ * 270: surface extraction from a per-tet occupancy — deftet_tet_face_neighbours_i64, deftet_surface_extract_count_f32 / _fill_f32,
  *      deftet_surface_weld_f32 and their workspace sizes.
  * 260: the evaluation metrics — deftet_point_mesh_distance_f32 / _scan_f32, deftet_sample_points_f32, deftet_nn_distance_f32,
  *      deftet_surface_metrics_f32 and their workspace sizes.
@@ -709,6 +711,47 @@ size_t deftet_surface_metrics_workspace_bytes(int n_batch);
 int deftet_surface_metrics_f32(const float *p1_bxn1x3, const float *p2_bxn2x3, const int32_t *idx12_bxn1, const int32_t *idx21_bxn2,
                                const float *dist_a_bxnh, const float *dist_b_bxnh, int n_batch, int n1, int n2, int nh, float radius,
                                float *out_bx5, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Rendering straight from the vertices (280): what diff_render/diftet_6_subdiv/3_model/deftet.py:427-468,
+ * 3_model/cameraop.py:19-33 and 5_rendereq/deftetrneder.py:78-95 do in torch between the optimiser's per-vertex parameters and
+ * the rasterizer's dense per-face buffers.
+ *
+ * deftet_face_vertex_csr_i32: face_idx int64 [F,3] -> offsets int32 [V+1], slots int32 [3F] holding 3*f+corner in ascending order
+ * per vertex; *bad_flag (device int32, required) = 1 when an index is outside [0,V).  The 3-corner twin of
+ * deftet_tet_vertex_csr_i32 (the same code); workspace 256-byte aligned.
+ *
+ * deftet_project_vertices_fwd_f32: pos f32 [pos_batch,V,3], feat f32 [feat_batch,V,D] (each batch 1 = shared by all views, or B),
+ * rot f32 [B,3,3], cam_pos f32 [B,3], proj f32 [3] (device) -> z f32 [B,V], xy f32 [B,V,2], act f32 [B,V,Do]:
+ *   cam = R (p - c), every row summed left to right;  z = cam.z;  xy = (cam.x proj.x, cam.y proj.y) / (cam.z proj.z) * multiplier;
+ *   act = sigmoid(feat), Do = D;  with depth_channel != 0: Do = D + 1, act[...,0] = cam.z (not squashed), act[...,1:] = sigmoid(feat).
+ * The operations and their order are those of `perspective`; they are evaluated in fp64 and every output is rounded once (an
+ * fp32 chain misses the 1e-5 element-relative bound where cam.x / cam.y cancel).
+ * deftet_project_vertices_bwd_f32: g_xy f32 [B,V,2], g_act f32 [B,V,Do] (either may be NULL = zeros) and the forward's INPUTS
+ * (recomputing cam in fp64 is cheaper and more exact than reading saved fp32 outputs back) ->
+ * grad_pos f32 [pos_batch,V,3], grad_feat f32 [feat_batch,V,D] (either may be NULL = not wanted).  A shared input's gradient is
+ * the sum over the views, added in ascending b inside the kernel (in fp64, rounded once).  cam.z gets a gradient through the depth
+ * channel only (the rasterizer has none for face_z); cameras get none.
+ *
+ * deftet_face_gather_fwd_f32: one launch writes face_z f32 [B,F,3], face_xy f32 [B,F,3,2], face_feat f32 [B,F,3,Do] — rows of z,
+ * xy, act at face_idx int64 [F,3].  An index outside [0,V) yields NaNs and sets *bad_flag (may be NULL), as
+ * deftet_tet_gather_fwd_f32.  xy and face_xy 8-byte aligned.
+ * deftet_face_gather_bwd_f32: grad_face_xy f32 [B,F,3,2], grad_face_feat f32 [B,F,3,Do] (either may be NULL = zeros) ->
+ * g_xy f32 [B,V,2], g_act f32 [B,V,Do]: every component is the sum over the vertex's incidences, added ONE AFTER THE OTHER in slot
+ * order in fp32 (no atomics, no partial sums: the bits do not depend on the launch shape); a vertex without a face gets zeros. */
+size_t deftet_face_vertex_csr_workspace_bytes(int n_vertex, int n_face);
+int deftet_face_vertex_csr_i32(const int64_t *face_idx, int32_t *offsets, int32_t *slots, int32_t *bad_flag, int n_vertex, int n_face,
+                               void *workspace, size_t workspace_bytes, void *stream);
+int deftet_project_vertices_fwd_f32(const float *pos, const float *feat, const float *rot, const float *cam_pos, const float *proj,
+                                    float multiplier, int depth_channel, float *z, float *xy, float *act, int n_batch, int n_vertex,
+                                    int n_feat, int pos_batch, int feat_batch, void *stream);
+int deftet_project_vertices_bwd_f32(const float *g_xy, const float *g_act, const float *pos, const float *feat, const float *rot,
+                                    const float *cam_pos, const float *proj, float multiplier, int depth_channel, float *grad_pos,
+                                    float *grad_feat, int n_batch, int n_vertex, int n_feat, int pos_batch, int feat_batch, void *stream);
+int deftet_face_gather_fwd_f32(const float *z, const float *xy, const float *act, const int64_t *face_idx, float *face_z,
+                               float *face_xy, float *face_feat, int32_t *bad_flag, int n_batch, int n_vertex, int n_face, int n_act,
+                               void *stream);
+int deftet_face_gather_bwd_f32(const float *grad_face_xy, const float *grad_face_feat, const int32_t *offsets, const int32_t *slots,
+                               float *g_xy, float *g_act, int n_batch, int n_vertex, int n_face, int n_act, void *stream);
 
 #ifdef __cplusplus
 }

@@ -65,6 +65,100 @@ def emit(**kw):
     print(json.dumps(kw), flush=True)
 
 
+def bench_render_vertices(dev):
+    """fwd+bwd of a render step from per-vertex leaves at BASELINE configs[4] (res-70 faces, 512^2 pixels, k = 64, D = 4, one view):
+    render_vertices against the torch glue (perspective + render_mesh_color(fused=True)), and the glue alone on both paths (for the
+    new path: project_vertices + face_gather; for the torch path: perspective, sigmoid and the three face_attributes gathers), each
+    backward driven by the same per-face gradients.  HIP events around every call, median, four rotating input sets."""
+    from oracle import oracle as O
+    from deftet_amd import hip_ops
+    from deftet_amd.render import face_attributes, perspective, render_mesh_color, render_vertices
+    res, npx, knum, mult = (40, 256, 64, 1000.0) if quick else (70, 512, 64, 1000.0)
+    verts, tets = grids.kuhn_grid(res)
+    V = verts.shape[0]
+    f3 = np.asarray(O.tet_to_face(tets, V, with_boundary=True)[0], np.int64)
+    F = f3.shape[0]
+    ax, ay = 0.35, 0.5
+    rx = np.array([[1, 0, 0], [0, np.cos(ax), -np.sin(ax)], [0, np.sin(ax), np.cos(ax)]])
+    ry = np.array([[np.cos(ay), 0, np.sin(ay)], [0, 1, 0], [-np.sin(ay), 0, np.cos(ay)]])
+    rot = (rx @ ry).astype(np.float32)[None]
+    cams = tuple(torch.from_numpy(x).to(dev) for x in (rot, (rot[0].T @ np.array([0, 0, 4.0], np.float32))[None].astype(np.float32),
+                                                       np.array([[1111.0 / 800.0 * 2.0] * 2 + [-1.0]], np.float32).T.copy()))
+    faces = torch.from_numpy(f3).to(dev)
+    topo = hip_ops.FaceTopology(faces, V)
+    pix, rngs = (torch.from_numpy(x).to(dev) for x in grids.pixel_grid(npx))
+    rng = np.random.default_rng(0)
+    sets = []
+    for k in range(4):
+        p = torch.from_numpy(((verts - 0.5) * 2.5 + rng.normal(size=verts.shape) * 1e-3).astype(np.float32)).to(dev).requires_grad_(True)
+        f = torch.from_numpy(rng.random((V, 4)).astype(np.float32) * 4 - 2).to(dev).requires_grad_(True)
+        sets.append((p, f))
+    P = pix.shape[1]
+    g_img = [torch.rand(1, P, 3, device=dev), torch.rand(1, P, 1, device=dev)]
+    g_fxy, g_ff = torch.randn(1, F, 3, 2, device=dev), torch.randn(1, F, 3, 4, device=dev)
+    calls = [0]
+
+    def new_step():
+        p, f = sets[calls[0] % 4]
+        c, v, _ = render_vertices(p, f, topo, cams, pix, rngs, multiplier=mult, knum=knum)
+        return torch.autograd.grad((c, v), (p, f), g_img)
+
+    def old_step():
+        p, f = sets[calls[0] % 4]
+        cam, xy = perspective(p[None], cams)
+        c, v, _ = render_mesh_color(pix, rngs, cam, xy * mult, f[None], faces, knum=knum, fused=True)
+        return torch.autograd.grad((c, v), (p, f), g_img)
+
+    def new_glue():
+        p, f = sets[calls[0] % 4]
+        z, xy, act = hip_ops.project_vertices(p, f, cams, mult)
+        _, fxy, ff = hip_ops.face_gather(z, xy, act, topo)
+        return torch.autograd.grad((fxy, ff), (p, f), (g_fxy, g_ff))
+
+    def old_glue():
+        p, f = sets[calls[0] % 4]
+        cam, xy = perspective(p[None], cams)
+        act = torch.sigmoid(f[None])
+        fz = face_attributes(cam, faces).reshape(1, -1, 3, 3)[:, :, :, -1]
+        fxy = face_attributes(xy * mult, faces).reshape(1, -1, 3, 2)
+        ff = face_attributes(act, faces).reshape(1, F, 3, -1)
+        return torch.autograd.grad((fxy, ff), (p, f), (g_fxy, g_ff)), fz
+
+    def timed(fn, reps=15, warm=4):
+        for _ in range(warm):
+            fn()
+            calls[0] += 1
+        ms = []
+        for _ in range(reps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ms.append(a.elapsed_time(b))
+            calls[0] += 1
+        return float(np.median(ms)), float(np.min(ms))
+
+    out = {}
+    for name, fn in (("new_step", new_step), ("torch_step", old_step), ("new_glue", new_glue), ("torch_glue", old_glue)):
+        out[name + "_ms"], out[name + "_min_ms"] = (round(x, 4) for x in timed(fn))
+    ga, gb = new_step(), old_step()
+    emit(op="render_vertices", res=res, n_vertex=V, n_face=F, n_pixel=P, knum=knum, n_feat=4, views=1, **out,
+         grad_points_maxdiff_new_vs_torch=float((ga[0] - gb[0]).abs().max()), grad_points_scale=float(gb[0].abs().max()),
+         reproducible=bool(torch.equal(ga[0], new_step()[0])), torch_path_reproducible=bool(torch.equal(gb[0], old_step()[0])))
+    try:                                                     # device launches per call (kernels and copies), after the timings
+        from torch.profiler import ProfilerActivity, profile
+        counts = {}
+        for name, fn in (("new_step", new_step), ("torch_step", old_step), ("new_glue", new_glue), ("torch_glue", old_glue)):
+            with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                fn()
+                torch.cuda.synchronize()
+            counts[name] = int(sum(e.count for e in prof.key_averages() if getattr(e, "device_time_total", 0) > 0))
+        emit(op="render_vertices_launches", **counts)
+    except Exception as e:                                   # noqa: BLE001
+        emit(op="render_vertices_launches", error=repr(e))
+
+
 def main():
     res = 40 if quick else 70
     verts, tets = grids.kuhn_grid(res)
@@ -157,6 +251,8 @@ def main():
          cpu_fwd_ms=round(tc * 1e3, 0), cpu_kind="port (brute force, extrapolated from %d pixels)" % subp, cpu_cores=1,
          nominal_pixel_face_tests_per_s=round(Pn * Fn / tg / 1e9, 1), unit="G pixel-face tests/s (fwd)",
          hits=int((face_i >= 0).sum().item()), parity="unpinned (Kaolin not in the reference tree)")
+
+    bench_render_vertices(dev)
 
     # ---- N2: vertex <-> tet gather (deftet.py:65-68) against torch's own gather / scatter-add on the same GPU
     Bv = 2 if quick else 8
@@ -265,4 +361,7 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if "--only-render-vertices" in sys.argv:
+        bench_render_vertices(dev)
+    else:
+        main()
