@@ -143,6 +143,14 @@ SIGNATURES = {
     "deftet_project_vertices_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "deftet_face_gather_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "deftet_face_gather_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "deftet_pointvoxel_workspace_bytes": (_sz, [_i, _i, _i]),
+    "deftet_avg_voxelize_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "deftet_avg_voxelize_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "deftet_voxel_sample_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "deftet_voxel_cells_f32": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "deftet_voxel_cells_from_inds_i32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    "deftet_voxel_sample_bwd_vol_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "deftet_voxel_sample_bwd_pos_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
 }
 
 _lock = threading.Lock()

@@ -1,0 +1,580 @@
+// pointvoxel.hip — the two point-voxel operators that join the point-cloud encoder to the tet grid:
+//   average voxelization (layers/pv_module/functional/src/voxelization/vox.cu) forward and backward, and
+//   trilinear sampling of voxel volumes at points (pc_model.py:182-194 sample_f; functional/devoxelization.py;
+//   src/interpolate/trilinear_devox.cu) forward, backward to the volumes and backward to the positions.
+// No float atomics anywhere: both scatters are turned into gathers by a stable sort of the points by voxel / by cell
+// (prims.hpp), so every sum has one fixed order and two runs give the same bits.
+//
+// Orders of summation (the contracts of include/deftet_hip.h):
+//   voxelization   out[b,c,s] = 0 + feat[i0] * inv + feat[i1] * inv + ...   over the points of voxel s in ascending i, every
+//                  product rounded before it is added (what the reference kernel computes with its threads one after another)
+//   sampling       ((w000 f000 + w001 f001) + w010 f010) + ... + w111 f111, z fastest, w = (wx * wy) * wz
+//   to the volumes per (channel, cell) eight corner sums over the cell's points in ascending p (the sort is stable; a long segment
+//                  by 64 lanes and a fixed butterfly, see k_vs_cell_partials), then per voxel the partials of corner 000 .. 111
+//   to positions   channels in ascending order, one volume after the other (the caller's list order)
+#include "prims.hpp"
+
+namespace deftet {
+namespace {
+
+constexpr int kPvBlock = 256;
+
+// u of one point per axis: `raw` before the clamp (the border rule of the position gradient reads it), `u` after it.
+// pos_mode 0: pos f32 [B,N,3], normalised: u = clamp((pos + 0.5) r, 0, r - 1)   (sample_f's arithmetic, in that order)
+// pos_mode 1: coords f32 [B,3,N] in voxel units: u = clamp(coords, 0, r - 1)    (trilinear_devoxelize's argument)
+// fmaxf / fminf return the other operand for a NaN, so a NaN lands on 0 and every index below stays inside the volume.
+__device__ __forceinline__ void load_u(const float *__restrict__ pos, int mode, int b, int p, int N, int r, float raw[3], float u[3])
+{
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        raw[j] = mode == 0 ? (pos[((size_t)b * N + p) * 3 + j] + 0.5f) * (float)r : pos[((size_t)b * 3 + j) * N + p];
+        u[j] = fminf(fmaxf(raw[j], 0.0f), (float)(r - 1));
+    }
+}
+
+// the cell of u: lo corner, the eight linear indices and weights (corner k = 4 kx + 2 ky + kz, z fastest).
+// legacy: hi = lo where d == 0 (trilinear_devox.cu:64-75), else hi = min(lo + 1, r - 1); both stay below r as u <= r - 1.
+struct Corners {
+    int idx[8];
+    float w[8];
+};
+__device__ __forceinline__ void corners_of(const float u[3], int r, bool legacy, Corners &c)
+{
+    int lo[3], hi[3];
+    float d1[3], d0[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float f = floorf(u[j]);
+        d1[j] = u[j] - f;
+        d0[j] = 1.0f - d1[j];
+        lo[j] = (int)f;
+        hi[j] = legacy ? lo[j] + (d1[j] > 0.0f ? 1 : 0) : min(lo[j] + 1, r - 1);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int kx = k >> 2, ky = (k >> 1) & 1, kz = k & 1;
+        c.idx[k] = ((kx ? hi[0] : lo[0]) * r + (ky ? hi[1] : lo[1])) * r + (kz ? hi[2] : lo[2]);
+        c.w[k] = ((kx ? d1[0] : d0[0]) * (ky ? d1[1] : d0[1])) * (kz ? d1[2] : d0[2]);
+    }
+}
+
+// ---------------------------------------------------------------------------- sort plumbing
+// seg[s] = the first sorted position whose key is >= s, s in [0, n_keys]: voxel / cell s owns [seg[s], seg[s + 1])
+__global__ __launch_bounds__(kPvBlock) void k_pv_segments(const unsigned *__restrict__ sorted, unsigned n, unsigned n_keys, int32_t *seg)
+{
+    const unsigned s = blockIdx.x * kPvBlock + threadIdx.x;
+    if (s > n_keys) return;
+    unsigned a = 0u, b = n;
+    while (a < b) {
+        const unsigned m = a + (b - a) / 2u;
+        if (sorted[m] < s) a = m + 1u;
+        else b = m;
+    }
+    seg[s] = (int32_t)a;
+}
+
+inline int key_bits(unsigned n_keys)
+{
+    int bits = 1;
+    while (bits < 32 && (n_keys >> bits) != 0u) ++bits;             // the sentinel n_keys itself must be representable
+    return bits;
+}
+
+struct SortBufs {
+    unsigned *keys, *sorted;
+    void *tmp;
+    size_t tmp_bytes;
+};
+inline size_t sort_bytes(size_t n)
+{
+    return 2 * align_up(n * sizeof(unsigned), 256) + prims::radix_sort_temp_bytes<unsigned, unsigned>(n) + 512;
+}
+inline bool carve(Arena &A, void *ws, size_t ws_bytes, size_t n, SortBufs &s)
+{
+    if (!ws || ((uintptr_t)ws & 255) != 0 || ws_bytes < sort_bytes(n)) return false;
+    s.keys = A.take<unsigned>(n);
+    s.sorted = A.take<unsigned>(n);
+    s.tmp_bytes = prims::radix_sort_temp_bytes<unsigned, unsigned>(n);
+    s.tmp = A.take<char>(s.tmp_bytes);
+    return A.ok();
+}
+// keys (already written) -> perm (the point ids b N + p in key order, stable) and seg
+inline int sort_and_segment(const SortBufs &s, int32_t *perm, int32_t *seg, size_t n, unsigned n_keys, hipStream_t st)
+{
+    const int rc = prims::radix_sort_from<unsigned, unsigned>(prims::PtrLoad<unsigned>{s.keys}, s.sorted, prims::IotaLoad{}, (unsigned *)perm,
+                                                               n, key_bits(n_keys), s.tmp, s.tmp_bytes, st);
+    if (rc != DEFTET_OK) return rc;
+    DEFTET_LAUNCH(k_pv_segments, dim3((n_keys + 1 + kPvBlock - 1) / kPvBlock), dim3(kPvBlock), st, (const unsigned *)s.sorted, (unsigned)n,
+                  n_keys, seg);
+    return DEFTET_OK;
+}
+
+// channels per thread so that the grid has a few thousand workgroups; the sums do not depend on it
+inline int channels_per_thread(int C, long long groups_per_channel_chunk)
+{
+    const long long want = 4096;
+    long long chunks = (want + groups_per_channel_chunk - 1) / groups_per_channel_chunk;
+    chunks = chunks < 1 ? 1 : (chunks > C ? C : chunks);
+    return (int)((C + chunks - 1) / chunks);
+}
+
+// ---------------------------------------------------------------------------- average voxelization
+__global__ __launch_bounds__(kPvBlock) void k_vox_keys(const int32_t *__restrict__ coords, int32_t *ind, unsigned *keys, int N, int R,
+                                                       unsigned n_keys)
+{
+    const int p = blockIdx.x * kPvBlock + threadIdx.x, b = blockIdx.y;
+    if (p >= N) return;
+    const int x = coords[((size_t)b * 3 + 0) * N + p], y = coords[((size_t)b * 3 + 1) * N + p], z = coords[((size_t)b * 3 + 2) * N + p];
+    const bool ok = x >= 0 && x < R && y >= 0 && y < R && z >= 0 && z < R;
+    const int i = ok ? (x * R + y) * R + z : -1;
+    ind[(size_t)b * N + p] = i;
+    keys[(size_t)b * N + p] = ok ? (unsigned)b * (unsigned)(R * R * R) + (unsigned)i : n_keys;
+}
+
+__global__ __launch_bounds__(kPvBlock) void k_vox_fwd(const float *__restrict__ feat, const int32_t *__restrict__ perm,
+                                                      const int32_t *__restrict__ seg, float *out, int32_t *cnt, int C, int N, int R3,
+                                                      int c_per)
+{
+    const int s = blockIdx.x * kPvBlock + threadIdx.x, b = blockIdx.z;
+    if (s >= R3) return;
+    const int j0 = seg[(size_t)b * R3 + s], j1 = seg[(size_t)b * R3 + s + 1];
+    if (blockIdx.y == 0) cnt[(size_t)b * R3 + s] = j1 - j0;
+    const float inv = j1 > j0 ? 1.0f / (float)(j1 - j0) : 0.0f;
+    const int c0 = blockIdx.y * c_per, c1 = min(C, c0 + c_per);
+    for (int c = c0; c < c1; ++c) {
+        const float *f = feat + ((size_t)b * C + c) * N - (size_t)b * N;       // perm holds b N + p
+        float acc = 0.0f;
+        for (int j = j0; j < j1; ++j) acc = __fadd_rn(acc, __fmul_rn(f[perm[j]], inv));
+        out[((size_t)b * C + c) * R3 + s] = acc;
+    }
+}
+
+__global__ __launch_bounds__(kPvBlock) void k_vox_bwd(const float *__restrict__ gy, const int32_t *__restrict__ ind,
+                                                      const int32_t *__restrict__ cnt, float *gx, int C, int N, int R3, int c_per)
+{
+    const int p = blockIdx.x * kPvBlock + threadIdx.x, b = blockIdx.z;
+    if (p >= N) return;
+    const int i = ind[(size_t)b * N + p];
+    const bool ok = i >= 0 && i < R3;
+    const int n = ok ? cnt[(size_t)b * R3 + i] : 0;
+    const float inv = n > 0 ? 1.0f / (float)n : 0.0f;
+    const int c0 = blockIdx.y * c_per, c1 = min(C, c0 + c_per);
+    for (int c = c0; c < c1; ++c)
+        gx[((size_t)b * C + c) * N + p] = n > 0 ? __fmul_rn(gy[((size_t)b * C + c) * R3 + i], inv) : 0.0f;
+}
+
+// ---------------------------------------------------------------------------- trilinear sampling, forward
+__global__ __launch_bounds__(kPvBlock) void k_vs_fwd(const float *__restrict__ vol, const float *__restrict__ pos, float *out, int32_t *inds,
+                                                     float *wgts, int C, int R, int N, int c_off, int C_total, int mode, int legacy,
+                                                     int c_per)
+{
+    const int p = blockIdx.x * kPvBlock + threadIdx.x, b = blockIdx.z;
+    if (p >= N) return;
+    float raw[3], u[3];
+    load_u(pos, mode, b, p, N, R, raw, u);
+    Corners cn;
+    corners_of(u, R, legacy != 0, cn);
+    if (inds && blockIdx.y == 0) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            inds[((size_t)b * 8 + k) * N + p] = cn.idx[k];
+            wgts[((size_t)b * 8 + k) * N + p] = cn.w[k];
+        }
+    }
+    const size_t R3 = (size_t)R * R * R;
+    const int c0 = blockIdx.y * c_per, c1 = min(C, c0 + c_per);
+    for (int c = c0; c < c1; ++c) {
+        const float *f = vol + ((size_t)b * C + c) * R3;
+        float acc = __fmul_rn(cn.w[0], f[cn.idx[0]]);
+#pragma unroll
+        for (int k = 1; k < 8; ++k) acc = __fadd_rn(acc, __fmul_rn(cn.w[k], f[cn.idx[k]]));
+        out[((size_t)b * C_total + c_off + c) * N + p] = acc;
+    }
+}
+
+// ---------------------------------------------------------------------------- backward to the volumes
+__global__ __launch_bounds__(kPvBlock) void k_cell_keys(const float *__restrict__ pos, int mode, unsigned *keys, int N, int R)
+{
+    const int p = blockIdx.x * kPvBlock + threadIdx.x, b = blockIdx.y;
+    if (p >= N) return;
+    float raw[3], u[3];
+    load_u(pos, mode, b, p, N, R, raw, u);
+    const int x = (int)floorf(u[0]), y = (int)floorf(u[1]), z = (int)floorf(u[2]);
+    keys[(size_t)b * N + p] = (unsigned)b * (unsigned)(R * R * R) + (unsigned)((x * R + y) * R + z);
+}
+// the eight weights of the points in sorted order, corner-major: wsorted[k][j]
+__global__ __launch_bounds__(kPvBlock) void k_cell_weights(const float *__restrict__ pos, int mode, const int32_t *__restrict__ perm,
+                                                           float *wsorted, int B, int N, int R)
+{
+    const size_t BN = (size_t)B * N, j = (size_t)blockIdx.x * kPvBlock + threadIdx.x;
+    if (j >= BN) return;
+    const int g = perm[j], b = g / N, p = g - b * N;
+    float raw[3], u[3];
+    load_u(pos, mode, b, p, N, R, raw, u);
+    Corners cn;
+    corners_of(u, R, false, cn);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) wsorted[(size_t)k * BN + j] = cn.w[k];
+}
+// the legacy pair: the cell is inds[:,0,:]; a first index outside the volume drops the point (sentinel key)
+__global__ __launch_bounds__(kPvBlock) void k_inds_keys(const int32_t *__restrict__ inds, unsigned *keys, int N, int R3, unsigned n_keys)
+{
+    const int p = blockIdx.x * kPvBlock + threadIdx.x, b = blockIdx.y;
+    if (p >= N) return;
+    const int i = inds[(size_t)b * 8 * N + p];
+    keys[(size_t)b * N + p] = i >= 0 && i < R3 ? (unsigned)b * (unsigned)R3 + (unsigned)i : n_keys;
+}
+__global__ __launch_bounds__(kPvBlock) void k_inds_gather(const int32_t *__restrict__ inds, const float *__restrict__ wgts,
+                                                          const int32_t *__restrict__ perm, float *wsorted, int32_t *isorted, int B, int N)
+{
+    const size_t BN = (size_t)B * N, j = (size_t)blockIdx.x * kPvBlock + threadIdx.x;
+    if (j >= BN) return;
+    const int g = perm[j], b = g / N, p = g - b * N;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        wsorted[(size_t)k * BN + j] = wgts[((size_t)b * 8 + k) * N + p];
+        isorted[(size_t)k * BN + j] = inds[((size_t)b * 8 + k) * N + p];
+    }
+}
+
+// Two stages, so that every gout element is read once.
+// k_vs_cell_partials: per (channel, cell) the eight corner sums part[b][c][k][cell] = sum over the cell's points, in sorted
+// (= ascending point) order, of wsorted[k][j] * gout[b,c,perm[j]].  A thread owns a cell; a segment of up to kPvShort points it
+// walks itself (the fine volumes: ~1.4 points per cell, most cells empty).  A longer segment (the coarse volumes: ~90 points per
+// cell, or every point of a clustered set in one cell) is summed by the whole wave: lane l adds the points j0 + l, j0 + l + 64,
+// ... in that order, then the 64 lane sums are added by a fixed butterfly (offsets 32, 16, ... 1).  The order depends on the
+// segment's length only, never on the launch or on timing.  HAS_INDS (the legacy pair): a term counts only where the recorded
+// index IS the voxel the corner nominally lands in — the reference's hi index falls back on lo where d == 0, and there its
+// weight is exactly 0, so the terms left out are zeros.
+// k_vs_vol_from_partials: voxel v adds the up to eight partials that meet in it, corner 000 .. 111 in that order, from 0.
+// Gathers both: the only stores are the thread's own cell and the thread's own voxel.
+constexpr int kPvShort = 32;
+constexpr size_t kPvPartialBudget = (size_t)64 << 20;               // scratch for the partials: the channels are chunked to fit it
+inline size_t partial_bytes_per_channel(size_t B, size_t R3) { return B * R3 * 8 * sizeof(float); }
+
+template <bool HAS_INDS>
+__device__ __forceinline__ void add_point(float acc[8], const float *__restrict__ wsorted, const int32_t *__restrict__ isorted, size_t BN, int j,
+                                          float gv, const int vk[8])
+{
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        if (HAS_INDS && isorted[(size_t)k * BN + j] != vk[k]) continue;
+        acc[k] = __fadd_rn(acc[k], __fmul_rn(wsorted[(size_t)k * BN + j], gv));
+    }
+}
+// the voxel corner k of `cell` nominally lands in, -1 outside the volume
+__device__ __forceinline__ void corner_voxels(int cell, int R, int vk[8])
+{
+    const int cx = cell / (R * R), cy = (cell / R) % R, cz = cell % R;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int x = cx + (k >> 2), y = cy + ((k >> 1) & 1), z = cz + (k & 1);
+        vk[k] = x < R && y < R && z < R ? (x * R + y) * R + z : -1;
+    }
+}
+
+template <bool HAS_INDS>
+__global__ __launch_bounds__(kPvBlock) void k_vs_cell_partials(const float *__restrict__ gout, const int32_t *__restrict__ perm,
+                                                               const int32_t *__restrict__ seg, const float *__restrict__ wsorted,
+                                                               const int32_t *__restrict__ isorted, float *part, int B, int R, int N,
+                                                               int c_first, int C_total, int c_chunk)
+{
+    const int R3 = R * R * R, b = blockIdx.z, cl = blockIdx.y, lane = threadIdx.x & 63;
+    const int cell = blockIdx.x * kPvBlock + threadIdx.x;           // (no early return: the wave's shuffles below need every lane)
+    const bool in = cell < R3;
+    const size_t BN = (size_t)B * N;
+    const int j0 = in ? seg[(size_t)b * R3 + cell] : 0, j1 = in ? seg[(size_t)b * R3 + cell + 1] : 0;
+    const float *g = gout + ((size_t)b * C_total + c_first + cl) * N - (size_t)b * N;      // perm holds b N + p
+    float acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    int vk[8];
+    corner_voxels(in ? cell : 0, R, vk);
+    const bool is_long = j1 - j0 > kPvShort;
+    if (!is_long)
+        for (int j = j0; j < j1; ++j) add_point<HAS_INDS>(acc, wsorted, isorted, BN, j, g[perm[j]], vk);
+    unsigned long long longs = __ballot(is_long);                   // wave-uniform: every lane runs the loop below alike
+    while (longs) {
+        const int src = __ffsll((long long)longs) - 1;
+        longs &= longs - 1ull;
+        const int a0 = __shfl(j0, src), a1 = __shfl(j1, src);
+        int wk[8];
+        corner_voxels(__shfl(cell, src), R, wk);
+        float s[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        for (int j = a0 + lane; j < a1; j += 64) add_point<HAS_INDS>(s, wsorted, isorted, BN, j, g[perm[j]], wk);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) s[k] = __fadd_rn(s[k], __shfl_xor(s[k], off));
+            if (lane == src) acc[k] = s[k];
+        }
+    }
+    if (in) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) part[(((size_t)b * c_chunk + cl) * 8 + k) * R3 + cell] = acc[k];
+    }
+}
+
+__global__ __launch_bounds__(kPvBlock) void k_vs_vol_from_partials(const float *__restrict__ part, float *gvol, int C, int R, int c_first,
+                                                                   int c_chunk, int c_count)
+{
+    const int R3 = R * R * R, b = blockIdx.y;
+    const size_t t = (size_t)blockIdx.x * kPvBlock + threadIdx.x;
+    if (t >= (size_t)c_count * R3) return;
+    const int cl = (int)(t / R3), v = (int)(t - (size_t)cl * R3);
+    const int vx = v / (R * R), vy = (v / R) % R, vz = v % R;
+    float acc = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int cx = vx - (k >> 2), cy = vy - ((k >> 1) & 1), cz = vz - (k & 1);
+        if (cx < 0 || cy < 0 || cz < 0) continue;
+        acc = __fadd_rn(acc, part[(((size_t)b * c_chunk + cl) * 8 + k) * R3 + (size_t)((cx * R + cy) * R + cz)]);
+    }
+    gvol[((size_t)b * C + c_first + cl) * R3 + v] = acc;
+}
+
+// ---------------------------------------------------------------------------- backward to the positions
+__global__ __launch_bounds__(kPvBlock) void k_vs_bwd_pos(const float *__restrict__ vol, const float *__restrict__ pos,
+                                                         const float *__restrict__ gout, float *gpos, int C, int R, int N, int c_off,
+                                                         int C_total, int mode, int accumulate)
+{
+    const int p = blockIdx.x * kPvBlock + threadIdx.x, b = blockIdx.y;
+    if (p >= N) return;
+    float raw[3], u[3];
+    load_u(pos, mode, b, p, N, R, raw, u);
+    Corners cn;
+    corners_of(u, R, false, cn);
+    float d1[3], d0[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        d1[j] = u[j] - floorf(u[j]);
+        d0[j] = 1.0f - d1[j];
+    }
+    const float wyz[4] = {d0[1] * d0[2], d0[1] * d1[2], d1[1] * d0[2], d1[1] * d1[2]};
+    const float wxz[4] = {d0[0] * d0[2], d0[0] * d1[2], d1[0] * d0[2], d1[0] * d1[2]};
+    const float wxy[4] = {d0[0] * d0[1], d0[0] * d1[1], d1[0] * d0[1], d1[0] * d1[1]};
+    const size_t R3 = (size_t)R * R * R;
+    float gx = 0.0f, gy = 0.0f, gz = 0.0f;
+    for (int c = 0; c < C; ++c) {
+        const float *f = vol + ((size_t)b * C + c) * R3;
+        const float go = gout[((size_t)b * C_total + c_off + c) * N + p];
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = f[cn.idx[k]];
+        const float ddx = (v[4] - v[0]) * wyz[0] + (v[5] - v[1]) * wyz[1] + (v[6] - v[2]) * wyz[2] + (v[7] - v[3]) * wyz[3];
+        const float ddy = (v[2] - v[0]) * wxz[0] + (v[3] - v[1]) * wxz[1] + (v[6] - v[4]) * wxz[2] + (v[7] - v[5]) * wxz[3];
+        const float ddz = (v[1] - v[0]) * wxy[0] + (v[3] - v[2]) * wxy[1] + (v[5] - v[4]) * wxy[2] + (v[7] - v[6]) * wxy[3];
+        gx += go * ddx;
+        gy += go * ddy;
+        gz += go * ddz;
+    }
+    // grid_sample's border rule: no gradient for a coordinate the clamp holds (u <= 0 or u >= r - 1, a NaN included)
+    const float scale = mode == 0 ? (float)R : 1.0f, top = (float)(R - 1);
+    const float res[3] = {raw[0] > 0.0f && raw[0] < top ? scale * gx : 0.0f, raw[1] > 0.0f && raw[1] < top ? scale * gy : 0.0f,
+                          raw[2] > 0.0f && raw[2] < top ? scale * gz : 0.0f};
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        float *dst = mode == 0 ? gpos + ((size_t)b * N + p) * 3 + j : gpos + ((size_t)b * 3 + j) * N + p;
+        *dst = accumulate ? *dst + res[j] : res[j];
+    }
+}
+
+inline int check_sizes(int B, int C, int N, int R, const char *what)
+{
+    if (B < 0 || C < 0 || N < 0 || R < 1) return set_error(DEFTET_EINVAL, "%s: negative size or resolution below 1", what);
+    if (B > 65535) return set_error(DEFTET_ELIMIT, "%s: more than 65535 shapes", what);
+    if ((long long)R * R * R * (long long)(B > 0 ? B : 1) >= 0x7FFFFFFFll || (long long)B * N >= 0x7FFFFFFFll)
+        return set_error(DEFTET_ELIMIT, "%s: B R^3 or B N does not fit 31 bits", what);
+    if ((long long)C * R * R * R / kPvBlock >= 0x7FFFFFFFll) return set_error(DEFTET_ELIMIT, "%s: C R^3 too large", what);
+    return DEFTET_OK;
+}
+
+}  // namespace
+}  // namespace deftet
+
+using namespace deftet;
+
+extern "C" {
+
+size_t deftet_pointvoxel_workspace_bytes(int n_batch, int n_point, int resolution)
+{
+    if (n_batch < 0 || n_point < 0 || resolution < 0) return 0;
+    const size_t n = (size_t)n_batch * (size_t)n_point, r = (size_t)resolution;
+    // the sort with the voxelization's own perm [B N] and seg [B R^3 + 1], or the volume backward's corner partials
+    const size_t one = partial_bytes_per_channel((size_t)n_batch, r * r * r);
+    const size_t sorting = sort_bytes(n) + align_up(n * 4, 256) + align_up(((size_t)n_batch * r * r * r + 1) * 4, 256) + 512;
+    const size_t partials = (one > kPvPartialBudget ? one : kPvPartialBudget) + 256;
+    return sorting > partials ? sorting : partials;
+}
+
+int deftet_avg_voxelize_fwd_f32(const float *feat, const int32_t *coords, float *out, int32_t *ind, int32_t *cnt, int n_batch,
+                                int n_channel, int n_point, int resolution, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const int B = n_batch, C = n_channel, N = n_point, R = resolution;
+    if (int rc = check_sizes(B, C, N, R, "avg_voxelize")) return rc;
+    const size_t R3 = (size_t)R * R * R;
+    hipStream_t st = as_stream(stream);
+    if (B == 0) return DEFTET_OK;
+    DEFTET_CHECK_ARG(cnt && (out || C == 0), "avg_voxelize: null output");
+    if (N == 0 || C == 0) {
+        if (C > 0) DEFTET_HIP(hipMemsetAsync(out, 0, (size_t)B * C * R3 * sizeof(float), st));
+        if (N == 0) {
+            DEFTET_HIP(hipMemsetAsync(cnt, 0, (size_t)B * R3 * sizeof(int32_t), st));
+            return DEFTET_OK;
+        }
+    }
+    DEFTET_CHECK_ARG(coords && ind && (feat || C == 0), "avg_voxelize: null pointer");
+    const size_t n = (size_t)B * N;
+    const unsigned n_keys = (unsigned)((size_t)B * R3);
+    SortBufs s;
+    Arena A(workspace, workspace_bytes);
+    if (!carve(A, workspace, workspace_bytes, n, s)) return set_error(DEFTET_EINVAL, "avg_voxelize: workspace missing, misaligned or too small");
+    int32_t *perm = A.take<int32_t>(n), *seg = A.take<int32_t>((size_t)n_keys + 1);
+    if (!A.ok()) return set_error(DEFTET_EINVAL, "avg_voxelize: workspace too small");
+    const unsigned gN = (unsigned)((N + kPvBlock - 1) / kPvBlock);
+    DEFTET_LAUNCH(k_vox_keys, dim3(gN, B), dim3(kPvBlock), st, coords, ind, s.keys, N, R, n_keys);
+    if (int rc = sort_and_segment(s, perm, seg, n, n_keys, st)) return rc;
+    const unsigned gS = (unsigned)((R3 + kPvBlock - 1) / kPvBlock);
+    const int c_per = C > 0 ? channels_per_thread(C, (long long)gS * B) : 1;
+    const unsigned gC = C > 0 ? (unsigned)((C + c_per - 1) / c_per) : 1u;
+    if (gC > 65535u) return set_error(DEFTET_ELIMIT, "avg_voxelize: too many channel chunks");
+    DEFTET_LAUNCH(k_vox_fwd, dim3(gS, gC, B), dim3(kPvBlock), st, feat, (const int32_t *)perm, (const int32_t *)seg, out, cnt, C, N, (int)R3,
+                  c_per);
+    return DEFTET_OK;
+}
+
+int deftet_avg_voxelize_bwd_f32(const float *grad_y, const int32_t *ind, const int32_t *cnt, float *grad_x, int n_batch, int n_channel,
+                                int n_point, int resolution, void *stream)
+{
+    const int B = n_batch, C = n_channel, N = n_point, R = resolution;
+    if (int rc = check_sizes(B, C, N, R, "avg_voxelize_bwd")) return rc;
+    if (B == 0 || C == 0 || N == 0) return DEFTET_OK;
+    DEFTET_CHECK_ARG(grad_y && ind && cnt && grad_x, "avg_voxelize_bwd: null pointer");
+    const unsigned gN = (unsigned)((N + kPvBlock - 1) / kPvBlock);
+    const int c_per = channels_per_thread(C, (long long)gN * B);
+    const unsigned gC = (unsigned)((C + c_per - 1) / c_per);
+    if (gC > 65535u) return set_error(DEFTET_ELIMIT, "avg_voxelize_bwd: too many channel chunks");
+    DEFTET_LAUNCH(k_vox_bwd, dim3(gN, gC, B), dim3(kPvBlock), as_stream(stream), grad_y, ind, cnt, grad_x, C, N, R * R * R, c_per);
+    return DEFTET_OK;
+}
+
+int deftet_voxel_sample_fwd_f32(const float *vol, const float *pos, float *out, int32_t *inds, float *wgts, int n_batch, int n_channel,
+                                int resolution, int n_point, int channel_offset, int n_channel_total, int pos_mode, int legacy,
+                                void *stream)
+{
+    const int B = n_batch, C = n_channel, N = n_point, R = resolution;
+    if (int rc = check_sizes(B, C, N, R, "voxel_sample")) return rc;
+    DEFTET_CHECK_ARG(channel_offset >= 0 && n_channel_total >= channel_offset + C, "voxel_sample: channel offset + channels exceed the destination");
+    DEFTET_CHECK_ARG(pos_mode == 0 || pos_mode == 1, "voxel_sample: pos_mode 0 (pos [B,N,3]) or 1 (coords [B,3,N])");
+    DEFTET_CHECK_ARG((inds == nullptr) == (wgts == nullptr), "voxel_sample: inds and wgts come together");
+    if (B == 0 || N == 0 || (C == 0 && !inds)) return DEFTET_OK;
+    DEFTET_CHECK_ARG(pos && (C == 0 || (vol && out)), "voxel_sample: null pointer");
+    const unsigned gN = (unsigned)((N + kPvBlock - 1) / kPvBlock);
+    const int c_per = C > 0 ? channels_per_thread(C, (long long)gN * B) : 1;
+    const unsigned gC = C > 0 ? (unsigned)((C + c_per - 1) / c_per) : 1u;
+    if (gC > 65535u) return set_error(DEFTET_ELIMIT, "voxel_sample: too many channel chunks");
+    DEFTET_LAUNCH(k_vs_fwd, dim3(gN, gC, B), dim3(kPvBlock), as_stream(stream), vol, pos, out, inds, wgts, C, R, N, channel_offset,
+                  n_channel_total, pos_mode, legacy, c_per);
+    return DEFTET_OK;
+}
+
+int deftet_voxel_cells_f32(const float *pos, int pos_mode, int32_t *perm, int32_t *seg, float *wsorted, int n_batch, int n_point,
+                           int resolution, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const int B = n_batch, N = n_point, R = resolution;
+    if (int rc = check_sizes(B, 0, N, R, "voxel_cells")) return rc;
+    DEFTET_CHECK_ARG(pos_mode == 0 || pos_mode == 1, "voxel_cells: pos_mode 0 or 1");
+    if (B == 0) return DEFTET_OK;
+    DEFTET_CHECK_ARG(seg, "voxel_cells: null pointer");
+    hipStream_t st = as_stream(stream);
+    const unsigned n_keys = (unsigned)((size_t)B * R * R * R);
+    if (N == 0) {
+        DEFTET_HIP(hipMemsetAsync(seg, 0, ((size_t)n_keys + 1) * sizeof(int32_t), st));
+        return DEFTET_OK;
+    }
+    DEFTET_CHECK_ARG(pos && perm && wsorted, "voxel_cells: null pointer");
+    const size_t n = (size_t)B * N;
+    SortBufs s;
+    Arena A(workspace, workspace_bytes);
+    if (!carve(A, workspace, workspace_bytes, n, s)) return set_error(DEFTET_EINVAL, "voxel_cells: workspace missing, misaligned or too small");
+    DEFTET_LAUNCH(k_cell_keys, dim3((unsigned)((N + kPvBlock - 1) / kPvBlock), B), dim3(kPvBlock), st, pos, pos_mode, s.keys, N, R);
+    if (int rc = sort_and_segment(s, perm, seg, n, n_keys, st)) return rc;
+    DEFTET_LAUNCH(k_cell_weights, dim3((unsigned)((n + kPvBlock - 1) / kPvBlock)), dim3(kPvBlock), st, pos, pos_mode, (const int32_t *)perm,
+                  wsorted, B, N, R);
+    return DEFTET_OK;
+}
+
+int deftet_voxel_cells_from_inds_i32(const int32_t *inds, const float *wgts, int32_t *perm, int32_t *seg, float *wsorted,
+                                     int32_t *isorted, int n_batch, int n_point, int resolution, void *workspace, size_t workspace_bytes,
+                                     void *stream)
+{
+    const int B = n_batch, N = n_point, R = resolution;
+    if (int rc = check_sizes(B, 0, N, R, "voxel_cells_from_inds")) return rc;
+    if (B == 0) return DEFTET_OK;
+    DEFTET_CHECK_ARG(seg, "voxel_cells_from_inds: null pointer");
+    hipStream_t st = as_stream(stream);
+    const int R3 = R * R * R;
+    const unsigned n_keys = (unsigned)((size_t)B * R3);
+    if (N == 0) {
+        DEFTET_HIP(hipMemsetAsync(seg, 0, ((size_t)n_keys + 1) * sizeof(int32_t), st));
+        return DEFTET_OK;
+    }
+    DEFTET_CHECK_ARG(inds && wgts && perm && wsorted && isorted, "voxel_cells_from_inds: null pointer");
+    const size_t n = (size_t)B * N;
+    SortBufs s;
+    Arena A(workspace, workspace_bytes);
+    if (!carve(A, workspace, workspace_bytes, n, s))
+        return set_error(DEFTET_EINVAL, "voxel_cells_from_inds: workspace missing, misaligned or too small");
+    DEFTET_LAUNCH(k_inds_keys, dim3((unsigned)((N + kPvBlock - 1) / kPvBlock), B), dim3(kPvBlock), st, inds, s.keys, N, R3, n_keys);
+    if (int rc = sort_and_segment(s, perm, seg, n, n_keys, st)) return rc;
+    DEFTET_LAUNCH(k_inds_gather, dim3((unsigned)((n + kPvBlock - 1) / kPvBlock)), dim3(kPvBlock), st, inds, wgts, (const int32_t *)perm, wsorted,
+                  isorted, B, N);
+    return DEFTET_OK;
+}
+
+int deftet_voxel_sample_bwd_vol_f32(const float *grad_out, const int32_t *perm, const int32_t *seg, const float *wsorted,
+                                    const int32_t *isorted, float *grad_vol, int n_batch, int n_channel, int resolution, int n_point,
+                                    int channel_offset, int n_channel_total, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const int B = n_batch, C = n_channel, N = n_point, R = resolution;
+    if (int rc = check_sizes(B, C, N, R, "voxel_sample_bwd_vol")) return rc;
+    DEFTET_CHECK_ARG(channel_offset >= 0 && n_channel_total >= channel_offset + C, "voxel_sample_bwd_vol: channel offset + channels exceed the source");
+    if (B == 0 || C == 0) return DEFTET_OK;
+    DEFTET_CHECK_ARG(seg && grad_vol && (N == 0 || (grad_out && perm && wsorted)), "voxel_sample_bwd_vol: null pointer");
+    const size_t R3 = (size_t)R * R * R, one = partial_bytes_per_channel((size_t)B, R3);
+    if (!workspace || ((uintptr_t)workspace & 255) != 0 || workspace_bytes < one)
+        return set_error(DEFTET_EINVAL, "voxel_sample_bwd_vol: workspace missing, misaligned or below one channel of partials");
+    size_t fit = workspace_bytes / one;
+    if (fit > kPvPartialBudget / one) fit = kPvPartialBudget / one > 0 ? kPvPartialBudget / one : 1;
+    const int c_chunk = (int)(fit > 65535 ? 65535 : fit) < C ? (int)(fit > 65535 ? 65535 : fit) : C;
+    float *part = static_cast<float *>(workspace);
+    hipStream_t st = as_stream(stream);
+    const unsigned gCell = (unsigned)((R3 + kPvBlock - 1) / kPvBlock);
+    for (int c0 = 0; c0 < C; c0 += c_chunk) {                       // one chunk after the other on the stream: the scratch is reused
+        const int cc = C - c0 < c_chunk ? C - c0 : c_chunk;
+        const dim3 gridA(gCell, (unsigned)cc, (unsigned)B), gridB((unsigned)(((size_t)cc * R3 + kPvBlock - 1) / kPvBlock), (unsigned)B);
+        if (isorted)
+            DEFTET_LAUNCH(k_vs_cell_partials<true>, gridA, dim3(kPvBlock), st, grad_out, perm, seg, wsorted, isorted, part, B, R, N,
+                          channel_offset + c0, n_channel_total, c_chunk);
+        else
+            DEFTET_LAUNCH(k_vs_cell_partials<false>, gridA, dim3(kPvBlock), st, grad_out, perm, seg, wsorted, isorted, part, B, R, N,
+                          channel_offset + c0, n_channel_total, c_chunk);
+        DEFTET_LAUNCH(k_vs_vol_from_partials, gridB, dim3(kPvBlock), st, (const float *)part, grad_vol, C, R, c0, c_chunk, cc);
+    }
+    return DEFTET_OK;
+}
+
+int deftet_voxel_sample_bwd_pos_f32(const float *vol, const float *pos, const float *grad_out, float *grad_pos, int n_batch, int n_channel,
+                                    int resolution, int n_point, int channel_offset, int n_channel_total, int pos_mode, int accumulate,
+                                    void *stream)
+{
+    const int B = n_batch, C = n_channel, N = n_point, R = resolution;
+    if (int rc = check_sizes(B, C, N, R, "voxel_sample_bwd_pos")) return rc;
+    DEFTET_CHECK_ARG(channel_offset >= 0 && n_channel_total >= channel_offset + C, "voxel_sample_bwd_pos: channel offset + channels exceed the source");
+    DEFTET_CHECK_ARG(pos_mode == 0 || pos_mode == 1, "voxel_sample_bwd_pos: pos_mode 0 or 1");
+    if (B == 0 || N == 0) return DEFTET_OK;
+    DEFTET_CHECK_ARG(pos && grad_pos && (C == 0 || (vol && grad_out)), "voxel_sample_bwd_pos: null pointer");
+    DEFTET_LAUNCH(k_vs_bwd_pos, dim3((unsigned)((N + kPvBlock - 1) / kPvBlock), B), dim3(kPvBlock), as_stream(stream), vol, pos, grad_out,
+                  grad_pos, C, R, N, channel_offset, n_channel_total, pos_mode, accumulate);
+    return DEFTET_OK;
+}
+
+}  // extern "C"

@@ -1967,3 +1967,228 @@ def face_gather(z, xy, act, topology):
     if not isinstance(topology, FaceTopology):
         raise TypeError("face_gather: topology must be a hip_ops.FaceTopology")
     return _FaceGather.apply(z, xy, act, topology)
+
+
+# ------------------------------------------------------------------------------------
+# point-voxel operators (pointvoxel.hip): average voxelization and trilinear sampling of voxel volumes
+# ------------------------------------------------------------------------------------
+def _pv_need(t, dtype, what):
+    if t.dtype != dtype:
+        raise RuntimeError("%s must be %s (got %s)" % (what, str(dtype).replace("torch.", ""), str(t.dtype).replace("torch.", "")))
+    return t.contiguous()
+
+
+def _pv_workspace(lib, dev, B, N, R):
+    nbytes = lib.deftet_pointvoxel_workspace_bytes(B, N, R)
+    return _lib.workspace(dev, nbytes), nbytes
+
+
+def avg_voxelize_fwd(features, coords, resolution):
+    """(out f32 [B,C,R^3], ind i32 [B,N], cnt i32 [B,R^3]) of features f32 [B,C,N] and coords i32 [B,3,N]: the extension's
+    avg_voxelize_forward.  out[b,c,s] adds feat * (1.0f / cnt) over the points of voxel s in ascending point order, from 0 (the
+    bits of the reference kernel run serially); a coordinate outside [0,R) gives ind = -1 and takes no part.  No atomics."""
+    _lib.require_gpu(features, coords)
+    lib = _lib.load()
+    features, coords = _pv_need(features, torch.float32, "avg_voxelize: features"), _pv_need(coords, torch.int32, "avg_voxelize: coords")
+    R = int(resolution)
+    if features.dim() != 3 or coords.dim() != 3 or coords.shape[1] != 3 or R < 1:
+        raise RuntimeError("avg_voxelize: features [B,C,N], coords [B,3,N] and a resolution >= 1 expected")
+    B, C, N = features.shape
+    if coords.shape[0] != B or coords.shape[2] != N or coords.device != features.device:
+        raise RuntimeError("avg_voxelize: coords %s do not match features %s" % (tuple(coords.shape), tuple(features.shape)))
+    dev = features.device
+    out = torch.empty(B, C, R ** 3, device=dev, dtype=torch.float32)
+    ind = torch.empty(B, N, device=dev, dtype=torch.int32)
+    cnt = torch.empty(B, R ** 3, device=dev, dtype=torch.int32)
+    with _lib.on_device(dev):
+        ws, nbytes = _pv_workspace(lib, dev, B, N, R)
+        _lib.check(lib.deftet_avg_voxelize_fwd_f32(_lib.ptr(features), _lib.ptr(coords), _lib.ptr(out), _lib.ptr(ind), _lib.ptr(cnt), B, C, N, R,
+                                                   _lib.ptr(ws), nbytes, _lib.current_stream(dev)), "deftet_avg_voxelize_fwd_f32")
+    return out, ind, cnt
+
+
+def avg_voxelize_bwd(grad_y, ind, cnt):
+    """grad_x f32 [B,C,N] = grad_y[b,c,ind] * (1.0f / cnt[ind]) of grad_y f32 [B,C,R^3]: avg_voxelize_backward, as a gather."""
+    _lib.require_gpu(grad_y, ind, cnt)
+    lib = _lib.load()
+    grad_y = _pv_need(grad_y, torch.float32, "avg_voxelize_bwd: grad_y")
+    ind, cnt = _pv_need(ind, torch.int32, "avg_voxelize_bwd: ind"), _pv_need(cnt, torch.int32, "avg_voxelize_bwd: cnt")
+    if grad_y.dim() != 3 or ind.dim() != 2 or cnt.dim() != 2:
+        raise RuntimeError("avg_voxelize_bwd: grad_y [B,C,R^3], ind [B,N], cnt [B,R^3] expected")
+    B, C, S = grad_y.shape
+    R = int(round(S ** (1.0 / 3.0)))
+    if R ** 3 != S or ind.shape[0] != B or tuple(cnt.shape) != (B, S):
+        raise RuntimeError("avg_voxelize_bwd: grad_y %s, ind %s, cnt %s do not agree" % (tuple(grad_y.shape), tuple(ind.shape), tuple(cnt.shape)))
+    N, dev = ind.shape[1], grad_y.device
+    grad_x = torch.empty(B, C, N, device=dev, dtype=torch.float32)
+    with _lib.on_device(dev):
+        _lib.check(lib.deftet_avg_voxelize_bwd_f32(_lib.ptr(grad_y), _lib.ptr(ind), _lib.ptr(cnt), _lib.ptr(grad_x), B, C, N, R,
+                                                   _lib.current_stream(dev)), "deftet_avg_voxelize_bwd_f32")
+    return grad_x
+
+
+class VoxelCells:
+    """The points of one set sorted by the cell they fall in at one resolution (deftet_voxel_cells_*): what the backward to the
+    volumes gathers through.  Volumes of equal resolution share it."""
+    __slots__ = ("perm", "seg", "wsorted", "isorted", "B", "N", "R")
+
+
+def _voxel_cells(lib, B, N, R, dev, pos=None, pos_mode=0, inds=None, wgts=None):
+    cells = VoxelCells()
+    cells.B, cells.N, cells.R = B, N, R
+    cells.perm = torch.empty(B * N, device=dev, dtype=torch.int32)
+    cells.seg = torch.empty(B * R ** 3 + 1, device=dev, dtype=torch.int32)
+    cells.wsorted = torch.empty(8, B * N, device=dev, dtype=torch.float32)
+    cells.isorted = torch.empty(8, B * N, device=dev, dtype=torch.int32) if inds is not None else None
+    with _lib.on_device(dev):
+        ws, nbytes = _pv_workspace(lib, dev, B, N, R)
+        if inds is None:
+            _lib.check(lib.deftet_voxel_cells_f32(_lib.ptr(pos), pos_mode, _lib.ptr(cells.perm), _lib.ptr(cells.seg), _lib.ptr(cells.wsorted),
+                                                  B, N, R, _lib.ptr(ws), nbytes, _lib.current_stream(dev)), "deftet_voxel_cells_f32")
+        else:
+            _lib.check(lib.deftet_voxel_cells_from_inds_i32(_lib.ptr(inds), _lib.ptr(wgts), _lib.ptr(cells.perm), _lib.ptr(cells.seg),
+                                                            _lib.ptr(cells.wsorted), _lib.ptr(cells.isorted), B, N, R, _lib.ptr(ws), nbytes,
+                                                            _lib.current_stream(dev)), "deftet_voxel_cells_from_inds_i32")
+    return cells
+
+
+def _bwd_vol(lib, gout, cells, C, c_off, C_total):
+    B, N, R, dev = cells.B, cells.N, cells.R, gout.device
+    gvol = torch.empty(B, C, R, R, R, device=dev, dtype=torch.float32)
+    with _lib.on_device(dev):
+        ws, nbytes = _pv_workspace(lib, dev, B, N, R)
+        _lib.check(lib.deftet_voxel_sample_bwd_vol_f32(_lib.ptr(gout), _lib.ptr(cells.perm), _lib.ptr(cells.seg), _lib.ptr(cells.wsorted),
+                                                       _lib.ptr(cells.isorted), _lib.ptr(gvol), B, C, R, N, c_off, C_total, _lib.ptr(ws), nbytes,
+                                                       _lib.current_stream(dev)), "deftet_voxel_sample_bwd_vol_f32")
+    return gvol
+
+
+class _VoxelSample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, append_pos, pos_mode, *volumes):
+        lib = _lib.load()
+        dev = pos.device
+        B, N = (pos.shape[0], pos.shape[1]) if pos_mode == 0 else (pos.shape[0], pos.shape[2])
+        C_feat = sum(v.shape[1] for v in volumes)
+        C_total = C_feat + (3 if append_pos else 0)
+        out = torch.empty(B, C_total, N, device=dev, dtype=torch.float32)
+        c_off = 0
+        with _lib.on_device(dev):
+            for v in volumes:
+                _lib.check(lib.deftet_voxel_sample_fwd_f32(_lib.ptr(v), _lib.ptr(pos), _lib.ptr(out), None, None, B, v.shape[1], v.shape[-1], N,
+                                                           c_off, C_total, pos_mode, 0, _lib.current_stream(dev)),
+                           "deftet_voxel_sample_fwd_f32")
+                c_off += v.shape[1]
+        if append_pos:
+            out[:, C_feat:, :].copy_(pos.transpose(1, 2) if pos_mode == 0 else pos)
+        ctx.save_for_backward(pos, *volumes)
+        ctx.args = (bool(append_pos), pos_mode, B, N, C_feat, C_total)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        pos, volumes = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        append_pos, pos_mode, B, N, C_feat, C_total = ctx.args
+        lib = _lib.load()
+        dev = pos.device
+        gout = _f32c(gout)
+        grads, cells, c_off = [], {}, 0
+        for k, v in enumerate(volumes):
+            C, R = v.shape[1], v.shape[-1]
+            if ctx.needs_input_grad[3 + k]:
+                if R not in cells:                                   # one sort per point set and distinct resolution
+                    cells[R] = _voxel_cells(lib, B, N, R, dev, pos=pos, pos_mode=pos_mode)
+                grads.append(_bwd_vol(lib, gout, cells[R], C, c_off, C_total))
+            else:
+                grads.append(None)
+            c_off += C
+        gpos = None
+        if ctx.needs_input_grad[0]:
+            gpos = torch.zeros_like(pos) if not volumes else torch.empty_like(pos)
+            c_off = 0
+            with _lib.on_device(dev):
+                for k, v in enumerate(volumes):                      # list order; channels ascending inside the kernel
+                    _lib.check(lib.deftet_voxel_sample_bwd_pos_f32(_lib.ptr(v), _lib.ptr(pos), _lib.ptr(gout), _lib.ptr(gpos), B, v.shape[1],
+                                                                   v.shape[-1], N, c_off, C_total, pos_mode, int(k > 0),
+                                                                   _lib.current_stream(dev)), "deftet_voxel_sample_bwd_pos_f32")
+                    c_off += v.shape[1]
+            if append_pos:
+                gpos += gout[:, C_feat:, :].transpose(1, 2) if pos_mode == 0 else gout[:, C_feat:, :]
+        return (gpos, None, None) + tuple(grads)
+
+
+def voxel_sample(volumes, pos, append_pos=False, voxel_units=False):
+    """f32 [B, sum C_k (+3), N]: the volumes f32 [B,C_k,R_k,R_k,R_k] read trilinearly at pos f32 [B,N,3] and written side by side into
+    one result (`sample_f`, pc_model.py:182-194: every volume's launch writes its own channel range, so there is no per-volume
+    tensor and no torch.cat; with append_pos the three position rows are one strided torch copy into the same tensor).  Per volume u = clamp((pos + 0.5) R, 0, R-1),
+    lo = floor(u), hi = min(lo + 1, R - 1), the eight products added in corner order 000 .. 111 (z fastest).  append_pos: the last
+    three channels are pos transposed (decode_pos / decode_occ).  voxel_units=True: `pos` is coords f32 [B,3,N] already in voxel
+    units, u = clamp(coords, 0, R - 1) (`trilinear_devoxelize`'s argument; appended as it stands).
+    Differentiable in every volume and in pos.  The gradient of a volume is a gather over the points sorted by cell (one sort per
+    distinct R): no atomics, the same bits on every run.  The gradient of pos follows grid_sample's border rule: 0 for a coordinate
+    the clamp holds (u <= 0 or u >= R - 1), the right-hand cell's slope at an interior integer u."""
+    volumes = list(volumes)
+    _lib.require_gpu(pos, *volumes)
+    pos = _pv_need(pos, torch.float32, "voxel_sample: pos")
+    if voxel_units:
+        if pos.dim() != 3 or pos.shape[1] != 3:
+            raise RuntimeError("voxel_sample: coords [B,3,N] expected with voxel_units")
+    elif pos.dim() != 3 or pos.shape[2] != 3:
+        raise RuntimeError("voxel_sample: pos [B,N,3] expected")
+    B = pos.shape[0]
+    vols = []
+    for v in volumes:
+        v = _pv_need(v, torch.float32, "voxel_sample: volume")
+        if v.dim() != 5 or v.shape[2] != v.shape[3] or v.shape[3] != v.shape[4] or v.shape[4] < 1:
+            raise RuntimeError("voxel_sample: volumes [B,C,R,R,R] expected (got %s)" % (tuple(v.shape),))
+        if v.shape[0] != B or v.device != pos.device:
+            raise RuntimeError("voxel_sample: volume %s and pos %s differ in batch or device" % (tuple(v.shape), tuple(pos.shape)))
+        vols.append(v)
+    return _VoxelSample.apply(pos, bool(append_pos), 1 if voxel_units else 0, *vols)
+
+
+def trilinear_devoxelize_fwd(r, is_training, coords, features):
+    """(outs f32 [B,C,N], inds i32 [B,8,N], wgts f32 [B,8,N]) of coords f32 [B,3,N] in voxel units and features f32 [B,C,r^3]: the
+    extension's trilinear_devoxelize_forward, one fixed expression per point (the reference kernel's bits).  hi = lo where
+    d == 0, so nothing past r - 1 is read; coordinates are clamped to [0, r-1] first (the reference reads out of bounds there).
+    Not training: inds and wgts are [1]-shaped zeros."""
+    _lib.require_gpu(coords, features)
+    lib = _lib.load()
+    coords, features = _pv_need(coords, torch.float32, "trilinear_devoxelize: coords"), _pv_need(features, torch.float32, "trilinear_devoxelize: features")
+    r = int(r)
+    if coords.dim() != 3 or coords.shape[1] != 3 or features.dim() != 3 or r < 1:
+        raise RuntimeError("trilinear_devoxelize: coords [B,3,N] and features [B,C,r^3] expected")
+    B, C, S = features.shape
+    if S != r ** 3 or coords.shape[0] != B or coords.device != features.device:
+        raise RuntimeError("trilinear_devoxelize: features %s do not match r = %d and coords %s" % (tuple(features.shape), r, tuple(coords.shape)))
+    N, dev = coords.shape[2], features.device
+    outs = torch.empty(B, C, N, device=dev, dtype=torch.float32)
+    if is_training:
+        inds = torch.empty(B, 8, N, device=dev, dtype=torch.int32)
+        wgts = torch.empty(B, 8, N, device=dev, dtype=torch.float32)
+    else:
+        inds, wgts = torch.zeros(1, device=dev, dtype=torch.int32), torch.zeros(1, device=dev, dtype=torch.float32)
+    with _lib.on_device(dev):
+        _lib.check(lib.deftet_voxel_sample_fwd_f32(_lib.ptr(features), _lib.ptr(coords), _lib.ptr(outs), _lib.ptr(inds) if is_training else None,
+                                                   _lib.ptr(wgts) if is_training else None, B, C, r, N, 0, C, 1, 1, _lib.current_stream(dev)),
+                   "deftet_voxel_sample_fwd_f32")
+    return outs, inds, wgts
+
+
+def trilinear_devoxelize_bwd(grad_y, inds, wgts, r):
+    """grad_x f32 [B,C,r^3] of grad_y f32 [B,C,N] through the recorded inds i32 / wgts f32 [B,8,N]: trilinear_devoxelize_backward on
+    the sampler's atomic-free reduction, keyed by inds[:,0,:].  A term counts where the recorded index is the voxel its corner
+    nominally lands in (cell + corner offset); the kernel's own fallen-back hi indices carry weight 0, so nothing is lost for
+    inds / wgts that come from trilinear_devoxelize_fwd.  Hand-made inds without that lo / hi structure lose the other terms, and a
+    non-finite grad_y does not spread through weight-0 terms as the reference's atomics would (0 * inf)."""
+    _lib.require_gpu(grad_y, inds, wgts)
+    lib = _lib.load()
+    grad_y, wgts = _pv_need(grad_y, torch.float32, "trilinear_devoxelize_bwd: grad_y"), _pv_need(wgts, torch.float32, "trilinear_devoxelize_bwd: wgts")
+    inds, r = _pv_need(inds, torch.int32, "trilinear_devoxelize_bwd: inds"), int(r)
+    if grad_y.dim() != 3 or inds.dim() != 3 or inds.shape != wgts.shape or inds.shape[1] != 8 or r < 1:
+        raise RuntimeError("trilinear_devoxelize_bwd: grad_y [B,C,N] and inds, wgts [B,8,N] expected")
+    B, C, N = grad_y.shape
+    if inds.shape[0] != B or inds.shape[2] != N:
+        raise RuntimeError("trilinear_devoxelize_bwd: grad_y %s and inds %s do not agree" % (tuple(grad_y.shape), tuple(inds.shape)))
+    cells = _voxel_cells(lib, B, N, r, grad_y.device, inds=inds, wgts=wgts)
+    return _bwd_vol(lib, grad_y, cells, C, 0, C).view(B, C, r ** 3)

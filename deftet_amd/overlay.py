@@ -23,6 +23,9 @@ With `deftet_module=True` also `layers.DefTet.deftet` (the `DefTet` nn.Module bu
 operators) — otherwise the reference's own module runs on top of the replaced L1 operators.
 With `render_model=True` also the flat module name `utils_tetsv` (a render-side checkout puts
 diff_render/diftet_6_subdiv/3_model on sys.path and imports it by that name): the surface extraction and its OBJ writers.
+With `point_voxel=True` also `layers.pv_module.functional.backend` (a module whose `_backend` carries the extension's twelve
+names on this library's kernels, so importing it compiles nothing) and `layers.pv_module.functional.devoxelization`
+(`deftet_amd.pointvoxel`); the reference's own functional/*.py, voxelization.py and pvconv.py run unchanged on top.
 Nothing here touches a CPU fallback: every replaced entry point raises on non-GPU tensors.
 """
 import importlib
@@ -77,7 +80,16 @@ def kaolin_shim():
             "kaolin.metrics.trianglemesh": met_tm}
 
 
-def install(kaolin=None, deftet_module=False, stub_cv2=True, render_model=False):
+def point_voxel_modules():
+    """The two modules `point_voxel=True` registers: the extension's backend by name, and the devoxelization functions."""
+    from deftet_amd import pointvoxel
+    backend = types.ModuleType("layers.pv_module.functional.backend")
+    backend._backend = pointvoxel.backend
+    backend.__all__ = ["_backend"]
+    return {"layers.pv_module.functional.backend": backend, "layers.pv_module.functional.devoxelization": pointvoxel}
+
+
+def install(kaolin=None, deftet_module=False, stub_cv2=True, render_model=False, point_voxel=False):
     """Register the overlay in sys.modules; returns the list of names it registered.
     kaolin: True = always shim, False = never, None = shim only if `import kaolin` would fail."""
     done = []
@@ -90,6 +102,10 @@ def install(kaolin=None, deftet_module=False, stub_cv2=True, render_model=False)
     if render_model:
         sys.modules["utils_tetsv"] = importlib.import_module("deftet_amd.render.utils_tetsv")
         done.append("utils_tetsv")
+    if point_voxel:
+        for name, mod in point_voxel_modules().items():
+            sys.modules[name] = mod
+            done.append(name)
     if kaolin is None:
         kaolin = "kaolin" not in sys.modules and importlib.util.find_spec("kaolin") is None
     if kaolin:

@@ -753,6 +753,58 @@ int deftet_face_gather_fwd_f32(const float *z, const float *xy, const float *act
 int deftet_face_gather_bwd_f32(const float *grad_face_xy, const float *grad_face_feat, const int32_t *offsets, const int32_t *slots,
                                float *g_xy, float *g_act, int n_batch, int n_vertex, int n_face, int n_act, void *stream);
 
+/* The point-voxel operators between the point-cloud encoder and the tet grid (pointvoxel.hip).  No float atomics:
+ * both scatters are gathers over a stable sort of the points (by voxel, by cell), so every sum has ONE order and two runs agree
+ * bit for bit.  Workspaces 256-byte aligned, deftet_pointvoxel_workspace_bytes(B, N, R) covers every entry point below.
+ *
+ * deftet_avg_voxelize_fwd_f32 (vox.cu avg_voxelize): feat f32 [B,C,N], coords i32 [B,3,N] -> out f32 [B,C,R^3], ind i32 [B,N] =
+ * x R^2 + y R + z, cnt i32 [B,R^3].  out[b,c,s] = 0 + feat[b,c,i] * (1.0f / (float)cnt[s]) over the points of voxel s in ascending
+ * i, every product rounded, then added (the reference kernel with its threads one after another).  A coordinate outside [0,R)
+ * gives ind = -1: not counted, no contribution, zero gradient.  N = 0: zeros.
+ * deftet_avg_voxelize_bwd_f32: grad_x[b,c,i] = grad_y[b,c,ind[i]] * (1.0f / (float)cnt[ind[i]]), a gather.
+ *
+ * deftet_voxel_sample_fwd_f32: vol f32 [B,C,R,R,R] read at N points -> out[b, channel_offset + c, p] of out f32 [B,C_total,N] (one
+ * call per volume of a list writes its own channel range of the shared result).
+ *   pos_mode 0: pos f32 [B,N,3], u = clamp((pos + 0.5) R, 0, R - 1);   pos_mode 1: coords f32 [B,3,N], u = clamp(coords, 0, R - 1)
+ *   lo = floor(u), d = u - lo, hi = min(lo + 1, R - 1); weights (1-d | d) as (wx * wy) * wz; corners 000 .. 111, z fastest, index
+ *   x R^2 + y R + z; value = the eight products added in that order.  A NaN coordinate is read as 0.
+ *   legacy != 0 (trilinear_devox.cu): hi = lo where d == 0; inds i32 [B,8,N] and wgts f32 [B,8,N] (both or neither) are written.
+ * deftet_voxel_cells_f32: the sort the volume backward needs, per point set and resolution (shared by volumes of equal R):
+ *   perm i32 [B N] (b N + p in cell order, stable), seg i32 [B R^3 + 1] (cell s of shape b owns [seg[b R^3 + s], seg[.. + 1])),
+ *   wsorted f32 [8, B N] (the weights in sorted order, corner-major).
+ * deftet_voxel_cells_from_inds_i32: the same from recorded inds / wgts [B,8,N], keyed by inds[:,0,:] (outside [0,R^3): dropped);
+ *   also isorted i32 [8, B N].
+ * deftet_voxel_sample_bwd_vol_f32: two stages, every grad_out element read once.  Per (channel, cell) the eight corner sums
+ *   part[k] = sum over the cell's points j in sorted order of wsorted[k][j] * grad_out[b, channel_offset + c, p(j)] (a segment of
+ *   up to 32 points one after the other from 0; a longer one by 64 lanes — lane l adds points l, l + 64, ... in that order — and
+ *   a fixed butterfly over the lanes, offsets 32 .. 1); then grad_vol[b,c,v] = the up to eight part[k] of the cells v - k, corner
+ *   k = 000 .. 111 in that order, from 0.  With isorted a term counts only where isorted[k][j] is the voxel corner k of the cell
+ *   nominally lands in (the legacy hi index falls back on lo where its weight is 0): recorded indices that do not have this lo / hi
+ *   structure lose their terms, and a non-finite grad_out does not reach voxels through a weight-0 term.  The workspace holds the
+ *   partials of a chunk of channels (at least B R^3 32 bytes = one channel; deftet_pointvoxel_workspace_bytes gives up to 64 MiB).
+ * deftet_voxel_sample_bwd_pos_f32: grad_pos[b,p,j] (=, or += with accumulate) s * sum_c grad_out[b, channel_offset + c, p] *
+ *   d interp / d u_j, channels ascending, s = R for pos_mode 0 and 1 for pos_mode 1 (grad_pos has the layout of pos); 0 for a
+ *   coordinate the clamp holds (u <= 0 or u >= R - 1: grid_sample's border rule); the right-hand cell at an interior integer u. */
+size_t deftet_pointvoxel_workspace_bytes(int n_batch, int n_point, int resolution);
+int deftet_avg_voxelize_fwd_f32(const float *feat, const int32_t *coords, float *out, int32_t *ind, int32_t *cnt, int n_batch,
+                                int n_channel, int n_point, int resolution, void *workspace, size_t workspace_bytes, void *stream);
+int deftet_avg_voxelize_bwd_f32(const float *grad_y, const int32_t *ind, const int32_t *cnt, float *grad_x, int n_batch, int n_channel,
+                                int n_point, int resolution, void *stream);
+int deftet_voxel_sample_fwd_f32(const float *vol, const float *pos, float *out, int32_t *inds, float *wgts, int n_batch, int n_channel,
+                                int resolution, int n_point, int channel_offset, int n_channel_total, int pos_mode, int legacy,
+                                void *stream);
+int deftet_voxel_cells_f32(const float *pos, int pos_mode, int32_t *perm, int32_t *seg, float *wsorted, int n_batch, int n_point,
+                           int resolution, void *workspace, size_t workspace_bytes, void *stream);
+int deftet_voxel_cells_from_inds_i32(const int32_t *inds, const float *wgts, int32_t *perm, int32_t *seg, float *wsorted,
+                                     int32_t *isorted, int n_batch, int n_point, int resolution, void *workspace, size_t workspace_bytes,
+                                     void *stream);
+int deftet_voxel_sample_bwd_vol_f32(const float *grad_out, const int32_t *perm, const int32_t *seg, const float *wsorted,
+                                    const int32_t *isorted, float *grad_vol, int n_batch, int n_channel, int resolution, int n_point,
+                                    int channel_offset, int n_channel_total, void *workspace, size_t workspace_bytes, void *stream);
+int deftet_voxel_sample_bwd_pos_f32(const float *vol, const float *pos, const float *grad_out, float *grad_pos, int n_batch, int n_channel,
+                                    int resolution, int n_point, int channel_offset, int n_channel_total, int pos_mode, int accumulate,
+                                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif
