@@ -441,7 +441,7 @@ extern "C" int deftet_tet_energies_fwd_f32(const float *tet, const float *inv_v,
 extern "C" int deftet_tet_energies_bwd_f32(const float *tet, const float *inv_v, const double *stats, const float *grad_out,
                                            float *grad_tet, int B, int T, int pow_v, int pow_e, float scale, void *stream_)
 {
-    DEFTET_CHECK_ARG(B >= 0 && T > 0 && B <= 65535 && pow_v >= 1 && pow_e >= 1, "bad argument");
+    DEFTET_CHECK_ARG(B >= 0 && T > 0 && B <= 65535 && pow_v >= 1 && pow_e >= 1 && pow_v <= 16 && pow_e <= 16, "bad argument");
     if (B == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(tet && stats && grad_out && grad_tet && ((uintptr_t)tet & 15) == 0 && ((uintptr_t)grad_tet & 15) == 0,
                      "null or misaligned pointer");

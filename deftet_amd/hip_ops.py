@@ -7,6 +7,7 @@ reference's names and signatures) lives in deftet_amd/layers/ and deftet_amd/uti
 from __future__ import annotations
 
 import collections
+import operator
 import os
 import threading
 
@@ -1565,6 +1566,15 @@ def boundary_index(tet_face_fx3, tet_idx_fx2, occ_bxn, mode=1):
     (Measured and not kept, round 6: the lengths read back on a side stream while the energies are enqueued behind the boundary
     kernels, so that the device has work when the host resumes — the pinned buffer, two events and the stream switch cost the
     host more than the 40 us of overlap return: geometry step 2.29 -> 2.34 ms.)"""
+    if tet_face_fx3.dim() != 2 or tet_face_fx3.shape[1] != 3:
+        raise _lib.DefTetHipError("boundary_index: face [F,3] expected, got %s" % (tuple(tet_face_fx3.shape),))
+    if tet_idx_fx2.dim() != 2 or tuple(tet_idx_fx2.shape) != (tet_face_fx3.shape[0], 2):
+        raise _lib.DefTetHipError("boundary_index: tet_idx [%d,2] expected (one pair of tets per face), got %s"
+                                  % (tet_face_fx3.shape[0], tuple(tet_idx_fx2.shape)))
+    if occ_bxn.dim() != 2:
+        raise _lib.DefTetHipError("boundary_index: occ [B,T] expected, got %s" % (tuple(occ_bxn.shape),))
+    if mode not in (1, 2):
+        raise _lib.DefTetHipError("boundary_index: mode must be 1 (boundary) or 2 (internal), got %r" % (mode,))
     _lib.require_gpu(tet_face_fx3, tet_idx_fx2, occ_bxn)
     lib = _lib.load()
     face = tet_face_fx3.contiguous().long()
@@ -1578,15 +1588,31 @@ def boundary_index(tet_face_fx3, tet_idx_fx2, occ_bxn, mode=1):
     with _lib.on_device(dev):
         ws = _lib.workspace(dev, lib.deftet_boundary_index_workspace_bytes(B, Fi))
         _lib.check(lib.deftet_boundary_index_i64(_lib.ptr(face), _lib.ptr(tidx), _lib.ptr(occ), _lib.ptr(out), _lib.ptr(offs),
-                                                 B, T, Fi, mode, _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
+                                                 B, T, Fi, int(mode), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
                    "deftet_boundary_index_i64")
     o = offs.tolist()                                   # one sync (the reference syncs once per shape)
     return [out[o[b]:o[b + 1]] for b in range(B)]
 
 
+def _energy_pow(name, p):
+    try:
+        q = operator.index(p)
+    except TypeError:
+        q = 0
+    if not 1 <= q <= 16:                                   # the kernels multiply pow times: an integer, 16 at the most
+        raise _lib.DefTetHipError("tet_energies: %s must be an integer in 1..16, got %r" % (name, p))
+    return q
+
+
 class _TetEnergies(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tet_bxfx4x3, inverse_v, pow_v, pow_e, scale):
+        if tet_bxfx4x3.dim() != 4 or tuple(tet_bxfx4x3.shape[2:]) != (4, 3):
+            raise _lib.DefTetHipError("tet_energies: tet [B,T,4,3] expected, got %s" % (tuple(tet_bxfx4x3.shape),))
+        if inverse_v is not None and tuple(inverse_v.shape) != (tet_bxfx4x3.shape[1], 3, 3):     # the kernels read one 3x3 per tet
+            raise _lib.DefTetHipError("tet_energies: inverse_v [%d,3,3] expected (one matrix per tet), got %s"
+                                      % (tet_bxfx4x3.shape[1], tuple(inverse_v.shape)))
+        pow_v, pow_e = _energy_pow("pow_v", pow_v), _energy_pow("pow_e", pow_e)
         _lib.require_gpu(tet_bxfx4x3, inverse_v)
         lib = _lib.load()
         tet = _f32c(tet_bxfx4x3)

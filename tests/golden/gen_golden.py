@@ -20,6 +20,9 @@ What is pinned:
                        get_internal_index (:197-203), paste_occ (:132-136),
                        volume_variance (:239-263), amips_energy (:266-298),
                        edge_length (:320-338), tet_inverse_v (:300-318).
+  deftet_energies_pows.npz  the same file's volume_variance / edge_length at pow 1..5 and at their default (pow=2),
+                       amips_energy (:266-298) with every 7th tet inverted, each with the gradient of its sum w.r.t. the
+                       tets, on 2 x 200 tets of tests/tet_energies_ref.make_tets (GEN_GOLDEN_ONLY=energies writes only this).
   pit_index_<case>.npz A1 index pin: utils/tet_utils.py:28-45 bary_centric_tet evaluated (fp64) for EVERY
                        (tet, query) pair of seeded cases; expected = lowest tet index whose four reference
                        weights all exceed MARGIN, `ambiguous` = queries where a tet at or below that index
@@ -54,6 +57,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 REF = "/root/reference"
 sys.path.insert(0, ROOT)
 from deftet_amd import grids  # noqa: E402
+from tests.tet_energies_ref import make_tets  # noqa: E402
 
 
 def sha(a):
@@ -190,6 +194,44 @@ def pit_index_fixtures(tu, torch):
             name, tet.shape[0], pts.shape[0], int((exp >= 0).sum()), int((exp < 0).sum()), int(amb.sum())))
 
 
+def reference_deftet():
+    """The reference's layers/DefTet/deftet.py DefTet with its third-party and JIT-CUDA imports stubbed."""
+    for modname in ("kaolin", "cv2", "layers.DefTet.check_condition_tetrahedron_base.utils",
+                    "layers.DefTet.tet_face_adj_m_idx.utils", "layers.DefTet.tet_analytic_distance_batch.utils",
+                    "layers.nearest_neighbor"):
+        m = types.ModuleType(modname)
+        for attr in ("check_condition_f_base", "tet_face_adj_m_f_idx", "tet_analytic_distance_f_batch", "NearestNeighbor"):
+            setattr(m, attr, None)
+        sys.modules[modname] = m
+    sys.path.insert(0, REF)
+    from layers.DefTet.deftet import DefTet
+    return DefTet()
+
+
+ENERGY_POWS = (1, 2, 3, 4, 5)
+
+
+def energies_pows_fixture(D, torch):
+    """deftet_energies_pows.npz: volume_variance (:239-263) and edge_length (:320-338) at the exponents the reference supports
+    besides its default, amips_energy (:266-298) on tets some of which are inverted, each with the gradient of its sum w.r.t. the
+    tets — on a few hundred tets of tests/tet_energies_ref.make_tets (fp32 torch on the CPU, as deftet_module.npz)."""
+    tet, inv, inverted = make_tets(2, 200, seed=77)
+    tg = tet.clone().requires_grad_(True)
+    out = dict(tet_bxtx4x3=tet.numpy(), inverse_v=inv.numpy(), inverted=inverted.numpy())
+
+    def record(key, y):
+        (gr,) = torch.autograd.grad(y.sum(), tg)
+        out[key], out["g_" + key] = y.detach().numpy(), gr.numpy()
+
+    for p in ENERGY_POWS:
+        record("volume_variance_pow%d" % p, D.volume_variance(tg, pow=p))
+        record("edge_length_pow%d" % p, D.edge_length(tg, pow=p))
+    record("volume_variance_default", D.volume_variance(tg))
+    record("edge_length_default", D.edge_length(tg))
+    record("amips", D.amips_energy(tg, inv))
+    np.savez_compressed(os.path.join(HERE, "deftet_energies_pows.npz"), **out)
+
+
 def main():
     if not os.path.isdir(REF):
         raise SystemExit("reference tree not present; fixtures can only be generated in the authoring container")
@@ -198,6 +240,10 @@ def main():
     from utils import tet_utils as tu
     import prepare_for_wz as pw
     import utils_tetsv as tsv
+
+    if os.environ.get("GEN_GOLDEN_ONLY") == "energies":
+        energies_pows_fixture(reference_deftet(), torch)
+        return
 
     # ---------------- builders on tiny hand grids and small synthetic grids
     one = (np.array([[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]], float), np.array([[0, 1, 2, 3]]))
@@ -311,16 +357,7 @@ def main():
                             w_f64=w64.detach().numpy(), grad_tet_f64=t64.grad.numpy(), grad_pts_f64=p64.grad.numpy())
 
     # ---------------- layers/DefTet/deftet.py methods with stubbed third-party imports
-    for modname in ("kaolin", "cv2", "layers.DefTet.check_condition_tetrahedron_base.utils",
-                    "layers.DefTet.tet_face_adj_m_idx.utils", "layers.DefTet.tet_analytic_distance_batch.utils",
-                    "layers.nearest_neighbor"):
-        m = types.ModuleType(modname)
-        for attr in ("check_condition_f_base", "tet_face_adj_m_f_idx", "tet_analytic_distance_f_batch", "NearestNeighbor"):
-            setattr(m, attr, None)
-        sys.modules[modname] = m
-    sys.path.insert(0, REF)
-    from layers.DefTet.deftet import DefTet
-    D = DefTet()
+    D = reference_deftet()
     verts, tets = grids.kuhn_grid(4)
     pos = grids.jittered_positions(verts, 4, 3, 0.1)
     tet = torch.from_numpy(grids.gather_tets(pos, tets))
@@ -355,6 +392,7 @@ def main():
         out["boundary_%d" % i] = bnd[i].numpy()
         out["internal_%d" % i] = inn[i].numpy()
     np.savez_compressed(os.path.join(HERE, "deftet_module.npz"), **out)
+    energies_pows_fixture(D, torch)
 
     # ---------------- render-side rebuilds (prepare_for_wz.py, 3_model/deftet.py)
     import prepare_for_wz as W
