@@ -22,6 +22,7 @@
 //    silhouette faces, non-finite or huge ones) and faces spanning more than kMaxSpan cells go to a
 //    per-shape list that every point tests; non-finite / huge points test every face.
 #include <cstring>
+#include "grid_setup.hpp"
 #include "prims.hpp"
 
 #include "common.hpp"
@@ -57,13 +58,6 @@ __device__ __forceinline__ int hit(const float4 r0, const float4 r1, const float
     if (v < 0.0f || u + v > 1.0f) return 0;
     const float t = f * ((e2x * qx + e2y * qy) + e2z * qz);
     return t > kEps ? 1 : 0;
-}
-
-__device__ __forceinline__ int cell_of(float x, float o, float inv, int G)
-{
-    float f = floorf((x - o) * inv);
-    f = fminf(fmaxf(f, 0.f), (float)(G - 1));          // NaN -> 0 (fmaxf/fminf drop NaN)
-    return (int)f;
 }
 
 // one shape's slice of the vertex / face / record arrays.  Uniform batches: V and F per shape, ONE face
@@ -122,7 +116,7 @@ __global__ __launch_bounds__(256) void k_prep(const float *__restrict__ verts, c
     F = M.F;
     const float *vb = verts + (size_t)M.vBase * 3;
     faces += (size_t)M.fBase * 3;
-    float lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
+    BoxStats<2, 0> bs;                                               // (y, z) box of the regular faces
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < F; k += gridDim.x * blockDim.x) {
         long long i0 = faces[(size_t)k * 3], i1 = faces[(size_t)k * 3 + 1], i2 = faces[(size_t)k * 3 + 2];
         if (i0 < 0 || i0 >= V || i1 < 0 || i1 >= V || i2 < 0 || i2 >= V) {      // torch.index_select raises
@@ -145,30 +139,14 @@ __global__ __launch_bounds__(256) void k_prep(const float *__restrict__ verts, c
         kind[(size_t)M.rBase + k] = (signed char)kd;
         box[(size_t)M.rBase + k] = make_float4(bx.ylo, bx.yhi, bx.zlo, bx.zhi);
         if (kd == 1) {
-            lo[0] = fminf(lo[0], bx.ylo); hi[0] = fmaxf(hi[0], bx.yhi);
-            lo[1] = fminf(lo[1], bx.zlo); hi[1] = fmaxf(hi[1], bx.zhi);
+            const float l[2] = {bx.ylo, bx.zlo}, h[2] = {bx.yhi, bx.zhi};
+            bs.add_box(l, h);
         } else if (kd == 2) {
             irreg[(size_t)M.rBase + atomicAdd(&counters[b * 2], 1)] = k;
         }
     }
     if (!kind) return;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            lo[k] = fminf(lo[k], __shfl_xor(lo[k], off));
-            hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off));
-        }
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sh[w][0] = lo[0]; sh[w][1] = hi[0]; sh[w][2] = lo[1]; sh[w][3] = hi[1]; }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const int k = threadIdx.x;
-        float v = sh[0][k];
-        for (int i = 1; i < 4; ++i) v = (k & 1) ? fmaxf(v, sh[i][k]) : fminf(v, sh[i][k]);
-        part[((size_t)b * kParts + blockIdx.x) * 4 + k] = v;
-    }
+    bs.block_store(sh, part + ((size_t)b * kParts + blockIdx.x) * 4);
 }
 
 struct Dom {
@@ -178,23 +156,15 @@ struct Dom {
 // every wave reduces the <= kParts box partials of its shape (cheaper than one more launch)
 __device__ __forceinline__ Dom reduce_domain(const float *__restrict__ part, int nPart, int G)
 {
-    const int lane = threadIdx.x & 63;
-    float v[4] = {INFINITY, -INFINITY, INFINITY, -INFINITY};
-    for (int i = lane; i < nPart; i += 64) {
-        v[0] = fminf(v[0], part[i * 4]); v[1] = fmaxf(v[1], part[i * 4 + 1]);
-        v[2] = fminf(v[2], part[i * 4 + 2]); v[3] = fmaxf(v[3], part[i * 4 + 3]);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        v[0] = fminf(v[0], __shfl_xor(v[0], off)); v[1] = fmaxf(v[1], __shfl_xor(v[1], off));
-        v[2] = fminf(v[2], __shfl_xor(v[2], off)); v[3] = fmaxf(v[3], __shfl_xor(v[3], off));
-    }
+    BoxStats<2, 0> bs;
+    bs.load_reduce(part, nPart);
     Dom d;
-    const bool oky = v[1] >= v[0], okz = v[3] >= v[2];
-    d.oy = oky ? v[0] : 0.f;
-    d.oz = okz ? v[2] : 0.f;
-    d.invy = (oky && v[1] - v[0] > 1e-30f) ? (float)G / (v[1] - v[0]) : 0.f;
-    d.invz = (okz && v[3] - v[2] > 1e-30f) ? (float)G / (v[3] - v[2]) : 0.f;
+    const float *lo = bs.lo, *hi = bs.hi;
+    const bool oky = hi[0] >= lo[0], okz = hi[1] >= lo[1];
+    d.oy = oky ? lo[0] : 0.f;
+    d.oz = okz ? lo[1] : 0.f;
+    d.invy = (oky && hi[0] - lo[0] > 1e-30f) ? (float)G / (hi[0] - lo[0]) : 0.f;
+    d.invz = (okz && hi[1] - lo[1] > 1e-30f) ? (float)G / (hi[1] - lo[1]) : 0.f;
     return d;
 }
 
@@ -217,8 +187,8 @@ __global__ __launch_bounds__(256) void k_bin(const signed char *kind, const floa
     const size_t i = (size_t)M.rBase + k;
     if (kind[i] != 1) return;
     const float4 bx = box[i];
-    const int cy0 = cell_of(bx.x, d.oy, d.invy, G), cy1 = cell_of(bx.y, d.oy, d.invy, G);
-    const int cz0 = cell_of(bx.z, d.oz, d.invz, G), cz1 = cell_of(bx.w, d.oz, d.invz, G);
+    const int cy0 = grid_cell(bx.x, d.oy, d.invy, G), cy1 = grid_cell(bx.y, d.oy, d.invy, G);
+    const int cz0 = grid_cell(bx.z, d.oz, d.invz, G), cz1 = grid_cell(bx.w, d.oz, d.invz, G);
     const int span = (cy1 - cy0 + 1) * (cz1 - cz0 + 1);
     if (PASS == 0 && span > kMaxSpan) {
         irreg[(size_t)M.rBase + atomicAdd(&counters[b * 2], 1)] = k;
@@ -253,7 +223,7 @@ __global__ __launch_bounds__(256) void k_query(const float *__restrict__ points,
     if (!regular) {                                                 // not certified for the grid: every face
         for (int k = 0; k < F; ++k) c += hit(rb[k * 3], rb[k * 3 + 1], rb[k * 3 + 2], px, py, pz);
     } else {
-        const int cy = cell_of(py, dom[b * 4], dom[b * 4 + 2], G), cz = cell_of(pz, dom[b * 4 + 1], dom[b * 4 + 3], G);
+        const int cy = grid_cell(py, dom[b * 4], dom[b * 4 + 2], G), cz = grid_cell(pz, dom[b * 4 + 1], dom[b * 4 + 3], G);
         const size_t cc = (size_t)b * ((size_t)G * G + 1) + (size_t)cz * G + cy;
         const int s = cellStart[cc], e = cellStart[cc + 1];
         int j = s;

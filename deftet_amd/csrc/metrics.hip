@@ -8,6 +8,7 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "grid_setup.hpp"
 
 namespace deftet {
 namespace met {
@@ -180,64 +181,40 @@ __global__ __launch_bounds__(256) void k_pm_stats(const float *__restrict__ face
     const int b = blockIdx.y;
     const int nf = shape_faces(n_face, b, F);
     const float *fb = face + (size_t)b * F * 9;
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, sw = 0.f, cnt = 0.f;
+    BoxStats<3, 2> bs;                                              // sums: largest box extent of the binned faces, their number
     for (int f = blockIdx.x * 256 + threadIdx.x; f < nf; f += gridDim.x * 256) {
         float fc[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) fc[k] = fb[(size_t)f * 9 + k];
         if (!face_finite(fc) || !face_binned(fc)) continue;
-        float w = 0.f;
+        float l[3], h[3], w = 0.f;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const float l = fminf(fc[k], fminf(fc[3 + k], fc[6 + k])), h = fmaxf(fc[k], fmaxf(fc[3 + k], fc[6 + k]));
-            lo[k] = fminf(lo[k], l); hi[k] = fmaxf(hi[k], h); w = fmaxf(w, h - l);
+            l[k] = fminf(fc[k], fminf(fc[3 + k], fc[6 + k])); h[k] = fmaxf(fc[k], fmaxf(fc[3 + k], fc[6 + k]));
+            w = fmaxf(w, h[k] - l[k]);
         }
-        sw += w; cnt += 1.f;
+        bs.add_box(l, h);
+        bs.add_sum(0, w);
+        bs.add_sum(1, 1.f);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], __shfl_xor(lo[k], off)); hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off)); }
-        sw += __shfl_xor(sw, off);
-        cnt += __shfl_xor(cnt, off);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { sh[w][k] = lo[k]; sh[w][3 + k] = hi[k]; }
-        sh[w][6] = sw; sh[w][7] = cnt;
-    }
-    __syncthreads();
-    if (threadIdx.x < 8) {
-        const int k = threadIdx.x;
-        float v = sh[0][k];
-        for (int i = 1; i < 4; ++i) v = k < 3 ? fminf(v, sh[i][k]) : (k < 6 ? fmaxf(v, sh[i][k]) : v + sh[i][k]);
-        part[((size_t)b * kPParts + blockIdx.x) * 8 + k] = v;
-    }
+    bs.block_store(sh, part + ((size_t)b * kPParts + blockIdx.x) * 8);
 }
 
 __global__ __launch_bounds__(64) void k_pm_grid(const float *__restrict__ part, PGrid *grids)
 {
     const int b = blockIdx.x, lane = threadIdx.x;
-    const float *pp = part + ((size_t)b * kPParts + lane) * 8;
-    float lo[3], hi[3], sw = pp[6], cnt = pp[7];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { lo[k] = pp[k]; hi[k] = pp[3 + k]; }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], __shfl_xor(lo[k], off)); hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off)); }
-        sw += __shfl_xor(sw, off);
-        cnt += __shfl_xor(cnt, off);
-    }
+    BoxStats<3, 2> bs;
+    bs.load(part + ((size_t)b * kPParts + lane) * 8);
+    bs.wave_reduce();
     if (lane == 0) {
         PGrid g;
+        const float sw = bs.sum[0], cnt = bs.sum[1];
         const float meanw = cnt > 0.f ? sw / cnt : 0.f;
         float scale = 0.f;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const bool ok = hi[k] >= lo[k];
-            const float l = ok ? lo[k] : 0.f, h = ok ? hi[k] : 0.f, ext = h - l;
+            const bool ok = bs.hi[k] >= bs.lo[k];
+            const float l = ok ? bs.lo[k] : 0.f, h = ok ? bs.hi[k] : 0.f, ext = h - l;
             float n = (meanw > 0.f && ext > 0.f) ? ceilf(ext / meanw) : 1.f;
             n = fminf(fmaxf(n, 1.f), (float)kPGMax);
             g.g[k] = (int)n;
@@ -250,13 +227,6 @@ __global__ __launch_bounds__(64) void k_pm_grid(const float *__restrict__ part, 
         g.any = cnt > 0.f;
         grids[b] = g;
     }
-}
-
-__device__ __forceinline__ int p_cell(float x, float o, float inv, int G)
-{
-    float f = floorf((x - o) * inv);
-    f = fminf(fmaxf(f, 0.f), (float)(G - 1));                         // NaN -> 0
-    return (int)f;
 }
 
 // mode 0: count the cells of every binned face, append the wide faces; mode 1: fill the cell lists
@@ -278,8 +248,8 @@ __global__ __launch_bounds__(256) void k_pm_bin(const float *__restrict__ face, 
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const float l = fminf(fc[k], fminf(fc[3 + k], fc[6 + k])), h = fmaxf(fc[k], fmaxf(fc[3 + k], fc[6 + k]));
-            c0[k] = p_cell(l - pad, g.o[k], g.inv[k], g.g[k]);
-            c1[k] = p_cell(h + pad, g.o[k], g.inv[k], g.g[k]);
+            c0[k] = grid_cell(l - pad, g.o[k], g.inv[k], g.g[k]);
+            c1[k] = grid_cell(h + pad, g.o[k], g.inv[k], g.g[k]);
         }
         binned = (c1[0] - c0[0] + 1) * (c1[1] - c0[1] + 1) * (c1[2] - c0[2] + 1) <= kPMaxCells;
     }
@@ -338,7 +308,7 @@ __global__ __launch_bounds__(256) void k_pm_query(const float *__restrict__ pts,
         if (g.any) {
             int c[3];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) c[k] = p_cell(p[k], g.o[k], g.inv[k], g.g[k]);
+            for (int k = 0; k < 3; ++k) c[k] = grid_cell(p[k], g.o[k], g.inv[k], g.g[k]);
             const float margin = kPMargin * (g.scale + fmaxf(fabsf(p[0]), fmaxf(fabsf(p[1]), fabsf(p[2]))));
             const int *cnt = count + (size_t)b * kPCells, *st = start + (size_t)b * kPCells;
             for (int r = 0;; ++r) {

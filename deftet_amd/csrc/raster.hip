@@ -28,6 +28,7 @@
 
 #include "common.hpp"
 
+#include "grid_setup.hpp"
 #include "prims.hpp"
 
 namespace deftet {
@@ -44,40 +45,15 @@ constexpr int kG2Max = 90;             // tiles per axis (upper bound; the actua
                                        // the two sorts below fit 13 (+ 2) bits = two radix passes each (512 per axis, rounds 1-5: 19 / 21 bits = three),
                                        // and the per-tile tables and the chunk launch shrink from 262 k to 8 k entries.  BASELINE configs[4] picks 32 x 32.
 
-__device__ __forceinline__ int cell_of(float x, float o, float inv, int G)
-{
-    float f = floorf((x - o) * inv);
-    f = fminf(fmaxf(f, 0.f), (float)(G - 1));
-    return (int)f;
-}
-
 __global__ __launch_bounds__(256) void k_pix_bbox(const float *__restrict__ pix, int P, float *part)
 {
     __shared__ float sh[4][4];
-    float lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
+    BoxStats<2, 0> bs;
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) {
-        const float x = pix[p * 2], y = pix[p * 2 + 1];
-        if (fabsf(x) <= kBig && fabsf(y) <= kBig) {
-            lo[0] = fminf(lo[0], x); lo[1] = fminf(lo[1], y);
-            hi[0] = fmaxf(hi[0], x); hi[1] = fmaxf(hi[1], y);
-        }
+        const float xy[2] = {pix[p * 2], pix[p * 2 + 1]};
+        if (fabsf(xy[0]) <= kBig && fabsf(xy[1]) <= kBig) bs.add_point(xy);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            lo[k] = fminf(lo[k], __shfl_xor(lo[k], off));
-            hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off));
-        }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sh[w][0] = lo[0]; sh[w][1] = lo[1]; sh[w][2] = hi[0]; sh[w][3] = hi[1]; }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const int k = threadIdx.x;
-        float v = sh[0][k];
-        for (int i = 1; i < 4; ++i) v = k < 2 ? fminf(v, sh[i][k]) : fmaxf(v, sh[i][k]);
-        part[blockIdx.x * 4 + k] = v;
-    }
+    bs.block_store(sh, part + blockIdx.x * 4);
 }
 
 // mean image-space extent of the finite faces and the largest finite |corner depth| (per-block partials: sum of w, count,
@@ -115,20 +91,14 @@ __global__ __launch_bounds__(256) void k_face_stats(const float *__restrict__ xy
 __global__ __launch_bounds__(64) void k_pix_grid(const float *__restrict__ part, const float *__restrict__ fpart, Grid2 *g, unsigned *zAbsMax)
 {
     const int lane = threadIdx.x;
-    float lo[2] = {INFINITY, INFINITY}, hi[2] = {-INFINITY, -INFINITY};
+    BoxStats<2, 0> bs;
+    bs.load_reduce(part, kBoxBlocks);
     float sw = 0.f, cnt = 0.f, zm = 0.f;
     for (int i = lane; i < kBoxBlocks; i += 64) {                   // fixed order: the same tile grid on every run
-        lo[0] = fminf(lo[0], part[i * 4]); lo[1] = fminf(lo[1], part[i * 4 + 1]);
-        hi[0] = fmaxf(hi[0], part[i * 4 + 2]); hi[1] = fmaxf(hi[1], part[i * 4 + 3]);
         sw += fpart[i * 3]; cnt += fpart[i * 3 + 1]; zm = fmaxf(zm, fpart[i * 3 + 2]);
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            lo[k] = fminf(lo[k], __shfl_xor(lo[k], off));
-            hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off));
-        }
         sw += __shfl_xor(sw, off);
         cnt += __shfl_xor(cnt, off);
         zm = fmaxf(zm, __shfl_xor(zm, off));
@@ -136,9 +106,9 @@ __global__ __launch_bounds__(64) void k_pix_grid(const float *__restrict__ part,
     if (lane == 0) {
         *zAbsMax = __float_as_uint(zm);                             // scales the rounding margin of the NEAREST walk's stop test
         Grid2 r;
-        const bool okx = hi[0] >= lo[0], oky = hi[1] >= lo[1];
-        r.lox = okx ? lo[0] : 0.f; r.hix = okx ? hi[0] : 0.f;
-        r.loy = oky ? lo[1] : 0.f; r.hiy = oky ? hi[1] : 0.f;
+        const bool okx = bs.hi[0] >= bs.lo[0], oky = bs.hi[1] >= bs.lo[1];
+        r.lox = okx ? bs.lo[0] : 0.f; r.hix = okx ? bs.hi[0] : 0.f;
+        r.loy = oky ? bs.lo[1] : 0.f; r.hiy = oky ? bs.hi[1] : 0.f;
         r.ox = r.lox; r.oy = r.loy;
         const float ex = r.hix - r.lox, ey = r.hiy - r.loy;
         const float meanw = cnt > 0.f ? sw / cnt : 0.f;
@@ -203,8 +173,8 @@ __device__ __forceinline__ FaceBox face_box(const float *__restrict__ xy, int f,
     const float mg = w * kMargin;
     const float elx = lox - mg, ehx = hix + mg, ely = loy - mg, ehy = hiy + mg;
     if (ehx < g.lox || elx > g.hix || ehy < g.loy || ely > g.hiy) { r.mode = 0; return r; }
-    r.tx0 = cell_of(elx, g.ox, g.ix, g.gx); r.tx1 = cell_of(ehx, g.ox, g.ix, g.gx);
-    r.ty0 = cell_of(ely, g.oy, g.iy, g.gy); r.ty1 = cell_of(ehy, g.oy, g.iy, g.gy);
+    r.tx0 = grid_cell(elx, g.ox, g.ix, g.gx); r.tx1 = grid_cell(ehx, g.ox, g.ix, g.gx);
+    r.ty0 = grid_cell(ely, g.oy, g.iy, g.gy); r.ty1 = grid_cell(ehy, g.oy, g.iy, g.gy);
     r.mode = ((r.tx1 - r.tx0 + 1) * (r.ty1 - r.ty0 + 1) <= kMaxTiles) ? 1 : 2;
     r.elx = elx; r.ehx = ehx; r.ely = ely; r.ehy = ehy;
     return r;
@@ -310,7 +280,7 @@ __global__ __launch_bounds__(256) void k_pix_keys(const float *__restrict__ pix,
     const bool tame = fabsf(px) <= kBig && fabsf(py) <= kBig;
     unsigned k = (unsigned)(kG2Max * kG2Max) * 4u;                   // the pseudo-tile nTilesCap of the NaN / Inf / huge pixels
     if (tame) {
-        const int tx = cell_of(px, g.ox, g.ix, g.gx), ty = cell_of(py, g.oy, g.iy, g.gy);
+        const int tx = grid_cell(px, g.ox, g.ix, g.gx), ty = grid_cell(py, g.oy, g.iy, g.gy);
         // two more key bits: the quadrant of the tile, so that 64 consecutive pixels form a compact patch
         const float fx = (px - g.ox) * g.ix - (float)tx, fy = (py - g.oy) * g.iy - (float)ty;
         k = (unsigned)(ty * g.gx + tx) * 4u + (fy >= 0.5f ? 2u : 0u) + (fx >= 0.5f ? 1u : 0u);

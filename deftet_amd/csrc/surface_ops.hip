@@ -18,6 +18,7 @@
 
 #include "common.hpp"
 
+#include "grid_setup.hpp"
 #include "prims.hpp"
 
 namespace deftet {
@@ -176,32 +177,12 @@ __global__ __launch_bounds__(256) void k_nn_bbox(const float *__restrict__ pts, 
     SHAPE(part); SHAPE(cells); SHAPE(rep); SHAPE(nRep);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nc; i += gridDim.x * blockDim.x) { cells[i] = 0; rep[i] = -1; }
     if (blockIdx.x == 0 && threadIdx.x < 4) nRep[threadIdx.x] = 0;
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    BoxStats<3, 0> bs;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += gridDim.x * blockDim.x) {
-        const float x = pts[i * 3], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
-        if (fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY) {     // finite (NaN fails)
-            lo[0] = fminf(lo[0], x); lo[1] = fminf(lo[1], y); lo[2] = fminf(lo[2], z);
-            hi[0] = fmaxf(hi[0], x); hi[1] = fmaxf(hi[1], y); hi[2] = fmaxf(hi[2], z);
-        }
+        const float p[3] = {pts[i * 3], pts[i * 3 + 1], pts[i * 3 + 2]};
+        if (fabsf(p[0]) < INFINITY && fabsf(p[1]) < INFINITY && fabsf(p[2]) < INFINITY) bs.add_point(p);     // finite (NaN fails)
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = fminf(lo[k], __shfl_xor(lo[k], off));
-            hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off));
-        }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { sh[w][k] = lo[k]; sh[w][3 + k] = hi[k]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int k = threadIdx.x;
-        float v = sh[0][k];
-        for (int i = 1; i < 4; ++i) v = k < 3 ? fminf(v, sh[i][k]) : fmaxf(v, sh[i][k]);
-        part[blockIdx.x * 6 + k] = v;
-    }
+    bs.block_store(sh, part + blockIdx.x * 6);
 }
 
 __global__ __launch_bounds__(64) void k_nn_grid(const float *__restrict__ part, int G, NNGrid *g, size_t slice)
@@ -209,24 +190,17 @@ __global__ __launch_bounds__(64) void k_nn_grid(const float *__restrict__ part, 
     const int sb = blockIdx.x;
     SHAPE(part); SHAPE(g);
     const int lane = threadIdx.x;
-    float lo[3], hi[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { lo[k] = part[lane * 6 + k]; hi[k] = part[lane * 6 + 3 + k]; }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = fminf(lo[k], __shfl_xor(lo[k], off));
-            hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off));
-        }
+    BoxStats<3, 0> bs;
+    bs.load(part + lane * 6);
+    bs.wave_reduce();
     if (lane == 0) {
         NNGrid r;
         r.G = G;
         r.Gc = (G + kNNCoarse - 1) / kNNCoarse;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const bool ok = hi[k] >= lo[k];
-            const float l = ok ? lo[k] : 0.f, h = ok ? hi[k] : 0.f;
+            const bool ok = bs.hi[k] >= bs.lo[k];
+            const float l = ok ? bs.lo[k] : 0.f, h = ok ? bs.hi[k] : 0.f;
             const float ext = h - l;
             r.o[k] = l;
             const bool flat = !(ext > 1e-30f) || !(ext < 1e30f);
@@ -237,13 +211,6 @@ __global__ __launch_bounds__(64) void k_nn_grid(const float *__restrict__ part, 
         }
         *g = r;
     }
-}
-
-__device__ __forceinline__ int nn_cell(float x, float o, float inv, int G)
-{
-    float f = floorf((x - o) * inv);
-    f = fminf(fmaxf(f, 0.f), (float)(G - 1));
-    return (int)f;
 }
 
 __global__ __launch_bounds__(256) void k_nn_bin(const float *__restrict__ pts, int M, const NNGrid *__restrict__ gp, int *cells,
@@ -260,7 +227,7 @@ __global__ __launch_bounds__(256) void k_nn_bin(const float *__restrict__ pts, i
     int2 r = make_int2(-1, 0);
     int cx = 0, cy = 0, cz = 0;
     if (live && fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY) {
-        cx = nn_cell(x, g.o[0], g.inv[0], g.G); cy = nn_cell(y, g.o[1], g.inv[1], g.G); cz = nn_cell(z, g.o[2], g.inv[2], g.G);
+        cx = grid_cell(x, g.o[0], g.inv[0], g.G); cy = grid_cell(y, g.o[1], g.inv[1], g.G); cz = grid_cell(z, g.o[2], g.inv[2], g.G);
         r.x = (cz * g.G + cy) * g.G + cx;
     }
     r.y = run_atomic_rank(cells, r.x);
@@ -417,8 +384,8 @@ __global__ __launch_bounds__(256) void k_nn_query(const float *__restrict__ quer
     int lo[3], hi[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        lo[k] = nn_cell(qq[k] - R - g.slack[k], g.o[k], g.inv[k], G);
-        hi[k] = nn_cell(qq[k] + R + g.slack[k], g.o[k], g.inv[k], G);
+        lo[k] = grid_cell(qq[k] - R - g.slack[k], g.o[k], g.inv[k], G);
+        hi[k] = grid_cell(qq[k] + R + g.slack[k], g.o[k], g.inv[k], G);
     }
     // distance from q to the slab of cell layer c on axis k (0 inside; a flat axis is one unbounded slab)
     auto slab = [&](int k, int c) -> float {
@@ -442,7 +409,7 @@ __global__ __launch_bounds__(256) void k_nn_query(const float *__restrict__ quer
             const float rem = R2 - dy * dy - dz * dz;
             if (rem < 0.f) continue;                                 // the whole row is farther than R
             const float rx = sqrtf(rem) * 1.00001f;
-            const int x0 = nn_cell(qx - rx - g.slack[0], g.o[0], g.inv[0], G), x1 = nn_cell(qx + rx + g.slack[0], g.o[0], g.inv[0], G);
+            const int x0 = grid_cell(qx - rx - g.slack[0], g.o[0], g.inv[0], G), x1 = grid_cell(qx + rx + g.slack[0], g.o[0], g.inv[0], G);
             const int row = (cz * G + cy) * G;
             const int s = start[row + x0], e = start[row + x1 + 1];
             for (int j = s; j < e; j += 4) {                         // four gathers in flight per lane
@@ -615,8 +582,8 @@ __global__ __launch_bounds__(kFarWaves * 64) void k_nn_far_bound(const float *__
         const bool have = L.best < 1e20f;
         const int bi = have ? L.besti : 0;
         const float bx = pts[bi * 3], by = pts[bi * 3 + 1], bz = pts[bi * 3 + 2];
-        const int mine = ((nn_cell(bz, g.o[2], g.inv[2], G) / kNNCoarse) * Gc + nn_cell(by, g.o[1], g.inv[1], G) / kNNCoarse) * Gc +
-                         nn_cell(bx, g.o[0], g.inv[0], G) / kNNCoarse;
+        const int mine = ((grid_cell(bz, g.o[2], g.inv[2], G) / kNNCoarse) * Gc + grid_cell(by, g.o[1], g.inv[1], G) / kNNCoarse) * Gc +
+                         grid_cell(bx, g.o[0], g.inv[0], G) / kNNCoarse;
         unsigned long long todo = __ballot(have);
         for (int round = 0; round < 4 && todo; ++round) {
             const int c = __builtin_amdgcn_readlane(mine, __ffsll((long long)todo) - 1);
@@ -691,8 +658,8 @@ __global__ __launch_bounds__(kFarWaves * 64) void k_nn_far_rows(const float *__r
                     s = rs[k]; e = rs[k + 1];
                     if (e - s > 3 * kNNBatch) {                     // long row: only the x-range the lanes can reach
                         const float rx = sqrtf(fmaxf(rem, 0.f)) * 1.00001f;
-                        int x0 = need ? nn_cell(L.qx - rx - g.slack[0], g.o[0], g.inv[0], G) : G - 1;
-                        int x1 = need ? nn_cell(L.qx + rx + g.slack[0], g.o[0], g.inv[0], G) : 0;
+                        int x0 = need ? grid_cell(L.qx - rx - g.slack[0], g.o[0], g.inv[0], G) : G - 1;
+                        int x1 = need ? grid_cell(L.qx + rx + g.slack[0], g.o[0], g.inv[0], G) : 0;
                         if (need && !(rx < INFINITY)) { x0 = 0; x1 = G - 1; }
 #pragma unroll
                         for (int off = 32; off > 0; off >>= 1) {
@@ -1323,42 +1290,19 @@ __global__ __launch_bounds__(256) void k_tri_face_stats(const float *__restrict_
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nRepCells; i += gridDim.x * blockDim.x) rep[i] = -1;
     if (blockIdx.x == 0 && threadIdx.x < 8) counters[threadIdx.x] = 0;
     const int nf = (int)nfb[0];
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, sw = 0.f, cnt = 0.f;
+    BoxStats<3, 2> bs;                                              // sums: largest box extent of the regular faces, their number
     for (int f = blockIdx.x * blockDim.x + threadIdx.x; f < nf; f += gridDim.x * blockDim.x) {
         float fc[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) fc[k] = face[(size_t)f * 9 + k];
-        float a, b, c, d, e, g;
-        if (face_regular(fc, a, b, c, d, e, g)) {
-            lo[0] = fminf(lo[0], a); lo[1] = fminf(lo[1], b); lo[2] = fminf(lo[2], c);
-            hi[0] = fmaxf(hi[0], d); hi[1] = fmaxf(hi[1], e); hi[2] = fmaxf(hi[2], g);
-            sw += fmaxf(fmaxf(d - a, e - b), g - c);
-            cnt += 1.f;
+        float l[3], h[3];
+        if (face_regular(fc, l[0], l[1], l[2], h[0], h[1], h[2])) {
+            bs.add_box(l, h);
+            bs.add_sum(0, fmaxf(fmaxf(h[0] - l[0], h[1] - l[1]), h[2] - l[2]));
+            bs.add_sum(1, 1.f);
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = fminf(lo[k], __shfl_xor(lo[k], off));
-            hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off));
-        }
-        sw += __shfl_xor(sw, off);
-        cnt += __shfl_xor(cnt, off);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { sh[w][k] = lo[k]; sh[w][3 + k] = hi[k]; }
-        sh[w][6] = sw; sh[w][7] = cnt;
-    }
-    __syncthreads();
-    if (threadIdx.x < 8) {
-        const int k = threadIdx.x;
-        float v = sh[0][k];
-        for (int i = 1; i < 4; ++i) v = k < 3 ? fminf(v, sh[i][k]) : (k < 6 ? fmaxf(v, sh[i][k]) : v + sh[i][k]);
-        part[blockIdx.x * 8 + k] = v;
-    }
+    bs.block_store(sh, part + blockIdx.x * 8);
 }
 
 __global__ __launch_bounds__(64) void k_tri_grid(const float *__restrict__ part, TGrid *gp, size_t slice)
@@ -1366,27 +1310,18 @@ __global__ __launch_bounds__(64) void k_tri_grid(const float *__restrict__ part,
     const int sb = blockIdx.x;
     SHAPE(part); SHAPE(gp);
     const int lane = threadIdx.x;
-    float lo[3], hi[3], sw = part[lane * 8 + 6], cnt = part[lane * 8 + 7];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { lo[k] = part[lane * 8 + k]; hi[k] = part[lane * 8 + 3 + k]; }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = fminf(lo[k], __shfl_xor(lo[k], off));
-            hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off));
-        }
-        sw += __shfl_xor(sw, off);
-        cnt += __shfl_xor(cnt, off);
-    }
+    BoxStats<3, 2> bs;
+    bs.load(part + lane * 8);
+    bs.wave_reduce();
     if (lane == 0) {
         TGrid r;
+        const float sw = bs.sum[0], cnt = bs.sum[1];
         const float meanw = cnt > 0.f ? sw / cnt : 0.f;
         float diag2 = 0.f;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const bool ok = hi[k] >= lo[k];
-            const float l = ok ? lo[k] : 0.f, h = ok ? hi[k] : 0.f, ext = h - l;
+            const bool ok = bs.hi[k] >= bs.lo[k];
+            const float l = ok ? bs.lo[k] : 0.f, h = ok ? bs.hi[k] : 0.f, ext = h - l;
             float n = (meanw > 0.f && ext > 0.f) ? ceilf(ext / (meanw * kTCellScale)) : 1.f;
             n = fminf(fmaxf(n, 1.f), (float)kTGMax);
             r.g[k] = (int)n;
@@ -1399,13 +1334,6 @@ __global__ __launch_bounds__(64) void k_tri_grid(const float *__restrict__ part,
         r.abs_slack = 1e-8f * diag2;                               // see the bound in k_tri_query_coop
         *gp = r;
     }
-}
-
-__device__ __forceinline__ int t_cell(float x, float o, float inv, int G)
-{
-    float f = floorf((x - o) * inv);
-    f = fminf(fmaxf(f, 0.f), (float)(G - 1));
-    return (int)f;
 }
 
 // mode 0: count cells / append to the wide list; mode 1: fill the cell lists
@@ -1430,9 +1358,9 @@ __global__ __launch_bounds__(256) void k_tri_face_bin(const float *__restrict__ 
     bool tiles = face_regular(fc, lox, loy, loz, hix, hiy, hiz);
     int x0 = 0, x1 = 0, y0 = 0, y1 = 0, z0 = 0, z1 = 0;
     if (tiles) {
-        x0 = t_cell(lox - g.slack[0], g.o[0], g.inv[0], g.g[0]); x1 = t_cell(hix + g.slack[0], g.o[0], g.inv[0], g.g[0]);
-        y0 = t_cell(loy - g.slack[1], g.o[1], g.inv[1], g.g[1]); y1 = t_cell(hiy + g.slack[1], g.o[1], g.inv[1], g.g[1]);
-        z0 = t_cell(loz - g.slack[2], g.o[2], g.inv[2], g.g[2]); z1 = t_cell(hiz + g.slack[2], g.o[2], g.inv[2], g.g[2]);
+        x0 = grid_cell(lox - g.slack[0], g.o[0], g.inv[0], g.g[0]); x1 = grid_cell(hix + g.slack[0], g.o[0], g.inv[0], g.g[0]);
+        y0 = grid_cell(loy - g.slack[1], g.o[1], g.inv[1], g.g[1]); y1 = grid_cell(hiy + g.slack[1], g.o[1], g.inv[1], g.g[1]);
+        z0 = grid_cell(loz - g.slack[2], g.o[2], g.inv[2], g.g[2]); z1 = grid_cell(hiz + g.slack[2], g.o[2], g.inv[2], g.g[2]);
         tiles = (x1 - x0 + 1) * (y1 - y0 + 1) * (z1 - z0 + 1) <= kTMaxCells;
     }
     if (!tiles) {
@@ -1497,11 +1425,7 @@ __global__ __launch_bounds__(256) void k_tri_point_keys(const float *__restrict_
     const TGrid g = *gp;
     int c[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        float f = floorf((pts[(live ? q : 0) * 3 + k] - g.o[k]) * g.inv[k]);
-        f = fminf(fmaxf(f, 0.f), (float)(g.g[k] - 1));               // NaN -> 0
-        c[k] = (int)f;
-    }
+    for (int k = 0; k < 3; ++k) c[k] = grid_cell(pts[(live ? q : 0) * 3 + k], g.o[k], g.inv[k], g.g[k]);
     const int cell = live ? (c[2] * kTGMax + c[1]) * kTGMax + c[0] : -1;   // 18 bits: z, y, x
     const int rank = run_atomic_rank(pcount, cell);                    // one atomic per run of lanes in the same cell
     if (live) prank[q] = make_int2(cell, rank);
@@ -2140,8 +2064,8 @@ __global__ __launch_bounds__(kTriWaves * 64) void k_tri_far_rows(const float *__
         const bool need = !(rem < 0.f);                             // NaN points need everything (and select nothing)
         if (!__any(need)) continue;
         const float rx = sqrtf(fmaxf(rem, 0.f)) * 1.00001f;
-        int x0 = need ? t_cell(L.p[0] - rx - g.slack[0], g.o[0], g.inv[0], g.g[0]) : g.g[0] - 1;
-        int x1 = need ? t_cell(L.p[0] + rx + g.slack[0], g.o[0], g.inv[0], g.g[0]) : 0;
+        int x0 = need ? grid_cell(L.p[0] - rx - g.slack[0], g.o[0], g.inv[0], g.g[0]) : g.g[0] - 1;
+        int x1 = need ? grid_cell(L.p[0] + rx + g.slack[0], g.o[0], g.inv[0], g.g[0]) : 0;
         if (need && !(rx < INFINITY)) { x0 = 0; x1 = g.g[0] - 1; }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) {

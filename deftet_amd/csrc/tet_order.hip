@@ -18,6 +18,7 @@
 // the column changes or z jumps — so that the caller can keep the identity when the list is already coherent (no indirection,
 // coalesced 48-byte loads).
 #pragma clang fp contract(off)
+#include "grid_setup.hpp"
 #include "prims.hpp"
 
 #include "common.hpp"
@@ -27,7 +28,7 @@ namespace order {
 
 constexpr int kStatBlocks = 128;
 constexpr int kFine = 1024;            // histogram bins per axis the column boundaries are chosen on
-constexpr int kStatWords = 10;         // lo xyz, hi xyz of the lower box corners of the finite tets; sum of the box extents xyz; count
+constexpr int kStatWords = BoxStats<3, 4>::kWords;   // lo xyz, hi xyz of the lower box corners of the finite tets; sum of the box extents xyz; count
 constexpr int kColBits = 10, kZBits = 10;
 constexpr unsigned kBadKey = (1u << (2 * kColBits + kZBits)) - 1u;      // non-finite tets: behind everything else
 constexpr int kZJump = 1 << (kZBits - 2);                                // a z step of more than a quarter of the range breaks a run
@@ -53,44 +54,20 @@ __device__ __forceinline__ bool centroid_of(const float *__restrict__ tet, int t
 __global__ __launch_bounds__(256) void k_order_stats(const float *__restrict__ tet, int T, float *part)
 {
     __shared__ float sh[4][kStatWords];
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, se[3] = {0.f, 0.f, 0.f}, n = 0.f;
+    BoxStats<3, 4> bs;
     for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < T; t += gridDim.x * blockDim.x) {
         float c[3], e[3], m[3];
         if (!centroid_of(tet, t, c, e, m)) continue;
+        bs.add_point(m);                                               // range of the lower box corners
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = fminf(lo[k], m[k]);                                 // range of the lower box corners
-            hi[k] = fmaxf(hi[k], m[k]);
-            se[k] += e[k];
-        }
-        n += 1.f;
+        for (int k = 0; k < 3; ++k) bs.add_sum(k, e[k]);
+        bs.add_sum(3, 1.f);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            lo[k] = fminf(lo[k], __shfl_xor(lo[k], off));
-            hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off));
-            se[k] += __shfl_xor(se[k], off);
-        }
-        n += __shfl_xor(n, off);
-    }
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { sh[w][k] = lo[k]; sh[w][3 + k] = hi[k]; sh[w][6 + k] = se[k]; }
-        sh[w][9] = n;
-    }
-    __syncthreads();
-    if (threadIdx.x < kStatWords) {
-        const int k = threadIdx.x;
-        float v = sh[0][k];
-        for (int i = 1; i < 4; ++i) v = k < 3 ? fminf(v, sh[i][k]) : k < 6 ? fmaxf(v, sh[i][k]) : v + sh[i][k];
-        part[blockIdx.x * kStatWords + k] = v;
-    }
+    bs.block_store(sh, part + blockIdx.x * kStatWords);
 }
 
-// statistics of the whole list from the per-block partials (every thread of a block gets them)
+// statistics of the whole list from the per-block partials (every thread of a block gets them).  The kStatBlocks partials are
+// added one after the other, not by BoxStats::load_reduce: the order of the sums is part of the result.
 __device__ __forceinline__ void reduce_stats(const float *__restrict__ part, float *st /* shared, kStatWords */)
 {
     if (threadIdx.x < kStatWords) {
