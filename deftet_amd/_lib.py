@@ -123,6 +123,7 @@ SIGNATURES = {
     "deftet_vertex_laplacian_workspace_bytes": (_sz, [_i, _i]),
     "deftet_vertex_laplacian_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "deftet_vertex_laplacian_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "deftet_vertex_aggregate_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "deftet_point_mesh_distance_workspace_bytes": (_sz, [_i, _i, _i]),
     "deftet_point_mesh_distance_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "deftet_point_mesh_distance_scan_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -1559,6 +1559,51 @@ def vertex_laplacian(x, adjacency, reduction="shape"):
     return _VertexLaplacian.apply(_f32c(x), adjacency, _VLAP_REDUCTIONS[reduction])
 
 
+# --------------------------------------------------------------------------------- vertex aggregation
+def _vertex_aggregate(x, offsets, idx, vals, nnz):
+    """out = M·x for the CSR (offsets, idx, vals): the one library call both directions make"""
+    lib = _lib.load()
+    B, V, C = x.shape
+    out = torch.empty(B, V, C, device=x.device, dtype=torch.float32)
+    with _lib.on_device(x.device):
+        _lib.check(lib.deftet_vertex_aggregate_f32(_lib.ptr(x), _lib.ptr(offsets), _lib.ptr(idx), _lib.ptr(vals), B, V, C, nnz,
+                                                   _lib.ptr(out), _lib.current_stream(x.device)), "deftet_vertex_aggregate_f32")
+    return out
+
+
+class _VertexAggregate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, adjacency):
+        ctx.set_materialize_grads(False)
+        ctx.adj = adjacency
+        return _vertex_aggregate(x, adjacency.offsets, adjacency.cols, adjacency.vals, adjacency.nnz)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if grad_out is None or not ctx.needs_input_grad[0]:
+            return None, None
+        adj = ctx.adj
+        return _vertex_aggregate(_f32c(grad_out), adj.t_offsets, adj.t_rows, adj.t_vals, adj.nnz), None
+
+
+def vertex_aggregate(x, adjacency):
+    """M·x over a VertexAdjacency M with values (from_sparse, from_tets), x f32 [B,V,C] with any C >= 1 (differentiable w.r.t.
+    x; M is a constant): out[b,i,c] = Σ_k v_ik x[b,k,c], contiguous f32 [B,V,C] — sparse_batch_matmul of the GCN decoder
+    (layers/gcn_decoder.py:55-56).  Every channel is one fmaf chain in CSR order: bit-reproducible, and independent of C.
+    No host synchronisation: the call can be captured in a graph."""
+    _lib.require_gpu(x)
+    if not isinstance(adjacency, VertexAdjacency):
+        raise TypeError("vertex_aggregate: a hip_ops.VertexAdjacency expected, got %s" % type(adjacency).__name__)
+    if adjacency.weighting != VLAP_VALUES:
+        raise ValueError("vertex_aggregate: a VLAP_VALUES adjacency (from_sparse, from_tets) expected; a VLAP_ROW_DIVISOR one "
+                         "(from_table) is not supported")
+    if x.dim() != 3 or x.shape[1] != adjacency.n_vertex or x.shape[2] < 1:
+        raise RuntimeError("vertex_aggregate: x [B,%d,C] with C >= 1 expected, got %s" % (adjacency.n_vertex, tuple(x.shape)))
+    if x.device != adjacency.device:
+        raise RuntimeError("vertex_aggregate: x is on %s, the adjacency on %s" % (x.device, adjacency.device))
+    return _VertexAggregate.apply(_f32c(x), adjacency)
+
+
 # --------------------------------------------------------------------------------- A7 / A11
 def boundary_index(tet_face_fx3, tet_idx_fx2, occ_bxn, mode=1):
     """list of B int64 [Fb_i,3] tensors — DefTet.get_boundary_index (mode 1) /

@@ -26,6 +26,9 @@ diff_render/diftet_6_subdiv/3_model on sys.path and imports it by that name): th
 With `point_voxel=True` also `layers.pv_module.functional.backend` (a module whose `_backend` carries the extension's twelve
 names on this library's kernels, so importing it compiles nothing) and `layers.pv_module.functional.devoxelization`
 (`deftet_amd.pointvoxel`); the reference's own functional/*.py, voxelization.py and pvconv.py run unchanged on top.
+With `graph_conv=True` also `utils.matrix_utils` (`deftet_amd.utils.matrix_utils`): an unchanged layers/gcn_decoder.py then runs
+the sparse product of every GraphConv (`sparse_batch_matmul`, gcn_decoder.py:55-56) on `hip_ops.vertex_aggregate`, with the
+adjacency converted once per tensor and device; `convert_torch_sparse`, `cross_dot_torch`, `det_m` and `MySparse` come with it.
 Nothing here touches a CPU fallback: every replaced entry point raises on non-GPU tensors.
 """
 import importlib
@@ -89,7 +92,7 @@ def point_voxel_modules():
     return {"layers.pv_module.functional.backend": backend, "layers.pv_module.functional.devoxelization": pointvoxel}
 
 
-def install(kaolin=None, deftet_module=False, stub_cv2=True, render_model=False, point_voxel=False):
+def install(kaolin=None, deftet_module=False, stub_cv2=True, render_model=False, point_voxel=False, graph_conv=False):
     """Register the overlay in sys.modules; returns the list of names it registered.
     kaolin: True = always shim, False = never, None = shim only if `import kaolin` would fail."""
     done = []
@@ -106,6 +109,9 @@ def install(kaolin=None, deftet_module=False, stub_cv2=True, render_model=False,
         for name, mod in point_voxel_modules().items():
             sys.modules[name] = mod
             done.append(name)
+    if graph_conv:
+        sys.modules["utils.matrix_utils"] = importlib.import_module("deftet_amd.utils.matrix_utils")
+        done.append("utils.matrix_utils")
     if kaolin is None:
         kaolin = "kaolin" not in sys.modules and importlib.util.find_spec("kaolin") is None
     if kaolin:

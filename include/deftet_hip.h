@@ -42,7 +42,10 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
-/* 280: rendering straight from the vertices — deftet_face_vertex_csr_i32 (+ workspace size), deftet_project_vertices_fwd_f32 /
+/* 300: the wide-channel vertex aggregation — deftet_vertex_aggregate_f32 (vertex_aggregate.hip).
+ * 290: the point-voxel operators — deftet_avg_voxelize_fwd_f32 / _bwd_f32, deftet_voxel_sample_fwd_f32, deftet_voxel_cells_f32 /
+ *      _from_inds_i32, deftet_voxel_sample_bwd_vol_f32 / _bwd_pos_f32 and their workspace size (pointvoxel.hip).
+ * 280: rendering straight from the vertices — deftet_face_vertex_csr_i32 (+ workspace size), deftet_project_vertices_fwd_f32 /
  *      _bwd_f32, deftet_face_gather_fwd_f32 / _bwd_f32 (render_vertices.hip).
  * 270: surface extraction from a per-tet occupancy — deftet_tet_face_neighbours_i64, deftet_surface_extract_count_f32 / _fill_f32,
  *      deftet_surface_weld_f32 and their workspace sizes.
@@ -671,6 +674,19 @@ int deftet_vertex_laplacian_fwd_f32(const float *x, const int32_t *offsets, cons
 int deftet_vertex_laplacian_bwd_f32(const float *r, const float *grad_out, const int32_t *t_offsets, const int32_t *t_rows,
                                     const float *t_vals, const float *row_weights, int weighting, int reduction, int n_batch,
                                     int n_vertex, int n_chan, int nnz, float *grad_x, void *stream);
+
+/* Vertex aggregation (300): out = M·x over the same CSR, for wide rows — the sparse product of the GCN position decoder
+ * (GraphConv.forward, layers/gcn_decoder.py:55-56, through sparse_batch_matmul, utils/matrix_utils.py:22-33).
+ *
+ * deftet_vertex_aggregate_f32: x f32 [B,V,C], any C >= 1; out f32 [B,V,C] (overwritten, must not alias x),
+ *   out[b,i,c] = Σ_k vals[k] · x[b, idx[k], c] over k in [offsets[i], offsets[i+1]).  One entry point serves both directions:
+ *   the forward passes (offsets, cols, vals), the backward the transposed CSR (t_offsets, t_rows, t_vals) and the upstream
+ *   gradient.  Every channel starts at 0.f and takes one fmaf per entry in CSR order, whatever C is: the vector path
+ *   (C % 4 == 0 and x, out 16-byte aligned) and the scalar path give the same bits, and a channel's result does not depend
+ *   on its neighbours.  No atomics, no workspace, no host synchronisation; nothing is launched when B·V == 0.  B <= 65535.
+ *   The CSR must come from deftet_vertex_adjacency_csr_i32 with values and *bad_flag == 0: the kernel does not re-check it. */
+int deftet_vertex_aggregate_f32(const float *x, const int32_t *offsets, const int32_t *idx, const float *vals, int n_batch,
+                                int n_vertex, int n_channel, int nnz, float *out, void *stream);
 
 /* Evaluation metrics (260): what eval.py:237-260 and utils/point_cloud_utils.py compute with Kaolin, forward only.
  *
