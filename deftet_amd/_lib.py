@@ -152,6 +152,19 @@ SIGNATURES = {
     "deftet_voxel_cells_from_inds_i32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     "deftet_voxel_sample_bwd_vol_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "deftet_voxel_sample_bwd_pos_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "deftet_mesh_voxelize_workspace_bytes": (_sz, [_i, _i]),
+    "deftet_mesh_voxelize_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "deftet_voxel_pack_u8": (_i, [_vp, _i, _i, _vp, _vp]),
+    "deftet_voxel_unpack_u8": (_i, [_vp, _i, _i, _vp, _vp]),
+    "deftet_extract_odms_u8": (_i, [_vp, _i, _i, _vp, _vp]),
+    "deftet_project_odms_i32": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "deftet_voxel_fill_workspace_bytes": (_sz, [_i, _i]),
+    "deftet_voxel_fill_b32": (_i, [_vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "deftet_voxel_surface_workspace_bytes": (_sz, [_i, _i]),
+    "deftet_voxel_surface_count_b32": (_i, [_vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "deftet_voxel_surface_fill_b32": (_i, [_vp, _i, _i, _ll, _ll, _vp, _vp, _vp, _sz, _vp]),
+    "deftet_face_edges_workspace_bytes": (_sz, [_i]),
+    "deftet_face_edges_i32": (_i, [_vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lock = threading.Lock()

@@ -1430,7 +1430,7 @@ class VertexAdjacency:
         self.device = offsets.device
 
     @classmethod
-    def _build(cls, rows, cols, values, n_vertex, order, weighting, row_weights=None):
+    def _build(cls, rows, cols, values, n_vertex, order, weighting, row_weights=None, checked=False):
         _lib.require_gpu(rows, cols, values, row_weights)
         lib = _lib.load()
         V, nnz, dev = int(n_vertex), int(rows.numel()), rows.device
@@ -1456,7 +1456,8 @@ class VertexAdjacency:
                                                            _lib.ptr(t_offsets), _lib.ptr(t_rows), _lib.ptr(t_vals), _lib.ptr(bad),
                                                            _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
                        "deftet_vertex_adjacency_csr_i32")
-        if int(bad.item()):                                 # (the one host sync: build time only)
+        # (the one host sync: build time only; `checked`: the caller's own kernel has already refused indices outside [0, V))
+        if not checked and int(bad.item()):
             raise RuntimeError("VertexAdjacency: vertex index out of range [0, %d)" % V)
         return cls(V, weighting, offsets, out_cols, vals, t_offsets, t_rows, t_vals, row_weights)
 
@@ -1503,6 +1504,20 @@ class VertexAdjacency:
         keep = t != -1                                      # the padding; anything else outside [0, P) raises in the build
         rows = torch.arange(P, device=t.device).unsqueeze(1).expand(P, m)[keep]      # (row-major: table order)
         return cls._build(rows, t[keep], None, P, _VADJ_ROW_INPUT, VLAP_ROW_DIVISOR, w)
+
+    @classmethod
+    def from_faces(cls, faces_fx3, n_vertex, normalize=True):
+        """The vertex adjacency of a triangle mesh (kal.ops.mesh.adjacency_matrix): the unique undirected edges (face_edges: a
+        radix sort of the edge keys, one entry per run) as ones, or D⁻¹A with `normalize` (1/deg rounded once from fp64, as
+        from_tets) — vertex_aggregate then gives the neighbour mean."""
+        V = int(n_vertex)
+        pairs = face_edges(faces_fx3, V)                                # sorted unique directed pairs, int32 [n,2]
+        rows, cols = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
+        vals = None
+        if normalize:
+            deg = torch.bincount(rows.long(), minlength=V).double()
+            vals = (1.0 / deg)[rows.long()].float()
+        return cls._build(rows, cols, vals, V, _VADJ_ROW_COL, VLAP_VALUES, checked=True)     # face_edges raised on a bad index
 
 
 class _VertexLaplacian(torch.autograd.Function):
@@ -2263,3 +2278,188 @@ def trilinear_devoxelize_bwd(grad_y, inds, wgts, r):
         raise RuntimeError("trilinear_devoxelize_bwd: grad_y %s and inds %s do not agree" % (tuple(grad_y.shape), tuple(inds.shape)))
     cells = _voxel_cells(lib, B, N, r, grad_y.device, inds=inds, wgts=wgts)
     return _bwd_vol(lib, grad_y, cells, C, 0, C).view(B, C, r ** 3)
+
+
+# --------------------------------------------------------------------------------- ground-truth preparation
+VOXELIZE_UNIT_BUDGET = 256                          # include/deftet_hip.h DEFTET_VOXELIZE_UNIT_BUDGET
+
+
+class VoxelBits:
+    """The bit-packed voxel grid the preparation stages hand to each other: `words` int32 [B,R,R,ceil(R/32)] on the GPU, bit
+    k % 32 of word k // 32 of row (i, j) is voxel (i, j, k); pad bits are zero.  `stats` (mesh_voxelize only): int32 [4] on the
+    GPU = (wave tasks, triangles split over several tasks, bad face index flag, 0)."""
+
+    def __init__(self, words, resolution, stats=None):
+        self.words, self.resolution, self.stats = words, int(resolution), stats
+        self.n_batch, self.device = int(words.shape[0]), words.device
+
+    def unpack(self):
+        """uint8 [B,R,R,R]"""
+        lib = _lib.load()
+        B, R, dev = self.n_batch, self.resolution, self.device
+        vox = torch.empty(B, R, R, R, device=dev, dtype=torch.uint8)
+        with _lib.on_device(dev):
+            _lib.check(lib.deftet_voxel_unpack_u8(_lib.ptr(self.words), B, R, _lib.ptr(vox), _lib.current_stream(dev)), "deftet_voxel_unpack_u8")
+        return vox
+
+
+def _vox_u8(vox, what):
+    """[B,R,R,R] of any dtype -> contiguous uint8 (non-zero = occupied)"""
+    _lib.require_gpu(vox)
+    if vox.dim() != 4 or not (vox.shape[1] == vox.shape[2] == vox.shape[3]) or vox.shape[0] < 1 or vox.shape[1] < 1:
+        raise RuntimeError("%s: a voxel grid [B,R,R,R] expected, got %s" % (what, tuple(vox.shape)))
+    if vox.dtype == torch.bool:
+        return vox.contiguous().view(torch.uint8)
+    return vox.contiguous() if vox.dtype == torch.uint8 else (vox != 0).view(torch.uint8)
+
+
+def voxel_pack(vox):
+    """VoxelBits of a grid [B,R,R,R] (non-zero = occupied)."""
+    v = _vox_u8(vox, "voxel_pack")
+    lib = _lib.load()
+    B, R, dev = int(v.shape[0]), int(v.shape[1]), v.device
+    words = torch.empty(B, R, R, (R + 31) // 32, device=dev, dtype=torch.int32)
+    with _lib.on_device(dev):
+        _lib.check(lib.deftet_voxel_pack_u8(_lib.ptr(v), B, R, _lib.ptr(words), _lib.current_stream(dev)), "deftet_voxel_pack_u8")
+    return VoxelBits(words, R)
+
+
+def _as_bits(v, what):
+    return v if isinstance(v, VoxelBits) else voxel_pack(v)
+
+
+def mesh_voxelize(vertices, faces, resolution, origin=None, scale=None, return_bits=False):
+    """Conservative surface voxelization (parity unpinned; the rule is this library's own, include/deftet_hip.h): vertices f32
+    [B,V,3], faces int [F,3], origin f32 [B,3] (None: the per-shape minimum), scale f32 [B] (None: the largest per-shape extent)
+    -> uint8 [B,R,R,R], or the VoxelBits (with .stats) when return_bits.  q = ((v - origin) / scale) * R in fp32; voxel (i,j,k) is
+    set iff a triangle overlaps the closed box [i,i+1] x [j,j+1] x [k,k+1] under the 13-axis separating-axis test in fp32.
+    No host synchronisation."""
+    _lib.require_gpu(vertices, faces, origin, scale)
+    lib = _lib.load()
+    v = _f32c(vertices)
+    f = faces.long().contiguous()
+    R = int(resolution)
+    if v.dim() != 3 or v.shape[2] != 3 or f.dim() != 2 or f.shape[1] != 3:
+        raise RuntimeError("mesh_voxelize: vertices [B,V,3] and faces [F,3] expected, got %s and %s" % (tuple(v.shape), tuple(f.shape)))
+    B, V, F, dev = int(v.shape[0]), int(v.shape[1]), int(f.shape[0]), v.device
+    if origin is not None:
+        origin = _f32c(origin)
+        if tuple(origin.shape) != (B, 3):
+            raise RuntimeError("mesh_voxelize: origin [%d,3] expected, got %s" % (B, tuple(origin.shape)))
+    if scale is not None:
+        scale = _f32c(scale).reshape(-1)
+        if scale.numel() != B:
+            raise RuntimeError("mesh_voxelize: scale [%d] expected" % B)
+    if R < 1:
+        raise _lib.DefTetHipError("mesh_voxelize: resolution=%d must be positive (DEFTET_EINVAL)" % R)
+    words = torch.empty(B, R, R, (R + 31) // 32, device=dev, dtype=torch.int32)
+    vox = None if return_bits else torch.empty(B, R, R, R, device=dev, dtype=torch.uint8)
+    stats = torch.empty(4, device=dev, dtype=torch.int32)
+    with _lib.on_device(dev):
+        ws = _lib.workspace(dev, lib.deftet_mesh_voxelize_workspace_bytes(B, F))
+        _lib.check(lib.deftet_mesh_voxelize_f32(_lib.ptr(v), _lib.ptr(f), _lib.ptr(origin), _lib.ptr(scale), B, V, F, R, _lib.ptr(words),
+                                                _lib.ptr(vox), _lib.ptr(stats), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
+                   "deftet_mesh_voxelize_f32")
+    return VoxelBits(words, R, stats) if return_bits else vox
+
+
+def extract_odms(vox):
+    """Orthographic depth maps int32 [B,6,R,R] of a grid [B,R,R,R] (or VoxelBits).  This library's own order: direction d scans
+    axis d // 2, ascending for even d, descending for odd d; a map is indexed by the two other axes in ascending axis order;
+    a depth is the number of empty voxels in front of the first occupied one, R for an empty ray."""
+    v = vox.unpack() if isinstance(vox, VoxelBits) else _vox_u8(vox, "extract_odms")
+    lib = _lib.load()
+    B, R, dev = int(v.shape[0]), int(v.shape[1]), v.device
+    odms = torch.empty(B, 6, R, R, device=dev, dtype=torch.int32)
+    with _lib.on_device(dev):
+        _lib.check(lib.deftet_extract_odms_u8(_lib.ptr(v), B, R, _lib.ptr(odms), _lib.current_stream(dev)), "deftet_extract_odms_u8")
+    return odms
+
+
+def project_odms(odms, voxelgrids=None, votes=1):
+    """uint8 [B,R,R,R]: start from a full grid (or `voxelgrids`); direction d carves the voxels in front of its depth; a voxel
+    stays iff fewer than `votes` directions carve it (extract_odms' direction order)."""
+    _lib.require_gpu(odms)
+    lib = _lib.load()
+    if odms.dim() != 4 or odms.shape[1] != 6 or odms.shape[2] != odms.shape[3] or odms.shape[0] < 1 or odms.shape[2] < 1:
+        raise RuntimeError("project_odms: odms [B,6,R,R] expected, got %s" % (tuple(odms.shape),))
+    o = odms.to(torch.int32).contiguous()
+    B, R, dev = int(o.shape[0]), int(o.shape[2]), o.device
+    vin = None
+    if voxelgrids is not None:
+        vin = _vox_u8(voxelgrids, "project_odms")
+        if tuple(vin.shape) != (B, R, R, R) or vin.device != dev:
+            raise RuntimeError("project_odms: voxelgrids [%d,%d,%d,%d] on %s expected" % (B, R, R, R, dev))
+    out = torch.empty(B, R, R, R, device=dev, dtype=torch.uint8)
+    with _lib.on_device(dev):
+        _lib.check(lib.deftet_project_odms_i32(_lib.ptr(o), _lib.ptr(vin), B, R, int(votes), _lib.ptr(out), _lib.current_stream(dev)),
+                   "deftet_project_odms_i32")
+    return out
+
+
+def voxel_fill(vox_or_bits):
+    """project_odms(extract_odms(v)) at votes = 1 in one launch sequence on the bit grid, without depth maps: a voxel stays iff on
+    every axis it lies between the first and the last occupied voxel of its ray.  A VoxelBits gives a VoxelBits, a grid a uint8 grid."""
+    bits = _as_bits(vox_or_bits, "voxel_fill")
+    lib = _lib.load()
+    B, R, dev = bits.n_batch, bits.resolution, bits.device
+    out = torch.empty_like(bits.words)
+    with _lib.on_device(dev):
+        ws = _lib.workspace(dev, lib.deftet_voxel_fill_workspace_bytes(B, R))
+        _lib.check(lib.deftet_voxel_fill_b32(_lib.ptr(bits.words), B, R, _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
+                   "deftet_voxel_fill_b32")
+    res = VoxelBits(out, R)
+    return res if isinstance(vox_or_bits, VoxelBits) else res.unpack()
+
+
+def voxel_surface_mesh(vox, iso_value=0.5):
+    """The faces of the occupied region (cuberille) of a grid [B,R,R,R] (occupied: vox > iso_value) or a VoxelBits:
+    (list of B verts f32 [V_b,3], list of B faces int64 [F_b,3]).  Every occupied voxel and each of its six directions (-i, +i,
+    -j, +j, -k, +k) whose neighbour is empty or outside emits two triangles with the normal pointing out.  Vertices are the
+    lattice corners in use, integer coordinates 0..R, numbered in ascending (i (R+1) + j) (R+1) + k: welded by construction.
+    Faces come in (voxel linear index, direction, triangle) order.  One read-back (the per-shape counts).
+    Kaolin runs marching cubes here (parity unpinned): on a binary grid both surfaces lie on the voxel faces and differ by the
+    chamfer at the corners; dataloader.py:55-60 rescales the result to the input's box, so offset and unit do not matter."""
+    if isinstance(vox, VoxelBits):
+        bits = vox
+    else:
+        _lib.require_gpu(vox)
+        bits = voxel_pack(vox > iso_value)
+    lib = _lib.load()
+    B, R, dev = bits.n_batch, bits.resolution, bits.device
+    offs = torch.empty(2 * (B + 1), device=dev, dtype=torch.int32)
+    with _lib.on_device(dev):
+        st = _lib.current_stream(dev)
+        wsb = lib.deftet_voxel_surface_workspace_bytes(B, R)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)            # the count pass leaves its tables here for the fill pass
+        _lib.check(lib.deftet_voxel_surface_count_b32(_lib.ptr(bits.words), B, R, _lib.ptr(offs), _lib.ptr(ws), wsb, st),
+                   "deftet_voxel_surface_count_b32")
+        o = offs.tolist()                                                # the one sync
+        fo, vo = o[:B + 1], o[B + 1:]
+        faces = torch.empty(fo[B], 3, device=dev, dtype=torch.int64)
+        verts = torch.empty(vo[B], 3, device=dev, dtype=torch.float32)
+        _lib.check(lib.deftet_voxel_surface_fill_b32(_lib.ptr(bits.words), B, R, fo[B], vo[B], _lib.ptr(verts) if vo[B] else None,
+                                                     _lib.ptr(faces) if fo[B] else None, _lib.ptr(ws), wsb, st),
+                   "deftet_voxel_surface_fill_b32")
+    return [verts[vo[b]:vo[b + 1]] for b in range(B)], [faces[fo[b]:fo[b + 1]] for b in range(B)]
+
+
+def face_edges(faces_fx3, n_vertex):
+    """The unique directed vertex pairs (a, b), a != b, of a triangle list, ascending by (a, b): int32 [n,2].  One read-back."""
+    _lib.require_gpu(faces_fx3)
+    lib = _lib.load()
+    f = faces_fx3.long().contiguous()
+    if f.dim() != 2 or f.shape[1] != 3:
+        raise RuntimeError("face_edges: faces [F,3] expected, got %s" % (tuple(f.shape),))
+    F, V, dev = int(f.shape[0]), int(n_vertex), f.device
+    pairs = torch.empty(6 * F, 2, device=dev, dtype=torch.int32)
+    n = torch.empty(2, device=dev, dtype=torch.int32)
+    with _lib.on_device(dev):
+        ws = _lib.workspace(dev, lib.deftet_face_edges_workspace_bytes(F))
+        _lib.check(lib.deftet_face_edges_i32(_lib.ptr(f), F, V, _lib.ptr(pairs) if F else None, _lib.ptr(n), _lib.ptr(ws), ws.numel(),
+                                             _lib.current_stream(dev)), "deftet_face_edges_i32")
+    count, bad = n.tolist()
+    if bad:
+        raise RuntimeError("face_edges: a face index is outside [0, %d)" % V)
+    return pairs[:count]
+

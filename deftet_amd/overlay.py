@@ -17,6 +17,8 @@ every import the hot path goes through:
                                                            importable, or with kaolin=True; parity unpinned)
     kaolin.ops.mesh.{sample_points,index_vertices_by_faces}, kaolin.metrics.pointcloud.sided_distance,
     kaolin.metrics.trianglemesh.point_to_mesh_distance    (the evaluation metrics, same condition)
+    kaolin.ops.conversions.{trianglemeshes_to_voxelgrids,voxelgrids_to_trianglemeshes}, kaolin.ops.voxelgrid.{extract_odms,
+    project_odms}, kaolin.ops.mesh.{adjacency_matrix,face_normals}   (ground-truth preparation, dataloader.py; same condition)
     cv2                                                    empty stub (imported, never used: check_condition.../utils.py:14)
 
 With `deftet_module=True` also `layers.DefTet.deftet` (the `DefTet` nn.Module built on the fused
@@ -58,7 +60,7 @@ def _kaolin_check_sign(verts, faces, points, hash_resolution=512):
 def kaolin_shim():
     """A module tree exposing the two Kaolin entry points the hot path calls
     (layers/DefTet/deftet.py:46, diff_render/diftet_6_subdiv/5_rendereq/deftetrneder.py:97-100) and the four the evaluation
-    metrics call."""
+    metrics call, and the six of the ground-truth preparation (dataloader.py:33-46, :80; deftet_amd.dataprep)."""
     from deftet_amd.render.deftet_sparse_render import deftet_sparse_render
     kal = types.ModuleType("kaolin")
     kal.__path__ = []                                  # a package, so `import kaolin.ops.mesh` resolves through sys.modules
@@ -77,8 +79,15 @@ def kaolin_shim():
     met_pc.sided_distance = metrics.sided_distance
     met_tm.point_to_mesh_distance = metrics.point_to_mesh_distance
     kal.metrics, met.pointcloud, met.trianglemesh = met, met_pc, met_tm
+    from deftet_amd import dataprep
+    ops_conv, ops_vox = types.ModuleType("kaolin.ops.conversions"), types.ModuleType("kaolin.ops.voxelgrid")
+    ops_conv.trianglemeshes_to_voxelgrids = dataprep.trianglemeshes_to_voxelgrids
+    ops_conv.voxelgrids_to_trianglemeshes = dataprep.voxelgrids_to_trianglemeshes
+    ops_vox.extract_odms, ops_vox.project_odms = dataprep.extract_odms, dataprep.project_odms
+    ops_mesh.adjacency_matrix, ops_mesh.face_normals = dataprep.adjacency_matrix, dataprep.face_normals
+    ops.conversions, ops.voxelgrid = ops_conv, ops_vox
     kal.__deftet_amd_shim__ = True
-    return {"kaolin": kal, "kaolin.ops": ops, "kaolin.render": render, "kaolin.ops.mesh": ops_mesh,
+    return {"kaolin": kal, "kaolin.ops.conversions": ops_conv, "kaolin.ops.voxelgrid": ops_vox, "kaolin.ops": ops, "kaolin.render": render, "kaolin.ops.mesh": ops_mesh,
             "kaolin.render.mesh": render_mesh, "kaolin.metrics": met, "kaolin.metrics.pointcloud": met_pc,
             "kaolin.metrics.trianglemesh": met_tm}
 

@@ -42,7 +42,10 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
-/* 300: the wide-channel vertex aggregation — deftet_vertex_aggregate_f32 (vertex_aggregate.hip).
+/* 310: ground-truth preparation — deftet_mesh_voxelize_f32, deftet_voxel_pack_u8 / _unpack_u8, deftet_extract_odms_u8,
+ *      deftet_project_odms_i32, deftet_voxel_fill_b32, deftet_voxel_surface_count_b32 / _fill_b32, deftet_face_edges_i32 and their
+ *      workspace sizes (dataprep.hip).
+ * 300: the wide-channel vertex aggregation — deftet_vertex_aggregate_f32 (vertex_aggregate.hip).
  * 290: the point-voxel operators — deftet_avg_voxelize_fwd_f32 / _bwd_f32, deftet_voxel_sample_fwd_f32, deftet_voxel_cells_f32 /
  *      _from_inds_i32, deftet_voxel_sample_bwd_vol_f32 / _bwd_pos_f32 and their workspace size (pointvoxel.hip).
  * 280: rendering straight from the vertices — deftet_face_vertex_csr_i32 (+ workspace size), deftet_project_vertices_fwd_f32 /
@@ -820,6 +823,65 @@ int deftet_voxel_sample_bwd_vol_f32(const float *grad_out, const int32_t *perm, 
 int deftet_voxel_sample_bwd_pos_f32(const float *vol, const float *pos, const float *grad_out, float *grad_pos, int n_batch, int n_channel,
                                     int resolution, int n_point, int channel_offset, int n_channel_total, int pos_mode, int accumulate,
                                     void *stream);
+
+/* Ground-truth preparation (310; dataprep.hip): what dataloader.py:24-61 (MakeSurfaceMesh) does with Kaolin's
+ * trianglemeshes_to_voxelgrids, extract_odms, project_odms, voxelgrids_to_trianglemeshes and adjacency_matrix.  PARITY UNPINNED:
+ * Kaolin's arithmetic cannot be read or run next to this library; the rules below are this library's own.  Forward only.
+ * Workspaces 256-byte aligned.  Every output is bit-reproducible (integer atomicOr / atomicAdd only, stable sorts, scans).
+ *
+ * The bit grid: uint32 [B,R,R,W], W = ceil(R / 32); bit k % 32 of word k / 32 of row (i, j) is voxel (i, j, k); pad bits are 0.
+ * 1 <= R <= 1024.
+ *
+ * deftet_mesh_voxelize_f32: verts f32 [B,V,3], faces i64 [F,3] shared by the batch, origin f32 [B,3] (NULL: the per-shape minimum
+ *   of the vertices), scale f32 [B] (NULL: the largest per-shape extent).  q = ((v - origin) / scale) * R in fp32.  Voxel (i,j,k),
+ *   the closed box [i,i+1] x [j,j+1] x [k,k+1], is set iff a triangle overlaps it under the 13-axis separating-axis test in fp32
+ *   (half size 0.5, corners relative to the voxel centre): the box axes (reject iff min > h or max < -h), the plane n = e0 x e1
+ *   (|n.a0| > h (|nx| + |ny| + |nz|)), the nine axes e_i x unit axis (min > r or max < -r, r by the same formula).  Candidates:
+ *   i + 1 >= min q_x and i <= max q_x (likewise y, z), clipped to the grid.  Degenerate triangles pass their zero axes; a triangle
+ *   with a non-finite corner is skipped; a face index outside [0,V) is skipped and sets stats[2].
+ *   bits (required, overwritten) receives the bit grid, vox u8 [B,R,R,R] (optional) its bytes.  stats (device int32 [4], required):
+ *   [0] wave tasks, [1] triangles whose candidate box took more than one task (DEFTET_VOXELIZE_UNIT_BUDGET word columns
+ *   (i, j, word of k) each), [2] bad index flag, [3] 0.  The task table is int32: n_batch * n_face * ceil(R R W /
+ *   DEFTET_VOXELIZE_UNIT_BUDGET), the most tasks the input could have, must be below 2^31 (DEFTET_EINVAL otherwise).
+ * deftet_voxel_pack_u8 / _unpack_u8: u8 [B,R,R,R] (non-zero = occupied) <-> the bit grid.
+ * deftet_extract_odms_u8: odms i32 [B,6,R,R].  Direction d scans axis d / 2, ascending for even d and descending for odd d; a map
+ *   is indexed by the two other axes in ascending axis order; the depth is the number of empty voxels in front of the first
+ *   occupied one, R for an empty ray.
+ * deftet_project_odms_i32: starts from a full grid (vox_in NULL) or from vox_in; direction d carves the voxels in front of its
+ *   depth; out u8 [B,R,R,R] = 1 iff the start voxel is set and fewer than `votes` (1..6) directions carve it.
+ * deftet_voxel_fill_b32: out = project(extract(bits)) at votes = 1 on the bit grid, no depth map stored (out must not alias bits).
+ * deftet_voxel_surface_count_b32 / _fill_b32: the faces of the occupied region.  Every set voxel and each of its directions
+ *   (0 / 1 towards -i / +i, 2 / 3 -j / +j, 4 / 5 -k / +k) whose neighbour is empty or outside emits two triangles wound so that the
+ *   normal points out of the voxel: with u, v the axes after the face's axis a (cyclic), corners p00, p10 = p00 + e_u, p11, p01 =
+ *   p00 + e_v, the triangles are (p00,p10,p11), (p00,p11,p01) towards +a and (p00,p01,p11), (p00,p11,p10) towards -a.  Rows in
+ *   (voxel linear index, direction, triangle) order; vertices are the lattice corners in use, coordinates 0..R as f32, numbered
+ *   per shape in ascending (i (R+1) + j) (R+1) + k.  count: offsets i32 [2 (B+1)] = first triangle of every shape and the total,
+ *   then first vertex of every shape and the total; it leaves the scanned tables in the workspace, which the fill pass of the
+ *   SAME workspace reads: faces i64 [cap_faces,3] (vertex ids local to the shape), verts f32 [cap_verts,3]; rows beyond a
+ *   capacity are not written.  The tables are int32: 6 n_batch R R (R + 1), the most triangles a batch could have, must be
+ *   below 2^31 (R <= 709 at n_batch = 1; DEFTET_EINVAL otherwise).
+ * deftet_face_edges_i32: the unique directed vertex pairs (a, b), a != b, of a triangle list, ascending by (a, b): pairs i32 [6 F,2]
+ *   (capacity), n_out i32 [2] = (number of pairs, bad index flag).  Radix sort of the keys a V + b, one entry per run. */
+#define DEFTET_VOXELIZE_UNIT_BUDGET 256
+size_t deftet_mesh_voxelize_workspace_bytes(int n_batch, int n_face);
+int deftet_mesh_voxelize_f32(const float *verts, const int64_t *faces, const float *origin, const float *scale, int n_batch, int n_vertex,
+                             int n_face, int resolution, uint32_t *bits, uint8_t *vox, int32_t *stats, void *workspace,
+                             size_t workspace_bytes, void *stream);
+int deftet_voxel_pack_u8(const uint8_t *vox, int n_batch, int resolution, uint32_t *bits, void *stream);
+int deftet_voxel_unpack_u8(const uint32_t *bits, int n_batch, int resolution, uint8_t *vox, void *stream);
+int deftet_extract_odms_u8(const uint8_t *vox, int n_batch, int resolution, int32_t *odms, void *stream);
+int deftet_project_odms_i32(const int32_t *odms, const uint8_t *vox_in, int n_batch, int resolution, int votes, uint8_t *out, void *stream);
+size_t deftet_voxel_fill_workspace_bytes(int n_batch, int resolution);
+int deftet_voxel_fill_b32(const uint32_t *bits, int n_batch, int resolution, uint32_t *out, void *workspace, size_t workspace_bytes,
+                          void *stream);
+size_t deftet_voxel_surface_workspace_bytes(int n_batch, int resolution);
+int deftet_voxel_surface_count_b32(const uint32_t *bits, int n_batch, int resolution, int32_t *offsets, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+int deftet_voxel_surface_fill_b32(const uint32_t *bits, int n_batch, int resolution, long long cap_faces, long long cap_verts, float *verts,
+                                  int64_t *faces, void *workspace, size_t workspace_bytes, void *stream);
+size_t deftet_face_edges_workspace_bytes(int n_face);
+int deftet_face_edges_i32(const int64_t *faces, int n_face, int n_vertex, int32_t *pairs, int32_t *n_out, void *workspace,
+                          size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
