@@ -629,7 +629,9 @@ def test_tri_dist_backward_with_forward_order_matches_atomic_and_sorted_paths(cu
 def test_chamfer_to_cloud_matches_the_torch_composition(cuda, oracle):
     """hip_ops.chamfer_to_cloud (sample placement + distance + gradient as three HIP launches around A10) == the same
     quantity written with torch ops on the same random numbers: sample_on_faces -> nn_index -> gather -> sqrt -> masked
-    sum, value and gradient w.r.t. the corners (fp64 autograd of the torch expression as the gradient reference)."""
+    sum, value and gradient w.r.t. the corners.  The torch expression and its autograd run in fp32 here (this test pins
+    the generator path); the fp64 reference of the same quantity, at the same bounds, is held in
+    test_surface_ops_switches_gpu.py::test_chamfer_to_cloud_vs_fp64_across_shape_groups."""
     from deftet_amd import hip_ops
     from deftet_amd import surface_losses as SL
     radii = [0.3, 0.22, 0.0, 0.38]                                    # one empty surface
