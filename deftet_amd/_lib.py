@@ -165,6 +165,13 @@ SIGNATURES = {
     "deftet_voxel_surface_fill_b32": (_i, [_vp, _i, _i, _ll, _ll, _vp, _vp, _vp, _sz, _vp]),
     "deftet_face_edges_workspace_bytes": (_sz, [_i]),
     "deftet_face_edges_i32": (_i, [_vp, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "deftet_edge_vertex_csr_workspace_bytes": (_sz, [_i, _i]),
+    "deftet_edge_vertex_csr_i32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "deftet_marching_tets_workspace_bytes": (_sz, [_i, _i, _i]),
+    "deftet_marching_tets_count_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
+    "deftet_marching_tets_fill_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _ll, _ll, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _vp, _sz, _vp]),
+    "deftet_marching_tets_bwd_f32": (_i, [_vp, _vp, _ll, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
 }
 
 _lock = threading.Lock()

@@ -1905,6 +1905,151 @@ def surface_weld(verts_vx3, faces_fx3, attrs=None):
     return vout[:n_used], (aout[:n_used] if aout is not None else None), fout, old[:n_used]
 
 
+# --------------------------------------------------------------------------------- marching tetrahedra
+IsoMesh = collections.namedtuple("IsoMesh", "verts faces vert_attr edge_id t tet_id")
+
+
+class TetEdges:
+    """The edge topology of a tet list for marching_tets, built once and reused (like FaceTopology / VertexAdjacency): `edges`
+    int32 [E,2] — the unique (min,max) rows in lexicographic order — and `tet_edge` int32 [T,6] — the edge ids in local order
+    (0,1),(0,2),(0,3),(1,2),(1,3),(2,3) — exactly what tet_edges returns; `tets` int32 [T,4]; and the vertex -> edge-end CSR
+    `offsets` int32 [V+1], `slots` int32 [2E] holding 2*e+side (side 0 = the min end) in ascending order per vertex.  Raises
+    IndexError on an index outside [0, n_vertex).  A snapshot of the list it was built from: a new tet list means a new object.
+    `device`: where to put a host list."""
+
+    def __init__(self, tet_tx4, n_vertex, device=None):
+        tets = torch.as_tensor(tet_tx4)
+        if device is not None:
+            tets = tets.to(device)
+        _lib.require_gpu(tets)
+        lib = _lib.load()
+        tets = _i64_tets(tets)
+        T, V, dev = int(tets.shape[0]), int(n_vertex), tets.device
+        if T == 0 or V <= 0:
+            raise ValueError("TetEdges: an empty tet list or no vertices")
+        edges, tet_edge = tet_edges(tets, V)                          # (IndexError on an index outside [0, V))
+        E = int(edges.shape[0])
+        offsets = torch.empty(V + 1, device=dev, dtype=torch.int32)
+        slots = torch.empty(2 * E, device=dev, dtype=torch.int32)
+        bad = torch.zeros(1, device=dev, dtype=torch.int32)
+        with _lib.on_device(dev):
+            ws = _lib.workspace(dev, lib.deftet_edge_vertex_csr_workspace_bytes(V, E))
+            _lib.check(lib.deftet_edge_vertex_csr_i32(_lib.ptr(edges), _lib.ptr(offsets), _lib.ptr(slots), _lib.ptr(bad), V, E,
+                                                      _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)), "deftet_edge_vertex_csr_i32")
+        if int(bad.item()):
+            raise IndexError("TetEdges: vertex index outside [0, %d)" % V)
+        self.tets = tets.to(torch.int32).contiguous()
+        self.edges, self.tet_edge = edges.to(torch.int32).contiguous(), tet_edge.to(torch.int32).contiguous()
+        self.offsets, self.slots = offsets, slots
+        self.n_vertex, self.n_tet, self.n_edge, self.device = V, T, E, dev
+
+
+class _MarchingTets(torch.autograd.Function):
+    """flat outputs for the whole batch: (verts [Nv,3], vert_attr [Nv,C] | None, faces, edge_id, t, tet_id, offsets [2,B+1] on the
+    host); marching_tets splits them by shape"""
+
+    @staticmethod
+    def forward(ctx, pos, field, attr, topology, iso, return_index):
+        lib = _lib.load()
+        top = topology
+        B, V, T, E, dev = pos.shape[0], top.n_vertex, top.n_tet, top.n_edge, pos.device
+        C = 0 if attr is None else int(attr.shape[2])
+        ev = torch.empty(B, E, dtype=torch.int32, device=dev)
+        offs = torch.empty(2, B + 1, dtype=torch.int32, device=dev)
+        with _lib.on_device(dev):
+            st = _lib.current_stream(dev)
+            # the count pass leaves the output rows in its workspace for the fill pass: a tensor of this call, not the shared one
+            wsb = lib.deftet_marching_tets_workspace_bytes(B, T, E)
+            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+            _lib.check(lib.deftet_marching_tets_count_f32(_lib.ptr(field), _lib.ptr(top.edges), _lib.ptr(top.tets), B, V, T, E, iso,
+                                                          _lib.ptr(ev), _lib.ptr(offs), _lib.ptr(ws), wsb, st),
+                       "deftet_marching_tets_count_f32")
+            o = offs.tolist()                           # the one sync
+            Nv, Nf = o[0][B], o[1][B]
+            verts = torch.empty(Nv, 3, dtype=torch.float32, device=dev)
+            vattr = torch.empty(Nv, C, dtype=torch.float32, device=dev) if C else None
+            faces = torch.empty(Nf, 3, dtype=torch.int64, device=dev)
+            edge_id = torch.empty(Nv, dtype=torch.int64, device=dev) if return_index else None
+            t = torch.empty(Nv, dtype=torch.float32, device=dev) if return_index else None
+            tet_id = torch.empty(Nf, dtype=torch.int64, device=dev) if return_index else None
+            _lib.check(lib.deftet_marching_tets_fill_f32(_lib.ptr(pos), _lib.ptr(field), _lib.ptr(attr), C, _lib.ptr(top.edges),
+                                                         _lib.ptr(top.tets), _lib.ptr(top.tet_edge), _lib.ptr(ev), B, V, T, E, iso, Nv, Nf,
+                                                         _lib.ptr(verts), _lib.ptr(vattr), _lib.ptr(faces), _lib.ptr(edge_id), _lib.ptr(t),
+                                                         _lib.ptr(tet_id), _lib.ptr(ws), wsb, st), "deftet_marching_tets_fill_f32")
+        ctx.save_for_backward(pos, field, attr, ev, offs)
+        ctx.topology, ctx.iso, ctx.offsets = top, iso, o
+        outs = (verts, vattr, faces, edge_id, t, tet_id)
+        ctx.mark_non_differentiable(*[x for x in outs[2:] if x is not None])
+        ctx.set_materialize_grads(False)
+        return outs + (o,)
+
+    @staticmethod
+    def backward(ctx, g_verts, g_vattr, *_unused):
+        pos, field, attr, ev, offs = ctx.saved_tensors
+        want = ctx.needs_input_grad[:3]
+        top, Nv = ctx.topology, ctx.offsets[0][-1]
+        B, V, dev = pos.shape[0], top.n_vertex, pos.device
+        C = 0 if attr is None else int(attr.shape[2])
+        want_attr = want[2] and attr is not None
+        if not (want[0] or want[1] or want_attr):
+            return (None,) * 6
+        if Nv == 0 or (g_verts is None and g_vattr is None):
+            return (torch.zeros_like(pos) if want[0] else None, torch.zeros_like(field) if want[1] else None,
+                    torch.zeros_like(attr) if want_attr else None, None, None, None)
+        lib = _lib.load()
+        g_verts, g_vattr = (None if g is None else _f32c(g) for g in (g_verts, g_vattr))
+        gp = torch.empty(B, V, 3, device=dev, dtype=torch.float32) if want[0] else None
+        gf = torch.empty(B, V, device=dev, dtype=torch.float32) if want[1] else None
+        ga = torch.empty(B, V, C, device=dev, dtype=torch.float32) if want_attr else None
+        with _lib.on_device(dev):
+            _lib.check(lib.deftet_marching_tets_bwd_f32(_lib.ptr(g_verts), _lib.ptr(g_vattr), Nv, _lib.ptr(pos), _lib.ptr(field),
+                                                        _lib.ptr(attr), C, _lib.ptr(top.edges), _lib.ptr(top.offsets), _lib.ptr(top.slots),
+                                                        _lib.ptr(ev), _lib.ptr(offs), B, V, top.n_edge, ctx.iso, _lib.ptr(gp), _lib.ptr(gf),
+                                                        _lib.ptr(ga), _lib.current_stream(dev)), "deftet_marching_tets_bwd_f32")
+        return gp, gf, ga, None, None, None
+
+
+def marching_tets(pos, field, topology, iso=0.0, attr=None, return_index=False):
+    """Marching tetrahedra on a per-vertex field: IsoMesh(verts, faces, vert_attr, edge_id, t, tet_id), each a list of B tensors
+    (or None) — verts f32 [Nv_b,3] in ascending edge id, faces int64 [Nf_b,3] (local to the shape) in ascending tet id, vert_attr
+    f32 [Nv_b,C] with attr f32 [B,V,C] (1 <= C <= 8); with return_index also edge_id int64 [Nv_b], t f32 [Nv_b], tet_id int64
+    [Nf_b].  pos f32 [B,V,3] (or [V,3] for one shape), field f32 [B,V], topology a TetEdges.  A corner is inside iff field > iso
+    (fp32, strict; NaN is outside); every crossing edge gets one vertex at t = (iso - f_min) / (f_max - f_min) between its lower
+    and its higher vertex id, so the mesh is welded.  Normals point from the inside to the outside of positively oriented tets
+    (a negatively oriented tet comes out flipped; nothing is detected).  Differentiable: the gradients of verts and vert_attr
+    flow to pos, attr and field through one CSR reduction (no atomics, the same bits on every run).  One read-back (the offsets)."""
+    if attr is not None and (attr.dim() not in (2, 3) or not 1 <= int(attr.shape[-1]) <= 8):
+        raise _lib.DefTetHipError("marching_tets: attr [B,V,C] with 1 <= C <= 8 expected, got %s (DEFTET_EINVAL)" % (tuple(attr.shape),))
+    _lib.require_gpu(pos, field, attr)
+    if not isinstance(topology, TetEdges):
+        raise TypeError("marching_tets: topology must be a hip_ops.TetEdges (built once per tet list)")
+    iso = float(iso)
+    if not np.isfinite(np.float32(iso)):
+        raise _lib.DefTetHipError("marching_tets: iso = %r is not a finite float32 (DEFTET_EINVAL)" % iso)
+    V = topology.n_vertex
+    p = _f32c(pos)
+    if p.dim() == 2:
+        p = p[None]
+    B = int(p.shape[0])
+    if p.dim() != 3 or tuple(p.shape[1:]) != (V, 3) or p.device != topology.device:
+        raise RuntimeError("marching_tets: pos [B,%d,3] or [%d,3] on %s expected, got %s" % (V, V, topology.device, tuple(pos.shape)))
+    f = _f32c(field)
+    if f.numel() != B * V:
+        raise RuntimeError("marching_tets: field [%d,%d] expected, got %s" % (B, V, tuple(field.shape)))
+    f = f.reshape(B, V)
+    a = None
+    if attr is not None:
+        a = _f32c(attr)
+        if a.numel() != B * V * int(a.shape[-1]):
+            raise RuntimeError("marching_tets: attr [%d,%d,C] expected, got %s" % (B, V, tuple(attr.shape)))
+        a = a.reshape(B, V, int(a.shape[-1]))
+    verts, vattr, faces, edge_id, t, tet_id, o = _MarchingTets.apply(p, f, a, topology, iso, bool(return_index))
+
+    def split(x, row):
+        return None if x is None else [x[o[row][b]:o[row][b + 1]] for b in range(B)]
+    return IsoMesh(split(verts, 0), split(faces, 1), split(vattr, 0), split(edge_id, 0), split(t, 0), split(tet_id, 1))
+
+
 # --------------------------------------------------------------------------------- rendering from the vertices (DESIGN.md section 6h)
 class FaceTopology:
     """A face list for face_gather, built once and reused (like TetTopology / VertexAdjacency): `faces` int64 [F,3] on the GPU

@@ -63,6 +63,7 @@ class TetTopology:
         self.csr = hip_ops.tet_vertex_csr(self.tet_idx, self.n_vertex)     # (raises on an index outside [0, n_vertex))
         self.tet_idx32 = self.tet_idx.to(torch.int32).contiguous()         # what the indexed query reads (hip_ops.point_in_tet_indexed)
         self._vertex_adjacency = {}                                         # normalize -> hip_ops.VertexAdjacency (vertex_adjacency)
+        self._edges = None                                                  # hip_ops.TetEdges (edges)
 
     def gather(self, vertice_pos):
         return _TetGather.apply(vertice_pos, self.tet_idx, self.csr)
@@ -81,6 +82,18 @@ class TetTopology:
             adj = hip_ops.VertexAdjacency.from_tets(tets, self.n_vertex, normalize=key)
             self._vertex_adjacency[key] = adj
         return adj
+
+    def edges(self):
+        """hip_ops.TetEdges of this tet list (unique edges, tet -> edge table, vertex -> edge-end CSR), for
+        hip_ops.marching_tets; built on the first call and kept."""
+        if self._edges is None:
+            tets = self.tet_idx
+            if tets.dim() == 3:
+                if tets.shape[0] != 1:
+                    raise RuntimeError("TetTopology.edges: the shapes of this batch have different tet lists")
+                tets = tets[0]
+            self._edges = hip_ops.TetEdges(tets, self.n_vertex)
+        return self._edges
 
 
 # Cache of the incidence CSR, per device and index shape, at MODULE level: nn.DataParallel (train_multigpu.py:138)

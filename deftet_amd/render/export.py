@@ -5,7 +5,8 @@
                                           3_model/utils_tetsv.py:131-141, 228-239), byte for byte: 'v %f %f %f\\n' per corner
                                           (six numbers with colours) and 'f %d %d %d\\n' with idx+1, idx+3, idx+2 per triangle
     mesh_obj_text                         an indexed mesh in the same conventions (new: the reference has no indexed writer)
-    save_surface_objs                     the eight files of saveobj (+ the indexed `tet-mesh-...` files with welded=True)
+    save_surface_objs                     the eight files of saveobj (+ the indexed `tet-mesh-...` files with welded=True, + the
+                                          marching-tetrahedra `mt-geo-...` / `mt-color-...` files with iso)
 
 The reference formats per triangle in a Python loop and grows one string; here one '%' application formats a block of rows.
 '%f' of inf and nan is left as Python prints it.
@@ -69,7 +70,8 @@ def _write(path, text):
         f.write(text)
 
 
-def save_surface_objs(points_px3, feat, tet_tx4, nbr, savedir, prefix, thresholds=(0.005, 0.05, 0.15, 0.25), welded=False):
+def save_surface_objs(points_px3, feat, tet_tx4, nbr, savedir, prefix, thresholds=(0.005, 0.05, 0.15, 0.25), welded=False,
+                      iso=None):
     """Writes what Deftet.saveobj writes (3_model/deftet.py:533-557): for every threshold `tet-geo-<prefix>-thres-<t>.obj` and
     `tet-color-<prefix>-thres-<t>.obj`.  `feat` = (weights [P] / [P,1], colours [P,3]) as `processfunc` returns them, or one
     [P,4] tensor holding them side by side; the colours are written reversed (colorsnp_px3[:, ::-1], :513).  The per-tet
@@ -77,7 +79,9 @@ def save_surface_objs(points_px3, feat, tet_tx4, nbr, savedir, prefix, threshold
     of the tet list (or the reference's list of four sparse matrices).  welded=True adds `tet-mesh-<prefix>-thres-<t>.obj`, the
     same surface as an indexed mesh with colours.  Returns the list of paths.  An export path, not a training step: every threshold is
     one surface_extract call (its own read-back of the offsets, the fused maximum computed again) and, with welded, one more
-    read-back in surface_weld."""
+    read-back in surface_weld.  With `iso` it additionally writes `mt-geo-<prefix>-iso-<iso>.obj` and `mt-color-<prefix>-iso-<iso>.obj`:
+    the marching-tetrahedra surface of the per-vertex weights at that level (hip_ops.marching_tets) as an indexed mesh, without and
+    with the colours, faces in the operator's winding (normals towards the lower weights)."""
     if isinstance(feat, (tuple, list)):
         weights, colours = feat
     else:
@@ -104,4 +108,11 @@ def save_surface_objs(points_px3, feat, tet_tx4, nbr, savedir, prefix, threshold
             v, c, f, _old = hip_ops.surface_weld(pts, soup.faces[0], col)
             paths.append("%s/tet-mesh-%s-thres-%.3f.obj" % (savedir, prefix, thres))
             _write(paths[-1], mesh_obj_text(v, f, c))
+    if iso is not None:
+        mesh = hip_ops.marching_tets(pts, w, hip_ops.TetEdges(tet, pts.shape[0]), iso=iso, attr=col)
+        v, f, c = mesh.verts[0].detach(), mesh.faces[0][:, [0, 2, 1]], mesh.vert_attr[0].detach()     # (the writer swaps them back)
+        paths.append("%s/mt-geo-%s-iso-%.3f.obj" % (savedir, prefix, iso))
+        _write(paths[-1], mesh_obj_text(v, f))
+        paths.append("%s/mt-color-%s-iso-%.3f.obj" % (savedir, prefix, iso))
+        _write(paths[-1], mesh_obj_text(v, f, c))
     return paths

@@ -42,7 +42,9 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
-/* 310: ground-truth preparation — deftet_mesh_voxelize_f32, deftet_voxel_pack_u8 / _unpack_u8, deftet_extract_odms_u8,
+/* 320: marching tetrahedra on a per-vertex field — deftet_edge_vertex_csr_i32, deftet_marching_tets_count_f32 / _fill_f32 / _bwd_f32
+ *      and their workspace sizes (marching_tets.hip).
+ * 310: ground-truth preparation — deftet_mesh_voxelize_f32, deftet_voxel_pack_u8 / _unpack_u8, deftet_extract_odms_u8,
  *      deftet_project_odms_i32, deftet_voxel_fill_b32, deftet_voxel_surface_count_b32 / _fill_b32, deftet_face_edges_i32 and their
  *      workspace sizes (dataprep.hip).
  * 300: the wide-channel vertex aggregation — deftet_vertex_aggregate_f32 (vertex_aggregate.hip).
@@ -330,6 +332,52 @@ size_t deftet_surface_weld_workspace_bytes(int n_vertex);
 int deftet_surface_weld_f32(const int64_t *faces_fx3, long long n_face, const float *verts_vx3, const float *attr_vxc, int n_attr,
                             int n_vertex, int capacity, int32_t *n_out, int64_t *old_id, float *verts_out, float *attr_out,
                             int64_t *faces_out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * Marching tetrahedra on a per-vertex field (320; marching_tets.hip): a welded iso-surface mesh per shape, with
+ * the gradient of its vertices.  A corner is inside iff field > iso (fp32, strict; NaN is outside).  Every edge of the unique
+ * edge list whose ends differ gets one vertex, t = (iso - f_min) / (f_max - f_min), p = p_min + t (p_max - p_min) with min / max
+ * = the edge's lower / higher vertex id; attributes use the same t.  Faces: per tet the triangles of its case code
+ * sum(inside_k << k) as crossing-edge ids mapped to vertex rows, starting at the lowest local edge id, normals from the inside
+ * to the outside corners of a positively oriented tet (a negatively oriented tet comes out flipped; nothing is detected).
+ * Rows per shape: vertices in ascending edge id, faces in ascending tet id.
+ *
+ * deftet_edge_vertex_csr_i32: the vertex -> edge-end CSR of edges_ex2 int64 [n_edge,2] (deftet_tet_edges_i64): offsets int32
+ * [n_vertex+1], slots int32 [2 n_edge] holding 2*e+side (side 0 = min) in ascending order per vertex; *bad_flag = 1 for an index
+ * outside [0, n_vertex). */
+size_t deftet_edge_vertex_csr_workspace_bytes(int n_vertex, int n_edge);
+int deftet_edge_vertex_csr_i32(const int64_t *edges_ex2, int32_t *offsets, int32_t *slots, int32_t *bad_flag, int n_vertex, int n_edge,
+                               void *workspace, size_t workspace_bytes, void *stream);
+/* Count pass.  field_bxv f32 [B,n_vertex]; edges_ex2 int32 [n_edge,2] (8-byte aligned), tet_idx_tx4 int32 [n_tet,4] (16-byte
+ * aligned), both with every index inside [0, n_vertex) (the caller's topology object has checked them).  Writes edge_vertex_bxe
+ * int32 [B,n_edge] = the vertex row of the edge inside its shape, -1 where it does not cross, and offsets_2xb1 int32 [2,B+1]
+ * (device) = first vertex row / first face row of every shape, [.][B] = the totals.  The workspace keeps the scanned counts:
+ * hand the SAME, untouched workspace to the fill pass.  n_batch * (n_edge + 2 n_tet) must stay below 2^31 - 1 (the int32 row sums of
+ * the one scan both counts share) and n_batch * n_vertex below 2^31; both passes check it. */
+size_t deftet_marching_tets_workspace_bytes(int n_batch, int n_tet, int n_edge);
+int deftet_marching_tets_count_f32(const float *field_bxv, const int32_t *edges_ex2, const int32_t *tet_idx_tx4, int n_batch, int n_vertex,
+                                   int n_tet, int n_edge, float iso, int32_t *edge_vertex_bxe, int32_t *offsets_2xb1, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+/* Fill pass, same field, iso and lists.  n_vert / n_face = rows the outputs hold (the totals of the count pass).  verts f32
+ * [n_vert,3]; with attr_bxvxc f32 [B,n_vertex,n_attr] (1 <= n_attr <= 8; NULL with n_attr = 0) vert_attr f32 [n_vert,n_attr];
+ * faces int64 [n_face,3] = vertex rows local to the shape; optional edge_id int64 [n_vert], t f32 [n_vert], tet_id int64 [n_face]. */
+int deftet_marching_tets_fill_f32(const float *pos_bxvx3, const float *field_bxv, const float *attr_bxvxc, int n_attr,
+                                  const int32_t *edges_ex2, const int32_t *tet_idx_tx4, const int32_t *tet_edge_tx6,
+                                  const int32_t *edge_vertex_bxe, int n_batch, int n_vertex, int n_tet, int n_edge, float iso,
+                                  long long n_vert, long long n_face, float *verts, float *vert_attr, int64_t *faces, int64_t *edge_id,
+                                  float *t, int64_t *tet_id, void *workspace, size_t workspace_bytes, void *stream);
+/* Backward: grad_verts f32 [n_vert,3] and / or grad_vert_attr f32 [n_vert,n_attr] (either may be NULL = zero) to grad_pos f32
+ * [B,n_vertex,3], grad_field f32 [B,n_vertex], grad_attr f32 [B,n_vertex,n_attr] (each may be NULL).  One thread per (b,v) walks
+ * the vertex's CSR row in slot order and skips the edges whose edge_vertex entry is -1: (1-t) g or t g into grad_pos / grad_attr,
+ * dt/df (g_p . (p_max - p_min) + g_a . (a_max - a_min)) into grad_field with dt/df_min = (iso - f_max) / (f_max - f_min)^2,
+ * dt/df_max = -(iso - f_min) / (f_max - f_min)^2.  Sums in double in a fixed order, no atomics: the same bits on every run;
+ * exact zeros for vertices without a crossing edge.  edge_vertex_bxe and offsets_2xb1 are what the count pass wrote.  n_batch <= 65535
+ * (the batch is the grid's second dimension). */
+int deftet_marching_tets_bwd_f32(const float *grad_verts, const float *grad_vert_attr, long long n_vert, const float *pos_bxvx3,
+                                 const float *field_bxv, const float *attr_bxvxc, int n_attr, const int32_t *edges_ex2,
+                                 const int32_t *csr_offsets, const int32_t *csr_slots, const int32_t *edge_vertex_bxe,
+                                 const int32_t *offsets_2xb1, int n_batch, int n_vertex, int n_edge, float iso, float *grad_pos,
+                                 float *grad_field, float *grad_attr, void *stream);
 
 /* ---------------------------------------------------------------------------------
  * N1  ground-truth occupancy by ray parity:

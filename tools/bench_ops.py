@@ -348,6 +348,22 @@ def main():
     emit(op="surface_extract binary", res=res, batch=Be, n_tet=T, rows=rows_s, gpu_ms=round(tsx * 1e3, 3),
          **roof(2 * Be * T * 20 + rows_s * 72, tsx, "latency (two small passes and one read-back of the offsets)"))
 
+    # ---- marching tetrahedra: welded iso-surface of sphere fields on the vertices, whole batch, forward + backward;
+    # the A/B against the torch restatement is tools/marching_tets_ab.py
+    pos_m = torch.from_numpy(grids.jittered_positions(verts, res, Be)).to(dev).requires_grad_(True)
+    fld_m = (0.3 - pos_m.detach().norm(dim=-1)).requires_grad_(True)
+    top_m = hip_ops.TetEdges(tets_d.long(), n_point)
+
+    def mt_step():
+        m = hip_ops.marching_tets(pos_m, fld_m, top_m)
+        return torch.autograd.grad(sum(v.sum() for v in m.verts), (pos_m, fld_m))
+    tmt = gpu_time(mt_step, reps=10)
+    mesh_m = hip_ops.marching_tets(pos_m.detach(), fld_m.detach(), top_m)
+    nv_m, nf_m = sum(int(v.shape[0]) for v in mesh_m.verts), sum(int(f.shape[0]) for f in mesh_m.faces)
+    emit(op="marching_tets fwd+bwd", res=res, batch=Be, n_tet=T, n_edge=top_m.n_edge, verts=nv_m, faces=nf_m, gpu_ms=round(tmt * 1e3, 3),
+         **roof(2 * Be * (top_m.n_edge * 12 + T * 20) + Be * top_m.n_edge * 4 + nv_m * 16 + nf_m * 48 + Be * n_point * 32, tmt,
+                "latency (five small launches, one read-back of the offsets, the CSR walk of the backward)"))
+
     # ---- A1 forward: the binned path against the brute-force HIP formulation (the algorithmic equivalent of the
     # reference kernel: every query meets every tet in index order), BASELINE configs[2]
     Bp, Qp = (2, 20000) if quick else (8, 100000)
