@@ -12,6 +12,7 @@
 //
 // Integer work only: results are bit-exact with the oracle / oracle/_ref.
 #include <cstring>
+#include <initializer_list>
 
 #include "common.hpp"
 
@@ -494,38 +495,185 @@ static int key_bits(u64 max_key)
     return b;
 }
 
-// temporary storage of the sorts and scans (prims.hpp) is carved from the tail of the caller's workspace
-struct Ws {
-    Arena A;
-    Ws(void *p, size_t n) : A(p, n) {}
-    void *tail() { A.off = align_up(A.off, 256); return A.base + A.off; }
-    size_t left() const { return A.cap > A.off ? A.cap - A.off : 0; }
+// temporary storage of a sort or a scan (prims.hpp): a member of the builder's layout, sized by prims for that builder's n
+struct Tmp {
+    void *p;
+    size_t bytes;
 };
 
 template <typename V>
-static int sort_pairs(Ws &W, const u64 *kin, u64 *kout, const V *vin, V *vout, size_t n, int bits, hipStream_t st)
+static int sort_pairs(Tmp W, const u64 *kin, u64 *kout, const V *vin, V *vout, size_t n, int bits, hipStream_t st)
 {
-    void *tmp = W.tail();
-    return prims::radix_sort<u64, V>(kin, kout, vin, vout, n, bits, tmp, W.left(), st);
+    return prims::radix_sort<u64, V>(kin, kout, vin, vout, n, bits, W.p, W.bytes, st);
 }
 
-static int sort_keys(Ws &W, const u64 *kin, u64 *kout, size_t n, int bits, hipStream_t st)
+static int sort_keys(Tmp W, const u64 *kin, u64 *kout, size_t n, int bits, hipStream_t st)
 {
-    void *tmp = W.tail();
-    return prims::radix_sort_keys<u64>(kin, kout, n, bits, tmp, W.left(), st);
+    return prims::radix_sort_keys<u64>(kin, kout, n, bits, W.p, W.bytes, st);
 }
 
 template <typename T>
-static int ex_scan(Ws &W, const T *in, T *out, size_t n, hipStream_t st)
+static int ex_scan(Tmp W, const T *in, T *out, size_t n, hipStream_t st)
 {
-    void *tmp = W.tail();
-    return prims::scan<T, prims::Plus, true>(in, out, n, T(0), prims::Plus(), tmp, W.left(), st);
+    return prims::scan<T, prims::Plus, true>(in, out, n, T(0), prims::Plus(), W.p, W.bytes, st);
 }
 
-static int max_scan(Ws &W, const int *in, int *out, size_t n, hipStream_t st)
+static int max_scan(Tmp W, const int *in, int *out, size_t n, hipStream_t st)
 {
-    void *tmp = W.tail();
-    return prims::scan<int, prims::Max, false>(in, out, n, (int)0x80000000, prims::Max(), tmp, W.left(), st);
+    return prims::scan<int, prims::Max, false>(in, out, n, (int)0x80000000, prims::Max(), W.p, W.bytes, st);
+}
+
+static Tmp take_tmp(Arena &A, size_t bytes) { return Tmp{A.take<char>(bytes), bytes}; }
+
+// ---- one layout per builder: the size (null base) and the arrays (the caller's workspace) come from the same function ----
+// n sorted (key, owner) pairs and one flag / position per pair: tet_adj_share (n = 4T), tet_edges (n = 6T)
+struct PairLayout {
+    size_t bytes;
+    u64 *key, *skey;
+    u32 *own, *sown;
+    int *flag, *pos;
+    Tmp sort, scan;
+};
+static PairLayout pair_layout(size_t n, void *ws)
+{
+    PairLayout L{};
+    Arena A(ws);
+    L.key = A.take<u64>(n); L.skey = A.take<u64>(n);
+    L.own = A.take<u32>(n); L.sown = A.take<u32>(n);
+    L.flag = A.take<int>(n); L.pos = A.take<int>(n);
+    L.sort = take_tmp(A, prims::radix_sort_temp_bytes<u64, u32>(n));
+    L.scan = take_tmp(A, prims::scan_temp_bytes<int>(n));
+    L.bytes = A.end();
+    return L;
+}
+static PairLayout share_layout(int T, void *ws) { return pair_layout((size_t)T * 4, ws); }
+static PairLayout edges_layout(int T, void *ws) { return pair_layout((size_t)T * 6, ws); }
+
+struct ToFaceLayout {
+    size_t bytes;
+    u64 *key, *skey;
+    u32 *own, *sown;
+    int *gsize, *second, *f_in, *f_bd, *f_mu, *p_in, *p_bd, *p_mu;
+    Tmp sort, scan;
+};
+static ToFaceLayout to_face_layout(int T, void *ws)
+{
+    ToFaceLayout L{};
+    const size_t n = (size_t)T * 4;
+    Arena A(ws);
+    L.key = A.take<u64>(n); L.skey = A.take<u64>(n);
+    L.own = A.take<u32>(n); L.sown = A.take<u32>(n);
+    L.gsize = A.take<int>(n); L.second = A.take<int>(n);
+    L.f_in = A.take<int>(n); L.f_bd = A.take<int>(n); L.f_mu = A.take<int>(n);
+    L.p_in = A.take<int>(n); L.p_bd = A.take<int>(n); L.p_mu = A.take<int>(n);
+    L.sort = take_tmp(A, prims::radix_sort_temp_bytes<u64, u32>(n));
+    L.scan = take_tmp(A, prims::scan_temp_bytes<int>(n));
+    L.bytes = A.end();
+    return L;
+}
+
+struct FaceAdjLayout {
+    size_t bytes;
+    u64 *key, *skey, *fkey;
+    u32 *ord, *sord;
+    long long *cnt, *pos;
+    Tmp sort, scan;
+};
+static FaceAdjLayout face_adj_layout(int T, void *ws)
+{
+    FaceAdjLayout L{};
+    const size_t n = (size_t)T * 12, nf = (size_t)T * 4;
+    Arena A(ws);
+    L.key = A.take<u64>(n); L.skey = A.take<u64>(n); L.fkey = A.take<u64>(nf);
+    L.ord = A.take<u32>(n); L.sord = A.take<u32>(n);
+    L.cnt = A.take<long long>(n); L.pos = A.take<long long>(n);
+    L.sort = take_tmp(A, prims::radix_sort_temp_bytes<u64, u32>(n));
+    L.scan = take_tmp(A, prims::scan_temp_bytes<long long>(n));
+    L.bytes = A.end();
+    return L;
+}
+
+struct PointAdjLayout {
+    size_t bytes;
+    u64 *key, *skey;
+    int *flag, *pos;
+    Tmp sort, scan;
+};
+static PointAdjLayout point_adj_layout(int T, void *ws)
+{
+    PointAdjLayout L{};
+    const size_t n = (size_t)T * 12;
+    Arena A(ws);
+    L.key = A.take<u64>(n); L.skey = A.take<u64>(n);
+    L.flag = A.take<int>(n); L.pos = A.take<int>(n);
+    L.sort = take_tmp(A, prims::radix_sort_temp_bytes<u64, unsigned>(n, false));
+    L.scan = take_tmp(A, prims::scan_temp_bytes<int>(n));
+    L.bytes = A.end();
+    return L;
+}
+
+struct ColapsLayout {
+    size_t bytes;
+    u64 *kx, *ky, *kz, *ka, *kb;
+    u32 *i0, *i1;
+    int *hp, *hps, *first, *isf, *nid;
+    Tmp sort, scan;
+};
+static ColapsLayout colaps_layout(int N, void *ws)
+{
+    ColapsLayout L{};
+    const size_t n = (size_t)N;
+    Arena A(ws);
+    L.kx = A.take<u64>(n); L.ky = A.take<u64>(n); L.kz = A.take<u64>(n); L.ka = A.take<u64>(n); L.kb = A.take<u64>(n);
+    L.i0 = A.take<u32>(n); L.i1 = A.take<u32>(n);
+    L.hp = A.take<int>(n); L.hps = A.take<int>(n); L.first = A.take<int>(n); L.isf = A.take<int>(n); L.nid = A.take<int>(n);
+    L.sort = take_tmp(A, prims::radix_sort_temp_bytes<u64, u32>(n));
+    L.scan = take_tmp(A, prims::scan_temp_bytes<int>(n));
+    L.bytes = A.end();
+    return L;
+}
+
+struct SubdivLayout {
+    size_t bytes;
+    int *keepOld, *split, *posOld, *posSplit;
+    Tmp scan;
+};
+static SubdivLayout subdiv_layout(int T, void *ws)
+{
+    SubdivLayout L{};
+    Arena A(ws);
+    L.keepOld = A.take<int>(T); L.split = A.take<int>(T); L.posOld = A.take<int>(T); L.posSplit = A.take<int>(T);
+    L.scan = take_tmp(A, prims::scan_temp_bytes<int>((size_t)T));
+    L.bytes = A.end();
+    return L;
+}
+
+struct DeleteLayout {
+    size_t bytes;
+    int *keep, *pos;
+    Tmp scan;
+};
+static DeleteLayout delete_layout(int T, void *ws)
+{
+    DeleteLayout L{};
+    Arena A(ws);
+    L.keep = A.take<int>(T); L.pos = A.take<int>(T);
+    L.scan = take_tmp(A, prims::scan_temp_bytes<int>((size_t)T));
+    L.bytes = A.end();
+    return L;
+}
+
+struct NeighboursLayout {
+    size_t bytes;
+    int *slotFace, *slotNbr;                                             // read as int4 per tet (k_neighbour_rows)
+};
+static NeighboursLayout neighbours_layout(int T, void *ws)
+{
+    NeighboursLayout L{};
+    Arena A(ws);
+    L.slotFace = A.take<int>((size_t)T * 4); L.slotNbr = A.take<int>((size_t)T * 4);
+    L.bytes = A.end();
+    return L;
 }
 
 #define TRY(x)                     \
@@ -611,12 +759,16 @@ __global__ __launch_bounds__(256) void k_neighbour_rows(const int *__restrict__ 
 using namespace deftet;
 using namespace deftet::bld;
 
-// Upper bound of what any builder needs for (n_point, n_tet): our arrays over 12T records
-// plus the sorts' spare buffers and digit tables (prims.hpp).
+// What any builder needs for (n_point, n_tet): the largest of their layouts.
 extern "C" size_t deftet_builder_workspace_bytes(int n_point, int n_tet)
 {
-    size_t n = (size_t)(n_tet > 0 ? n_tet : 0) * 12 + (size_t)(n_point > 0 ? n_point : 0) + 1024;
-    return n * 96 + ((size_t)8 << 20);
+    const int P = n_point > 0 ? n_point : 0, T = n_tet > 0 ? n_tet : 0;
+    size_t m = 0;
+    for (size_t b : {share_layout(T, nullptr).bytes, to_face_layout(T, nullptr).bytes, face_adj_layout(T, nullptr).bytes,
+                     point_adj_layout(T, nullptr).bytes, colaps_layout(P, nullptr).bytes, edges_layout(T, nullptr).bytes,
+                     subdiv_layout(T, nullptr).bytes, delete_layout(T, nullptr).bytes, neighbours_layout(T, nullptr).bytes})
+        m = b > m ? b : m;
+    return m;
 }
 
 extern "C" int deftet_tet_adj_share_i32(const int32_t *tet, int32_t *out_rows, int32_t *n_out, int n_point, int T,
@@ -628,17 +780,14 @@ extern "C" int deftet_tet_adj_share_i32(const int32_t *tet, int32_t *out_rows, i
     if (T == 0) { DEFTET_HIP(hipMemsetAsync(n_out, 0, 4, st)); return DEFTET_OK; }
     DEFTET_CHECK_ARG(out_rows, "null out_rows");
     const size_t n = (size_t)T * 4;
-    Ws W(workspace, wsb);
-    u64 *key = W.A.take<u64>(n), *skey = W.A.take<u64>(n);
-    u32 *own = W.A.take<u32>(n), *sown = W.A.take<u32>(n);
-    int *flag = W.A.take<int>(n), *pos = W.A.take<int>(n);
-    DEFTET_CHECK_ARG(W.A.ok(), "workspace too small");
+    const PairLayout L = share_layout(T, workspace);
+    DEFTET_CHECK_ARG(L.bytes <= wsb, "workspace too small");
     const u64 np = (u64)n_point;
-    DEFTET_LAUNCH(k_face_keys, grid_for(n), dim3(256), st, tet, T, np, key, own, (u64 *)nullptr);
-    TRY(sort_pairs(W, key, skey, own, sown, n, key_bits(np * np * np), st));
-    DEFTET_LAUNCH(k_share_flag, grid_for(n), dim3(256), st, skey, (int)n, flag);
-    TRY(ex_scan(W, flag, pos, n, st));
-    DEFTET_LAUNCH(k_share_emit, grid_for(n), dim3(256), st, flag, pos, sown, (int)n, out_rows, n_out);
+    DEFTET_LAUNCH(k_face_keys, grid_for(n), dim3(256), st, tet, T, np, L.key, L.own, (u64 *)nullptr);
+    TRY(sort_pairs(L.sort, L.key, L.skey, L.own, L.sown, n, key_bits(np * np * np), st));
+    DEFTET_LAUNCH(k_share_flag, grid_for(n), dim3(256), st, L.skey, (int)n, L.flag);
+    TRY(ex_scan(L.scan, L.flag, L.pos, n, st));
+    DEFTET_LAUNCH(k_share_emit, grid_for(n), dim3(256), st, L.flag, L.pos, L.sown, (int)n, out_rows, n_out);
     return DEFTET_OK;
 }
 
@@ -652,32 +801,24 @@ extern "C" int deftet_tet_to_face_i32(const int32_t *tet, int64_t *face_fx3, int
     if (T == 0) { DEFTET_HIP(hipMemsetAsync(counts, 0, 12, st)); return DEFTET_OK; }
     DEFTET_CHECK_ARG(face_fx3 && tetidx_fx2 && tetfaceidx_fx2, "null output");
     const size_t n = (size_t)T * 4;
-    Ws W(workspace, wsb);
-    u64 *key = W.A.take<u64>(n), *skey = W.A.take<u64>(n);
-    u32 *own = W.A.take<u32>(n), *sown = W.A.take<u32>(n);
-    int *gsize = W.A.take<int>(n), *second = W.A.take<int>(n);
-    int *f_in = W.A.take<int>(n), *f_bd = W.A.take<int>(n), *f_mu = W.A.take<int>(n);
-    int *p_in = W.A.take<int>(n), *p_bd = W.A.take<int>(n), *p_mu = W.A.take<int>(n);
-    DEFTET_CHECK_ARG(W.A.ok(), "workspace too small");
+    const ToFaceLayout L = to_face_layout(T, workspace);
+    DEFTET_CHECK_ARG(L.bytes <= wsb, "workspace too small");
     const u64 np = (u64)n_point;
-    DEFTET_LAUNCH(k_face_keys, grid_for(n), dim3(256), st, tet, T, np, key, own, (u64 *)nullptr);
-    TRY(sort_pairs(W, key, skey, own, sown, n, key_bits(np * np * np), st));
-    DEFTET_HIP(hipMemsetAsync(gsize, 0, n * 4, st));
-    DEFTET_LAUNCH(k_group_info, grid_for(n), dim3(256), st, skey, sown, (int)n, gsize, second);
-    DEFTET_LAUNCH(k_face_flags, grid_for(n), dim3(256), st, gsize, (int)n, with_boundary, f_in, f_bd, f_mu);
-    TRY(ex_scan(W, f_in, p_in, n, st));
-    TRY(ex_scan(W, f_bd, p_bd, n, st));
-    TRY(ex_scan(W, f_mu, p_mu, n, st));
-    DEFTET_LAUNCH(k_face_emit, grid_for(n), dim3(256), st, tet, gsize, second, f_in, p_in, f_bd, p_bd, f_mu, p_mu, (int)n,
+    DEFTET_LAUNCH(k_face_keys, grid_for(n), dim3(256), st, tet, T, np, L.key, L.own, (u64 *)nullptr);
+    TRY(sort_pairs(L.sort, L.key, L.skey, L.own, L.sown, n, key_bits(np * np * np), st));
+    DEFTET_HIP(hipMemsetAsync(L.gsize, 0, n * 4, st));
+    DEFTET_LAUNCH(k_group_info, grid_for(n), dim3(256), st, L.skey, L.sown, (int)n, L.gsize, L.second);
+    DEFTET_LAUNCH(k_face_flags, grid_for(n), dim3(256), st, L.gsize, (int)n, with_boundary, L.f_in, L.f_bd, L.f_mu);
+    TRY(ex_scan(L.scan, L.f_in, L.p_in, n, st));
+    TRY(ex_scan(L.scan, L.f_bd, L.p_bd, n, st));
+    TRY(ex_scan(L.scan, L.f_mu, L.p_mu, n, st));
+    DEFTET_LAUNCH(k_face_emit, grid_for(n), dim3(256), st, tet, L.gsize, L.second, L.f_in, L.p_in, L.f_bd, L.p_bd, L.f_mu, L.p_mu, (int)n,
                   (long long *)face_fx3, (long long *)tetidx_fx2, (long long *)tetfaceidx_fx2, (long long *)boundary_fx3,
                   counts);
     return DEFTET_OK;
 }
 
-extern "C" size_t deftet_tet_neighbours_workspace_bytes(int n_tet)
-{
-    return align_up((size_t)(n_tet > 0 ? n_tet : 0) * 16, 256) * 2 + 256;
-}
+extern "C" size_t deftet_tet_neighbours_workspace_bytes(int n_tet) { return neighbours_layout(n_tet > 0 ? n_tet : 0, nullptr).bytes; }
 
 extern "C" int deftet_tet_neighbours_i64(const int64_t *tetidx_fx2, const int64_t *tetfaceidx_fx2, int n_face, int T,
                                          int64_t *nbr_tx4, int64_t *withtet_4tx2, void *workspace, size_t wsb, void *stream_)
@@ -686,16 +827,15 @@ extern "C" int deftet_tet_neighbours_i64(const int64_t *tetidx_fx2, const int64_
     if (T == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(nbr_tx4, "null nbr_tx4");
     DEFTET_CHECK_ARG(n_face == 0 || (tetidx_fx2 && tetfaceidx_fx2), "null face table");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && wsb >= deftet_tet_neighbours_workspace_bytes(T), "workspace null, misaligned or too small");
+    const NeighboursLayout L = neighbours_layout(T, workspace);
+    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && L.bytes <= wsb, "workspace null, misaligned or too small");
     hipStream_t st = as_stream(stream_);
-    Arena A(workspace, wsb);
-    int *slotFace = A.take<int>((size_t)T * 4), *slotNbr = A.take<int>((size_t)T * 4);
-    DEFTET_HIP(hipMemsetAsync(slotFace, 0x7F, (size_t)T * 16, st));
-    DEFTET_HIP(hipMemsetAsync(slotNbr, 0xFF, (size_t)T * 16, st));
+    DEFTET_HIP(hipMemsetAsync(L.slotFace, 0x7F, (size_t)T * 16, st));
+    DEFTET_HIP(hipMemsetAsync(L.slotNbr, 0xFF, (size_t)T * 16, st));
     if (n_face > 0)
         DEFTET_LAUNCH(k_owner_scatter, grid_for((size_t)n_face), dim3(256), st, (const long long *)tetidx_fx2, (const long long *)tetfaceidx_fx2,
-                      n_face, slotFace, slotNbr, (long long *)withtet_4tx2);
-    DEFTET_LAUNCH(k_neighbour_rows, grid_for((size_t)T), dim3(256), st, slotFace, slotNbr, T, (long long *)nbr_tx4);
+                      n_face, L.slotFace, L.slotNbr, (long long *)withtet_4tx2);
+    DEFTET_LAUNCH(k_neighbour_rows, grid_for((size_t)T), dim3(256), st, L.slotFace, L.slotNbr, T, (long long *)nbr_tx4);
     return DEFTET_OK;
 }
 
@@ -708,18 +848,15 @@ extern "C" int deftet_tet_face_adj_i32(const int32_t *tet, int32_t *out_rows, lo
     if (T == 0) { DEFTET_HIP(hipMemsetAsync(n_out, 0, 8, st)); return DEFTET_OK; }
     DEFTET_CHECK_ARG(out_rows || capacity == 0, "null out_rows");
     const size_t n = (size_t)T * 12, nf = (size_t)T * 4;
-    Ws W(workspace, wsb);
-    u64 *key = W.A.take<u64>(n), *skey = W.A.take<u64>(n), *fkey = W.A.take<u64>(nf);
-    u32 *ord = W.A.take<u32>(n), *sord = W.A.take<u32>(n);
-    long long *cnt = W.A.take<long long>(n), *pos = W.A.take<long long>(n);
-    DEFTET_CHECK_ARG(W.A.ok(), "workspace too small");
+    const FaceAdjLayout L = face_adj_layout(T, workspace);
+    DEFTET_CHECK_ARG(L.bytes <= wsb, "workspace too small");
     const u64 np = (u64)n_point;
-    DEFTET_LAUNCH(k_face_keys, grid_for(nf), dim3(256), st, tet, T, np, (u64 *)nullptr, (u32 *)nullptr, fkey);
-    DEFTET_LAUNCH(k_edge_keys, grid_for(n), dim3(256), st, tet, T, np, wrap32, key, ord);
-    TRY(sort_pairs(W, key, skey, ord, sord, n, wrap32 ? 32 : key_bits(np * np), st));
-    DEFTET_LAUNCH(k_edge_count, grid_for(n), dim3(256), st, skey, sord, fkey, (int)n, cnt);
-    TRY(ex_scan(W, cnt, pos, n, st));
-    DEFTET_LAUNCH(k_edge_emit, grid_for(n), dim3(256), st, skey, sord, fkey, cnt, pos, (int)n, capacity, out_rows, n_out);
+    DEFTET_LAUNCH(k_face_keys, grid_for(nf), dim3(256), st, tet, T, np, (u64 *)nullptr, (u32 *)nullptr, L.fkey);
+    DEFTET_LAUNCH(k_edge_keys, grid_for(n), dim3(256), st, tet, T, np, wrap32, L.key, L.ord);
+    TRY(sort_pairs(L.sort, L.key, L.skey, L.ord, L.sord, n, wrap32 ? 32 : key_bits(np * np), st));
+    DEFTET_LAUNCH(k_edge_count, grid_for(n), dim3(256), st, L.skey, L.sord, L.fkey, (int)n, L.cnt);
+    TRY(ex_scan(L.scan, L.cnt, L.pos, n, st));
+    DEFTET_LAUNCH(k_edge_emit, grid_for(n), dim3(256), st, L.skey, L.sord, L.fkey, L.cnt, L.pos, (int)n, capacity, out_rows, n_out);
     return DEFTET_OK;
 }
 
@@ -732,16 +869,14 @@ extern "C" int deftet_tet_point_adj_i32(const int32_t *tet, int32_t *out_edges, 
     if (T == 0) { DEFTET_HIP(hipMemsetAsync(n_out, 0, 4, st)); return DEFTET_OK; }
     DEFTET_CHECK_ARG(out_edges, "null out_edges");
     const size_t n = (size_t)T * 12;
-    Ws W(workspace, wsb);
-    u64 *key = W.A.take<u64>(n), *skey = W.A.take<u64>(n);
-    int *flag = W.A.take<int>(n), *pos = W.A.take<int>(n);
-    DEFTET_CHECK_ARG(W.A.ok(), "workspace too small");
+    const PointAdjLayout L = point_adj_layout(T, workspace);
+    DEFTET_CHECK_ARG(L.bytes <= wsb, "workspace too small");
     const u64 np = (u64)n_point;
-    DEFTET_LAUNCH(k_pt_keys, grid_for(n), dim3(256), st, tet, T, np, key);
-    TRY(sort_keys(W, key, skey, n, key_bits(np * np), st));
-    DEFTET_LAUNCH(k_unique_flag, grid_for(n), dim3(256), st, skey, (int)n, flag);
-    TRY(ex_scan(W, flag, pos, n, st));
-    DEFTET_LAUNCH(k_pt_emit, grid_for(n), dim3(256), st, skey, flag, pos, (int)n, np, out_edges, n_out);
+    DEFTET_LAUNCH(k_pt_keys, grid_for(n), dim3(256), st, tet, T, np, L.key);
+    TRY(sort_keys(L.sort, L.key, L.skey, n, key_bits(np * np), st));
+    DEFTET_LAUNCH(k_unique_flag, grid_for(n), dim3(256), st, L.skey, (int)n, L.flag);
+    TRY(ex_scan(L.scan, L.flag, L.pos, n, st));
+    DEFTET_LAUNCH(k_pt_emit, grid_for(n), dim3(256), st, L.skey, L.flag, L.pos, (int)n, np, out_edges, n_out);
     return DEFTET_OK;
 }
 
@@ -755,23 +890,20 @@ extern "C" int deftet_colaps_v_f32(const float *pts, int32_t *map_array, int32_t
     DEFTET_CHECK_ARG(pts && map_array && inverse_idx, "null pointer");
     DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0, "workspace null or misaligned");
     const size_t n = (size_t)N;
-    Ws W(workspace, wsb);
-    u64 *kx = W.A.take<u64>(n), *ky = W.A.take<u64>(n), *kz = W.A.take<u64>(n), *ka = W.A.take<u64>(n), *kb = W.A.take<u64>(n);
-    u32 *i0 = W.A.take<u32>(n), *i1 = W.A.take<u32>(n);
-    int *hp = W.A.take<int>(n), *hps = W.A.take<int>(n), *first = W.A.take<int>(n), *isf = W.A.take<int>(n), *nid = W.A.take<int>(n);
-    DEFTET_CHECK_ARG(W.A.ok(), "workspace too small");
-    DEFTET_LAUNCH(k_dec_keys, grid_for(n), dim3(256), st, pts, N, kx, ky, kz, i0);
+    const ColapsLayout L = colaps_layout(N, workspace);
+    DEFTET_CHECK_ARG(L.bytes <= wsb, "workspace too small");
+    DEFTET_LAUNCH(k_dec_keys, grid_for(n), dim3(256), st, pts, N, L.kx, L.ky, L.kz, L.i0);
     // LSD over the three coordinate keys (stable): z, then y, then x
-    TRY(sort_pairs(W, kz, kb, i0, i1, n, 64, st));
-    DEFTET_LAUNCH(k_gather_u64, grid_for(n), dim3(256), st, ky, i1, N, ka);
-    TRY(sort_pairs(W, ka, kb, i1, i0, n, 64, st));
-    DEFTET_LAUNCH(k_gather_u64, grid_for(n), dim3(256), st, kx, i0, N, ka);
-    TRY(sort_pairs(W, ka, kb, i0, i1, n, 64, st));
-    DEFTET_LAUNCH(k_colaps_heads, grid_for(n), dim3(256), st, kx, ky, kz, i1, N, hp);
-    TRY(max_scan(W, hp, hps, n, st));
-    DEFTET_LAUNCH(k_colaps_first, grid_for(n), dim3(256), st, hps, i1, N, first, isf);
-    TRY(ex_scan(W, isf, nid, n, st));
-    DEFTET_LAUNCH(k_colaps_emit, grid_for(n), dim3(256), st, first, isf, nid, N, map_array, inverse_idx, n_out);
+    TRY(sort_pairs(L.sort, L.kz, L.kb, L.i0, L.i1, n, 64, st));
+    DEFTET_LAUNCH(k_gather_u64, grid_for(n), dim3(256), st, L.ky, L.i1, N, L.ka);
+    TRY(sort_pairs(L.sort, L.ka, L.kb, L.i1, L.i0, n, 64, st));
+    DEFTET_LAUNCH(k_gather_u64, grid_for(n), dim3(256), st, L.kx, L.i0, N, L.ka);
+    TRY(sort_pairs(L.sort, L.ka, L.kb, L.i0, L.i1, n, 64, st));
+    DEFTET_LAUNCH(k_colaps_heads, grid_for(n), dim3(256), st, L.kx, L.ky, L.kz, L.i1, N, L.hp);
+    TRY(max_scan(L.scan, L.hp, L.hps, n, st));
+    DEFTET_LAUNCH(k_colaps_first, grid_for(n), dim3(256), st, L.hps, L.i1, N, L.first, L.isf);
+    TRY(ex_scan(L.scan, L.isf, L.nid, n, st));
+    DEFTET_LAUNCH(k_colaps_emit, grid_for(n), dim3(256), st, L.first, L.isf, L.nid, N, map_array, inverse_idx, n_out);
     return DEFTET_OK;
 }
 
@@ -793,21 +925,18 @@ extern "C" int deftet_tet_edges_i64(const int64_t *tet, int64_t *edges_ex2, int6
     TRY(check_i64(tet, n_point, T, workspace));
     hipStream_t st = as_stream(stream_);
     DEFTET_CHECK_ARG(n_edge && bad_flag, "null n_edge / bad_flag");
+    const PairLayout L = edges_layout(T, workspace);
+    DEFTET_CHECK_ARG(T == 0 || L.bytes <= wsb, "workspace too small");
     DEFTET_HIP(hipMemsetAsync(bad_flag, 0, 4, st));
     if (T == 0) { DEFTET_HIP(hipMemsetAsync(n_edge, 0, 4, st)); return DEFTET_OK; }
     DEFTET_CHECK_ARG(edges_ex2 && tet_edge_tx6, "null output");
     const size_t n = (size_t)T * 6;
-    Ws W(workspace, wsb);
-    u64 *key = W.A.take<u64>(n), *skey = W.A.take<u64>(n);
-    u32 *inc = W.A.take<u32>(n), *sinc = W.A.take<u32>(n);
-    int *flag = W.A.take<int>(n), *pos = W.A.take<int>(n);
-    DEFTET_CHECK_ARG(W.A.ok(), "workspace too small");
     const u64 np = (u64)(n_point > 0 ? n_point : 1);
-    DEFTET_LAUNCH(k_uedge_keys, grid_for(n), dim3(256), st, (const long long *)tet, T, np, key, inc, bad_flag);
-    TRY(sort_pairs(W, key, skey, inc, sinc, n, key_bits(np * np), st));
-    DEFTET_LAUNCH(k_unique_flag, grid_for(n), dim3(256), st, skey, (int)n, flag);
-    TRY(ex_scan(W, flag, pos, n, st));
-    DEFTET_LAUNCH(k_uedge_emit, grid_for(n), dim3(256), st, skey, sinc, flag, pos, (int)n, np, (long long *)edges_ex2,
+    DEFTET_LAUNCH(k_uedge_keys, grid_for(n), dim3(256), st, (const long long *)tet, T, np, L.key, L.own, bad_flag);
+    TRY(sort_pairs(L.sort, L.key, L.skey, L.own, L.sown, n, key_bits(np * np), st));
+    DEFTET_LAUNCH(k_unique_flag, grid_for(n), dim3(256), st, L.skey, (int)n, L.flag);
+    TRY(ex_scan(L.scan, L.flag, L.pos, n, st));
+    DEFTET_LAUNCH(k_uedge_emit, grid_for(n), dim3(256), st, L.skey, L.sown, L.flag, L.pos, (int)n, np, (long long *)edges_ex2,
                   (long long *)tet_edge_tx6, n_edge);
     return DEFTET_OK;
 }
@@ -820,6 +949,8 @@ extern "C" int deftet_subdivide_f32(const int64_t *tet, const int64_t *tet_edge_
     TRY(check_i64(tet, n_point, T, workspace));
     DEFTET_CHECK_ARG(n_edge >= 0 && n_feat >= 0, "negative size");
     DEFTET_CHECK_ARG(n_tet_new, "null n_tet_new");
+    const SubdivLayout L = subdiv_layout(T, workspace);
+    DEFTET_CHECK_ARG(T == 0 || L.bytes <= wsb, "workspace too small");
     hipStream_t st = as_stream(stream_);
     if (n_point + n_edge > 0) {
         DEFTET_CHECK_ARG(points && points_new && (n_edge == 0 || edges_ex2), "null point arrays");
@@ -833,14 +964,11 @@ extern "C" int deftet_subdivide_f32(const int64_t *tet, const int64_t *tet_edge_
     }
     if (T == 0) { DEFTET_HIP(hipMemsetAsync(n_tet_new, 0, 4, st)); return DEFTET_OK; }
     DEFTET_CHECK_ARG(tet_edge_tx6 && tet_new, "null tet arrays");
-    Ws W(workspace, wsb);
-    int *keepOld = W.A.take<int>(T), *split = W.A.take<int>(T), *posOld = W.A.take<int>(T), *posSplit = W.A.take<int>(T);
-    DEFTET_CHECK_ARG(W.A.ok(), "workspace too small");
-    DEFTET_LAUNCH(k_subdiv_flags, grid_for(T), dim3(256), st, subdiv_sig, T, keepOld, split);
-    TRY(ex_scan(W, keepOld, posOld, (size_t)T, st));
-    TRY(ex_scan(W, split, posSplit, (size_t)T, st));
+    DEFTET_LAUNCH(k_subdiv_flags, grid_for(T), dim3(256), st, subdiv_sig, T, L.keepOld, L.split);
+    TRY(ex_scan(L.scan, L.keepOld, L.posOld, (size_t)T, st));
+    TRY(ex_scan(L.scan, L.split, L.posSplit, (size_t)T, st));
     DEFTET_LAUNCH(k_subdiv_tets, grid_for(T), dim3(256), st, (const long long *)tet, (const long long *)tet_edge_tx6, subdiv_sig,
-                  posOld, posSplit, T, n_point, (long long *)tet_new, n_tet_new);
+                  L.posOld, L.posSplit, T, n_point, (long long *)tet_new, n_tet_new);
     return DEFTET_OK;
 }
 
@@ -873,12 +1001,11 @@ extern "C" int deftet_delete_tet_i64(const int64_t *tet, const float *weights_tx
     if (T == 0) { DEFTET_HIP(hipMemsetAsync(n_kept, 0, 4, st)); return DEFTET_OK; }
     DEFTET_CHECK_ARG(tet && tet_kept && (K == 0 || weights_txk), "null pointer");
     DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0, "workspace null or not 256-byte aligned");
-    Ws W(workspace, wsb);
-    int *keep = W.A.take<int>(T), *pos = W.A.take<int>(T);
-    DEFTET_CHECK_ARG(W.A.ok(), "workspace too small");
-    DEFTET_LAUNCH(k_delete_flags, grid_for(T), dim3(256), st, weights_txk, T, K, thres, keep);
-    TRY(ex_scan(W, keep, pos, (size_t)T, st));
-    DEFTET_LAUNCH(k_compact_tets, grid_for(T), dim3(256), st, (const long long *)tet, keep, pos, T, (long long *)tet_kept, n_kept);
+    const DeleteLayout L = delete_layout(T, workspace);
+    DEFTET_CHECK_ARG(L.bytes <= wsb, "workspace too small");
+    DEFTET_LAUNCH(k_delete_flags, grid_for(T), dim3(256), st, weights_txk, T, K, thres, L.keep);
+    TRY(ex_scan(L.scan, L.keep, L.pos, (size_t)T, st));
+    DEFTET_LAUNCH(k_compact_tets, grid_for(T), dim3(256), st, (const long long *)tet, L.keep, L.pos, T, (long long *)tet_kept, n_kept);
     return DEFTET_OK;
 }
 

@@ -62,11 +62,14 @@ void prof_end(hipStream_t st);
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// bump allocator over the caller's workspace
+// bump allocator over the caller's workspace.  Over a null base it only measures: a layout function runs once that way for the
+// *_workspace_bytes value and once over the real pointer for the arrays, so the two cannot disagree ("Workspaces").
 struct Arena {
     char *base;
     size_t off, cap;
     Arena(void *p, size_t bytes) : base(static_cast<char *>(p)), off(0), cap(bytes) {}
+    explicit Arena(void *p) : Arena(p, ~(size_t)0) {}                 // no capacity of its own: the caller compares end() with what it was given
+    size_t end() const { return align_up(off, 256); }                // bytes of the layout so far, whole 256-byte lines
     template <typename T>
     T *take(size_t n) {
         off = align_up(off, 256);

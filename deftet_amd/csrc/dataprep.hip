@@ -523,14 +523,57 @@ struct SurfWs {
 static SurfWs surf_carve(void *ws, int B, int R)
 {
     const size_t nf = (size_t)B * R * R * words_of(R) + 1, nv = (size_t)B * (R + 1) * (R + 1) * words_of(R + 1) + 1;
-    Arena A(ws, (size_t)-1);
+    Arena A(ws);
     SurfWs s;
     s.fpos = A.take<int>(nf);
     s.vpos = A.take<int>(nv);
     s.used = A.take<unsigned>(nv);
     s.tmp_bytes = prims::scan_temp_bytes<int>(nf > nv ? nf : nv);
     s.tmp = A.take<char>(s.tmp_bytes);
-    s.total = align_up(A.off, 256);
+    s.total = A.end();
+    return s;
+}
+
+// the frame of every shape, the wave tasks of every triangle (scanned in place; the last entry becomes the total)
+struct VoxWs {
+    float4 *os;
+    int *tpos;
+    void *tmp;
+    size_t n, tmp_bytes, total;
+};
+static VoxWs vox_carve(void *ws, int B, int F)
+{
+    Arena A(ws);
+    VoxWs s;
+    s.n = (size_t)B * F + 1;
+    s.os = A.take<float4>(B);
+    s.tpos = A.take<int>(s.n);
+    s.tmp_bytes = prims::scan_temp_bytes<int>(s.n);
+    s.tmp = A.take<char>(s.tmp_bytes);
+    s.total = A.end();
+    return s;
+}
+
+// the six directed edge keys of every face before and after the sort, the heads' flags (scanned in place; entry n is the count)
+struct EdgeWs {
+    unsigned long long *k0, *k1;
+    int *pos;
+    void *scan_tmp, *sort_tmp;
+    size_t n, scan_bytes, sort_bytes, total;
+};
+static EdgeWs edge_carve(void *ws, int F)
+{
+    Arena A(ws);
+    EdgeWs s;
+    s.n = (size_t)F * 6;
+    s.k0 = A.take<unsigned long long>(s.n);
+    s.k1 = A.take<unsigned long long>(s.n);
+    s.pos = A.take<int>(s.n + 1);
+    s.scan_bytes = prims::scan_temp_bytes<int>(s.n + 1);
+    s.scan_tmp = A.take<char>(s.scan_bytes);
+    s.sort_bytes = prims::radix_sort_temp_bytes<unsigned long long, unsigned>(s.n, false);
+    s.sort_tmp = A.take<char>(s.sort_bytes);
+    s.total = A.end();
     return s;
 }
 
@@ -542,9 +585,7 @@ using namespace deftet::dp;
 
 extern "C" size_t deftet_mesh_voxelize_workspace_bytes(int B, int F)
 {
-    if (B <= 0 || F < 0) return 256;
-    const size_t n = (size_t)B * F + 1;
-    return align_up((size_t)B * 16, 256) + align_up(n * 4, 256) + prims::scan_temp_bytes<int>(n) + 256;
+    return B <= 0 || F < 0 ? 256 : vox_carve(nullptr, B, F).total;
 }
 
 extern "C" int deftet_mesh_voxelize_f32(const float *verts, const int64_t *faces, const float *origin, const float *scale, int B, int V,
@@ -567,23 +608,20 @@ extern "C" int deftet_mesh_voxelize_f32(const float *verts, const int64_t *faces
     DEFTET_CHECK_ARG(bits && stats, "null pointer: bits / stats");
     DEFTET_CHECK_ARG(F == 0 || (verts && faces && V > 0), "null pointer: verts / faces");
     DEFTET_CHECK_ARG(V > 0 || (origin && scale), "no vertices: origin and scale cannot be derived");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && wsb >= deftet_mesh_voxelize_workspace_bytes(B, F),
+    const VoxWs S = vox_carve(workspace, B, F);
+    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && S.total <= wsb,
                      "workspace null, misaligned or smaller than deftet_mesh_voxelize_workspace_bytes");
     hipStream_t st = as_stream(stream_);
     const int W = words_of(R);
-    const size_t nword = (size_t)B * R * R * W, n = (size_t)B * F + 1;
+    const size_t nword = (size_t)B * R * R * W, n = S.n;
     DEFTET_HIP(hipMemsetAsync(bits, 0, nword * 4, st));
     DEFTET_HIP(hipMemsetAsync(stats, 0, 16, st));
     if (F > 0) {
-        Arena A(workspace, wsb);
-        float4 *os = A.take<float4>(B);
-        int *tpos = A.take<int>(n);
-        void *tmp = A.take<char>(prims::scan_temp_bytes<int>(n));
-        DEFTET_LAUNCH(k_vx_frame, dim3(B), dim3(kThreads), st, verts, V, origin, scale, os);
-        DEFTET_LAUNCH(k_vx_count, dim3(grid_for(n)), dim3(kThreads), st, verts, (const long long *)faces, (const float4 *)os, B, V, F, R, tpos,
+        DEFTET_LAUNCH(k_vx_frame, dim3(B), dim3(kThreads), st, verts, V, origin, scale, S.os);
+        DEFTET_LAUNCH(k_vx_count, dim3(grid_for(n)), dim3(kThreads), st, verts, (const long long *)faces, (const float4 *)S.os, B, V, F, R, S.tpos,
                       (int *)stats);
         {
-            const int rc = prims::scan<int, prims::Plus, true>(tpos, tpos, n, 0, prims::Plus(), tmp, prims::scan_temp_bytes<int>(n), st);
+            const int rc = prims::scan<int, prims::Plus, true>(S.tpos, S.tpos, n, 0, prims::Plus(), S.tmp, S.tmp_bytes, st);
             if (rc != DEFTET_OK) return rc;
         }
         // the number of tasks stays on the device, so the grid cannot follow it: one wave per triangle, but never fewer than
@@ -591,8 +629,8 @@ extern "C" int deftet_mesh_voxelize_f32(const float *verts, const int64_t *faces
         // and never more than a full machine of waves; the waves stride over the tasks
         const size_t want = (n - 1 + 3) / 4;
         const unsigned nblk = (unsigned)(want < kMinRasterBlocks ? kMinRasterBlocks : (want < 8192 ? want : 8192));
-        DEFTET_LAUNCH(k_vx_raster, dim3(nblk), dim3(kThreads), st, verts, (const long long *)faces, (const float4 *)os, B, V, F, R, W,
-                      (const int *)tpos, (unsigned *)bits, (int *)stats);
+        DEFTET_LAUNCH(k_vx_raster, dim3(nblk), dim3(kThreads), st, verts, (const long long *)faces, (const float4 *)S.os, B, V, F, R, W,
+                      (const int *)S.tpos, (unsigned *)bits, (int *)stats);
     }
     if (vox) DEFTET_LAUNCH(k_unpack, dim3(grid_for((size_t)B * R * R * R)), dim3(kThreads), st, (const unsigned *)bits, (size_t)B * R * R * R, R, W, vox);
     return DEFTET_OK;
@@ -726,10 +764,7 @@ extern "C" int deftet_voxel_surface_fill_b32(const uint32_t *bits, int B, int R,
 
 extern "C" size_t deftet_face_edges_workspace_bytes(int F)
 {
-    if (F <= 0) return 256;
-    const size_t n = (size_t)F * 6;
-    return 2 * align_up(n * 8, 256) + align_up((n + 1) * 4, 256) + prims::scan_temp_bytes<int>(n + 1) +
-           prims::radix_sort_temp_bytes<unsigned long long, unsigned>(n, false) + 256;
+    return F <= 0 ? 256 : edge_carve(nullptr, F).total;
 }
 
 extern "C" int deftet_face_edges_i32(const int64_t *faces, int F, int V, int32_t *pairs, int32_t *n_out, void *workspace, size_t wsb,
@@ -739,27 +774,22 @@ extern "C" int deftet_face_edges_i32(const int64_t *faces, int F, int V, int32_t
     DEFTET_CHECK_ARG(V > 0, "n_vertex=%d must be positive", V);
     DEFTET_CHECK_ARG(n_out, "null pointer: n_out");
     hipStream_t st = as_stream(stream_);
+    const EdgeWs S = edge_carve(workspace, F);
+    DEFTET_CHECK_ARG(F == 0 || (faces && pairs), "null pointer: faces / pairs");
+    DEFTET_CHECK_ARG(F == 0 || (workspace && ((uintptr_t)workspace & 255) == 0 && S.total <= wsb),
+                     "workspace null, misaligned or smaller than deftet_face_edges_workspace_bytes");
     DEFTET_HIP(hipMemsetAsync(n_out, 0, 8, st));
     if (F == 0) return DEFTET_OK;
-    DEFTET_CHECK_ARG(faces && pairs, "null pointer: faces / pairs");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && wsb >= deftet_face_edges_workspace_bytes(F),
-                     "workspace null, misaligned or smaller than deftet_face_edges_workspace_bytes");
-    const size_t n = (size_t)F * 6;
-    Arena A(workspace, wsb);
-    unsigned long long *k0 = A.take<unsigned long long>(n), *k1 = A.take<unsigned long long>(n);
-    int *pos = A.take<int>(n + 1);
-    const size_t scan_b = prims::scan_temp_bytes<int>(n + 1), sort_b = prims::radix_sort_temp_bytes<unsigned long long, unsigned>(n, false);
-    void *scan_tmp = A.take<char>(scan_b);
-    void *sort_tmp = A.take<char>(sort_b);
+    const size_t n = S.n;
     int bits = 1;
     while (bits < 64 && ((unsigned long long)V * (unsigned long long)V) >> bits) ++bits;       // the sentinel V^2 must sort last
-    DEFTET_LAUNCH(k_edge_keys, dim3(grid_for(n)), dim3(kThreads), st, (const long long *)faces, (long long)n, V, k0, (int *)n_out);
-    int rc = prims::radix_sort_keys<unsigned long long>(k0, k1, n, bits, sort_tmp, sort_b, st);
+    DEFTET_LAUNCH(k_edge_keys, dim3(grid_for(n)), dim3(kThreads), st, (const long long *)faces, (long long)n, V, S.k0, (int *)n_out);
+    int rc = prims::radix_sort_keys<unsigned long long>(S.k0, S.k1, n, bits, S.sort_tmp, S.sort_bytes, st);
     if (rc != DEFTET_OK) return rc;
-    DEFTET_LAUNCH(k_edge_flag, dim3(grid_for(n + 1)), dim3(kThreads), st, (const unsigned long long *)k1, (long long)n, V, pos);
-    rc = prims::scan<int, prims::Plus, true>(pos, pos, n + 1, 0, prims::Plus(), scan_tmp, scan_b, st);
+    DEFTET_LAUNCH(k_edge_flag, dim3(grid_for(n + 1)), dim3(kThreads), st, (const unsigned long long *)S.k1, (long long)n, V, S.pos);
+    rc = prims::scan<int, prims::Plus, true>(S.pos, S.pos, n + 1, 0, prims::Plus(), S.scan_tmp, S.scan_bytes, st);
     if (rc != DEFTET_OK) return rc;
-    DEFTET_LAUNCH(k_edge_compact, dim3(grid_for(n + 1)), dim3(kThreads), st, (const unsigned long long *)k1, (long long)n, V, (const int *)pos,
+    DEFTET_LAUNCH(k_edge_compact, dim3(grid_for(n + 1)), dim3(kThreads), st, (const unsigned long long *)S.k1, (long long)n, V, (const int *)S.pos,
                   (int *)pairs, (int *)n_out);
     return DEFTET_OK;
 }

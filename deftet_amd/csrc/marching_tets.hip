@@ -207,14 +207,34 @@ __global__ __launch_bounds__(kThreads) void k_mt_bwd(Shape s, const float *__res
 
 static inline size_t n_count(int B, int T, int E) { return (size_t)B * E + (size_t)B * T + 1; }
 
-static int check_shape(int B, int V, int T, int E, float iso, const void *workspace, size_t wsb)
+// the counts of every (shape, edge) and (shape, tet), scanned in place: the count entry writes them, the fill entry reads them
+struct Layout {
+    size_t bytes, n, scanTmpBytes;
+    int *cnt;
+    void *scanTmp;
+};
+
+static Layout make_layout(int B, int T, int E, void *ws)
+{
+    Layout L{};
+    L.n = n_count(B, T, E);
+    Arena A(ws);
+    L.cnt = A.take<int>(L.n);
+    L.scanTmpBytes = prims::scan_temp_bytes<int>(L.n);
+    L.scanTmp = A.take<char>(L.scanTmpBytes);
+    L.bytes = A.end();
+    return L;
+}
+
+static int check_shape(int B, int V, int T, int E, float iso, void *workspace, size_t wsb, Layout &L)
 {
     DEFTET_CHECK_ARG(B > 0 && T > 0 && E > 0 && V > 0, "n_batch=%d, n_vertex=%d, n_tet=%d, n_edge=%d must be positive", B, V, T, E);
     DEFTET_CHECK_ARG(iso == iso && iso - iso == 0.0f, "iso is not finite");
     DEFTET_CHECK_ARG((long long)B * E < 2147483648LL && (long long)B * T < 2147483648LL, "n_batch * n_edge or n_batch * n_tet does not fit 31 bits");
     DEFTET_CHECK_ARG((long long)B * E + 2LL * B * T < 2147483647LL && (long long)B * V < 2147483648LL,
                      "n_batch * (n_edge + 2 n_tet) or n_batch * n_vertex does not fit 31 bits");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && wsb >= deftet_marching_tets_workspace_bytes(B, T, E),
+    L = make_layout(B, T, E, workspace);
+    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && L.bytes <= wsb,
                      "workspace null, misaligned or smaller than deftet_marching_tets_workspace_bytes");
     return DEFTET_OK;
 }
@@ -238,33 +258,30 @@ extern "C" int deftet_edge_vertex_csr_i32(const int64_t *edges_ex2, int32_t *off
 
 extern "C" size_t deftet_marching_tets_workspace_bytes(int B, int T, int E)
 {
-    if (B <= 0 || T <= 0 || E <= 0) return 256;
-    const size_t n = n_count(B, T, E);
-    return align_up(n * 4, 256) + prims::scan_temp_bytes<int>(n);
+    return B <= 0 || T <= 0 || E <= 0 ? 256 : make_layout(B, T, E, nullptr).bytes;
 }
 
 extern "C" int deftet_marching_tets_count_f32(const float *field_bxv, const int32_t *edges_ex2, const int32_t *tet_idx_tx4, int B, int V,
                                               int T, int E, float iso, int32_t *edge_vertex_bxe, int32_t *offsets_2xb1, void *workspace,
                                               size_t wsb, void *stream_)
 {
+    Layout L;
     {
-        const int rc = check_shape(B, V, T, E, iso, workspace, wsb);
+        const int rc = check_shape(B, V, T, E, iso, workspace, wsb, L);
         if (rc != DEFTET_OK) return rc;
     }
     DEFTET_CHECK_ARG(field_bxv && edges_ex2 && tet_idx_tx4 && edge_vertex_bxe && offsets_2xb1, "null pointer");
     DEFTET_CHECK_ARG(((uintptr_t)edges_ex2 & 7) == 0 && ((uintptr_t)tet_idx_tx4 & 15) == 0, "misaligned edges_ex2 / tet_idx_tx4");
     hipStream_t st = as_stream(stream_);
-    const size_t n = n_count(B, T, E);
-    int *cnt = static_cast<int *>(workspace);
-    void *tmp = static_cast<char *>(workspace) + align_up(n * 4, 256);
+    const size_t n = L.n;
     const Shape s{field_bxv, (const int2 *)edges_ex2, (const int4 *)tet_idx_tx4, B, V, T, E, iso};
-    DEFTET_LAUNCH(k_mt_count, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), st, s, cnt);
+    DEFTET_LAUNCH(k_mt_count, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), st, s, L.cnt);
     {
-        const int rc = prims::scan<int, prims::Plus, true>(cnt, cnt, n, 0, prims::Plus(), tmp, prims::scan_temp_bytes<int>(n), st);
+        const int rc = prims::scan<int, prims::Plus, true>(L.cnt, L.cnt, n, 0, prims::Plus(), L.scanTmp, L.scanTmpBytes, st);
         if (rc != DEFTET_OK) return rc;
     }
     const size_t nf = (size_t)B * E > (size_t)B + 1 ? (size_t)B * E : (size_t)B + 1;
-    DEFTET_LAUNCH(k_mt_finish, dim3((unsigned)((nf + kThreads - 1) / kThreads)), dim3(kThreads), st, (const int *)cnt, B, T, E, edge_vertex_bxe,
+    DEFTET_LAUNCH(k_mt_finish, dim3((unsigned)((nf + kThreads - 1) / kThreads)), dim3(kThreads), st, (const int *)L.cnt, B, T, E, edge_vertex_bxe,
                   offsets_2xb1);
     return DEFTET_OK;
 }
@@ -275,8 +292,9 @@ extern "C" int deftet_marching_tets_fill_f32(const float *pos_bxvx3, const float
                                              long long n_face, float *verts, float *vert_attr, int64_t *faces, int64_t *edge_id, float *t,
                                              int64_t *tet_id, void *workspace, size_t wsb, void *stream_)
 {
+    Layout L;
     {
-        const int rc = check_shape(B, V, T, E, iso, workspace, wsb);
+        const int rc = check_shape(B, V, T, E, iso, workspace, wsb, L);
         if (rc != DEFTET_OK) return rc;
     }
     DEFTET_CHECK_ARG(C >= 0 && C <= 8 && (attr_bxvxc == nullptr) == (C == 0), "n_attr=%d outside 0..8, or attr_bxvxc does not go with it", C);
@@ -286,11 +304,11 @@ extern "C" int deftet_marching_tets_fill_f32(const float *pos_bxvx3, const float
     if (n_vert == 0 && n_face == 0) return DEFTET_OK;                  // (no row: the outputs may be empty, hence null)
     DEFTET_CHECK_ARG(verts && faces && (attr_bxvxc == nullptr) == (vert_attr == nullptr), "null output, or attr_bxvxc and vert_attr do not go together");
     hipStream_t st = as_stream(stream_);
-    const size_t n = n_count(B, T, E);
+    const size_t n = L.n;
     const Shape s{field_bxv, (const int2 *)edges_ex2, (const int4 *)tet_idx_tx4, B, V, T, E, iso};
     const Out o{pos_bxvx3, attr_bxvxc, tet_edge_tx6, edge_vertex_bxe, verts, vert_attr, (long long *)faces, (long long *)edge_id, t,
                 (long long *)tet_id, n_vert, n_face, C};
-    DEFTET_LAUNCH(k_mt_fill, dim3((unsigned)((n - 1 + kThreads - 1) / kThreads)), dim3(kThreads), st, s, o, (const int *)workspace);
+    DEFTET_LAUNCH(k_mt_fill, dim3((unsigned)((n - 1 + kThreads - 1) / kThreads)), dim3(kThreads), st, s, o, (const int *)L.cnt);
     return DEFTET_OK;
 }
 

@@ -545,7 +545,7 @@ struct PMSlices {
 };
 static size_t pm_layout(int B, int F, void *base, PMSlices *s)
 {
-    Arena ar(base, (size_t)-1);
+    Arena ar(base);
     const size_t nc = (size_t)B * kPCells;
     PMSlices t;
     t.grids = ar.take<PGrid>(B);
@@ -560,6 +560,24 @@ static size_t pm_layout(int B, int F, void *base, PMSlices *s)
     t.scan_ws = ar.take<char>(t.scan_bytes);
     if (s) *s = t;
     return ar.off + 256;
+}
+
+// areas, their quantised tickets (scanned in place), the largest area per shape
+struct SampLayout {
+    float *a; long long *cum; unsigned *amax; void *scan_ws; size_t scan_bytes, bytes;
+};
+static SampLayout samp_layout(int B, int F, void *base)
+{
+    SampLayout L{};
+    Arena ar(base);
+    const size_t n = (size_t)B * F;
+    L.a = ar.take<float>(n);
+    L.cum = ar.take<long long>(n);
+    L.amax = ar.take<unsigned>(B);
+    L.scan_bytes = deftet_scan_workspace_bytes((long long)n, 8);
+    L.scan_ws = ar.take<char>(L.scan_bytes);
+    L.bytes = ar.end();
+    return L;
 }
 
 }  // namespace met
@@ -628,10 +646,7 @@ extern "C" int deftet_point_mesh_distance_scan_f32(const float *pts, const float
 
 extern "C" size_t deftet_sample_points_workspace_bytes(int n_batch, int n_face)
 {
-    if (n_batch < 0 || n_face < 0) return 0;
-    const size_t n = (size_t)n_batch * n_face;
-    return align_up(n * 4, 256) + align_up(n * 8, 256) + align_up((size_t)n_batch * 4, 256) +
-           align_up(deftet_scan_workspace_bytes((long long)n, 8), 256) + 256;
+    return n_batch < 0 || n_face < 0 ? 0 : met::samp_layout(n_batch, n_face, nullptr).bytes;
 }
 
 extern "C" int deftet_sample_points_f32(const float *face, const float *areas, const int32_t *n_face, const float *uniforms, int B, int F,
@@ -644,27 +659,21 @@ extern "C" int deftet_sample_points_f32(const float *face, const float *areas, c
     DEFTET_CHECK_ARG(met::aligned(face, 4) && met::aligned(areas, 4) && met::aligned(n_face, 4) && met::aligned(uniforms, 4) &&
                          met::aligned(points, 4) && met::aligned(face_choice, 8) && met::aligned(empty_flag, 4),
                      "misaligned pointer");
-    DEFTET_CHECK_ARG(workspace && met::aligned(workspace, 256) && workspace_bytes >= deftet_sample_points_workspace_bytes(B, F),
-                     "workspace null, misaligned or too small");
+    const met::SampLayout L = met::samp_layout(B, F, workspace);
+    DEFTET_CHECK_ARG(workspace && met::aligned(workspace, 256) && L.bytes <= workspace_bytes, "workspace null, misaligned or too small");
     hipStream_t st = as_stream(stream_);
     const size_t n = (size_t)B * F;
-    Arena ar(workspace, workspace_bytes);
-    float *a = ar.take<float>(n);
-    long long *cum = ar.take<long long>(n);
-    unsigned *amax = ar.take<unsigned>(B);
-    const size_t sb = deftet_scan_workspace_bytes((long long)n, 8);
-    void *sws = ar.take<char>(sb);
     DEFTET_HIP(hipMemsetAsync(empty_flag, 0, (size_t)B * 4, st));
-    DEFTET_HIP(hipMemsetAsync(amax, 0, (size_t)B * 4, st));
+    DEFTET_HIP(hipMemsetAsync(L.amax, 0, (size_t)B * 4, st));
     if (F > 0) {
         const dim3 fg((F + 255) / 256, B);
-        DEFTET_LAUNCH(met::k_samp_area, fg, dim3(256), st, face, areas, (const int *)n_face, F, a, amax);
-        DEFTET_LAUNCH(met::k_samp_quant, fg, dim3(256), st, a, amax, F, cum);
-        const int src = deftet_scan(cum, cum, (long long)n, 8, 1, sws, sb, stream_);
+        DEFTET_LAUNCH(met::k_samp_area, fg, dim3(256), st, face, areas, (const int *)n_face, F, L.a, L.amax);
+        DEFTET_LAUNCH(met::k_samp_quant, fg, dim3(256), st, L.a, L.amax, F, L.cum);
+        const int src = deftet_scan(L.cum, L.cum, (long long)n, 8, 1, L.scan_ws, L.scan_bytes, stream_);
         if (src != DEFTET_OK) return src;
     }
     if (N > 0)
-        DEFTET_LAUNCH(met::k_samp_points, dim3((N + 255) / 256, B), dim3(256), st, F > 0 ? face : uniforms, cum, uniforms, F, N, points,
+        DEFTET_LAUNCH(met::k_samp_points, dim3((N + 255) / 256, B), dim3(256), st, F > 0 ? face : uniforms, L.cum, uniforms, F, N, points,
                       (long long *)face_choice, (int *)empty_flag);
     return DEFTET_OK;
 }

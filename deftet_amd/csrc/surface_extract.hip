@@ -242,8 +242,6 @@ __global__ __launch_bounds__(256) void k_weld_remap(const long long *__restrict_
     faces_out[e] = (v < 0 || v >= V) ? -1 : (long long)pos[v];
 }
 
-static inline size_t scan_bytes(size_t n) { return prims::scan_temp_bytes<int>(n); }
-
 }  // namespace sx
 }  // namespace deftet
 
@@ -268,33 +266,46 @@ extern "C" int deftet_tet_face_neighbours_i64(const int64_t *tetidx_fx2, const i
 
 static inline int sx_nblk(int T) { return (T + kThreads - 1) / kThreads; }
 
-extern "C" size_t deftet_surface_extract_workspace_bytes(int B, int T, int with_vertex_weights)
-{
-    if (B <= 0 || T <= 0) return 256;
-    const size_t n = (size_t)B * sx_nblk(T) + 1;
-    return 256 + align_up(n * 4, 256) + scan_bytes(n) + (with_vertex_weights ? align_up((size_t)B * T * 4, 256) : 0);
-}
-
 namespace {
+// state: the bad flag and which occupancy the count pass ran on (k_sx_offsets); pos: faces per workgroup, scanned in place;
+// occ: the occupancy the count pass derives from vertex weights, kept for the fill pass
 struct Ws {
     int *bad, *pos;
     void *tmp;
-    size_t tmp_bytes;
+    size_t n, tmp_bytes, bytes;
     float *occ;
 };
-Ws carve(void *workspace, int B, int T)
+Ws carve(void *workspace, int B, int T, int with_vertex_weights)
 {
-    const size_t n = (size_t)B * sx_nblk(T) + 1;
-    char *p = static_cast<char *>(workspace);
-    Ws w;
-    w.bad = reinterpret_cast<int *>(p);
-    w.pos = reinterpret_cast<int *>(p + 256);
-    w.tmp = p + 256 + align_up(n * 4, 256);
-    w.tmp_bytes = scan_bytes(n);
-    w.occ = reinterpret_cast<float *>(p + 256 + align_up(n * 4, 256) + scan_bytes(n));
+    Arena A(workspace);
+    Ws w{};
+    w.n = (size_t)B * sx_nblk(T) + 1;
+    w.bad = A.take<int>(2);
+    w.pos = A.take<int>(w.n);
+    w.tmp_bytes = prims::scan_temp_bytes<int>(w.n);
+    w.tmp = A.take<char>(w.tmp_bytes);
+    if (with_vertex_weights) w.occ = A.take<float>((size_t)B * T);
+    w.bytes = A.end();
     return w;
 }
-int check_shape(int B, int T, int mode, double htres, const void *nbr, void *workspace, size_t wsb, int with_w)
+
+// flag: one word per vertex and one behind them, scanned in place into the new ids and their count
+struct WeldWs {
+    int *flag;
+    void *tmp;
+    size_t tmp_bytes, bytes;
+};
+WeldWs weld_carve(void *workspace, int V)
+{
+    Arena A(workspace);
+    WeldWs w{};
+    w.flag = A.take<int>((size_t)V + 1);
+    w.tmp_bytes = prims::scan_temp_bytes<int>((size_t)V + 1);
+    w.tmp = A.take<char>(w.tmp_bytes);
+    w.bytes = A.end();
+    return w;
+}
+int check_shape(int B, int T, int mode, double htres, const void *nbr, void *workspace, size_t wsb, int with_w, Ws &W)
 {
     DEFTET_CHECK_ARG(T > 0, "n_tet=%d must be positive", T);
     DEFTET_CHECK_ARG(B > 0 && B <= 65535, "n_batch=%d outside 1..65535", B);
@@ -302,19 +313,26 @@ int check_shape(int B, int T, int mode, double htres, const void *nbr, void *wor
     DEFTET_CHECK_ARG(mode == DEFTET_SX_BINARY || mode == DEFTET_SX_THRESHOLD, "mode=%d is neither DEFTET_SX_BINARY nor DEFTET_SX_THRESHOLD", mode);
     DEFTET_CHECK_ARG(mode == DEFTET_SX_BINARY || htres == htres, "htres is NaN");
     DEFTET_CHECK_ARG(nbr && ((uintptr_t)nbr & 15) == 0, "null or misaligned pointer: nbr32_tx4");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && wsb >= deftet_surface_extract_workspace_bytes(B, T, with_w),
+    W = carve(workspace, B, T, with_w);
+    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && W.bytes <= wsb,
                      "workspace null, misaligned or smaller than deftet_surface_extract_workspace_bytes");
     return DEFTET_OK;
 }
 }  // namespace
+
+extern "C" size_t deftet_surface_extract_workspace_bytes(int B, int T, int with_vertex_weights)
+{
+    return B <= 0 || T <= 0 ? 256 : carve(nullptr, B, T, with_vertex_weights).bytes;
+}
 
 extern "C" int deftet_surface_extract_count_f32(const float *occ_bxt, const float *weights_bxv, const int32_t *tet_idx_tx4, int V,
                                                 const int32_t *nbr32_tx4, int B, int T, int mode, double htres, int32_t *offsets,
                                                 void *workspace, size_t wsb, void *stream_)
 {
     const int with_w = weights_bxv != nullptr;
+    Ws W;
     {
-        const int rc = check_shape(B, T, mode, htres, nbr32_tx4, workspace, wsb, with_w);
+        const int rc = check_shape(B, T, mode, htres, nbr32_tx4, workspace, wsb, with_w, W);
         if (rc != DEFTET_OK) return rc;
     }
     DEFTET_CHECK_ARG(offsets, "null pointer: offsets");
@@ -322,16 +340,14 @@ extern "C" int deftet_surface_extract_count_f32(const float *occ_bxt, const floa
     DEFTET_CHECK_ARG(!with_w || (tet_idx_tx4 && ((uintptr_t)tet_idx_tx4 & 15) == 0 && V > 0),
                      "vertex weights need a 16-byte aligned tet_idx_tx4 and n_vertex > 0");
     hipStream_t st = as_stream(stream_);
-    const Ws W = carve(workspace, B, T);
     const int nblk = sx_nblk(T);
     DEFTET_HIP(hipMemsetAsync(W.bad, 0, 4, st));
     if (with_w)
         DEFTET_LAUNCH(k_sx_occ_max, dim3((T + 255) / 256, B), dim3(256), st, weights_bxv, (const int4 *)tet_idx_tx4, V, T, W.occ, W.bad);
     Pred p{(const int4 *)nbr32_tx4, with_w ? W.occ : occ_bxt, T, mode, htres, (float)(htres * 2.0)};
     DEFTET_LAUNCH(k_sx_count, dim3(nblk, B), dim3(kThreads), st, p, nblk, B, W.pos, W.bad);
-    const size_t n = (size_t)B * nblk + 1;
     {
-        const int rc = prims::scan<int, prims::Plus, true>(W.pos, W.pos, n, 0, prims::Plus(), W.tmp, W.tmp_bytes, st);
+        const int rc = prims::scan<int, prims::Plus, true>(W.pos, W.pos, W.n, 0, prims::Plus(), W.tmp, W.tmp_bytes, st);
         if (rc != DEFTET_OK) return rc;
     }
     DEFTET_LAUNCH(k_sx_offsets, dim3((B + 256) / 256), dim3(256), st, (const int *)W.pos, nblk, B, W.bad, with_w ? kOccFused : kOccGiven, offsets);
@@ -344,8 +360,9 @@ extern "C" int deftet_surface_extract_fill_f32(const float *tet_bxtx4x3, const f
                                                int64_t *faces, void *workspace, size_t wsb, void *stream_)
 {
     const int with_w = occ_bxt == nullptr;                             // the count pass left the fused occupancy in the workspace
+    Ws W;
     {
-        const int rc = check_shape(B, T, mode, htres, nbr32_tx4, workspace, wsb, with_w);
+        const int rc = check_shape(B, T, mode, htres, nbr32_tx4, workspace, wsb, with_w, W);
         if (rc != DEFTET_OK) return rc;
     }
     DEFTET_CHECK_ARG(capacity >= 0, "negative capacity");
@@ -355,7 +372,6 @@ extern "C" int deftet_surface_extract_fill_f32(const float *tet_bxtx4x3, const f
     DEFTET_CHECK_ARG((attr_bxtx4xc != nullptr) == (face_attr != nullptr), "attr_bxtx4xc and face_attr go together");
     DEFTET_CHECK_ARG(tet_bxtx4x3 && face, "null pointer: tet_bxtx4x3 / face");
     hipStream_t st = as_stream(stream_);
-    const Ws W = carve(workspace, B, T);
     const int nblk = sx_nblk(T);
     Pred p{(const int4 *)nbr32_tx4, with_w ? W.occ : occ_bxt, T, mode, htres, (float)(htres * 2.0)};
     Out o{tet_bxtx4x3, attr_bxtx4xc, tet_idx_tx4, face, face_attr, (long long *)index, (long long *)faces, capacity, C};
@@ -365,8 +381,7 @@ extern "C" int deftet_surface_extract_fill_f32(const float *tet_bxtx4x3, const f
 
 extern "C" size_t deftet_surface_weld_workspace_bytes(int V)
 {
-    if (V <= 0) return 256;
-    return align_up(((size_t)V + 1) * 4, 256) + scan_bytes((size_t)V + 1) + 256;
+    return V <= 0 ? 256 : weld_carve(nullptr, V).bytes;
 }
 
 extern "C" int deftet_surface_weld_f32(const int64_t *faces_fx3, long long n_face, const float *verts_vx3, const float *attr_vxc, int C,
@@ -384,21 +399,20 @@ extern "C" int deftet_surface_weld_f32(const int64_t *faces_fx3, long long n_fac
     DEFTET_CHECK_ARG(faces_fx3 && verts_vx3 && old_id && verts_out && faces_out, "null pointer");
     DEFTET_CHECK_ARG((long long)capacity >= (n_face * 3 < (long long)V ? n_face * 3 : (long long)V),
                      "capacity=%d below min(n_vertex, 3 n_face)", capacity);
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && wsb >= deftet_surface_weld_workspace_bytes(V),
+    const WeldWs W = weld_carve(workspace, V);
+    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && W.bytes <= wsb,
                      "workspace null, misaligned or smaller than deftet_surface_weld_workspace_bytes");
-    int *flag = static_cast<int *>(workspace);
-    void *tmp = static_cast<char *>(workspace) + align_up(((size_t)V + 1) * 4, 256);
     const long long n = n_face * 3;
-    DEFTET_HIP(hipMemsetAsync(flag, 0, ((size_t)V + 1) * 4, st));
+    DEFTET_HIP(hipMemsetAsync(W.flag, 0, ((size_t)V + 1) * 4, st));
     DEFTET_HIP(hipMemsetAsync(n_out, 0, 8, st));
-    DEFTET_LAUNCH(k_weld_flag, dim3((unsigned)((n + 255) / 256)), dim3(256), st, (const long long *)faces_fx3, n, V, flag, n_out);
+    DEFTET_LAUNCH(k_weld_flag, dim3((unsigned)((n + 255) / 256)), dim3(256), st, (const long long *)faces_fx3, n, V, W.flag, n_out);
     {
-        const int rc = prims::scan<int, prims::Plus, true>(flag, flag, (size_t)V + 1, 0, prims::Plus(), tmp, scan_bytes((size_t)V + 1), st);
+        const int rc = prims::scan<int, prims::Plus, true>(W.flag, W.flag, (size_t)V + 1, 0, prims::Plus(), W.tmp, W.tmp_bytes, st);
         if (rc != DEFTET_OK) return rc;
     }
-    DEFTET_LAUNCH(k_weld_gather, dim3((V + 256) / 256), dim3(256), st, (const int *)flag, verts_vx3, attr_vxc, C, V, capacity,
+    DEFTET_LAUNCH(k_weld_gather, dim3((V + 256) / 256), dim3(256), st, (const int *)W.flag, verts_vx3, attr_vxc, C, V, capacity,
                   (long long *)old_id, verts_out, attr_out, n_out);
-    DEFTET_LAUNCH(k_weld_remap, dim3((unsigned)((n + 255) / 256)), dim3(256), st, (const long long *)faces_fx3, n, V, (const int *)flag,
+    DEFTET_LAUNCH(k_weld_remap, dim3((unsigned)((n + 255) / 256)), dim3(256), st, (const long long *)faces_fx3, n, V, (const int *)W.flag,
                   (long long *)faces_out);
     return DEFTET_OK;
 }

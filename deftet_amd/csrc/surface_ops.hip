@@ -2319,25 +2319,48 @@ static int nn_pick_G(int M)
     return G;
 }
 
-// per-shape scratch of the grid search (one slice per shape of a launch group), and the all-shapes far-key arrays + sort
-// scratch behind the slices
-static size_t nn_slice_bytes(int N, int M)
+// The grid search's workspace for a launch group of nS shapes: one slice of per-shape scratch per shape (the members point into
+// slice 0; the kernels rebase to their shape by `slice` bytes), and behind the slices the far keys / sorted keys / iota / sorted
+// positions of ALL shapes of the group with the sort's temporary.
+struct NNLayout {
+    size_t slice, bytes, sortTmpBytes;
+    float *part;
+    NNGrid *grid;
+    int *cells, *start, *rep;
+    int2 *pcell;
+    float4 *sorted, *repList;
+    int *rowStart, *nRep;
+    unsigned long long *bound;
+    int *nFar;
+    unsigned *farKey, *farKeyS, *iota, *farList;
+    void *sortTmp;
+};
+static NNLayout nn_layout(int nS, int N, int M, void *ws)
 {
+    NNLayout L{};
     const int G = nn_pick_G(M);
-    const size_t nc = (size_t)G * G * G + 1;
-    return align_up(nc * 4 * 3 + (size_t)(M > 0 ? M : 0) * (8 + 16) + (size_t)(N > 0 ? N : 0) * 8 + nc * 8 + nc + 8192 + (size_t)G * G * 4 +
-                        ((size_t)1 << 20), 256);
+    const size_t nc = (size_t)G * G * G + 1, Nn = (size_t)(N > 0 ? N : 0), Mn = (size_t)(M > 0 ? M : 0);
+    Arena A(ws);
+    L.part = A.take<float>(kNNBlocks * 6);
+    L.grid = A.take<NNGrid>(1);
+    L.cells = A.take<int>(nc); L.start = A.take<int>(nc); L.rep = A.take<int>(nc);
+    L.pcell = A.take<int2>(Mn);
+    L.sorted = A.take<float4>(Mn + 64);                                               // k_nn_far reads whole 64-record tiles
+    L.repList = A.take<float4>(nc / (kNNCoarse * kNNCoarse) + 64 + 64);               // >= Gc^3 + pad
+    L.rowStart = A.take<int>((size_t)G * G + 2 * kNNBatch); L.nRep = A.take<int>(4);
+    L.bound = A.take<unsigned long long>(Nn + 1);
+    L.nFar = A.take<int>(4);
+    L.slice = A.end();
+    const size_t nAll = (size_t)nS * (Nn + 1);
+    Arena T(static_cast<char *>(ws) + L.slice * nS);
+    L.farKey = T.take<unsigned>(nAll); L.farKeyS = T.take<unsigned>(nAll); L.iota = T.take<unsigned>(nAll); L.farList = T.take<unsigned>(nAll);
+    L.sortTmpBytes = prims::radix_sort_temp_bytes<unsigned, unsigned>(nAll);
+    L.sortTmp = T.take<char>(L.sortTmpBytes);
+    L.bytes = L.slice * nS + T.end();
+    return L;
 }
-static size_t nn_sort_bytes(int nShapes, int N)
-{
-    const size_t sortTmp = prims::radix_sort_temp_bytes<unsigned, unsigned>((size_t)nShapes * ((size_t)(N > 0 ? N : 0) + 1));
-    return align_up(sortTmp, 256) + 4 * align_up((size_t)nShapes * ((size_t)(N > 0 ? N : 0) + 1) * 4, 256) + 1024;
-}
-extern "C" size_t deftet_nn_index_workspace_bytes(int B, int N, int M)
-{
-    const int g = B < 1 ? 1 : (B < kBatchShapes ? B : kBatchShapes);
-    return nn_slice_bytes(N, M) * (size_t)g + nn_sort_bytes(g, N);
-}
+static int group_shapes(int B) { return B < 1 ? 1 : (B < kBatchShapes ? B : kBatchShapes); }      // the largest launch group of B shapes
+extern "C" size_t deftet_nn_index_workspace_bytes(int B, int N, int M) { return nn_layout(group_shapes(B), N, M, nullptr).bytes; }
 
 __global__ __launch_bounds__(256) void k_iota(unsigned *v, long long n)
 {
@@ -2347,60 +2370,46 @@ __global__ __launch_bounds__(256) void k_iota(unsigned *v, long long n)
 
 // the grid search for a GROUP of nS <= kBatchShapes shapes: one launch per kernel for the whole group
 static int nn_group(const float *queries, const float *points, int32_t *result, int nS, int N, int M, const ShapeCounts &cnt, void *ws,
-                    size_t wsb, hipStream_t st)
+                    hipStream_t st)
 {
     const int G = nn_pick_G(M), keyBits = nn_far_key_bits(G);
-    const size_t nc = (size_t)G * G * G + 1, slice = nn_slice_bytes(N, M);
+    const size_t nc = (size_t)G * G * G + 1;
     int nmax = 0;
     for (int i = 0; i < nS; ++i) nmax = std::max(nmax, cnt.n[i]);
     if (nmax == 0) return DEFTET_OK;
-    Arena A(ws, slice);                                               // layout of slice 0; the kernels rebase to their shape
-    float *part = A.take<float>(kNNBlocks * 6);
-    NNGrid *grid = A.take<NNGrid>(1);
-    int *cells = A.take<int>(nc), *start = A.take<int>(nc), *rep = A.take<int>(nc);
-    int2 *pcell = A.take<int2>(M);
-    float4 *sorted = A.take<float4>((size_t)M + 64);                                  // k_nn_far reads whole 64-record tiles
-    float4 *repList = A.take<float4>(nc / (kNNCoarse * kNNCoarse) + 64 + 64);         // >= Gc^3 + pad
-    int *rowStart = A.take<int>((size_t)G * G + 2 * kNNBatch), *nRep = A.take<int>(4);
-    unsigned long long *bound = A.take<unsigned long long>((size_t)N + 1);
-    int *nFar = A.take<int>(4);
-    if (A.off > slice) return set_error(DEFTET_EINVAL, "nn slice layout exceeds its size");
-    // behind the slices: far keys / sorted keys / iota / sorted positions of ALL shapes of the group, then the sort scratch
+    const NNLayout L = nn_layout(nS, N, M, ws);                       // at most what nn_index_impl checked: a group is no larger than the largest
+    const size_t slice = L.slice;
     const int Nst = N + 1;
     const size_t nAll = (size_t)nS * Nst;
-    Arena T(static_cast<char *>(ws) + slice * nS, wsb - slice * nS);
-    unsigned *farKey = T.take<unsigned>(nAll), *farKeyS = T.take<unsigned>(nAll), *iota = T.take<unsigned>(nAll), *farList = T.take<unsigned>(nAll);
-    void *tmp = T.base + align_up(T.off, 256);
-    const size_t left = (wsb - slice * nS) - align_up(T.off, 256);
     const unsigned shapeShift = (unsigned)keyBits + 1;
     const dim3 blk(256);
-    DEFTET_LAUNCH(k_nn_bbox, dim3(kNNBlocks, nS), blk, st, points, M, part, slice, cells, rep, nRep, (int)nc);
-    DEFTET_LAUNCH(k_nn_grid, dim3(nS), dim3(64), st, (const float *)part, G, grid, slice);
-    DEFTET_LAUNCH(k_nn_bin, dim3((M + 255) / 256, nS), blk, st, points, M, (const NNGrid *)grid, cells, pcell, rep, slice);
-    DEFTET_LAUNCH(k_scan_excl, dim3(scan_tiles(nc), nS), dim3(kScanThreads), st, (const int *)cells, start, (int)nc, slice, 0);
-    DEFTET_LAUNCH(k_nn_scatter, dim3((M + 255) / 256, nS), blk, st, points, M, (const int2 *)pcell, (const int *)start, sorted, slice);
-    DEFTET_LAUNCH(k_nn_query, dim3((Nst + 255) / 256, nS), blk, st, queries, N, (const NNGrid *)grid, (const int *)start,
-                  (const float4 *)sorted, (const int *)rep, points, M, result, farKey, 1u << keyBits, slice, cnt, Nst, shapeShift);
-    DEFTET_LAUNCH(k_iota, dim3((unsigned)((nAll + 255) / 256)), blk, st, iota, (long long)nAll);
+    DEFTET_LAUNCH(k_nn_bbox, dim3(kNNBlocks, nS), blk, st, points, M, L.part, slice, L.cells, L.rep, L.nRep, (int)nc);
+    DEFTET_LAUNCH(k_nn_grid, dim3(nS), dim3(64), st, (const float *)L.part, G, L.grid, slice);
+    DEFTET_LAUNCH(k_nn_bin, dim3((M + 255) / 256, nS), blk, st, points, M, (const NNGrid *)L.grid, L.cells, L.pcell, L.rep, slice);
+    DEFTET_LAUNCH(k_scan_excl, dim3(scan_tiles(nc), nS), dim3(kScanThreads), st, (const int *)L.cells, L.start, (int)nc, slice, 0);
+    DEFTET_LAUNCH(k_nn_scatter, dim3((M + 255) / 256, nS), blk, st, points, M, (const int2 *)L.pcell, (const int *)L.start, L.sorted, slice);
+    DEFTET_LAUNCH(k_nn_query, dim3((Nst + 255) / 256, nS), blk, st, queries, N, (const NNGrid *)L.grid, (const int *)L.start,
+                  (const float4 *)L.sorted, (const int *)L.rep, points, M, result, L.farKey, 1u << keyBits, slice, cnt, Nst, shapeShift);
+    DEFTET_LAUNCH(k_iota, dim3((unsigned)((nAll + 255) / 256)), blk, st, L.iota, (long long)nAll);
     int shapeBitsN = 0;
     while ((1 << shapeBitsN) < nS) ++shapeBitsN;
     {
-        const int rc = prims::radix_sort<unsigned, unsigned>(farKey, farKeyS, iota, reinterpret_cast<unsigned *>(farList), nAll,
-                                                             keyBits + 1 + shapeBitsN, tmp, left, st);
+        const int rc = prims::radix_sort<unsigned, unsigned>(L.farKey, L.farKeyS, L.iota, reinterpret_cast<unsigned *>(L.farList), nAll,
+                                                             keyBits + 1 + shapeBitsN, L.sortTmp, L.sortTmpBytes, st);
         if (rc != DEFTET_OK) return rc;
     }
     const int Gc = (G + kNNCoarse - 1) / kNNCoarse, Gc3 = Gc * Gc * Gc, nt = std::max(Gc3, G * G + 2 * kNNBatch);
-    DEFTET_LAUNCH(k_nn_far_tables, dim3((nt + 255) / 256, nS), blk, st, (const int *)rep, points, Gc3, (const int *)start, G, repList, nRep,
-                  rowStart, sorted, slice, M);
-    DEFTET_LAUNCH(k_nn_far_pad, dim3(nS), dim3(64), st, repList, (const int *)nRep, slice);
-    DEFTET_LAUNCH(k_nn_far_bound, dim3((nmax + 63) / 64, nS), dim3(kFarWaves * 64), st, queries, (const NNGrid *)grid, (const int *)start,
-                  (const float4 *)sorted, (const float4 *)repList, (const int *)nRep, points, N, (const unsigned *)farKeyS,
-                  (const unsigned *)farList, bound, nFar, 1u << keyBits, slice, M, Nst, shapeShift);
-    DEFTET_LAUNCH(k_nn_far_rows, dim3((nmax + 63) / 64, kFarSlices, nS), dim3(kFarWaves * 64), st, queries, (const NNGrid *)grid,
-                  (const int *)start, (const float4 *)sorted, (const int *)rowStart, (const int *)nFar, (const unsigned *)farList, bound, slice,
+    DEFTET_LAUNCH(k_nn_far_tables, dim3((nt + 255) / 256, nS), blk, st, (const int *)L.rep, points, Gc3, (const int *)L.start, G, L.repList, L.nRep,
+                  L.rowStart, L.sorted, slice, M);
+    DEFTET_LAUNCH(k_nn_far_pad, dim3(nS), dim3(64), st, L.repList, (const int *)L.nRep, slice);
+    DEFTET_LAUNCH(k_nn_far_bound, dim3((nmax + 63) / 64, nS), dim3(kFarWaves * 64), st, queries, (const NNGrid *)L.grid, (const int *)L.start,
+                  (const float4 *)L.sorted, (const float4 *)L.repList, (const int *)L.nRep, points, N, (const unsigned *)L.farKeyS,
+                  (const unsigned *)L.farList, L.bound, L.nFar, 1u << keyBits, slice, M, Nst, shapeShift);
+    DEFTET_LAUNCH(k_nn_far_rows, dim3((nmax + 63) / 64, kFarSlices, nS), dim3(kFarWaves * 64), st, queries, (const NNGrid *)L.grid,
+                  (const int *)L.start, (const float4 *)L.sorted, (const int *)L.rowStart, (const int *)L.nFar, (const unsigned *)L.farList, L.bound, slice,
                   N, Nst);
-    DEFTET_LAUNCH(k_nn_far_final, dim3((nmax + 255) / 256, nS), blk, st, (const unsigned long long *)bound, (const int *)nFar,
-                  (const unsigned *)farList, result, slice, N, Nst);
+    DEFTET_LAUNCH(k_nn_far_final, dim3((nmax + 255) / 256, nS), blk, st, (const unsigned long long *)L.bound, (const int *)L.nFar,
+                  (const unsigned *)L.farList, result, slice, N, Nst);
     return DEFTET_OK;
 }
 
@@ -2427,14 +2436,14 @@ static int nn_index_impl(const float *queries, const float *points, int32_t *res
         }
         return DEFTET_OK;
     }
-    DEFTET_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && wsb >= deftet_nn_index_workspace_bytes(B, N, M),
+    DEFTET_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && nn_layout(group_shapes(B), N, M, workspace).bytes <= wsb,
                      "workspace misaligned or too small");
     for (int b0 = 0; b0 < B; b0 += kBatchShapes) {                   // groups of kBatchShapes shapes reuse the workspace (stream order)
         const int nS = std::min(kBatchShapes, B - b0);
         ShapeCounts cnt{};
         for (int i = 0; i < nS; ++i) cnt.n[i] = n_query_host ? n_query_host[b0 + i] : N;
         const int rc = nn_group(queries + (size_t)b0 * N * 3, points + (size_t)b0 * M * 3, result + (size_t)b0 * N, nS, N, M, cnt, workspace,
-                                wsb, st);
+                                st);
         if (rc != DEFTET_OK) return rc;
     }
     return DEFTET_OK;
@@ -2460,13 +2469,23 @@ static u32 a8_table_mask(int F)
     while (n < (u32)(F > 0 ? F : 0) * 6u) n <<= 1;                   // >= 2 slots per edge record
     return n - 1;
 }
-static size_t a8_bytes(int B, int F_max)
+// the edge hash of every shape: chain heads per table slot, the next record per edge record (three per face)
+struct A8Layout {
+    size_t bytes;
+    int *head, *next;
+};
+static A8Layout a8_layout(int B, int F_max, void *ws)
 {
+    A8Layout L{};
     const size_t b = (size_t)(B > 0 ? B : 0);
-    return align_up(b * ((size_t)a8_table_mask(F_max) + 1) * 4, 256) + align_up(b * (size_t)(F_max > 0 ? F_max : 0) * 3 * 4, 256) + 256;
+    Arena A(ws);
+    L.head = A.take<int>(b * ((size_t)a8_table_mask(F_max) + 1));
+    L.next = A.take<int>(b * (size_t)(F_max > 0 ? F_max : 0) * 3);
+    L.bytes = A.end();
+    return L;
 }
-extern "C" size_t deftet_face_edge_adj_workspace_bytes(int F) { return a8_bytes(1, F); }
-extern "C" size_t deftet_face_edge_adj_ragged_workspace_bytes(int B, int F_max) { return a8_bytes(B, F_max); }
+extern "C" size_t deftet_face_edge_adj_workspace_bytes(int F) { return a8_layout(1, F, nullptr).bytes; }
+extern "C" size_t deftet_face_edge_adj_ragged_workspace_bytes(int B, int F_max) { return a8_layout(B, F_max, nullptr).bytes; }
 
 // A8 for a batch of surfaces with different face counts: face f32 [B, F_max, 3, 3], adj f32 [B, F_max, max_nei] (pre-filled
 // with -1 by the caller), shape b has n_face_host[b] <= F_max faces (HOST integers); neighbour indices are local to the
@@ -2487,11 +2506,10 @@ extern "C" int deftet_face_edge_adj_ragged_f32(const float *face, float *adj, in
                               adj + (size_t)b * F_max * max_nei, n_face_host[b], max_nei);
         return DEFTET_OK;
     }
-    DEFTET_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && wsb >= a8_bytes(B, F_max), "workspace misaligned or too small");
+    const A8Layout L = a8_layout(B, F_max, workspace);
+    DEFTET_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && L.bytes <= wsb, "workspace misaligned or too small");
     const u32 mask = a8_table_mask(F_max);
-    Arena A(workspace, wsb);
-    int *head = A.take<int>((size_t)B * (mask + 1)), *next = A.take<int>((size_t)B * F_max * 3);
-    DEFTET_HIP(hipMemsetAsync(head, 0xFF, (size_t)B * (mask + 1) * 4, st));   // -1 = empty chain
+    DEFTET_HIP(hipMemsetAsync(L.head, 0xFF, (size_t)B * (mask + 1) * 4, st));   // -1 = empty chain
     for (int b0 = 0; b0 < B; b0 += kA8Shapes) {
         const int nb = std::min(kA8Shapes, B - b0);
         A8Counts cnt{};
@@ -2499,10 +2517,10 @@ extern "C" int deftet_face_edge_adj_ragged_f32(const float *face, float *adj, in
         for (int i = 0; i < nb; ++i) { cnt.n[i] = n_face_host[b0 + i]; fmax = std::max(fmax, cnt.n[i]); }
         if (fmax == 0) continue;
         const float *fb = face + (size_t)b0 * F_max * 9;
-        DEFTET_LAUNCH(k_edge_insert, dim3((fmax * 3 + 255) / 256, nb), dim3(256), st, fb, F_max, cnt, mask, head + (size_t)b0 * (mask + 1),
-                      next + (size_t)b0 * F_max * 3);
+        DEFTET_LAUNCH(k_edge_insert, dim3((fmax * 3 + 255) / 256, nb), dim3(256), st, fb, F_max, cnt, mask, L.head + (size_t)b0 * (mask + 1),
+                      L.next + (size_t)b0 * F_max * 3);
         DEFTET_LAUNCH(k_face_neighbors, dim3((fmax + 255) / 256, nb), dim3(256), st, fb, F_max, cnt, mask,
-                      (const int *)(head + (size_t)b0 * (mask + 1)), (const int *)(next + (size_t)b0 * F_max * 3),
+                      (const int *)(L.head + (size_t)b0 * (mask + 1)), (const int *)(L.next + (size_t)b0 * F_max * 3),
                       adj + (size_t)b0 * F_max * max_nei, max_nei);
     }
     return DEFTET_OK;
@@ -2590,7 +2608,7 @@ struct TriSlice {
     size_t lay(void *base, int P, int Fmax)
     {
         const size_t nc = (size_t)kTGMax * kTGMax * kTGMax + 1, F = (size_t)(Fmax > 0 ? Fmax : 0), Pn = (size_t)(P > 0 ? P : 0);
-        Arena A(base, ~(size_t)0);
+        Arena A(base);
         part = A.take<float>(kTParts * 8);
         grid = A.take<TGrid>(1);
         cnt = A.take<int>(nc); start = A.take<int>(nc); fill = A.take<int>(nc);
@@ -2604,34 +2622,37 @@ struct TriSlice {
         frange = A.take<uint2>(F + 1);
         pcount = A.take<int>(nc); pstart = A.take<int>(nc + 1);
         prank = A.take<int2>(Pn + 1);
-        return align_up(A.off, 256);
+        return A.end();
     }
 };
-static size_t tri_slice_bytes(int P, int Fmax)
+// per-shape scratch slices for a launch group of nS <= kBatchShapes shapes; behind them the cell keys and the point order of
+// all shapes of the group in the cells' order (P entries per shape each, one spare)
+struct TriLayout {
+    TriSlice S;                                                       // slice 0; the kernels rebase to their shape by `slice` bytes
+    size_t slice, bytes;
+    unsigned *pskey, *order;
+};
+static TriLayout tri_layout(int nS, int P, int Fmax, void *ws)
 {
-    TriSlice L;
-    return L.lay(nullptr, P, Fmax);
+    TriLayout L{};
+    L.slice = L.S.lay(ws, P, Fmax);
+    const size_t nAll = (size_t)nS * (size_t)(P > 0 ? P : 0);
+    Arena T(static_cast<char *>(ws) + L.slice * nS);
+    L.pskey = T.take<unsigned>(nAll + 1);
+    L.order = T.take<unsigned>(nAll + 1);
+    L.bytes = L.slice * nS + T.end();
+    return L;
 }
-// behind the slices: the sorted cell keys and the point order of all shapes of a group (P entries per shape each)
-static size_t tri_sort_bytes(int nShapes, int P)
-{
-    const size_t n = (size_t)nShapes * (size_t)(P > 0 ? P : 0);
-    return 2 * align_up(n * 4 + 4, 256) + 1024;
-}
-// per-shape scratch slices for a launch group of <= kBatchShapes shapes + the all-shapes point keys and sort scratch
-extern "C" size_t deftet_tri_dist_workspace_bytes(int B, int P, int Fmax)
-{
-    const int g = B < 1 ? 1 : (B < kBatchShapes ? B : kBatchShapes);
-    return tri_slice_bytes(P, Fmax) * (size_t)g + tri_sort_bytes(g, P);
-}
+extern "C" size_t deftet_tri_dist_workspace_bytes(int B, int P, int Fmax) { return tri_layout(group_shapes(B), P, Fmax, nullptr).bytes; }
 
 // the grid search for a GROUP of nS <= kBatchShapes shapes: one launch per kernel for the whole group
 static int tri_dist_group(const float *pts, const float *face, const float *nfb, float *cd, float *cf, int nS, int P, int Fmax, void *ws,
-                          size_t wsb, hipStream_t st, int *order_out)
+                          hipStream_t st, int *order_out)
 {
     const size_t nc = (size_t)kTGMax * kTGMax * kTGMax + 1;
-    TriSlice L;                                                       // layout of slice 0; the kernels rebase to their shape
-    const size_t slice = L.lay(ws, P, Fmax);
+    const TriLayout TL = tri_layout(nS, P, Fmax, ws);                 // at most what the entry checked: a group is no larger than the largest
+    const TriSlice &L = TL.S;
+    const size_t slice = TL.slice;
     float *part = L.part;
     TGrid *grid = L.grid;
     int *cnt = L.cnt, *start = L.start, *fill = L.fill, *list = L.list, *wide = L.wide, *farList = L.farList, *counters = L.counters;
@@ -2642,9 +2663,7 @@ static int tri_dist_group(const float *pts, const float *face, const float *nfb,
     int *pcount = L.pcount, *pstart = L.pstart;
     int2 *prank = L.prank;
     const size_t nAll = (size_t)nS * P;
-    if (slice * nS + tri_sort_bytes(nS, P) > wsb) return set_error(DEFTET_EINVAL, "tri_dist workspace smaller than its layout");
-    Arena T(static_cast<char *>(ws) + slice * nS, wsb - slice * nS);
-    unsigned *pskey = T.take<unsigned>(nAll + 1), *order = T.take<unsigned>(nAll + 1);
+    unsigned *pskey = TL.pskey, *order = TL.order;
     const dim3 blk(256);
     DEFTET_LAUNCH(k_tri_face_stats, dim3(kTParts, nS), blk, st, face, nfb, part, slice, Fmax, cnt, fill, counters, rep, (int)nc, kTGc * kTGc * kTGc,
                   pcount);
@@ -2697,13 +2716,13 @@ extern "C" int deftet_tri_dist_fwd_order_f32(const float *pts, const float *face
         DEFTET_LAUNCH(k_tri_dist_fwd, dim3((P + 255) / 256, B), dim3(256), st, pts, face, n_face_b, closest_d, closest_f, P, Fmax);
         return DEFTET_OK;
     }
-    DEFTET_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && wsb >= deftet_tri_dist_workspace_bytes(B, P, Fmax),
+    DEFTET_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && tri_layout(group_shapes(B), P, Fmax, workspace).bytes <= wsb,
                      "workspace misaligned or too small");
     DEFTET_CHECK_ARG((long long)Fmax * kTMaxCells < 2147483647LL && (long long)P * 3 < 2147483647LL, "too many faces / points");
     for (int b0 = 0; b0 < B; b0 += kBatchShapes) {                   // groups of kBatchShapes shapes reuse the workspace (stream order)
         const int nS = std::min(kBatchShapes, B - b0);
         const int rc = tri_dist_group(pts + (size_t)b0 * P * 3, face + (size_t)b0 * Fmax * 9, n_face_b + b0, closest_d + (size_t)b0 * P,
-                                      closest_f + (size_t)b0 * P, nS, P, Fmax, workspace, wsb, st,
+                                      closest_f + (size_t)b0 * P, nS, P, Fmax, workspace, st,
                                       order_out ? order_out + (size_t)b0 * P : nullptr);
         if (rc != DEFTET_OK) return rc;
     }

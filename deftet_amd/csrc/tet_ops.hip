@@ -373,11 +373,45 @@ __global__ __launch_bounds__(256) void k_energy_bwd(const float *__restrict__ te
 using namespace deftet;
 using namespace deftet::tops;
 
-extern "C" size_t deftet_boundary_index_workspace_bytes(int B, int Fi)
+namespace {
+struct BndLayout {
+    size_t bytes, scanTmpBytes;
+    int *flag, *pos;
+    void *scanTmp;
+};
+BndLayout bnd_layout(int B, int Fi, void *ws)
 {
+    BndLayout L{};
     const size_t n = (size_t)(B > 0 ? B : 0) * (size_t)(Fi > 0 ? Fi : 0);
-    return align_up(n * 4, 256) * 2 + n * 8 + ((size_t)1 << 20);
+    Arena A(ws);
+    L.flag = A.take<int>(n);
+    L.pos = A.take<int>(n);
+    L.scanTmpBytes = prims::scan_temp_bytes<int>(n);
+    L.scanTmp = A.take<char>(L.scanTmpBytes);
+    L.bytes = A.end();
+    return L;
 }
+
+// kEParts partial sums per shape: three doubles each for pass 1, two for pass 2; one float per tet, the saved volumes of the forward
+struct EnergyLayout {
+    size_t bytes;
+    double *part1, *part2;
+    float *vol;
+};
+EnergyLayout energy_layout(int B, int T, void *ws)
+{
+    EnergyLayout L{};
+    const size_t nb = (size_t)(B > 0 ? B : 0);
+    Arena A(ws);
+    L.part1 = A.take<double>(nb * kEParts * 3);
+    L.part2 = A.take<double>(nb * kEParts * 2);
+    L.vol = A.take<float>(nb * (size_t)(T > 0 ? T : 0));
+    L.bytes = A.end();
+    return L;
+}
+}  // namespace
+
+extern "C" size_t deftet_boundary_index_workspace_bytes(int B, int Fi) { return bnd_layout(B, Fi, nullptr).bytes; }
 
 extern "C" int deftet_boundary_index_i64(const int64_t *face_fx3, const int64_t *tetidx_fx2, const float *occ_bxt,
                                          int64_t *out_rows, int32_t *offsets, int B, int T, int Fi, int mode, void *workspace,
@@ -389,29 +423,20 @@ extern "C" int deftet_boundary_index_i64(const int64_t *face_fx3, const int64_t 
     DEFTET_CHECK_ARG(offsets, "null offsets");
     if (B == 0 || Fi == 0) { DEFTET_HIP(hipMemsetAsync(offsets, 0, ((size_t)B + 1) * 4, st)); return DEFTET_OK; }
     DEFTET_CHECK_ARG(face_fx3 && tetidx_fx2 && occ_bxt && out_rows, "null pointer");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && wsb >= deftet_boundary_index_workspace_bytes(B, Fi),
-                     "workspace null, misaligned or too small");
+    const BndLayout L = bnd_layout(B, Fi, workspace);
+    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && L.bytes <= wsb, "workspace null, misaligned or too small");
     const size_t n = (size_t)B * Fi;
-    Arena A(workspace, wsb);
-    int *flag = A.take<int>(n), *pos = A.take<int>(n);
-    void *tmp = A.base + align_up(A.off, 256);
-    const size_t left = wsb - align_up(A.off, 256);
-    DEFTET_LAUNCH(k_bnd_flag, dim3((Fi + 255) / 256, B), dim3(256), st, (const long long *)tetidx_fx2, occ_bxt, T, Fi, mode, flag);
+    DEFTET_LAUNCH(k_bnd_flag, dim3((Fi + 255) / 256, B), dim3(256), st, (const long long *)tetidx_fx2, occ_bxt, T, Fi, mode, L.flag);
     {
-        const int rc = prims::scan<int, prims::Plus, true>(flag, pos, n, 0, prims::Plus(), tmp, left, st);
+        const int rc = prims::scan<int, prims::Plus, true>(L.flag, L.pos, n, 0, prims::Plus(), L.scanTmp, L.scanTmpBytes, st);
         if (rc != DEFTET_OK) return rc;
     }
     DEFTET_LAUNCH(k_bnd_emit, dim3((Fi + 255) / 256, B), dim3(256), st, (const long long *)face_fx3, (const long long *)tetidx_fx2,
-                  occ_bxt, flag, pos, T, Fi, B, mode, (long long *)out_rows, offsets);
+                  occ_bxt, L.flag, L.pos, T, Fi, B, mode, (long long *)out_rows, offsets);
     return DEFTET_OK;
 }
 
-// B * kEParts * 5 doubles of partial sums (+ with n_tet > 0: one float per tet, the saved volumes of the forward)
-extern "C" size_t deftet_tet_energies_workspace_bytes2(int B, int T)
-{
-    return align_up((size_t)(B > 0 ? B : 0) * kEParts * 5 * 8 + 256, 256) + align_up((size_t)(B > 0 ? B : 0) * (size_t)(T > 0 ? T : 0) * 4, 256);
-}
-static size_t energies_partials_bytes(int B) { return deftet_tet_energies_workspace_bytes2(B, 0); }
+extern "C" size_t deftet_tet_energies_workspace_bytes2(int B, int T) { return energy_layout(B, T, nullptr).bytes; }
 
 // out f32 [B,3] = {volume_variance(pow_v), amips_energy (0 if inv_v == NULL), edge_length(pow_e)};
 // stats f64 [B,8] is kept by the caller for the backward.
@@ -421,20 +446,19 @@ extern "C" int deftet_tet_energies_fwd_f32(const float *tet, const float *inv_v,
     DEFTET_CHECK_ARG(B >= 0 && T > 0 && B <= 65535 && pow_v >= 1 && pow_e >= 1 && pow_v <= 16 && pow_e <= 16, "bad argument");
     if (B == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(tet && out && stats && ((uintptr_t)tet & 15) == 0, "null or misaligned pointer");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && wsb >= deftet_tet_energies_workspace_bytes2(B, T),
+    const EnergyLayout L = energy_layout(B, T, workspace);
+    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && L.bytes <= wsb,
                      "workspace null, misaligned or smaller than deftet_tet_energies_workspace_bytes2(B, T)");
     hipStream_t st = as_stream(stream_);
-    double *part1 = static_cast<double *>(workspace), *part2 = part1 + (size_t)B * kEParts * 3;
-    float *vol = reinterpret_cast<float *>(static_cast<char *>(workspace) + energies_partials_bytes(B));
     // B <= kETicketShapes: two launches, each pass finishes its own reduction on the counters of this stream's slot
     const int slot = B <= kETicketShapes ? ticket_slot_for_stream(st, kETicketSlots) : -1;
     const bool p4 = pow_v == 4 && pow_e == 4;
-    if (p4) DEFTET_LAUNCH(k_energy_pass1<true>, dim3(kEParts, B), dim3(kEThreads), st, tet, inv_v, T, scale, pow_e, part1, vol, stats, slot);
-    else DEFTET_LAUNCH(k_energy_pass1<false>, dim3(kEParts, B), dim3(kEThreads), st, tet, inv_v, T, scale, pow_e, part1, vol, stats, slot);
-    if (slot < 0) DEFTET_LAUNCH(k_energy_mean, dim3(B), dim3(64), st, part1, T, stats);
-    if (p4) DEFTET_LAUNCH(k_energy_pass2<true>, dim3(kEParts, B), dim3(kEThreads), st, (const float *)vol, T, pow_v, stats, part2, out, slot);
-    else DEFTET_LAUNCH(k_energy_pass2<false>, dim3(kEParts, B), dim3(kEThreads), st, (const float *)vol, T, pow_v, stats, part2, out, slot);
-    if (slot < 0) DEFTET_LAUNCH(k_energy_final, dim3(B), dim3(64), st, part2, T, stats, out);
+    if (p4) DEFTET_LAUNCH(k_energy_pass1<true>, dim3(kEParts, B), dim3(kEThreads), st, tet, inv_v, T, scale, pow_e, L.part1, L.vol, stats, slot);
+    else DEFTET_LAUNCH(k_energy_pass1<false>, dim3(kEParts, B), dim3(kEThreads), st, tet, inv_v, T, scale, pow_e, L.part1, L.vol, stats, slot);
+    if (slot < 0) DEFTET_LAUNCH(k_energy_mean, dim3(B), dim3(64), st, L.part1, T, stats);
+    if (p4) DEFTET_LAUNCH(k_energy_pass2<true>, dim3(kEParts, B), dim3(kEThreads), st, (const float *)L.vol, T, pow_v, stats, L.part2, out, slot);
+    else DEFTET_LAUNCH(k_energy_pass2<false>, dim3(kEParts, B), dim3(kEThreads), st, (const float *)L.vol, T, pow_v, stats, L.part2, out, slot);
+    if (slot < 0) DEFTET_LAUNCH(k_energy_final, dim3(B), dim3(64), st, L.part2, T, stats, out);
     return DEFTET_OK;
 }
 

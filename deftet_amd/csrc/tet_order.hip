@@ -265,6 +265,22 @@ static Layout make_layout(int T, void *ws, size_t wsb)
     return L;
 }
 
+struct FarLayout {
+    float *part;
+    int *blockFar;
+    size_t bytes;
+};
+
+static FarLayout far_layout(void *ws)
+{
+    FarLayout L{};
+    Arena A(ws);
+    L.part = A.take<float>((size_t)kStatBlocks * kStatWords);
+    L.blockFar = A.take<int>((size_t)kFarBlocks);
+    L.bytes = A.end();
+    return L;
+}
+
 }  // namespace order
 }  // namespace deftet
 
@@ -308,8 +324,7 @@ extern "C" int deftet_tet_spatial_order_f32(const float *tet, int n_tet, int32_t
 // one thread and may be host-mapped memory (a caller can poll it without synchronising).  Three small launches.
 extern "C" size_t deftet_tet_order_coherence_workspace_bytes(int n_tet)
 {
-    if (n_tet <= 0) return 0;
-    return align_up((size_t)deftet::order::kStatBlocks * deftet::order::kStatWords * 4, 256) + align_up((size_t)deftet::order::kFarBlocks * 4, 256);
+    return n_tet <= 0 ? 0 : order::far_layout(nullptr).bytes;
 }
 
 extern "C" int deftet_tet_order_coherence_f32(const float *tet, int n_tet, const int32_t *order, int32_t *out2, void *workspace,
@@ -323,12 +338,10 @@ extern "C" int deftet_tet_order_coherence_f32(const float *tet, int n_tet, const
         return DEFTET_OK;
     }
     DEFTET_CHECK_ARG(tet && ((uintptr_t)tet & 15) == 0, "null or misaligned pointer");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && workspace_bytes >= deftet_tet_order_coherence_workspace_bytes(n_tet),
-                     "workspace null, misaligned or too small");
-    float *part = static_cast<float *>(workspace);
-    int *blockFar = reinterpret_cast<int *>(static_cast<char *>(workspace) + align_up((size_t)kStatBlocks * kStatWords * 4, 256));
-    DEFTET_LAUNCH(k_order_stats, dim3(kStatBlocks), dim3(256), st, tet, n_tet, part);
-    DEFTET_LAUNCH(k_order_far, dim3(kFarBlocks), dim3(256), st, tet, n_tet, (const int *)order, (const float *)part, blockFar);
-    DEFTET_LAUNCH(k_order_far_sum, dim3(1), dim3(kFarBlocks), st, (const int *)blockFar, n_tet, out2);
+    const FarLayout L = far_layout(workspace);
+    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && L.bytes <= workspace_bytes, "workspace null, misaligned or too small");
+    DEFTET_LAUNCH(k_order_stats, dim3(kStatBlocks), dim3(256), st, tet, n_tet, L.part);
+    DEFTET_LAUNCH(k_order_far, dim3(kFarBlocks), dim3(256), st, tet, n_tet, (const int *)order, (const float *)L.part, L.blockFar);
+    DEFTET_LAUNCH(k_order_far_sum, dim3(1), dim3(kFarBlocks), st, (const int *)L.blockFar, n_tet, out2);
     return DEFTET_OK;
 }

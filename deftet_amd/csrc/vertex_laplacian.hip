@@ -198,29 +198,43 @@ inline unsigned grid_x(int V) { return (unsigned)((((V + 255) / 256) + 7) / 8 * 
 
 inline size_t sort_tmp_bytes(size_t n) { return prims::radix_sort_temp_bytes<u64, unsigned>(n); }
 
+struct CsrLayout {
+    size_t bytes, sortTmpBytes;
+    u64 *key, *skey;
+    unsigned *perm;
+    void *sortTmp;
+};
+
+inline CsrLayout csr_layout(int nnz, void *ws)
+{
+    CsrLayout L{};
+    Arena A(ws);
+    L.key = A.take<u64>((size_t)nnz);
+    L.skey = A.take<u64>((size_t)nnz);
+    L.perm = A.take<unsigned>((size_t)nnz);
+    L.sortTmpBytes = sort_tmp_bytes((size_t)nnz);
+    L.sortTmp = A.take<char>(L.sortTmpBytes);
+    L.bytes = A.end();
+    return L;
+}
+
 template <typename I>
 int build_csr(const I *rows, const I *cols, const float *vals, int nnz, int V, int order, int32_t *offsets, int32_t *out_cols,
-              float *out_vals, int32_t *t_offsets, int32_t *t_rows, float *t_vals, int32_t *bad, void *workspace, size_t workspace_bytes,
-              hipStream_t st)
+              float *out_vals, int32_t *t_offsets, int32_t *t_rows, float *t_vals, int32_t *bad, const CsrLayout &L, hipStream_t st)
 {
-    Arena A(workspace, workspace_bytes);
-    u64 *key = A.take<u64>((size_t)nnz), *skey = A.take<u64>((size_t)nnz);
-    unsigned *perm = A.take<unsigned>((size_t)nnz);
-    const size_t tmpBytes = sort_tmp_bytes((size_t)nnz);
-    void *tmp = A.take<char>(tmpBytes);
     const int mb = bit_length((unsigned)V);                  // 2^mb > V: an all-ones major part is never a vertex
     const unsigned gk = (unsigned)((nnz + 255) / 256), gf = (unsigned)((nnz + 256) / 256);
     for (int t = 0; t < 2; ++t) {
         const int minorBits = t == 0 && order == DEFTET_VADJ_ROW_INPUT ? 0 : mb;
-        DEFTET_LAUNCH((k_vadj_keys<I>), dim3(gk), dim3(256), st, rows, cols, nnz, V, t, minorBits, key, bad);
-        const int rc = prims::radix_sort_from<u64, unsigned>(prims::PtrLoad<u64>{key}, skey, prims::IotaLoad{}, perm, (size_t)nnz,
-                                                             mb + minorBits, tmp, tmpBytes, st);
+        DEFTET_LAUNCH((k_vadj_keys<I>), dim3(gk), dim3(256), st, rows, cols, nnz, V, t, minorBits, L.key, bad);
+        const int rc = prims::radix_sort_from<u64, unsigned>(prims::PtrLoad<u64>{L.key}, L.skey, prims::IotaLoad{}, L.perm, (size_t)nnz,
+                                                             mb + minorBits, L.sortTmp, L.sortTmpBytes, st);
         if (rc != DEFTET_OK) return rc;
         if (t == 0)
-            DEFTET_LAUNCH((k_vadj_fill<I>), dim3(gf), dim3(256), st, (const u64 *)skey, (const unsigned *)perm, nnz, V, minorBits, cols, vals,
+            DEFTET_LAUNCH((k_vadj_fill<I>), dim3(gf), dim3(256), st, (const u64 *)L.skey, (const unsigned *)L.perm, nnz, V, minorBits, cols, vals,
                           out_cols, out_vals, offsets);
         else
-            DEFTET_LAUNCH((k_vadj_fill<I>), dim3(gf), dim3(256), st, (const u64 *)skey, (const unsigned *)perm, nnz, V, minorBits, rows, vals,
+            DEFTET_LAUNCH((k_vadj_fill<I>), dim3(gf), dim3(256), st, (const u64 *)L.skey, (const unsigned *)L.perm, nnz, V, minorBits, rows, vals,
                           t_rows, t_vals, t_offsets);
     }
     return DEFTET_OK;
@@ -257,9 +271,7 @@ using namespace deftet;
 
 extern "C" size_t deftet_vertex_adjacency_workspace_bytes(int nnz, int n_vertex)
 {
-    if (nnz < 0 || n_vertex < 0) return 0;
-    const size_t n = (size_t)nnz;
-    return 2 * align_up(n * 8, 256) + align_up(n * 4, 256) + align_up(vlap::sort_tmp_bytes(n), 256) + 256;
+    return nnz < 0 || n_vertex < 0 ? 0 : vlap::csr_layout(nnz, nullptr).bytes;
 }
 
 extern "C" int deftet_vertex_adjacency_csr_i32(const void *row_idx, const void *col_idx, int index_bytes, const float *values, int nnz,
@@ -277,8 +289,8 @@ extern "C" int deftet_vertex_adjacency_csr_i32(const void *row_idx, const void *
     DEFTET_CHECK_ARG(vlap::aligned(values, 4) && vlap::aligned(offsets, 4) && vlap::aligned(cols, 4) && vlap::aligned(vals, 4) &&
                          vlap::aligned(t_offsets, 4) && vlap::aligned(t_rows, 4) && vlap::aligned(t_vals, 4) && vlap::aligned(bad_flag, 4),
                      "outputs and values must be 4-byte aligned");
-    DEFTET_CHECK_ARG(nnz == 0 || (workspace && vlap::aligned(workspace, 256) &&
-                                  workspace_bytes >= deftet_vertex_adjacency_workspace_bytes(nnz, n_vertex)),
+    const vlap::CsrLayout L = vlap::csr_layout(nnz, workspace);
+    DEFTET_CHECK_ARG(nnz == 0 || (workspace && vlap::aligned(workspace, 256) && L.bytes <= workspace_bytes),
                      "workspace null, misaligned or too small");
     hipStream_t st = as_stream(stream_);
     DEFTET_HIP(hipMemsetAsync(bad_flag, 0, 4, st));
@@ -289,9 +301,9 @@ extern "C" int deftet_vertex_adjacency_csr_i32(const void *row_idx, const void *
     }
     if (index_bytes == 4)
         return vlap::build_csr(static_cast<const int32_t *>(row_idx), static_cast<const int32_t *>(col_idx), values, nnz, n_vertex, order,
-                               offsets, cols, vals, t_offsets, t_rows, t_vals, bad_flag, workspace, workspace_bytes, st);
+                               offsets, cols, vals, t_offsets, t_rows, t_vals, bad_flag, L, st);
     return vlap::build_csr(static_cast<const int64_t *>(row_idx), static_cast<const int64_t *>(col_idx), values, nnz, n_vertex, order,
-                           offsets, cols, vals, t_offsets, t_rows, t_vals, bad_flag, workspace, workspace_bytes, st);
+                           offsets, cols, vals, t_offsets, t_rows, t_vals, bad_flag, L, st);
 }
 
 extern "C" size_t deftet_vertex_laplacian_workspace_bytes(int n_batch, int n_vertex)

@@ -157,11 +157,29 @@ extern "C" int deftet_tet_gather_fwd_f32(const float *pos, const int64_t *tet_id
 
 // The incidence CSR of an index list with `corners` indices per element (4: tets, 3: faces — render_vertices.hip): slot
 // corners*e + corner, ascending per vertex.
+namespace {
+struct CsrLayout {
+    size_t bytes, sortTmpBytes;
+    unsigned *key, *val, *skey;
+    void *sortTmp;
+};
+CsrLayout csr_layout(size_t n, void *ws)                             // n: incidences of every shape
+{
+    CsrLayout L{};
+    Arena A(ws);
+    L.key = A.take<unsigned>(n);
+    L.val = A.take<unsigned>(n);
+    L.skey = A.take<unsigned>(n);
+    L.sortTmpBytes = vtx::sort_tmp_bytes(n);
+    L.sortTmp = A.take<char>(L.sortTmpBytes);
+    L.bytes = A.end();
+    return L;
+}
+}  // namespace
+
 size_t deftet::vtx::incidence_csr_workspace_bytes(int idx_batch, int V, int E, int corners)
 {
-    if (idx_batch <= 0 || V < 0 || E < 0) return 0;
-    const size_t n = (size_t)idx_batch * E * corners;
-    return 3 * align_up(n * 4, 256) + align_up(vtx::sort_tmp_bytes(n), 256) + 256;
+    return idx_batch <= 0 || V < 0 || E < 0 ? 0 : csr_layout((size_t)idx_batch * E * corners, nullptr).bytes;
 }
 
 int deftet::vtx::incidence_csr(const int64_t *idx, int32_t *offsets, int32_t *slots, int32_t *bad_flag, int idx_batch, int V, int E,
@@ -171,24 +189,20 @@ int deftet::vtx::incidence_csr(const int64_t *idx, int32_t *offsets, int32_t *sl
     DEFTET_CHECK_ARG((long long)idx_batch * V < 0xFFFFFFFFLL && (long long)idx_batch * E * corners < 0x7FFFFFFFLL, "topology too large for 32-bit keys");
     DEFTET_CHECK_ARG(offsets && bad_flag && (E == 0 || (idx && slots)), "null pointer");
     const long long n = (long long)idx_batch * E * corners, nKeys = (long long)idx_batch * V;
+    const CsrLayout L = csr_layout((size_t)n, workspace);
+    DEFTET_CHECK_ARG(n == 0 || (workspace && L.bytes <= workspace_bytes && ((uintptr_t)workspace & 255) == 0),
+                     "workspace null, misaligned or too small");
     DEFTET_HIP(hipMemsetAsync(bad_flag, 0, 4, st));
     if (n == 0) {
         DEFTET_HIP(hipMemsetAsync(offsets, 0, (size_t)(nKeys + 1) * 4, st));
         return DEFTET_OK;
     }
-    DEFTET_CHECK_ARG(workspace && workspace_bytes >= incidence_csr_workspace_bytes(idx_batch, V, E, corners) &&
-                         ((uintptr_t)workspace & 255) == 0,
-                     "workspace null, misaligned or too small");
-    Arena A(workspace, workspace_bytes);
-    unsigned *key = A.take<unsigned>((size_t)n), *val = A.take<unsigned>((size_t)n), *skey = A.take<unsigned>((size_t)n);
-    size_t tmpBytes = vtx::sort_tmp_bytes((size_t)n);
-    void *tmp = A.take<char>(tmpBytes);
     const unsigned gb = (unsigned)((n + 255) / 256);
-    DEFTET_LAUNCH(vtx::k_csr_keys, dim3(gb), dim3(256), st, idx, n, (long long)E * corners, V, key, val, bad_flag);
-    // all 32 key bits: invalid incidences carry the key 0xFFFFFFFF and must sort behind every vertex
-    const int rc = prims::radix_sort<unsigned, unsigned>(key, skey, val, reinterpret_cast<unsigned *>(slots), (size_t)n, 32, tmp, tmpBytes, st);
+    DEFTET_LAUNCH(vtx::k_csr_keys, dim3(gb), dim3(256), st, idx, n, (long long)E * corners, V, L.key, L.val, bad_flag);
+    // all 32 L.key bits: invalid incidences carry the L.key 0xFFFFFFFF and must sort behind every vertex
+    const int rc = prims::radix_sort<unsigned, unsigned>(L.key, L.skey, L.val, reinterpret_cast<unsigned *>(slots), (size_t)n, 32, L.sortTmp, L.sortTmpBytes, st);
     if (rc != DEFTET_OK) return rc;
-    DEFTET_LAUNCH(vtx::k_csr_offsets, dim3((unsigned)((n + 256) / 256)), dim3(256), st, skey, n, nKeys, offsets);
+    DEFTET_LAUNCH(vtx::k_csr_offsets, dim3((unsigned)((n + 256) / 256)), dim3(256), st, L.skey, n, nKeys, offsets);
     return DEFTET_OK;
 }
 
