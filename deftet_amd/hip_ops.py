@@ -7,6 +7,7 @@ reference's names and signatures) lives in deftet_amd/layers/ and deftet_amd/uti
 from __future__ import annotations
 
 import collections
+import ctypes
 import operator
 import os
 import threading
@@ -2376,6 +2377,165 @@ def voxel_sample(volumes, pos, append_pos=False, voxel_units=False):
             raise RuntimeError("voxel_sample: volume %s and pos %s differ in batch or device" % (tuple(v.shape), tuple(pos.shape)))
         vols.append(v)
     return _VoxelSample.apply(pos, bool(append_pos), 1 if voxel_units else 0, *vols)
+
+
+# --------------------------------------------------------------------------------- tet-centroid feature sampling
+_TCS_MAX_VOLUMES = 8
+
+
+def _tcs_volume_list(volumes):
+    """the host arrays of the C ABI's volume list: (device pointers, channels, resolutions, n); the tensors must stay alive"""
+    n = len(volumes)
+    ptrs = (ctypes.c_void_p * max(n, 1))(*[v.data_ptr() for v in volumes])
+    chans = (ctypes.c_int * max(n, 1))(*[v.shape[1] for v in volumes])
+    ress = (ctypes.c_int * max(n, 1))(*[v.shape[-1] for v in volumes])
+    return ptrs, chans, ress, n
+
+
+def tet_centroid_sample_bwd_pos(volumes, centroids, gout, append_pos=True):
+    """gcent f32 [B,K,3]: the gradient of tet_centroid_sample's result on its centroids, one launch for the whole volume list.  The
+    bits of voxel_sample's chain on the same centroids: per volume the channel sum from 0 in ascending order, the volumes added in
+    list order, the position rows of gout last.  A slot with a NaN centroid gets 0."""
+    lib = _lib.load()
+    B, K = centroids.shape[0], centroids.shape[1]
+    gcent = torch.empty(B, K, 3, device=centroids.device, dtype=torch.float32)
+    ptrs, chans, ress, n = _tcs_volume_list(volumes)
+    with _lib.on_device(centroids.device):
+        _lib.check(lib.deftet_tet_centroid_sample_bwd_pos_f32(ptrs, chans, ress, n, _lib.ptr(centroids), _lib.ptr(gout), _lib.ptr(gcent), B, K,
+                                                              1 if append_pos else 0, _lib.current_stream(centroids.device)),
+                   "deftet_tet_centroid_sample_bwd_pos_f32")
+    return gcent
+
+
+def tet_centroid_sample_bwd_vertices(gcent, csr, n_vertex, n_tet, select=None, first=0, out=None):
+    """gpos f32 [B,V,3] = 0.25f * (per vertex, over its incidences in the CSR's order and per incidence over the slots that chose
+    that tet in ascending slot, the sum of gcent f32 [B,K,3] in one fp32 accumulator from 0).  select int32 [K] or the range from
+    `first`; out: an existing contiguous f32 [B,V,3] to ADD to.  Every element is written: no memset, no atomics."""
+    lib = _lib.load()
+    offsets, slots, Bi = csr
+    B, K, V, T = gcent.shape[0], gcent.shape[1], int(n_vertex), int(n_tet)
+    if slots.numel() != Bi * T * 4 or offsets.numel() != Bi * V + 1 or Bi not in (1, B):
+        raise RuntimeError("tet_centroid_sample: the CSR does not match the tet list / n_vertex")
+    acc = out is not None
+    if acc and (out.shape != (B, V, 3) or out.dtype != torch.float32 or not out.is_contiguous()):
+        raise RuntimeError("tet_centroid_sample: out must be contiguous f32 [B,V,3]")
+    dev = gcent.device
+    gpos = out if acc else torch.empty(B, V, 3, device=dev, dtype=torch.float32)
+    with _lib.on_device(dev):
+        ws, nbytes = None, 0
+        if select is not None:
+            nbytes = lib.deftet_tet_centroid_sample_workspace_bytes(B, T, K)
+            ws = _lib.workspace(dev, nbytes)
+        _lib.check(lib.deftet_tet_centroid_sample_bwd_vertices_f32(_lib.ptr(gcent), _lib.ptr(offsets), _lib.ptr(slots), _lib.ptr(select),
+                                                                   int(first), _lib.ptr(gpos), B, V, T, Bi, K, 1 if acc else 0, _lib.ptr(ws),
+                                                                   nbytes, _lib.current_stream(dev)),
+                   "deftet_tet_centroid_sample_bwd_vertices_f32")
+    return gpos
+
+
+class _TetCentroidSample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pos, tet_idx, csr, select, first, K, append_pos, check, *volumes):
+        lib = _lib.load()
+        dev = pos.device
+        B, V, T = pos.shape[0], pos.shape[1], tet_idx.shape[1]
+        C_feat = sum(v.shape[1] for v in volumes)
+        C_total = C_feat + (3 if append_pos else 0)
+        out = torch.empty(B, C_total, K, device=dev, dtype=torch.float32)
+        centroids = torch.empty(B, K, 3, device=dev, dtype=torch.float32)
+        bad = torch.zeros(1, device=dev, dtype=torch.int32) if check else None
+        ptrs, chans, ress, n = _tcs_volume_list(volumes)
+        with _lib.on_device(dev):
+            _lib.check(lib.deftet_tet_centroid_sample_fwd_f32(ptrs, chans, ress, n, _lib.ptr(pos), _lib.ptr(tet_idx), _lib.ptr(select), first,
+                                                              _lib.ptr(out), _lib.ptr(centroids), _lib.ptr(bad), B, V, T, tet_idx.shape[0], K,
+                                                              1 if append_pos else 0, _lib.current_stream(dev)),
+                       "deftet_tet_centroid_sample_fwd_f32")
+        if check and int(bad.item()):
+            raise RuntimeError("tet_centroid_sample: a chosen tet is outside [0, %d) or one of its vertices outside [0, %d)" % (T, V))
+        ctx.save_for_backward(centroids, *volumes)
+        ctx.tet_idx, ctx.csr, ctx.select = tet_idx, csr, select
+        ctx.args = (bool(append_pos), first, B, V, T, K, C_feat, C_total)
+        ctx.mark_non_differentiable(centroids)
+        return out, centroids
+
+    @staticmethod
+    def backward(ctx, gout, _gcentroids):
+        centroids, volumes = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        append_pos, first, B, V, T, K, C_feat, C_total = ctx.args
+        lib = _lib.load()
+        dev = centroids.device
+        gout = _f32c(gout)
+        grads, cells, c_off = [], {}, 0
+        for k, v in enumerate(volumes):
+            C, R = v.shape[1], v.shape[-1]
+            if ctx.needs_input_grad[8 + k]:
+                if R not in cells:                                   # one sort of the centroids per distinct resolution
+                    cells[R] = _voxel_cells(lib, B, K, R, dev, pos=centroids, pos_mode=0)
+                grads.append(_bwd_vol(lib, gout, cells[R], C, c_off, C_total))
+            else:
+                grads.append(None)
+            c_off += C
+        gpos = None
+        if ctx.needs_input_grad[0]:
+            gcent = tet_centroid_sample_bwd_pos(volumes, centroids, gout, append_pos)
+            csr = ctx.csr
+            if csr is None:                                          # the slow path: a sort of 4 T incidences and a host sync per backward
+                csr = tet_vertex_csr(ctx.tet_idx, V)
+            gpos = tet_centroid_sample_bwd_vertices(gcent, csr, V, T, select=ctx.select, first=first)
+        return (gpos, None, None, None, None, None, None, None) + tuple(grads)
+
+
+def tet_centroid_sample(volumes, pos_bxvx3, tet_idx, csr=None, select=None, first=0, count=None, append_pos=True, check=False,
+                        return_centroids=False):
+    """f32 [B, sum C_k (+3), K]: the volumes f32 [B,C_k,R_k,R_k,R_k] (at most 8) read trilinearly at the centroids of K chosen tets of
+    the mesh (pos f32 [B,V,3], tet_idx int [T,4] or [B,T,4]), the centroids themselves behind them with append_pos — the input of
+    the occupancy decoder (`decode_occ`, pc_model.py:276-306) without the gathered [B,T,4,3] tensor, its mean or the index step.
+    The chosen tets: `select`, an int tensor [K] shared by the batch (`center_idx`; repeats allowed), or the range [first,
+    first + count) (`split_decode_occ`'s walk; count=None: to the end), never both.  The centroid is (((a + b) + c) + d) * 0.25f
+    in fp32; the values are voxel_sample's at that point, bit for bit.
+    Differentiable in pos and in every volume, with the same bits on every run and no atomics: the volumes through voxel_sample's
+    sort by cell, pos through the incidence CSR — `csr` = tet_vertex_csr(tet_idx, V), built once per tet list (TetTopology keeps
+    it).  csr=None with pos requiring grad is the SLOW PATH: the CSR is rebuilt in every backward (a sort and a host sync).
+    check=True synchronises and raises on a tet index outside [0,T) or a vertex index outside [0,V); otherwise such a slot's
+    values are NaN and it adds nothing to the gradient of pos.  return_centroids: also the centroids f32 [B,K,3] (no gradient)."""
+    volumes = list(volumes)
+    _lib.require_gpu(pos_bxvx3, tet_idx, select, *volumes)
+    pos = _pv_need(pos_bxvx3, torch.float32, "tet_centroid_sample: pos")
+    if pos.dim() != 3 or pos.shape[2] != 3:
+        raise RuntimeError("tet_centroid_sample: pos [B,V,3] expected")
+    if len(volumes) > _TCS_MAX_VOLUMES:
+        raise RuntimeError("tet_centroid_sample: at most %d volumes (got %d)" % (_TCS_MAX_VOLUMES, len(volumes)))
+    B = pos.shape[0]
+    if tet_idx.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError("tet_centroid_sample: tet_idx must be int32 or int64 (got %s)" % str(tet_idx.dtype).replace("torch.", ""))
+    idx = _idx32(tet_idx)
+    if idx.dim() != 3 or idx.shape[2] != 4 or idx.shape[0] not in (1, B) or idx.device != pos.device:
+        raise RuntimeError("tet_centroid_sample: tet_idx [T,4] or [B,T,4] on the device of pos expected (got %s)" % (tuple(tet_idx.shape),))
+    T = idx.shape[1]
+    vols = []
+    for v in volumes:
+        v = _pv_need(v, torch.float32, "tet_centroid_sample: volume")
+        if v.dim() != 5 or v.shape[2] != v.shape[3] or v.shape[3] != v.shape[4] or v.shape[4] < 1:
+            raise RuntimeError("tet_centroid_sample: volumes [B,C,R,R,R] expected (got %s)" % (tuple(v.shape),))
+        if v.shape[0] != B or v.device != pos.device:
+            raise RuntimeError("tet_centroid_sample: volume %s and pos %s differ in batch or device" % (tuple(v.shape), tuple(pos.shape)))
+        vols.append(v)
+    first = int(first)
+    if select is not None:
+        if count is not None or first != 0:
+            raise RuntimeError("tet_centroid_sample: either select or the range first / count, not both")
+        if select.dim() != 1 or select.dtype not in (torch.int32, torch.int64) or select.device != pos.device:
+            raise RuntimeError("tet_centroid_sample: select must be an int32 / int64 tensor [K] on the device of pos")
+        select = select.to(torch.int32).contiguous()
+        K = select.shape[0]
+    else:
+        K = T - first if count is None else int(count)
+        if first < 0 or K < 0 or first + K > T:
+            raise RuntimeError("tet_centroid_sample: the range [%d, %d) does not lie in the %d tets" % (first, first + K, T))
+    if csr is not None and (len(csr) != 3 or csr[1].numel() != csr[2] * T * 4 or csr[0].numel() != csr[2] * pos.shape[1] + 1):
+        raise RuntimeError("tet_centroid_sample: csr is not tet_vertex_csr(tet_idx, %d) of this tet list" % pos.shape[1])
+    out, centroids = _TetCentroidSample.apply(pos, idx, csr, select, first, K, bool(append_pos), bool(check), *vols)
+    return (out, centroids) if return_centroids else out
 
 
 def trilinear_devoxelize_fwd(r, is_training, coords, features):

@@ -68,6 +68,12 @@ class TetTopology:
     def gather(self, vertice_pos):
         return _TetGather.apply(vertice_pos, self.tet_idx, self.csr)
 
+    def centroid_sample(self, volumes, vertice_pos, select=None, first=0, count=None, append_pos=True):
+        """hip_ops.tet_centroid_sample on this tet list: the volumes read at the centroids of the chosen tets, [B, sum C (+3), K],
+        with the gradient on vertice_pos through the cached incidence CSR and no [B,T,4,3] tensor in either direction."""
+        return hip_ops.tet_centroid_sample(volumes, vertice_pos, self.tet_idx32, csr=self.csr, select=select, first=first, count=count,
+                                           append_pos=append_pos)
+
     def vertex_adjacency(self, normalize=True):
         """hip_ops.VertexAdjacency of this tet list (D⁻¹A with `normalize`, else A), for DefTet.laplacian_sparse; built on the
         first call per `normalize` and kept."""

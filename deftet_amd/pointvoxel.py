@@ -5,6 +5,7 @@
     trilinear_devoxelize(c, coords, r, training=None)     functional/devoxelization.py:44-50 (the live, grid_sample form)
     trilinear_devoxelize_ori(features, coords, r, is_training=True)   the extension's own pair
     sample_f(point_pos, c_list, append_pos=False)         pc_model.py:182-194 in one operator
+    decode_occ_features(pos, tet_bxfx4, c_list, ...)      pc_model.py:276-306: the decoder's input from the vertices, in one operator
     backend                                               the twelve names of functional/src/bindings.cpp
 
 `overlay.install(point_voxel=True)` registers `backend` as `layers.pv_module.functional.backend._backend` and this module as
@@ -15,7 +16,7 @@ from torch.autograd import Function
 
 from . import hip_ops
 
-__all__ = ["avg_voxelize", "trilinear_devoxelize", "trilinear_devoxelize_ori", "sample_f", "backend"]
+__all__ = ["avg_voxelize", "trilinear_devoxelize", "trilinear_devoxelize_ori", "sample_f", "decode_occ_features", "backend"]
 
 
 class AvgVoxelization(Function):
@@ -73,6 +74,17 @@ def sample_f(point_pos, c_list, append_pos=False):
     """point_pos f32 [B,N,3] in [-0.5, 0.5], c_list of volumes [B,C_k,R_k,R_k,R_k] -> [B, sum C_k (+3), N]: sample_f, and with
     append_pos the torch.cat([feat, pos.permute(0,2,1)], 1) that decode_pos / decode_occ put behind it, in one result."""
     return hip_ops.voxel_sample(c_list, point_pos, append_pos=append_pos)
+
+
+def decode_occ_features(pos, tet_bxfx4, c_list, center_idx=None, first=0, count=None):
+    """occ_feature f32 [B, sum C_k + 3, K] of decode_occ (pc_model.py:276-306, pos_encoder = None): the volumes c_list read at the
+    centroids of the tets of (pos f32 [B,V,3], tet_bxfx4 int [B,T,4]) and the centroids behind them.  center_idx int [K]: the
+    tets the training step keeps (`randperm(T)[:10000]`); otherwise the range [first, first + count) of split_decode_occ's walk
+    (count=None: to the end).  The gathered [B,T,4,3] tensor, its mean and the index step are never built; the gradient reaches
+    pos through the topology's cached incidence CSR and every volume of c_list (hip_ops.tet_centroid_sample)."""
+    from .layers.DefTet.deftet import _topology_for
+    topo = _topology_for(tet_bxfx4, pos.shape[1])
+    return topo.centroid_sample(c_list, pos, select=center_idx, first=first, count=count, append_pos=True)
 
 
 class _Backend:

@@ -42,7 +42,9 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
-/* 320: marching tetrahedra on a per-vertex field — deftet_edge_vertex_csr_i32, deftet_marching_tets_count_f32 / _fill_f32 / _bwd_f32
+/* 330: tet-centroid feature sampling straight from the vertices — deftet_tet_centroid_sample_fwd_f32 / _bwd_pos_f32 /
+ *      _bwd_vertices_f32 and their workspace size (tet_centroid_sample.hip).
+ * 320: marching tetrahedra on a per-vertex field — deftet_edge_vertex_csr_i32, deftet_marching_tets_count_f32 / _fill_f32 / _bwd_f32
  *      and their workspace sizes (marching_tets.hip).
  * 310: ground-truth preparation — deftet_mesh_voxelize_f32, deftet_voxel_pack_u8 / _unpack_u8, deftet_extract_odms_u8,
  *      deftet_project_odms_i32, deftet_voxel_fill_b32, deftet_voxel_surface_count_b32 / _fill_b32, deftet_face_edges_i32 and their
@@ -871,6 +873,43 @@ int deftet_voxel_sample_bwd_vol_f32(const float *grad_out, const int32_t *perm, 
 int deftet_voxel_sample_bwd_pos_f32(const float *vol, const float *pos, const float *grad_out, float *grad_pos, int n_batch, int n_channel,
                                     int resolution, int n_point, int channel_offset, int n_channel_total, int pos_mode, int accumulate,
                                     void *stream);
+
+/* Tet-centroid feature sampling (330; tet_centroid_sample.hip): the input of the occupancy decoder,
+ * cat(sample_f(mean(gather(pos, tets), 2)[:, chosen], volumes), centroids^T) (layers/pc_model.py:276-306), from the vertices, the
+ * tet list and the chosen tets, with nothing of size O(T 4 3) in between.  No float atomics; two runs agree bit for bit.
+ *
+ * The volume list is three HOST arrays of n_vol <= 8 entries: device pointers vols[k] to f32 [B,C_k,R_k,R_k,R_k], channels[k] = C_k
+ * >= 0 and resolutions[k] = R_k >= 1.  pos f32 [B,V,3]; tet_idx i32 [idx_batch,T,4], idx_batch 1 (shared) or B, 16-byte aligned.
+ * Slot j < n_slot of every shape is tet select[j] (select i32 [n_slot], shared by the batch, repeats allowed) or, with select NULL,
+ * tet first + j (first >= 0, first + n_slot <= T).
+ *
+ * deftet_tet_centroid_sample_fwd_f32, one launch: cent = (((a + b) + c) + d) * 0.25f per coordinate, corners in list order, every
+ *   step rounded (no fused multiply-add with what follows); centroids f32 [B,n_slot,3] receives it, and out f32 [B, sum C_k (+3),
+ *   n_slot] receives at rows c_off_k + c what deftet_voxel_sample_fwd_f32 (pos_mode 0, legacy 0) computes at that value, and with
+ *   append_pos the value itself in its last three rows.  A tet index outside [0,T) or a vertex index outside [0,V) is not followed:
+ *   the slot's centroid and rows are NaN and *bad_flag (optional; the caller zeroes it) is set to 1.
+ * The gradient of the volumes is deftet_voxel_cells_f32 (centroids, pos_mode 0) + deftet_voxel_sample_bwd_vol_f32.
+ * deftet_tet_centroid_sample_bwd_pos_f32, one launch: grad_cent f32 [B,n_slot,3] = per volume the sum of
+ *   deftet_voxel_sample_bwd_pos_f32 (channels ascending from 0, scaled, border rule), the volumes' results added in list order, the
+ *   position rows of grad_out (with append_pos) added last: the bits of that chain of calls.  A slot with a NaN centroid gets 0.
+ * deftet_tet_centroid_sample_bwd_vertices_f32: grad_pos[b,v,:] (=, or += with accumulate) 0.25f * S, S = one fp32 accumulator from
+ *   0 over the incidences of v in the order of the incidence CSR (offsets / slots of deftet_tet_vertex_csr_i32: 4 t + corner
+ *   ascending) and, per incidence, over the slots that chose tet t in ascending slot.  Every element of grad_pos is written; a
+ *   vertex none of whose tets was chosen gets 0 (or keeps its value with accumulate).  A tet that lists a vertex twice counts
+ *   twice, a tet chosen n times counts n times, a select entry outside [0,T) counts nowhere.  With select the slots are grouped
+ *   by a stable radix sort in the workspace (256-byte aligned, deftet_tet_centroid_sample_workspace_bytes(B, T, n_slot)); without
+ *   it no workspace is needed. */
+size_t deftet_tet_centroid_sample_workspace_bytes(int n_batch, int n_tet, int n_slot);
+int deftet_tet_centroid_sample_fwd_f32(const float *const *vols, const int *channels, const int *resolutions, int n_vol, const float *pos,
+                                       const int32_t *tet_idx, const int32_t *select, int first, float *out, float *centroids,
+                                       int32_t *bad_flag, int n_batch, int n_vertex, int n_tet, int idx_batch, int n_slot, int append_pos,
+                                       void *stream);
+int deftet_tet_centroid_sample_bwd_pos_f32(const float *const *vols, const int *channels, const int *resolutions, int n_vol,
+                                           const float *centroids, const float *grad_out, float *grad_cent, int n_batch, int n_slot,
+                                           int append_pos, void *stream);
+int deftet_tet_centroid_sample_bwd_vertices_f32(const float *grad_cent, const int32_t *offsets, const int32_t *slots, const int32_t *select,
+                                                int first, float *grad_pos, int n_batch, int n_vertex, int n_tet, int idx_batch, int n_slot,
+                                                int accumulate, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Ground-truth preparation (310; dataprep.hip): what dataloader.py:24-61 (MakeSurfaceMesh) does with Kaolin's
  * trianglemeshes_to_voxelgrids, extract_odms, project_odms, voxelgrids_to_trianglemeshes and adjacency_matrix.  PARITY UNPINNED:
