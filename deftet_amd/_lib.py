@@ -156,6 +156,10 @@ SIGNATURES = {
     "deftet_tet_centroid_sample_fwd_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "deftet_tet_centroid_sample_bwd_pos_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "deftet_tet_centroid_sample_bwd_vertices_f32": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "deftet_tet_field_sample_workspace_bytes": (_sz, [_i, _i, _i]),
+    "deftet_tet_field_sample_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i, _vp]),
+    "deftet_tet_field_sample_bwd_w_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "deftet_tet_field_sample_bwd_field_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "deftet_mesh_voxelize_workspace_bytes": (_sz, [_i, _i]),
     "deftet_mesh_voxelize_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "deftet_voxel_pack_u8": (_i, [_vp, _i, _i, _vp, _vp]),

@@ -2538,6 +2538,179 @@ def tet_centroid_sample(volumes, pos_bxvx3, tet_idx, csr=None, select=None, firs
     return (out, centroids) if return_centroids else out
 
 
+# ------------------------------------------------------------------------------------
+# a per-vertex field at query points (tet_field_sample.hip)
+# ------------------------------------------------------------------------------------
+def _tfs_sizes(caller, field, idx, cond):
+    """(B, V, C, T, Bi, Q) of contiguous f32 field [B,V,C], int32 idx [Bi,T,4] and cond [B,Q,1] or [B,Q], checked against each other"""
+    if field.dim() != 3 or field.shape[2] < 1:
+        raise RuntimeError("%s: field [B,V,C] with a channel dimension of at least 1 expected (got %s)" % (caller, tuple(field.shape)))
+    B, V, C = field.shape
+    if idx.dim() != 3 or idx.shape[2] != 4 or idx.shape[0] not in (1, B):
+        raise RuntimeError("%s: tet_idx [T,4] or [B,T,4] expected (got %s)" % (caller, tuple(idx.shape)))
+    if cond.dim() not in (2, 3) or cond.shape[0] != B or cond.numel() != B * cond.shape[1]:
+        raise RuntimeError("%s: cond [B,Q,1] with the B of field expected (got %s)" % (caller, tuple(cond.shape)))
+    return B, V, C, idx.shape[1], idx.shape[0], cond.shape[1]
+
+
+def tet_field_sample_fwd(field, tet_idx, cond, bary, fill=0.0, bad=None):
+    """out f32 [B,Q,C] = ((w0 f(v0) + w1 f(v1)) + w2 f(v2)) + w3 f(v3) per channel, every step rounded, in the tet cond names
+    (v_k its vertices in tet_idx, w = bary); `fill` where cond is -1, NaN where a vertex index lies outside [0,V) (bad: an int32
+    [1] tensor set to 1 then).  One launch.  The raw forward of tet_field_sample."""
+    _lib.require_gpu(field, tet_idx, cond, bary, bad)
+    lib = _lib.load()
+    field, idx, cond, bary = _pv_need(field, torch.float32, "tet_field_sample: field"), _idx32(tet_idx), _f32c(cond), _f32c(bary)
+    B, V, C, T, Bi, Q = _tfs_sizes("tet_field_sample", field, idx, cond)
+    if bary.shape != (B, Q, 4):
+        raise RuntimeError("tet_field_sample: bary [B,Q,4] expected (got %s)" % (tuple(bary.shape),))
+    dev = field.device
+    out = torch.empty(B, Q, C, device=dev, dtype=torch.float32)
+    with _lib.on_device(dev):
+        _lib.check(lib.deftet_tet_field_sample_fwd_f32(_lib.ptr(field), _lib.ptr(idx), _lib.ptr(cond), _lib.ptr(bary), _lib.ptr(out),
+                                                       _lib.ptr(bad), float(fill), B, V, T, Bi, Q, C, _lib.current_stream(dev)),
+                   "deftet_tet_field_sample_fwd_f32")
+    return out
+
+
+def tet_field_sample_bwd_w(field, tet_idx, cond, gout):
+    """grad_w f32 [B,Q,4]: the gradient of tet_field_sample's result on the barycentric weights, grad_w[b,q,k] = the sum over the
+    channels in ascending order of gout[b,q,c] * f(v_k,c), one fp32 accumulator from 0; 0 on a miss.  One launch."""
+    _lib.require_gpu(field, tet_idx, cond, gout)
+    lib = _lib.load()
+    field, idx, cond, gout = _pv_need(field, torch.float32, "tet_field_sample: field"), _idx32(tet_idx), _f32c(cond), _f32c(gout)
+    B, V, C, T, Bi, Q = _tfs_sizes("tet_field_sample_bwd_w", field, idx, cond)
+    if gout.shape != (B, Q, C):
+        raise RuntimeError("tet_field_sample_bwd_w: gout [B,Q,C] = %s expected (got %s)" % ((B, Q, C), tuple(gout.shape)))
+    dev = field.device
+    gw = torch.empty(B, Q, 4, device=dev, dtype=torch.float32)
+    with _lib.on_device(dev):
+        _lib.check(lib.deftet_tet_field_sample_bwd_w_f32(_lib.ptr(field), _lib.ptr(idx), _lib.ptr(cond), _lib.ptr(gout), _lib.ptr(gw), B, V, T,
+                                                         Bi, Q, C, _lib.current_stream(dev)),
+                   "deftet_tet_field_sample_bwd_w_f32")
+    return gw
+
+
+def tet_field_sample_bwd_field(gout, cond, bary, csr, n_vertex, n_tet, out=None, accumulate=False):
+    """grad_field f32 [B,V,C]: per vertex, over its incidences in the CSR's order and per incidence (t, k) over the queries with
+    cond == t in ascending q, the sum of bary[b,q,k] * gout[b,q,c] in one fp32 accumulator from 0.  out: an existing contiguous f32
+    [B,V,C] to write into, or with `accumulate` to ADD to.  Every element is written: no memset, no atomics."""
+    _lib.require_gpu(gout, cond, bary, out)
+    lib = _lib.load()
+    gout, cond, bary = _f32c(gout), _f32c(cond), _f32c(bary)
+    offsets, slots, Bi = csr
+    if gout.dim() != 3 or gout.shape[2] < 1:
+        raise RuntimeError("tet_field_sample_bwd_field: gout [B,Q,C] expected (got %s)" % (tuple(gout.shape),))
+    B, Q, C = gout.shape
+    V, T = int(n_vertex), int(n_tet)
+    if slots.numel() != Bi * T * 4 or offsets.numel() != Bi * V + 1 or Bi not in (1, B):
+        raise RuntimeError("tet_field_sample_bwd_field: the CSR does not match the tet list / n_vertex")
+    if cond.numel() != B * Q or bary.shape != (B, Q, 4):
+        raise RuntimeError("tet_field_sample_bwd_field: cond [B,Q,1] and bary [B,Q,4] of gout %s expected" % (tuple(gout.shape),))
+    if out is not None and (out.shape != (B, V, C) or out.dtype != torch.float32 or not out.is_contiguous()):
+        raise RuntimeError("tet_field_sample_bwd_field: out must be contiguous f32 [B,V,C]")
+    if accumulate and out is None:
+        raise RuntimeError("tet_field_sample_bwd_field: accumulate needs out")
+    acc = bool(accumulate)
+    dev = gout.device
+    gfield = out if out is not None else torch.empty(B, V, C, device=dev, dtype=torch.float32)
+    with _lib.on_device(dev):
+        nbytes = lib.deftet_tet_field_sample_workspace_bytes(B, T, Q)
+        ws = _lib.workspace(dev, nbytes)
+        _lib.check(lib.deftet_tet_field_sample_bwd_field_f32(_lib.ptr(gout), _lib.ptr(cond), _lib.ptr(bary), _lib.ptr(offsets), _lib.ptr(slots),
+                                                             _lib.ptr(gfield), B, V, T, Bi, Q, C, 1 if acc else 0, _lib.ptr(ws), nbytes,
+                                                             _lib.current_stream(dev)),
+                   "deftet_tet_field_sample_bwd_field_f32")
+    return gfield
+
+
+class _TetFieldSample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, field, pos, pts, idx, csr, topology, fill, check, want_records):
+        rec = bool(want_records) and bwd_uses_records(idx.shape[1], pts.shape[1])
+        res = point_in_tet_indexed(pos, idx, pts, want_bary=True, want_hits=rec, order="auto", query_box="track", topology=topology,
+                                   check=check)
+        cond, bary, hits = res if rec else (res + (None,))
+        bad = torch.zeros(1, device=pos.device, dtype=torch.int32) if check else None
+        out = tet_field_sample_fwd(field, idx, cond, bary, fill=fill, bad=bad)
+        if check and int(bad.item()):
+            raise RuntimeError("tet_field_sample: a vertex index outside [0, %d)" % pos.shape[1])
+        ctx.save_for_backward(field, pos, pts, cond, bary, hits)
+        ctx.idx, ctx.csr = idx, csr
+        ctx.mark_non_differentiable(cond, bary)
+        return out, cond, bary
+
+    @staticmethod
+    def backward(ctx, gout, _gcond, _gbary):
+        field, pos, pts, cond, bary, hits = ctx.saved_tensors
+        V, T = pos.shape[1], ctx.idx.shape[1]
+        gout = _f32c(gout)
+        csr = ctx.csr
+        if csr is None:                                              # the slow path: a sort of 4 T incidences and a host sync per backward
+            csr = tet_vertex_csr(ctx.idx, V)
+        g_field = g_pos = g_pts = None
+        if ctx.needs_input_grad[0]:
+            g_field = tet_field_sample_bwd_field(gout, cond, bary, csr, V, T)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            gw = tet_field_sample_bwd_w(field.detach(), ctx.idx, cond, gout)
+            g_pos, g_pts = point_in_tet_indexed_bwd_to_vertices(pos.detach(), ctx.idx, pts.detach(), cond, gw, csr,
+                                                                want_grad_pts=ctx.needs_input_grad[2], hits=hits)
+            if not ctx.needs_input_grad[1]:
+                g_pos = None
+        return g_field, g_pos, g_pts, None, None, None, None, None, None
+
+
+def tet_field_sample(field, pos_bxvx3, tet_idx, pts_bxqx3, csr=None, topology=None, fill=0.0, return_index=False, check=False):
+    """f32 [B,Q,C]: the per-vertex field f32 [B,V,C] (an SDF or occupancy for marching_tets, vertex features, an offset) read at the
+    query points pts f32 [B,Q,3] in the tet mesh (pos f32 [B,V,3], tet_idx int [T,4] or [B,T,4]): value = sum_k w_k field[v_k] with
+    the barycentric weights w of the point in the lowest tet that holds it (point_in_tet_indexed's cond and bary), `fill` where
+    no tet holds it.  Per channel ((w0 f0 + w1 f1) + w2 f2) + w3 f3 in fp32, every step rounded.
+    Differentiable in field, pos and pts, each gradient computed only when asked for, without float atomics: field through a sort
+    of the queries by tet and the incidence CSR, in one fixed order (the same bits on every run); pos and pts through the gradient
+    on the weights and point_in_tet_indexed_bwd_to_vertices, whose order is fixed up to 2 queries per tet (bwd_uses_records).  `csr` = tet_vertex_csr(tet_idx, V), built once per tet list (a TetTopology handed in as
+    `topology` brings its own, and keys the traversal-order decision).  csr=None with a gradient asked for is the SLOW PATH: the
+    CSR is rebuilt in every backward (a sort and a host sync).  check=True synchronises and raises on a vertex index outside
+    [0,V); otherwise a row whose tet names one is NaN and its grad_w is 0.  return_index: also cond f32 [B,Q,1] and bary f32
+    [B,Q,4] (no gradient)."""
+    _lib.require_gpu(field, pos_bxvx3, tet_idx, pts_bxqx3)
+    field = _pv_need(field, torch.float32, "tet_field_sample: field")
+    pos = _pv_need(pos_bxvx3, torch.float32, "tet_field_sample: pos")
+    pts = _pv_need(pts_bxqx3, torch.float32, "tet_field_sample: pts")
+    if tet_idx.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError("tet_field_sample: tet_idx must be int32 or int64 (got %s)" % str(tet_idx.dtype).replace("torch.", ""))
+    if pos.dim() != 3 or pos.shape[2] != 3:
+        raise RuntimeError("tet_field_sample: pos [B,V,3] expected (got %s)" % (tuple(pos.shape),))
+    if pts.dim() != 3 or pts.shape[2] != 3:
+        raise RuntimeError("tet_field_sample: pts [B,Q,3] expected (got %s)" % (tuple(pts.shape),))
+    if field.dim() != 3 or field.shape[2] < 1:
+        raise RuntimeError("tet_field_sample: field [B,V,C] with a channel dimension of at least 1 expected (got %s)" % (tuple(field.shape),))
+    B, V, C = field.shape
+    if pos.shape[:2] != (B, V) or pts.shape[0] != B:
+        raise RuntimeError("tet_field_sample: field %s, pos %s and pts %s differ in B or V" % (tuple(field.shape), tuple(pos.shape), tuple(pts.shape)))
+    idx = getattr(topology, "tet_idx32", None)
+    if idx is None or (tet_idx is not getattr(topology, "tet_idx", None) and tet_idx is not idx):
+        idx = tet_idx
+    idx = _idx32(idx)
+    if idx.dim() != 3 or idx.shape[2] != 4 or idx.shape[0] not in (1, B):
+        raise RuntimeError("tet_field_sample: tet_idx [T,4] or [B,T,4] expected (got %s)" % (tuple(tet_idx.shape),))
+    if pos.device != field.device or pts.device != field.device or idx.device != field.device:
+        raise RuntimeError("tet_field_sample: field, pos, tet_idx and pts must be on one device")
+    T, Q = idx.shape[1], pts.shape[1]
+    if csr is None:
+        csr = getattr(topology, "csr", None)
+    if csr is not None and (len(csr) != 3 or csr[2] != idx.shape[0] or csr[1].numel() != csr[2] * T * 4 or csr[0].numel() != csr[2] * V + 1):
+        raise RuntimeError("tet_field_sample: csr is not tet_vertex_csr(tet_idx, %d) of this tet list" % V)
+    if Q == 0:
+        out, cond, bary = field.new_empty(B, 0, C), field.new_empty(B, 0, 1), field.new_empty(B, 0, 4)
+    else:
+        # (without a TetTopology the caller's own index tensor keys the traversal-order decision: its fingerprint is taken once)
+        # the hit records serve the gradient on pos and pts alone (point_in_tet_indexed_bwd_to_vertices); cond and bary do not
+        # depend on whether they are asked for
+        records = torch.is_grad_enabled() and (pos.requires_grad or pts.requires_grad)
+        out, cond, bary = _TetFieldSample.apply(field, pos, pts, idx, csr, topology if topology is not None else tet_idx, float(fill),
+                                                bool(check), records)
+    return (out, cond, bary) if return_index else out
+
+
 def trilinear_devoxelize_fwd(r, is_training, coords, features):
     """(outs f32 [B,C,N], inds i32 [B,8,N], wgts f32 [B,8,N]) of coords f32 [B,3,N] in voxel units and features f32 [B,C,r^3]: the
     extension's trilinear_devoxelize_forward, one fixed expression per point (the reference kernel's bits).  hi = lo where

@@ -74,6 +74,13 @@ class TetTopology:
         return hip_ops.tet_centroid_sample(volumes, vertice_pos, self.tet_idx32, csr=self.csr, select=select, first=first, count=count,
                                            append_pos=append_pos)
 
+    def field_sample(self, field, vertice_pos, pts, fill=0.0, return_index=False):
+        """hip_ops.tet_field_sample on this tet list: the per-vertex field [B,V,C] read at the points pts [B,Q,3] with the
+        barycentric weights of the tet that holds each, [B,Q,C] (`fill` outside the mesh), differentiable in field, vertice_pos and
+        pts through the cached incidence CSR."""
+        return hip_ops.tet_field_sample(field, vertice_pos, self.tet_idx32, pts, csr=self.csr, topology=self, fill=fill,
+                                        return_index=return_index)
+
     def vertex_adjacency(self, normalize=True):
         """hip_ops.VertexAdjacency of this tet list (D⁻¹A with `normalize`, else A), for DefTet.laplacian_sparse; built on the
         first call per `normalize` and kept."""
@@ -208,6 +215,12 @@ class DefTet(nn.Module):
         if indexed and tet_bxfx4x3 is None:
             return point_in_tet_occ_indexed(vertice_pos, point_pos_bxpx3, pred_tet_occ, topo)
         return point_in_tet_occ_vertices(vertice_pos, point_pos_bxpx3, pred_tet_occ, topo, tet_bxfx4x3)
+
+    # --- a per-vertex field (an SDF, an occupancy, features) at the query points: located as in occupancy_query, then interpolated
+    def field_query(self, vertice_pos, tetrahedron_bxfx4, point_pos_bxpx3, field):
+        """[B,Q,C]: field [B,V,C] interpolated at the query points with their barycentric weights in the mesh (vertice_pos,
+        tetrahedron_bxfx4), 0 where no tet holds the point; the gradient reaches field, vertice_pos and the points."""
+        return _topology_for(tetrahedron_bxfx4, vertice_pos.shape[1]).field_sample(field, vertice_pos, point_pos_bxpx3)
 
     # --- A11 (each call evaluates the fused kernel and returns its own component)
     def volume_variance(self, tet_bxfx4x3, base_area_mask=None, area_normalize=(20, 20), pow=2, center_occ=None):

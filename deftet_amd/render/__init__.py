@@ -4,3 +4,4 @@ from .camera import perspective, face_attributes, render_mesh_color  # noqa: F40
 from .laplacian import get_featlap  # noqa: F401
 from .vertices import render_vertices, model_forward  # noqa: F401
 from .iso_surface import marching_tets, model_tet_edges  # noqa: F401
+from .field_points import field_at_points, model_tet_topology  # noqa: F401

@@ -42,7 +42,9 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
-/* 330: tet-centroid feature sampling straight from the vertices — deftet_tet_centroid_sample_fwd_f32 / _bwd_pos_f32 /
+/* 340: a per-vertex field at located query points — deftet_tet_field_sample_fwd_f32 / _bwd_w_f32 / _bwd_field_f32 and their
+ *      workspace size (tet_field_sample.hip).
+ * 330: tet-centroid feature sampling straight from the vertices — deftet_tet_centroid_sample_fwd_f32 / _bwd_pos_f32 /
  *      _bwd_vertices_f32 and their workspace size (tet_centroid_sample.hip).
  * 320: marching tetrahedra on a per-vertex field — deftet_edge_vertex_csr_i32, deftet_marching_tets_count_f32 / _fill_f32 / _bwd_f32
  *      and their workspace sizes (marching_tets.hip).
@@ -910,6 +912,39 @@ int deftet_tet_centroid_sample_bwd_pos_f32(const float *const *vols, const int *
 int deftet_tet_centroid_sample_bwd_vertices_f32(const float *grad_cent, const int32_t *offsets, const int32_t *slots, const int32_t *select,
                                                 int first, float *grad_pos, int n_batch, int n_vertex, int n_tet, int idx_batch, int n_slot,
                                                 int accumulate, void *workspace, size_t workspace_bytes, void *stream);
+
+/* A per-vertex field at query points (340; tet_field_sample.hip): value(p) = sum_k w_k(p) field[vertex k of the
+ * tet that holds p], on what the indexed query (deftet_point_in_tet_indexed_f32) returned for the same pos, list and points.
+ * No float atomics; two runs agree bit for bit.
+ *
+ * field f32 [B,V,C], channels last, C >= 1; tet_idx i32 [idx_batch,T,4], idx_batch 1 (shared) or B, 16-byte aligned; cond f32
+ * [B,Q,1], -1 = miss; bary f32 [B,Q,4], 16-byte aligned; out, grad_out f32 [B,Q,C].  With t = (int)cond[b,q], ib = 0 when
+ * idx_batch == 1, else b, and v_k = tet_idx[ib,t,k]:
+ *
+ * deftet_tet_field_sample_fwd_f32, one launch: out[b,q,c] = ((w0 f(v0,c) + w1 f(v1,c)) + w2 f(v2,c)) + w3 f(v3,c), every product
+ *   and every sum rounded in fp32, in that order (no fused multiply-add).  A miss writes `fill` in every channel.  A vertex index
+ *   outside [0,V) (or a cond outside [-1,T)) is not followed: the row is NaN and *bad_flag (optional; the caller zeroes it) is set
+ *   to 1.  One lane per query up to C = 8, lanes over the channels of a row beyond.
+ * deftet_tet_field_sample_bwd_w_f32, one launch: grad_w[b,q,k] = sum over c ascending of the rounded grad_out[b,q,c] * f(v_k,c),
+ *   one fp32 accumulator from 0; a miss and a row the forward refused give 0.  grad_w f32 [B,Q,4] is what
+ *   deftet_point_in_tet_indexed_bwd_to_vertices_f32 takes (with the forward's hit records) to grad_pos [B,V,3] and grad_pts.
+ * deftet_tet_field_sample_bwd_field_f32: grad_field[b,v,c] (=, or += with accumulate) S, S = one fp32 accumulator from 0 over
+ *   the incidences of v in the order of the incidence CSR (offsets / slots of deftet_tet_vertex_csr_i32 over the same list:
+ *   4 t + corner ascending) and, per incidence (t, k), over the queries q of shape b with cond == t in ascending q, of the
+ *   rounded product bary[b,q,k] * grad_out[b,q,c].  Every element of grad_field is written; a vertex none of whose tets was hit
+ *   gets 0 (or keeps its value with accumulate); a tet that lists a vertex twice counts twice.  The per-tet query lists come from
+ *   a stable radix sort of the keys b (T + 1) + t (misses at t = T) with the queries as values, in the workspace (256-byte
+ *   aligned, deftet_tet_field_sample_workspace_bytes(B, T, Q)); without a query no workspace is needed.  A vertex runs as long
+ *   as the lists of its tets: load skew is accepted. */
+size_t deftet_tet_field_sample_workspace_bytes(int n_batch, int n_tet, int n_query);
+int deftet_tet_field_sample_fwd_f32(const float *field, const int32_t *tet_idx, const float *cond, const float *bary, float *out,
+                                    int32_t *bad_flag, float fill, int n_batch, int n_vertex, int n_tet, int idx_batch, int n_query,
+                                    int n_channel, void *stream);
+int deftet_tet_field_sample_bwd_w_f32(const float *field, const int32_t *tet_idx, const float *cond, const float *grad_out, float *grad_w,
+                                      int n_batch, int n_vertex, int n_tet, int idx_batch, int n_query, int n_channel, void *stream);
+int deftet_tet_field_sample_bwd_field_f32(const float *grad_out, const float *cond, const float *bary, const int32_t *offsets,
+                                          const int32_t *slots, float *grad_field, int n_batch, int n_vertex, int n_tet, int idx_batch,
+                                          int n_query, int n_channel, int accumulate, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Ground-truth preparation (310; dataprep.hip): what dataloader.py:24-61 (MakeSurfaceMesh) does with Kaolin's
  * trianglemeshes_to_voxelgrids, extract_odms, project_odms, voxelgrids_to_trianglemeshes and adjacency_matrix.  PARITY UNPINNED:
