@@ -118,14 +118,16 @@ __global__ __launch_bounds__(256) void k_prep(const float *__restrict__ verts, c
     faces += (size_t)M.fBase * 3;
     BoxStats<2, 0> bs;                                               // (y, z) box of the regular faces
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < F; k += gridDim.x * blockDim.x) {
-        long long i0 = faces[(size_t)k * 3], i1 = faces[(size_t)k * 3 + 1], i2 = faces[(size_t)k * 3 + 2];
+        const long long i0 = faces[(size_t)k * 3], i1 = faces[(size_t)k * 3 + 1], i2 = faces[(size_t)k * 3 + 2];
+        // a face with an index outside its mesh reads NO vertex (a mesh may have none: vertex 0 would be the next mesh's, or
+        // past the array); its record has e1 = e2 = 0, a = 0 and kind 0 — it never hits, as vertex 0 three times would not
+        float v1[3] = {0.f, 0.f, 0.f}, v2[3] = {0.f, 0.f, 0.f}, v3[3] = {0.f, 0.f, 0.f};
         if (i0 < 0 || i0 >= V || i1 < 0 || i1 >= V || i2 < 0 || i2 >= V) {      // torch.index_select raises
             *bad = 1;
-            i0 = i1 = i2 = 0;
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { v1[c] = vb[i0 * 3 + c]; v2[c] = vb[i1 * 3 + c]; v3[c] = vb[i2 * 3 + c]; }
         }
-        const float v1[3] = {vb[i0 * 3], vb[i0 * 3 + 1], vb[i0 * 3 + 2]};
-        const float v2[3] = {vb[i1 * 3], vb[i1 * 3 + 1], vb[i1 * 3 + 2]};
-        const float v3[3] = {vb[i2 * 3], vb[i2 * 3 + 1], vb[i2 * 3 + 2]};
         const float e1x = v2[0] - v1[0], e1y = v2[1] - v1[1], e1z = v2[2] - v1[2];
         const float e2x = v3[0] - v1[0], e2y = v3[1] - v1[1], e2z = v3[2] - v1[2];
         const float a = e1y * (-e2z) + e1z * e2y;

@@ -1,7 +1,8 @@
 """N1: kal.ops.mesh.check_sign restated.  PARITY UNPINNED (Kaolin is not in the
 reference tree): the HIP paths are bit-exact (crossing COUNTS, not only parity) against
 oracle/deftet_oracle_sign.c and against each other, and pinned semantically: the centroid of a tet
-is inside the closed boundary surface of a tet subset iff its tet belongs to the subset."""
+is inside the closed boundary surface of a tet subset iff its tet belongs to the subset.
+Ground-truth mesh sizes, the size switches and the fp64 winding-number pin: test_check_sign_sizes_gpu.py."""
 import numpy as np
 import pytest
 import torch
