@@ -180,6 +180,9 @@ SIGNATURES = {
     "deftet_marching_tets_fill_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _ll, _ll, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp, _sz, _vp]),
     "deftet_marching_tets_bwd_f32": (_i, [_vp, _vp, _ll, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    "deftet_tet_components_workspace_bytes": (_sz, [_i, _i]),
+    "deftet_tet_components_u8": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "deftet_occupancy_cleanup_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lock = threading.Lock()

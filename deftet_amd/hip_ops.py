@@ -1906,6 +1906,114 @@ def surface_weld(verts_vx3, faces_fx3, attrs=None):
     return vout[:n_used], (aout[:n_used] if aout is not None else None), fout, old[:n_used]
 
 
+# --------------------------------------------------------------------------------- connected tet components
+TetComponents = collections.namedtuple("TetComponents", "labels sizes open count")
+
+
+def _inside_u8(caller, inside, nbr):
+    """(uint8 [B,T] view or copy of `inside`, whether the input had no batch dimension)"""
+    if not isinstance(nbr, TetFaceNeighbours):
+        raise TypeError("%s: nbr must be a TetFaceNeighbours (tet_face_neighbours / neighbours_from_adj_list)" % caller)
+    _lib.require_gpu(inside, nbr.table32)
+    single = inside.dim() == 1
+    m = inside.reshape(1, -1) if single else inside
+    if m.dim() != 2 or int(m.shape[1]) != nbr.n_tet or m.shape[0] < 1 or m.device != nbr.device:
+        raise RuntimeError("%s: inside [B,%d] or [%d] on %s expected, got %s on %s"
+                           % (caller, nbr.n_tet, nbr.n_tet, nbr.device, tuple(inside.shape), inside.device))
+    if m.dtype not in (torch.bool, torch.uint8):
+        m = m != 0                                      # (NaN != 0: inside)
+    m = m.contiguous()
+    return (m.view(torch.uint8) if m.dtype == torch.bool else m), single
+
+
+def _bad_neighbour(caller, bad):
+    if int(bad.item()):
+        raise RuntimeError("%s: a neighbour index is out of range" % caller)
+
+
+def _components_out(B, T, dev):
+    return (torch.empty(B, T, dtype=torch.int32, device=dev), torch.empty(B, T, dtype=torch.int32, device=dev),
+            torch.empty(B, T, dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+
+
+def _components_result(parts, single):
+    labels, sizes, opn, count = parts
+    opn = opn.view(torch.bool)
+    return TetComponents(labels[0], sizes[0], opn[0], count) if single else TetComponents(labels, sizes, opn, count)
+
+
+def _tet_components(inside, nbr):
+    """tet_components without the read-back: (TetComponents, bad int32 [1] on the device)"""
+    lib = _lib.load()
+    m, single = _inside_u8("tet_components", inside, nbr)
+    B, T = int(m.shape[0]), int(m.shape[1])
+    dev = m.device
+    parts = _components_out(B, T, dev)
+    bad = torch.empty(1, dtype=torch.int32, device=dev)
+    with _lib.on_device(dev):
+        ws = _lib.workspace(dev, lib.deftet_tet_components_workspace_bytes(B, T))
+        _lib.check(lib.deftet_tet_components_u8(_lib.ptr(m), _lib.ptr(nbr.table32), B, T, _lib.ptr(parts[0]), _lib.ptr(parts[1]),
+                                                _lib.ptr(parts[2]), _lib.ptr(parts[3]), _lib.ptr(bad), _lib.ptr(ws), ws.numel(),
+                                                _lib.current_stream(dev)), "deftet_tet_components_u8")
+    return _components_result(parts, single), bad
+
+
+def tet_components(inside, nbr, check=True):
+    """Connected components of the inside tets of every shape: TetComponents(labels, sizes, open, count), all on the device.
+    inside bool / uint8 / float [B,T] or [T] (non-zero = inside); nbr a TetFaceNeighbours, taken as undirected: two inside tets
+    are connected when either stands in the other's row.  labels int32 = -1 outside, otherwise the smallest tet index of the
+    component (the same bits on every run, whatever the schedule); sizes int32 = tets of the component at its label's index, 0
+    elsewhere; open bool = at the label's index, whether a tet of the component has a -1 entry in its row (the component
+    reaches the grid boundary); count int32 [B] ([1] for a [T] input) = components per shape.
+    The results themselves are not read back.  The count of neighbour entries outside [-1, T) is: four bytes, in this call,
+    because nothing later in it synchronises; a non-zero count raises RuntimeError (such an entry is never followed, so the
+    components it does not touch are still right).  check=False skips that read and the error with it."""
+    comps, bad = _tet_components(inside, nbr)
+    if check:
+        _bad_neighbour("tet_components", bad)
+    return comps
+
+
+def _occupancy_cleanup(inside, nbr, keep_largest, min_size, fill_voids, return_components):
+    """occupancy_cleanup without the read-back: (keep, TetComponents or None, bad int32 [1] on the device)"""
+    lib = _lib.load()
+    m, single = _inside_u8("occupancy_cleanup", inside, nbr)
+    if int(min_size) < 0:
+        raise ValueError("occupancy_cleanup: min_size=%d is negative" % min_size)
+    B, T = int(m.shape[0]), int(m.shape[1])
+    dev = m.device
+    keep = torch.empty(B, T, dtype=torch.uint8, device=dev)
+    parts = _components_out(B, T, dev) if return_components else (None, None, None, None)
+    bad = torch.empty(1, dtype=torch.int32, device=dev)
+    with _lib.on_device(dev):
+        ws = _lib.workspace(dev, lib.deftet_tet_components_workspace_bytes(B, T))
+        _lib.check(lib.deftet_occupancy_cleanup_u8(_lib.ptr(m), _lib.ptr(nbr.table32), B, T, int(bool(keep_largest)), int(min_size),
+                                                   int(bool(fill_voids)), _lib.ptr(keep), _lib.ptr(parts[0]), _lib.ptr(parts[1]),
+                                                   _lib.ptr(parts[2]), _lib.ptr(parts[3]), _lib.ptr(bad), _lib.ptr(ws), ws.numel(),
+                                                   _lib.current_stream(dev)), "deftet_occupancy_cleanup_u8")
+    keep = keep.view(torch.bool)
+    return (keep[0] if single else keep), (_components_result(parts, single) if return_components else None), bad
+
+
+def occupancy_cleanup(inside, nbr, keep_largest=False, min_size=0, fill_voids=False, return_components=False, check=True):
+    """Cleans a per-tet occupancy on the device: keep bool [B,T] ([T] for a [T] input).  In this order: fill_voids turns every
+    component of the OUTSIDE tets that does not reach the grid boundary into inside; the filled mask is labelled; min_size = m > 0
+    drops the components with fewer than m tets; keep_largest keeps the component with the most tets among those left, the one
+    with the smaller label among equal sizes (an empty shape stays empty).  With no option set keep is the inside mask.
+    return_components=True returns (keep, TetComponents) with the components of the filled mask, the labelling the selection
+    was made on.  inside, nbr and the four-byte read of the bad-neighbour count (check) as in tet_components."""
+    keep, comps, bad = _occupancy_cleanup(inside, nbr, keep_largest, min_size, fill_voids, return_components)
+    if check:
+        _bad_neighbour("occupancy_cleanup", bad)
+    return (keep, comps) if return_components else keep
+
+
+def cleaned_occupancy(occ, inside, keep):
+    """occ with the outcome of occupancy_cleanup written into it: 0 where an inside tet was dropped, 1 where an outside tet was
+    filled, occ everywhere else (all three of one shape)."""
+    return torch.where(keep, torch.where(inside, occ, torch.ones_like(occ)), torch.where(inside, torch.zeros_like(occ), occ))
+
+
 # --------------------------------------------------------------------------------- marching tetrahedra (DESIGN.md §6l)
 IsoMesh = collections.namedtuple("IsoMesh", "verts faces vert_attr edge_id t tet_id")
 

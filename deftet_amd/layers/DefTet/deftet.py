@@ -197,6 +197,22 @@ class DefTet(nn.Module):
     def get_internal_index(self, tet_face_fx3, tet_idx_fx2, occ_bxn):
         return hip_ops.boundary_index(tet_face_fx3, tet_idx_fx2, occ_bxn, mode=2)
 
+    # --- what the reference leaves to trimesh on the host ("use trimesh to fix the surface", utils/tet_utils.py:474)
+    def clean_occupancy(self, occ_bxn, nbr, thres=0.5, keep_largest=True, min_size=0, fill_voids=False):
+        """occ_bxn [B,T] / [B,T,1] with its floaters dropped and its enclosed voids filled, on the device (hip_ops.occupancy_cleanup
+        on the mask occ > thres): float32 of the input's shape, 0 where an inside tet was dropped, 1 where an outside tet was
+        filled, the input's value everywhere else — a 0 / 1 occupancy stays 0 / 1 and goes straight into get_boundary_index and
+        hip_ops.surface_extract(mode="binary").  nbr: hip_ops.tet_face_neighbours of the tet list (or the reference's list of
+        four sparse matrices).  No gradient."""
+        occ = occ_bxn.detach().float()
+        if occ.dim() not in (2, 3) or (occ.dim() == 3 and occ.shape[2] != 1):
+            raise RuntimeError("clean_occupancy: occ [B,T] or [B,T,1] expected, got %s" % (tuple(occ_bxn.shape),))
+        flat = occ.reshape(occ.shape[0], -1)
+        nbr = hip_ops.neighbours_from_adj_list(nbr, flat.device)
+        inside = flat > thres
+        keep = hip_ops.occupancy_cleanup(inside, nbr, keep_largest=keep_largest, min_size=min_size, fill_voids=fill_voids)
+        return hip_ops.cleaned_occupancy(flat, inside, keep).reshape(occ.shape)
+
     # --- A1 / A1b
     def check_condition(self, tet_bxfx4x3, point_pos_bxpx3):
         return check_condition_f_base(tet_bxfx4x3, point_pos_bxpx3)

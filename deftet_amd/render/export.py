@@ -71,7 +71,7 @@ def _write(path, text):
 
 
 def save_surface_objs(points_px3, feat, tet_tx4, nbr, savedir, prefix, thresholds=(0.005, 0.05, 0.15, 0.25), welded=False,
-                      iso=None):
+                      iso=None, keep_largest=False, min_component=0, fill_voids=False):
     """Writes what Deftet.saveobj writes (3_model/deftet.py:533-557): for every threshold `tet-geo-<prefix>-thres-<t>.obj` and
     `tet-color-<prefix>-thres-<t>.obj`.  `feat` = (weights [P] / [P,1], colours [P,3]) as `processfunc` returns them, or one
     [P,4] tensor holding them side by side; the colours are written reversed (colorsnp_px3[:, ::-1], :513).  The per-tet
@@ -81,7 +81,13 @@ def save_surface_objs(points_px3, feat, tet_tx4, nbr, savedir, prefix, threshold
     one surface_extract call (its own read-back of the offsets, the fused maximum computed again) and, with welded, one more
     read-back in surface_weld.  With `iso` it additionally writes `mt-geo-<prefix>-iso-<iso>.obj` and `mt-color-<prefix>-iso-<iso>.obj`:
     the marching-tetrahedra surface of the per-vertex weights at that level (hip_ops.marching_tets) as an indexed mesh, without and
-    with the colours, faces in the operator's winding (normals towards the lower weights)."""
+    with the colours, faces in the operator's winding (normals towards the lower weights).
+    keep_largest / min_component / fill_voids clean the occupancy of every threshold on the device before its surface is taken
+    (hip_ops.occupancy_cleanup: floaters dropped, enclosed voids filled; the reference leaves this to trimesh, utils_tetsv.py:132):
+    the per-tet occupancy is then a torch maximum over the corner weights (the fused maximum, bit for bit, on finite weights),
+    inside = occ > float32(2 thres) — the threshold mode's own inside test — a dropped tet gets 0, a filled one 1, and the result
+    goes to surface_extract as `occ`.  With all three left at their defaults nothing of this runs.  The `mt-` files are not
+    cleaned: a per-vertex field has no per-tet mask."""
     if isinstance(feat, (tuple, list)):
         weights, colours = feat
     else:
@@ -96,9 +102,18 @@ def save_surface_objs(points_px3, feat, tet_tx4, nbr, savedir, prefix, threshold
     tet_c = col[tet.reshape(-1)].reshape(1, -1, 4, 3)
     w = hip_ops._f32c(weights).reshape(1, -1)
     paths = []
+    clean = bool(keep_largest) or int(min_component) > 0 or bool(fill_voids)
+    occ = w[:, tet.reshape(-1)].reshape(1, -1, 4).amax(dim=2) if clean else None
     for thres in thresholds:
-        soup = hip_ops.surface_extract(tet_p, None, nbr, "threshold", thres=thres, attr=tet_c, vertex_weights=w, tet_idx=tet,
-                                       return_faces=welded)
+        if clean:
+            inside = occ > float(np.float32(2.0 * thres))
+            keep, _comps, bad = hip_ops._occupancy_cleanup(inside, nbr, keep_largest, min_component, fill_voids, False)
+            soup = hip_ops.surface_extract(tet_p, hip_ops.cleaned_occupancy(occ, inside, keep), nbr, "threshold", thres=thres, attr=tet_c,
+                                           tet_idx=tet, return_faces=welded)
+            hip_ops._bad_neighbour("save_surface_objs", bad)   # (read behind the extraction's own synchronisation)
+        else:
+            soup = hip_ops.surface_extract(tet_p, None, nbr, "threshold", thres=thres, attr=tet_c, vertex_weights=w, tet_idx=tet,
+                                           return_faces=welded)
         face, fcol = soup.face[0].cpu().numpy(), soup.face_attr[0].cpu().numpy()
         paths.append("%s/tet-geo-%s-thres-%.3f.obj" % (savedir, prefix, thres))
         _write(paths[-1], soup_obj_text(face))

@@ -42,7 +42,9 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
-/* 340: a per-vertex field at located query points — deftet_tet_field_sample_fwd_f32 / _bwd_w_f32 / _bwd_field_f32 and their
+/* 350: connected components of the inside tets and the occupancy clean-up on them — deftet_tet_components_u8,
+ *      deftet_occupancy_cleanup_u8 and their workspace size (tet_components.hip).
+ * 340: a per-vertex field at located query points — deftet_tet_field_sample_fwd_f32 / _bwd_w_f32 / _bwd_field_f32 and their
  *      workspace size (tet_field_sample.hip).
  * 330: tet-centroid feature sampling straight from the vertices — deftet_tet_centroid_sample_fwd_f32 / _bwd_pos_f32 /
  *      _bwd_vertices_f32 and their workspace size (tet_centroid_sample.hip).
@@ -336,6 +338,29 @@ size_t deftet_surface_weld_workspace_bytes(int n_vertex);
 int deftet_surface_weld_f32(const int64_t *faces_fx3, long long n_face, const float *verts_vx3, const float *attr_vxc, int n_attr,
                             int n_vertex, int capacity, int32_t *n_out, int64_t *old_id, float *verts_out, float *attr_out,
                             int64_t *faces_out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * Connected components of a per-tet occupancy (350; tet_components.hip).  The reference leaves this to trimesh on
+ * the host ("use trimesh to fix the surface": utils/tet_utils.py:474, utils/mesh_utils.py:259,270, 3_model/utils_tetsv.py:132,229).
+ * inside_bxt uint8 [B,T] (non-zero = inside); nbr32_tx4 int32 [T,4] as above (16-byte aligned), shared by the shapes and taken
+ * as undirected: tets t and u of one shape are connected when both are inside and u stands in row t or t in row u.
+ * Per shape: labels int32 [B,T] = -1 outside, otherwise the SMALLEST tet index of the component (independent of the schedule);
+ * sizes int32 [B,T] = tets of the component at its label's index, 0 elsewhere; open uint8 [B,T] = 1 at the label's index when a
+ * tet of the component has a -1 entry in its row (the component reaches the grid boundary), 0 elsewhere; count int32 [B] =
+ * components of the shape.  bad int32 [1] (device) = neighbour entries outside [-1, n_tet): counted, never followed (it also
+ * counts a parent chain or a retry loop that ran out of its trip bound: neither can happen).  n_batch <= 65535,
+ * n_batch * n_tet < 2^31.  Integer atomics only: the same bits on every run. */
+size_t deftet_tet_components_workspace_bytes(int n_batch, int n_tet);
+int deftet_tet_components_u8(const uint8_t *inside_bxt, const int32_t *nbr32_tx4, int n_batch, int n_tet, int32_t *labels, int32_t *sizes,
+                             uint8_t *open, int32_t *count, int32_t *bad, void *workspace, size_t workspace_bytes, void *stream);
+/* The clean-up, one device sequence without a read-back, in this order: (1) fill_voids: the components of the COMPLEMENT are
+ * labelled and every one whose open flag is 0 becomes inside; (2) the filled mask is labelled; (3) min_size = m > 0 drops the
+ * components with fewer than m tets; (4) keep_largest keeps the component with the most tets among those left, the smaller label
+ * among equal sizes (an empty shape stays empty).  keep uint8 [B,T] = 0 / 1.  labels, sizes, open and count are optional, all or
+ * none: the components of step (2), the labelling the selection was made on.  Same workspace size as above. */
+int deftet_occupancy_cleanup_u8(const uint8_t *inside_bxt, const int32_t *nbr32_tx4, int n_batch, int n_tet, int keep_largest,
+                                int min_size, int fill_voids, uint8_t *keep, int32_t *labels, int32_t *sizes, uint8_t *open,
+                                int32_t *count, int32_t *bad, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------
  * Marching tetrahedra on a per-vertex field (320; marching_tets.hip): a welded iso-surface mesh per shape, with
