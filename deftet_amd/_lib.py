@@ -152,6 +152,12 @@ SIGNATURES = {
     "deftet_voxel_cells_from_inds_i32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     "deftet_voxel_sample_bwd_vol_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "deftet_voxel_sample_bwd_pos_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "deftet_image_sample_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "deftet_image_sample_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "deftet_image_cells_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "deftet_image_sample_bwd_map_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "deftet_image_sample_bwd_uv_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "deftet_image_sample_bwd_global_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     "deftet_tet_centroid_sample_workspace_bytes": (_sz, [_i, _i, _i]),
     "deftet_tet_centroid_sample_fwd_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "deftet_tet_centroid_sample_bwd_pos_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -2487,6 +2487,144 @@ def voxel_sample(volumes, pos, append_pos=False, voxel_units=False):
     return _VoxelSample.apply(pos, bool(append_pos), 1 if voxel_units else 0, *vols)
 
 
+# --------------------------------------------------------------------------------- pixel-aligned image features
+class ImageCells:
+    """The points of one uv set sorted by the cell they fall in at one map size (deftet_image_cells_f32): what the backward to
+    the maps gathers through.  Maps of equal (H, W) share it."""
+    __slots__ = ("perm", "seg", "wsorted", "B", "N", "H", "W")
+
+
+def _image_cells(lib, uv, B, N, H, W, border, align):
+    dev = uv.device
+    cells = ImageCells()
+    cells.B, cells.N, cells.H, cells.W = B, N, H, W
+    cells.perm = torch.empty(B * N, device=dev, dtype=torch.int32)
+    cells.seg = torch.empty(B * (H + 1) * (W + 1) + 1, device=dev, dtype=torch.int32)
+    cells.wsorted = torch.empty(4, B * N, device=dev, dtype=torch.float32)
+    with _lib.on_device(dev):
+        nbytes = lib.deftet_image_sample_workspace_bytes(B, N, H, W)
+        ws = _lib.workspace(dev, nbytes)
+        _lib.check(lib.deftet_image_cells_f32(_lib.ptr(uv), _lib.ptr(cells.perm), _lib.ptr(cells.seg), _lib.ptr(cells.wsorted), B, N, H, W,
+                                              border, align, _lib.ptr(ws), nbytes, _lib.current_stream(dev)), "deftet_image_cells_f32")
+    return cells
+
+
+def _image_bwd_map(lib, gout, cells, C, c_off, C_total):
+    B, N, H, W, dev = cells.B, cells.N, cells.H, cells.W, gout.device
+    gmap = torch.empty(B, C, H, W, device=dev, dtype=torch.float32)
+    with _lib.on_device(dev):
+        nbytes = lib.deftet_image_sample_workspace_bytes(B, N, H, W)
+        ws = _lib.workspace(dev, nbytes)
+        _lib.check(lib.deftet_image_sample_bwd_map_f32(_lib.ptr(gout), _lib.ptr(cells.perm), _lib.ptr(cells.seg), _lib.ptr(cells.wsorted),
+                                                       _lib.ptr(gmap), B, C, H, W, N, c_off, C_total, _lib.ptr(ws), nbytes,
+                                                       _lib.current_stream(dev)), "deftet_image_sample_bwd_map_f32")
+    return gmap
+
+
+class _ImageSample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, uv, glob, app, border, align, *maps):
+        lib = _lib.load()
+        dev = uv.device
+        B, N = uv.shape[0], uv.shape[1]
+        G = glob.shape[1] if glob is not None else 0
+        A = app.shape[2] if app is not None else 0
+        C_total = G + sum(m.shape[1] for m in maps) + A
+        out = torch.empty(B, C_total, N, device=dev, dtype=torch.float32)
+        with _lib.on_device(dev):
+            st = _lib.current_stream(dev)
+            c_off = G
+            for k, m in enumerate(maps):                             # the first launch also writes the global and the appended rows
+                first = k == 0
+                _lib.check(lib.deftet_image_sample_fwd_f32(_lib.ptr(m), _lib.ptr(uv), _lib.ptr(glob) if first else None,
+                                                           _lib.ptr(app) if first else None, _lib.ptr(out), B, m.shape[1], m.shape[2],
+                                                           m.shape[3], N, G if first else 0, A if first else 0, c_off, C_total, border, align,
+                                                           st), "deftet_image_sample_fwd_f32")
+                c_off += m.shape[1]
+            if not maps and G + A > 0:
+                _lib.check(lib.deftet_image_sample_fwd_f32(None, _lib.ptr(uv), _lib.ptr(glob), _lib.ptr(app), _lib.ptr(out), B, 0, 1, 1, N, G, A,
+                                                           G, C_total, border, align, st), "deftet_image_sample_fwd_f32")
+        ctx.save_for_backward(uv, *maps)
+        ctx.args = (border, align, B, N, G, A, C_total)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        uv, maps = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        border, align, B, N, G, A, C_total = ctx.args
+        lib = _lib.load()
+        dev = uv.device
+        gout = _f32c(gout)
+        grads, cells, c_off = [], {}, G
+        for k, m in enumerate(maps):
+            C, H, W = m.shape[1], m.shape[2], m.shape[3]
+            if ctx.needs_input_grad[5 + k]:
+                if (H, W) not in cells:                              # one sort per uv set and distinct map size
+                    cells[(H, W)] = _image_cells(lib, uv, B, N, H, W, border, align)
+                grads.append(_image_bwd_map(lib, gout, cells[(H, W)], C, c_off, C_total))
+            else:
+                grads.append(None)
+            c_off += C
+        guv = None
+        if ctx.needs_input_grad[0]:
+            guv = torch.zeros_like(uv) if not maps else torch.empty_like(uv)
+            c_off = G
+            with _lib.on_device(dev):
+                for k, m in enumerate(maps):                         # list order; channels ascending inside the kernel
+                    _lib.check(lib.deftet_image_sample_bwd_uv_f32(_lib.ptr(m), _lib.ptr(uv), _lib.ptr(gout), _lib.ptr(guv), B, m.shape[1],
+                                                                  m.shape[2], m.shape[3], N, c_off, C_total, border, align, int(k > 0),
+                                                                  _lib.current_stream(dev)), "deftet_image_sample_bwd_uv_f32")
+                    c_off += m.shape[1]
+        gglob = None
+        if G > 0 and ctx.needs_input_grad[1]:
+            gglob = torch.empty(B, G, device=dev, dtype=torch.float32)
+            with _lib.on_device(dev):
+                _lib.check(lib.deftet_image_sample_bwd_global_f32(_lib.ptr(gout), _lib.ptr(gglob), B, G, N, C_total, _lib.current_stream(dev)),
+                           "deftet_image_sample_bwd_global_f32")
+        elif ctx.needs_input_grad[1]:
+            gglob = torch.zeros(B, 0, device=dev, dtype=torch.float32)
+        gapp = gout[:, C_total - A:, :].transpose(1, 2).contiguous() if ctx.needs_input_grad[2] else None
+        return (guv, gglob, gapp, None, None) + tuple(grads)
+
+
+def image_sample(maps, uv, global_features=None, append=None, padding_mode="zeros", align_corners=False):
+    """f32 [B, G + sum C_k + A, N], contiguous: the feature maps f32 [B,C_k,H_k,W_k] read bilinearly at uv f32 [B,N,2]
+    (grid_sample's convention: uv[...,0] along W, uv[...,1] along H, -1 .. 1 spans the image) and written side by side into one
+    result — what DISNDecoder._extract_point_image_features computes (layers/disn.py:278-305), without a per-map tensor, a cat or
+    an expand.  Rows [0,G) hold global_features f32 [B,G] for every point, then the maps in list order, then append f32 [B,N,A]
+    transposed (the positions).  padding_mode "zeros" or "border", align_corners as in F.grid_sample; the arithmetic is spelled
+    out at deftet_image_sample_fwd_f32 (include/deftet_hip.h).  A point fully outside the map under "zeros" (+-1e30, +-inf and NaN
+    included) has value 0 and no gradient; under "border" a NaN reads pixel 0.
+    Differentiable in every map, in uv, in global_features and in append, each computed only when needed.  The gradient of a map
+    is a gather over the points sorted by cell (one sort per distinct (H, W)), the gradient of global_features a fixed-order row
+    sum: no atomics, the same bits on every run."""
+    maps = list(maps)
+    _lib.require_gpu(uv, global_features, append, *maps)
+    if padding_mode not in ("zeros", "border"):
+        raise RuntimeError("image_sample: padding_mode 'zeros' or 'border' expected (got %r)" % (padding_mode,))
+    uv = _pv_need(uv, torch.float32, "image_sample: uv")
+    if uv.dim() != 3 or uv.shape[2] != 2:
+        raise RuntimeError("image_sample: uv [B,N,2] expected (got %s)" % (tuple(uv.shape),))
+    B, N = uv.shape[0], uv.shape[1]
+    ms = []
+    for m in maps:
+        m = _pv_need(m, torch.float32, "image_sample: map")
+        if m.dim() != 4 or m.shape[2] < 1 or m.shape[3] < 1:
+            raise RuntimeError("image_sample: maps [B,C,H,W] expected (got %s)" % (tuple(m.shape),))
+        if m.shape[0] != B or m.device != uv.device:
+            raise RuntimeError("image_sample: map %s and uv %s differ in batch or device" % (tuple(m.shape), tuple(uv.shape)))
+        ms.append(m)
+    if global_features is not None:
+        global_features = _pv_need(global_features, torch.float32, "image_sample: global_features")
+        if global_features.dim() != 2 or global_features.shape[0] != B or global_features.device != uv.device:
+            raise RuntimeError("image_sample: global_features [B,G] expected (got %s for B = %d)" % (tuple(global_features.shape), B))
+    if append is not None:
+        append = _pv_need(append, torch.float32, "image_sample: append")
+        if append.dim() != 3 or append.shape[0] != B or append.shape[1] != N or append.device != uv.device:
+            raise RuntimeError("image_sample: append [B,N,A] expected (got %s for uv %s)" % (tuple(append.shape), tuple(uv.shape)))
+    return _ImageSample.apply(uv, global_features, append, int(padding_mode == "border"), int(bool(align_corners)), *ms)
+
+
 # --------------------------------------------------------------------------------- tet-centroid feature sampling (DESIGN.md §6m)
 _TCS_MAX_VOLUMES = 8
 

@@ -42,7 +42,9 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
-/* 350: connected components of the inside tets and the occupancy clean-up on them — deftet_tet_components_u8,
+/* 360: pixel-aligned image-feature sampling for the single-image branch — deftet_image_sample_fwd_f32, deftet_image_cells_f32,
+ *      deftet_image_sample_bwd_map_f32 / _bwd_uv_f32 / _bwd_global_f32 and their workspace size (image_sample.hip).
+ * 350: connected components of the inside tets and the occupancy clean-up on them — deftet_tet_components_u8,
  *      deftet_occupancy_cleanup_u8 and their workspace size (tet_components.hip).
  * 340: a per-vertex field at located query points — deftet_tet_field_sample_fwd_f32 / _bwd_w_f32 / _bwd_field_f32 and their
  *      workspace size (tet_field_sample.hip).
@@ -900,6 +902,55 @@ int deftet_voxel_sample_bwd_vol_f32(const float *grad_out, const int32_t *perm, 
 int deftet_voxel_sample_bwd_pos_f32(const float *vol, const float *pos, const float *grad_out, float *grad_pos, int n_batch, int n_channel,
                                     int resolution, int n_point, int channel_offset, int n_channel_total, int pos_mode, int accumulate,
                                     void *stream);
+
+/* Pixel-aligned image features (360; image_sample.hip): feature maps read bilinearly at projected points, the
+ * operation of DISNDecoder._extract_point_image_features (layers/disn.py:257-305), written with the global feature rows and the
+ * appended rows into ONE result out f32 [B, C_total, N], C_total = G + sum C_k + A.  No float atomics; two runs agree bit for bit.
+ *
+ * map f32 [B,C,H,W]; uv f32 [B,N,2] in grid_sample's convention (uv[..,0] along W, uv[..,1] along H, -1 .. 1 spans the image).
+ * border 0: padding "zeros", 1: "border".  In fp32, in this order:
+ *   ix = ((x + 1) W - 1) 0.5 (align_corners 0) or (x + 1) 0.5 (W - 1) (align_corners 1), iy likewise with H;
+ *   border: ix = fminf(fmaxf(ix, 0), W - 1), iy likewise (a NaN reads pixel 0);
+ *   a point with !(ix > -1 && ix < W) or !(iy > -1 && iy < H) is fully outside: value 0, every gradient 0, nothing read and no
+ *   float converted to an integer (+-1e30, +-inf, NaN under zeros);
+ *   x0 = floor(ix), tx = ix - x0, y likewise; value = the four rounded products added in the order (y0,x0), (y0,x0+1), (y0+1,x0),
+ *   (y0+1,x0+1) with weights (1-tx)(1-ty), tx(1-ty), (1-tx)ty, tx ty; a corner outside the map adds 0 and is never read.
+ * deftet_image_sample_fwd_f32: out[b, channel_offset + c, p] for the C channels of one map (one call per map of a list); with
+ *   global_features f32 [B,G] non-NULL also out[b, g, p] = global_features[b,g], g < n_global, and with append f32 [B,N,A]
+ *   non-NULL out[b, C_total - A + a, p] = append[b,p,a].  n_channel = 0 writes those rows only (map may be NULL).
+ * deftet_image_cells_f32: the sort the map backward needs, per point set and distinct (H, W, border, align_corners): the key of a
+ *   point is b n_cells + (y0 + 1)(W + 1) + (x0 + 1), n_cells = (H + 1)(W + 1) (lo corners from -1: a partially-outside cell has a
+ *   key), a fully-outside point sorts behind every cell.  perm i32 [B N] (b N + p in key order, stable), seg i32 [B n_cells + 1],
+ *   wsorted f32 [4, B N] (the weights in sorted order, corner-major).
+ * deftet_image_sample_bwd_map_f32: grad_map f32 [B,C,H,W] (every element written) in two stages, every grad_out element read
+ *   once.  Per (channel, cell) the four corner sums part[k] = sum over the cell's points j in sorted order of wsorted[k][j] *
+ *   grad_out[b, channel_offset + c, p(j)] (a segment of up to 32 points one after the other from 0; a longer one by 64 lanes —
+ *   lane l adds points l, l + 64, ... in that order — and a fixed butterfly over the lanes, offsets 32 .. 1); then grad_map[b,c,y,x]
+ *   = the four part[k] of the cells (y - ky, x - kx), corner k = 2 ky + kx = 0 .. 3 in that order, from 0.  The channels are
+ *   chunked so that the partials (16 B n_cells bytes per channel) stay inside the workspace's 32 MiB.
+ * deftet_image_sample_bwd_uv_f32: grad_uv[b,p,:] (=, or += with accumulate) (sx gx, sy gy), gx = sum_c grad_out[b, channel_offset
+ *   + c, p] * ((v01 - v00)(1 - ty) + (v11 - v10) ty), gy with (v10 - v00)(1 - tx) + (v11 - v01) tx, channels ascending from 0,
+ *   texels outside the map counting 0; sx = W / 2 or (W - 1) / 2, sy with H.  0 for a fully-outside point and, under border, for
+ *   a coordinate the clamp holds (ix <= 0 or ix >= W - 1, a NaN included); the right-hand cell at an integer ix.
+ * deftet_image_sample_bwd_global_f32: grad_global[b,g] = sum_n grad_out[b,g,n] of the first n_global rows of grad_out f32
+ *   [B,C_total,N]: one wave per row, lane l adds n = l, l + 64, ... from 0, then the butterfly (offsets 32 .. 1).
+ * Workspace (256-byte aligned): deftet_image_sample_workspace_bytes(B, N, H, W) is the size of the one layout deftet_image_cells_f32
+ * and deftet_image_sample_bwd_map_f32 carve (the sort's arrays, then the partials); both refuse a smaller one with DEFTET_EINVAL
+ * before any device call.  The other entries need no workspace. */
+size_t deftet_image_sample_workspace_bytes(int n_batch, int n_point, int height, int width);
+int deftet_image_sample_fwd_f32(const float *map, const float *uv, const float *global_features, const float *append, float *out,
+                                int n_batch, int n_channel, int height, int width, int n_point, int n_global, int n_append,
+                                int channel_offset, int n_channel_total, int border, int align_corners, void *stream);
+int deftet_image_cells_f32(const float *uv, int32_t *perm, int32_t *seg, float *wsorted, int n_batch, int n_point, int height, int width,
+                           int border, int align_corners, void *workspace, size_t workspace_bytes, void *stream);
+int deftet_image_sample_bwd_map_f32(const float *grad_out, const int32_t *perm, const int32_t *seg, const float *wsorted, float *grad_map,
+                                    int n_batch, int n_channel, int height, int width, int n_point, int channel_offset, int n_channel_total,
+                                    void *workspace, size_t workspace_bytes, void *stream);
+int deftet_image_sample_bwd_uv_f32(const float *map, const float *uv, const float *grad_out, float *grad_uv, int n_batch, int n_channel,
+                                   int height, int width, int n_point, int channel_offset, int n_channel_total, int border,
+                                   int align_corners, int accumulate, void *stream);
+int deftet_image_sample_bwd_global_f32(const float *grad_out, float *grad_global, int n_batch, int n_global, int n_point, int n_channel_total,
+                                       void *stream);
 
 /* Tet-centroid feature sampling (330; tet_centroid_sample.hip): the input of the occupancy decoder,
  * cat(sample_f(mean(gather(pos, tets), 2)[:, chosen], volumes), centroids^T) (layers/pc_model.py:276-306), from the vertices, the
