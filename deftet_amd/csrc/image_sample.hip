@@ -2,12 +2,12 @@
 // read bilinearly at projected points uv f32 [B,N,2] (grid_sample's convention, layers/disn.py:257-305) and written side by side
 // with the global feature rows and the appended rows into ONE result f32 [B, G + sum C_k + A, N]; the gradients to the maps, to
 // uv and to the global features.  The 2-D twin of pointvoxel.hip: no float atomics anywhere, the scatter into the maps is a gather
-// over a stable sort of the points by cell (pointvoxel.hpp), so every sum has one fixed order and two runs give the same bits.
+// over a stable sort of the points by cell (cell_gather.hpp), so every sum has one fixed order and two runs give the same bits.
 //
 // Orders of summation (the contracts of include/deftet_hip.h):
 //   sampling      ((w00 f00 + w01 f01) + w10 f10) + w11 f11, x fastest, w = (x factor) * (y factor); a corner outside the map adds 0
 //   to the maps   per (channel, cell) four corner sums over the cell's points in ascending p (the sort is stable; a segment longer
-//                 than 32 points by 64 lanes and a fixed butterfly, see k_is_cell_partials), then per texel the partials of corner
+//                 than 32 points by 64 lanes and a fixed butterfly, see cell_gather.hpp), then per texel the partials of corner
 //                 (y0,x0), (y0,x0+1), (y0+1,x0), (y0+1,x0+1) in that order, from 0
 //   to uv         channels ascending from 0, one map after the other (the caller's list order: the first launch writes, later add)
 //   to global     per row lane l adds n = l, l + 64, ... from 0, then a fixed butterfly over the 64 lanes (offsets 32 .. 1)
@@ -16,26 +16,11 @@
 namespace deftet {
 namespace {
 
-constexpr int kIsShort = 32;                                         // a longer segment is taken by the whole wave
 constexpr size_t kIsPartialBudget = (size_t)32 << 20;                // scratch for the corner partials: the channels are chunked to fit it
-inline size_t partial_bytes_per_channel(size_t B, size_t n_cells) { return B * n_cells * 4 * sizeof(float); }
-
-// the one layout every entry with a workspace carves (over a null base: its size)
-struct IsWs {
-    SortBufs s;
-    float *part;
-    size_t part_bytes, bytes;
-};
-inline IsWs layout(int B, int N, int H, int W, void *ws)
+// the one layout both entries with a workspace carve: the sort's arrays, then the partials
+inline CellWs layout(int B, int N, int H, int W, void *ws)
 {
-    Arena A(ws);
-    IsWs w{};
-    take_sort(A, (size_t)B * N, w.s);
-    const size_t one = partial_bytes_per_channel((size_t)B, (size_t)cells_of(H, W));
-    w.part_bytes = one > kIsPartialBudget ? one : kIsPartialBudget;
-    w.part = A.take<float>(w.part_bytes / sizeof(float));
-    w.bytes = A.end();
-    return w;
+    return cell_layout<4>((size_t)B * N, (size_t)B * cells_of(H, W), kIsPartialBudget, false, false, ws);
 }
 
 // ---------------------------------------------------------------------------- forward
@@ -87,53 +72,10 @@ __global__ __launch_bounds__(kPvBlock) void k_is_weights(const float *__restrict
     for (int k = 0; k < 4; ++k) wsorted[(size_t)k * BN + j] = t.out ? 0.0f : t.w[k];
 }
 
-// Two stages, so that every gout element is read once (k_vs_cell_partials / k_vs_vol_from_partials of pointvoxel.hip in 2-D).
-// k_is_cell_partials: per (channel, cell) the four corner sums part[b][c][k][cell] over the cell's points in sorted (= ascending
-// point) order.  A thread owns a cell; a segment of up to kIsShort points it walks itself, a longer one — the usual case here, the
-// vertices along a viewing ray project to one pixel — is summed by the whole wave: lane l adds the points j0 + l, j0 + l + 64, ...
-// in that order, then the 64 lane sums are added by a fixed butterfly.  The order depends on the segment's length only.
+// The two stages of cell_gather.hpp with four corners, every term kept; a long segment is the usual case here: the vertices along
+// a viewing ray project to one pixel.
 // k_is_map_from_partials: texel (y,x) adds the up to four partials that meet in it, corner order, from 0.  A corner partial that
-// lands outside the map is never read.  Gathers both: the only stores are the thread's own cell and the thread's own texel.
-__device__ __forceinline__ void add_point(float acc[4], const float *__restrict__ wsorted, size_t BN, int j, float gv)
-{
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc[k] = __fadd_rn(acc[k], __fmul_rn(wsorted[(size_t)k * BN + j], gv));
-}
-
-__global__ __launch_bounds__(kPvBlock) void k_is_cell_partials(const float *__restrict__ gout, const int32_t *__restrict__ perm,
-                                                               const int32_t *__restrict__ seg, const float *__restrict__ wsorted, float *part,
-                                                               int B, int n_cells, int N, int c_first, int C_total, int c_chunk)
-{
-    const int b = blockIdx.z, cl = blockIdx.y, lane = threadIdx.x & 63;
-    const int cell = blockIdx.x * kPvBlock + threadIdx.x;           // (no early return: the wave's shuffles below need every lane)
-    const bool in = cell < n_cells;
-    const size_t BN = (size_t)B * N;
-    const int j0 = in ? seg[(size_t)b * n_cells + cell] : 0, j1 = in ? seg[(size_t)b * n_cells + cell + 1] : 0;
-    const float *g = gout + ((size_t)b * C_total + c_first + cl) * N - (size_t)b * N;      // perm holds b N + p
-    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    const bool is_long = j1 - j0 > kIsShort;
-    if (!is_long)
-        for (int j = j0; j < j1; ++j) add_point(acc, wsorted, BN, j, g[perm[j]]);
-    unsigned long long longs = __ballot(is_long);                   // wave-uniform: every lane runs the loop below alike
-    while (longs) {
-        const int src = __ffsll((long long)longs) - 1;
-        longs &= longs - 1ull;
-        const int a0 = __shfl(j0, src), a1 = __shfl(j1, src);
-        float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        for (int j = a0 + lane; j < a1; j += 64) add_point(s, wsorted, BN, j, g[perm[j]]);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) s[k] = __fadd_rn(s[k], __shfl_xor(s[k], off));
-            if (lane == src) acc[k] = s[k];
-        }
-    }
-    if (in) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) part[(((size_t)b * c_chunk + cl) * 4 + k) * n_cells + cell] = acc[k];
-    }
-}
-
+// lands outside the map is never read.
 __global__ __launch_bounds__(kPvBlock) void k_is_map_from_partials(const float *__restrict__ part, float *gmap, int C, int H, int W, int c_first,
                                                                    int c_chunk, int c_count)
 {
@@ -254,8 +196,8 @@ int deftet_image_cells_f32(const float *uv, int32_t *perm, int32_t *seg, float *
     const int B = n_batch, N = n_point, H = height, W = width;
     if (int rc = check_sizes(B, 0, N, H, W, "image_cells")) return rc;
     DEFTET_CHECK_ARG(flags_ok(border, align_corners), "image_cells: border and align_corners are 0 or 1");
-    const IsWs L = layout(B, N, H, W, workspace);
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && L.bytes <= workspace_bytes,
+    const CellWs L = layout(B, N, H, W, workspace);
+    DEFTET_CHECK_ARG(L.fits(workspace, workspace_bytes),
                      "image_cells: workspace null, misaligned or smaller than deftet_image_sample_workspace_bytes");
     if (B == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(seg, "image_cells: null pointer");
@@ -283,26 +225,19 @@ int deftet_image_sample_bwd_map_f32(const float *grad_out, const int32_t *perm, 
     if (int rc = check_sizes(B, C, N, H, W, "image_sample_bwd_map")) return rc;
     DEFTET_CHECK_ARG(channel_offset >= 0 && (long long)n_channel_total >= (long long)channel_offset + C,
                      "image_sample_bwd_map: channel offset + channels exceed the source");
-    const IsWs L = layout(B, N, H, W, workspace);
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && L.bytes <= workspace_bytes,
+    const CellWs L = layout(B, N, H, W, workspace);
+    DEFTET_CHECK_ARG(L.fits(workspace, workspace_bytes),
                      "image_sample_bwd_map: workspace null, misaligned or smaller than deftet_image_sample_workspace_bytes");
     if (B == 0 || C == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(seg && grad_map && (N == 0 || (grad_out && perm && wsorted)), "image_sample_bwd_map: null pointer");
-    const int n_cells = cells_of(H, W);
-    const size_t HW = (size_t)H * W, one = partial_bytes_per_channel((size_t)B, (size_t)n_cells);
-    size_t fit = L.part_bytes / one;                                // >= 1 by the layout
-    if (fit > 65535) fit = 65535;
-    const int c_chunk = (int)fit < C ? (int)fit : C;
+    const size_t HW = (size_t)H * W;
     hipStream_t st = as_stream(stream);
-    const unsigned gCell = (unsigned)((n_cells + kPvBlock - 1) / kPvBlock);
-    for (int c0 = 0; c0 < C; c0 += c_chunk) {                       // one chunk after the other on the stream: the scratch is reused
-        const int cc = C - c0 < c_chunk ? C - c0 : c_chunk;
-        const dim3 gridA(gCell, (unsigned)cc, (unsigned)B), gridB((unsigned)(((size_t)cc * HW + kPvBlock - 1) / kPvBlock), (unsigned)B);
-        DEFTET_LAUNCH(k_is_cell_partials, gridA, dim3(kPvBlock), st, grad_out, perm, seg, wsorted, L.part, B, n_cells, N, channel_offset + c0,
-                      n_channel_total, c_chunk);
-        DEFTET_LAUNCH(k_is_map_from_partials, gridB, dim3(kPvBlock), st, (const float *)L.part, grad_map, C, H, W, c0, c_chunk, cc);
-    }
-    return DEFTET_OK;
+    return cell_gather_bwd<4>(L, KeepEvery{}, grad_out, perm, seg, wsorted, B, cells_of(H, W), N, C, channel_offset, n_channel_total, st,
+                              [&](const float *part, int c0, int c_chunk, int cc) -> int {
+                                  DEFTET_LAUNCH(k_is_map_from_partials, dim3((unsigned)(((size_t)cc * HW + kPvBlock - 1) / kPvBlock), (unsigned)B),
+                                                dim3(kPvBlock), st, part, grad_map, C, H, W, c0, c_chunk, cc);
+                                  return DEFTET_OK;
+                              });
 }
 
 int deftet_image_sample_bwd_uv_f32(const float *map, const float *uv, const float *grad_out, float *grad_uv, int n_batch, int n_channel,

@@ -1,9 +1,9 @@
 // image_sample.hpp — the one statement of the bilinear arithmetic of image_sample.hip: the pixel coordinate of a
 // uv pair, the four corners of its cell with their weights and in-map masks, the cell key the map backward sorts by and the slope
 // of one channel along x and y.  The forward, the sorted weights and both backward kernels call these, so a value and its
-// gradients are the same expressions.  Anonymous namespace, as pointvoxel.hpp.
+// gradients are the same expressions.  Anonymous namespace, as cell_gather.hpp.
 #pragma once
-#include "pointvoxel.hpp"                       // kPvBlock and the sort plumbing
+#include "cell_gather.hpp"                      // kPvBlock, the sort by cell, the corner partials and their workspace
 
 namespace deftet {
 namespace {

@@ -10,9 +10,10 @@
 //                  product rounded before it is added (what the reference kernel computes with its threads one after another)
 //   sampling       ((w000 f000 + w001 f001) + w010 f010) + ... + w111 f111, z fastest, w = (wx * wy) * wz
 //   to the volumes per (channel, cell) eight corner sums over the cell's points in ascending p (the sort is stable; a long segment
-//                  by 64 lanes and a fixed butterfly, see k_vs_cell_partials), then per voxel the partials of corner 000 .. 111
+//                  by 64 lanes and a fixed butterfly, see cell_gather.hpp), then per voxel the partials of corner 000 .. 111
 //   to positions   channels in ascending order, one volume after the other (the caller's list order)
-#include "pointvoxel.hpp"                       // load_u, corners_of, pos_grad_of_volume, the sort plumbing: shared with tet_centroid_sample.hip
+#include "cell_gather.hpp"                      // the sort by cell, the corner partials and their workspace: shared with image_sample.hip
+#include "pointvoxel.hpp"                       // load_u, corners_of, pos_grad_of_volume: shared with tet_centroid_sample.hip
 
 namespace deftet {
 namespace {
@@ -133,81 +134,33 @@ __global__ __launch_bounds__(kPvBlock) void k_inds_gather(const int32_t *__restr
     }
 }
 
-// Two stages, so that every gout element is read once.
-// k_vs_cell_partials: per (channel, cell) the eight corner sums part[b][c][k][cell] = sum over the cell's points, in sorted
-// (= ascending point) order, of wsorted[k][j] * gout[b,c,perm[j]].  A thread owns a cell; a segment of up to kPvShort points it
-// walks itself (the fine volumes: ~1.4 points per cell, most cells empty).  A longer segment (the coarse volumes: ~90 points per
-// cell, or every point of a clustered set in one cell) is summed by the whole wave: lane l adds the points j0 + l, j0 + l + 64,
-// ... in that order, then the 64 lane sums are added by a fixed butterfly (offsets 32, 16, ... 1).  The order depends on the
-// segment's length only, never on the launch or on timing.  HAS_INDS (the legacy pair): a term counts only where the recorded
+// The two stages of cell_gather.hpp with eight corners.  KeepNominal (the legacy pair): a term counts only where the recorded
 // index IS the voxel the corner nominally lands in — the reference's hi index falls back on lo where d == 0, and there its
 // weight is exactly 0, so the terms left out are zeros.
 // k_vs_vol_from_partials: voxel v adds the up to eight partials that meet in it, corner 000 .. 111 in that order, from 0.
-// Gathers both: the only stores are the thread's own cell and the thread's own voxel.
-constexpr int kPvShort = 32;
 constexpr size_t kPvPartialBudget = (size_t)64 << 20;               // scratch for the partials: the channels are chunked to fit it
-inline size_t partial_bytes_per_channel(size_t B, size_t R3) { return B * R3 * 8 * sizeof(float); }
-
-template <bool HAS_INDS>
-__device__ __forceinline__ void add_point(float acc[8], const float *__restrict__ wsorted, const int32_t *__restrict__ isorted, size_t BN, int j,
-                                          float gv, const int vk[8])
+// the one layout the four entries with a workspace carve: the sort's arrays, the voxelization's perm / seg, and over them the partials
+inline CellWs layout(int B, int N, int R, void *ws)
 {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        if (HAS_INDS && isorted[(size_t)k * BN + j] != vk[k]) continue;
-        acc[k] = __fadd_rn(acc[k], __fmul_rn(wsorted[(size_t)k * BN + j], gv));
-    }
-}
-// the voxel corner k of `cell` nominally lands in, -1 outside the volume
-__device__ __forceinline__ void corner_voxels(int cell, int R, int vk[8])
-{
-    const int cx = cell / (R * R), cy = (cell / R) % R, cz = cell % R;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int x = cx + (k >> 2), y = cy + ((k >> 1) & 1), z = cz + (k & 1);
-        vk[k] = x < R && y < R && z < R ? (x * R + y) * R + z : -1;
-    }
+    return cell_layout<8>((size_t)B * N, (size_t)B * R * R * R, kPvPartialBudget, true, true, ws);
 }
 
-template <bool HAS_INDS>
-__global__ __launch_bounds__(kPvBlock) void k_vs_cell_partials(const float *__restrict__ gout, const int32_t *__restrict__ perm,
-                                                               const int32_t *__restrict__ seg, const float *__restrict__ wsorted,
-                                                               const int32_t *__restrict__ isorted, float *part, int B, int R, int N,
-                                                               int c_first, int C_total, int c_chunk)
-{
-    const int R3 = R * R * R, b = blockIdx.z, cl = blockIdx.y, lane = threadIdx.x & 63;
-    const int cell = blockIdx.x * kPvBlock + threadIdx.x;           // (no early return: the wave's shuffles below need every lane)
-    const bool in = cell < R3;
-    const size_t BN = (size_t)B * N;
-    const int j0 = in ? seg[(size_t)b * R3 + cell] : 0, j1 = in ? seg[(size_t)b * R3 + cell + 1] : 0;
-    const float *g = gout + ((size_t)b * C_total + c_first + cl) * N - (size_t)b * N;      // perm holds b N + p
-    float acc[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    int vk[8];
-    corner_voxels(in ? cell : 0, R, vk);
-    const bool is_long = j1 - j0 > kPvShort;
-    if (!is_long)
-        for (int j = j0; j < j1; ++j) add_point<HAS_INDS>(acc, wsorted, isorted, BN, j, g[perm[j]], vk);
-    unsigned long long longs = __ballot(is_long);                   // wave-uniform: every lane runs the loop below alike
-    while (longs) {
-        const int src = __ffsll((long long)longs) - 1;
-        longs &= longs - 1ull;
-        const int a0 = __shfl(j0, src), a1 = __shfl(j1, src);
-        int wk[8];
-        corner_voxels(__shfl(cell, src), R, wk);
-        float s[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        for (int j = a0 + lane; j < a1; j += 64) add_point<HAS_INDS>(s, wsorted, isorted, BN, j, g[perm[j]], wk);
+struct KeepNominal {
+    const int32_t *isorted;
+    size_t BN;
+    int R;
+    // the voxel corner k of `cell` nominally lands in, -1 outside the volume
+    __device__ void corners(int cell, int vk[8]) const
+    {
+        const int cx = cell / (R * R), cy = (cell / R) % R, cz = cell % R;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) s[k] = __fadd_rn(s[k], __shfl_xor(s[k], off));
-            if (lane == src) acc[k] = s[k];
+            const int x = cx + (k >> 2), y = cy + ((k >> 1) & 1), z = cz + (k & 1);
+            vk[k] = x < R && y < R && z < R ? (x * R + y) * R + z : -1;
         }
     }
-    if (in) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) part[(((size_t)b * c_chunk + cl) * 8 + k) * R3 + cell] = acc[k];
-    }
-}
+    __device__ bool operator()(int k, int j, const int vk[8]) const { return isorted[(size_t)k * BN + j] == vk[k]; }
+};
 
 __global__ __launch_bounds__(kPvBlock) void k_vs_vol_from_partials(const float *__restrict__ part, float *gvol, int C, int R, int c_first,
                                                                    int c_chunk, int c_count)
@@ -245,6 +198,7 @@ __global__ __launch_bounds__(kPvBlock) void k_vs_bwd_pos(const float *__restrict
     }
 }
 
+constexpr const char *kWsRefused = "workspace null, misaligned or smaller than deftet_pointvoxel_workspace_bytes";
 inline int check_sizes(int B, int C, int N, int R, const char *what)
 {
     if (B < 0 || C < 0 || N < 0 || R < 1) return set_error(DEFTET_EINVAL, "%s: negative size or resolution below 1", what);
@@ -265,12 +219,7 @@ extern "C" {
 size_t deftet_pointvoxel_workspace_bytes(int n_batch, int n_point, int resolution)
 {
     if (n_batch < 0 || n_point < 0 || resolution < 0) return 0;
-    const size_t n = (size_t)n_batch * (size_t)n_point, r = (size_t)resolution;
-    // the sort with the voxelization's own perm [B N] and seg [B R^3 + 1], or the volume backward's corner partials
-    const size_t one = partial_bytes_per_channel((size_t)n_batch, r * r * r);
-    const size_t sorting = sort_bytes(n) + align_up(n * 4, 256) + align_up(((size_t)n_batch * r * r * r + 1) * 4, 256) + 512;
-    const size_t partials = (one > kPvPartialBudget ? one : kPvPartialBudget) + 256;
-    return sorting > partials ? sorting : partials;
+    return layout(n_batch, n_point, resolution, nullptr).bytes;
 }
 
 int deftet_avg_voxelize_fwd_f32(const float *feat, const int32_t *coords, float *out, int32_t *ind, int32_t *cnt, int n_batch,
@@ -292,19 +241,16 @@ int deftet_avg_voxelize_fwd_f32(const float *feat, const int32_t *coords, float 
     DEFTET_CHECK_ARG(coords && ind && (feat || C == 0), "avg_voxelize: null pointer");
     const size_t n = (size_t)B * N;
     const unsigned n_keys = (unsigned)((size_t)B * R3);
-    SortBufs s;
-    Arena A(workspace, workspace_bytes);
-    if (!carve(A, workspace, workspace_bytes, n, s)) return set_error(DEFTET_EINVAL, "avg_voxelize: workspace missing, misaligned or too small");
-    int32_t *perm = A.take<int32_t>(n), *seg = A.take<int32_t>((size_t)n_keys + 1);
-    if (!A.ok()) return set_error(DEFTET_EINVAL, "avg_voxelize: workspace too small");
+    const CellWs L = layout(B, N, R, workspace);
+    DEFTET_CHECK_ARG(L.fits(workspace, workspace_bytes), "avg_voxelize: %s", kWsRefused);
     const unsigned gN = (unsigned)((N + kPvBlock - 1) / kPvBlock);
-    DEFTET_LAUNCH(k_vox_keys, dim3(gN, B), dim3(kPvBlock), st, coords, ind, s.keys, N, R, n_keys);
-    if (int rc = sort_and_segment(s, perm, seg, n, n_keys, st)) return rc;
+    DEFTET_LAUNCH(k_vox_keys, dim3(gN, B), dim3(kPvBlock), st, coords, ind, L.s.keys, N, R, n_keys);
+    if (int rc = sort_and_segment(L.s, L.perm, L.seg, n, n_keys, st)) return rc;
     const unsigned gS = (unsigned)((R3 + kPvBlock - 1) / kPvBlock);
     const int c_per = C > 0 ? channels_per_thread(C, (long long)gS * B) : 1;
     const unsigned gC = C > 0 ? (unsigned)((C + c_per - 1) / c_per) : 1u;
     if (gC > 65535u) return set_error(DEFTET_ELIMIT, "avg_voxelize: too many channel chunks");
-    DEFTET_LAUNCH(k_vox_fwd, dim3(gS, gC, B), dim3(kPvBlock), st, feat, (const int32_t *)perm, (const int32_t *)seg, out, cnt, C, N, (int)R3,
+    DEFTET_LAUNCH(k_vox_fwd, dim3(gS, gC, B), dim3(kPvBlock), st, feat, (const int32_t *)L.perm, (const int32_t *)L.seg, out, cnt, C, N, (int)R3,
                   c_per);
     return DEFTET_OK;
 }
@@ -360,11 +306,10 @@ int deftet_voxel_cells_f32(const float *pos, int pos_mode, int32_t *perm, int32_
     }
     DEFTET_CHECK_ARG(pos && perm && wsorted, "voxel_cells: null pointer");
     const size_t n = (size_t)B * N;
-    SortBufs s;
-    Arena A(workspace, workspace_bytes);
-    if (!carve(A, workspace, workspace_bytes, n, s)) return set_error(DEFTET_EINVAL, "voxel_cells: workspace missing, misaligned or too small");
-    DEFTET_LAUNCH(k_cell_keys, dim3((unsigned)((N + kPvBlock - 1) / kPvBlock), B), dim3(kPvBlock), st, pos, pos_mode, s.keys, N, R);
-    if (int rc = sort_and_segment(s, perm, seg, n, n_keys, st)) return rc;
+    const CellWs L = layout(B, N, R, workspace);
+    DEFTET_CHECK_ARG(L.fits(workspace, workspace_bytes), "voxel_cells: %s", kWsRefused);
+    DEFTET_LAUNCH(k_cell_keys, dim3((unsigned)((N + kPvBlock - 1) / kPvBlock), B), dim3(kPvBlock), st, pos, pos_mode, L.s.keys, N, R);
+    if (int rc = sort_and_segment(L.s, perm, seg, n, n_keys, st)) return rc;
     DEFTET_LAUNCH(k_cell_weights, dim3((unsigned)((n + kPvBlock - 1) / kPvBlock)), dim3(kPvBlock), st, pos, pos_mode, (const int32_t *)perm,
                   wsorted, B, N, R);
     return DEFTET_OK;
@@ -387,12 +332,10 @@ int deftet_voxel_cells_from_inds_i32(const int32_t *inds, const float *wgts, int
     }
     DEFTET_CHECK_ARG(inds && wgts && perm && wsorted && isorted, "voxel_cells_from_inds: null pointer");
     const size_t n = (size_t)B * N;
-    SortBufs s;
-    Arena A(workspace, workspace_bytes);
-    if (!carve(A, workspace, workspace_bytes, n, s))
-        return set_error(DEFTET_EINVAL, "voxel_cells_from_inds: workspace missing, misaligned or too small");
-    DEFTET_LAUNCH(k_inds_keys, dim3((unsigned)((N + kPvBlock - 1) / kPvBlock), B), dim3(kPvBlock), st, inds, s.keys, N, R3, n_keys);
-    if (int rc = sort_and_segment(s, perm, seg, n, n_keys, st)) return rc;
+    const CellWs L = layout(B, N, R, workspace);
+    DEFTET_CHECK_ARG(L.fits(workspace, workspace_bytes), "voxel_cells_from_inds: %s", kWsRefused);
+    DEFTET_LAUNCH(k_inds_keys, dim3((unsigned)((N + kPvBlock - 1) / kPvBlock), B), dim3(kPvBlock), st, inds, L.s.keys, N, R3, n_keys);
+    if (int rc = sort_and_segment(L.s, perm, seg, n, n_keys, st)) return rc;
     DEFTET_LAUNCH(k_inds_gather, dim3((unsigned)((n + kPvBlock - 1) / kPvBlock)), dim3(kPvBlock), st, inds, wgts, (const int32_t *)perm, wsorted,
                   isorted, B, N);
     return DEFTET_OK;
@@ -407,27 +350,19 @@ int deftet_voxel_sample_bwd_vol_f32(const float *grad_out, const int32_t *perm, 
     DEFTET_CHECK_ARG(channel_offset >= 0 && n_channel_total >= channel_offset + C, "voxel_sample_bwd_vol: channel offset + channels exceed the source");
     if (B == 0 || C == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(seg && grad_vol && (N == 0 || (grad_out && perm && wsorted)), "voxel_sample_bwd_vol: null pointer");
-    const size_t R3 = (size_t)R * R * R, one = partial_bytes_per_channel((size_t)B, R3);
-    if (!workspace || ((uintptr_t)workspace & 255) != 0 || workspace_bytes < one)
-        return set_error(DEFTET_EINVAL, "voxel_sample_bwd_vol: workspace missing, misaligned or below one channel of partials");
-    size_t fit = workspace_bytes / one;
-    if (fit > kPvPartialBudget / one) fit = kPvPartialBudget / one > 0 ? kPvPartialBudget / one : 1;
-    const int c_chunk = (int)(fit > 65535 ? 65535 : fit) < C ? (int)(fit > 65535 ? 65535 : fit) : C;
-    float *part = static_cast<float *>(workspace);
+    const CellWs L = layout(B, N, R, workspace);
+    DEFTET_CHECK_ARG(L.fits(workspace, workspace_bytes), "voxel_sample_bwd_vol: %s", kWsRefused);
+    const int R3 = R * R * R;
     hipStream_t st = as_stream(stream);
-    const unsigned gCell = (unsigned)((R3 + kPvBlock - 1) / kPvBlock);
-    for (int c0 = 0; c0 < C; c0 += c_chunk) {                       // one chunk after the other on the stream: the scratch is reused
-        const int cc = C - c0 < c_chunk ? C - c0 : c_chunk;
-        const dim3 gridA(gCell, (unsigned)cc, (unsigned)B), gridB((unsigned)(((size_t)cc * R3 + kPvBlock - 1) / kPvBlock), (unsigned)B);
-        if (isorted)
-            DEFTET_LAUNCH(k_vs_cell_partials<true>, gridA, dim3(kPvBlock), st, grad_out, perm, seg, wsorted, isorted, part, B, R, N,
-                          channel_offset + c0, n_channel_total, c_chunk);
-        else
-            DEFTET_LAUNCH(k_vs_cell_partials<false>, gridA, dim3(kPvBlock), st, grad_out, perm, seg, wsorted, isorted, part, B, R, N,
-                          channel_offset + c0, n_channel_total, c_chunk);
-        DEFTET_LAUNCH(k_vs_vol_from_partials, gridB, dim3(kPvBlock), st, (const float *)part, grad_vol, C, R, c0, c_chunk, cc);
-    }
-    return DEFTET_OK;
+    auto gather = [&](const float *part, int c0, int c_chunk, int cc) -> int {
+        DEFTET_LAUNCH(k_vs_vol_from_partials, dim3((unsigned)(((size_t)cc * R3 + kPvBlock - 1) / kPvBlock), (unsigned)B), dim3(kPvBlock), st, part,
+                      grad_vol, C, R, c0, c_chunk, cc);
+        return DEFTET_OK;
+    };
+    if (isorted)
+        return cell_gather_bwd<8>(L, KeepNominal{isorted, (size_t)B * N, R}, grad_out, perm, seg, wsorted, B, R3, N, C, channel_offset,
+                                  n_channel_total, st, gather);
+    return cell_gather_bwd<8>(L, KeepEvery{}, grad_out, perm, seg, wsorted, B, R3, N, C, channel_offset, n_channel_total, st, gather);
 }
 
 int deftet_voxel_sample_bwd_pos_f32(const float *vol, const float *pos, const float *grad_out, float *grad_pos, int n_batch, int n_channel,

@@ -1,15 +1,12 @@
-// pointvoxel.hpp — what the trilinear sampler's kernels share: the voxel coordinate of a point, the eight
-// corners of its cell, the slope of one volume along the three axes, and the sort-by-key plumbing that turns a scatter into a
-// gather.  pointvoxel.hip and tet_centroid_sample.hip both include it, so a value sampled at a tet centroid and its gradients
-// are the SAME expressions as the point sampler's, not a restatement of them.  Everything sits in an anonymous namespace: each
-// translation unit gets its own copy (the kernel below included), as before the split.
+// pointvoxel.hpp — the one statement of the trilinear arithmetic: the voxel coordinate of a point, the eight
+// corners of its cell and the slope of one volume along the three axes.  pointvoxel.hip and tet_centroid_sample.hip both include
+// it, so a value sampled at a tet centroid and its gradients are the SAME expressions as the point sampler's, not a restatement
+// of them.  Anonymous namespace: each translation unit gets its own copy.  (The sort plumbing lives in cell_gather.hpp.)
 #pragma once
-#include "prims.hpp"
+#include "common.hpp"
 
 namespace deftet {
 namespace {
-
-constexpr int kPvBlock = 256;
 
 // u of one point per axis: `raw` before the clamp (the border rule of the position gradient reads it), `u` after it.
 // pos_mode 0: pos f32 [B,N,3], normalised: u = clamp((pos + 0.5) r, 0, r - 1)   (sample_f's arithmetic, in that order)
@@ -96,71 +93,6 @@ __device__ __forceinline__ void pos_grad_of_volume(const float *__restrict__ vol
     res[0] = raw[0] > 0.0f && raw[0] < top ? scale * gx : 0.0f;
     res[1] = raw[1] > 0.0f && raw[1] < top ? scale * gy : 0.0f;
     res[2] = raw[2] > 0.0f && raw[2] < top ? scale * gz : 0.0f;
-}
-
-// ---------------------------------------------------------------------------- sort plumbing
-// seg[s] = the first sorted position whose key is >= s, s in [0, n_keys]: voxel / cell s owns [seg[s], seg[s + 1])
-__global__ __launch_bounds__(kPvBlock) void k_pv_segments(const unsigned *__restrict__ sorted, unsigned n, unsigned n_keys, int32_t *seg)
-{
-    const unsigned s = blockIdx.x * kPvBlock + threadIdx.x;
-    if (s > n_keys) return;
-    unsigned a = 0u, b = n;
-    while (a < b) {
-        const unsigned m = a + (b - a) / 2u;
-        if (sorted[m] < s) a = m + 1u;
-        else b = m;
-    }
-    seg[s] = (int32_t)a;
-}
-
-inline int key_bits(unsigned n_keys)
-{
-    int bits = 1;
-    while (bits < 32 && (n_keys >> bits) != 0u) ++bits;             // the sentinel n_keys itself must be representable
-    return bits;
-}
-
-struct SortBufs {
-    unsigned *keys, *sorted;
-    void *tmp;
-    size_t tmp_bytes;
-};
-inline size_t sort_bytes(size_t n)
-{
-    return 2 * align_up(n * sizeof(unsigned), 256) + prims::radix_sort_temp_bytes<unsigned, unsigned>(n) + 512;
-}
-// the three arrays of a sort of n keys, taken from A in this order (what sort_bytes bounds)
-inline void take_sort(Arena &A, size_t n, SortBufs &s)
-{
-    s.keys = A.take<unsigned>(n);
-    s.sorted = A.take<unsigned>(n);
-    s.tmp_bytes = prims::radix_sort_temp_bytes<unsigned, unsigned>(n);
-    s.tmp = A.take<char>(s.tmp_bytes);
-}
-inline bool carve(Arena &A, void *ws, size_t ws_bytes, size_t n, SortBufs &s)
-{
-    if (!ws || ((uintptr_t)ws & 255) != 0 || ws_bytes < sort_bytes(n)) return false;
-    take_sort(A, n, s);
-    return A.ok();
-}
-// keys (already written) -> perm (the point ids b N + p in key order, stable) and seg
-inline int sort_and_segment(const SortBufs &s, int32_t *perm, int32_t *seg, size_t n, unsigned n_keys, hipStream_t st)
-{
-    const int rc = prims::radix_sort_from<unsigned, unsigned>(prims::PtrLoad<unsigned>{s.keys}, s.sorted, prims::IotaLoad{}, (unsigned *)perm,
-                                                               n, key_bits(n_keys), s.tmp, s.tmp_bytes, st);
-    if (rc != DEFTET_OK) return rc;
-    DEFTET_LAUNCH(k_pv_segments, dim3((n_keys + 1 + kPvBlock - 1) / kPvBlock), dim3(kPvBlock), st, (const unsigned *)s.sorted, (unsigned)n,
-                  n_keys, seg);
-    return DEFTET_OK;
-}
-
-// channels per thread so that the grid has a few thousand workgroups; the sums do not depend on it
-inline int channels_per_thread(int C, long long groups_per_channel_chunk)
-{
-    const long long want = 4096;
-    long long chunks = (want + groups_per_channel_chunk - 1) / groups_per_channel_chunk;
-    chunks = chunks < 1 ? 1 : (chunks > C ? C : chunks);
-    return (int)((C + chunks - 1) / chunks);
 }
 
 }  // namespace

@@ -10,7 +10,8 @@
 //                 order, the position row of grad_out last
 //   to vertices   gpos[b,v] = 0.25f * sum over the incidences (4 t + corner, ascending) of v, over the slots that chose t in
 //                 ascending slot, of gcent[b,slot]: one accumulator from 0, one product at the end
-#include "pointvoxel.hpp"
+#include "cell_gather.hpp"                      // the sort plumbing
+#include "pointvoxel.hpp"                       // the trilinear arithmetic
 
 namespace deftet {
 namespace {

@@ -7,7 +7,7 @@
 //   to w      grad_w[b,q,k] = sum over c ascending of grad_out[b,q,c] * f(v_k,c): one accumulator from 0
 //   to field  grad_field[b,v,c] = one accumulator from 0 over the incidences (4 t + corner, ascending) of v, per incidence over
 //             the queries of shape b with cond == t in ascending q, of the rounded product bary[b,q,corner] * grad_out[b,q,c]
-#include "pointvoxel.hpp"
+#include "cell_gather.hpp"
 
 namespace deftet {
 namespace {

@@ -2318,8 +2318,9 @@ def _pv_need(t, dtype, what):
     return t.contiguous()
 
 
-def _pv_workspace(lib, dev, B, N, R):
-    nbytes = lib.deftet_pointvoxel_workspace_bytes(B, N, R)
+def _grid_workspace(lib, dev, B, N, size):
+    """the workspace of the operator whose grids have the spatial shape `size`: (R, R, R) volumes or (H, W) maps"""
+    nbytes = lib.deftet_pointvoxel_workspace_bytes(B, N, size[0]) if len(size) == 3 else lib.deftet_image_sample_workspace_bytes(B, N, *size)
     return _lib.workspace(dev, nbytes), nbytes
 
 
@@ -2341,7 +2342,7 @@ def avg_voxelize_fwd(features, coords, resolution):
     ind = torch.empty(B, N, device=dev, dtype=torch.int32)
     cnt = torch.empty(B, R ** 3, device=dev, dtype=torch.int32)
     with _lib.on_device(dev):
-        ws, nbytes = _pv_workspace(lib, dev, B, N, R)
+        ws, nbytes = _grid_workspace(lib, dev, B, N, (R, R, R))
         _lib.check(lib.deftet_avg_voxelize_fwd_f32(_lib.ptr(features), _lib.ptr(coords), _lib.ptr(out), _lib.ptr(ind), _lib.ptr(cnt), B, C, N, R,
                                                    _lib.ptr(ws), nbytes, _lib.current_stream(dev)), "deftet_avg_voxelize_fwd_f32")
     return out, ind, cnt
@@ -2367,40 +2368,76 @@ def avg_voxelize_bwd(grad_y, ind, cnt):
     return grad_x
 
 
-class VoxelCells:
-    """The points of one set sorted by the cell they fall in at one resolution (deftet_voxel_cells_*): what the backward to the
-    volumes gathers through.  Volumes of equal resolution share it."""
-    __slots__ = ("perm", "seg", "wsorted", "isorted", "B", "N", "R")
+class GridCells:
+    """The points of one set sorted by the cell they fall in on one grid size (deftet_voxel_cells_* for (R, R, R) volumes,
+    deftet_image_cells_f32 for (H, W) maps): what the backward to the grids gathers through.  Grids of equal size share it."""
+    __slots__ = ("perm", "seg", "wsorted", "isorted", "B", "N", "size")
 
 
-def _voxel_cells(lib, B, N, R, dev, pos=None, pos_mode=0, inds=None, wgts=None):
-    cells = VoxelCells()
-    cells.B, cells.N, cells.R = B, N, R
+def _grid_cells(lib, B, N, size, dev, pos=None, pos_mode=0, inds=None, wgts=None, uv=None, border=0, align=0):
+    """the cells of pos (or of the recorded inds / wgts) in volumes of shape `size`, or of uv in maps of shape `size`"""
+    n_cells, corners = (size[0] ** 3, 8) if uv is None else ((size[0] + 1) * (size[1] + 1), 4)
+    cells = GridCells()
+    cells.B, cells.N, cells.size = B, N, tuple(size)
     cells.perm = torch.empty(B * N, device=dev, dtype=torch.int32)
-    cells.seg = torch.empty(B * R ** 3 + 1, device=dev, dtype=torch.int32)
-    cells.wsorted = torch.empty(8, B * N, device=dev, dtype=torch.float32)
+    cells.seg = torch.empty(B * n_cells + 1, device=dev, dtype=torch.int32)
+    cells.wsorted = torch.empty(corners, B * N, device=dev, dtype=torch.float32)
     cells.isorted = torch.empty(8, B * N, device=dev, dtype=torch.int32) if inds is not None else None
+    out = (_lib.ptr(cells.perm), _lib.ptr(cells.seg), _lib.ptr(cells.wsorted))
     with _lib.on_device(dev):
-        ws, nbytes = _pv_workspace(lib, dev, B, N, R)
-        if inds is None:
-            _lib.check(lib.deftet_voxel_cells_f32(_lib.ptr(pos), pos_mode, _lib.ptr(cells.perm), _lib.ptr(cells.seg), _lib.ptr(cells.wsorted),
-                                                  B, N, R, _lib.ptr(ws), nbytes, _lib.current_stream(dev)), "deftet_voxel_cells_f32")
+        ws, nbytes = _grid_workspace(lib, dev, B, N, size)
+        tail = (_lib.ptr(ws), nbytes, _lib.current_stream(dev))
+        if uv is not None:
+            _lib.check(lib.deftet_image_cells_f32(_lib.ptr(uv), *out, B, N, size[0], size[1], border, align, *tail), "deftet_image_cells_f32")
+        elif inds is None:
+            _lib.check(lib.deftet_voxel_cells_f32(_lib.ptr(pos), pos_mode, *out, B, N, size[0], *tail), "deftet_voxel_cells_f32")
         else:
-            _lib.check(lib.deftet_voxel_cells_from_inds_i32(_lib.ptr(inds), _lib.ptr(wgts), _lib.ptr(cells.perm), _lib.ptr(cells.seg),
-                                                            _lib.ptr(cells.wsorted), _lib.ptr(cells.isorted), B, N, R, _lib.ptr(ws), nbytes,
-                                                            _lib.current_stream(dev)), "deftet_voxel_cells_from_inds_i32")
+            _lib.check(lib.deftet_voxel_cells_from_inds_i32(_lib.ptr(inds), _lib.ptr(wgts), *out, _lib.ptr(cells.isorted), B, N, size[0], *tail),
+                       "deftet_voxel_cells_from_inds_i32")
     return cells
 
 
-def _bwd_vol(lib, gout, cells, C, c_off, C_total):
-    B, N, R, dev = cells.B, cells.N, cells.R, gout.device
-    gvol = torch.empty(B, C, R, R, R, device=dev, dtype=torch.float32)
+def _grid_bwd(lib, gout, cells, C, c_off, C_total):
+    """the gradient f32 [B, C, *size] of one grid from the rows [c_off, c_off + C) of gout, gathered through `cells`"""
+    B, N, size, dev = cells.B, cells.N, cells.size, gout.device
+    ggrid = torch.empty((B, C) + size, device=dev, dtype=torch.float32)
+    head = (_lib.ptr(gout), _lib.ptr(cells.perm), _lib.ptr(cells.seg), _lib.ptr(cells.wsorted))
     with _lib.on_device(dev):
-        ws, nbytes = _pv_workspace(lib, dev, B, N, R)
-        _lib.check(lib.deftet_voxel_sample_bwd_vol_f32(_lib.ptr(gout), _lib.ptr(cells.perm), _lib.ptr(cells.seg), _lib.ptr(cells.wsorted),
-                                                       _lib.ptr(cells.isorted), _lib.ptr(gvol), B, C, R, N, c_off, C_total, _lib.ptr(ws), nbytes,
-                                                       _lib.current_stream(dev)), "deftet_voxel_sample_bwd_vol_f32")
-    return gvol
+        ws, nbytes = _grid_workspace(lib, dev, B, N, size)
+        tail = (N, c_off, C_total, _lib.ptr(ws), nbytes, _lib.current_stream(dev))
+        if len(size) == 3:
+            _lib.check(lib.deftet_voxel_sample_bwd_vol_f32(*head, _lib.ptr(cells.isorted), _lib.ptr(ggrid), B, C, size[0], *tail),
+                       "deftet_voxel_sample_bwd_vol_f32")
+        else:
+            _lib.check(lib.deftet_image_sample_bwd_map_f32(*head, _lib.ptr(ggrid), B, C, size[0], size[1], *tail),
+                       "deftet_image_sample_bwd_map_f32")
+    return ggrid
+
+
+def _grid_grads(lib, gout, grids, needs, c_off, C_total, make_cells):
+    """The gradients of the grids of a list (None where `needs` says so), grid k reading its rows of gout behind those of the
+    grids before it, from c_off: one sort of the points per distinct grid size (make_cells(size)), then the gather."""
+    grads, cells = [], {}
+    for g, need in zip(grids, needs):
+        size = tuple(g.shape[2:])
+        if need and size not in cells:
+            cells[size] = make_cells(size)
+        grads.append(_grid_bwd(lib, gout, cells[size], g.shape[1], c_off, C_total) if need else None)
+        c_off += g.shape[1]
+    return grads
+
+
+def _check_volumes(caller, volumes, pos):
+    """the volumes f32 [B,C,R,R,R] of `caller`, contiguous, on the device and with the batch of pos"""
+    vols = []
+    for v in volumes:
+        v = _pv_need(v, torch.float32, "%s: volume" % caller)
+        if v.dim() != 5 or v.shape[2] != v.shape[3] or v.shape[3] != v.shape[4] or v.shape[4] < 1:
+            raise RuntimeError("%s: volumes [B,C,R,R,R] expected (got %s)" % (caller, tuple(v.shape)))
+        if v.shape[0] != pos.shape[0] or v.device != pos.device:
+            raise RuntimeError("%s: volume %s and pos %s differ in batch or device" % (caller, tuple(v.shape), tuple(pos.shape)))
+        vols.append(v)
+    return vols
 
 
 class _VoxelSample(torch.autograd.Function):
@@ -2432,16 +2469,8 @@ class _VoxelSample(torch.autograd.Function):
         lib = _lib.load()
         dev = pos.device
         gout = _f32c(gout)
-        grads, cells, c_off = [], {}, 0
-        for k, v in enumerate(volumes):
-            C, R = v.shape[1], v.shape[-1]
-            if ctx.needs_input_grad[3 + k]:
-                if R not in cells:                                   # one sort per point set and distinct resolution
-                    cells[R] = _voxel_cells(lib, B, N, R, dev, pos=pos, pos_mode=pos_mode)
-                grads.append(_bwd_vol(lib, gout, cells[R], C, c_off, C_total))
-            else:
-                grads.append(None)
-            c_off += C
+        grads = _grid_grads(lib, gout, volumes, ctx.needs_input_grad[3:], 0, C_total,
+                            lambda size: _grid_cells(lib, B, N, size, dev, pos=pos, pos_mode=pos_mode))
         gpos = None
         if ctx.needs_input_grad[0]:
             gpos = torch.zeros_like(pos) if not volumes else torch.empty_like(pos)
@@ -2475,52 +2504,10 @@ def voxel_sample(volumes, pos, append_pos=False, voxel_units=False):
             raise RuntimeError("voxel_sample: coords [B,3,N] expected with voxel_units")
     elif pos.dim() != 3 or pos.shape[2] != 3:
         raise RuntimeError("voxel_sample: pos [B,N,3] expected")
-    B = pos.shape[0]
-    vols = []
-    for v in volumes:
-        v = _pv_need(v, torch.float32, "voxel_sample: volume")
-        if v.dim() != 5 or v.shape[2] != v.shape[3] or v.shape[3] != v.shape[4] or v.shape[4] < 1:
-            raise RuntimeError("voxel_sample: volumes [B,C,R,R,R] expected (got %s)" % (tuple(v.shape),))
-        if v.shape[0] != B or v.device != pos.device:
-            raise RuntimeError("voxel_sample: volume %s and pos %s differ in batch or device" % (tuple(v.shape), tuple(pos.shape)))
-        vols.append(v)
-    return _VoxelSample.apply(pos, bool(append_pos), 1 if voxel_units else 0, *vols)
+    return _VoxelSample.apply(pos, bool(append_pos), 1 if voxel_units else 0, *_check_volumes("voxel_sample", volumes, pos))
 
 
 # --------------------------------------------------------------------------------- pixel-aligned image features
-class ImageCells:
-    """The points of one uv set sorted by the cell they fall in at one map size (deftet_image_cells_f32): what the backward to
-    the maps gathers through.  Maps of equal (H, W) share it."""
-    __slots__ = ("perm", "seg", "wsorted", "B", "N", "H", "W")
-
-
-def _image_cells(lib, uv, B, N, H, W, border, align):
-    dev = uv.device
-    cells = ImageCells()
-    cells.B, cells.N, cells.H, cells.W = B, N, H, W
-    cells.perm = torch.empty(B * N, device=dev, dtype=torch.int32)
-    cells.seg = torch.empty(B * (H + 1) * (W + 1) + 1, device=dev, dtype=torch.int32)
-    cells.wsorted = torch.empty(4, B * N, device=dev, dtype=torch.float32)
-    with _lib.on_device(dev):
-        nbytes = lib.deftet_image_sample_workspace_bytes(B, N, H, W)
-        ws = _lib.workspace(dev, nbytes)
-        _lib.check(lib.deftet_image_cells_f32(_lib.ptr(uv), _lib.ptr(cells.perm), _lib.ptr(cells.seg), _lib.ptr(cells.wsorted), B, N, H, W,
-                                              border, align, _lib.ptr(ws), nbytes, _lib.current_stream(dev)), "deftet_image_cells_f32")
-    return cells
-
-
-def _image_bwd_map(lib, gout, cells, C, c_off, C_total):
-    B, N, H, W, dev = cells.B, cells.N, cells.H, cells.W, gout.device
-    gmap = torch.empty(B, C, H, W, device=dev, dtype=torch.float32)
-    with _lib.on_device(dev):
-        nbytes = lib.deftet_image_sample_workspace_bytes(B, N, H, W)
-        ws = _lib.workspace(dev, nbytes)
-        _lib.check(lib.deftet_image_sample_bwd_map_f32(_lib.ptr(gout), _lib.ptr(cells.perm), _lib.ptr(cells.seg), _lib.ptr(cells.wsorted),
-                                                       _lib.ptr(gmap), B, C, H, W, N, c_off, C_total, _lib.ptr(ws), nbytes,
-                                                       _lib.current_stream(dev)), "deftet_image_sample_bwd_map_f32")
-    return gmap
-
-
 class _ImageSample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, uv, glob, app, border, align, *maps):
@@ -2555,16 +2542,8 @@ class _ImageSample(torch.autograd.Function):
         lib = _lib.load()
         dev = uv.device
         gout = _f32c(gout)
-        grads, cells, c_off = [], {}, G
-        for k, m in enumerate(maps):
-            C, H, W = m.shape[1], m.shape[2], m.shape[3]
-            if ctx.needs_input_grad[5 + k]:
-                if (H, W) not in cells:                              # one sort per uv set and distinct map size
-                    cells[(H, W)] = _image_cells(lib, uv, B, N, H, W, border, align)
-                grads.append(_image_bwd_map(lib, gout, cells[(H, W)], C, c_off, C_total))
-            else:
-                grads.append(None)
-            c_off += C
+        grads = _grid_grads(lib, gout, maps, ctx.needs_input_grad[5:], G, C_total,
+                            lambda size: _grid_cells(lib, B, N, size, dev, uv=uv, border=border, align=align))
         guv = None
         if ctx.needs_input_grad[0]:
             guv = torch.zeros_like(uv) if not maps else torch.empty_like(uv)
@@ -2711,16 +2690,8 @@ class _TetCentroidSample(torch.autograd.Function):
         lib = _lib.load()
         dev = centroids.device
         gout = _f32c(gout)
-        grads, cells, c_off = [], {}, 0
-        for k, v in enumerate(volumes):
-            C, R = v.shape[1], v.shape[-1]
-            if ctx.needs_input_grad[8 + k]:
-                if R not in cells:                                   # one sort of the centroids per distinct resolution
-                    cells[R] = _voxel_cells(lib, B, K, R, dev, pos=centroids, pos_mode=0)
-                grads.append(_bwd_vol(lib, gout, cells[R], C, c_off, C_total))
-            else:
-                grads.append(None)
-            c_off += C
+        grads = _grid_grads(lib, gout, volumes, ctx.needs_input_grad[8:], 0, C_total,
+                            lambda size: _grid_cells(lib, B, K, size, dev, pos=centroids))
         gpos = None
         if ctx.needs_input_grad[0]:
             gcent = tet_centroid_sample_bwd_pos(volumes, centroids, gout, append_pos)
@@ -2758,14 +2729,7 @@ def tet_centroid_sample(volumes, pos_bxvx3, tet_idx, csr=None, select=None, firs
     if idx.dim() != 3 or idx.shape[2] != 4 or idx.shape[0] not in (1, B) or idx.device != pos.device:
         raise RuntimeError("tet_centroid_sample: tet_idx [T,4] or [B,T,4] on the device of pos expected (got %s)" % (tuple(tet_idx.shape),))
     T = idx.shape[1]
-    vols = []
-    for v in volumes:
-        v = _pv_need(v, torch.float32, "tet_centroid_sample: volume")
-        if v.dim() != 5 or v.shape[2] != v.shape[3] or v.shape[3] != v.shape[4] or v.shape[4] < 1:
-            raise RuntimeError("tet_centroid_sample: volumes [B,C,R,R,R] expected (got %s)" % (tuple(v.shape),))
-        if v.shape[0] != B or v.device != pos.device:
-            raise RuntimeError("tet_centroid_sample: volume %s and pos %s differ in batch or device" % (tuple(v.shape), tuple(pos.shape)))
-        vols.append(v)
+    vols = _check_volumes("tet_centroid_sample", volumes, pos)
     first = int(first)
     if select is not None:
         if count is not None or first != 0:
@@ -3000,8 +2964,8 @@ def trilinear_devoxelize_bwd(grad_y, inds, wgts, r):
     B, C, N = grad_y.shape
     if inds.shape[0] != B or inds.shape[2] != N:
         raise RuntimeError("trilinear_devoxelize_bwd: grad_y %s and inds %s do not agree" % (tuple(grad_y.shape), tuple(inds.shape)))
-    cells = _voxel_cells(lib, B, N, r, grad_y.device, inds=inds, wgts=wgts)
-    return _bwd_vol(lib, grad_y, cells, C, 0, C).view(B, C, r ** 3)
+    cells = _grid_cells(lib, B, N, (r, r, r), grad_y.device, inds=inds, wgts=wgts)
+    return _grid_bwd(lib, grad_y, cells, C, 0, C).view(B, C, r ** 3)
 
 
 # --------------------------------------------------------------------------------- ground-truth preparation

@@ -853,7 +853,8 @@ int deftet_face_gather_bwd_f32(const float *grad_face_xy, const float *grad_face
 
 /* The point-voxel operators between the point-cloud encoder and the tet grid (pointvoxel.hip).  No float atomics:
  * both scatters are gathers over a stable sort of the points (by voxel, by cell), so every sum has ONE order and two runs agree
- * bit for bit.  Workspaces 256-byte aligned, deftet_pointvoxel_workspace_bytes(B, N, R) covers every entry point below.
+ * bit for bit.  Workspace (256-byte aligned): deftet_pointvoxel_workspace_bytes(B, N, R) is the size of the one layout the four
+ * entries with a workspace carve; each refuses a null, misaligned or smaller one with DEFTET_EINVAL.
  *
  * deftet_avg_voxelize_fwd_f32 (vox.cu avg_voxelize): feat f32 [B,C,N], coords i32 [B,3,N] -> out f32 [B,C,R^3], ind i32 [B,N] =
  * x R^2 + y R + z, cnt i32 [B,R^3].  out[b,c,s] = 0 + feat[b,c,i] * (1.0f / (float)cnt[s]) over the points of voxel s in ascending
@@ -878,8 +879,8 @@ int deftet_face_gather_bwd_f32(const float *grad_face_xy, const float *grad_face
  *   a fixed butterfly over the lanes, offsets 32 .. 1); then grad_vol[b,c,v] = the up to eight part[k] of the cells v - k, corner
  *   k = 000 .. 111 in that order, from 0.  With isorted a term counts only where isorted[k][j] is the voxel corner k of the cell
  *   nominally lands in (the legacy hi index falls back on lo where its weight is 0): recorded indices that do not have this lo / hi
- *   structure lose their terms, and a non-finite grad_out does not reach voxels through a weight-0 term.  The workspace holds the
- *   partials of a chunk of channels (at least B R^3 32 bytes = one channel; deftet_pointvoxel_workspace_bytes gives up to 64 MiB).
+ *   structure lose their terms, and a non-finite grad_out does not reach voxels through a weight-0 term.  The channels are
+ *   chunked so that the partials (32 B R^3 bytes per channel) stay inside the workspace's 64 MiB (one channel if that is larger).
  * deftet_voxel_sample_bwd_pos_f32: grad_pos[b,p,j] (=, or += with accumulate) s * sum_c grad_out[b, channel_offset + c, p] *
  *   d interp / d u_j, channels ascending, s = R for pos_mode 0 and 1 for pos_mode 1 (grad_pos has the layout of pos); 0 for a
  *   coordinate the clamp holds (u <= 0 or u >= R - 1: grid_sample's border rule); the right-hand cell at an interior integer u. */

@@ -2,7 +2,10 @@
 """Generates tests/golden/workspace_sizes.json: what every *_workspace_bytes function whose size comes from a layout function
 returned BEFORE the layouts were introduced, at the shapes of tests/test_workspace_layout_cpu.py and at the workload's own.
 
-    DEFTET_HIP_LIB=<libdeftet_hip.so built from the commit before the layouts> python tests/golden/gen_workspace_sizes.py
+    DEFTET_HIP_LIB=<libdeftet_hip.so built from the commit before the layouts> python tests/golden/gen_workspace_sizes.py [FUNCTION ...]
+
+With function names only their rows are measured (the commit before THEIR layout: deftet_pointvoxel_workspace_bytes and
+deftet_image_sample_workspace_bytes came to cell_gather.hpp's layout later than the rest); every other function keeps its rows.
 
 The library loads without a GPU: the size functions are host arithmetic.  Each row is {"args": [...], "parent": bytes}; the rows
 at the workload's own shapes carry "workload": true (compared, never run).  A row where the parent under-declared what
@@ -52,6 +55,8 @@ SHAPES = {
     "deftet_face_vertex_csr_workspace_bytes": ([(125, 600)], [(VW, FW)]),
     "deftet_edge_vertex_csr_workspace_bytes": ([(125, 600)], [(VW, EW)]),
     "deftet_tet_order_coherence_workspace_bytes": ([(300,)], [(TW,)]),
+    "deftet_pointvoxel_workspace_bytes": ([(1, 257, 2), (3, 1000, 5), (2, 64, 8)], [(BW, VW, 32), (BW, VW, 8), (BW, 10000, 16)]),
+    "deftet_image_sample_workspace_bytes": ([(1, 257, 1, 1), (3, 1000, 5, 4)], [(BW, VW, 64, 64)]),
 }
 
 
@@ -65,6 +70,9 @@ def main():
     marks = {(f, tuple(r["args"])): r for f, rows in old.items() for r in rows if r.get("parent_too_small")}
     out = {}
     for name, (small, workload) in SHAPES.items():
+        if sys.argv[1:] and name not in sys.argv[1:]:
+            out[name] = old[name]
+            continue
         rows = []
         for args in small + workload:
             row = {"args": list(args), "parent": int(getattr(lib, name)(*args))}

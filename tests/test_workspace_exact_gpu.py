@@ -270,6 +270,39 @@ def test_sample_points(cuda, monkeypatch):
     check_exact(monkeypatch, lambda: metrics.sample_faces(fv, [1100, 700], u))
 
 
+# ------------------------------------------------------------------------------------------------ grid samplers (cell_gather.hpp)
+def test_avg_voxelize(cuda, monkeypatch):
+    from deftet_amd import hip_ops
+    feat, coords = rnd(32, 2, 3, 2100).to(cuda), rnd_idx(33, 7, 2, 3, 2100).int().to(cuda) - 1          # -1 and 5: outside R = 5
+    check_exact(monkeypatch, lambda: hip_ops.avg_voxelize_fwd(feat, coords, 5))
+
+
+def test_voxel_sample_forward_and_backward(cuda, monkeypatch):
+    """the sort of the points by cell and the corner partials of the volume backward, two resolutions"""
+    from deftet_amd import hip_ops
+    vols0, pos0, gout = [rnd(34, 2, 3, 5, 5, 5).to(cuda), rnd(35, 2, 2, 8, 8, 8).to(cuda)], (1.1 * (rnd(36, 2, 2100, 3) - 0.5)).to(cuda), rnd(37, 2, 5, 2100).to(cuda)
+
+    def call():
+        vols, pos = [v.clone().requires_grad_(True) for v in vols0], pos0.clone().requires_grad_(True)
+        out = hip_ops.voxel_sample(vols, pos)
+        out.backward(gout)
+        return out.detach(), pos.grad, [v.grad for v in vols]
+    check_exact(monkeypatch, call)
+
+
+def test_image_sample_forward_and_backward(cuda, monkeypatch):
+    from deftet_amd import hip_ops
+    maps0, uv0, gout = [rnd(38, 2, 3, 5, 4).to(cuda), rnd(39, 2, 2, 8, 8).to(cuda)], (2.6 * (rnd(40, 2, 2100, 2) - 0.5)).to(cuda), rnd(41, 2, 7, 2100).to(cuda)
+    glob0 = rnd(42, 2, 2).to(cuda)
+
+    def call():
+        maps, uv, glob = [m.clone().requires_grad_(True) for m in maps0], uv0.clone().requires_grad_(True), glob0.clone().requires_grad_(True)
+        out = hip_ops.image_sample(maps, uv, global_features=glob)
+        out.backward(gout)
+        return out.detach(), uv.grad, glob.grad, [m.grad for m in maps]
+    check_exact(monkeypatch, call)
+
+
 # ------------------------------------------------------------------------------------------------ private workspaces, by the C ABI
 @pytest.mark.parametrize("weights", [False, True], ids=["occ", "vertex_weights"])
 def test_surface_extract(grid8, cuda, weights):

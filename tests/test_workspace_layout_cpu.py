@@ -76,6 +76,15 @@ ENTRIES = {
     "deftet_face_vertex_csr_workspace_bytes": lambda L, w, V, F: [(L.deftet_face_vertex_csr_i32, (P, P, P, P, V, F, P, w, None))],
     "deftet_edge_vertex_csr_workspace_bytes": lambda L, w, V, E: [(L.deftet_edge_vertex_csr_i32, (P, P, P, P, V, E, P, w, None))],
     "deftet_tet_order_coherence_workspace_bytes": lambda L, w, T: [(L.deftet_tet_order_coherence_f32, (P, T, P, P, P, w, None))],
+    "deftet_pointvoxel_workspace_bytes": lambda L, w, B, N, R: [
+        (L.deftet_avg_voxelize_fwd_f32, (P, P, P, P, P, B, 3, N, R, P, w, None)),
+        (L.deftet_voxel_cells_f32, (P, 0, P, P, P, B, N, R, P, w, None)),
+        (L.deftet_voxel_cells_from_inds_i32, (P, P, P, P, P, P, B, N, R, P, w, None)),
+        (L.deftet_voxel_sample_bwd_vol_f32, (P, P, P, P, None, P, B, 3, R, N, 0, 3, P, w, None)),
+        (L.deftet_voxel_sample_bwd_vol_f32, (P, P, P, P, P, P, B, 3, R, N, 0, 3, P, w, None))],
+    "deftet_image_sample_workspace_bytes": lambda L, w, B, N, H, W: [
+        (L.deftet_image_cells_f32, (P, P, P, P, B, N, H, W, 0, 0, P, w, None)),
+        (L.deftet_image_sample_bwd_map_f32, (P, P, P, P, P, B, 3, H, W, N, 0, 3, P, w, None))],
 }
 
 

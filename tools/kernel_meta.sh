@@ -1,5 +1,5 @@
 #!/bin/bash
-# Registers, spills, scratch and LDS of every kernel of one source file of the library, as the compiler reports them in the code
+# Registers (vector, scalar), spills, scratch and LDS of every kernel of one source file of the library, as the compiler reports them in the code
 # object's metadata (no GPU needed):   tools/kernel_meta.sh point_in_tet.hip [-DNAME=V ...] [| grep k_tet_scan_wave]
 # The flags are the build's own (deftet_amd/build.py: FLAGS + the per-file ones).
 set -e
@@ -13,7 +13,7 @@ PY
 )
 tmp=$(mktemp -d)
 /opt/rocm/bin/hipcc $flags "$@" -I deftet_amd/csrc -x hip --cuda-device-only -S deftet_amd/csrc/$src -o $tmp/k.s 2>/dev/null
-grep -E "^\s+\.name:|\.vgpr_count|\.vgpr_spill_count|\.group_segment_fixed_size|\.private_segment_fixed_size" $tmp/k.s | paste - - - - - |
-  sed -E 's/\s+/ /g' | awk '{for(i=1;i<=NF;i++){if($i==".name:")n=$(i+1);if($i==".vgpr_count:")v=$(i+1);if($i==".vgpr_spill_count:")s=$(i+1);if($i==".group_segment_fixed_size:")l=$(i+1);if($i==".private_segment_fixed_size:")p=$(i+1)} print n, "vgpr", v, "spilled", s, "scratch_bytes", p, "lds_bytes", l}' |
-  while read n rest; do echo "$(echo $n | c++filt | sed -E 's/\(.*//; s/^void //') $rest"; done
+grep -E "^\s+\.name:|\.sgpr_count|\.vgpr_count|\.vgpr_spill_count|\.group_segment_fixed_size|\.private_segment_fixed_size" $tmp/k.s | paste - - - - - - |
+  sed -E 's/\s+/ /g' | awk '{for(i=1;i<=NF;i++){if($i==".name:")n=$(i+1);if($i==".sgpr_count:")g=$(i+1);if($i==".vgpr_count:")v=$(i+1);if($i==".vgpr_spill_count:")s=$(i+1);if($i==".group_segment_fixed_size:")l=$(i+1);if($i==".private_segment_fixed_size:")p=$(i+1)} print n, "vgpr", v, "sgpr", g, "spilled", s, "scratch_bytes", p, "lds_bytes", l}' |
+  while read n rest; do echo "$(echo $n | c++filt | sed -E 's/\(anonymous namespace\):://g; s/\(.*//; s/^void //') $rest"; done
 rm -rf $tmp
