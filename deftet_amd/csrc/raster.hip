@@ -24,7 +24,6 @@
 // accumulates its gradients in registers.
 #pragma clang fp contract(off)
 #include <cstring>
-#include <stdlib.h>
 
 #include "common.hpp"
 
@@ -319,20 +318,11 @@ __device__ unsigned long long g_rast_stats[8];
 #define RAST_STAT(i, v)
 #define RAST_STAT_MAX(i, v)
 #endif
-#ifndef RAST_ILP
-#define RAST_ILP 1                 // faces evaluated per trip of the face loop before they are committed in list order (1 / 2 / 4: 352 / 360 / 370 us)
-#endif
-#ifndef RAST_LDS_BCAST
-#define RAST_LDS_BCAST 1
-#endif
-#ifndef RAST_PROBE_NOSTORE
-#define RAST_PROBE_NOSTORE 0      // probe builds only (wrong results): the hit-record store of the NEAREST face loop left out
-#endif
 constexpr int kPendDepth = 4;          // admitted hits a full lane queues before the wave works the queues off (NEAREST)
 
 // One wave per 64 pixels OF ONE TILE: the face list is then the same for every lane, so the wave
 // loads 64 list entries and their 36 bytes of face data with one coalesced round trip (lane k holds
-// face k) and broadcasts them one after the other with v_readlane — the per-lane formulation spent
+// face k) and hands them to the pixel lanes one after the other through LDS — the per-lane formulation spent
 // two dependent gather latencies on every candidate (1.5 ms at configs[4], lists of ~1,700 faces).
 // FIRST policy: faces are visited in ascending index (tile list merged with the wide list), every lane keeps its first
 // `knum` hits and the wave stops when all its lanes are full.  NEAREST policy: the whole list is visited (from the end
@@ -432,9 +422,7 @@ __global__ __launch_bounds__(256) void k_pix_raster(const float *__restrict__ pi
     // pending hit in the same pass.  A queued hit is re-tested against the lane's current worst when it is taken out (the
     // threshold only tightens in between).
     __shared__ int4 s_pend[4][kPendDepth][64];
-#if RAST_LDS_BCAST
     __shared__ float4 s_face[4][64][3];                              // per wave: the batch's faces, 48 bytes each
-#endif
     int4(*pend)[64] = s_pend[threadIdx.x >> 6];
     float worstZ = INFINITY;                                        // the record a better hit would replace
     int worstF = -1, worstAt = 0, npend = 0;
@@ -445,11 +433,11 @@ __global__ __launch_bounds__(256) void k_pix_raster(const float *__restrict__ pi
         npend = 0;
     };
     // One (face, pixel) test in two halves: `eval` is pure arithmetic (the contract's operations, nothing else), `commit` records
-    // the hit.  The face loop below evaluates RAST_ILP faces per trip before it commits them in list order: a wave's trip is one
-    // long dependent chain (eleven lane reads, two IEEE division sequences of ten dependent instructions each, five compares),
-    // there are only four waves per SIMD to interleave (4,096 chunks on 1,024 SIMDs), and by the counters the vector ALU was
-    // "busy" 0.9 k cycles per trip for ~60 instructions — waiting for its own results (round 6: profiles/r06_raster_probes.jsonl;
-    // the hit-record stores, suspected first, are not it: without them the kernel takes 0.87 instead of 0.89 ms).
+    // the hit.  The face loop below evaluates one face per trip and commits it in list order: a wave's trip is one long dependent
+    // chain (two IEEE division sequences of ten dependent instructions each, five compares), there are only four waves per SIMD
+    // to interleave (4,096 chunks on 1,024 SIMDs), and by the counters the vector ALU was "busy" 0.9 k cycles per trip for ~60
+    // instructions — waiting for its own results (round 6: profiles/r06_raster_probes.jsonl; the hit-record stores, suspected
+    // first, are not it: without them the kernel takes 0.87 instead of 0.89 ms).
     struct Ev { float z, w1, w2; bool ok; };
     auto eval = [&](float ax, float ay, float m, float pp, float n, float q, float den, float az, float bz, float cz) __attribute__((always_inline)) {
         const float s_ = px - ax, t = py - ay;
@@ -476,11 +464,7 @@ __global__ __launch_bounds__(256) void k_pix_raster(const float *__restrict__ pi
         if (e.ok) {
             const int4 rec = make_int4(f, __float_as_int(e.z), __float_as_int(e.w1), __float_as_int(e.w2));
             if (nh < knum) {
-#if RAST_PROBE_NOSTORE == 0
                 out[nh] = rec;
-#elif RAST_PROBE_NOSTORE == 2
-                if (nh == 1000000) out[nh] = rec;                     // timing probe: the store stays in the code, never executes
-#endif
                 if (nh == 0 || worse(e.z, f, worstZ, worstF)) { worstZ = e.z; worstF = f; worstAt = nh; }
                 dnh = 1;
             } else if (live && knum > 0 && worse(worstZ, worstF, e.z, f)) {   // full (dead lanes only count as full)
@@ -613,11 +597,11 @@ __global__ __launch_bounds__(256) void k_pix_raster(const float *__restrict__ pi
         nBroadcast += __popcll(todo);
 #endif
         int since = 0;
-#if RAST_LDS_BCAST
         // The surviving faces are handed to the 64 pixel lanes through LDS: every lane parks the eleven words of ITS face, the
         // wave reads them back one face at a time with three 16-byte reads at a wave-uniform address (a broadcast: one LDS
         // cycle each, on the LDS pipe) — the next face's reads are in flight while this one is evaluated.  Eleven v_readlane
-        // per face were 8 cycles of the VECTOR pipe each on this chip (tools/probes/valu_rate_probe.hip), a quarter of a trip.
+        // per face were 8 cycles of the VECTOR pipe each on this chip (tools/probes/valu_rate_probe.hip), a quarter of a trip,
+        // and evaluating 1 / 2 / 4 faces per trip before committing them only made that loop slower (352 / 360 / 370 us).
         {
             float4 *mine = &s_face[threadIdx.x >> 6][lane][0];
             mine[0] = make_float4(a.x, a.y, fm_, fpp);
@@ -643,33 +627,6 @@ __global__ __launch_bounds__(256) void k_pix_raster(const float *__restrict__ pi
             c0 = n0; c1 = n1; c2 = n2;
         }
         __builtin_amdgcn_wave_barrier();                               // (the next batch overwrites s_face: DS operations of a wave execute in order)
-#else
-        while (todo) {
-            int kk[RAST_ILP], ff[RAST_ILP];
-            Ev ev[RAST_ILP];
-            bool have[RAST_ILP];
-#pragma unroll
-            for (int u = 0; u < RAST_ILP; ++u) {                      // (past the end of the batch: the last face again, not committed)
-                have[u] = todo != 0ull;
-                kk[u] = have[u] ? __ffsll((long long)todo) - 1 : kk[u > 0 ? u - 1 : 0];
-                todo &= todo - 1;
-                ff[u] = __builtin_amdgcn_readlane(fm, kk[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < RAST_ILP; ++u)
-                ev[u] = eval(bcast(a.x, kk[u]), bcast(a.y, kk[u]), bcast(fm_, kk[u]), bcast(fpp, kk[u]), bcast(fn, kk[u]), bcast(fq, kk[u]),
-                             bcast(fden, kk[u]), bcast(az, kk[u]), bcast(bz, kk[u]), bcast(cz, kk[u]));
-            bool stop = false;
-#pragma unroll
-            for (int u = 0; u < RAST_ILP; ++u) {
-                if (!have[u] || stop) continue;                       // (wave-uniform)
-                if (je > 0 && !nearest) wide_before(ff[u]);           // FIRST: wide faces merged in face order
-                commit(ff[u], ev[u]);
-                if (!nearest && (++since & 7) == 0 && __all(nh >= knum)) stop = true;
-            }
-            if (stop) break;
-        }
-#endif
         fmCur = fmNext; cur = nxt; fmNext = fmAfter;
     }
     if (je > 0) wide_before(0x7FFFFFFF);
@@ -680,7 +637,7 @@ __global__ __launch_bounds__(256) void k_pix_raster(const float *__restrict__ pi
     RAST_STAT_MAX(7, __builtin_amdgcn_s_memtime() - tStart);            // [7] longest wave, shader cycles
 #endif
     RAST_STAT(3, __popcll(__ballot(live)));                             // [3] live lanes
-    if (live) nhit[p] = (nearest && RAST_PROBE_NOSTORE) ? 0 : nh;      // (probe builds wrote no records: nothing for k_pix_emit to read)
+    if (live) nhit[p] = nh;
 }
 
 // The rank of hit `me` (record i0 + lane of the pixel's n records h[]) in the output order (z descending, face ascending): the
@@ -868,8 +825,8 @@ __device__ __forceinline__ void block_carry(float (&v)[N], float (*s_sum)[20], c
     }
     if (e.contL && e.w > 0) {
         int u = e.w - 1;
-        while (u > 0 && s_one[u]) --u;
-        fromBefore = u == 0 && s_one[0];
+        while (u >= 0 && s_one[u]) --u;                              // back over the waves that one run crosses from end to end, wave 0
+        fromBefore = u < 0;                                          // included (read apart, s_one[0] was hoisted to all lanes: +1 % time)
     }
     const lanemask_t mFirst = __ballot(inFirstRun);
 #pragma unroll
@@ -880,7 +837,6 @@ __device__ __forceinline__ void block_carry(float (&v)[N], float (*s_sum)[20], c
     ext = inFirstRun && fromBefore;
 }
 
-template <int DT>   // DT = number of feature channels when it is 4 (16-byte loads and stores, loops unroll), 0 = run-time D
 __global__ __launch_bounds__(kBwdWaves * 64) void k_bwd_sorted(const float *__restrict__ pix, const float *__restrict__ fxy,
                                                                const float *__restrict__ feat, const float *__restrict__ gout,
                                                                const unsigned *__restrict__ skey, const unsigned *__restrict__ sval,
@@ -892,7 +848,6 @@ __global__ __launch_bounds__(kBwdWaves * 64) void k_bwd_sorted(const float *__re
     if (skey[i0] >= (unsigned)F) return;                            // the padding tail (keys are sorted): whole block idle
     const long long i = i0 + threadIdx.x;
     const int lane = threadIdx.x & 63;
-    if (DT) D = DT;
     const unsigned key = i < n ? skey[i] : (unsigned)F;
     const bool valid = key < (unsigned)F;
     const unsigned kprev = (valid && i > 0) ? skey[i - 1] : 0xFFFFFFFFu;
@@ -924,7 +879,7 @@ __global__ __launch_bounds__(kBwdWaves * 64) void k_bwd_sorted(const float *__re
     {
         float gw1 = 0.f, gw2 = 0.f;                                  // dL/dw1, dL/dw2 (w0 = 1 - w1 - w2)
 #pragma unroll
-        for (int d = 0; d < (DT ? DT : D); ++d) {
+        for (int d = 0; d < D; ++d) {
             const float gd = g[d];
             gw1 += gd * (ff[D + d] - ff[d]);
             gw2 += gd * (ff[2 * D + d] - ff[d]);
@@ -950,7 +905,7 @@ __global__ __launch_bounds__(kBwdWaves * 64) void k_bwd_sorted(const float *__re
             for (int k = 0; k < 6; ++k) unsafeAtomicAdd(o + k, v[k]);
         }
     }
-    for (int c0 = 0; c0 < (DT ? DT : D); c0 += kDChunk) {         // one trip when DT == 4
+    for (int c0 = 0; c0 < D; c0 += kDChunk) {
         float v[3 * kDChunk];
 #pragma unroll
         for (int d = 0; d < kDChunk; ++d) {
@@ -962,17 +917,11 @@ __global__ __launch_bounds__(kBwdWaves * 64) void k_bwd_sorted(const float *__re
         block_carry(v, s_sum, s_one, e, lane, inFirstRun, ext);
         float *o = gfeat + (size_t)f * 3 * D + c0;
         if (ends && !ext) {
-            if (DT == 4) {
 #pragma unroll
-                for (int vtx = 0; vtx < 3; ++vtx)
-                    reinterpret_cast<float4 *>(o)[vtx] = make_float4(v[vtx * 4], v[vtx * 4 + 1], v[vtx * 4 + 2], v[vtx * 4 + 3]);
-            } else {
+            for (int vtx = 0; vtx < 3; ++vtx)
 #pragma unroll
-                for (int vtx = 0; vtx < 3; ++vtx)
-#pragma unroll
-                    for (int d = 0; d < kDChunk; ++d)
-                        if (c0 + d < D) o[(size_t)vtx * D + d] = v[vtx * kDChunk + d];
-            }
+                for (int d = 0; d < kDChunk; ++d)
+                    if (c0 + d < D) o[(size_t)vtx * D + d] = v[vtx * kDChunk + d];
         } else if ((ends && ext) || spill) {
 #pragma unroll
             for (int vtx = 0; vtx < 3; ++vtx)
@@ -1618,18 +1567,13 @@ static int reduce_by_face(KeyLoad keys, const float *pix, const float *fxy, cons
                                                                   L.tmpBytes, st);
         if (rc != DEFTET_OK) return rc;
     }
-#define RAST_BWD(DT)                                                                                                                  \
-    DEFTET_LAUNCH(k_bwd_sorted<DT>, dim3((unsigned)((n + kBwdWaves * 64 - 1) / (kBwdWaves * 64))), dim3(kBwdWaves * 64), st, pix, fxy, \
-                  feat, gout, (const unsigned *)L.skey, (const unsigned *)L.sval, n, F, D, knum, eps, gxy, gfeat)
-    // DEFTET_RAST_BWD=sorted: the round-5 kernel for D = 4 as well (A/B runs)
-    static const bool runs = [] { const char *e = getenv("DEFTET_RAST_BWD"); return !(e && e[0] == 's'); }();
-    const bool d4 = D == 4 && (((uintptr_t)feat | (uintptr_t)gout | (uintptr_t)gfeat) & 15) == 0;
-    if (d4 && runs)
+    // k_bwd_runs is written for four channels and 16-byte loads and stores; everything else takes the run-time-D kernel
+    if (D == 4 && (((uintptr_t)feat | (uintptr_t)gout | (uintptr_t)gfeat) & 15) == 0)
         DEFTET_LAUNCH(k_bwd_runs, dim3((unsigned)((n + kRunBlock - 1) / kRunBlock)), dim3(kRunWaves * 64), st, pix, fxy, feat, gout,
                       (const unsigned *)L.skey, (const unsigned *)L.sval, n, F, knum, eps, gxy, gfeat);
-    else if (d4) RAST_BWD(4);
-    else RAST_BWD(0);
-#undef RAST_BWD
+    else
+        DEFTET_LAUNCH(k_bwd_sorted, dim3((unsigned)((n + kBwdWaves * 64 - 1) / (kBwdWaves * 64))), dim3(kBwdWaves * 64), st, pix, fxy,
+                      feat, gout, (const unsigned *)L.skey, (const unsigned *)L.sval, n, F, D, knum, eps, gxy, gfeat);
     return DEFTET_OK;
 }
 

@@ -13,7 +13,6 @@
 // operation by operation in fp32 with FMA contraction off (the argmin / neighbour indices
 // are decided by exact fp32 comparisons), double-typed literals promoted as C++ does.
 #pragma clang fp contract(off)
-#include <cstdlib>
 #include <cstring>
 
 #include "common.hpp"
@@ -258,10 +257,7 @@ static int nn_far_key_bits(int G)
     while ((1 << bits) < G + 2) ++bits;
     return 3 * bits;
 }
-#ifndef NN_FAR_ROWS
-#define NN_FAR_ROWS 25
-#endif
-constexpr int kFarRows = NN_FAR_ROWS;
+constexpr int kFarRows = 25;
 
 __device__ __forceinline__ unsigned spread3(unsigned v)            // bit i of an 8-bit value -> bit 3i
 {
@@ -481,10 +477,7 @@ __global__ __launch_bounds__(64) void k_nn_far_pad(float4 *repList, const int *_
 // with one same-address atomic per query and every far query scanning ALL points 7.2 ms; pruned rows, one wave per 64
 // queries, one scalar load per record 14.3 ms; batches of eight and 4 / 16 waves per group 4.5 / 2.4 ms; A and B shared
 // between the waves 1.55 ms — the group that needs every point then kept one CU busy for 1 ms.)
-#ifndef NN_FAR_SLICES
-#define NN_FAR_SLICES 8
-#endif
-constexpr int kFarSlices = NN_FAR_SLICES;   // blocks per group of 64 far queries in k_nn_far_rows
+constexpr int kFarSlices = 8;            // blocks per group of 64 far queries in k_nn_far_rows
 constexpr int kFarWaves = 4;            // waves per block; they split the block's records
 
 struct FarLane {
@@ -1254,10 +1247,7 @@ constexpr int kTGMax = 64;             // cells per axis (upper bound)
 constexpr int kTMaxCells = 64;         // faces overlapping more cells go to the wide list
 constexpr int kTParts = 64;
 
-#ifndef TRI_CELL_SCALE
-#define TRI_CELL_SCALE 1.0f
-#endif
-constexpr float kTCellScale = TRI_CELL_SCALE;   // cell width in mean face extents
+constexpr float kTCellScale = 1.0f;    // cell width in mean face extents
 
 struct TGrid { float o[3], inv[3], cs[3], slack[3]; int g[3]; float abs_slack; };
 
@@ -1846,10 +1836,7 @@ constexpr int kTriQueryBlocks = 8192;
 // (Register budget of FOUR waves per SIMD: the allocator takes 145 VGPRs = three waves when left alone; held to 128 it
 // spills nine dwords and the kernel runs 0.76 -> 0.63 ms at 8 x 97 k points — five waves, 96 VGPRs with 176 bytes of
 // scratch, and six are slower again: geometry step 2.80 / 2.68 / 2.85 / 3.24 ms for 3 / 4 / 5 / 6 waves.)
-#ifndef TRI_WAVES
-#define TRI_WAVES 4
-#endif
-__attribute__((amdgpu_waves_per_eu(TRI_WAVES, 8)))
+__attribute__((amdgpu_waves_per_eu(4, 8)))
 __global__ __launch_bounds__(kTriChunkWaves * 64) void k_tri_query_coop(const float *__restrict__ pts, const float *__restrict__ face,
                                                                          const float *__restrict__ nfb, int P, const TGrid *__restrict__ gp,
                                                                          const int *__restrict__ cellStart, const int *__restrict__ list,
@@ -2307,13 +2294,7 @@ static int nn_pick_G(int M)
     // every query scans first held ~300 points).  Measured on the geometry step (8 x 97 k points, 8 x 80 k queries):
     // 3.49 / 3.32 / 3.27 / 3.22 ms per step at 1 / 1.4 / 1.8 / 2.4 x; a single shape (one call, 80 k queries) 0.32 / 0.29 /
     // 0.41 / 0.39 ms — finer grids cost a lone call more in rows visited per query than they save in points per row.
-    // DEFTET_NN_GSCALE (read once; experiments) scales the cells per axis further.
-    static const double scale = [] {
-        const char *e = std::getenv("DEFTET_NN_GSCALE");
-        const double v = e ? std::atof(e) : 1.0;
-        return v > 0.1 && v < 10.0 ? v : 1.0;
-    }();
-    int G = (int)llround(scale * 1.5 * cbrt((double)(M > 0 ? M : 1) / 4.0));
+    int G = (int)llround(1.5 * cbrt((double)(M > 0 ? M : 1) / 4.0));
     if (G < 1) G = 1;
     if (G > 160) G = 160;
     return G;
@@ -2653,49 +2634,40 @@ static int tri_dist_group(const float *pts, const float *face, const float *nfb,
     const TriLayout TL = tri_layout(nS, P, Fmax, ws);                 // at most what the entry checked: a group is no larger than the largest
     const TriSlice &L = TL.S;
     const size_t slice = TL.slice;
-    float *part = L.part;
-    TGrid *grid = L.grid;
-    int *cnt = L.cnt, *start = L.start, *fill = L.fill, *list = L.list, *wide = L.wide, *farList = L.farList, *counters = L.counters;
-    int *farFlag = L.farFlag, *farOff = L.farOff, *rep = L.rep, *ptStart = L.ptStart, *chunkCount = L.chunkCount, *chunkStart = L.chunkStart;
-    unsigned long long *bound = L.bound;
-    float4 *sph = L.sph;
-    uint2 *frange = L.frange;
-    int *pcount = L.pcount, *pstart = L.pstart;
-    int2 *prank = L.prank;
     const size_t nAll = (size_t)nS * P;
     unsigned *pskey = TL.pskey, *order = TL.order;
     const dim3 blk(256);
-    DEFTET_LAUNCH(k_tri_face_stats, dim3(kTParts, nS), blk, st, face, nfb, part, slice, Fmax, cnt, fill, counters, rep, (int)nc, kTGc * kTGc * kTGc,
-                  pcount);
-    DEFTET_LAUNCH(k_tri_grid, dim3(nS), dim3(64), st, (const float *)part, grid, slice);
-    DEFTET_LAUNCH(k_tri_face_bin, dim3((Fmax + 255) / 256, nS), blk, st, face, nfb, (const TGrid *)grid, 0, cnt, (const int *)start, fill, list, wide,
-                  counters, rep, slice, Fmax, sph, frange);
-    DEFTET_LAUNCH(k_scan_excl, dim3(scan_tiles(nc), nS), dim3(kScanThreads), st, (const int *)cnt, start, (int)nc, slice, 0);
-    DEFTET_LAUNCH(k_tri_face_bin, dim3((Fmax + 255) / 256, nS), blk, st, face, nfb, (const TGrid *)grid, 1, cnt, (const int *)start, fill, list, wide,
-                  counters, rep, slice, Fmax, sph, frange);
-    DEFTET_LAUNCH(k_tri_point_keys, dim3((P + 255) / 256, nS), blk, st, pts, P, (const TGrid *)grid, pcount, prank, slice);
-    DEFTET_LAUNCH(k_scan_excl, dim3(scan_tiles(nc), nS), dim3(kScanThreads), st, (const int *)pcount, pstart, (int)nc, slice, 0);
-    DEFTET_LAUNCH(k_tri_point_scatter, dim3((P + 255) / 256, nS), blk, st, P, (const int2 *)prank, (const int *)pstart, order, pskey, slice);
+    DEFTET_LAUNCH(k_tri_face_stats, dim3(kTParts, nS), blk, st, face, nfb, L.part, slice, Fmax, L.cnt, L.fill, L.counters, L.rep, (int)nc, kTGc * kTGc * kTGc,
+                  L.pcount);
+    DEFTET_LAUNCH(k_tri_grid, dim3(nS), dim3(64), st, (const float *)L.part, L.grid, slice);
+    DEFTET_LAUNCH(k_tri_face_bin, dim3((Fmax + 255) / 256, nS), blk, st, face, nfb, (const TGrid *)L.grid, 0, L.cnt, (const int *)L.start, L.fill, L.list, L.wide,
+                  L.counters, L.rep, slice, Fmax, L.sph, L.frange);
+    DEFTET_LAUNCH(k_scan_excl, dim3(scan_tiles(nc), nS), dim3(kScanThreads), st, (const int *)L.cnt, L.start, (int)nc, slice, 0);
+    DEFTET_LAUNCH(k_tri_face_bin, dim3((Fmax + 255) / 256, nS), blk, st, face, nfb, (const TGrid *)L.grid, 1, L.cnt, (const int *)L.start, L.fill, L.list, L.wide,
+                  L.counters, L.rep, slice, Fmax, L.sph, L.frange);
+    DEFTET_LAUNCH(k_tri_point_keys, dim3((P + 255) / 256, nS), blk, st, pts, P, (const TGrid *)L.grid, L.pcount, L.prank, slice);
+    DEFTET_LAUNCH(k_scan_excl, dim3(scan_tiles(nc), nS), dim3(kScanThreads), st, (const int *)L.pcount, L.pstart, (int)nc, slice, 0);
+    DEFTET_LAUNCH(k_tri_point_scatter, dim3((P + 255) / 256, nS), blk, st, P, (const int2 *)L.prank, (const int *)L.pstart, order, pskey, slice);
     if (order_out) DEFTET_HIP(hipMemcpyAsync(order_out, order, nAll * 4, hipMemcpyDeviceToDevice, st));   // for the grouped backward
-    DEFTET_LAUNCH(k_tri_chunks, dim3((kTRows + 1 + 255) / 256, nS), blk, st, (const int *)pstart, ptStart, chunkCount, slice);
-    DEFTET_LAUNCH(k_scan_excl, dim3(scan_tiles(kTRows + 1), nS), dim3(kScanThreads), st, (const int *)chunkCount, chunkStart, kTRows + 1, slice, 0);
+    DEFTET_LAUNCH(k_tri_chunks, dim3((kTRows + 1 + 255) / 256, nS), blk, st, (const int *)L.pstart, L.ptStart, L.chunkCount, slice);
+    DEFTET_LAUNCH(k_scan_excl, dim3(scan_tiles(kTRows + 1), nS), dim3(kScanThreads), st, (const int *)L.chunkCount, L.chunkStart, kTRows + 1, slice, 0);
     {
         const long long maxChunks = (long long)(P + 63) / 64 + (long long)kTRows;
         DEFTET_LAUNCH(k_tri_query_coop, dim3((unsigned)std::min<long long>(maxChunks, kTriQueryBlocks), nS), dim3(kTriChunkWaves * 64), st, pts,
-                      face, nfb, P, (const TGrid *)grid, (const int *)start, (const int *)list, (const int *)wide, (const int *)counters, cd, cf,
-                      farFlag, (const unsigned *)order, (const int *)ptStart, (const int *)chunkStart, (const int *)rep, slice, Fmax, (const float4 *)sph,
-                      (const unsigned *)pskey, (const uint2 *)frange);
+                      face, nfb, P, (const TGrid *)L.grid, (const int *)L.start, (const int *)L.list, (const int *)L.wide, (const int *)L.counters, cd, cf,
+                      L.farFlag, (const unsigned *)order, (const int *)L.ptStart, (const int *)L.chunkStart, (const int *)L.rep, slice, Fmax, (const float4 *)L.sph,
+                      (const unsigned *)pskey, (const uint2 *)L.frange);
     }
     // the far path (counters: [0] wide faces, [1] far points)
-    DEFTET_LAUNCH(k_scan_excl, dim3(scan_tiles(P), nS), dim3(kScanThreads), st, (const int *)farFlag, farOff, P, slice, 0);
-    DEFTET_LAUNCH(k_tri_compact, dim3((P + 255) / 256, nS), blk, st, (const int *)farFlag, (const int *)farOff, (const unsigned *)order, P, farList,
-                  counters + 1, slice);
-    DEFTET_LAUNCH(k_tri_far_bound, dim3((P + 63) / 64, nS), dim3(kTriWaves * 64), st, pts, face, (const TGrid *)grid, (const int *)wide,
-                  (const int *)counters, (const int *)rep, (const int *)farList, (const int *)(counters + 1), bound, slice, P, Fmax);
-    DEFTET_LAUNCH(k_tri_far_rows, dim3((P + 63) / 64, kTriSlices, nS), dim3(kTriWaves * 64), st, pts, face, nfb, (const TGrid *)grid,
-                  (const int *)start, (const int *)list, (const int *)farList, (const int *)(counters + 1), bound, slice, P, Fmax);
-    DEFTET_LAUNCH(k_tri_far_final, dim3((P + 255) / 256, nS), blk, st, (const unsigned long long *)bound, (const int *)(counters + 1),
-                  (const int *)farList, cd, cf, slice, P);
+    DEFTET_LAUNCH(k_scan_excl, dim3(scan_tiles(P), nS), dim3(kScanThreads), st, (const int *)L.farFlag, L.farOff, P, slice, 0);
+    DEFTET_LAUNCH(k_tri_compact, dim3((P + 255) / 256, nS), blk, st, (const int *)L.farFlag, (const int *)L.farOff, (const unsigned *)order, P, L.farList,
+                  L.counters + 1, slice);
+    DEFTET_LAUNCH(k_tri_far_bound, dim3((P + 63) / 64, nS), dim3(kTriWaves * 64), st, pts, face, (const TGrid *)L.grid, (const int *)L.wide,
+                  (const int *)L.counters, (const int *)L.rep, (const int *)L.farList, (const int *)(L.counters + 1), L.bound, slice, P, Fmax);
+    DEFTET_LAUNCH(k_tri_far_rows, dim3((P + 63) / 64, kTriSlices, nS), dim3(kTriWaves * 64), st, pts, face, nfb, (const TGrid *)L.grid,
+                  (const int *)L.start, (const int *)L.list, (const int *)L.farList, (const int *)(L.counters + 1), L.bound, slice, P, Fmax);
+    DEFTET_LAUNCH(k_tri_far_final, dim3((P + 255) / 256, nS), blk, st, (const unsigned long long *)L.bound, (const int *)(L.counters + 1),
+                  (const int *)L.farList, cd, cf, slice, P);
     return DEFTET_OK;
 }
 
@@ -2748,6 +2720,19 @@ extern "C" int deftet_tri_dist_bwd_order_f32(const float *pts, const float *face
     return DEFTET_OK;
 }
 
+// The deterministic backward between the allocation of its scratch and the release (the caller owns key, skey and tmp).
+static int tri_dist_bwd_sorted(const float *pts, const float *face, const float *closest_f, const float *dl_dd, float *dldface, long long n,
+                               int P, int F, unsigned long long *key, unsigned long long *skey, void *tmp, size_t tmpBytes, hipStream_t st)
+{
+    DEFTET_LAUNCH(k_bwd_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), st, closest_f, n, P, F, key);
+    {
+        const int rc = prims::radix_sort_keys<unsigned long long>(key, skey, (size_t)n, 64, tmp, tmpBytes, st);
+        if (rc != DEFTET_OK) return rc;
+    }
+    DEFTET_LAUNCH(k_tri_dist_bwd_sorted, dim3((unsigned)((n + 255) / 256)), dim3(256), st, pts, face, dl_dd, skey, n, P, F, dldface);
+    return DEFTET_OK;
+}
+
 extern "C" int deftet_tri_dist_bwd_f32(const float *pts, const float *face, const float *closest_f, const float *dl_dd,
                                        float *dldface, int B, int P, int F, int deterministic, void *stream_)
 {
@@ -2762,20 +2747,24 @@ extern "C" int deftet_tri_dist_bwd_f32(const float *pts, const float *face, cons
     // deterministic mode allocates its own scratch (stream-ordered), it is a test/debug path
     const long long n = (long long)B * P;
     DEFTET_CHECK_ARG((long long)B * F < 0xFFFFFFFFLL, "too many faces for the deterministic path");
-    unsigned long long *key = nullptr, *skey = nullptr;
-    void *tmp = nullptr;
-    const size_t need = prims::radix_sort_temp_bytes<unsigned long long, unsigned>((size_t)n, false);
-    DEFTET_HIP(hipMallocAsync((void **)&key, (size_t)n * 8, st));
-    DEFTET_HIP(hipMallocAsync((void **)&skey, (size_t)n * 8, st));
-    DEFTET_HIP(hipMallocAsync(&tmp, need, st));
-    DEFTET_LAUNCH(k_bwd_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), st, closest_f, n, P, F, key);
-    {
-        const int rc = prims::radix_sort_keys<unsigned long long>(key, skey, (size_t)n, 64, tmp, need, st);
-        if (rc != DEFTET_OK) return rc;
+    // key, skey and the sort's temporary: released on every way out, and the first error is the one reported
+    const size_t bytes[3] = {(size_t)n * 8, (size_t)n * 8, prims::radix_sort_temp_bytes<unsigned long long, unsigned>((size_t)n, false)};
+    void *buf[3] = {nullptr, nullptr, nullptr};
+    int rc = DEFTET_OK;
+    for (int k = 0; k < 3 && rc == DEFTET_OK; ++k) {
+        const hipError_t e = hipMallocAsync(&buf[k], bytes[k], st);
+        if (e != hipSuccess) {
+            buf[k] = nullptr;
+            rc = set_error(DEFTET_ELAUNCH, "hipMallocAsync of %zu bytes failed: %s", bytes[k], hipGetErrorString(e));
+        }
     }
-    DEFTET_LAUNCH(k_tri_dist_bwd_sorted, dim3((unsigned)((n + 255) / 256)), dim3(256), st, pts, face, dl_dd, skey, n, P, F, dldface);
-    DEFTET_HIP(hipFreeAsync(key, st));
-    DEFTET_HIP(hipFreeAsync(skey, st));
-    DEFTET_HIP(hipFreeAsync(tmp, st));
-    return DEFTET_OK;
+    if (rc == DEFTET_OK)
+        rc = tri_dist_bwd_sorted(pts, face, closest_f, dl_dd, dldface, n, P, F, (unsigned long long *)buf[0], (unsigned long long *)buf[1],
+                                 buf[2], bytes[2], st);
+    for (int k = 0; k < 3; ++k) {
+        if (!buf[k]) continue;
+        const hipError_t e = hipFreeAsync(buf[k], st);
+        if (e != hipSuccess && rc == DEFTET_OK) rc = set_error(DEFTET_ELAUNCH, "hipFreeAsync failed: %s", hipGetErrorString(e));
+    }
+    return rc;
 }

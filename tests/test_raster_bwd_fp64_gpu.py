@@ -1,4 +1,4 @@
-"""The rasterizer backward (k_bwd_runs, k_bwd_sorted<0>, k_bwd_sorted<4> of csrc/raster.hip; DESIGN.md section 6, "What is pinned")
+"""The rasterizer backward (k_bwd_runs and k_bwd_sorted of csrc/raster.hip; DESIGN.md section 6, "What is pinned")
 against fp64 on faces of known conditioning and on the edges of the reduction (tests/raster_bwd_cases.py; test_raster_bwd_ref_cpu.py
 is the CPU half and says where K and KAPPA_CAP come from).  Every call goes to deftet_sparse_render_bwd_f32 with a face list made
 by construction — which pixel hits which face, and how many hits a face collects: 4 per lane, 256 per wave, 1,024 per block for
@@ -9,9 +9,10 @@ with u = 2^-24 and K = raster_bwd_cases.K:
 
 1 bound         default path (k_bwd_runs, D = 4): band x flat x {lane, wave, block} x knum 1, 5; faces without a hit exactly zero; two
                 runs bit-equal on every face with at most 1,024 hits (larger ones meet through atomics: the bound only).
-2 width         k_bwd_sorted<0>: D = 3, 6, 9, B = 2 (the second shape a shifted copy with other features), bands image and unit.
-3 sorted<4>     one child process with DEFTET_RAST_BWD=sorted runs the image cases of 1; the same bounds, and the two kernels agree
-                within the sum of their bounds.
+2 width         k_bwd_sorted: D = 3, 6, 9, B = 2 (the second shape a shifted copy with other features), bands image and unit.
+3 unaligned     the image cases of 1 with the features 4 bytes off a 16-byte boundary, which sends D = 4 to k_bwd_sorted (the
+                library's launch counters say which kernel ran): the same bounds, and the two kernels agree within the sum of
+                their bounds.
 4 isolation     the gout rows of every hit of about 5 % of the faces (some at a wave edge, some at a block edge of the sorted order)
                 set to NaN or +Inf: every OTHER face with at most 1,024 hits is bit-equal to the run with those rows zeroed, the
                 poisoned faces are non-finite.
@@ -23,16 +24,12 @@ with u = 2^-24 and K = raster_bwd_cases.K:
 DEGENERATE and unasserted faces are in the inputs on purpose and carry hits; they are never compared with a bound, but their
 neighbours in the sorted order are.  Worst error / bound of an MI355X run: profiles/raster_bwd_tolerances.jsonl.
 """
-import os
-import subprocess
-import sys
-import tempfile
-
 import numpy as np
 import pytest
 import torch
 
 from tests import raster_bwd_cases as C
+from tests import raster_bwd_kernels as K
 from tests import raster_bwd_ref as R
 from tests import raster_scene as RS
 from tests.tol import check_bound
@@ -46,9 +43,10 @@ def _t(x, dev):
     return torch.from_numpy(np.array(x)).to(dev)                       # (a copy: the cases' arrays are read-only)
 
 
-def backward(dev, pix, fxy, feat, face, gout, eps):
+def backward(dev, pix, fxy, feat, face, gout, eps, unaligned=False):
     """deftet_sparse_render_bwd_f32 on numpy inputs with a leading batch axis -> (gxy [B,F,3,2], gfeat [B,F,3,D]) as numpy; the
-    outputs are filled with NaN before the call (the entry clears them)"""
+    outputs are filled with NaN before the call (the entry clears them).  unaligned: the features start 4 bytes off a 16-byte
+    boundary."""
     from deftet_amd import _lib
     lib = _lib.load()
     B, P, knum = face.shape
@@ -56,6 +54,9 @@ def backward(dev, pix, fxy, feat, face, gout, eps):
     assert pix.shape == (B, P, 2) and fxy.shape == (B, F, 3, 2) and feat.shape == (B, F, 3, D) and gout.shape == (B, P, knum, D)
     assert face.dtype == np.int64 and face.min() >= -1 and face.max() < F           # no index is out of range
     tp, txy, tff, tface, tg = (_t(x, dev) for x in (pix, fxy, feat, face, gout))
+    if unaligned:
+        tff = K.off_by_four_bytes(tff)
+    assert tff.data_ptr() % 16 == (4 if unaligned else 0) and tg.data_ptr() % 16 == 0
     assert tp.dtype == txy.dtype == tff.dtype == tg.dtype == torch.float32
     gxy = torch.full_like(txy, float("nan"))
     gff = torch.full_like(tff, float("nan"))
@@ -68,13 +69,13 @@ def backward(dev, pix, fxy, feat, face, gout, eps):
     return gxy.cpu().numpy(), gff.cpu().numpy()
 
 
-def run_case(dev, c, D=4, gout=None, shapes=None):
+def run_case(dev, c, D=4, gout=None, shapes=None, unaligned=False):
     """the backward on a case (or on `shapes`, cases of one structure as a batch) with its seeded features and gradients"""
     shapes = [c] if shapes is None else shapes
     feat = np.stack([C.features(s, D, seed=b) for b, s in enumerate(shapes)])
     g = np.stack([C.incoming(s, D, seed=b) for b, s in enumerate(shapes)]) if gout is None else gout
     out = backward(dev, np.stack([s["pix"] for s in shapes]), np.stack([s["fxy"] for s in shapes]), feat,
-                   np.stack([s["face"] for s in shapes]), g, c["eps"])
+                   np.stack([s["face"] for s in shapes]), g, c["eps"], unaligned=unaligned)
     return feat, g, out
 
 
@@ -116,7 +117,7 @@ def test_bound_run_time_width(cuda, band, flat, kind, knum, D):
     feat, g, (gxy, gfeat) = run_case(cuda, c, D=D, shapes=shapes)
     assert not np.array_equal(feat[0], feat[1]) and not np.array_equal(shapes[0]["fxy"], shapes[1]["fxy"])
     for b, s in enumerate(shapes):
-        hold("raster bwd pin, %s[%d], k_bwd_sorted<0> D=%d" % (c["name"], b, D), s, feat[b], g[b], gxy[b], gfeat[b])
+        hold("raster bwd pin, %s[%d], k_bwd_sorted D=%d" % (c["name"], b, D), s, feat[b], g[b], gxy[b], gfeat[b])
     _, _, (gxy2, gfeat2) = run_case(cuda, c, D=D, shapes=shapes)
     s = small_faces(c)
     assert np.array_equal(gxy[:, s], gxy2[:, s], equal_nan=True) and np.array_equal(gfeat[:, s], gfeat2[:, s], equal_nan=True)
@@ -126,37 +127,23 @@ def test_bound_run_time_width(cuda, band, flat, kind, knum, D):
 IMAGE_CASES = [x for x in C.CASES if x[0] == "image"]
 
 
-def child_main(path):
-    """(the child of test 3) the D = 4 image cases of test 1 in this process, saved to `path`"""
-    dev = torch.device("cuda:0")
-    out = {}
-    for i, x in enumerate(IMAGE_CASES):
-        _, _, (gxy, gfeat) = run_case(dev, C.case(*x))
-        out["gxy%d" % i], out["gfeat%d" % i] = gxy[0], gfeat[0]
-    np.savez(path, **out)
-
-
-def test_bound_and_agreement_of_the_sorted_kernel_in_a_child_process(cuda):
-    """DEFTET_RAST_BWD is read once per process: k_bwd_sorted<4> runs in one fresh child"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = "import sys; sys.path.insert(0, %r); from tests.test_raster_bwd_fp64_gpu import child_main; child_main(sys.argv[1])" % root
-    with tempfile.TemporaryDirectory() as d:
-        f = os.path.join(d, "sorted.npz")
-        r = subprocess.run(["timeout", "-k", "10", "240", sys.executable, "-c", code, f], env=dict(os.environ, DEFTET_RAST_BWD="sorted"),
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
-        child = dict(np.load(f))
-    assert len(child) == 2 * len(IMAGE_CASES) == 48
-    for i, x in enumerate(IMAGE_CASES):
+def test_bound_and_agreement_of_the_sorted_kernel_on_unaligned_features(cuda):
+    """D = 4 with features that are not 16-byte aligned goes to k_bwd_sorted: both kernels in this process, on the same inputs"""
+    ran = 0
+    for x in IMAGE_CASES:
         c = C.case(*x)
-        feat, g, (gxy, gfeat) = run_case(cuda, c)
-        sxy, sfeat = child["gxy%d" % i], child["gfeat%d" % i]
-        ref, _ = hold("raster bwd pin, %s, k_bwd_sorted<4>" % c["name"], c, feat[0], g[0], sxy, sfeat)
+        feat, g, (gxy, gfeat) = K.ran_only(b"k_bwd_runs", lambda: run_case(cuda, c))
+        sfeat_in, sg, (sxy, sfeat) = K.ran_only(b"k_bwd_sorted", lambda: run_case(cuda, c, unaligned=True))
+        assert np.array_equal(sfeat_in, feat) and np.array_equal(sg, g)
+        sxy, sfeat = sxy[0], sfeat[0]
+        tag = "raster bwd pin, %s, k_bwd_sorted, D=4 unaligned" % c["name"]
+        ref, _ = hold(tag, c, feat[0], g[0], sxy, sfeat)
         a = (c["asserted"] & (ref["n"] > 0))[:, None, None]
-        check_bound("raster bwd pin, %s, k_bwd_sorted<4> vs k_bwd_runs, gxy" % c["name"], sxy, gxy[0], 2 * R.bound_xy(ref, c["kappa"])[:, None, None], mask=a)
-        check_bound("raster bwd pin, %s, k_bwd_sorted<4> vs k_bwd_runs, gfeat" % c["name"], sfeat, gfeat[0], 2 * R.bound_feat(ref, c["kappa"])[:, None, None],
-                    mask=a)
+        check_bound(tag + " vs k_bwd_runs, gxy", sxy, gxy[0], 2 * R.bound_xy(ref, c["kappa"])[:, None, None], mask=a)
+        check_bound(tag + " vs k_bwd_runs, gfeat", sfeat, gfeat[0], 2 * R.bound_feat(ref, c["kappa"])[:, None, None], mask=a)
         assert not sxy[ref["n"] == 0].any() and not sfeat[ref["n"] == 0].any()
+        ran += 1
+    assert ran == len(IMAGE_CASES) == 24
 
 
 # ------------------------------------------------------------------------------------------------------------------------- 4

@@ -232,8 +232,8 @@ def test_backward_other_feature_widths_and_batches(cuda, oracle, D, B):
 @pytest.mark.parametrize("npix,knum", [(23, 3), (37, 5), (25, 1), (31, 64)])
 def test_backward_four_hits_per_lane_kernel_on_odd_sizes(cuda, oracle, npix, knum):
     """k_bwd_runs (D = 4: four consecutive sorted hits per lane): hit counts that are no multiple of four (the last lanes load one by
-    one), k = 1 (runs of one or two hits: heads, tails and whole runs inside a lane), against fp64 autograd and against the round-5
-    kernel (DEFTET_RAST_BWD=sorted is read once per process: the comparison runs in a child process)"""
+    one), k = 1 (runs of one or two hits: heads, tails and whole runs inside a lane), against fp64 autograd, and twice the same
+    bits (test_backward_kernels_agree_on_unaligned_features compares it with k_bwd_sorted)"""
     from deftet_amd.render import deftet_sparse_render
     fz, fxy, ff = projected_grid(6)
     pix, rngs = pixel_grid(npix)
@@ -258,45 +258,32 @@ def test_backward_four_hits_per_lane_kernel_on_odd_sizes(cuda, oracle, npix, knu
     assert torch.equal(gxy, gxy2) and torch.equal(gff, gff2)
 
 
-def test_backward_kernels_agree_in_a_child_process(cuda):
-    """DEFTET_RAST_BWD=sorted (the round-5 reduction, one hit per lane) and the default (k_bwd_runs) on the same inputs: the same
-    gradients up to the order of the fp32 additions"""
-    import os
-    import subprocess
-    import sys
-    import tempfile
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = (
-        "import sys, numpy as np, torch\n"
-        "sys.path.insert(0, %r)\n"
-        "from tests.test_raster_gpu import projected_grid, pixel_grid\n"
-        "from deftet_amd.render import deftet_sparse_render\n"
-        "dev = torch.device('cuda:0')\n"
-        "out = {}\n"
-        "for case, (res, npix, knum, zoom) in enumerate([(8, 61, 33, 0.6), (4, 97, 7, 0.5), (10, 40, 64, 0.25), (6, 128, 2, 0.7), (12, 50, 16, 0.9)]):\n"
-        "    fz, fxy, ff = projected_grid(res)\n"
-        "    pix, rngs = pixel_grid(npix)\n"
-        "    t = [torch.from_numpy(x).to(dev) for x in (pix * zoom, rngs, fz, fxy, ff)]\n"
-        "    t[3].requires_grad_(True); t[4].requires_grad_(True)\n"
-        "    feat, face = deftet_sparse_render(*t, knum=knum)\n"
-        "    go = torch.rand(feat.shape, device=dev, generator=torch.Generator(device=dev).manual_seed(case))\n"
-        "    g = torch.autograd.grad(feat, (t[3], t[4]), go)\n"
-        "    out['gxy%%d' %% case] = g[0].cpu().numpy(); out['gff%%d' %% case] = g[1].cpu().numpy()\n"
-        "np.savez(sys.argv[1], **out)\n" % root)
-    outs = []
-    with tempfile.TemporaryDirectory() as d:
-        for mode in ("sorted", "runs"):
-            f = os.path.join(d, mode + ".npz")
-            env = dict(os.environ, DEFTET_RAST_BWD=mode)
-            r = subprocess.run([sys.executable, "-c", code, f], env=env, capture_output=True, text=True, timeout=600)
-            assert r.returncode == 0, r.stdout + r.stderr
-            outs.append(dict(np.load(f)))
-    assert len(outs[0]) == 10
-    for k in sorted(outs[0]):                                           # five scenes (coarse / fine faces, k from 2 to 64, zoomed in and out)
-        a, b = outs[0][k], outs[1][k]
-        assert np.abs(b).max() > 0
-        assert np.abs(a - b).max() <= 2e-6 * np.abs(a).max(), (k, np.abs(a - b).max(), np.abs(a).max())
-        assert ((a == 0) == (b == 0)).all()                             # faces without hits: exactly zero in both
+def test_backward_kernels_agree_on_unaligned_features(cuda):
+    """k_bwd_sorted (one hit per lane; what D = 4 takes when face_features is not 16-byte aligned, a slice for instance) and
+    k_bwd_runs (the aligned case) on the same inputs: the same gradients up to the order of the fp32 additions"""
+    from deftet_amd.render import deftet_sparse_render
+    from tests import raster_bwd_kernels as K
+    # five scenes (coarse / fine faces, k from 2 to 64, zoomed in and out)
+    for case, (res, npix, knum, zoom) in enumerate([(8, 61, 33, 0.6), (4, 97, 7, 0.5), (10, 40, 64, 0.25), (6, 128, 2, 0.7), (12, 50, 16, 0.9)]):
+        fz, fxy, ff = projected_grid(res)
+        pix, rngs = pixel_grid(npix)
+        tp, tr, tz = (torch.from_numpy(x).to(cuda) for x in (pix * zoom, rngs, fz))
+        outs = []
+        for kernel in (b"k_bwd_sorted", b"k_bwd_runs"):
+            txy = torch.from_numpy(fxy).to(cuda).requires_grad_(True)
+            tff = torch.from_numpy(ff).to(cuda)
+            if kernel == b"k_bwd_sorted":                               # a leaf whose storage starts 4 bytes off: the operator does not copy it
+                tff = K.off_by_four_bytes(tff).detach()
+            tff.requires_grad_(True)
+            assert tff.is_leaf and tff.data_ptr() % 16 == (4 if kernel == b"k_bwd_sorted" else 0)
+            feat, face = deftet_sparse_render(tp, tr, tz, txy, tff, knum=knum)
+            go = torch.rand(feat.shape, device=cuda, generator=torch.Generator(device=cuda).manual_seed(case))
+            g = K.ran_only(kernel, lambda: torch.autograd.grad(feat, (txy, tff), go, retain_graph=True))
+            outs.append([x.cpu().numpy() for x in g])
+        for a, b in zip(*outs):                                         # gxy, gff
+            assert np.abs(b).max() > 0
+            assert np.abs(a - b).max() <= 2e-6 * np.abs(a).max(), (case, np.abs(a - b).max(), np.abs(a).max())
+            assert ((a == 0) == (b == 0)).all()                         # faces without hits: exactly zero in both
 
 
 def test_backward_face_with_thousands_of_hits(cuda, oracle):
