@@ -94,11 +94,18 @@ def make_surface_mesh(vertices, faces, resolution=100, smoothing_iterations=3, m
         return new_v * (omax - omin) + omin, new_f
 
 
-def mesh_to_sdf(verts, faces, points):
+def mesh_to_sdf(verts, faces, points, sign="parity"):
     """kaolin_mesh_to_sdf (dataloader.py:91-97): verts f32 [B,V,3], faces [F,3], points f32 [B,N,3] -> f32 [B,N] =
     (2 check_sign - 1) · point_to_mesh_distance, positive inside.  The reference's quirk is kept: the distance is the SQUARED one
-    (Kaolin's point_to_mesh_distance returns squared distances and the reference does not take the root)."""
+    (Kaolin's point_to_mesh_distance returns squared distances and the reference does not take the root).
+    sign="winding" takes the sign from the generalised winding number (w > 0.5) instead of ray parity: for meshes that are not
+    watertight."""
+    if sign not in ("parity", "winding"):
+        raise ValueError("mesh_to_sdf: sign %r is not 'parity' or 'winding'" % (sign,))
     with torch.no_grad():
-        sign = hip_ops.check_sign(verts, faces, points)
+        if sign == "winding":
+            sign = hip_ops.winding_inside(hip_ops.winding_number(verts, faces, points))
+        else:
+            sign = hip_ops.check_sign(verts, faces, points)
         distance, _, _ = metrics.point_to_mesh_distance(points, metrics.index_vertices_by_faces(verts, faces))
         return (sign.float() * 2.0 - 1.0) * distance

@@ -1226,6 +1226,87 @@ def check_sign_ragged(verts_list, faces_list, points_bxnx3, brute=False, return_
     return (inside, cnt) if return_count else inside
 
 
+# --------------------------------------------------------------------------------- generalised winding number
+WINDING_ALGOS = {"auto": 0, "exact": 1, "fast": 2, "fast_unsorted": 3}
+
+
+def _winding_call(name, v, v_off, f, f_off, p, B, V, ftot, fmax, algo, beta, check):
+    lib = _lib.load()
+    if algo not in WINDING_ALGOS:
+        raise ValueError("%s: algo %r is not one of %s" % (name, algo, sorted(WINDING_ALGOS)))
+    beta = 0.0 if beta is None else float(beta)
+    if beta != 0.0 and not (1.0 <= beta <= 1e6):
+        raise ValueError("%s: beta=%r: None (the default) or a value in [1, 1e6] expected" % (name, beta))
+    N, dev, a = p.shape[1], p.device, WINDING_ALGOS[algo]
+    out = torch.empty(B, N, device=dev, dtype=torch.float32)
+    bad = torch.zeros(4, device=dev, dtype=torch.int32)
+    with _lib.on_device(dev):
+        ws = _lib.workspace(dev, lib.deftet_winding_number_workspace_bytes(B, ftot, fmax, N, a))
+        _lib.check(lib.deftet_winding_number_f32(_lib.ptr(v), _lib.ptr(v_off), _lib.ptr(f), _lib.ptr(f_off), _lib.ptr(p), _lib.ptr(out),
+                                                 _lib.ptr(bad), B, V, ftot, fmax, N, a, beta, _lib.ptr(ws), ws.numel(),
+                                                 _lib.current_stream(dev)), "deftet_winding_number_f32")
+    if check:
+        n_idx, n_corner, n_point = bad[:3].tolist()
+        if n_idx:
+            raise IndexError("%s: %d faces with a vertex index outside their mesh" % (name, n_idx))
+        if n_corner or n_point:
+            raise ValueError("%s: non-finite input (%d faces with such a corner, %d such points)" % (name, n_corner, n_point))
+    return out
+
+
+def winding_number(verts_bxvx3, faces_fx3, points_bxnx3, algo="auto", beta=None, check=True):
+    """f32 [B,N]: the generalised winding number (Jacobson et al. 2013) of the mesh about every point — the sum over the faces of
+    the signed solid angle over 4 pi.  An integer on a closed, consistently oriented mesh (1 inside an outward oriented surface,
+    -1 inside a flipped one, 2 inside two nested ones), smooth across holes; see winding_inside for the two ways to read it.
+    verts f32 [B,V,3], faces int [F,3] shared by the batch, points f32 [B,N,3].
+
+    algo: "exact" tests every point against every face; "fast" walks an octree of the faces and takes clusters farther than `beta`
+    radii as dipoles (beta None = 3: within 0.05 of the exact value); "auto" picks by the face count.  A point's
+    value does not depend on the other points of the call and is the same bits on every run.
+    check=True raises IndexError for a face index outside [0,V) and ValueError for non-finite vertices of faces or points (one
+    read-back); with check=False the points of such a mesh, and such points, are NaN.
+    There is no backward: the result is a label, and the tensors it comes from are not tracked."""
+    _lib.require_gpu(verts_bxvx3, faces_fx3, points_bxnx3)
+    v, p = _f32c(verts_bxvx3.detach()), _f32c(points_bxnx3.detach())
+    f = faces_fx3.long().contiguous()
+    if v.dim() != 3 or p.dim() != 3 or f.dim() != 2 or f.shape[1] != 3 or v.shape[0] != p.shape[0] or v.shape[2] != 3 or p.shape[2] != 3:
+        raise RuntimeError("winding_number: verts [B,V,3], faces [F,3], points [B,N,3] expected")
+    B, V, F = v.shape[0], v.shape[1], f.shape[0]
+    return _winding_call("winding_number", v, None, f, None, p, B, V, B * F, F, algo, beta, check)
+
+
+def winding_number_ragged(verts_list, faces_list, points_bxnx3, algo="auto", beta=None, check=True):
+    """winding_number for a different mesh per shape in one launch sequence: verts_list[b] f32 [V_b,3] (or [1,V_b,3]), faces_list[b]
+    int [F_b,3] with indices local to mesh b, points f32 [B,N,3] -> f32 [B,N].  Every shape gets the tree its own face count asks
+    for, so a shape's values are those of its single call, bit for bit ("auto" is resolved once, by the largest mesh).  No backward."""
+    _lib.require_gpu(points_bxnx3, *verts_list, *faces_list)
+    p = _f32c(points_bxnx3.detach())
+    if p.dim() != 3 or p.shape[2] != 3:
+        raise RuntimeError("winding_number_ragged: points [B,N,3] expected")
+    B, dev = p.shape[0], p.device
+    if len(verts_list) != B or len(faces_list) != B:
+        raise RuntimeError("winding_number_ragged: one mesh per shape expected")
+    vs = [_f32c(v.detach()).reshape(-1, 3) for v in verts_list]
+    fs = [f.long().reshape(-1, 3) for f in faces_list]
+    f_cnt = [f.shape[0] for f in fs]
+    offs = host_ints([0] + list(np.cumsum([v.shape[0] for v in vs])) + [0] + list(np.cumsum(f_cnt)), dev, i32=True)
+    v_off, f_off = offs[:B + 1], offs[B + 1:]
+    v_cat, f_cat = torch.cat(vs, 0).contiguous(), torch.cat(fs, 0).contiguous()
+    return _winding_call("winding_number_ragged", v_cat, v_off, f_cat, f_off, p, B, 0, int(sum(f_cnt)), int(max(f_cnt) if f_cnt else 0),
+                         algo, beta, check)
+
+
+def winding_inside(w, rule="positive"):
+    """bool, same shape as w: the inside label of a winding number.  "positive": w > 0.5 (Jacobson et al.: the majority reading, for
+    open, nested and self-intersecting meshes).  "parity": round(|w|) is odd — what ray parity answers on a watertight mesh (inside
+    two nested surfaces of the same orientation is outside)."""
+    if rule == "positive":
+        return w > 0.5
+    if rule == "parity":
+        return torch.round(torch.abs(w)).to(torch.int64) % 2 == 1
+    raise ValueError("winding_inside: rule %r is not 'positive' or 'parity'" % (rule,))
+
+
 # --------------------------------------------------------------------------------- N3 render-side rebuilds
 def _i64_tets(tet_tx4):
     t = tet_tx4 if tet_tx4.dtype == torch.int64 else tet_tx4.long()

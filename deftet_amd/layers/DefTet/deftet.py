@@ -176,7 +176,11 @@ class DefTet(nn.Module):
         return _topology_for(tetrahedron_bxfx4, vertice_pos.shape[1]).gather(vertice_pos)
 
     # --- N1: GT occupancy of the tet centroids (deftet.py:33-49)
-    def check_tet_inside_sdfs(self, tet_bxfx4x3, mesh_list):
+    def check_tet_inside_sdfs(self, tet_bxfx4x3, mesh_list, method="parity"):
+        """method="parity" (the reference's): +x ray parity, meaningful on watertight meshes only.  method="winding": the centroids
+        are labelled by their generalised winding number (w > 0.5), which also reads open, nested and self-intersecting meshes."""
+        if method not in ("parity", "winding"):
+            raise ValueError("check_tet_inside_sdfs: method %r is not 'parity' or 'winding'" % (method,))
         verts, faces = mesh_list[0], mesh_list[1]
         with torch.no_grad():
             center = torch.mean(tet_bxfx4x3, dim=2)                     # [B,T,3], same reduction as per shape
@@ -186,8 +190,13 @@ class DefTet(nn.Module):
             if same_mesh and len(verts) == tet_bxfx4x3.shape[0]:
                 # one launch sequence for the whole batch (faces shared, per-shape vertices)
                 v = torch.cat([x.reshape(1, -1, 3) for x in verts], dim=0)
+                if method == "winding":
+                    return hip_ops.winding_inside(hip_ops.winding_number(v, faces[0][0], center, check=False)).unsqueeze(-1).float()
                 return hip_ops.check_sign(v, faces[0][0], center, check=False).unsqueeze(-1).float()
             # a different ground-truth mesh per shape (the reference loops over the batch): one ragged call
+            if method == "winding":
+                w = hip_ops.winding_number_ragged(list(verts), [f[0] for f in faces], center, check=False)
+                return hip_ops.winding_inside(w).unsqueeze(-1).float()
             return hip_ops.check_sign_ragged(list(verts), [f[0] for f in faces], center).unsqueeze(-1).float()
 
     # --- A7

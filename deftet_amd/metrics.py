@@ -155,7 +155,7 @@ def metric_block(surface_points, pred_points, dist_a=None, dist_b=None, radius=0
 
 
 def surface_metrics(pred_faces, pred_n_face, gt_faces, gt_n_face, surface_points, num_samples=100000, uniforms=None, generator=None,
-                    radius=0.01, pred_verts=None, pred_faces_idx=None, sdf_points=None, gt_occ=None):
+                    radius=0.01, pred_verts=None, pred_faces_idx=None, sdf_points=None, gt_occ=None, inside_test="parity"):
     """eval.py's metric block for a batch of shapes, with no host synchronisation.
 
     pred_faces f32 [B,Fp,3,3] / gt_faces f32 [B,Fg,3,3]: padded face vertices, pred_n_face / gt_n_face int32 [B] their counts;
@@ -163,9 +163,13 @@ def surface_metrics(pred_faces, pred_n_face, gt_faces, gt_n_face, surface_points
     from `uniforms` f32 [B,N,3] or torch.rand with `generator`), both sided distances are taken once each, both point-to-mesh
     queries are run, and one fused reduction gives f32 [B] tensors keyed chamfer, chamfer_l1, f_score, mean_hausdorff,
     max_hausdorff.  With pred_verts / pred_faces_idx (lists of [V_b,3] / [F_b,3] per shape), sdf_points [B,Q,3] and gt_occ [B,Q],
-    also iou (check_sign of the predicted mesh against gt_occ > 0, as eval.py's point_cloud_iou at thresh 0.5).
+    also iou (check_sign of the predicted mesh against gt_occ > 0, as eval.py's point_cloud_iou at thresh 0.5; with
+    inside_test="winding" the generalised winding number, w > 0.5, labels the points instead of ray parity: for predicted meshes
+    that are not watertight).
     A shape with nothing to sample gets NaN metrics."""
     _lib.require_gpu(pred_faces, gt_faces, surface_points, uniforms, sdf_points, gt_occ)
+    if inside_test not in ("parity", "winding"):
+        raise ValueError("surface_metrics: inside_test %r is not 'parity' or 'winding'" % (inside_test,))
     _no_grad(pred_faces, gt_faces, surface_points)
     B, dev = pred_faces.shape[0], pred_faces.device
     if uniforms is None:
@@ -180,7 +184,10 @@ def surface_metrics(pred_faces, pred_n_face, gt_faces, gt_n_face, surface_points
     out = metric_block(s, pred_pts, da, db, radius)
     res = {"chamfer": out[:, 0], "chamfer_l1": out[:, 1], "f_score": out[:, 2], "mean_hausdorff": out[:, 3], "max_hausdorff": out[:, 4]}
     if sdf_points is not None:
-        inside = hip_ops.check_sign_ragged(pred_verts, pred_faces_idx, sdf_points)
+        if inside_test == "winding":
+            inside = hip_ops.winding_inside(hip_ops.winding_number_ragged(pred_verts, pred_faces_idx, sdf_points, check=False))
+        else:
+            inside = hip_ops.check_sign_ragged(pred_verts, pred_faces_idx, sdf_points)
         a, g = inside.float(), (gt_occ > 0.0).float()
         res["iou"] = (a * g).sum(-1) / (a + g).clamp(0, 1).sum(-1)
     return res

@@ -42,7 +42,9 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
-/* 360: pixel-aligned image-feature sampling for the single-image branch — deftet_image_sample_fwd_f32, deftet_image_cells_f32,
+/* 370: generalised winding numbers for inside tests on open meshes — deftet_winding_number_f32, its workspace size,
+ *      deftet_winding_number_levels, deftet_winding_number_resolve_algo (winding_number.hip).
+ * 360: pixel-aligned image-feature sampling for the single-image branch — deftet_image_sample_fwd_f32, deftet_image_cells_f32,
  *      deftet_image_sample_bwd_map_f32 / _bwd_uv_f32 / _bwd_global_f32 and their workspace size (image_sample.hip).
  * 350: connected components of the inside tets and the occupancy clean-up on them — deftet_tet_components_u8,
  *      deftet_occupancy_cleanup_u8 and their workspace size (tet_components.hip).
@@ -437,6 +439,37 @@ int deftet_check_sign_ragged_f32(const float *verts_cat, const int32_t *vert_off
                                  int32_t *count, int32_t *bad_flag, int n_batch, long long n_face_total,
                                  int n_face_max, int n_point, int algo,
                                  void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * Generalised winding number (Jacobson et al. 2013): the sum over the faces of the signed solid
+ * angle 2 atan2(det(a,b,c), |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|) over 4 pi, a, b, c the corners minus the point.
+ * An integer on a closed, consistently oriented mesh, smooth across holes: the inside test where ray parity is noise.
+ *
+ * One entry point for both batch forms.  Uniform (vert_offsets == face_offsets == NULL): verts f32 [B,n_vertex,3], faces
+ * int64 [n_face_max,3] shared by the batch, n_face_total = B * n_face_max.  Ragged: verts f32 [sum V_b,3] and faces int64
+ * [sum F_b,3] (indices local to their shape) back to back, vert_offsets / face_offsets int32 [B+1] (device) their row
+ * offsets, n_face_total = sum F_b, n_face_max = max F_b, n_vertex ignored.  points f32 [B,N,3]; winding f32 [B,N].
+ * bad_counts (device int32 [4], cleared here): [0] faces with an index outside their mesh, [1] faces with a non-finite
+ * corner, [2] non-finite points.  Such faces are never read: every value of their SHAPE is NaN; a non-finite point gets NaN.
+ * A mesh without faces gives 0.
+ * algo: DEFTET_WN_EXACT = every point against every face in face order; DEFTET_WN_FAST = a centroid octree of depth
+ * deftet_winding_number_levels(F_b) per shape, walked by the wave, a node farther than beta radii taken as a dipole, the
+ * points sorted by leaf first; DEFTET_WN_FAST_UNSORTED = the same without that sort (same bits; 5-7x slower on incoherent points); DEFTET_WN_AUTO =
+ * what deftet_winding_number_resolve_algo(AUTO, n_face_max, n_batch * n_point) returns.  beta: 0 = the default (3), else in [1, 1e6]; the
+ * exact path ignores it.  No float atomics; a point's value does not depend on the other points of the call and is the same
+ * bits on every run.  n_batch <= 65535.
+ * --------------------------------------------------------------------------------- */
+#define DEFTET_WN_AUTO 0
+#define DEFTET_WN_EXACT 1
+#define DEFTET_WN_FAST 2
+#define DEFTET_WN_FAST_UNSORTED 3
+int deftet_winding_number_levels(int n_face);
+int deftet_winding_number_resolve_algo(int algo, int n_face_max, long long n_point_total);
+size_t deftet_winding_number_workspace_bytes(int n_batch, long long n_face_total, int n_face_max, int n_point, int algo);
+int deftet_winding_number_f32(const float *verts, const int32_t *vert_offsets, const int64_t *faces, const int32_t *face_offsets,
+                              const float *points, float *winding, int32_t *bad_counts, int n_batch, int n_vertex,
+                              long long n_face_total, int n_face_max, int n_point, int algo, float beta, void *workspace,
+                              size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------
  * N3  render-side geometry rebuilds of diff_render/diftet_6_subdiv/3_model/
