@@ -11,13 +11,19 @@ def default_frame(vertices, dtype=np.float32):
     return mn, (mx - mn).max(axis=1)
 
 
-def _axis_margins(a, e, h, xp_abs=np.abs):
-    """a [3 corners, 3, n] relative to the voxel centres, e [3 edges, 3] -> list of (separation, axis length) per axis; the voxel
-    and the triangle are separated on an axis iff its separation is > 0.  Every product and sum is one rounded operation."""
+def _box_axes(a, h):
+    """the three box axes of _axis_margins"""
     out = []
     for c in range(3):
         mn, mx = np.minimum(np.minimum(a[0, c], a[1, c]), a[2, c]), np.maximum(np.maximum(a[0, c], a[1, c]), a[2, c])
         out.append((np.maximum(mn - h, -h - mx), a.dtype.type(1)))
+    return out
+
+
+def _axis_margins(a, e, h, xp_abs=np.abs):
+    """a [3 corners, 3, n] relative to the voxel centres, e [3 edges, 3] -> list of (separation, axis length) per axis; the voxel
+    and the triangle are separated on an axis iff its separation is > 0.  Every product and sum is one rounded operation."""
+    out = _box_axes(a, h)
     nx, ny, nz = e[0, 1] * e[1, 2] - e[0, 2] * e[1, 1], e[0, 2] * e[1, 0] - e[0, 0] * e[1, 2], e[0, 0] * e[1, 1] - e[0, 1] * e[1, 0]
     d = (nx * a[0, 0] + ny * a[0, 1]) + nz * a[0, 2]
     out.append((np.abs(d) - h * ((abs(nx) + abs(ny)) + abs(nz)), np.sqrt(nx * nx + ny * ny + nz * nz)))
@@ -80,15 +86,109 @@ def _voxelize(vertices, faces, R, origin, scale, dtype, want_margin):
     return (vox, near) if want_margin else vox
 
 
-def mesh_voxelize_f32(vertices, faces, R, origin=None, scale=None):
-    """uint8 [B,R,R,R]: the rule evaluated in fp32 in the stated operation order"""
-    return _voxelize(vertices, faces, R, origin, scale, np.float32, None)
+def _frame(v, origin, scale, dtype):
+    if origin is None or scale is None:
+        o0, s0 = default_frame(v, np.float32)
+        origin = o0 if origin is None else origin
+        scale = s0 if scale is None else scale
+    return np.asarray(origin, np.float32).astype(dtype), np.asarray(scale, np.float32).astype(dtype)
 
 
-def mesh_voxelize_f64(vertices, faces, R, origin=None, scale=None, margin=1e-4):
+def _candidate_boxes(q, faces, n_vertex, R, ring):
+    """q [V,3] in voxel units, faces int64 [F,3] -> (corners [F,3 corners,3], lo, hi int64 [F,3] inclusive, ok bool [F]): the
+    candidate rule of include/deftet_hip.h for every triangle at once (`ring`: one more voxel on every side, as the fp64 margin
+    pass looks); ok is False for a face index outside [0,V), a non-finite corner and an empty box"""
+    valid = ((faces >= 0) & (faces < n_vertex)).all(axis=1)
+    qf = q[np.where(valid[:, None], faces, 0)]
+    ok = valid & np.isfinite(qf).all(axis=(1, 2))
+    qf = np.where(ok[:, None, None], qf, q.dtype.type(0))
+    lo = np.maximum(np.ceil(np.clip(qf.min(axis=1), -1, R + 1)).astype(np.int64) - 1, 0)
+    hi = np.minimum(np.floor(np.clip(qf.max(axis=1), -1, R + 1)).astype(np.int64), R - 1)
+    if ring:
+        lo, hi = np.maximum(lo - 1, 0), np.minimum(hi + 1, R - 1)
+    return qf, lo, hi, ok & (lo <= hi).all(axis=1)
+
+
+def _voxelize_flat(vertices, faces, R, origin, scale, dtype, want_margin, chunk=1 << 19):
+    """_voxelize without the loop over the triangles: the same rule, the same operations in the same order, over flat
+    (triangle, voxel) pairs, `chunk` of them at a time.  Pinned bit for bit to the loop in test_dataprep_cases_cpu.py."""
+    v = np.asarray(vertices, np.float32)
+    faces = np.asarray(faces, np.int64).reshape(-1, 3)
+    B = v.shape[0]
+    origin, scale = _frame(v, origin, scale, dtype)
+    vox = np.zeros((B, R, R, R), np.uint8)
+    near = np.zeros((B, R, R, R), bool) if want_margin else None
+    h, Rt = dtype(0.5), dtype(R)
+    with np.errstate(all="ignore"):
+        for b in range(B):
+            q_all = ((v[b].astype(dtype) - origin[b][None, :]) / scale[b]) * Rt
+            qf, lo, hi, ok = _candidate_boxes(q_all, faces, v.shape[1], R, bool(want_margin))
+            ext = np.where(ok[:, None], hi - lo + 1, 0)
+            sel = np.flatnonzero(ext.prod(axis=1))
+            ends = np.cumsum(ext[sel].prod(axis=1))
+            first = 0
+            while first < sel.shape[0]:
+                done = ends[first - 1] if first else 0
+                last = max(int(np.searchsorted(ends, done + chunk, side="right")), first + 1)
+                fs = sel[first:last]
+                first = last
+                n_f = ext[fs].prod(axis=1)
+                own = np.repeat(np.arange(fs.shape[0]), n_f)            # the pair's triangle, and its place in that triangle's box
+                local = np.arange(int(n_f.sum())) - np.repeat(np.cumsum(n_f) - n_f, n_f)
+                ny, nz = ext[fs, 1][own], ext[fs, 2][own]
+                idx = np.stack([lo[fs, 0][own] + local // (ny * nz), lo[fs, 1][own] + (local // nz) % ny, lo[fs, 2][own] + local % nz])
+                qt = qf[fs]                                             # [m, 3 corners, 3]
+                centre = idx.astype(dtype) + h
+                a = np.moveaxis(qt, 0, -1)[:, :, own] - centre[None, :, :]
+                # a pair that a box axis separates by the margin or more (fp32: at all) is neither set nor near, whatever the
+                # ten other axes say: most of the candidate box, and nearly all of its ring
+                cut = np.zeros(idx.shape[1], bool)
+                for s, _ in _box_axes(a, h):
+                    cut |= (s >= want_margin) if want_margin else (s > 0)
+                keep = np.flatnonzero(~cut)
+                idx, a, own = idx[:, keep], a[:, :, keep], own[keep]
+                e = np.moveaxis(np.stack([qt[:, 1] - qt[:, 0], qt[:, 2] - qt[:, 1], qt[:, 0] - qt[:, 2]]), 1, -1)[:, :, own]
+                axes = _axis_margins(a, e, h)
+                sep = np.zeros(idx.shape[1], bool)
+                for s, _ in axes:
+                    sep |= s > 0
+                hit = ~sep
+                vox[b, idx[0][hit], idx[1][hit], idx[2][hit]] = 1
+                if want_margin:
+                    worst = np.full(idx.shape[1], -np.inf)
+                    for s, length in axes:
+                        worst = np.where(length > 0, np.maximum(worst, s / length), worst)
+                    close = np.abs(worst) < want_margin
+                    near[b, idx[0][close], idx[1][close], idx[2][close]] = True
+    return (vox, near) if want_margin else vox
+
+
+def mesh_voxelize_f32(vertices, faces, R, origin=None, scale=None, flat=False):
+    """uint8 [B,R,R,R]: the rule evaluated in fp32 in the stated operation order (`flat`: by the vectorised evaluator)"""
+    return (_voxelize_flat if flat else _voxelize)(vertices, faces, R, origin, scale, np.float32, None)
+
+
+def mesh_voxelize_f64(vertices, faces, R, origin=None, scale=None, margin=1e-4, flat=False):
     """(uint8 [B,R,R,R], bool [B,R,R,R]) in fp64; the second grid marks the voxels with a (triangle, voxel) decision whose smallest
     separating margin, in voxel units, is below `margin` — where an fp32 evaluation may decide the other way"""
-    return _voxelize(vertices, faces, R, origin, scale, np.float64, margin)
+    return (_voxelize_flat if flat else _voxelize)(vertices, faces, R, origin, scale, np.float64, margin)
+
+
+def voxelize_tasks(vertices, faces, R, origin=None, scale=None, budget=256):
+    """int64 [B,F]: the wave tasks of every triangle (include/deftet_hip.h): its candidate box in fp32 has (i extent) (j extent)
+    (words of k it touches) word columns, a task is `budget` (DEFTET_VOXELIZE_UNIT_BUDGET) of them; a triangle with a bad index,
+    a non-finite corner or an empty box has none.  stats = (tasks.sum(), (tasks > 1).sum(), 0, 0) when no index is bad."""
+    v = np.asarray(vertices, np.float32)
+    faces = np.asarray(faces, np.int64).reshape(-1, 3)
+    origin, scale = _frame(v, origin, scale, np.float32)
+    out = np.zeros((v.shape[0], faces.shape[0]), np.int64)
+    with np.errstate(all="ignore"):
+        for b in range(v.shape[0]):
+            q_all = ((v[b] - origin[b][None, :]) / scale[b]) * np.float32(R)
+            _, lo, hi, ok = _candidate_boxes(q_all, faces, v.shape[1], R, False)
+            units = (hi[:, 0] - lo[:, 0] + 1) * (hi[:, 1] - lo[:, 1] + 1) * ((hi[:, 2] >> 5) - (lo[:, 2] >> 5) + 1)
+            out[b] = np.where(ok, (units + budget - 1) // budget, 0)
+    return out
 
 
 # ---------------------------------------------------------------------------- depth maps
