@@ -35,9 +35,11 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # k_finalize 64 -> 53 (29.4 -> 28.0), the traversal 62.7 -> 61.5; the packed FMAs the traversal loop WANTS are written as vector
 # types and stay.  reduce.hip is the opposite case (k_rowdot_fused 16.9 -> 20.7 us without the packing), so the flag is per file.
 # DEFTET_BUILD_NOSLP=a.hip,b.hip adds files for an experiment.
-# (surface_ops.hip: k_tri_query_coop 0.632 -> 0.616 ms, geometry step 2.49 -> 2.465; raster.hip: slower without, 2.415 -> 2.44 ms;
-# tet_ops / check_sign / vertex_ops: no difference — tools/probes/r05_noslp.sh)
-PER_FILE_FLAGS = {"point_in_tet.hip": ["-fno-slp-vectorize"], "surface_ops.hip": ["-fno-slp-vectorize"]}
+# (tri_distance.hip: k_tri_query_coop 0.632 -> 0.616 ms, geometry step 2.49 -> 2.465 — measured when it was one source with
+# nearest_neighbor.hip, chamfer.hip and face_adjacency.hip, whose kernels were compiled with the flag ever since and keep it;
+# raster.hip: slower without, 2.415 -> 2.44 ms; tet_ops / check_sign / vertex_ops: no difference — tools/probes/r05_noslp.sh)
+_NOSLP = ("point_in_tet.hip", "tri_distance.hip", "nearest_neighbor.hip", "chamfer.hip", "face_adjacency.hip")
+PER_FILE_FLAGS = {f: ["-fno-slp-vectorize"] for f in _NOSLP}
 
 
 def _file_flags(src):

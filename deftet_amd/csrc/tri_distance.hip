@@ -1,1092 +1,15 @@
-// surface_ops.hip — the per-shape surface operators layers.DefTet.forward calls
-//  for CDNA4 / gfx950.
-//
-//   A8  deftet_face_edge_adj_f32   layers/DefTet/tet_face_adj_m_idx/tet_face_adj_m_for.cu:15-130
-//   A9  deftet_tri_dist_fwd/bwd    layers/DefTet/tet_analytic_distance_batch/tet_analytic_distance_for.cu:15-334
+// tri_distance.hip — the point-to-triangle distance layers.DefTet.forward calls per shape for
+// CDNA4 / gfx950; what it shares with the other surface operators is in surface_batch.hpp.
+//   A9  deftet_tri_dist_fwd/bwd   layers/DefTet/tet_analytic_distance_batch/tet_analytic_distance_for.cu:15-334
 //                                  layers/DefTet/tet_analytic_distance_batch/tet_analytic_distance_back.cu:15-715
-//   A10 deftet_nn_index_f32        layers/nearest_neighbor/nearest_neighbor_cuda.cu:15-80
-//
-// All three reference kernels are "one thread per query, loop over every primitive from
-// global memory".  Here the primitive stream is wave-uniform: it is read once per wave through
-// the scalar cache (s_load) and broadcast as SGPR operands, one query per lane, so the vector
-// memory pipe only carries the queries and the results.  The arithmetic follows the reference
-// operation by operation in fp32 with FMA contraction off (the argmin / neighbour indices
-// are decided by exact fp32 comparisons), double-typed literals promoted as C++ does.
 #pragma clang fp contract(off)
-#include <cstring>
-
 #include "common.hpp"
-
 #include "grid_setup.hpp"
 #include "prims.hpp"
+#include "surface_batch.hpp"
 
 namespace deftet {
 namespace surf {
-
-// ---------------------------------------------------------------------------- A10 nearest neighbour
-// result = index of the first point with the strictly smallest ((dx*dx + dy*dy) + dz*dz)
-__global__ __launch_bounds__(256) void k_nn(const float *__restrict__ queries, const float *__restrict__ points, int N,
-                                            int M, int *result)
-{
-    const int b = blockIdx.y;
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = q < N;
-    const float *qq = queries + ((size_t)b * N + (live ? q : 0)) * 3;
-    const float qx = qq[0], qy = qq[1], qz = qq[2];
-    const float *__restrict__ pp = points + (size_t)b * M * 3;      // wave-uniform stream -> s_load
-    float best = 1e20f;                                             // nearest_neighbor_cuda.cu:28
-    int besti = 0;
-    int i = 0;
-    for (; i + 4 <= M; i += 4) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float dx = pp[(i + k) * 3] - qx, dy = pp[(i + k) * 3 + 1] - qy, dz = pp[(i + k) * 3 + 2] - qz;
-            float d = 0.f;
-            d += dx * dx;                                           // :42
-            d += dy * dy;                                           // :44
-            d += dz * dz;                                           // :46
-            if (d < best) { best = d; besti = i + k; }              // :48-51
-        }
-    }
-    for (; i < M; ++i) {
-        const float dx = pp[i * 3] - qx, dy = pp[i * 3 + 1] - qy, dz = pp[i * 3 + 2] - qz;
-        float d = 0.f;
-        d += dx * dx;
-        d += dy * dy;
-        d += dz * dz;
-        if (d < best) { best = d; besti = i; }
-    }
-    if (live) result[(size_t)b * N + q] = besti;
-}
-
-// --- batching across shapes ----------------------------------------------------------------------------
-// The grid-accelerated operators keep every per-shape scratch array in a workspace SLICE of `slice` bytes; slice s starts
-// s * slice bytes after slice 0.  A batched launch covers kBatchShapes shapes with its y (or z) grid dimension: the
-// kernels get the pointers of slice 0 and rebase them with SHAPE(ptr), their inputs / outputs with their own strides.
-// The per-shape element counts travel by value.  (One launch sequence for a batch instead of one per shape: at ~40
-// launches per shape and operator the command processor was what bounded a training step's surface terms.)
-constexpr int kBatchShapes = 8;
-struct ShapeCounts { int n[kBatchShapes]; };
-#define SHAPE(ptr) (ptr) = reinterpret_cast<decltype(ptr)>(reinterpret_cast<uintptr_t>(ptr) + (size_t)sb * slice)
-
-// exclusive prefix sums of n ints per shape, one launch: workgroup (j, shape) scans tile j (kScanThreads * kScanPer
-// elements) after adding up everything before its tile itself — the arrays are a few hundred thousand ints, so the
-// redundant reads (L2 hits) cost less than a carry chain through one workgroup (94 us per call in round 2) or a second
-// launch.  out[n] receives the total when with_total.
-constexpr int kScanThreads = 1024, kScanPer = 16, kScanTile = kScanThreads * kScanPer;
-static inline unsigned scan_tiles(long long n) { return (unsigned)((n + kScanTile - 1) / kScanTile > 0 ? (n + kScanTile - 1) / kScanTile : 1); }
-__global__ __launch_bounds__(kScanThreads) void k_scan_excl(const int *in, int *out, int n, size_t slice, int with_total)
-{
-    __shared__ int wsum[kScanThreads / 64];
-    const int sb = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    SHAPE(in); SHAPE(out);
-    const int base = blockIdx.x * kScanTile;
-    // carry: the sum of in[0, base) (base is a multiple of the tile, the arrays are 256-byte aligned)
-    int carry = 0;
-    for (int i = tid * 4; i < base; i += kScanThreads * 4) {
-        const int4 q = *reinterpret_cast<const int4 *>(in + i);
-        carry += (q.x + q.y) + (q.z + q.w);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) carry += __shfl_xor(carry, off);
-    if (lane == 0) wsum[w] = carry;
-    __syncthreads();
-    carry = 0;
-#pragma unroll
-    for (int k = 0; k < kScanThreads / 64; ++k) carry += wsum[k];
-    __syncthreads();
-    int v[kScanPer], sum = 0;
-    const int i0 = base + tid * kScanPer;
-    if (i0 + kScanPer <= n) {                                       // 16-byte loads
-#pragma unroll
-        for (int k = 0; k < kScanPer; k += 4) {
-            const int4 q = *reinterpret_cast<const int4 *>(in + i0 + k);
-            v[k] = q.x; v[k + 1] = q.y; v[k + 2] = q.z; v[k + 3] = q.w;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kScanPer; ++k) v[k] = i0 + k < n ? in[i0 + k] : 0;
-    }
-#pragma unroll
-    for (int k = 0; k < kScanPer; ++k) sum += v[k];
-    int incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    int run = carry + incl - sum, tot = 0;
-#pragma unroll
-    for (int k = 0; k < kScanThreads / 64; ++k) { if (k < w) run += wsum[k]; tot += wsum[k]; }
-    if (i0 + kScanPer <= n) {
-#pragma unroll
-        for (int k = 0; k < kScanPer; k += 4) {
-            int4 q;
-            q.x = run; q.y = q.x + v[k]; q.z = q.y + v[k + 1]; q.w = q.z + v[k + 2];
-            run = q.w + v[k + 3];
-            *reinterpret_cast<int4 *>(out + i0 + k) = q;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < kScanPer; ++k) { if (i0 + k < n) out[i0 + k] = run; run += v[k]; }
-    }
-    if (with_total && tid == 0 && blockIdx.x == gridDim.x - 1) out[n] = carry + tot;
-}
-
-// rank = atomicAdd(&counter[key], 1) for every lane with key >= 0, with ONE atomic per run of consecutive lanes that share
-// a key: point clouds sampled face by face put ~20 consecutive points into the same cell, and returning atomics on a
-// handful of addresses were what the binning kernels spent their time on (k_tri_point_keys 76 us, k_nn_bin 42 us per
-// 8 x 97 k points).  Must be called by all lanes of the wave (key < 0: no count).
-__device__ __forceinline__ int run_atomic_rank(int *counter, int key)
-{
-    const int lane = threadIdx.x & 63;
-    const int prev = __shfl_up(key, 1);
-    const bool head = key >= 0 && (lane == 0 || prev != key);
-    const unsigned long long heads = __ballot(head || key < 0);     // a lane without a key also ends the run before it
-    const unsigned long long upto = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);   // lanes 0..lane
-    const int start = 63 - __clzll((long long)(heads & upto));
-    const unsigned long long above = heads & ~upto;
-    const int end = above ? __ffsll((long long)above) - 1 : 64;
-    int base = 0;
-    if (head) base = atomicAdd(&counter[key], end - start);
-    base = __shfl(base, start);
-    return key >= 0 ? base + (lane - start) : 0;
-}
-
-// --- A10, grid-accelerated (exact) -------------------------------------------------------------------
-// Points are counting-sorted into a uniform G^3 grid over their bounding box; a query walks the
-// cell shells around its own (virtual) cell in increasing Chebyshev radius r and stops as soon as
-// the best distance found is smaller than a certified lower bound for everything outside the
-// shell box.  Distances are evaluated exactly as the reference does, and candidates are combined
-// lexicographically (distance, index), which equals "first strict minimum of an ascending scan".
-constexpr int kNNBlocks = 64;
-
-constexpr int kNNCoarse = 4;           // coarse cells are 4x4x4 fine cells
-struct NNGrid { float o[3], inv[3], cs[3], slack[3]; int G, Gc; };
-
-// (the same launch clears what the later kernels accumulate into: cell counters, coarse-cell representatives, nRep)
-__global__ __launch_bounds__(256) void k_nn_bbox(const float *__restrict__ pts, int M, float *part, size_t slice, int *cells, int *rep,
-                                                 int *nRep, int nc)
-{
-    __shared__ float sh[4][6];
-    const int sb = blockIdx.y;
-    pts += (size_t)sb * M * 3;
-    SHAPE(part); SHAPE(cells); SHAPE(rep); SHAPE(nRep);
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nc; i += gridDim.x * blockDim.x) { cells[i] = 0; rep[i] = -1; }
-    if (blockIdx.x == 0 && threadIdx.x < 4) nRep[threadIdx.x] = 0;
-    BoxStats<3, 0> bs;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < M; i += gridDim.x * blockDim.x) {
-        const float p[3] = {pts[i * 3], pts[i * 3 + 1], pts[i * 3 + 2]};
-        if (fabsf(p[0]) < INFINITY && fabsf(p[1]) < INFINITY && fabsf(p[2]) < INFINITY) bs.add_point(p);     // finite (NaN fails)
-    }
-    bs.block_store(sh, part + blockIdx.x * 6);
-}
-
-__global__ __launch_bounds__(64) void k_nn_grid(const float *__restrict__ part, int G, NNGrid *g, size_t slice)
-{
-    const int sb = blockIdx.x;
-    SHAPE(part); SHAPE(g);
-    const int lane = threadIdx.x;
-    BoxStats<3, 0> bs;
-    bs.load(part + lane * 6);
-    bs.wave_reduce();
-    if (lane == 0) {
-        NNGrid r;
-        r.G = G;
-        r.Gc = (G + kNNCoarse - 1) / kNNCoarse;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const bool ok = bs.hi[k] >= bs.lo[k];
-            const float l = ok ? bs.lo[k] : 0.f, h = ok ? bs.hi[k] : 0.f;
-            const float ext = h - l;
-            r.o[k] = l;
-            const bool flat = !(ext > 1e-30f) || !(ext < 1e30f);
-            r.inv[k] = flat ? 0.f : (float)G / ext;
-            r.cs[k] = flat ? INFINITY : ext / (float)G;          // cell size (inf: one slab, no bound on this axis)
-            // absolute uncertainty of a cell boundary position as seen through the fp32 cell assignment
-            r.slack[k] = 8e-6f * (fabsf(l) + fabsf(h)) + 1e-30f;
-        }
-        *g = r;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_nn_bin(const float *__restrict__ pts, int M, const NNGrid *__restrict__ gp, int *cells,
-                                                int2 *pcell, int *rep, size_t slice)
-{
-    const int sb = blockIdx.y;
-    pts += (size_t)sb * M * 3;
-    SHAPE(gp); SHAPE(cells); SHAPE(pcell); SHAPE(rep);
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = i < M;                                       // (no early return: run_atomic_rank is a wave operation)
-    const NNGrid g = *gp;
-    const int ii = live ? i : 0;
-    const float x = pts[ii * 3], y = pts[ii * 3 + 1], z = pts[ii * 3 + 2];
-    int2 r = make_int2(-1, 0);
-    int cx = 0, cy = 0, cz = 0;
-    if (live && fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY) {
-        cx = grid_cell(x, g.o[0], g.inv[0], g.G); cy = grid_cell(y, g.o[1], g.inv[1], g.G); cz = grid_cell(z, g.o[2], g.inv[2], g.G);
-        r.x = (cz * g.G + cy) * g.G + cx;
-    }
-    r.y = run_atomic_rank(cells, r.x);
-    // any point of the coarse cell will do as its representative: the first arrival of every fine cell offers itself
-    // (one atomic per occupied fine cell — one per POINT put hundreds of them on the same address: 0.33 ms per 8 shapes)
-    if (r.x >= 0 && r.y == 0) atomicMax(&rep[((cz / kNNCoarse) * g.Gc + cy / kNNCoarse) * g.Gc + cx / kNNCoarse], i);
-    if (live) pcell[i] = r;                                        // non-finite points can never be nearest (d is inf/NaN)
-}
-
-__global__ __launch_bounds__(256) void k_nn_scatter(const float *__restrict__ pts, int M, const int2 *__restrict__ pcell,
-                                                    const int *__restrict__ start, float4 *sorted, size_t slice)
-{
-    const int sb = blockIdx.y;
-    pts += (size_t)sb * M * 3;
-    SHAPE(pcell); SHAPE(start); SHAPE(sorted);
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M) return;
-    const int2 r = pcell[i];
-    if (r.x < 0) return;
-    sorted[start[r.x] + r.y] = make_float4(pts[i * 3], pts[i * 3 + 1], pts[i * 3 + 2], __int_as_float(i));
-}
-
-// Sort key of the queries k_nn_query answered itself: the first power of two above every Morton key of the grid (three
-// interleaved coordinates 0..G+1), so that the far queries sort to the front on 3*bits + 1 key bits (16 for G <= 30).
-static int nn_far_key_bits(int G)
-{
-    int bits = 1;
-    while ((1 << bits) < G + 2) ++bits;
-    return 3 * bits;
-}
-constexpr int kFarRows = 25;
-
-__device__ __forceinline__ unsigned spread3(unsigned v)            // bit i of an 8-bit value -> bit 3i
-{
-    v = (v | (v << 8)) & 0x0000F00Fu;
-    v = (v | (v << 4)) & 0x000C30C3u;
-    v = (v | (v << 2)) & 0x00249249u;
-    return v;
-}
-
-// Two phases per query (one lane each):
-//  1. an UPPER bound U on the nearest distance from the coarse grid: shells of coarse cells are
-//     searched until one holds a representative point; U = smallest exact distance to those;
-//  2. every fine-grid row (cz,cy) whose slab can intersect the ball of radius sqrt(U) is visited
-//     once: the x-interval of the ball in that row is one contiguous slice of the sorted points.
-// All points with fp32 distance <= U lie in the enumerated slices (margins below), so the
-// lexicographic (distance, index) minimum over them equals the reference's ascending scan.
-__global__ __launch_bounds__(256) void k_nn_query(const float *__restrict__ queries, int N, const NNGrid *__restrict__ gp,
-                                                  const int *__restrict__ start, const float4 *__restrict__ sorted,
-                                                  const int *__restrict__ rep, const float *__restrict__ pts, int M, int *result,
-                                                  unsigned *farKey, unsigned notFar, size_t slice, ShapeCounts cnt, int Nst,
-                                                  unsigned shapeShift)
-{
-    // N = the query stride; shape sb has cnt.n[sb] <= N queries.  farKey is ONE array of Nst keys per shape (not in the
-    // slices: the far keys of all shapes are sorted by one call, with the shape index above the key bits).
-    const int sb = blockIdx.y;
-    queries += (size_t)sb * N * 3; pts += (size_t)sb * M * 3; result += (size_t)sb * N; farKey += (size_t)sb * Nst;
-    SHAPE(gp); SHAPE(start); SHAPE(sorted); SHAPE(rep);
-    const unsigned shapeBits = (unsigned)sb << shapeShift;
-    notFar |= shapeBits;
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= cnt.n[sb]) {
-        if (q < Nst) farKey[q] = notFar;                            // padding keys sort behind the shape's far queries
-        return;
-    }
-    const NNGrid g = *gp;
-    const int G = g.G, Gc = g.Gc;
-    const float qx = queries[q * 3], qy = queries[q * 3 + 1], qz = queries[q * 3 + 2];
-    const float qq[3] = {qx, qy, qz};
-    farKey[q] = notFar;
-    if (!(fabsf(qx) < INFINITY && fabsf(qy) < INFINITY && fabsf(qz) < INFINITY)) { result[q] = 0; return; }   // every d is inf/NaN
-    // a far query is keyed by the Morton code of its (clamped) fine cell: sorted by it, the lanes of k_nn_far are neighbours
-    auto far_key = [&]() {
-        unsigned key = 0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            float f = floorf((qq[k] - g.o[k]) * g.inv[k]);
-            f = fminf(fmaxf(f, -1.f), (float)G) + 1.f;              // 0 .. G+1 <= 161: eight bits
-            key |= spread3((unsigned)f) << k;
-        }
-        return key;
-    };
-    auto dist = [&](float px, float py, float pz) {
-        const float dx = px - qx, dy = py - qy, dz = pz - qz;
-        float d = 0.f;
-        d += dx * dx;                                               // nearest_neighbor_cuda.cu:42
-        d += dy * dy;                                               // :44
-        d += dz * dz;                                               // :46
-        return d;
-    };
-    // ---- phase 0: tight upper bound from the 3x3x3 fine cells around the query (near queries)
-    float U = INFINITY;
-    {
-        int c[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            float f = floorf((qq[k] - g.o[k]) * g.inv[k]);
-            f = fminf(fmaxf(f, -2.f), (float)(G + 1));
-            c[k] = (int)f;
-        }
-        const int x0 = max(c[0] - 1, 0), x1 = min(c[0] + 1, G - 1);
-        if (x0 <= x1)
-            for (int cz = max(c[2] - 1, 0); cz <= min(c[2] + 1, G - 1); ++cz)
-                for (int cy = max(c[1] - 1, 0); cy <= min(c[1] + 1, G - 1); ++cy) {
-                    const int row = (cz * G + cy) * G;
-                    const int s = start[row + x0], e = start[row + x1 + 1];
-                    for (int j = s; j < e; j += 4) {
-                        float4 p[4];
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) p[k] = sorted[min(j + k, e - 1)];
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) U = fminf(U, dist(p[k].x, p[k].y, p[k].z));
-                    }
-                }
-    }
-    // ---- phase 1: otherwise a loose bound from the coarse grid (one representative point per 4^3 cells)
-    int cc[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        float f = floorf((qq[k] - g.o[k]) * g.inv[k] * (1.0f / kNNCoarse));
-        f = fminf(fmaxf(f, -1.f), (float)Gc);
-        cc[k] = (int)f;
-    }
-    constexpr int kCoarseRings = 1;                                  // beyond that the query is "far": streaming scan
-    for (int r = 0; r <= kCoarseRings && !(U < INFINITY); ++r) {
-        for (int dz = -r; dz <= r; ++dz) {
-            const int z = cc[2] + dz;
-            if (z < 0 || z >= Gc) continue;
-            for (int dy = -r; dy <= r; ++dy) {
-                const int y = cc[1] + dy;
-                if (y < 0 || y >= Gc) continue;
-                const bool face = max(abs(dz), abs(dy)) == r;
-                for (int dx = -r; dx <= r; dx += (face ? 1 : (r > 0 ? 2 * r : 1))) {
-                    const int x = cc[0] + dx;
-                    if (x < 0 || x >= Gc) continue;
-                    const int i = rep[(z * Gc + y) * Gc + x];
-                    if (i >= 0) U = fminf(U, dist(pts[i * 3], pts[i * 3 + 1], pts[i * 3 + 2]));
-                }
-            }
-        }
-    }
-    float best = 1e20f;                                             // :28
-    int besti = 0;
-    if (!(U < INFINITY)) {                                           // nothing within one coarse ring: far (or no finite point)
-        farKey[q] = far_key() | shapeBits;
-        return;
-    }
-    U = fminf(U, 1e20f);                                            // nothing farther than the initial best can win
-    // ---- phase 2: rows intersecting the ball of radius R (inflated for fp32 rounding of d and of the cell map)
-    const float R = sqrtf(U) * 1.00001f;
-    int lo[3], hi[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        lo[k] = grid_cell(qq[k] - R - g.slack[k], g.o[k], g.inv[k], G);
-        hi[k] = grid_cell(qq[k] + R + g.slack[k], g.o[k], g.inv[k], G);
-    }
-    // distance from q to the slab of cell layer c on axis k (0 inside; a flat axis is one unbounded slab)
-    auto slab = [&](int k, int c) -> float {
-        if (!(g.cs[k] < INFINITY)) return 0.f;
-        const float l = g.o[k] + (float)c * g.cs[k] - g.slack[k], h = g.o[k] + (float)(c + 1) * g.cs[k] + g.slack[k];
-        return fmaxf(fmaxf(l - qq[k], qq[k] - h), 0.f);
-    };
-    const float R2 = R * R;
-    // A query whose ball spans many cell rows pays a dependent lookup per row and gathers points at
-    // ~4x the per-point cost of a wave-uniform stream: hand it to the k_nn_far_* kernels.  (Threshold measured on 80k
-    // queries against 100k points on a sphere: uniform queries 1.03 / 1.39 / 2.66 ms for 9 / 25 / 100 rows; queries sampled
-    // on a nearby surface 0.59 / 0.47 / 0.47 ms — the far path has ~0.15 ms of dependent-load latency of its own.)
-    if ((long long)(hi[2] - lo[2] + 1) * (hi[1] - lo[1] + 1) > kFarRows) {
-        farKey[q] = far_key() | shapeBits;
-        return;
-    }
-    for (int cz = lo[2]; cz <= hi[2]; ++cz) {
-        const float dz = slab(2, cz);
-        for (int cy = lo[1]; cy <= hi[1]; ++cy) {
-            const float dy = slab(1, cy);
-            const float rem = R2 - dy * dy - dz * dz;
-            if (rem < 0.f) continue;                                 // the whole row is farther than R
-            const float rx = sqrtf(rem) * 1.00001f;
-            const int x0 = grid_cell(qx - rx - g.slack[0], g.o[0], g.inv[0], G), x1 = grid_cell(qx + rx + g.slack[0], g.o[0], g.inv[0], G);
-            const int row = (cz * G + cy) * G;
-            const int s = start[row + x0], e = start[row + x1 + 1];
-            for (int j = s; j < e; j += 4) {                         // four gathers in flight per lane
-                float4 p[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) p[k] = sorted[min(j + k, e - 1)];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float d = dist(p[k].x, p[k].y, p[k].z);
-                    const int idx = __float_as_int(p[k].w);
-                    if (j + k < e && (d < best || (d == best && idx < besti && best < 1e20f))) { best = d; besti = idx; }
-                }
-            }
-        }
-    }
-    result[q] = besti;
-}
-
-// compact helper tables for k_nn_far: the representatives as (x, y, z, index) records and the first sorted slot of
-// every cell row; both padded so that k_nn_far can read them eight entries at a time
-constexpr int kNNBatch = 8;
-
-__global__ __launch_bounds__(256) void k_nn_far_tables(const int *__restrict__ rep, const float *__restrict__ pts, int Gc3,
-                                                       const int *__restrict__ start, int G, float4 *repList, int *nRep,
-                                                       int *rowStart, float4 *sorted, size_t slice, int M)
-{
-    const int sb = blockIdx.y;
-    pts += (size_t)sb * M * 3;
-    SHAPE(rep); SHAPE(start); SHAPE(repList); SHAPE(nRep); SHAPE(rowStart); SHAPE(sorted);
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < Gc3) {
-        const int r = rep[i];
-        const unsigned long long m = __ballot(r >= 0);
-        int base = 0;
-        if ((threadIdx.x & 63) == 0 && m) base = atomicAdd(nRep, __popcll(m));
-        base = __shfl(base, 0);
-        if (r >= 0)
-            repList[base + __popcll(m & ((1ull << (threadIdx.x & 63)) - 1ull))] =
-                make_float4(pts[r * 3], pts[r * 3 + 1], pts[r * 3 + 2], __int_as_float(r));
-    }
-    const int total = start[G * G * G];
-    if (i < G * G + 2 * kNNBatch) rowStart[i] = i < G * G ? start[i * G] : total;
-    if (i < 64) sorted[total + i] = make_float4(INFINITY, INFINITY, INFINITY, 0.f);   // tile padding (never considered)
-}
-
-__global__ __launch_bounds__(64) void k_nn_far_pad(float4 *repList, const int *__restrict__ nRep, size_t slice)
-{
-    const int sb = blockIdx.x;
-    SHAPE(repList); SHAPE(nRep);
-    repList[*nRep + threadIdx.x] = make_float4(INFINITY, INFINITY, INFINITY, 0.f);   // tile padding (64 threads)
-}
-
-// Far queries (answer farther than one coarse ring, or a ball over more than kFarRows cell rows).  One lane per query,
-// the queries SORTED by the Morton code of their cell so that a wave holds 64 neighbours, and everything a wave reads
-// is wave-uniform (scalar loads, eight records per batch, points as SGPR operands — the vector memory pipe is idle):
-//   k_nn_far_bound  A. every coarse cell's representative point bounds the answer from above;
-//                   B. the points of the coarse cells holding the lanes' best representatives tighten the bound;
-//   k_nn_far_rows   C. the cell rows (cz,cy) are visited; a row is skipped when its slab is farther than the current
-//                      best of EVERY lane (same certified margins as k_nn_query), otherwise the x-range the lanes can
-//                      still need is streamed;
-//   k_nn_far_final  scatters the answers back to query order.
-// Any point is a valid candidate for any lane (reading a few records past a row's end is harmless), and candidates are
-// combined as the 64-bit word (distance bits, index) under min — distances are non-negative, so that is the
-// lexicographic (distance, index) minimum = the reference's first strict minimum of an ascending scan — first in
-// registers, then across the four waves of a block in LDS, then across blocks with one atomicMin per lane.
-// A group of 64 queries at the centre of a sphere needs every point: 6.4 M distance evaluations that must not land on
-// one CU, so the rows of every group are split over kFarSlices blocks.
-// (Measured history, 80,640 uniform queries against 100,000 points on a sphere, plain scan 5.5 ms: far list appended
-// with one same-address atomic per query and every far query scanning ALL points 7.2 ms; pruned rows, one wave per 64
-// queries, one scalar load per record 14.3 ms; batches of eight and 4 / 16 waves per group 4.5 / 2.4 ms; A and B shared
-// between the waves 1.55 ms — the group that needs every point then kept one CU busy for 1 ms.)
-constexpr int kFarSlices = 8;            // blocks per group of 64 far queries in k_nn_far_rows
-constexpr int kFarWaves = 4;            // waves per block; they split the block's records
-
-struct FarLane {
-    float qx, qy, qz, best;
-    int besti;
-    __device__ __forceinline__ void consider(const float4 p)
-    {
-        const float dx = p.x - qx, dy = p.y - qy, dz = p.z - qz;
-        const int idx = __float_as_int(p.w);
-        float d = 0.f;
-        d += dx * dx;                                               // nearest_neighbor_cuda.cu:42
-        d += dy * dy;                                               // :44
-        d += dz * dz;                                               // :46
-        if (d < best || (d == best && idx < besti && best < 1e20f)) { best = d; besti = idx; }
-    }
-    // records [s, e) of a wave-uniform table (and up to seven more: the tables are padded with d = inf records)
-    __device__ __forceinline__ void stream(const float4 *__restrict__ src, int s, int e)
-    {
-        for (int j = s; j < e; j += kNNBatch) {
-            float4 p[kNNBatch];
-#pragma unroll
-            for (int k = 0; k < kNNBatch; ++k) p[k] = src[j + k];
-#pragma unroll
-            for (int k = 0; k < kNNBatch; ++k) consider(p[k]);
-        }
-    }
-    __device__ __forceinline__ unsigned long long packed() const
-    {
-        return ((unsigned long long)(unsigned)__float_as_int(best) << 32) | (unsigned)besti;
-    }
-    __device__ __forceinline__ void unpack(unsigned long long v)
-    {
-        best = __int_as_float((int)(v >> 32));
-        besti = (int)(unsigned)v;
-    }
-    // every wave of the block leaves with the block's best answer so far
-    __device__ __forceinline__ void share(unsigned long long (*s_pack)[64], int part, int lane)
-    {
-        s_pack[part][lane] = packed();
-        __syncthreads();
-        unsigned long long v = s_pack[0][lane];
-#pragma unroll
-        for (int w = 1; w < kFarWaves; ++w) v = min(v, s_pack[w][lane]);
-        unpack(v);
-        __syncthreads();
-    }
-};
-
-// (keys carry the shape index above the key bits: within a shape's segment the comparison with its own notFar is the same)
-__device__ __forceinline__ int far_count(const unsigned *__restrict__ farKeyS, int N, unsigned notFar)
-{
-    int lo = 0, hi = N;                                            // first sorted key == notFar
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (farKeyS[mid] < notFar) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-__global__ __launch_bounds__(kFarWaves * 64) void k_nn_far_bound(const float *__restrict__ queries, const NNGrid *__restrict__ gp,
-                                                                 const int *__restrict__ start, const float4 *__restrict__ sorted,
-                                                                 const float4 *__restrict__ repList, const int *__restrict__ nRepP,
-                                                                 const float *__restrict__ pts, int N,
-                                                                 const unsigned *__restrict__ farKeyS, const unsigned *__restrict__ farList,
-                                                                 unsigned long long *bound, int *nFar, unsigned notFar, size_t slice,
-                                                                 int M, int Nst, unsigned shapeShift)
-{
-    __shared__ unsigned long long s_pack[kFarWaves][64];
-    const int sb = blockIdx.y;
-    queries += (size_t)sb * N * 3; pts += (size_t)sb * M * 3; farKeyS += (size_t)sb * Nst; farList += (size_t)sb * Nst;
-    SHAPE(gp); SHAPE(start); SHAPE(sorted); SHAPE(repList); SHAPE(nRepP); SHAPE(bound); SHAPE(nFar);
-    const unsigned qbase = (unsigned)sb * (unsigned)Nst;            // farList holds positions in the all-shapes key array
-    const int n = far_count(farKeyS, Nst, notFar | ((unsigned)sb << shapeShift));
-    if (blockIdx.x == 0 && threadIdx.x == 0) *nFar = n;
-    const int lane = threadIdx.x & 63;
-    const int part = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform for the compiler too: scalar loads below
-    const int i = blockIdx.x * 64 + lane;
-    if (blockIdx.x * 64 >= n) return;                              // whole block idle
-    const int q = (int)(farList[i < n ? i : n - 1] - qbase);        // idle lanes shadow the last far query
-    const NNGrid g = *gp;
-    const int G = g.G, Gc = g.Gc;
-    FarLane L;
-    L.qx = queries[q * 3]; L.qy = queries[q * 3 + 1]; L.qz = queries[q * 3 + 2];
-    L.best = 1e20f;                                                 // nearest_neighbor_cuda.cu:28
-    L.besti = 0;
-    // ---- A: representatives, one batch per wave and turn
-    {
-        const int nRep = *nRepP;
-        for (int j = part * kNNBatch; j < nRep; j += kFarWaves * kNNBatch) L.stream(repList, j, j + kNNBatch);
-    }
-    L.share(s_pack, part, lane);
-    // ---- B: the coarse cells of the lanes' best representatives (at most four distinct ones per block); a coarse cell
-    //         is 4 x 4 rows of four cells: four rows per wave
-    {
-        const bool have = L.best < 1e20f;
-        const int bi = have ? L.besti : 0;
-        const float bx = pts[bi * 3], by = pts[bi * 3 + 1], bz = pts[bi * 3 + 2];
-        const int mine = ((grid_cell(bz, g.o[2], g.inv[2], G) / kNNCoarse) * Gc + grid_cell(by, g.o[1], g.inv[1], G) / kNNCoarse) * Gc +
-                         grid_cell(bx, g.o[0], g.inv[0], G) / kNNCoarse;
-        unsigned long long todo = __ballot(have);
-        for (int round = 0; round < 4 && todo; ++round) {
-            const int c = __builtin_amdgcn_readlane(mine, __ffsll((long long)todo) - 1);
-            todo &= ~__ballot(mine == c);
-            const int x0 = (c % Gc) * kNNCoarse, x1 = min(x0 + kNNCoarse - 1, G - 1);
-            const int cy0 = ((c / Gc) % Gc) * kNNCoarse, cz = (c / (Gc * Gc)) * kNNCoarse + part;
-            int se[2 * kNNCoarse];
-#pragma unroll
-            for (int k = 0; k < kNNCoarse; ++k) {
-                const int row = (min(cz, G - 1) * G + min(cy0 + k, G - 1)) * G;
-                se[2 * k] = start[row + x0]; se[2 * k + 1] = start[row + x1 + 1];
-            }
-#pragma unroll
-            for (int k = 0; k < kNNCoarse; ++k)
-                if (cz < G && cy0 + k < G) L.stream(sorted, se[2 * k], se[2 * k + 1]);
-        }
-    }
-    L.share(s_pack, part, lane);
-    if (part == 0 && i < n) bound[i] = L.packed();
-}
-
-__global__ __launch_bounds__(kFarWaves * 64) void k_nn_far_rows(const float *__restrict__ queries, const NNGrid *__restrict__ gp,
-                                                                const int *__restrict__ start, const float4 *__restrict__ sorted,
-                                                                const int *__restrict__ rowStart, const int *__restrict__ nFar,
-                                                                const unsigned *__restrict__ farList, unsigned long long *bound,
-                                                                size_t slice, int N, int Nst)
-{
-    __shared__ unsigned long long s_pack[kFarWaves][64];
-    const int sb = blockIdx.z;
-    queries += (size_t)sb * N * 3; farList += (size_t)sb * Nst;
-    SHAPE(gp); SHAPE(start); SHAPE(sorted); SHAPE(rowStart); SHAPE(nFar); SHAPE(bound);
-    const unsigned qbase = (unsigned)sb * (unsigned)Nst;
-    const int n = *nFar;
-    const int lane = threadIdx.x & 63;
-    const int part = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int i = blockIdx.x * 64 + lane;
-    if (blockIdx.x * 64 >= n) return;                              // whole block idle
-    const int ii = i < n ? i : n - 1;                              // idle lanes shadow the last far query
-    const int q = (int)(farList[ii] - qbase);
-    const NNGrid g = *gp;
-    const int G = g.G;
-    FarLane L;
-    L.qx = queries[q * 3]; L.qy = queries[q * 3 + 1]; L.qz = queries[q * 3 + 2];
-    L.unpack(bound[ii]);                                           // as k_nn_far_bound left it (other slices may have improved it)
-    const float qq[3] = {L.qx, L.qy, L.qz};
-    auto slab = [&](int k, int c) -> float {                        // as in k_nn_query
-        if (!(g.cs[k] < INFINITY)) return 0.f;
-        const float l = g.o[k] + (float)c * g.cs[k] - g.slack[k], h = g.o[k] + (float)(c + 1) * g.cs[k] + g.slack[k];
-        return fmaxf(fmaxf(l - qq[k], qq[k] - h), 0.f);
-    };
-    const int nb = (G + kNNBatch - 1) / kNNBatch;                   // work item = (layer cz, batch of eight rows cy0..cy0+7)
-    for (int item = blockIdx.y * kFarWaves + part; item < G * nb; item += kFarWaves * kFarSlices) {
-        const int cz = item / nb, cy0 = (item % nb) * kNNBatch;
-        const float dz = slab(2, cz);
-        if (!__any(!(L.best * 1.00003f - dz * dz < 0.f))) continue; // the whole layer is out of reach of every lane
-        int rs[kNNBatch + 1];
-#pragma unroll
-        for (int k = 0; k <= kNNBatch; ++k) rs[k] = rowStart[cz * G + cy0 + k];   // padded: reads past G*G return the total
-        // first the slice [s, e) of each of the eight rows that some lane can still need (lane k of vs/ve keeps row k's;
-        // the eight pairs of cell-start loads are independent), then ONE copy of the streaming loop walks them
-        int vs = 0, ve = 0;
-#pragma unroll
-        for (int k = 0; k < kNNBatch; ++k) {
-            const int cy = cy0 + k;
-            int s = 0, e = 0;
-            if (cy < G && rs[k] != rs[k + 1]) {
-                const float dy = slab(1, cy);
-                // squared reach, inflated for the fp32 rounding of d and of the cell map (k_nn_query: R = sqrt(U) * 1.00001)
-                const float rem = L.best * 1.00003f - dy * dy - dz * dz;
-                const bool need = !(rem < 0.f);
-                if (__any(need)) {
-                    s = rs[k]; e = rs[k + 1];
-                    if (e - s > 3 * kNNBatch) {                     // long row: only the x-range the lanes can reach
-                        const float rx = sqrtf(fmaxf(rem, 0.f)) * 1.00001f;
-                        int x0 = need ? grid_cell(L.qx - rx - g.slack[0], g.o[0], g.inv[0], G) : G - 1;
-                        int x1 = need ? grid_cell(L.qx + rx + g.slack[0], g.o[0], g.inv[0], G) : 0;
-                        if (need && !(rx < INFINITY)) { x0 = 0; x1 = G - 1; }
-#pragma unroll
-                        for (int off = 32; off > 0; off >>= 1) {
-                            x0 = min(x0, __shfl_xor(x0, off));
-                            x1 = max(x1, __shfl_xor(x1, off));
-                        }
-                        x0 = __builtin_amdgcn_readfirstlane(x0);
-                        x1 = __builtin_amdgcn_readfirstlane(x1);
-                        const int row = (cz * G + cy) * G;
-                        s = start[row + x0]; e = start[row + x1 + 1];
-                    }
-                }
-            }
-            vs = lane == k ? s : vs;
-            ve = lane == k ? e : ve;
-        }
-#pragma unroll 1
-        for (int k = 0; k < kNNBatch; ++k) L.stream(sorted, __builtin_amdgcn_readlane(vs, k), __builtin_amdgcn_readlane(ve, k));
-    }
-    L.share(s_pack, part, lane);
-    if (part == 0 && i < n) atomicMin(&bound[i], L.packed());
-}
-
-__global__ __launch_bounds__(256) void k_nn_far_final(const unsigned long long *__restrict__ bound, const int *__restrict__ nFar,
-                                                      const unsigned *__restrict__ farList, int *result, size_t slice, int N, int Nst)
-{
-    const int sb = blockIdx.y;
-    farList += (size_t)sb * Nst; result += (size_t)sb * N;
-    SHAPE(bound); SHAPE(nFar);
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < *nFar) result[farList[i] - (unsigned)sb * (unsigned)Nst] = (int)(unsigned)bound[i];
-}
-
-// ---------------------------------------------------------------------------- chamfer term of the surface loss
-// layers/DefTet/deftet.py:174-177 composed (utils/mesh_utils.py:290-299, :360-374): K area-uniform samples per predicted
-// face, each measured against its nearest ground-truth point (operator A10).  As torch expressions these are ~45 small
-// launches per step (forward and backward); here: one to place the samples, one for the distances, one for the gradient.
-constexpr float kChamferEps = 1e-10f;   // inside the square root (utils/mesh_utils.py:14)
-
-// samples f32 [B, F*K, 3]: sample j of face f in row f*K + j = wa*a + wb*b + wc*c with s = sqrt(r0), wa = 1 - s,
-// wb = s (1 - r1), wc = s r1 (square-root warp of two uniform numbers r f32 [2, B, F, K])
-__global__ __launch_bounds__(256) void k_face_samples(const float *__restrict__ tri, const float *__restrict__ r, float *samples, int K,
-                                                      long long total)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const float *t = tri + (i / K) * 9;
-    const float s = sqrtf(r[i]), r1 = r[total + i];
-    const float wa = 1.0f - s, wb = s * (1.0f - r1), wc = s * r1;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) samples[i * 3 + k] = (wa * t[k] + wb * t[3 + k]) + wc * t[6 + k];
-}
-
-// d f32 [B,N] = sqrt(|sample - gt[idx]|^2 + eps) for the first n_valid[b] rows of shape b, 0 beyond
-__global__ __launch_bounds__(256) void k_chamfer_fwd(const float *__restrict__ samples, const float *__restrict__ gt,
-                                                     const int *__restrict__ idx, const int *__restrict__ n_valid, float *d, int N, int M)
-{
-    const int b = blockIdx.y;
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= N) return;
-    const size_t i = (size_t)b * N + j;
-    float v = 0.f;
-    if (j < n_valid[b]) {
-        const float *sp = samples + i * 3, *g = gt + ((size_t)b * M + idx[i]) * 3;
-        const float dx = sp[0] - g[0], dy = sp[1] - g[1], dz = sp[2] - g[2];
-        v = sqrtf(((dx * dx + dy * dy) + dz * dz) + kChamferEps);
-    }
-    d[i] = v;
-}
-
-// grad_tri f32 [B,F,3,3]: one lane per face adds up its K samples' gradients (no atomics); gscale f32 [B] = dL/d(sum of d)
-__global__ __launch_bounds__(256) void k_chamfer_bwd(const float *__restrict__ samples, const float *__restrict__ gt,
-                                                     const int *__restrict__ idx, const int *__restrict__ n_valid,
-                                                     const float *__restrict__ d, const float *__restrict__ r,
-                                                     const float *__restrict__ gscale, float *grad_tri, int F, int K, int M, long long total)
-{
-    const int b = blockIdx.y;
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= F) return;
-    float ga[3] = {0.f, 0.f, 0.f}, gb[3] = {0.f, 0.f, 0.f}, gc[3] = {0.f, 0.f, 0.f};
-    const int N = F * K;
-    const float gs = gscale[b];
-    for (int j = 0; j < K; ++j) {
-        const int row = f * K + j;
-        if (row >= n_valid[b]) break;
-        const size_t i = (size_t)b * N + row;
-        const float *sp = samples + i * 3, *g = gt + ((size_t)b * M + idx[i]) * 3;
-        const float s = sqrtf(r[i]), r1 = r[total + i];
-        const float wa = 1.0f - s, wb = s * (1.0f - r1), wc = s * r1;
-        const float w = gs / d[i];                                     // d(sqrt(q + eps))/d(sample) = (sample - near) / d
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            const float gk = w * (sp[k] - g[k]);
-            ga[k] += wa * gk; gb[k] += wb * gk; gc[k] += wc * gk;
-        }
-    }
-    float *o = grad_tri + ((size_t)b * F + f) * 9;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { o[k] = ga[k]; o[3 + k] = gb[k]; o[6 + k] = gc[k]; }
-}
-
-// ---------------------------------------------------------------------------- A8 face edge adjacency
-__device__ __forceinline__ bool pos_equal(const float *a, const float *b)
-{   // equal(), tet_face_adj_m_for.cu:26-35
-    float diff = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        float d = a[i] - b[i];
-        if (d < 0) d = -d;
-        diff += d;
-    }
-    return (double)diff <= 1e-15;
-}
-
-__global__ __launch_bounds__(256) void k_face_edge_adj(const float *__restrict__ face, float *__restrict__ adj, int F, int max_nei)
-{
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = f < F;
-    float fa[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) fa[i] = face[(size_t)(live ? f : 0) * 9 + i];
-    int found = live ? 0 : max_nei;
-    for (int g = 0; g < F; ++g) {                                   // ascending g, :95
-        if (__ballot(found < max_nei) == 0ull) break;               // every lane of the wave is full (:104-106)
-        float fb[9];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) fb[i] = face[(size_t)g * 9 + i];   // wave-uniform -> scalar loads
-        // check_share (:38-69) through the 3x3 vertex-equality matrix: equal() is a pure
-        // function of its two vertices, so evaluating each pair once gives the same boolean
-        bool E[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) E[i][j] = pos_equal(fa + 3 * i, fb + 3 * j);
-        bool share = false;
-#pragma unroll
-        for (int ia = 0; ia < 3; ++ia)
-#pragma unroll
-            for (int ib = 0; ib < 3; ++ib) {
-                const int ia2 = (ia + 1) % 3, ib2 = (ib + 1) % 3;
-                share = share || (E[ia][ib] && E[ia2][ib2]) || (E[ia][ib2] && E[ia2][ib]);   // :60, :63
-            }
-        if (share && g != f && found < max_nei) {                   // :96, :100-103
-            adj[(size_t)f * max_nei + found] = (float)g;
-            ++found;
-        }
-    }
-}
-
-// --- A8, hash-based (exact): O(F) instead of O(F^2) --------------------------------------------------
-// equal(a,b) (L1 distance <= 1e-15 in fp32) can only hold if, coordinate by coordinate, the two
-// floats are bitwise identical or both "tiny" (|x| < 2^-24: one ulp there is still > 1e-15 above
-// that magnitude, so distinct non-tiny floats differ by >= 7e-15).  NaN/Inf coordinates never
-// compare equal (the difference is NaN).  So a NECESSARY condition for two faces to share an edge
-// is equality of a 192-bit edge key built from per-coordinate keys (float bits, or one tag for
-// all tiny values, or a unique tag for non-finite ones).  Edge records are chained per slot of a hash table
-// on that key (one atomicExch each), and every face runs the EXACT check_share() only on the chain
-// entries whose full key equals the key of one of its three edges, keeping the 30 smallest neighbour
-// ids in ascending order.  Two launches for a whole batch of surfaces (rounds 1-2 radix-sorted the
-// records by the 192-bit key: three 64-bit passes, ~38 launches per surface).
-using u64 = unsigned long long;
-using u32 = unsigned int;
-
-struct VKey { u32 x, y, z; };
-
-__device__ __forceinline__ u32 coord_key(float v, u32 unique, bool &bad)
-{
-    const u32 b = __float_as_uint(v);
-    if ((b & 0x7F800000u) == 0x7F800000u) { bad = true; return unique; }   // NaN / Inf: never equal to anything
-    if (fabsf(v) < 5.9604645e-08f) return 0u;                                // tiny (|x| < 2^-24), includes +-0
-    return b;
-}
-__device__ __forceinline__ VKey vertex_key(const float *v, u32 unique)
-{
-    bool bad = false;
-    VKey k{coord_key(v[0], unique, bad), coord_key(v[1], unique, bad), coord_key(v[2], unique, bad)};
-    if (bad) { k.x = 0xFFFFFFFFu; k.y = unique; k.z = 0u; }                 // 0xFFFFFFFF is itself a NaN pattern: no finite float has it
-    return k;
-}
-__device__ __forceinline__ bool vkey_less(const VKey &a, const VKey &b)
-{
-    if (a.x != b.x) return a.x < b.x;
-    if (a.y != b.y) return a.y < b.y;
-    return a.z < b.z;
-}
-
-// 64-bit hash of an edge key (a <= b in vkey order): the chains of a table slot hold every edge with that key plus
-// the few that collide with it; keys are compared in full before check_share() runs.
-__device__ __forceinline__ u64 mix64(u64 x)
-{
-    x ^= x >> 33; x *= 0xff51afd7ed558ccdULL; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ULL; x ^= x >> 33;
-    return x;
-}
-struct EKey { VKey a, b; };
-__device__ __forceinline__ EKey edge_key(const float *fa, int f, int e)
-{
-    VKey a = vertex_key(fa + 3 * e, (u32)(f * 3 + e)), b = vertex_key(fa + 3 * ((e + 1) % 3), (u32)(f * 3 + (e + 1) % 3));
-    if (vkey_less(b, a)) { const VKey t = a; a = b; b = t; }
-    return EKey{a, b};
-}
-__device__ __forceinline__ bool ekey_equal(const EKey &p, const EKey &q)
-{
-    return p.a.x == q.a.x && p.a.y == q.a.y && p.a.z == q.a.z && p.b.x == q.b.x && p.b.y == q.b.y && p.b.z == q.b.z;
-}
-__device__ __forceinline__ u32 ekey_slot(const EKey &k, u32 mask)
-{
-    u64 h = mix64(((u64)k.a.x << 32) | k.a.y);
-    h = mix64(h ^ (((u64)k.a.z << 32) | k.b.x));
-    h = mix64(h ^ (((u64)k.b.y << 32) | k.b.z));
-    return (u32)h & mask;
-}
-
-constexpr int kA8Shapes = 32;          // shapes per launch (their face counts travel by value)
-struct A8Counts { int n[kA8Shapes]; };
-
-// every edge record r = 3 f + e of shape blockIdx.y is pushed onto the chain of its table slot (one atomicExch)
-__global__ __launch_bounds__(256) void k_edge_insert(const float *__restrict__ face, int Fmax, A8Counts cnt, u32 mask, int *head, int *next)
-{
-    const int b = blockIdx.y, F = cnt.n[b];
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= F * 3) return;
-    const int f = r / 3, e = r % 3;
-    const EKey k = edge_key(face + ((size_t)b * Fmax + f) * 9, f, e);
-    int *hb = head + (size_t)b * (mask + 1), *nb = next + (size_t)b * Fmax * 3;
-    nb[r] = atomicExch(&hb[ekey_slot(k, mask)], r);
-}
-
-__device__ __forceinline__ bool check_share_exact(const float *fa, const float *fb)
-{   // check_share, tet_face_adj_m_for.cu:38-69 (through the 3x3 vertex-equality matrix)
-    bool E[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) E[i][j] = pos_equal(fa + 3 * i, fb + 3 * j);
-    bool share = false;
-#pragma unroll
-    for (int ia = 0; ia < 3; ++ia)
-#pragma unroll
-        for (int ib = 0; ib < 3; ++ib) {
-            const int ia2 = (ia + 1) % 3, ib2 = (ib + 1) % 3;
-            share = share || (E[ia][ib] && E[ia2][ib2]) || (E[ia][ib2] && E[ia2][ib]);
-        }
-    return share;
-}
-
-constexpr int kMaxNeiFast = 32;        // the sorted path keeps its candidate list in registers/scratch
-
-
-// every face walks the chains of its three edges: candidates with an identical 192-bit key get the EXACT check_share(),
-// the max_nei smallest neighbour ids are kept in ascending order (the chain order does not matter)
-__global__ __launch_bounds__(256) void k_face_neighbors(const float *__restrict__ face, int Fmax, A8Counts cnt, u32 mask,
-                                                        const int *__restrict__ head, const int *__restrict__ next,
-                                                        float *__restrict__ adj, int max_nei)
-{
-    const int b = blockIdx.y, F = cnt.n[b];
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= F) return;
-    const float *fbase = face + (size_t)b * Fmax * 9;
-    const int *hb = head + (size_t)b * (mask + 1), *nxt = next + (size_t)b * Fmax * 3;
-    float fa[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) fa[i] = fbase[(size_t)f * 9 + i];
-    int nb[kMaxNeiFast];
-    int n = 0;
-    for (int e = 0; e < 3; ++e) {
-        const EKey k = edge_key(fa, f, e);
-        for (int rj = hb[ekey_slot(k, mask)]; rj >= 0; rj = nxt[rj]) {
-            const int g = rj / 3;
-            if (g == f) continue;
-            if (n == max_nei && g > nb[n - 1]) continue;             // cannot be among the max_nei smallest
-            float fb[9];
-#pragma unroll
-            for (int i = 0; i < 9; ++i) fb[i] = fbase[(size_t)g * 9 + i];
-            if (!ekey_equal(k, edge_key(fb, g, rj % 3))) continue;  // a hash collision, or another key in the same slot
-            if (!check_share_exact(fa, fb)) continue;
-            // insert g into the ascending list (no duplicates), keep the max_nei smallest
-            int pos = 0;
-            while (pos < n && nb[pos] < g) ++pos;
-            if (pos < n && nb[pos] == g) continue;
-            if (n < max_nei) ++n;
-            for (int kk = n - 1; kk > pos; --kk) nb[kk] = nb[kk - 1];
-            if (pos < n) nb[pos] = g;
-        }
-    }
-    float *ab = adj + ((size_t)b * Fmax + f) * max_nei;
-    for (int kk = 0; kk < n; ++kk) ab[kk] = (float)nb[kk];
-}
-
-// --- normal consistency on the A8 table (utils/mesh_utils.py:28-39 composed: unit normals, pairs, mean of 1 - cos) ----
-// loss_b = mean over the valid entries (i, j = adj[i][k] >= 0) of 1 - <n_i, n_j>,  n = c / sqrt(|c|^2 + 1e-12),
-// c = (v1 - v0) x (v2 - v0); 0 when there is no pair.  One workgroup per shape (fixed reduction order: deterministic
-// forward); the backward adds the two adjacency directions with float atomics and chains through the normalisation and
-// the cross product.  (The torch composition of the same thing gathers a [B, F, 30, 3] tensor and scatters it back in
-// the backward: 1.8 ms per call at F = 4,056, B = 8, against ~0.03 ms here.)
-constexpr int kNCThreads = 1024;
-constexpr float kNormalEps = 1e-12f;
-
-__device__ __forceinline__ void face_cross(const float *t, float *c)
-{
-    const float e1[3] = {t[3] - t[0], t[4] - t[1], t[5] - t[2]}, e2[3] = {t[6] - t[0], t[7] - t[1], t[8] - t[2]};
-    c[0] = e1[1] * e2[2] - e1[2] * e2[1];
-    c[1] = e1[2] * e2[0] - e1[0] * e2[2];
-    c[2] = e1[0] * e2[1] - e1[1] * e2[0];
-}
-
-__device__ __forceinline__ float block_sum(float v, float *sh)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float tot = 0.f;
-    for (int k = 0; k < (int)(blockDim.x >> 6); ++k) tot += sh[k];     // fixed order
-    return tot;
-}
-
-constexpr int kNCLdsFaces = 4096;       // normals of a shape kept in LDS up to this many faces (48 KB)
-__global__ __launch_bounds__(kNCThreads) void k_normal_consistency_fwd(const float *__restrict__ tri, const float *__restrict__ adj,
-                                                                       const int *__restrict__ n_face, float *loss, float *nrm,
-                                                                       float *count, int Fmax, int max_nei)
-{
-    __shared__ float sh[kNCThreads / 64];
-    __shared__ float s_n[kNCLdsFaces * 3];
-    const int b = blockIdx.x, F = min(n_face[b], Fmax);
-    const float *tb = tri + (size_t)b * Fmax * 9, *ab = adj + (size_t)b * Fmax * max_nei;
-    float *nb = nrm + (size_t)b * Fmax * 3;
-    const bool lds = F <= kNCLdsFaces;                               // block-uniform
-    for (int f = threadIdx.x; f < F; f += kNCThreads) {
-        float t[9], c[3];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) t[k] = tb[(size_t)f * 9 + k];
-        face_cross(t, c);
-        const float r = 1.0f / sqrtf(c[0] * c[0] + c[1] * c[1] + c[2] * c[2] + kNormalEps);
-        const float n0 = c[0] * r, n1 = c[1] * r, n2 = c[2] * r;
-        nb[f * 3] = n0; nb[f * 3 + 1] = n1; nb[f * 3 + 2] = n2;     // kept for the backward
-        if (lds) { s_n[f * 3] = n0; s_n[f * 3 + 1] = n1; s_n[f * 3 + 2] = n2; }
-    }
-    __syncthreads();                                                 // the shape's normals are this workgroup's own writes
-    // One (face, neighbour slot) pair per thread and step: the table is read with consecutive addresses, the normals come
-    // from LDS, and nothing in a step depends on the previous one, so the unrolled steps overlap.  (One face per thread
-    // walking its row — 30 dependent loads behind a branch, four faces after each other — took 65 us for 8 x 4,056
-    // faces; the pair loop with the normals gathered from global memory 91 us.)  Surfaces of more than 4,096 faces keep
-    // the row walk.
-    float s = 0.f, cnt = 0.f;
-    if (lds) {
-        const int nPair = F * max_nei;
-#pragma unroll 4
-        for (int i = threadIdx.x; i < nPair; i += kNCThreads) {
-            const int f = i / max_nei;
-            const float a = ab[i];
-            const bool valid = a >= 0.f && a < (float)F;            // (entries outside [0, F) — or NaN — count as "no neighbour")
-            const int j = valid ? (int)a : f;
-            const float d = s_n[f * 3] * s_n[j * 3] + s_n[f * 3 + 1] * s_n[j * 3 + 1] + s_n[f * 3 + 2] * s_n[j * 3 + 2];
-            s += valid ? 1.0f - d : 0.f;
-            cnt += valid ? 1.0f : 0.f;
-        }
-    } else {
-        for (int f = threadIdx.x; f < F; f += kNCThreads) {
-            const float n0 = nb[f * 3], n1 = nb[f * 3 + 1], n2 = nb[f * 3 + 2];
-            for (int k = 0; k < max_nei; ++k) {
-                const float a = ab[(size_t)f * max_nei + k];
-                if (!(a >= 0.f && a < (float)F)) continue;
-                const int j = (int)a;
-                s += 1.0f - (n0 * nb[j * 3] + n1 * nb[j * 3 + 1] + n2 * nb[j * 3 + 2]);
-                cnt += 1.0f;
-            }
-        }
-    }
-    const float S = block_sum(s, sh), C = block_sum(cnt, sh);
-    if (threadIdx.x == 0) {
-        count[b] = C;
-        loss[b] = C > 0.f ? S / C : 0.f;
-    }
-}
-
-// backward, two launches over (faces, shapes) grids (one workgroup per shape, as the forward still is, ran its ~4 faces x 30
-// dependent neighbour loads per thread unhidden: 0.13 ms per 8 shapes):
-//  scatter: G_k = d(sum of 1 - <n_i, n_j>)/d n_k = -(sum over row k of n_j) - (sum over the rows i that list k of n_i),
-//           formed in acc (zeroed by the caller) with float atomics — the table need not be symmetric (rows are cut at
-//           max_nei entries);
-//  final:   chain through the normalisation and the cross product, one lane per face.
-__global__ __launch_bounds__(256) void k_normal_consistency_bwd_scatter(const float *__restrict__ adj, const int *__restrict__ n_face,
-                                                                        const float *__restrict__ nrm, float *acc, int Fmax, int max_nei)
-{
-    const int b = blockIdx.y, F = min(n_face[b], Fmax);
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= F) return;
-    const float *ab = adj + ((size_t)b * Fmax + f) * max_nei, *nb = nrm + (size_t)b * Fmax * 3;
-    float *accb = acc + (size_t)b * Fmax * 3;
-    const float n0 = nb[f * 3], n1 = nb[f * 3 + 1], n2 = nb[f * 3 + 2];
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    for (int k = 0; k < max_nei; ++k) {
-        const float a = ab[k];
-        if (!(a >= 0.f && a < (float)F)) continue;                  // same validity rule as the forward
-        const int j = (int)a;
-        s0 += nb[j * 3]; s1 += nb[j * 3 + 1]; s2 += nb[j * 3 + 2];
-        unsafeAtomicAdd(&accb[j * 3], -n0); unsafeAtomicAdd(&accb[j * 3 + 1], -n1); unsafeAtomicAdd(&accb[j * 3 + 2], -n2);
-    }
-    unsafeAtomicAdd(&accb[f * 3], -s0); unsafeAtomicAdd(&accb[f * 3 + 1], -s1); unsafeAtomicAdd(&accb[f * 3 + 2], -s2);
-}
-
-__global__ __launch_bounds__(256) void k_normal_consistency_bwd_final(const float *__restrict__ tri, const int *__restrict__ n_face,
-                                                                      const float *__restrict__ count, const float *__restrict__ gloss,
-                                                                      const float *__restrict__ acc, float *gtri, int Fmax)
-{
-    const int b = blockIdx.y, F = min(n_face[b], Fmax);
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= Fmax) return;
-    const float C = count[b], w = C > 0.f ? gloss[b] / C : 0.f;
-    float g[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) g[k] = 0.f;
-    if (f < F) {
-        const float *tb = tri + ((size_t)b * Fmax + f) * 9, *accf = acc + ((size_t)b * Fmax + f) * 3;
-        float t[9], c[3];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) t[k] = tb[k];
-        face_cross(t, c);
-        const float r2 = c[0] * c[0] + c[1] * c[1] + c[2] * c[2] + kNormalEps, r = 1.0f / sqrtf(r2);
-        const float G[3] = {accf[0] * w, accf[1] * w, accf[2] * w};
-        const float cg = (c[0] * G[0] + c[1] * G[1] + c[2] * G[2]) * r * r * r;          // n = c r:  dL/dc = G r - c (c.G) r^3
-        const float dc[3] = {G[0] * r - c[0] * cg, G[1] * r - c[1] * cg, G[2] * r - c[2] * cg};
-        const float e1[3] = {t[3] - t[0], t[4] - t[1], t[5] - t[2]}, e2[3] = {t[6] - t[0], t[7] - t[1], t[8] - t[2]};
-        // c = e1 x e2:  dL/de1 = e2 x dc,  dL/de2 = dc x e1
-        const float d1[3] = {e2[1] * dc[2] - e2[2] * dc[1], e2[2] * dc[0] - e2[0] * dc[2], e2[0] * dc[1] - e2[1] * dc[0]};
-        const float d2[3] = {dc[1] * e1[2] - dc[2] * e1[1], dc[2] * e1[0] - dc[0] * e1[2], dc[0] * e1[1] - dc[1] * e1[0]};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { g[k] = -(d1[k] + d2[k]); g[3 + k] = d1[k]; g[6 + k] = d2[k]; }
-    }
-    float *gb = gtri + ((size_t)b * Fmax + f) * 9;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) gb[k] = g[k];
-}
 
 // ---------------------------------------------------------------------------- A9 point -> triangle distance
 __device__ __forceinline__ float divide_non_zero(float a)
@@ -1519,13 +442,8 @@ __device__ __forceinline__ void tri_query_chunk(int W, int part, float (*s_lb)[6
     // LDS, as a packed (value, index) word under atomicMin: a wave that only sees far rows prunes with what the wave on the
     // near rows has found.  Any published word is the value of an evaluated face, so pruning against it is as valid as
     // against the wave's own best, whenever it arrives; the final minimum does not depend on the timing.
-    auto pack = [](float d, int f) { return ((unsigned long long)(unsigned)__float_as_int(d) << 32) | (unsigned)f; };
-    auto publish = [&]() { atomicMin(&s_best[lane], pack(min_d, min_idx)); };
-    auto refresh = [&]() {
-        const unsigned long long v = s_best[lane];
-        min_d = __int_as_float((int)(v >> 32));
-        min_idx = (int)(unsigned)v;
-    };
+    auto publish = [&]() { atomicMin(&s_best[lane], pack_best(min_d, min_idx)); };
+    auto refresh = [&]() { unpack_best(s_best[lane], min_d, min_idx); };
     // wave-uniform evaluation (the wide list): every lane evaluates the broadcast face, with the plane-offset vote
     auto eval = [&](int f, const float *fc) {
         float dis;
@@ -1593,7 +511,7 @@ __device__ __forceinline__ void tri_query_chunk(int W, int part, float (*s_lb)[6
 #pragma unroll
                     for (int j = 0; j < 9; ++j) fc[j] = src[j];
                     const float dis = min_triangle_distance<false>(fc, fc + 3, fc + 6, pp, ret, ip, 10000.0f);
-                    atomicMin(&s_best[pl], pack(dis, f));           // lexicographic (value, index): values are >= +0, NaN packs above all
+                    atomicMin(&s_best[pl], pack_best(dis, f));           // lexicographic (value, index): values are >= +0, NaN packs above all
                 }
             }
             __builtin_amdgcn_wave_barrier();
@@ -1730,7 +648,7 @@ __device__ __forceinline__ void tri_query_chunk(int W, int part, float (*s_lb)[6
             return;
         }
     }
-    if (part == 0) s_best[lane] = pack(10000.0f, -1);               // for.cu:277
+    if (part == 0) s_best[lane] = pack_best(10000.0f, -1);              // for.cu:277
     __syncthreads();
     bool done = false;
     TRI_STAT(0, 1);                                                 // [0] wave-chunks that search
@@ -1889,15 +807,6 @@ struct TriLane {
         if (!min_triangle_distance_voted(fc, fc + 3, fc + 6, p, min_d, true, dis)) return;
         if (min_d > dis || (min_d == dis && f < min_idx)) { min_d = dis; min_idx = f; }   // lexicographic (value, index)
     }
-    __device__ __forceinline__ unsigned long long packed() const
-    {
-        return ((unsigned long long)(unsigned)__float_as_int(min_d) << 32) | (unsigned)min_idx;   // index -1 is the largest
-    }
-    __device__ __forceinline__ void unpack(unsigned long long v)
-    {
-        min_d = __int_as_float((int)(v >> 32));
-        min_idx = (int)(unsigned)v;
-    }
     // entries [s, e) of a face list: 64 per round trip, lane k loads face k, the wave evaluates them one by one
     template <bool DEDUPE>
     __device__ __forceinline__ void run(const float *__restrict__ face, const int *__restrict__ lst, int s, int e, unsigned *bits, int lane)
@@ -1923,17 +832,6 @@ struct TriLane {
                 eval(__builtin_amdgcn_readlane(fm, k), fc);
             }
         }
-    }
-    template <int W>
-    __device__ __forceinline__ void share(unsigned long long (*s_pack)[64], int part, int lane)
-    {
-        s_pack[part][lane] = packed();
-        __syncthreads();
-        unsigned long long v = s_pack[0][lane];
-#pragma unroll
-        for (int w = 1; w < W; ++w) v = min(v, s_pack[w][lane]);
-        unpack(v);
-        __syncthreads();
     }
 };
 
@@ -2004,8 +902,8 @@ __global__ __launch_bounds__(kTriWaves * 64) void k_tri_far_bound(const float *_
                     L.eval(r[k], fc);
                 }
             }
-    L.share<kTriWaves>(s_pack, part, lane);
-    if (part == 0 && i < n) bound[i] = L.packed();
+    share_best<kTriWaves>(s_pack, part, lane, L.min_d, L.min_idx);     // (index -1 is the largest)
+    if (part == 0 && i < n) bound[i] = pack_best(L.min_d, L.min_idx);
 }
 
 __global__ __launch_bounds__(kTriWaves * 64) void k_tri_far_rows(const float *__restrict__ pts, const float *__restrict__ face,
@@ -2035,16 +933,11 @@ __global__ __launch_bounds__(kTriWaves * 64) void k_tri_far_rows(const float *__
     }
     TriLane L;
     L.p[0] = pts[q * 3]; L.p[1] = pts[q * 3 + 1]; L.p[2] = pts[q * 3 + 2];
-    L.unpack(bound[ii]);                                           // as k_tri_far_bound left it (other slices may have improved it)
-    auto slab = [&](int k, int c) -> float {                        // distance to the slab of cell layer c on axis k
-        if (!(g.cs[k] < INFINITY)) return 0.f;
-        const float l = g.o[k] + (float)c * g.cs[k] - g.slack[k], h = g.o[k] + (float)(c + 1) * g.cs[k] + g.slack[k];
-        return fmaxf(fmaxf(l - L.p[k], L.p[k] - h), 0.f);
-    };
+    unpack_best(bound[ii], L.min_d, L.min_idx);                    // as k_tri_far_bound left it (other slices may have improved it)
     const int rows = g.g[1] * g.g[2];
     for (int r = blockIdx.y * kTriWaves + part; r < rows; r += kTriWaves * kTriSlices) {
         const int cy = r % g.g[1], cz = r / g.g[1];
-        const float dy = slab(1, cy), dz = slab(2, cz);
+        const float dy = slab_dist(g, 1, cy, L.p[1]), dz = slab_dist(g, 2, cz, L.p[2]);
         // a cell at distance d is out of reach when 0.9998 d^2 - abs_slack > best (k_tri_query_coop); 0.9997 covers the
         // rounding of this test itself
         const float rem = (L.min_d + g.abs_slack) * (1.0f / 0.9997f) - dy * dy - dz * dz;
@@ -2066,8 +959,8 @@ __global__ __launch_bounds__(kTriWaves * 64) void k_tri_far_rows(const float *__
         if (dedupe) L.run<true>(face, list, s, e, bits, lane);
         else L.run<false>(face, list, s, e, bits, lane);
     }
-    L.share<kTriWaves>(s_pack, part, lane);
-    if (part == 0 && i < n) atomicMin(&bound[i], L.packed());
+    share_best<kTriWaves>(s_pack, part, lane, L.min_d, L.min_idx);
+    if (part == 0 && i < n) atomicMin(&bound[i], pack_best(L.min_d, L.min_idx));
 }
 
 __global__ __launch_bounds__(256) void k_tri_far_final(const unsigned long long *__restrict__ bound, const int *__restrict__ nFar,
@@ -2286,295 +1179,6 @@ extern "C" int deftet_debug_tri_stats(unsigned long long *out16, int reset)
     return 0;
 }
 #endif
-
-static int nn_pick_G(int M)
-{
-    // 1.5x the cells per axis that ~4 points per cell of a VOLUME-filling cloud would give (round 2): the clouds of this
-    // operator are surface samples, which leaves ~10 points in an occupied cell (round 2: ~35, and the 3x3x3 neighbourhood
-    // every query scans first held ~300 points).  Measured on the geometry step (8 x 97 k points, 8 x 80 k queries):
-    // 3.49 / 3.32 / 3.27 / 3.22 ms per step at 1 / 1.4 / 1.8 / 2.4 x; a single shape (one call, 80 k queries) 0.32 / 0.29 /
-    // 0.41 / 0.39 ms — finer grids cost a lone call more in rows visited per query than they save in points per row.
-    int G = (int)llround(1.5 * cbrt((double)(M > 0 ? M : 1) / 4.0));
-    if (G < 1) G = 1;
-    if (G > 160) G = 160;
-    return G;
-}
-
-// The grid search's workspace for a launch group of nS shapes: one slice of per-shape scratch per shape (the members point into
-// slice 0; the kernels rebase to their shape by `slice` bytes), and behind the slices the far keys / sorted keys / iota / sorted
-// positions of ALL shapes of the group with the sort's temporary.
-struct NNLayout {
-    size_t slice, bytes, sortTmpBytes;
-    float *part;
-    NNGrid *grid;
-    int *cells, *start, *rep;
-    int2 *pcell;
-    float4 *sorted, *repList;
-    int *rowStart, *nRep;
-    unsigned long long *bound;
-    int *nFar;
-    unsigned *farKey, *farKeyS, *iota, *farList;
-    void *sortTmp;
-};
-static NNLayout nn_layout(int nS, int N, int M, void *ws)
-{
-    NNLayout L{};
-    const int G = nn_pick_G(M);
-    const size_t nc = (size_t)G * G * G + 1, Nn = (size_t)(N > 0 ? N : 0), Mn = (size_t)(M > 0 ? M : 0);
-    Arena A(ws);
-    L.part = A.take<float>(kNNBlocks * 6);
-    L.grid = A.take<NNGrid>(1);
-    L.cells = A.take<int>(nc); L.start = A.take<int>(nc); L.rep = A.take<int>(nc);
-    L.pcell = A.take<int2>(Mn);
-    L.sorted = A.take<float4>(Mn + 64);                                               // k_nn_far reads whole 64-record tiles
-    L.repList = A.take<float4>(nc / (kNNCoarse * kNNCoarse) + 64 + 64);               // >= Gc^3 + pad
-    L.rowStart = A.take<int>((size_t)G * G + 2 * kNNBatch); L.nRep = A.take<int>(4);
-    L.bound = A.take<unsigned long long>(Nn + 1);
-    L.nFar = A.take<int>(4);
-    L.slice = A.end();
-    const size_t nAll = (size_t)nS * (Nn + 1);
-    Arena T(static_cast<char *>(ws) + L.slice * nS);
-    L.farKey = T.take<unsigned>(nAll); L.farKeyS = T.take<unsigned>(nAll); L.iota = T.take<unsigned>(nAll); L.farList = T.take<unsigned>(nAll);
-    L.sortTmpBytes = prims::radix_sort_temp_bytes<unsigned, unsigned>(nAll);
-    L.sortTmp = T.take<char>(L.sortTmpBytes);
-    L.bytes = L.slice * nS + T.end();
-    return L;
-}
-static int group_shapes(int B) { return B < 1 ? 1 : (B < kBatchShapes ? B : kBatchShapes); }      // the largest launch group of B shapes
-extern "C" size_t deftet_nn_index_workspace_bytes(int B, int N, int M) { return nn_layout(group_shapes(B), N, M, nullptr).bytes; }
-
-__global__ __launch_bounds__(256) void k_iota(unsigned *v, long long n)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) v[i] = (unsigned)i;
-}
-
-// the grid search for a GROUP of nS <= kBatchShapes shapes: one launch per kernel for the whole group
-static int nn_group(const float *queries, const float *points, int32_t *result, int nS, int N, int M, const ShapeCounts &cnt, void *ws,
-                    hipStream_t st)
-{
-    const int G = nn_pick_G(M), keyBits = nn_far_key_bits(G);
-    const size_t nc = (size_t)G * G * G + 1;
-    int nmax = 0;
-    for (int i = 0; i < nS; ++i) nmax = std::max(nmax, cnt.n[i]);
-    if (nmax == 0) return DEFTET_OK;
-    const NNLayout L = nn_layout(nS, N, M, ws);                       // at most what nn_index_impl checked: a group is no larger than the largest
-    const size_t slice = L.slice;
-    const int Nst = N + 1;
-    const size_t nAll = (size_t)nS * Nst;
-    const unsigned shapeShift = (unsigned)keyBits + 1;
-    const dim3 blk(256);
-    DEFTET_LAUNCH(k_nn_bbox, dim3(kNNBlocks, nS), blk, st, points, M, L.part, slice, L.cells, L.rep, L.nRep, (int)nc);
-    DEFTET_LAUNCH(k_nn_grid, dim3(nS), dim3(64), st, (const float *)L.part, G, L.grid, slice);
-    DEFTET_LAUNCH(k_nn_bin, dim3((M + 255) / 256, nS), blk, st, points, M, (const NNGrid *)L.grid, L.cells, L.pcell, L.rep, slice);
-    DEFTET_LAUNCH(k_scan_excl, dim3(scan_tiles(nc), nS), dim3(kScanThreads), st, (const int *)L.cells, L.start, (int)nc, slice, 0);
-    DEFTET_LAUNCH(k_nn_scatter, dim3((M + 255) / 256, nS), blk, st, points, M, (const int2 *)L.pcell, (const int *)L.start, L.sorted, slice);
-    DEFTET_LAUNCH(k_nn_query, dim3((Nst + 255) / 256, nS), blk, st, queries, N, (const NNGrid *)L.grid, (const int *)L.start,
-                  (const float4 *)L.sorted, (const int *)L.rep, points, M, result, L.farKey, 1u << keyBits, slice, cnt, Nst, shapeShift);
-    DEFTET_LAUNCH(k_iota, dim3((unsigned)((nAll + 255) / 256)), blk, st, L.iota, (long long)nAll);
-    int shapeBitsN = 0;
-    while ((1 << shapeBitsN) < nS) ++shapeBitsN;
-    {
-        const int rc = prims::radix_sort<unsigned, unsigned>(L.farKey, L.farKeyS, L.iota, reinterpret_cast<unsigned *>(L.farList), nAll,
-                                                             keyBits + 1 + shapeBitsN, L.sortTmp, L.sortTmpBytes, st);
-        if (rc != DEFTET_OK) return rc;
-    }
-    const int Gc = (G + kNNCoarse - 1) / kNNCoarse, Gc3 = Gc * Gc * Gc, nt = std::max(Gc3, G * G + 2 * kNNBatch);
-    DEFTET_LAUNCH(k_nn_far_tables, dim3((nt + 255) / 256, nS), blk, st, (const int *)L.rep, points, Gc3, (const int *)L.start, G, L.repList, L.nRep,
-                  L.rowStart, L.sorted, slice, M);
-    DEFTET_LAUNCH(k_nn_far_pad, dim3(nS), dim3(64), st, L.repList, (const int *)L.nRep, slice);
-    DEFTET_LAUNCH(k_nn_far_bound, dim3((nmax + 63) / 64, nS), dim3(kFarWaves * 64), st, queries, (const NNGrid *)L.grid, (const int *)L.start,
-                  (const float4 *)L.sorted, (const float4 *)L.repList, (const int *)L.nRep, points, N, (const unsigned *)L.farKeyS,
-                  (const unsigned *)L.farList, L.bound, L.nFar, 1u << keyBits, slice, M, Nst, shapeShift);
-    DEFTET_LAUNCH(k_nn_far_rows, dim3((nmax + 63) / 64, kFarSlices, nS), dim3(kFarWaves * 64), st, queries, (const NNGrid *)L.grid,
-                  (const int *)L.start, (const float4 *)L.sorted, (const int *)L.rowStart, (const int *)L.nFar, (const unsigned *)L.farList, L.bound, slice,
-                  N, Nst);
-    DEFTET_LAUNCH(k_nn_far_final, dim3((nmax + 255) / 256, nS), blk, st, (const unsigned long long *)L.bound, (const int *)L.nFar,
-                  (const unsigned *)L.farList, result, slice, N, Nst);
-    return DEFTET_OK;
-}
-
-// n_query_host == NULL: every shape has N queries.  Otherwise shape b has n_query_host[b] <= N queries (rows beyond
-// that are left untouched); the counts are HOST integers (the caller knows its face counts), strides stay N.
-static int nn_index_impl(const float *queries, const float *points, int32_t *result, int B, int N, int M, const int *n_query_host,
-                         void *workspace, size_t wsb, void *stream_)
-{
-    DEFTET_CHECK_ARG(B >= 0 && N >= 0 && M >= 0 && B <= 65535, "bad size");
-    if (B == 0 || N == 0) return DEFTET_OK;
-    DEFTET_CHECK_ARG(queries && result && (M == 0 || points), "null pointer");
-    DEFTET_CHECK_ARG((long long)M * 3 < 2147483647LL && (long long)N * 3 < 2147483647LL, "too many points per shape");
-    if (n_query_host)
-        for (int b = 0; b < B; ++b) DEFTET_CHECK_ARG(n_query_host[b] >= 0 && n_query_host[b] <= N, "n_query[%d]=%d outside [0,%d]", b, n_query_host[b], N);
-    hipStream_t st = as_stream(stream_);
-    if (!workspace || M == 0) {
-        if (!n_query_host) {
-            DEFTET_LAUNCH(k_nn, dim3((N + 255) / 256, B), dim3(256), st, queries, points, N, M, result);
-        } else {
-            for (int b = 0; b < B; ++b)
-                if (n_query_host[b] > 0)
-                    DEFTET_LAUNCH(k_nn, dim3((n_query_host[b] + 255) / 256, 1), dim3(256), st, queries + (size_t)b * N * 3, points + (size_t)b * M * 3,
-                                  n_query_host[b], M, result + (size_t)b * N);
-        }
-        return DEFTET_OK;
-    }
-    DEFTET_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && nn_layout(group_shapes(B), N, M, workspace).bytes <= wsb,
-                     "workspace misaligned or too small");
-    for (int b0 = 0; b0 < B; b0 += kBatchShapes) {                   // groups of kBatchShapes shapes reuse the workspace (stream order)
-        const int nS = std::min(kBatchShapes, B - b0);
-        ShapeCounts cnt{};
-        for (int i = 0; i < nS; ++i) cnt.n[i] = n_query_host ? n_query_host[b0 + i] : N;
-        const int rc = nn_group(queries + (size_t)b0 * N * 3, points + (size_t)b0 * M * 3, result + (size_t)b0 * N, nS, N, M, cnt, workspace,
-                                st);
-        if (rc != DEFTET_OK) return rc;
-    }
-    return DEFTET_OK;
-}
-
-// workspace == NULL: the scalar-stream brute force; otherwise the grid search (both exact).
-extern "C" int deftet_nn_index_f32(const float *queries, const float *points, int32_t *result, int B, int N, int M,
-                                   void *workspace, size_t wsb, void *stream_)
-{
-    return nn_index_impl(queries, points, result, B, N, M, nullptr, workspace, wsb, stream_);
-}
-
-extern "C" int deftet_nn_index_ragged_f32(const float *queries, const float *points, int32_t *result, int B, int N_max, int M,
-                                          const int *n_query_host, void *workspace, size_t wsb, void *stream_)
-{
-    DEFTET_CHECK_ARG(n_query_host || B == 0, "null n_query_host");
-    return nn_index_impl(queries, points, result, B, N_max, M, n_query_host, workspace, wsb, stream_);
-}
-
-static u32 a8_table_mask(int F)
-{
-    u32 n = 64;
-    while (n < (u32)(F > 0 ? F : 0) * 6u) n <<= 1;                   // >= 2 slots per edge record
-    return n - 1;
-}
-// the edge hash of every shape: chain heads per table slot, the next record per edge record (three per face)
-struct A8Layout {
-    size_t bytes;
-    int *head, *next;
-};
-static A8Layout a8_layout(int B, int F_max, void *ws)
-{
-    A8Layout L{};
-    const size_t b = (size_t)(B > 0 ? B : 0);
-    Arena A(ws);
-    L.head = A.take<int>(b * ((size_t)a8_table_mask(F_max) + 1));
-    L.next = A.take<int>(b * (size_t)(F_max > 0 ? F_max : 0) * 3);
-    L.bytes = A.end();
-    return L;
-}
-extern "C" size_t deftet_face_edge_adj_workspace_bytes(int F) { return a8_layout(1, F, nullptr).bytes; }
-extern "C" size_t deftet_face_edge_adj_ragged_workspace_bytes(int B, int F_max) { return a8_layout(B, F_max, nullptr).bytes; }
-
-// A8 for a batch of surfaces with different face counts: face f32 [B, F_max, 3, 3], adj f32 [B, F_max, max_nei] (pre-filled
-// with -1 by the caller), shape b has n_face_host[b] <= F_max faces (HOST integers); neighbour indices are local to the
-// shape.  workspace == NULL (or max_nei > 32): the O(F^2) scan per shape; otherwise three launches per 32 shapes.
-extern "C" int deftet_face_edge_adj_ragged_f32(const float *face, float *adj, int B, int F_max, const int *n_face_host, int max_nei,
-                                               void *workspace, size_t wsb, void *stream_)
-{
-    DEFTET_CHECK_ARG(B >= 0 && F_max >= 0 && max_nei >= 0 && B <= 65535, "bad size");
-    if (F_max >= (1 << 24)) return set_error(DEFTET_ELIMIT, "n_face=%d does not fit a float-encoded index", F_max);
-    if (B == 0 || F_max == 0 || max_nei == 0) return DEFTET_OK;
-    DEFTET_CHECK_ARG(face && adj && n_face_host, "null pointer");
-    for (int b = 0; b < B; ++b) DEFTET_CHECK_ARG(n_face_host[b] >= 0 && n_face_host[b] <= F_max, "n_face[%d]=%d outside [0,%d]", b, n_face_host[b], F_max);
-    hipStream_t st = as_stream(stream_);
-    if (!workspace || max_nei > kMaxNeiFast) {
-        for (int b = 0; b < B; ++b)
-            if (n_face_host[b] > 0)
-                DEFTET_LAUNCH(k_face_edge_adj, dim3((n_face_host[b] + 255) / 256), dim3(256), st, face + (size_t)b * F_max * 9,
-                              adj + (size_t)b * F_max * max_nei, n_face_host[b], max_nei);
-        return DEFTET_OK;
-    }
-    const A8Layout L = a8_layout(B, F_max, workspace);
-    DEFTET_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && L.bytes <= wsb, "workspace misaligned or too small");
-    const u32 mask = a8_table_mask(F_max);
-    DEFTET_HIP(hipMemsetAsync(L.head, 0xFF, (size_t)B * (mask + 1) * 4, st));   // -1 = empty chain
-    for (int b0 = 0; b0 < B; b0 += kA8Shapes) {
-        const int nb = std::min(kA8Shapes, B - b0);
-        A8Counts cnt{};
-        int fmax = 0;
-        for (int i = 0; i < nb; ++i) { cnt.n[i] = n_face_host[b0 + i]; fmax = std::max(fmax, cnt.n[i]); }
-        if (fmax == 0) continue;
-        const float *fb = face + (size_t)b0 * F_max * 9;
-        DEFTET_LAUNCH(k_edge_insert, dim3((fmax * 3 + 255) / 256, nb), dim3(256), st, fb, F_max, cnt, mask, L.head + (size_t)b0 * (mask + 1),
-                      L.next + (size_t)b0 * F_max * 3);
-        DEFTET_LAUNCH(k_face_neighbors, dim3((fmax + 255) / 256, nb), dim3(256), st, fb, F_max, cnt, mask,
-                      (const int *)(L.head + (size_t)b0 * (mask + 1)), (const int *)(L.next + (size_t)b0 * F_max * 3),
-                      adj + (size_t)b0 * F_max * max_nei, max_nei);
-    }
-    return DEFTET_OK;
-}
-
-// workspace == NULL (or max_nei > 32): the scalar-stream brute force; otherwise the hash-based path.
-extern "C" int deftet_face_edge_adj_f32(const float *face, float *adj, int F, int max_nei, void *workspace, size_t wsb,
-                                        void *stream_)
-{
-    DEFTET_CHECK_ARG(F >= 0 && max_nei >= 0, "negative size");
-    return deftet_face_edge_adj_ragged_f32(face, adj, 1, F, &F, max_nei, workspace, wsb, stream_);
-}
-
-// Normal consistency of B surfaces on their A8 tables (see k_normal_consistency_fwd).  tri f32 [B,F_max,3,3], adj f32
-// [B,F_max,max_nei] (-1 padded, indices local to the shape), n_face int32 [B] ON THE DEVICE; loss f32 [B];
-// nrm f32 [B,F_max,3] and count f32 [B] are saved for the backward.  grad_tri f32 [B,F_max,3,3] is fully overwritten
-// (zeros for the padding faces); acc f32 [B,F_max,3] is scratch.
-extern "C" int deftet_normal_consistency_fwd_f32(const float *tri, const float *adj, const int32_t *n_face, float *loss, float *nrm,
-                                                 float *count, int B, int F_max, int max_nei, void *stream_)
-{
-    DEFTET_CHECK_ARG(B >= 0 && F_max >= 0 && max_nei >= 0, "bad size");
-    if (B == 0) return DEFTET_OK;
-    DEFTET_CHECK_ARG(loss && count && n_face && (F_max == 0 || (tri && nrm)) && (F_max == 0 || max_nei == 0 || adj), "null pointer");
-    DEFTET_LAUNCH(k_normal_consistency_fwd, dim3(B), dim3(kNCThreads), as_stream(stream_), tri, adj, n_face, loss, nrm, count, F_max, max_nei);
-    return DEFTET_OK;
-}
-
-extern "C" int deftet_normal_consistency_bwd_f32(const float *tri, const float *adj, const int32_t *n_face, const float *nrm,
-                                                 const float *count, const float *grad_loss, float *grad_tri, float *acc, int B,
-                                                 int F_max, int max_nei, void *stream_)
-{
-    DEFTET_CHECK_ARG(B >= 0 && F_max >= 0 && max_nei >= 0 && B <= 65535, "bad size");
-    if (B == 0 || F_max == 0) return DEFTET_OK;
-    DEFTET_CHECK_ARG(tri && n_face && nrm && count && grad_loss && grad_tri && acc && (max_nei == 0 || adj), "null pointer");
-    hipStream_t st = as_stream(stream_);
-    DEFTET_HIP(hipMemsetAsync(acc, 0, (size_t)B * F_max * 3 * sizeof(float), st));
-    DEFTET_LAUNCH(k_normal_consistency_bwd_scatter, dim3((F_max + 255) / 256, B), dim3(256), st, adj, n_face, nrm, acc, F_max, max_nei);
-    DEFTET_LAUNCH(k_normal_consistency_bwd_final, dim3((F_max + 255) / 256, B), dim3(256), st, tri, n_face, count, grad_loss, (const float *)acc,
-                  grad_tri, F_max);
-    return DEFTET_OK;
-}
-
-extern "C" int deftet_face_samples_f32(const float *tri, const float *r, float *samples, int B, int F, int K, void *stream_)
-{
-    DEFTET_CHECK_ARG(B >= 0 && F >= 0 && K >= 1, "bad size");
-    const long long total = (long long)B * F * K;
-    if (total == 0) return DEFTET_OK;
-    DEFTET_CHECK_ARG(tri && r && samples, "null pointer");
-    DEFTET_CHECK_ARG(total * 3 < (1LL << 40), "too many samples");
-    DEFTET_LAUNCH(k_face_samples, dim3((unsigned)((total + 255) / 256)), dim3(256), as_stream(stream_), tri, r, samples, K, total);
-    return DEFTET_OK;
-}
-
-extern "C" int deftet_chamfer_fwd_f32(const float *samples, const float *gt, const int32_t *idx, const int32_t *n_valid, float *d, int B,
-                                      int N, int M, void *stream_)
-{
-    DEFTET_CHECK_ARG(B >= 0 && N >= 0 && M >= 1 && B <= 65535, "bad size");
-    if (B == 0 || N == 0) return DEFTET_OK;
-    DEFTET_CHECK_ARG(samples && gt && idx && n_valid && d, "null pointer");
-    DEFTET_LAUNCH(k_chamfer_fwd, dim3((N + 255) / 256, B), dim3(256), as_stream(stream_), samples, gt, idx, n_valid, d, N, M);
-    return DEFTET_OK;
-}
-
-extern "C" int deftet_chamfer_bwd_f32(const float *samples, const float *gt, const int32_t *idx, const int32_t *n_valid, const float *d,
-                                      const float *r, const float *gscale, float *grad_tri, int B, int F, int K, int M, void *stream_)
-{
-    DEFTET_CHECK_ARG(B >= 0 && F >= 0 && K >= 1 && M >= 1 && B <= 65535, "bad size");
-    if (B == 0 || F == 0) return DEFTET_OK;
-    DEFTET_CHECK_ARG(samples && gt && idx && n_valid && d && r && gscale && grad_tri, "null pointer");
-    DEFTET_LAUNCH(k_chamfer_bwd, dim3((F + 255) / 256, B), dim3(256), as_stream(stream_), samples, gt, idx, n_valid, d, r, gscale, grad_tri, F, K,
-                  M, (long long)B * F * K);
-    return DEFTET_OK;
-}
 
 // the per-shape scratch slice of the grid search: ONE description of the layout, used for the size and for the pointers
 struct TriSlice {

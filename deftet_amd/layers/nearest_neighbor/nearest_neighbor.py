@@ -3,7 +3,7 @@
 Replaces layers/nearest_neighbor/nearest_neighbor.py:21-60 of the reference: `NearestNeighbor()(q, pts)` with
 q float [B, N, 3] and pts float [B, M, 3] gives int64 [B, N], the index of the nearest point of the same batch entry
 (lowest index on ties, as the reference kernel's strict `<` scan does).  The search itself is
-`deftet_nn_index_f32` (exact grid search, `deftet_amd/csrc/surface_ops.hip`).  Like the reference, the operator has no
+`deftet_nn_index_f32` (exact grid search, `deftet_amd/csrc/nearest_neighbor.hip`).  Like the reference, the operator has no
 gradient: asking for one raises NotImplementedError; malformed shapes fail an assertion.
 """
 import torch

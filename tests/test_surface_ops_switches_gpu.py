@@ -1,4 +1,4 @@
-"""The surface operators (deftet_amd/csrc/surface_ops.hip) past the switches that a size or a batch count selects and that
+"""The surface operators (deftet_amd/csrc/{nearest_neighbor,chamfer,face_adjacency,tri_distance}.hip) past the switches that a size or a batch count selects and that
 BASELINE (8 shapes, 4,056 faces, n_max_nei = 30) never reaches:
 
   A10 / A9   more than kBatchShapes = 8 shapes: the second and later launch groups reuse one workspace in stream order,
