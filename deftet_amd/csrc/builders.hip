@@ -17,6 +17,7 @@
 #include "common.hpp"
 
 #include "prims.hpp"
+#include "wave.hpp"
 
 namespace deftet {
 namespace bld {
@@ -433,8 +434,7 @@ __global__ __launch_bounds__(256) void k_adj_degree(const int *__restrict__ rowS
         d = rowStart[p + 1] - rowStart[p];
         adjsum[p] = (float)d;                                     // np.sum of a float32 0/1 row, :139
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) d = max(d, __shfl_xor(d, off));
+    d = wave_max(d);
     if ((threadIdx.x & 63) == 0 && d > 0) atomicMax(maxDeg, d);
 }
 

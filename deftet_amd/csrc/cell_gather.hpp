@@ -153,7 +153,7 @@ __global__ __launch_bounds__(kPvBlock) void k_cell_partials(const float *__restr
         for (int j = a0 + lane; j < a1; j += 64) add_point<NC>(s, wsorted, BN, j, g[perm[j]], keep, wk);
 #pragma unroll
         for (int k = 0; k < NC; ++k) {
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
             for (int off = 32; off >= 1; off >>= 1) s[k] = __fadd_rn(s[k], __shfl_xor(s[k], off));
             if (lane == src) acc[k] = s[k];
         }

@@ -61,6 +61,22 @@ void prof_end(hipStream_t st);
     } while (0)
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+inline bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }   // a: a power of two
+__device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7FC00000); }
+__device__ __forceinline__ void cross3(const float *a, const float *b, float *o)
+{
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+}
+__device__ __forceinline__ float dot3(const float *a, const float *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+// XCD-aware placement of a 1-D grid whose size is a MULTIPLE OF 8: workgroups go round-robin to the eight XCDs, so every XCD
+// takes one CONTIGUOUS share of the logical blocks and the rows that neighbouring ones share are fetched into one L2.  Speed only.
+__device__ __forceinline__ int xcd_logical_block() { return (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3); }
+// Keeps the RETURNING form of an atomic whose old value is not used: it is complete at the memory side once it has returned,
+// and that return is what the s_waitcnt of the ticket reductions observes before they draw their ticket.
+template <typename T>
+__device__ __forceinline__ void keep_returning(T old) { asm volatile("" ::"v"(old)); }
 
 // bump allocator over the caller's workspace.  Over a null base it only measures: a layout function runs once that way for the
 // *_workspace_bytes value and once over the real pointer for the arrays, so the two cannot disagree ("Workspaces").

@@ -58,7 +58,7 @@ __global__ __launch_bounds__(kThreads) void k_vx_frame(const float *__restrict__
             }
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-#pragma unroll
+#pragma unroll  // wave_min's and wave_max's order (wave.hpp); written out, a call changes this kernel's instruction stream
             for (int off = 32; off > 0; off >>= 1) {
                 mn[k] = fminf(mn[k], __shfl_xor(mn[k], off));
                 mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], off));

@@ -210,7 +210,7 @@ __device__ __forceinline__ void face_cross(const float *t, float *c)
 
 __device__ __forceinline__ float block_sum(float v, float *sh)
 {
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;

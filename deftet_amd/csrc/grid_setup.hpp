@@ -11,8 +11,8 @@
 // axis, the slack — differs per operator on purpose and feeds the certified bounds of DESIGN.md ("Grid set-up" lists the
 // differences); it stays with the operator.
 //
-// ORDER OF THE SUMS.  The sums decide cell counts, so their order is part of the result: a thread's own strided sum, the xor
-// butterfly from offset 32 down to 1, then waves 0, 1, 2, 3 one after the other.  min / max do not depend on the order.
+// ORDER OF THE SUMS.  The sums decide cell counts, so their order is part of the result: a thread's own strided sum, the wave
+// butterfly in wave.hpp's order (wave_sum), then waves 0, 1, 2, 3 one after the other.  min / max do not depend on the order.
 #pragma once
 #include "common.hpp"
 
@@ -51,7 +51,7 @@ struct BoxStats {
     }
     __device__ __forceinline__ void add_sum(int s, float v) { sum[s] += v; }
 
-    // every lane of the wave ends up with the wave's box and sums
+    // every lane ends up with the wave's box and sums (wave.hpp's order, written out: calls change the statistics kernels' streams)
     __device__ __forceinline__ void wave_reduce()
     {
 #pragma unroll

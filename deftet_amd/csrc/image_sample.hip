@@ -129,7 +129,7 @@ __global__ __launch_bounds__(kPvBlock) void k_is_rowsum(const float *__restrict_
     const float *src = gout + ((size_t)b * C_total + g) * N;
     float s = 0.0f;
     for (int n = lane; n < N; n += 64) s = __fadd_rn(s, src[n]);
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
     for (int off = 32; off >= 1; off >>= 1) s = __fadd_rn(s, __shfl_xor(s, off));
     if (lane == 0) gglob[row] = s;
 }

@@ -494,7 +494,7 @@ __global__ __launch_bounds__(256) void k_met_partial(const float *__restrict__ p
             v[9] = nanmax(v[9], sa);
             v[10] = nanmax(v[10], sb);
         }
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp) with nanmax beside it; written out, a call changes this kernel's instruction stream
     for (int off = 32; off > 0; off >>= 1) {
 #pragma unroll
         for (int i = 0; i < 9; ++i) v[i] += __shfl_xor(v[i], off);
@@ -520,7 +520,7 @@ __global__ __launch_bounds__(64) void k_met_final(const float *__restrict__ part
     float v[kMVals];
 #pragma unroll
     for (int i = 0; i < kMVals; ++i) v[i] = part[((size_t)b * kMParts + lane) * kMVals + i];
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp) with nanmax beside it; written out, a call changes this kernel's instruction stream
     for (int off = 32; off > 0; off >>= 1) {
 #pragma unroll
         for (int i = 0; i < 9; ++i) v[i] += __shfl_xor(v[i], off);
@@ -537,8 +537,6 @@ __global__ __launch_bounds__(64) void k_met_final(const float *__restrict__ part
         out[b * 5 + 4] = have_h ? (v[9] + v[10]) / 2.0f : NAN;
     }
 }
-
-inline bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 struct PMSlices {
     PGrid *grids; float *part; int *count, *start, *fill, *nWide, *wide, *list; void *scan_ws; size_t scan_bytes;
@@ -592,8 +590,8 @@ static int pm_check(const float *pts, const float *face, const int32_t *n_face, 
     DEFTET_CHECK_ARG(F <= (1 << 24) && (long long)B * F <= (1LL << 26) && P <= (1 << 28), "too many faces or points (B=%d, P=%d, F=%d)", B, P, F);
     if (B == 0 || P == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(pts && dist && face_idx && dist_type && (F == 0 || face), "null pointer");
-    DEFTET_CHECK_ARG(met::aligned(pts, 4) && met::aligned(face, 4) && met::aligned(n_face, 4) && met::aligned(dist, 4) &&
-                         met::aligned(face_idx, 8) && met::aligned(dist_type, 4),
+    DEFTET_CHECK_ARG(aligned(pts, 4) && aligned(face, 4) && aligned(n_face, 4) && aligned(dist, 4) &&
+                         aligned(face_idx, 8) && aligned(dist_type, 4),
                      "misaligned pointer");
     return DEFTET_OK;
 }
@@ -609,7 +607,7 @@ extern "C" int deftet_point_mesh_distance_f32(const float *pts, const float *fac
 {
     const int rc = pm_check(pts, face, n_face, B, P, F, dist, face_idx, dist_type);
     if (rc != DEFTET_OK || B == 0 || P == 0) return rc;
-    DEFTET_CHECK_ARG(workspace && met::aligned(workspace, 256) && workspace_bytes >= deftet_point_mesh_distance_workspace_bytes(B, P, F),
+    DEFTET_CHECK_ARG(workspace && aligned(workspace, 256) && workspace_bytes >= deftet_point_mesh_distance_workspace_bytes(B, P, F),
                      "workspace null, misaligned or too small");
     hipStream_t st = as_stream(stream_);
     met::PMSlices s;
@@ -656,11 +654,11 @@ extern "C" int deftet_sample_points_f32(const float *face, const float *areas, c
     DEFTET_CHECK_ARG(B >= 0 && F >= 0 && N >= 0 && B <= 65535 && (long long)B * F <= (1LL << 30), "bad size (B=%d, F=%d, N=%d)", B, F, N);
     if (B == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(empty_flag && (N == 0 || (uniforms && points && face_choice)) && (F == 0 || face), "null pointer");
-    DEFTET_CHECK_ARG(met::aligned(face, 4) && met::aligned(areas, 4) && met::aligned(n_face, 4) && met::aligned(uniforms, 4) &&
-                         met::aligned(points, 4) && met::aligned(face_choice, 8) && met::aligned(empty_flag, 4),
+    DEFTET_CHECK_ARG(aligned(face, 4) && aligned(areas, 4) && aligned(n_face, 4) && aligned(uniforms, 4) &&
+                         aligned(points, 4) && aligned(face_choice, 8) && aligned(empty_flag, 4),
                      "misaligned pointer");
     const met::SampLayout L = met::samp_layout(B, F, workspace);
-    DEFTET_CHECK_ARG(workspace && met::aligned(workspace, 256) && L.bytes <= workspace_bytes, "workspace null, misaligned or too small");
+    DEFTET_CHECK_ARG(workspace && aligned(workspace, 256) && L.bytes <= workspace_bytes, "workspace null, misaligned or too small");
     hipStream_t st = as_stream(stream_);
     const size_t n = (size_t)B * F;
     DEFTET_HIP(hipMemsetAsync(empty_flag, 0, (size_t)B * 4, st));
@@ -684,8 +682,8 @@ extern "C" int deftet_nn_distance_f32(const float *queries, const float *points,
     DEFTET_CHECK_ARG(B >= 0 && N >= 0 && M >= 0 && B <= 65535, "bad size (B=%d, N=%d, M=%d)", B, N, M);
     if (B == 0 || N == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(queries && idx && dist && (M == 0 || points), "null pointer");
-    DEFTET_CHECK_ARG(met::aligned(queries, 4) && met::aligned(points, 4) && met::aligned(idx, 4) && met::aligned(dist, 4) &&
-                         met::aligned(idx64, 8),
+    DEFTET_CHECK_ARG(aligned(queries, 4) && aligned(points, 4) && aligned(idx, 4) && aligned(dist, 4) &&
+                         aligned(idx64, 8),
                      "misaligned pointer");
     DEFTET_LAUNCH(met::k_nn_dist, dim3((N + 255) / 256, B), dim3(256), as_stream(stream_), queries, M > 0 ? points : queries,
                   (const int *)idx, N, M, dist, (long long *)idx64);
@@ -707,10 +705,10 @@ extern "C" int deftet_surface_metrics_f32(const float *p1, const float *p2, cons
     DEFTET_CHECK_ARG((dist_a == nullptr) == (dist_b == nullptr), "dist_a and dist_b: both or neither");
     if (B == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(p1 && p2 && idx12 && idx21 && out, "null pointer");
-    DEFTET_CHECK_ARG(met::aligned(p1, 4) && met::aligned(p2, 4) && met::aligned(idx12, 4) && met::aligned(idx21, 4) &&
-                         met::aligned(dist_a, 4) && met::aligned(dist_b, 4) && met::aligned(out, 4),
+    DEFTET_CHECK_ARG(aligned(p1, 4) && aligned(p2, 4) && aligned(idx12, 4) && aligned(idx21, 4) &&
+                         aligned(dist_a, 4) && aligned(dist_b, 4) && aligned(out, 4),
                      "misaligned pointer");
-    DEFTET_CHECK_ARG(workspace && met::aligned(workspace, 256) && workspace_bytes >= deftet_surface_metrics_workspace_bytes(B),
+    DEFTET_CHECK_ARG(workspace && aligned(workspace, 256) && workspace_bytes >= deftet_surface_metrics_workspace_bytes(B),
                      "workspace null, misaligned or too small");
     hipStream_t st = as_stream(stream_);
     float *part = static_cast<float *>(workspace);

@@ -503,7 +503,7 @@ __global__ __launch_bounds__(kFarWaves * 64) void k_nn_far_rows(const float *__r
                         int x0 = need ? grid_cell(L.qx - rx - g.slack[0], g.o[0], g.inv[0], G) : G - 1;
                         int x1 = need ? grid_cell(L.qx + rx + g.slack[0], g.o[0], g.inv[0], G) : 0;
                         if (need && !(rx < INFINITY)) { x0 = 0; x1 = G - 1; }
-#pragma unroll
+#pragma unroll  // wave_min's and wave_max's order (wave.hpp); written out, a call changes this kernel's instruction stream
                         for (int off = 32; off > 0; off >>= 1) {
                             x0 = min(x0, __shfl_xor(x0, off));
                             x1 = max(x1, __shfl_xor(x1, off));

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace deftet {
 namespace pit {
@@ -254,7 +255,7 @@ __device__ __forceinline__ void reduce_box(const float *__restrict__ part, int n
             hi[k] = fmaxf(hi[k], part[(size_t)i * 6 + 3 + k]);
         }
     }
-#pragma unroll
+#pragma unroll  // wave_min's and wave_max's order (wave.hpp); written out, a call changes this kernel's instruction stream
     for (int off = 32; off > 0; off >>= 1) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -393,7 +394,7 @@ __global__ __launch_bounds__(256) void k_query_bbox(const float *__restrict__ pt
                 hi[0] = fmaxf(hi[0], x[k]); hi[1] = fmaxf(hi[1], y[k]); hi[2] = fmaxf(hi[2], z[k]);
             }
     }
-#pragma unroll
+#pragma unroll  // wave_min's and wave_max's order (wave.hpp); written out, a call changes this kernel's instruction stream
     for (int off = 32; off > 0; off >>= 1) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -563,7 +564,7 @@ __global__ __launch_bounds__(kLocalThreads) void k_slab_local(const float *__res
         }
     }
     if (HINT) {                                                    // the chunk's box for the next call's hint
-#pragma unroll
+#pragma unroll  // wave_min's and wave_max's order (wave.hpp); written out, a call changes this kernel's instruction stream
         for (int off = 32; off > 0; off >>= 1) {
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
@@ -597,13 +598,8 @@ __global__ __launch_bounds__(kLocalThreads) void k_slab_local(const float *__res
             n[j] = (j < per && i0 + j < R1) ? hist[i0 + j] : 0;
             sum += n[j];
         }
-        int incl = sum;
         const int lane = tid & 63, w = tid >> 6;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(incl, off);
-            if (lane >= off) incl += t;
-        }
+        const int incl = wave_incl_sum(sum, lane);
         if (lane == 63) wtot[w] = incl;
         __syncthreads();
         int run = incl - sum;
@@ -722,7 +718,7 @@ __global__ __launch_bounds__(kSortThreads) void k_slab_sort(const float4 *__rest
     int s0, n;
     {
         int ia = asum, il = lsum;                                   // inclusive scans over the threads
-#pragma unroll
+#pragma unroll  // wave_incl's order (wave.hpp), two values interleaved; written out, calls change this kernel's instruction stream
         for (int off = 1; off < 64; off <<= 1) {
             const int ta = __shfl_up(ia, off), tl = __shfl_up(il, off);
             if (lane >= off) { ia += ta; il += tl; }
@@ -799,12 +795,7 @@ __global__ __launch_bounds__(kSortThreads) void k_slab_sort(const float4 *__rest
             const int4 v = c4[i];
             sum += (v.x + v.y) + (v.z + v.w);
         }
-        int incl = sum;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(incl, off);
-            if (lane >= off) incl += t;
-        }
+        const int incl = wave_incl_sum(sum, lane);
         __syncthreads();                                            // wsum is reused
         if (lane == 63) wsum[w] = incl;
         __syncthreads();
@@ -1151,21 +1142,6 @@ struct Filter {
     float twoEmax;
 };
 
-// Select with the lane mask in an SGPR pair (VOP3 v_cndmask_b32_e64).  hipcc likes to shrink selects whose mask sits in
-// VCC to the VOP2 form `v_cndmask_b32_e32 …, vcc`, which gfx950 issues ~7.5x slower than an FMA (9.4 vs 1.25 ns per
-// wave-instruction per SIMD, tools/probes/valu_rate_probe.hip; the SGPR-pair form: 1.85 ns).  The traversal loop carries
-// a dozen selects per iteration, so the form matters more than the count.
-typedef unsigned long long lanemask_t;
-__device__ __forceinline__ int sel(lanemask_t m, int if_set, int if_clear)
-{
-    int d;
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(d) : "v"(if_clear), "v"(if_set), "s"(m));
-    return d;
-}
-__device__ __forceinline__ unsigned sel(lanemask_t m, unsigned if_set, unsigned if_clear)
-{
-    return (unsigned)sel(m, (int)if_set, (int)if_clear);
-}
 __device__ __forceinline__ lanemask_t mask_of(bool c) { return __builtin_amdgcn_ballot_w64(c); }
 
 
@@ -1472,9 +1448,9 @@ __global__ __launch_bounds__(256, PIT_WAVES) void k_tet_scan_slab(typename C::TS
         if (c >= P4) {                                                  // enter the prefetched step, prefetch the one after it
             const int rem = ny - yoff;                                  // rows of this chunk: min(rem, 4)
             const int n0 = nE.x - nS.x;
-            const int n1 = sel(mask_of(rem > 1), nE.y - nS.y, 0);
-            const int n2 = sel(mask_of(rem > 2), nE.z - nS.z, 0);
-            const int n3 = sel(mask_of(rem > 3), nE.w - nS.w, 0);
+            const int n1 = lane_select(mask_of(rem > 1), nE.y - nS.y, 0);
+            const int n2 = lane_select(mask_of(rem > 2), nE.z - nS.z, 0);
+            const int n3 = lane_select(mask_of(rem > 3), nE.w - nS.w, 0);
             P1 = n0; P2 = P1 + n1; P3 = P2 + n2; P4 = P3 + n3;
             o0 = nS.x; o1 = nS.y - P1; o2 = nS.z - P2; o3 = nS.w - P3;
             c = 0;
@@ -1483,9 +1459,9 @@ __global__ __launch_bounds__(256, PIT_WAVES) void k_tet_scan_slab(typename C::TS
             // for the prefetch right after issuing it)
             asm volatile("" : "+v"(P1), "+v"(P2), "+v"(P3), "+v"(P4), "+v"(o0), "+v"(o1), "+v"(o2), "+v"(o3));
             const lanemask_t wrap = mask_of(rem <= 4);                  // last chunk of this cz
-            offS += sel(wrap, slabB - (unsigned)yoff * 4u, 16u);
-            yoff = sel(wrap, 0, yoff + 4);
-            cz += sel(wrap, 1, 0);
+            offS += lane_select(wrap, slabB - (unsigned)yoff * 4u, 16u);
+            yoff = lane_select(wrap, 0, yoff + 4);
+            cz += lane_select(wrap, 1, 0);
             haveNext = cz <= cz1;
             if (haveNext) {
                 nS = ld_off_u4(tb, offS);
@@ -1501,11 +1477,11 @@ __global__ __launch_bounds__(256, PIT_WAVES) void k_tet_scan_slab(typename C::TS
 #pragma unroll
             for (int k = 1; k < PIT_BATCH; ++k) {
                 live[k] = c + k < P4;
-                cc[k] = sel(mask_of(live[k]), c + k, c);
+                cc[k] = lane_select(mask_of(live[k]), c + k, c);
             }
 #pragma unroll
             for (int k = 0; k < PIT_BATCH; ++k) {
-                jq[k] = cc[k] + sel(mask_of(cc[k] < P1), o0, sel(mask_of(cc[k] < P2), o1, sel(mask_of(cc[k] < P3), o2, o3)));
+                jq[k] = cc[k] + lane_select(mask_of(cc[k] < P1), o0, lane_select(mask_of(cc[k] < P2), o1, lane_select(mask_of(cc[k] < P3), o2, o3)));
                 q[k] = ld_off<float4>(sq, (unsigned)jq[k] * 16u);
             }
             __builtin_amdgcn_sched_barrier(0);                         // all gathers in flight before the first filter value is needed
@@ -1524,10 +1500,10 @@ __global__ __launch_bounds__(256, PIT_WAVES) void k_tet_scan_slab(typename C::TS
 #pragma unroll
                 for (int k = 0; k < PIT_BATCH; ++k) {                          // remember the candidate; decided after the loop
                     const lanemask_t bd = mask_of(live[k] && fabsf(av[k]) <= F.twoEmax);
-                    pend1 = sel(bd, pend0, pend1);
-                    pend0 = sel(bd, jq[k], pend0);
-                    npend += sel(bd, 1, 0);
-                    av[k] = __int_as_float(sel(bd, __float_as_int(-1.0f), __float_as_int(av[k])));
+                    pend1 = lane_select(bd, pend0, pend1);
+                    pend0 = lane_select(bd, jq[k], pend0);
+                    npend += lane_select(bd, 1, 0);
+                    av[k] = __int_as_float(lane_select(bd, __float_as_int(-1.0f), __float_as_int(av[k])));
                 }
             }
             lanemask_t acc[PIT_BATCH];
@@ -1535,7 +1511,7 @@ __global__ __launch_bounds__(256, PIT_WAVES) void k_tet_scan_slab(typename C::TS
 #pragma unroll
             for (int k = 0; k < PIT_BATCH; ++k) {
                 acc[k] = mask_of(live[k] && av[k] > 0.f);
-                cnew += sel(acc[k], 1, 0);
+                cnew += lane_select(acc[k], 1, 0);
             }
             if (__builtin_amdgcn_ballot_w64(cnew > cap) != 0ull) {            // rare: more acceptances than the register holds
                 if (cnew > cap) {
@@ -1550,11 +1526,11 @@ __global__ __launch_bounds__(256, PIT_WAVES) void k_tet_scan_slab(typename C::TS
 #pragma unroll
             for (int k = 0; k < PIT_BATCH; ++k) {
                 const int qi = __float_as_int(q[k].w);
-                h3 = sel(acc[k], h2, h3);
-                h2 = sel(acc[k], h1, h2);
-                h1 = sel(acc[k], h0, h1);
-                h0 = sel(acc[k], qi, h0);
-                hcnt += sel(acc[k], 1, 0);
+                h3 = lane_select(acc[k], h2, h3);
+                h2 = lane_select(acc[k], h1, h2);
+                h1 = lane_select(acc[k], h0, h1);
+                h0 = lane_select(acc[k], qi, h0);
+                hcnt += lane_select(acc[k], 1, 0);
             }
             c += PIT_BATCH;
         }
@@ -1597,7 +1573,7 @@ __global__ __launch_bounds__(256, PIT_WAVES) void k_tet_scan_slab(typename C::TS
         // record (record and low half were written when the register spilled); 2: overflow marker
         if (full == 0) {
             const lanemask_t sp = mask_of(hcnt > 2);
-            store_b64_off(uniform_ptr(hits + (size_t)b * T), (unsigned)t * 8u, sel(sp, h0 | kHitSpilled, h0), h1);
+            store_b64_off(uniform_ptr(hits + (size_t)b * T), (unsigned)t * 8u, lane_select(sp, h0 | kHitSpilled, h0), h1);
             if (hcnt > 2) store_b128_off(uniform_ptr(spill + (size_t)b * T), (unsigned)t * 16u, h2, h3, -1, -1);
         } else if (full == 1) {                                          // (rare: one dword per held acceptance, behind the slots in use)
             int *sp = reinterpret_cast<int *>(spill + (size_t)b * T + t) + scnt;
@@ -1723,38 +1699,6 @@ struct __attribute__((aligned(16))) WaveStageT {       // one tet per lane: 2.8 
     marker_t marker[CAP];                               // row id + 1 at the LDS position where a non-empty row starts
 };
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp0(int v)             // lanes without a source (or masked rows) read 0
-{
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, true);
-}
-// inclusive scans over the 64 lanes (row_shr 1/2/4/8 inside rows of 16, then row_bcast 15 / 31)
-__device__ __forceinline__ int wave_scan_add(int x)
-{
-    x += dpp0<0x111, 0xf>(x); x += dpp0<0x112, 0xf>(x); x += dpp0<0x114, 0xf>(x); x += dpp0<0x118, 0xf>(x);
-    x += dpp0<0x142, 0xa>(x); x += dpp0<0x143, 0xc>(x);
-    return x;
-}
-__device__ __forceinline__ int wave_scan_max(int x)    // x >= 0
-{
-    x = max(x, dpp0<0x111, 0xf>(x)); x = max(x, dpp0<0x112, 0xf>(x)); x = max(x, dpp0<0x114, 0xf>(x)); x = max(x, dpp0<0x118, 0xf>(x));
-    x = max(x, dpp0<0x142, 0xa>(x)); x = max(x, dpp0<0x143, 0xc>(x));
-    return x;
-}
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pk_max(unsigned a, unsigned b)
-{
-    const u16x2 r = __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b));
-    return __builtin_bit_cast(unsigned, r);
-}
-// max of both 16-bit halves over all lanes (max is idempotent: the row masks of a scan are not needed); wave-uniform
-__device__ __forceinline__ unsigned wave_pk_max(unsigned v)
-{
-    v = pk_max(v, (unsigned)dpp0<0x111, 0xf>((int)v)); v = pk_max(v, (unsigned)dpp0<0x112, 0xf>((int)v));
-    v = pk_max(v, (unsigned)dpp0<0x114, 0xf>((int)v)); v = pk_max(v, (unsigned)dpp0<0x118, 0xf>((int)v));
-    v = pk_max(v, (unsigned)dpp0<0x142, 0xf>((int)v)); v = pk_max(v, (unsigned)dpp0<0x143, 0xf>((int)v));
-    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
 // wave-private LDS hand-off between lanes: DS operations of a wave execute in order, the fence keeps the compiler from
 // moving them
 __device__ __forceinline__ void wave_sync()
@@ -1767,10 +1711,6 @@ __device__ __forceinline__ void atomic_smin_off_nh(int *base, unsigned byte_off,
     asm volatile("global_atomic_smin %0, %1, %2" ::"v"(byte_off), "v"(v), "s"(base) : "memory");
 }
 
-__device__ __forceinline__ float sel(lanemask_t m, float if_set, float if_clear)
-{
-    return __int_as_float(sel(m, __float_as_int(if_set), __float_as_int(if_clear)));
-}
 __device__ __forceinline__ void cross_fma(float ax, float ay, float az, float bx, float by, float bz, float *n)
 {
     n[0] = fmaf(ay, bz, -(az * by));
@@ -2169,13 +2109,13 @@ __device__ __forceinline__ void tet_scan_wave_body(typename TS::Arg tet, int T, 
         const int nzA = gnz[0];
         const bool second = lane >= nzA, slabLane = lane < slabsTot;
         const lanemask_t m2 = mask_of(second);
-        const int zl = sel(m2, lane - nzA, lane), sh = sel(m2, gsh[1], gsh[0]), ny = sel(m2, gny[1], gny[0]);
-        const int rowId0 = sel(m2, rowOff1, 0) + (zl << sh);
+        const int zl = lane_select(m2, lane - nzA, lane), sh = lane_select(m2, gsh[1], gsh[0]), ny = lane_select(m2, gny[1], gny[0]);
+        const int rowId0 = lane_select(m2, rowOff1, 0) + (zl << sh);
         int a[4], len[4];
         {
-            const unsigned zrow = (unsigned)(sel(m2, gz0[1], gz0[0]) + (slabLane ? zl : 0)) * (unsigned)(Gx + 1);
-            const unsigned la = ((zrow + (unsigned)sel(m2, gx0[1], gx0[0])) * (unsigned)Gp + (unsigned)sel(m2, gy0[1], gy0[0])) * 4u;
-            const unsigned le = ((zrow + (unsigned)sel(m2, gx1[1], gx1[0]) + 1u) * (unsigned)Gp + (unsigned)sel(m2, gy0[1], gy0[0])) * 4u;
+            const unsigned zrow = (unsigned)(lane_select(m2, gz0[1], gz0[0]) + (slabLane ? zl : 0)) * (unsigned)(Gx + 1);
+            const unsigned la = ((zrow + (unsigned)lane_select(m2, gx0[1], gx0[0])) * (unsigned)Gp + (unsigned)lane_select(m2, gy0[1], gy0[0])) * 4u;
+            const unsigned le = ((zrow + (unsigned)lane_select(m2, gx1[1], gx1[0]) + 1u) * (unsigned)Gp + (unsigned)lane_select(m2, gy0[1], gy0[0])) * 4u;
             const int4u a0 = ld_off_u4(tb, la), e0 = ld_off_u4(tb, le);
             a[0] = a0.x; a[1] = a0.y; a[2] = a0.z; a[3] = a0.w;
             len[0] = e0.x - a0.x; len[1] = e0.y - a0.y; len[2] = e0.z - a0.z; len[3] = e0.w - a0.w;
@@ -2185,7 +2125,7 @@ __device__ __forceinline__ void tet_scan_wave_body(typename TS::Arg tet, int T, 
         int lmax = 0;
 #pragma unroll
         for (int y = 0; y < 4; ++y) {
-            len[y] = sel(mask_of(slabLane && y < ny), len[y], 0);
+            len[y] = lane_select(mask_of(slabLane && y < ny), len[y], 0);
             pre[y + 1] = pre[y] + len[y];
             lmax = max(lmax, len[y]);
         }
@@ -2213,9 +2153,9 @@ __device__ __forceinline__ void tet_scan_wave_body(typename TS::Arg tet, int T, 
         }
         PHASE_MARK(4);                                                   // [4] row bounds, scan
         // the lane's rows: the slabs [cz0, cz1] of its group's footprint, all of the footprint's y rows
-        // (sel: the SGPR-pair form of the select; written as ?: the compiler emits the VCC form, which gfx950 issues eight times slower)
+        // (lane_select: the SGPR-pair form of the select; written as ?: the compiler emits the VCC form, which gfx950 issues eight times slower)
         const lanemask_t mine2 = mask_of(gid == 1);
-        const int rowOff = sel(mine2, rowOff1, 0), gz = sel(mine2, gz0[1], gz0[0]), gs = sel(mine2, gsh[1], gsh[0]);
+        const int rowOff = lane_select(mine2, rowOff1, 0), gz = lane_select(mine2, gz0[1], gz0[0]), gs = lane_select(mine2, gsh[1], gsh[0]);
         int rn = rowOff + ((cz0 - gz) << gs);                          // next row to walk
         const int re = rowOff + ((cz1 + 1 - gz) << gs);
         if (!fitsRows) { REASON_COUNT(7, __builtin_amdgcn_ballot_w64(gid >= 0)); gid = -1; }
@@ -2659,13 +2599,6 @@ __global__ __launch_bounds__(256) void k_brute(const float *__restrict__ rec, co
 // ------------------------------------------------------------------------------------
 // A1b backward: dL/dtet = -w_k * G,  G = sum_i g_i * grad_p(w_i)   
 // ------------------------------------------------------------------------------------
-__device__ __forceinline__ void cross3(const float *a, const float *b, float *o)
-{
-    o[0] = a[1] * b[2] - a[2] * b[1];
-    o[1] = a[2] * b[0] - a[0] * b[2];
-    o[2] = a[0] * b[1] - a[1] * b[0];
-}
-
 template <class TS>
 __global__ __launch_bounds__(256) void k_bary_bwd(typename TS::Arg tet, const float *__restrict__ pts,
                                                   const float *__restrict__ cond, const float *__restrict__ grad_w, int T,
@@ -2753,7 +2686,7 @@ __global__ __launch_bounds__(256) void k_hit_link(const float *__restrict__ cond
     for (int k = 0; k < kLinkPer; ++k)
         if (tgt[k] >= 0) next[(size_t)b * Q + q0 + k * 256] = prev[k];
     if (gocc) {
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
         for (int off = 32; off > 0; off >>= 1) gm += __shfl_xor(gm, off);
         if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = gm;
         __syncthreads();
@@ -2886,7 +2819,7 @@ __device__ __forceinline__ float mem_read_f32(float *p) { return __int_as_float(
 __device__ __forceinline__ void mem_write_f32(float *p, float v)
 {
     const int old = atomicExch(reinterpret_cast<int *>(p), __float_as_int(v));
-    asm volatile("" ::"v"(old));                                   // keep the RETURNING form: its completion is what s_waitcnt observes
+    keep_returning(old);
 }
 
 constexpr int kMissStride = 80;    // floats of workspace per shape: kMissParts partials + the tet-0 lane's own sum
@@ -2942,7 +2875,7 @@ __device__ __forceinline__ bool bwd_rescan(typename TS::Arg tet, const float *__
                 if (mine) best = min(best, q);
                 if (count) m += __popcll(__ballot(mine));
             }
-#pragma unroll
+#pragma unroll  // wave_min's order (wave.hpp); written out, a call changes this kernel's instruction stream
             for (int off = 32; off > 0; off >>= 1) best = min(best, __shfl_xor(best, off));
             return best;
         };
@@ -2983,7 +2916,7 @@ __device__ __forceinline__ bool bwd_rescan(typename TS::Arg tet, const float *__
 #pragma unroll
             for (int k = 0; k < 13; ++k) {
                 float v = part[k];
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
                 for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);  // fixed tree; which lane holds which hit follows the list order
                 part[k] = v;
             }
@@ -3035,7 +2968,7 @@ __global__ __launch_bounds__(256, PIT_BWD_WAVES) void k_bary_bwd_hits(typename C
         float gm = 0.f;
         for (int q = bx * blockDim.x + tid; q < Q; q += nMissParts * blockDim.x)
             if (cond[(size_t)b * Q + q] < 0.f) gm += gocc[(size_t)b * Q + q];
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
         for (int off = 32; off > 0; off >>= 1) gm += __shfl_xor(gm, off);
         if (lane == 0) wsum[tid >> 6] = gm;
         __syncthreads();
@@ -3209,7 +3142,7 @@ __global__ __launch_bounds__(256) void k_paste_bwd(const float *__restrict__ con
     // summed across the wave first and sent as one atomic
     const bool miss = live && c < 1.0f;
     float gm = miss ? g : 0.f;
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
     for (int off = 32; off > 0; off >>= 1) gm += __shfl_xor(gm, off);
     __shared__ float wsum[4];
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = gm;

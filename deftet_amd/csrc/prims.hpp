@@ -21,6 +21,7 @@
 // radix_sort_temp_bytes<K, V>(n).
 #pragma once
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace deftet {
 namespace prims {
@@ -40,17 +41,6 @@ struct Max {
     template <typename T>
     __host__ __device__ T operator()(T a, T b) const { return a > b ? a : b; }
 };
-
-template <typename T, typename Op>
-__device__ __forceinline__ T wave_incl(T v, Op op, int lane)
-{
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const T t = __shfl_up(v, off);
-        if (lane >= off) v = op(v, t);
-    }
-    return v;
-}
 
 // tile totals: part[tile] = op over the tile's elements
 template <typename T, typename Op>
@@ -282,8 +272,8 @@ static __global__ __launch_bounds__(1024) void k_cs_spine(unsigned *part, unsign
     }
     unsigned incl = dtot;                                           // exclusive scan of the totals over the digits (every quarter
 #pragma unroll                                                      // computes it: waves 0-3 of a quarter hold digits 0-255)
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned t = __shfl_up(incl, off);
+    for (int off = 1; off < 64; off <<= 1) {                        // (wave_incl's order, wave.hpp; written out: a call changes
+        const unsigned t = __shfl_up(incl, off);                    // this kernel's instruction stream)
         if (lane >= (unsigned)off) incl += t;
     }
     if (q == 0 && lane == 63u) wtot[d >> 6] = incl;
@@ -371,7 +361,7 @@ __global__ __launch_bounds__(kTileThreads) void k_rs_scatter(KL kin, K *kout, VL
 #pragma unroll
         for (int k = 0; k < kTileThreads / 64; ++k) tot += cnt[k][d];
         unsigned incl = tot;
-#pragma unroll
+#pragma unroll  // wave_incl's order (wave.hpp); written out, a call changes this kernel's instruction stream
         for (int off = 1; off < 64; off <<= 1) {
             const unsigned t = __shfl_up(incl, off);
             if (lane >= off) incl += t;
@@ -397,7 +387,7 @@ __global__ __launch_bounds__(kTileThreads) void k_rs_scatter(KL kin, K *kout, VL
             }
             gincl = total;
 #pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
+            for (int off = 1; off < 64; off <<= 1) {                             // (written out, as above)
                 const unsigned t = __shfl_up(gincl, off);
                 if (lane >= off) gincl += t;
             }

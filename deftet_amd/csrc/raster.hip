@@ -29,6 +29,7 @@
 
 #include "grid_setup.hpp"
 #include "prims.hpp"
+#include "wave.hpp"
 
 namespace deftet {
 namespace rast {
@@ -70,7 +71,7 @@ __global__ __launch_bounds__(256) void k_face_stats(const float *__restrict__ xy
                               fmaxf(a.y, fmaxf(b.y, c.y)) - fminf(a.y, fminf(b.y, c.y)));
         if (w <= 2.f * kBig && w > 0.f) { sw += w; cnt += 1.f; }      // NaN fails
     }
-#pragma unroll
+#pragma unroll  // wave_sum's and wave_max's order (wave.hpp); written out, a call changes this kernel's instruction stream
     for (int off = 32; off > 0; off >>= 1) {
         sw += __shfl_xor(sw, off); cnt += __shfl_xor(cnt, off);
         zm = fmaxf(zm, __shfl_xor(zm, off));
@@ -96,10 +97,9 @@ __global__ __launch_bounds__(64) void k_pix_grid(const float *__restrict__ part,
     for (int i = lane; i < kBoxBlocks; i += 64) {                   // fixed order: the same tile grid on every run
         sw += fpart[i * 3]; cnt += fpart[i * 3 + 1]; zm = fmaxf(zm, fpart[i * 3 + 2]);
     }
-#pragma unroll
+#pragma unroll  // wave_sum's and wave_max's order (wave.hpp); written out, a call changes this kernel's instruction stream
     for (int off = 32; off > 0; off >>= 1) {
-        sw += __shfl_xor(sw, off);
-        cnt += __shfl_xor(cnt, off);
+        sw += __shfl_xor(sw, off); cnt += __shfl_xor(cnt, off);
         zm = fmaxf(zm, __shfl_xor(zm, off));
     }
     if (lane == 0) {
@@ -328,7 +328,6 @@ constexpr int kPendDepth = 4;          // admitted hits a full lane queues befor
 // `knum` hits and the wave stops when all its lanes are full.  NEAREST policy: the whole list is visited (from the end
 // whose faces are nearer); a full lane replaces its worst record (smallest z, then largest face index) by a better hit.
 // The chunk of NaN/Inf/huge pixels (pseudo-tile nTilesCap) visits every face.
-__device__ __forceinline__ float bcast(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
 
 // a after b in the output order (z descending, then face index ascending)
 __device__ __forceinline__ bool rast_worse(float za, int fa, float zb, int fb) { return za < zb || (za == zb && fa > fb); }
@@ -369,7 +368,7 @@ __device__ __noinline__ Worst rast_work_off(const int4 (*pend)[64], int npend, W
                 const int fi = i == atL ? newF : o.x;
                 if (wat < 0 || rast_worse(zi, fi, wz, wf)) { wz = zi; wf = fi; wat = i; }
             }
-#pragma unroll
+#pragma unroll  // wave_reduce's order (wave.hpp) on the (z, face, at) triple, its own combiner: stays written out
             for (int off = 32; off > 0; off >>= 1) {
                 const float oz = __shfl_xor(wz, off);
                 const int of = __shfl_xor(wf, off), oat = __shfl_xor(wat, off);
@@ -491,7 +490,7 @@ __global__ __launch_bounds__(256) void k_pix_raster(const float *__restrict__ pi
     // image-space box of this wave's pixels: a listed (regular) face whose enlarged box misses it
     // cannot be accepted by any lane (the certified-box argument of face_box) and is skipped
     float cxl = live ? px : INFINITY, cxh = live ? px : -INFINITY, cyl = live ? py : INFINITY, cyh = live ? py : -INFINITY;
-#pragma unroll
+#pragma unroll  // wave_min's and wave_max's order (wave.hpp); written out, a call changes this kernel's instruction stream
     for (int off = 32; off > 0; off >>= 1) {
         cxl = fminf(cxl, __shfl_xor(cxl, off)); cxh = fmaxf(cxh, __shfl_xor(cxh, off));
         cyl = fminf(cyl, __shfl_xor(cyl, off)); cyh = fmaxf(cyh, __shfl_xor(cyh, off));
@@ -572,11 +571,11 @@ __global__ __launch_bounds__(256) void k_pix_raster(const float *__restrict__ pi
             // (Lanes that are not full yet admit anything: -inf.  The bound is refreshed per batch; a stale one is only
             // less sharp.)
             float mw = live ? (nh >= knum ? worstZ : -INFINITY) : INFINITY;
-#pragma unroll
+#pragma unroll  // wave_min's order (wave.hpp); written out, a call changes this kernel's instruction stream
             for (int off = 32; off > 0; off >>= 1) mw = fminf(mw, __shfl_xor(mw, off));
             if (!allFaces) {                                         // sorted list: nothing from here on can be admitted
                 const bool nanz = !(az == az) || !(bz == bz) || !(cz == cz);     // such faces sort first: no bound from them
-                const float zfirst = bcast(nanz ? INFINITY : fmaxf(az, fmaxf(bz, cz)), 0);
+                const float zfirst = lane_bcast(nanz ? INFINITY : fmaxf(az, fmaxf(bz, cz)), 0);
                 if (zfirst + zMargin < mw) break;                    // (a NaN bound compares false: walk on)
             }
             const float zhi = fmaxf(az, fmaxf(bz, cz)), zabs = fmaxf(fabsf(az), fmaxf(fabsf(bz), fabsf(cz)));
@@ -745,23 +744,7 @@ struct FaceKeyLoad {
 
 constexpr int kDChunk = 4;
 
-// Select with the lane mask in an SGPR pair (v_cndmask_b32_e64).  Written as `c ? a : b` on a per-lane bool the compiler emits the
-// VCC form where it can, and gfx950 issues that form about eight times slower than any other VALU instruction (23 cycles
-// against 3-4.5: tools/probes/valu_rate_probe.hip) — 21 of them were a seventh of a wave's time in k_bwd_sorted.
-typedef unsigned long long lanemask_t;
-__device__ __forceinline__ float sel_f(lanemask_t m, float if_set, float if_clear)
-{
-    float d;
-    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(d) : "v"(if_clear), "v"(if_set), "s"(m));
-    return d;
-}
-
-// Data-parallel-primitive moves (full-rate VALU; ds_bpermute shuffles made this kernel LDS-pipe bound: 1.07 ms):
-// row_shr:n inside the 16-lane rows, then row_bcast:15 (lane 15 of each row to the next row; rows 1 and 3
-// written) and row_bcast:31 (lane 31 to rows 2 and 3).  Lanes without a source receive 0.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_mov(int x) { return __builtin_amdgcn_update_dpp(0, x, CTRL, ROW_MASK, 0xf, false); }
-
+// The scans below move by DPP without bound_ctrl (wave.hpp; ds_bpermute shuffles made k_bwd_sorted LDS-pipe bound: 1.07 ms).
 struct SegFlags { bool s1, s2, s4, s8, b15, b31; };
 
 // which lanes of the sorted key sequence continue the run of the lane the move reads from
@@ -769,8 +752,8 @@ __device__ __forceinline__ SegFlags seg_flags(unsigned key, int lane)
 {
     const int k = (int)key, r = lane & 15;
     SegFlags f;
-    const int k1 = dpp_mov<0x111, 0xf>(k), k2 = dpp_mov<0x112, 0xf>(k), k4 = dpp_mov<0x114, 0xf>(k), k8 = dpp_mov<0x118, 0xf>(k);
-    const int k15 = dpp_mov<0x142, 0xa>(k), k31 = dpp_mov<0x143, 0xc>(k);
+    const int k1 = row_shr<1, false>(k), k2 = row_shr<2, false>(k), k4 = row_shr<4, false>(k), k8 = row_shr<8, false>(k);
+    const int k15 = row_bcast15<false>(k), k31 = row_bcast31<false>(k);
     f.s1 = r >= 1 && k1 == k; f.s2 = r >= 2 && k2 == k; f.s4 = r >= 4 && k4 == k; f.s8 = r >= 8 && k8 == k;
     f.b15 = (lane & 16) != 0 && k15 == k;
     f.b31 = (lane & 32) != 0 && k31 == k;
@@ -784,12 +767,12 @@ __device__ __forceinline__ void seg_scan(float (&v)[N], const SegFlags &f)
 #pragma unroll
     for (int k = 0; k < N; ++k) {
         float x = v[k], t;                                           // every move is executed by all lanes, then selected
-        t = __int_as_float(dpp_mov<0x111, 0xf>(__float_as_int(x))); x += f.s1 ? t : 0.f;
-        t = __int_as_float(dpp_mov<0x112, 0xf>(__float_as_int(x))); x += f.s2 ? t : 0.f;
-        t = __int_as_float(dpp_mov<0x114, 0xf>(__float_as_int(x))); x += f.s4 ? t : 0.f;
-        t = __int_as_float(dpp_mov<0x118, 0xf>(__float_as_int(x))); x += f.s8 ? t : 0.f;
-        t = __int_as_float(dpp_mov<0x142, 0xa>(__float_as_int(x))); x += f.b15 ? t : 0.f;
-        t = __int_as_float(dpp_mov<0x143, 0xc>(__float_as_int(x))); x += f.b31 ? t : 0.f;
+        t = row_shr<1, false>(x); x += f.s1 ? t : 0.f;
+        t = row_shr<2, false>(x); x += f.s2 ? t : 0.f;
+        t = row_shr<4, false>(x); x += f.s4 ? t : 0.f;
+        t = row_shr<8, false>(x); x += f.s8 ? t : 0.f;
+        t = row_bcast15<false>(x); x += f.b15 ? t : 0.f;
+        t = row_bcast31<false>(x); x += f.b31 ? t : 0.f;
         v[k] = x;
     }
 }
@@ -831,8 +814,8 @@ __device__ __forceinline__ void block_carry(float (&v)[N], float (*s_sum)[20], c
     const lanemask_t mFirst = __ballot(inFirstRun);
 #pragma unroll
     for (int k = 0; k < N; ++k) {
-        const float ck = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(c), k));
-        v[k] += sel_f(mFirst, ck, 0.f);
+        const float ck = lane_bcast(c, k);
+        v[k] += lane_select(mFirst, ck, 0.f);
     }
     ext = inFirstRun && fromBefore;
 }
@@ -891,7 +874,7 @@ __global__ __launch_bounds__(kBwdWaves * 64) void k_bwd_sorted(const float *__re
         {
             const lanemask_t mValid = __ballot(valid);
 #pragma unroll
-            for (int k = 0; k < 6; ++k) v[k] = sel_f(mValid, v[k], 0.f);
+            for (int k = 0; k < 6; ++k) v[k] = lane_select(mValid, v[k], 0.f);
         }
         seg_scan(v, same);
         bool ext;
@@ -947,13 +930,6 @@ __global__ __launch_bounds__(kBwdWaves * 64) void k_bwd_sorted(const float *__re
 // Runs that cross wave boundaries are carried through LDS, runs that cross block boundaries add their parts atomically into the
 // cleared output — as in k_bwd_sorted.  Every order of additions is fixed: bit-reproducible from run to run.
 constexpr int kRunHPL = 4, kRunWaves = 4, kRunBlock = kRunWaves * 64 * kRunHPL;   // 1,024 sorted hits per block
-
-// the value of the lane below (wave_shr:1: across the 16-lane rows too; lane 0 receives 0)
-__device__ __forceinline__ float lane_below(float x)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ int lane_below(int x) { return __builtin_amdgcn_update_dpp(0, x, 0x138, 0xf, 0xf, false); }
 
 __global__ __launch_bounds__(kRunWaves * 64) void k_bwd_runs(const float *__restrict__ pix, const float *__restrict__ fxy,
                                                              const float *__restrict__ feat, const float *__restrict__ gout,
@@ -1074,8 +1050,8 @@ __global__ __launch_bounds__(kRunWaves * 64) void k_bwd_runs(const float *__rest
     float cinv[NV];
 #pragma unroll
     for (int q = 0; q < NV; ++q) {
-        cinv[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cin), q));
-        acc[q] += sel_f(mFirst, cinv[q], 0.f);
+        cinv[q] = lane_bcast(cin, q);
+        acc[q] += lane_select(mFirst, cinv[q], 0.f);
     }
     const bool tailExt = inFirstRun && contL && fromBefore;          // the tail's run began in an earlier block
     // ---- the heads of the lanes that are not uniform: head + what the lanes before hold of that run ----------------------------
@@ -1087,8 +1063,8 @@ __global__ __launch_bounds__(kRunWaves * 64) void k_bwd_runs(const float *__rest
         const lanemask_t mCarry = __ballot(!uniform && headCont), mLane0 = __ballot(lane == 0);
 #pragma unroll
         for (int q = 0; q < NV; ++q) {
-            const float below = sel_f(mLane0, cinv[q], lane_below(acc[q]));   // lane 0: the carry of the waves before
-            A[q] += sel_f(mCarry, below, 0.f);
+            const float below = lane_select(mLane0, cinv[q], lane_below(acc[q]));   // lane 0: the carry of the waves before
+            A[q] += lane_select(mCarry, below, 0.f);
         }
         if (!uniform && kf < (unsigned)F) {
             float *o = gxy + (size_t)kf * 6, *of = gfeat + (size_t)kf * 3 * D;
@@ -1135,27 +1111,19 @@ constexpr float kAlphaLo = 1e-10f, kAlphaHi = 1.0f;          // torch's clamp(al
 
 __device__ __forceinline__ float clamp_alpha(float x) { return x < kAlphaLo ? kAlphaLo : (x > kAlphaHi ? kAlphaHi : x); }   // NaN stays NaN
 
-// sum over the wave by a butterfly: every lane ends with the same bits (a + b == b + a)
-__device__ __forceinline__ float wave_sum(float x)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-    return x;
-}
-
 // Exclusive product scan over the wave (lane 0 receives 1) in a fixed order — DPP row_shr 1, 2, 4, 8 inside the rows, row_bcast
 // 15 and 31 across them (as seg_scan), then one lane up — and the product of all 64 in `total`.
 __device__ __forceinline__ float wave_excl_prod(float x, int lane, float &total)
 {
     const int r = lane & 15;
     float t;
-    t = __int_as_float(dpp_mov<0x111, 0xf>(__float_as_int(x))); x *= r >= 1 ? t : 1.f;
-    t = __int_as_float(dpp_mov<0x112, 0xf>(__float_as_int(x))); x *= r >= 2 ? t : 1.f;
-    t = __int_as_float(dpp_mov<0x114, 0xf>(__float_as_int(x))); x *= r >= 4 ? t : 1.f;
-    t = __int_as_float(dpp_mov<0x118, 0xf>(__float_as_int(x))); x *= r >= 8 ? t : 1.f;
-    t = __int_as_float(dpp_mov<0x142, 0xa>(__float_as_int(x))); x *= (lane & 16) ? t : 1.f;
-    t = __int_as_float(dpp_mov<0x143, 0xc>(__float_as_int(x))); x *= (lane & 32) ? t : 1.f;
-    total = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), 63));
+    t = row_shr<1, false>(x); x *= r >= 1 ? t : 1.f;
+    t = row_shr<2, false>(x); x *= r >= 2 ? t : 1.f;
+    t = row_shr<4, false>(x); x *= r >= 4 ? t : 1.f;
+    t = row_shr<8, false>(x); x *= r >= 8 ? t : 1.f;
+    t = row_bcast15<false>(x); x *= (lane & 16) ? t : 1.f;
+    t = row_bcast31<false>(x); x *= (lane & 32) ? t : 1.f;
+    total = lane_bcast(x, 63);
     const float e = lane_below(x);
     return lane == 0 ? 1.f : e;
 }
@@ -1332,7 +1300,7 @@ __global__ __launch_bounds__(256) void k_pix_composite_bwd(const float *__restri
             if (lane + d < 64) { A = A + Bm * oA; Bm = Bm * oB; }
         }
         const float Qi = A + Bm * Q;
-        Q = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Qi), 0));
+        Q = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Qi), 0));   // (lane_bcast, written out: a call changes this kernel's stream)
         vNext = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0));
         aNext = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(alpha), 0));
         if (used) {

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void k_rowdot_partial(const float *__restrict_
     const long long r = blockIdx.y;
     float acc = rowdot_slice<SQRT>(a, b, r, n_cols, eps);
     if (!SQRT && a2) acc += rowdot_slice(a2, b2, r, n_cols2);
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
     __syncthreads();
@@ -97,14 +97,14 @@ __global__ __launch_bounds__(256) void k_rowdot_fused(const float *__restrict__ 
     const long long r = blockIdx.y;
     float acc = rowdot_slice<SQRT>(a, b, r, n_cols, eps);
     if (!SQRT && a2) acc += rowdot_slice(a2, b2, r, n_cols2);
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
         const float v = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
         const int old = atomicExch(reinterpret_cast<int *>(part + r * kParts + blockIdx.x), __float_as_int(v));
-        asm volatile("" ::"v"(old));                               // returning form: complete (at the memory side) once it has returned
+        keep_returning(old);
         __builtin_amdgcn_s_waitcnt(0);
         s_last = atomicAdd(&g_tickets[slot][r], 1) == (int)gridDim.x - 1;
     }
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void k_rowdot_fused(const float *__restrict__ 
     __syncthreads();
     if (threadIdx.x < 64) {
         float v = vals[threadIdx.x] + vals[64 + threadIdx.x];      // same tree as k_rowdot_final
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
         for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
         if (threadIdx.x == 0) {
             out[r] = v;
@@ -128,7 +128,7 @@ __global__ __launch_bounds__(64) void k_rowdot_final(const float *__restrict__ p
 {
     const long long r = blockIdx.x;
     float v = part[r * kParts + threadIdx.x] + part[r * kParts + 64 + threadIdx.x];
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     if (threadIdx.x == 0) out[r] = v;
 }

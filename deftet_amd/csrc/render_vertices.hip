@@ -11,8 +11,6 @@
 namespace deftet {
 namespace rv {
 
-__device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7FC00000); }
-
 // The camera of one view in fp64, and cam = R (p - c) with every row summed left to right — the operations and the order of
 // `perspective`, evaluated in fp64 and rounded once per output.  Why not an fp32 chain: near the image centre cam.x and cam.y are
 // differences of terms ~|p - c|, and an fp32 chain leaves them (and the gradients, which cancel the same way) with 3e-5..5e-5

@@ -18,6 +18,7 @@
 // comparisons), double-typed literals promoted as C++ does.
 #pragma once
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace deftet {
 namespace surf {
@@ -54,8 +55,7 @@ static __global__ __launch_bounds__(kScanThreads) void k_scan_excl(const int *in
         const int4 q = *reinterpret_cast<const int4 *>(in + i);
         carry += (q.x + q.y) + (q.z + q.w);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) carry += __shfl_xor(carry, off);
+    carry = wave_sum(carry);
     if (lane == 0) wsum[w] = carry;
     __syncthreads();
     carry = 0;
@@ -76,12 +76,7 @@ static __global__ __launch_bounds__(kScanThreads) void k_scan_excl(const int *in
     }
 #pragma unroll
     for (int k = 0; k < kScanPer; ++k) sum += v[k];
-    int incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int t = __shfl_up(incl, off);
-        if (lane >= off) incl += t;
-    }
+    const int incl = wave_incl_sum(sum, lane);
     if (lane == 63) wsum[w] = incl;
     __syncthreads();
     int run = carry + incl - sum, tot = 0;

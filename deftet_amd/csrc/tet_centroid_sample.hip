@@ -30,8 +30,6 @@ struct TcsChunks {
     unsigned char vol[kTcsMaxChunk];
 };
 
-__device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7FC00000); }
-
 // the centroid of slot j of shape b; false (and NaNs) for a tet index outside [0,T) or a vertex index outside [0,V)
 __device__ __forceinline__ bool centroid_of(const float *__restrict__ pos, const int32_t *__restrict__ tet_idx,
                                             const int32_t *__restrict__ select, int first, int b, int j, int V, int T, int idx_batch,

@@ -28,6 +28,7 @@
 // largest surviving component, the smaller label among equals: a 64-bit max of size << 32 | ~label), k_tc_keep.
 // Every loop has a trip bound in the code; a chain that breaks the invariant or a loop that runs out is counted in `bad`.
 #include "common.hpp"
+#include "wave.hpp"
 
 namespace deftet {
 namespace tc {
@@ -96,8 +97,7 @@ __global__ __launch_bounds__(kThreads) void k_tc_init(const unsigned char *__res
         const unsigned long long any = __ballot(nbad > 0);
         if (any) {
             int s = nbad;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+            s = wave_sum(s);
             if ((threadIdx.x & 63) == 0) atomicAdd(bad, s);
         }
     }
@@ -197,11 +197,7 @@ __global__ __launch_bounds__(kThreads) void k_tc_best(const int *__restrict__ la
         const unsigned size = acc[(size_t)b * T + t] & kSizeMask;
         if (size >= (unsigned)min_size) key = ((unsigned long long)size << 32) | (unsigned long long)(~(unsigned)t);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = __shfl_xor(key, o);
-        key = other > key ? other : key;
-    }
+    key = wave_reduce(key, [](unsigned long long mine, unsigned long long other) { return other > mine ? other : mine; });
     if ((threadIdx.x & 63) == 0 && key) atomicMax(best + b, key);
 }
 

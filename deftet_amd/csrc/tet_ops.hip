@@ -65,13 +65,6 @@ __device__ __forceinline__ TetV load_tet(const float *__restrict__ tet, size_t i
     v.C[0] = t1.z; v.C[1] = t1.w; v.C[2] = t2.x; v.D[0] = t2.y; v.D[1] = t2.z; v.D[2] = t2.w;
     return v;
 }
-__device__ __forceinline__ void cross3(const float *a, const float *b, float *o)
-{
-    o[0] = a[1] * b[2] - a[2] * b[1];
-    o[1] = a[2] * b[0] - a[0] * b[2];
-    o[2] = a[0] * b[1] - a[1] * b[0];
-}
-__device__ __forceinline__ float dot3(const float *a, const float *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 __device__ __forceinline__ float ipow(float x, int p)
 {
     float r = 1.f;
@@ -187,7 +180,7 @@ __device__ int g_energy_tickets[kETicketSlots][2][kETicketShapes];
 __device__ __forceinline__ void mem_write_f64(double *p, double v)
 {
     const unsigned long long old = atomicExch(reinterpret_cast<unsigned long long *>(p), (unsigned long long)__double_as_longlong(v));
-    asm volatile("" ::"v"(old));                                   // keep the RETURNING form: its completion is what s_waitcnt observes
+    keep_returning(old);
 }
 __device__ __forceinline__ double mem_read_f64(double *p)
 {
@@ -204,7 +197,7 @@ __device__ __forceinline__ bool block_reduce_store(double (&v)[N], double *part,
     __shared__ int s_last;
 #pragma unroll
     for (int k = 0; k < N; ++k)
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
         for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_xor(v[k], off);
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0)
@@ -239,7 +232,7 @@ __device__ __forceinline__ void sum_parts(double *part, int b, bool at_memory, d
     for (int k = 0; k < N; ++k) {
         double *src = part + ((size_t)b * kEParts + (threadIdx.x & 63)) * N + k;
         double v = at_memory ? mem_read_f64(src) : *src;
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
         for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
         out[k] = v;
     }

@@ -177,7 +177,7 @@ __global__ __launch_bounds__(256) void k_order_breaks(const unsigned *__restrict
         b0 = brk(key[i], key[i - 1]);
         b1 = brk(skey[i], skey[i - 1]);
     }
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
     for (int off = 32; off > 0; off >>= 1) {
         b0 += __shfl_xor(b0, off);
         b1 += __shfl_xor(b1, off);
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(256) void k_order_far(const float *__restrict__ tet
         for (int k = 0; k < 3; ++k) f = f || !(fabsf(c1[k] - c0[k]) <= lim[k]);
         far += f ? 1 : 0;
     }
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
     for (int off = 32; off > 0; off >>= 1) far += __shfl_xor(far, off);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = far;
     __syncthreads();
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(kFarBlocks) void k_order_far_sum(const int *__restr
 {
     __shared__ int sh[kFarBlocks / 64];
     int v = blockFar[threadIdx.x];
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();

@@ -7,6 +7,7 @@
 #include "grid_setup.hpp"
 #include "prims.hpp"
 #include "surface_batch.hpp"
+#include "wave.hpp"
 
 namespace deftet {
 namespace surf {
@@ -19,7 +20,6 @@ __device__ __forceinline__ float divide_non_zero(float a)
     if (a > 0) return (float)((double)a + 1e-10);
     return (float)1e-10;
 }
-__device__ __forceinline__ float dot3(const float *a, const float *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 __device__ __forceinline__ float abs_ref(float a) { return a > 0.0f ? a : -a; }                 // :20-28
 __device__ __forceinline__ float min3(float a, float b, float c) { float m = a; if (b < m) m = b; if (c < m) m = c; return m; }
 __device__ __forceinline__ float min3_idx(float a, float b, float c)
@@ -385,8 +385,6 @@ __global__ __launch_bounds__(256) void k_tri_chunks(const int *__restrict__ psta
     chunkCount[r] = r < kTRows ? (pstart[(r + 1) << 6] - s0 + 63) >> 6 : 0;
 }
 
-__device__ __forceinline__ float bcastf(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
-
 #ifdef TRI_STATS          // probe builds only (tools/probes/tri_stats_probe.py): where k_tri_query_coop spends its instructions
 __device__ unsigned long long g_tri_stats[16];
 #define TRI_STAT(i, v) do { if (lane == 0) atomicAdd(&g_tri_stats[i], (unsigned long long)(v)); } while (0)
@@ -417,7 +415,7 @@ __device__ __forceinline__ void tri_query_chunk(int W, int part, float (*s_lb)[6
     const bool live = slot < ptStart[row + 1];
     const int q = live ? (int)order[slot] : 0;
     int xa = live ? (int)(skey[slot] & 63u) : 63, xb = live ? (int)(skey[slot] & 63u) : 0;   // the chunk's cells on x
-#pragma unroll
+#pragma unroll  // wave_min's and wave_max's order (wave.hpp); written out, a call changes this kernel's instruction stream
     for (int off = 32; off > 0; off >>= 1) {
         xa = min(xa, __shfl_xor(xa, off));
         xb = max(xb, __shfl_xor(xb, off));
@@ -485,12 +483,7 @@ __device__ __forceinline__ void tri_query_chunk(int W, int part, float (*s_lb)[6
         for (int j = 0; j < kTriCand; ++j)
             if (j < ncand && j != first && !ruled_out(s_lb[j][lane])) surv |= 1u << j;
         const int mine = __popc(surv);
-        int incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int t = __shfl_up(incl, off);
-            if (lane >= off) incl += t;
-        }
+        const int incl = wave_incl_sum(mine, lane);
         const int total = __builtin_amdgcn_readlane(incl, 63);
         TRI_STAT(4, 1);                                             // [4] drains
         TRI_STAT(6, (total + 63) >> 6);                             // [6] queue rounds
@@ -596,12 +589,12 @@ __device__ __forceinline__ void tri_query_chunk(int W, int part, float (*s_lb)[6
                 todo &= todo - 1;
                 const int f = __builtin_amdgcn_readlane(fm, k);
                 if (filter) {
-                    const float dx = p[0] - bcastf(sp.x, k), dy = p[1] - bcastf(sp.y, k), dz = p[2] - bcastf(sp.z, k);
-                    const float lb = fmaxf(sqrtf(dx * dx + dy * dy + dz * dz) - bcastf(sp.w, k) - sph_slack, 0.f);
+                    const float dx = p[0] - lane_bcast(sp.x, k), dy = p[1] - lane_bcast(sp.y, k), dz = p[2] - lane_bcast(sp.z, k);
+                    const float lb = fmaxf(sqrtf(dx * dx + dy * dy + dz * dz) - lane_bcast(sp.w, k) - sph_slack, 0.f);
                     float box2 = 0.f;                                  // ... and the point's distance to its bounding box
 #pragma unroll
                     for (int a = 0; a < 3; ++a) {
-                        const float d = fmaxf(fmaxf(bcastf(blo[a], k) - p[a], p[a] - bcastf(bhi[a], k)), 0.f);
+                        const float d = fmaxf(fmaxf(lane_bcast(blo[a], k) - p[a], p[a] - lane_bcast(bhi[a], k)), 0.f);
                         box2 += d * d;
                     }
                     const float lb2 = fmaxf(lb * lb, box2);
@@ -613,12 +606,12 @@ __device__ __forceinline__ void tri_query_chunk(int W, int part, float (*s_lb)[6
                     if (__any(ncand == kTriCand)) drain();
                 } else {
                     // the vote of eval() from the precomputed plane (the same fp32 operations as plane_project: same t)
-                    const float n[3] = {bcastf(sp.x, k), bcastf(sp.y, k), bcastf(sp.z, k)};
-                    const float t = bcastf(sp.w, k) - dot3(n, p);
+                    const float n[3] = {lane_bcast(sp.x, k), lane_bcast(sp.y, k), lane_bcast(sp.z, k)};
+                    const float t = lane_bcast(sp.w, k) - dot3(n, p);
                     if (!__any(live && t * t <= min_d)) continue;
                     float fc[9];
 #pragma unroll
-                    for (int j = 0; j < 9; ++j) fc[j] = bcastf(fv[j], k);
+                    for (int j = 0; j < 9; ++j) fc[j] = lane_bcast(fv[j], k);
                     eval(f, fc);
                 }
             }
@@ -685,7 +678,7 @@ __device__ __forceinline__ void tri_query_chunk(int W, int part, float (*s_lb)[6
             float r2 = act ? (more ? m * m : INFINITY) : 0.f;
 #pragma unroll
             for (int k = 0; k < 3; ++k) { plo[k] = act ? p[k] : INFINITY; phi[k] = act ? p[k] : -INFINITY; }
-#pragma unroll
+#pragma unroll  // wave_min's and wave_max's order (wave.hpp); written out, a call changes this kernel's instruction stream
             for (int off = 32; off > 0; off >>= 1) {
                 r2 = fmaxf(r2, __shfl_xor(r2, off));
 #pragma unroll
@@ -729,8 +722,7 @@ __device__ __forceinline__ void tri_query_chunk(int W, int part, float (*s_lb)[6
             // vertical ones of a grid-like surface, hundreds of them) fail the plane-offset vote of eval() at once
             drain();
             bestmax = (live && tame) ? min_d : 0.f;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) bestmax = fmaxf(bestmax, __shfl_xor(bestmax, off));
+            bestmax = wave_max(bestmax);
             const int nw = *nWide;                                  // every wave of the block takes every kTriChunkWaves-th batch
             list_run(wide, 0, nw, false, 0, 0, 0, 0, 0, kTriChunkWaves, part);
         }
@@ -828,7 +820,7 @@ struct TriLane {
                 todo &= todo - 1;
                 float fc[9];
 #pragma unroll
-                for (int j = 0; j < 9; ++j) fc[j] = bcastf(fv[j], k);
+                for (int j = 0; j < 9; ++j) fc[j] = lane_bcast(fv[j], k);
                 eval(__builtin_amdgcn_readlane(fm, k), fc);
             }
         }
@@ -947,7 +939,7 @@ __global__ __launch_bounds__(kTriWaves * 64) void k_tri_far_rows(const float *__
         int x0 = need ? grid_cell(L.p[0] - rx - g.slack[0], g.o[0], g.inv[0], g.g[0]) : g.g[0] - 1;
         int x1 = need ? grid_cell(L.p[0] + rx + g.slack[0], g.o[0], g.inv[0], g.g[0]) : 0;
         if (need && !(rx < INFINITY)) { x0 = 0; x1 = g.g[0] - 1; }
-#pragma unroll
+#pragma unroll  // wave_min's and wave_max's order (wave.hpp); written out, a call changes this kernel's instruction stream
         for (int off = 32; off > 0; off >>= 1) {
             x0 = min(x0, __shfl_xor(x0, off));
             x1 = max(x1, __shfl_xor(x1, off));
@@ -1104,7 +1096,7 @@ __global__ __launch_bounds__(256) void k_tri_dist_bwd_grouped(const float *__res
 #pragma unroll
         for (int s = 0; s < 9; ++s) {
             v[s] = mine ? gsum[s] : 0.f;
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
             for (int off = 32; off > 0; off >>= 1) v[s] += __shfl_xor(v[s], off);
         }
         if (lane == L) {

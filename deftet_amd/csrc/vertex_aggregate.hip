@@ -11,10 +11,6 @@
 namespace deftet {
 namespace vagg {
 
-// XCD-aware placement, as vertex_laplacian.hip: every XCD takes one CONTIGUOUS share of the vertex range, so the neighbour rows
-// that neighbouring workgroups share are fetched into one L2.  The grid is a multiple of 8.  Speed only.
-__device__ __forceinline__ int logical_block() { return (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3); }
-
 template <int VEC>
 struct Chan;
 template <>
@@ -53,13 +49,13 @@ __global__ __launch_bounds__(256) void k_vagg(const float *__restrict__ x, const
     constexpr int RPW = 64 / LPR, U = VEC == 4 ? 4 : 8;
     static_assert(LPR % U == 0, "a trip never crosses the window");
     const int lane = threadIdx.x & 63, g = lane & (LPR - 1);
-    const long long row = ((long long)logical_block() * 4 + (threadIdx.x >> 6)) * RPW + lane / LPR;
+    const long long row = ((long long)xcd_logical_block() * 4 + (threadIdx.x >> 6)) * RPW + lane / LPR;
     const bool live = row < V;
     const int i = live ? (int)row : 0;
     const size_t xb = (size_t)blockIdx.y * V * C;
     const int k0 = live ? offsets[i] : 0, k1 = live ? offsets[i + 1] : 0;
     int nmax = k1 - k0;
-#pragma unroll
+#pragma unroll  // across the row groups of the wave, offsets LPR upward: an order of its own, not wave.hpp's wave_max (int max: same value)
     for (int off = LPR; off < 64; off <<= 1) nmax = max(nmax, __shfl_xor(nmax, off));
     const int CV = C / VEC;
     for (int c0 = 0; c0 < CV; c0 += LPR) {
@@ -115,8 +111,6 @@ int launch_width(hipStream_t st, const float *x, const int *offsets, const int *
     return launch<VEC, 64>(st, x, offsets, idx, vals, B, V, C, out);
 }
 
-inline bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 }  // namespace vagg
 }  // namespace deftet
 
@@ -132,12 +126,12 @@ extern "C" int deftet_vertex_aggregate_f32(const float *x, const int32_t *offset
     DEFTET_CHECK_ARG(offsets && (nnz == 0 || (idx && vals)), "null CSR pointer");
     const bool work = n_batch > 0 && n_vertex > 0;
     DEFTET_CHECK_ARG(!work || (x && out), "null pointer");
-    DEFTET_CHECK_ARG(vagg::aligned(x, 4) && vagg::aligned(out, 4) && vagg::aligned(offsets, 4) && vagg::aligned(idx, 4) &&
-                         vagg::aligned(vals, 4),
+    DEFTET_CHECK_ARG(aligned(x, 4) && aligned(out, 4) && aligned(offsets, 4) && aligned(idx, 4) &&
+                         aligned(vals, 4),
                      "x, out and the CSR must be 4-byte aligned");
     if (!work) return DEFTET_OK;
     hipStream_t st = as_stream(stream_);
-    if (n_channel % 4 == 0 && vagg::aligned(x, 16) && vagg::aligned(out, 16))
+    if (n_channel % 4 == 0 && aligned(x, 16) && aligned(out, 16))
         return vagg::launch_width<4>(st, x, offsets, idx, vals, n_batch, n_vertex, n_channel, out);
     return vagg::launch_width<1>(st, x, offsets, idx, vals, n_batch, n_vertex, n_channel, out);
 }

@@ -59,10 +59,6 @@ struct Unroll {
     static constexpr int value = CM <= 4 ? 8 : CM <= 8 ? 4 : 2;
 };
 
-// XCD-aware placement, as k_gather_bwd (vertex_ops.hip): every XCD takes one CONTIGUOUS share of the vertex range, so the
-// neighbour rows that neighbouring workgroups share are fetched into one L2.  The grid is a multiple of 8.  Speed only.
-__device__ __forceinline__ int logical_block() { return (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3); }
-
 // One lane per (shape, vertex).  nei_i = Σ_k v_k x[col_k] (fmaf, CSR order) or (Σ_k x[col_k]) / w_i (adds in table order, one
 // IEEE division); r = nei − x written to r; then r² to out (NONE) or Σ_c r² of the lane into a per-workgroup partial (SHAPE),
 // part[b][logical block]: a butterfly over the wave, then the four waves as (w0 + w1) + (w2 + w3).
@@ -72,7 +68,7 @@ __global__ __launch_bounds__(256) void k_vlap_fwd(const float *__restrict__ x, c
                                                   float *out, float *part)
 {
     constexpr int U = Unroll<CM>::value;
-    const int b = blockIdx.y, lb = logical_block();
+    const int b = blockIdx.y, lb = xcd_logical_block();
     const int i = lb * 256 + threadIdx.x;
     const size_t xb = (size_t)b * V * C;
     float sq = 0.f;
@@ -117,7 +113,7 @@ __global__ __launch_bounds__(256) void k_vlap_fwd(const float *__restrict__ x, c
     }
     if (SHAPE) {
         __shared__ float wsum[4];
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
         for (int off = 32; off > 0; off >>= 1) sq += __shfl_xor(sq, off);
         if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = sq;
         __syncthreads();
@@ -132,7 +128,7 @@ __global__ __launch_bounds__(256) void k_vlap_final(const float *__restrict__ pa
     const int b = blockIdx.x;
     float s = 0.f;
     for (int k = threadIdx.x; k < n; k += 256) s += part[(size_t)b * n + k];
-#pragma unroll
+#pragma unroll  // wave_sum's order (wave.hpp); written out, a call changes this kernel's instruction stream
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
     __syncthreads();
@@ -148,7 +144,7 @@ __global__ __launch_bounds__(256) void k_vlap_bwd(const float *__restrict__ r, c
 {
     constexpr int U = Unroll<CM>::value;
     const int b = blockIdx.y;
-    const int j = logical_block() * 256 + threadIdx.x;
+    const int j = xcd_logical_block() * 256 + threadIdx.x;
     if (j >= V) return;
     const size_t xb = (size_t)b * V * C;
     const float g2 = SHAPE ? 2.f * g[b] : 0.f;
@@ -262,8 +258,6 @@ int launch_bwd(bool rowdiv, bool shape, dim3 grid, hipStream_t st, const float *
     return DEFTET_OK;
 }
 
-inline bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 }  // namespace vlap
 }  // namespace deftet
 
@@ -284,13 +278,13 @@ extern "C" int deftet_vertex_adjacency_csr_i32(const void *row_idx, const void *
     DEFTET_CHECK_ARG(order == DEFTET_VADJ_ROW_COL || order == DEFTET_VADJ_ROW_INPUT, "unknown order %d", order);
     DEFTET_CHECK_ARG(offsets && t_offsets && bad_flag, "null pointer");
     DEFTET_CHECK_ARG(nnz == 0 || (row_idx && col_idx && cols && t_rows), "null pointer");
-    DEFTET_CHECK_ARG(vlap::aligned(row_idx, index_bytes) && vlap::aligned(col_idx, index_bytes), "indices must be %d-byte aligned",
+    DEFTET_CHECK_ARG(aligned(row_idx, index_bytes) && aligned(col_idx, index_bytes), "indices must be %d-byte aligned",
                      index_bytes);
-    DEFTET_CHECK_ARG(vlap::aligned(values, 4) && vlap::aligned(offsets, 4) && vlap::aligned(cols, 4) && vlap::aligned(vals, 4) &&
-                         vlap::aligned(t_offsets, 4) && vlap::aligned(t_rows, 4) && vlap::aligned(t_vals, 4) && vlap::aligned(bad_flag, 4),
+    DEFTET_CHECK_ARG(aligned(values, 4) && aligned(offsets, 4) && aligned(cols, 4) && aligned(vals, 4) &&
+                         aligned(t_offsets, 4) && aligned(t_rows, 4) && aligned(t_vals, 4) && aligned(bad_flag, 4),
                      "outputs and values must be 4-byte aligned");
     const vlap::CsrLayout L = vlap::csr_layout(nnz, workspace);
-    DEFTET_CHECK_ARG(nnz == 0 || (workspace && vlap::aligned(workspace, 256) && L.bytes <= workspace_bytes),
+    DEFTET_CHECK_ARG(nnz == 0 || (workspace && aligned(workspace, 256) && L.bytes <= workspace_bytes),
                      "workspace null, misaligned or too small");
     hipStream_t st = as_stream(stream_);
     DEFTET_HIP(hipMemsetAsync(bad_flag, 0, 4, st));
@@ -325,7 +319,7 @@ static int vlap_check(int weighting, int reduction, int n_batch, int n_vertex, i
     DEFTET_CHECK_ARG(offsets && (nnz == 0 || idx), "null pointer");
     DEFTET_CHECK_ARG(weighting != DEFTET_VLAP_VALUES || nnz == 0 || vals, "null values");
     DEFTET_CHECK_ARG(weighting != DEFTET_VLAP_ROW_DIVISOR || n_vertex == 0 || row_weights, "null row weights");
-    DEFTET_CHECK_ARG(vlap::aligned(offsets, 4) && vlap::aligned(idx, 4) && vlap::aligned(vals, 4) && vlap::aligned(row_weights, 4),
+    DEFTET_CHECK_ARG(aligned(offsets, 4) && aligned(idx, 4) && aligned(vals, 4) && aligned(row_weights, 4),
                      "CSR and weights must be 4-byte aligned");
     return DEFTET_OK;
 }
@@ -339,8 +333,8 @@ extern "C" int deftet_vertex_laplacian_fwd_f32(const float *x, const int32_t *of
     if (rc != DEFTET_OK) return rc;
     const bool shape = reduction == DEFTET_VLAP_SHAPE, rowdiv = weighting == DEFTET_VLAP_ROW_DIVISOR;
     DEFTET_CHECK_ARG(out && (n_vertex == 0 || (x && r)), "null pointer");
-    DEFTET_CHECK_ARG(vlap::aligned(x, 4) && vlap::aligned(r, 4) && vlap::aligned(out, 4), "x, r and out must be 4-byte aligned");
-    DEFTET_CHECK_ARG(!shape || (workspace && vlap::aligned(workspace, 256) &&
+    DEFTET_CHECK_ARG(aligned(x, 4) && aligned(r, 4) && aligned(out, 4), "x, r and out must be 4-byte aligned");
+    DEFTET_CHECK_ARG(!shape || (workspace && aligned(workspace, 256) &&
                                 workspace_bytes >= deftet_vertex_laplacian_workspace_bytes(n_batch, n_vertex)),
                      "workspace null, misaligned or too small");
     if (n_batch == 0) return DEFTET_OK;
@@ -369,7 +363,7 @@ extern "C" int deftet_vertex_laplacian_bwd_f32(const float *r, const float *grad
     if (rc != DEFTET_OK) return rc;
     const bool shape = reduction == DEFTET_VLAP_SHAPE, rowdiv = weighting == DEFTET_VLAP_ROW_DIVISOR;
     DEFTET_CHECK_ARG(grad_out && (n_vertex == 0 || (r && grad_x)), "null pointer");
-    DEFTET_CHECK_ARG(vlap::aligned(r, 4) && vlap::aligned(grad_out, 4) && vlap::aligned(grad_x, 4),
+    DEFTET_CHECK_ARG(aligned(r, 4) && aligned(grad_out, 4) && aligned(grad_x, 4),
                      "r, grad_out and grad_x must be 4-byte aligned");
     if (n_batch == 0 || n_vertex == 0) return DEFTET_OK;
     const dim3 grid(vlap::grid_x(n_vertex), n_batch);

@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void k_gather_bwd(const float *__restrict__ gr
             }
         }
     }
-    // (s0 + s1) + (s2 + s3); lanes of one vertex are adjacent, the whole wave takes part
+    // (s0 + s1) + (s2 + s3), offsets 1 then 2 (wave.hpp's butterfly goes downward: other bits); adjacent lanes, the whole wave takes part
     ax += __shfl_xor(ax, 1); ay += __shfl_xor(ay, 1); az += __shfl_xor(az, 1);
     ax += __shfl_xor(ax, 2); ay += __shfl_xor(ay, 2); az += __shfl_xor(az, 2);
     if (v < V && k == 0) {
