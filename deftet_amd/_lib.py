@@ -254,6 +254,7 @@ def require_gpu(*tensors) -> None:
 # step; tools/probes/host_call_probe.py: 11-15 us per library call against 4 us per torch elementwise launch).  So: raw stream
 # handles from torch._C (no Stream object), plain integers for pointers (ctypes converts them for c_void_p parameters), the
 # device guard only when the current device is another one, the workspace looked up without the lock when it is large enough.
+# call() below puts these together: the operators go through it, the pieces stay exported for tests, bench.py and the tools.
 def ptr(t):
     return t.data_ptr() if t is not None else None
 
@@ -312,3 +313,38 @@ def workspace(device, nbytes: int):
             buf = torch.empty(max(int(nbytes * 1.25), 1 << 20), dtype=torch.uint8, device=device)
             _ws[key] = buf
     return buf
+
+
+from torch import Tensor as _Tensor                     # noqa: E402  (torch is imported above already, for the raw stream)
+
+_NO_WS = object()                                       # call(ws=) not given: the entry has no workspace parameters
+
+
+def call(name, device, *args, ws=_NO_WS, what=None):
+    """The calling convention of every stream-taking entry point, stated once:
+
+        status = lib.<name>(*args[, workspace pointer, workspace bytes], raw current stream of `device`)
+
+    under the guard for `device` (free when it is the current one), DefTetHipError("<what or name> failed (status): last
+    error") on a non-zero status.  Tensors in args go in as their data_ptr(), None as NULL, everything else as it is (ints,
+    floats, ctypes arrays, host addresses).  ws: not given = the entry takes no workspace; a byte count = the cached
+    workspace(device, count); a tensor = the caller's own buffer; None = (NULL, 0), the paths that need none.  The size handed
+    over is always the buffer's numel(): the library only checks that it is large enough."""
+    argv = [a.data_ptr() if isinstance(a, _Tensor) else a for a in args]
+    if ws is not _NO_WS:
+        if ws is None:
+            argv += (None, 0)
+        else:
+            if not isinstance(ws, _Tensor):
+                ws = workspace(device, ws)
+            argv += (ws.data_ptr(), ws.numel())
+    argv.append(current_stream(device))
+    fn = getattr(_lib or load(), name)
+    guard = on_device(device)
+    if guard is _NO_GUARD:                              # (the usual case, without entering and leaving a context)
+        status = fn(*argv)
+    else:
+        with guard:
+            status = fn(*argv)
+    if status:
+        check(status, what or name)

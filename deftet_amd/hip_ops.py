@@ -1,8 +1,13 @@
 """Thin torch-tensor front-ends over the C ABI (one function per entry point).
 
-Everything here is plumbing: argument checks, output allocation, workspace, stream.  The
-reference-shaped operator surface (torch.autograd.Function / nn.Module with the
-reference's names and signatures) lives in deftet_amd/layers/ and deftet_amd/utils/.
+Everything here is plumbing, and an operator states only what is its own: its argument checks,
+its outputs and the arguments of its entry point.  How an entry point is called — tensors as
+pointers, the workspace pair directly before the stream, the stream and the guard of one device,
+the error raised on a non-zero status — is stated once, in _lib.call.  The entries that take no
+stream, or their workspace first (deftet_point_in_tet_grid_dims, deftet_point_in_tet_read_stats),
+are called as written out.  The reference-shaped operator surface (torch.autograd.Function /
+nn.Module with the reference's names and signatures) lives in deftet_amd/layers/ and
+deftet_amd/utils/.
 """
 from __future__ import annotations
 
@@ -217,9 +222,7 @@ def prepare_queries(pts_bxqx3, n_tet, algo=PIT_AUTO, query_box=None, query_box_m
         nbytes = max(lib.deftet_point_in_tet_workspace_bytes(B, pq.n_tet, Q, algo), 256)
         pq.workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)       # private: outlives the cached per-stream workspace
         box_in, box_out, box_miss = _resolve_query_box(query_box, dev, B, Q, algo, query_box_misses)
-        _lib.check(lib.deftet_point_in_tet_prepare_ex_f32(_lib.ptr(pts), B, pq.n_tet, Q, algo, _lib.ptr(box_in), _lib.ptr(box_out),
-                                                          _lib.ptr(box_miss), _lib.ptr(pq.workspace), nbytes, _lib.current_stream(dev)),
-                   "deftet_point_in_tet_prepare_ex_f32")
+        _lib.call("deftet_point_in_tet_prepare_ex_f32", dev, pts, B, pq.n_tet, Q, algo, box_in, box_out, box_miss, ws=pq.workspace)
         pq.event = torch.cuda.Event()
         pq.event.record(torch.cuda.current_stream(dev))
     return pq
@@ -257,10 +260,7 @@ def tet_spatial_order(tet_tx4x3, want_breaks=False):
     T, dev = tet.shape[0], tet.device
     order = torch.empty(T, device=dev, dtype=torch.int32)
     breaks = torch.zeros(2, device=dev, dtype=torch.int32)
-    with _lib.on_device(dev):
-        ws = _lib.workspace(dev, max(lib.deftet_tet_spatial_order_workspace_bytes(T), 256))
-        _lib.check(lib.deftet_tet_spatial_order_f32(_lib.ptr(tet), T, _lib.ptr(order), _lib.ptr(breaks), _lib.ptr(ws), ws.numel(),
-                                                    _lib.current_stream(dev)), "deftet_tet_spatial_order_f32")
+    _lib.call("deftet_tet_spatial_order_f32", dev, tet, T, order, breaks, ws=max(lib.deftet_tet_spatial_order_workspace_bytes(T), 256))
     order._deftet_permutation = order._version                          # a permutation by construction (see _check_order)
     return (order, breaks) if want_breaks else order
 
@@ -282,10 +282,7 @@ def tet_order_coherence(tet_tx4x3, order=None, out=None):
         out = torch.empty(2, device=dev, dtype=torch.int32)
     elif out.dtype != torch.int32 or out.numel() < 2 or not out.is_contiguous():
         raise RuntimeError("out must be a contiguous int32 tensor of at least 2 entries")
-    with _lib.on_device(dev):
-        ws = _lib.workspace(dev, max(lib.deftet_tet_order_coherence_workspace_bytes(T), 256))
-        _lib.check(lib.deftet_tet_order_coherence_f32(_lib.ptr(tet), T, _lib.ptr(order), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                                                      _lib.current_stream(dev)), "deftet_tet_order_coherence_f32")
+    _lib.call("deftet_tet_order_coherence_f32", dev, tet, T, order, out, ws=max(lib.deftet_tet_order_coherence_workspace_bytes(T), 256))
     return out
 
 
@@ -489,15 +486,9 @@ def point_in_tet(tet_bxtx4x3, pts_bxqx3, want_bary=False, algo=PIT_AUTO, pred_bx
                                                                  order, query_box, query_box_misses,
                                                                  lambda: _auto_order(dev, B, T, Q, algo, topology, lambda: tet[0]))
         if prepared is not None:
-            _lib.check(lib.deftet_point_in_tet_scan_ex_f32(_lib.ptr(tet), _lib.ptr(pts), _lib.ptr(cond), _lib.ptr(bary), _lib.ptr(pred),
-                                                           _lib.ptr(occ), _lib.ptr(hits), B, T, Q, algo, _lib.ptr(order), _lib.ptr(ws),
-                                                           ws.numel(), _lib.current_stream(dev)), "deftet_point_in_tet_scan_ex_f32")
+            _lib.call("deftet_point_in_tet_scan_ex_f32", dev, tet, pts, cond, bary, pred, occ, hits, B, T, Q, algo, order, ws=ws)
         else:
-            _lib.check(lib.deftet_point_in_tet_ex_f32(_lib.ptr(tet), _lib.ptr(pts), _lib.ptr(cond), _lib.ptr(bary), _lib.ptr(pred),
-                                                      _lib.ptr(occ), _lib.ptr(hits), B, T, Q, algo, _lib.ptr(order), _lib.ptr(box[0]),
-                                                      _lib.ptr(box[1]), _lib.ptr(box[2]), _lib.ptr(ws), ws.numel(),
-                                                      _lib.current_stream(dev)),
-                       "deftet_point_in_tet_ex_f32")
+            _lib.call("deftet_point_in_tet_ex_f32", dev, tet, pts, cond, bary, pred, occ, hits, B, T, Q, algo, order, *box, ws=ws)
     return _pit_result(cond, bary, occ, hits, want_hits)
 
 
@@ -548,16 +539,11 @@ def point_in_tet_indexed(pos_bxvx3, tet_idx, pts_bxqx3, want_bary=False, algo=PI
                                                                  prepared, order, query_box, query_box_misses,
                                                                  lambda: _auto_order(dev, B, T, Q, algo, key, lambda: tet_gather(pos[:1], idx[:1])[0]))
         if prepared is not None:
-            _lib.check(lib.deftet_point_in_tet_indexed_scan_f32(_lib.ptr(pos), _lib.ptr(idx), Bi, _lib.ptr(pts), _lib.ptr(cond), _lib.ptr(bary),
-                                                                _lib.ptr(pred), _lib.ptr(occ), _lib.ptr(hits), B, V, T, Q, algo, _lib.ptr(order),
-                                                                _lib.ptr(bad), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
-                       "deftet_point_in_tet_indexed_scan_f32")
+            _lib.call("deftet_point_in_tet_indexed_scan_f32", dev, pos, idx, Bi, pts, cond, bary, pred, occ, hits, B, V, T, Q, algo, order,
+                      bad, ws=ws)
         else:
-            _lib.check(lib.deftet_point_in_tet_indexed_f32(_lib.ptr(pos), _lib.ptr(idx), Bi, _lib.ptr(pts), _lib.ptr(cond), _lib.ptr(bary),
-                                                           _lib.ptr(pred), _lib.ptr(occ), _lib.ptr(hits), B, V, T, Q, algo, _lib.ptr(order),
-                                                           _lib.ptr(box[0]), _lib.ptr(box[1]), _lib.ptr(box[2]), _lib.ptr(bad),
-                                                           _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
-                       "deftet_point_in_tet_indexed_f32")
+            _lib.call("deftet_point_in_tet_indexed_f32", dev, pos, idx, Bi, pts, cond, bary, pred, occ, hits, B, V, T, Q, algo, order,
+                      *box, bad, ws=ws)
     if check and int(bad.item()):
         raise RuntimeError("point_in_tet_indexed: index out of range [0, %d)" % V)
     return _pit_result(cond, bary, occ, hits, want_hits)
@@ -565,7 +551,6 @@ def point_in_tet_indexed(pos_bxvx3, tet_idx, pts_bxqx3, want_bary=False, algo=PI
 
 def point_in_tet_grid(n_tet, n_query):
     """(y/z cells per axis, x cells) of the query grid the binned algos build for this problem size."""
-    import ctypes
     g, gx = ctypes.c_int(0), ctypes.c_int(0)
     _lib.check(_lib.load().deftet_point_in_tet_grid_dims(int(n_tet), int(n_query), ctypes.byref(g), ctypes.byref(gx)), "deftet_point_in_tet_grid_dims")
     return g.value, gx.value
@@ -604,21 +589,16 @@ def point_in_tet_bwd(tet_bxtx4x3, pts_bxqx3, cond, grad_w, want_grad_pts=False, 
     grad_pts = torch.empty_like(pts) if want_grad_pts else None
     go = _f32c(grad_occ) if grad_occ is not None else None
     grad_pred = torch.empty(B, T, device=dev, dtype=torch.float32) if go is not None else None
-    with _lib.on_device(dev):
-        ws = _lib.workspace(dev, lib.deftet_point_in_tet_bwd_workspace_bytes(B, T, Q))
-        _lib.check(lib.deftet_point_in_tet_bwd_f32(_lib.ptr(tet), _lib.ptr(pts), _lib.ptr(cond), _lib.ptr(gw),
-                                                   _lib.ptr(grad_tet), _lib.ptr(grad_pts), _lib.ptr(go), _lib.ptr(grad_pred),
-                                                   _lib.ptr(hits), B, T, Q, 0, _lib.ptr(ws), ws.numel(),
-                                                   _lib.current_stream(dev)),
-                   "deftet_point_in_tet_bwd_f32")
+    _lib.call("deftet_point_in_tet_bwd_f32", dev, tet, pts, cond, gw, grad_tet, grad_pts, go, grad_pred, hits, B, T, Q, 0,
+              ws=lib.deftet_point_in_tet_bwd_workspace_bytes(B, T, Q))
     if go is not None:
         return grad_tet, grad_pts, grad_pred
     return grad_tet, grad_pts
 
 
-def _to_vertices_begin(caller, lib, csr, Bi, B, V, T, pts, want_grad_pts, grad_occ, out):
-    """The checks, outputs and workspace of the two *_bwd_to_vertices, on the queries' device (Bi: the index lists the tets come
-    from, None = the CSR's).  Returns (offsets, slots, Bi, grad_pos, grad_pts, grad_occ as f32, grad_pred, workspace)."""
+def _to_vertices_begin(caller, csr, Bi, B, V, T, pts, want_grad_pts, grad_occ, out):
+    """The checks, outputs and workspace size of the two *_bwd_to_vertices, on the queries' device (Bi: the index lists the tets
+    come from, None = the CSR's).  Returns (offsets, slots, Bi, grad_pos, grad_pts, grad_occ as f32, grad_pred, workspace bytes)."""
     offsets, slots, Bc = csr
     if Bi is not None and Bc != Bi:
         raise RuntimeError("%s: the CSR was built over %d index list(s), tet_idx has %d" % (caller, Bc, Bi))
@@ -632,8 +612,7 @@ def _to_vertices_begin(caller, lib, csr, Bi, B, V, T, pts, want_grad_pts, grad_o
     go = _f32c(grad_occ) if grad_occ is not None else None
     # (`accumulate` of the C entry covers grad_pos AND grad_pred: a fresh grad_pred must then start from zero)
     grad_pred = (torch.zeros if out is not None else torch.empty)(B, T, device=dev, dtype=torch.float32) if go is not None else None
-    ws = _lib.workspace(dev, lib.deftet_point_in_tet_bwd_to_vertices_workspace_bytes(B, T, pts.shape[1]))
-    return offsets, slots, Bc, grad_pos, grad_pts, go, grad_pred, ws
+    return offsets, slots, Bc, grad_pos, grad_pts, go, grad_pred, _lib.load().deftet_point_in_tet_bwd_to_vertices_workspace_bytes(B, T, pts.shape[1])
 
 
 def point_in_tet_bwd_to_vertices(tet_bxtx4x3, pts_bxqx3, cond, grad_w, csr, n_vertex, want_grad_pts=False, grad_occ=None, hits=None,
@@ -643,18 +622,12 @@ def point_in_tet_bwd_to_vertices(tet_bxtx4x3, pts_bxqx3, cond, grad_w, csr, n_ve
     and the query.  csr = tet_vertex_csr(...) of the topology the tets were gathered with; bit-identical to the two-call form.
     out: existing [B,V,3] tensor to ADD to."""
     _lib.require_gpu(tet_bxtx4x3, pts_bxqx3, cond, grad_w, grad_occ)
-    lib = _lib.load()
     tet, pts, cond, gw = _f32c(tet_bxtx4x3), _f32c(pts_bxqx3), _f32c(cond), _f32c(grad_w)
     B, T, Q, V = tet.shape[0], tet.shape[1], pts.shape[1], int(n_vertex)
-    dev = pts.device
-    with _lib.on_device(dev):
-        offsets, slots, Bi, grad_pos, grad_pts, go, grad_pred, ws = _to_vertices_begin("point_in_tet_bwd_to_vertices", lib, csr, None, B, V, T,
-                                                                                       pts, want_grad_pts, grad_occ, out)
-        _lib.check(lib.deftet_point_in_tet_bwd_to_vertices_f32(_lib.ptr(tet), _lib.ptr(pts), _lib.ptr(cond), _lib.ptr(gw), _lib.ptr(go),
-                                                               _lib.ptr(hits), _lib.ptr(offsets), _lib.ptr(slots), Bi, _lib.ptr(grad_pos),
-                                                               _lib.ptr(grad_pts), _lib.ptr(grad_pred), B, V, T, Q, 1 if out is not None else 0,
-                                                               _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
-                   "deftet_point_in_tet_bwd_to_vertices_f32")
+    offsets, slots, Bi, grad_pos, grad_pts, go, grad_pred, nbytes = _to_vertices_begin("point_in_tet_bwd_to_vertices", csr, None, B, V, T, pts,
+                                                                                       want_grad_pts, grad_occ, out)
+    _lib.call("deftet_point_in_tet_bwd_to_vertices_f32", pts.device, tet, pts, cond, gw, go, hits, offsets, slots, Bi, grad_pos, grad_pts,
+              grad_pred, B, V, T, Q, 1 if out is not None else 0, ws=nbytes)
     return (grad_pos, grad_pts) if grad_pred is None else (grad_pos, grad_pts, grad_pred)
 
 
@@ -664,47 +637,33 @@ def point_in_tet_indexed_bwd_to_vertices(pos, tet_idx, pts, cond, grad_w, csr, w
     for bit the same values on the same inputs; hits from either forward."""
     pos, idx, pts = _indexed_inputs(pos, tet_idx, pts, None)
     _lib.require_gpu(cond, grad_w, grad_occ)
-    lib = _lib.load()
     cond, gw = _f32c(cond), _f32c(grad_w)
     B, V, T, Q, Bi = pos.shape[0], pos.shape[1], idx.shape[1], pts.shape[1], idx.shape[0]
-    dev = pts.device
-    with _lib.on_device(dev):
-        offsets, slots, _, grad_pos, grad_pts, go, grad_pred, ws = _to_vertices_begin("point_in_tet_indexed_bwd_to_vertices", lib, csr, Bi, B, V,
-                                                                                      T, pts, want_grad_pts, grad_occ, out)
-        _lib.check(lib.deftet_point_in_tet_indexed_bwd_to_vertices_f32(_lib.ptr(pos), _lib.ptr(idx), Bi, _lib.ptr(pts), _lib.ptr(cond),
-                                                                       _lib.ptr(gw), _lib.ptr(go), _lib.ptr(hits), _lib.ptr(offsets),
-                                                                       _lib.ptr(slots), _lib.ptr(grad_pos), _lib.ptr(grad_pts),
-                                                                       _lib.ptr(grad_pred), B, V, T, Q, 1 if out is not None else 0, _lib.ptr(ws),
-                                                                       ws.numel(), _lib.current_stream(dev)),
-                   "deftet_point_in_tet_indexed_bwd_to_vertices_f32")
+    offsets, slots, _, grad_pos, grad_pts, go, grad_pred, nbytes = _to_vertices_begin("point_in_tet_indexed_bwd_to_vertices", csr, Bi, B, V, T,
+                                                                                      pts, want_grad_pts, grad_occ, out)
+    _lib.call("deftet_point_in_tet_indexed_bwd_to_vertices_f32", pts.device, pos, idx, Bi, pts, cond, gw, go, hits, offsets, slots, grad_pos,
+              grad_pts, grad_pred, B, V, T, Q, 1 if out is not None else 0, ws=nbytes)
     return (grad_pos, grad_pts) if grad_pred is None else (grad_pos, grad_pts, grad_pred)
 
 
 def paste_occ_fwd(pred_bxt, cond_bxqx1, clamp_inplace=True):
     _lib.require_gpu(pred_bxt, cond_bxqx1)
-    lib = _lib.load()
     pred = _f32c(pred_bxt)
     if not (cond_bxqx1.is_contiguous() and cond_bxqx1.dtype == torch.float32):
         raise RuntimeError("condition must be a contiguous float32 tensor (it is clamped in place)")
     B, T = pred.shape
     Q = cond_bxqx1.shape[1]
     out = torch.empty(B, Q, device=pred.device, dtype=torch.float32)
-    with _lib.on_device(pred.device):
-        _lib.check(lib.deftet_paste_occ_fwd_f32(_lib.ptr(pred), _lib.ptr(cond_bxqx1), _lib.ptr(out), B, T, Q,
-                                                int(clamp_inplace), _lib.current_stream(pred.device)),
-                   "deftet_paste_occ_fwd_f32")
+    _lib.call("deftet_paste_occ_fwd_f32", pred.device, pred, cond_bxqx1, out, B, T, Q, int(clamp_inplace))
     return out
 
 
 def paste_occ_bwd(cond_bxqx1, grad_out_bxq, n_tet):
     _lib.require_gpu(cond_bxqx1, grad_out_bxq)
-    lib = _lib.load()
     cond, go = _f32c(cond_bxqx1), _f32c(grad_out_bxq)
     B, Q = go.shape
     gp = torch.empty(B, n_tet, device=go.device, dtype=torch.float32)
-    with _lib.on_device(go.device):
-        _lib.check(lib.deftet_paste_occ_bwd_f32(_lib.ptr(cond), _lib.ptr(go), _lib.ptr(gp), B, n_tet, Q, 1,
-                                                _lib.current_stream(go.device)), "deftet_paste_occ_bwd_f32")
+    _lib.call("deftet_paste_occ_bwd_f32", go.device, cond, go, gp, B, n_tet, Q, 1)
     return gp
 
 
@@ -728,10 +687,8 @@ def radix_sort(keys, values=None, bits=None, n_valid=None):
         raise RuntimeError("radix_sort: values must have the keys' length and 4- or 8-byte elements")
     ko = torch.empty_like(k)
     vo = torch.empty_like(v) if v is not None else None
-    with _lib.on_device(k.device):
-        ws = _lib.workspace(k.device, lib.deftet_radix_sort_workspace_bytes(n, kb, vb))
-        _lib.check(lib.deftet_radix_sort(_lib.ptr(k), _lib.ptr(ko), _lib.ptr(v), _lib.ptr(vo), n, kb, vb, int(bits or kb * 8),
-                                         _lib.ptr(n_valid), _lib.ptr(ws), ws.numel(), _lib.current_stream(k.device)), "deftet_radix_sort")
+    _lib.call("deftet_radix_sort", k.device, k, ko, v, vo, n, kb, vb, int(bits or kb * 8), n_valid,
+              ws=lib.deftet_radix_sort_workspace_bytes(n, kb, vb))
     return ko, vo
 
 
@@ -743,10 +700,8 @@ def scan(x, kind="exclusive"):
     if t.dtype not in (torch.int32, torch.int64):
         raise RuntimeError("scan: int32 or int64")
     out = torch.empty_like(t)
-    with _lib.on_device(t.device):
-        ws = _lib.workspace(t.device, lib.deftet_scan_workspace_bytes(t.numel(), t.element_size()))
-        _lib.check(lib.deftet_scan(_lib.ptr(t), _lib.ptr(out), t.numel(), t.element_size(), {"exclusive": 0, "inclusive": 1, "max": 2}[kind],
-                                   _lib.ptr(ws), ws.numel(), _lib.current_stream(t.device)), "deftet_scan")
+    _lib.call("deftet_scan", t.device, t, out, t.numel(), t.element_size(), {"exclusive": 0, "inclusive": 1, "max": 2}[kind],
+              ws=lib.deftet_scan_workspace_bytes(t.numel(), t.element_size()))
     return out
 
 
@@ -770,11 +725,7 @@ def rowdot(a, b=None, a2=None, b2=None):
     elif b2 is not None:
         raise RuntimeError("rowdot: b2 without a2")
     out = torch.empty(R, device=a.device, dtype=torch.float32)
-    with _lib.on_device(a.device):
-        ws = _lib.workspace(a.device, lib.deftet_rowdot_workspace_bytes(R))
-        _lib.check(lib.deftet_rowdot2_f32(_lib.ptr(a), _lib.ptr(b), a.numel() // max(R, 1), _lib.ptr(a2), _lib.ptr(b2), n2,
-                                          _lib.ptr(out), R, _lib.ptr(ws), ws.numel(), _lib.current_stream(a.device)),
-                   "deftet_rowdot2_f32")
+    _lib.call("deftet_rowdot2_f32", a.device, a, b, a.numel() // max(R, 1), a2, b2, n2, out, R, ws=lib.deftet_rowdot_workspace_bytes(R))
     return out
 
 
@@ -794,24 +745,18 @@ class _SqrtRowSum(torch.autograd.Function):
         if x.numel() == 0:
             return torch.zeros(R, device=x.device, dtype=torch.float32)
         out = torch.empty(R, device=x.device, dtype=torch.float32)
-        with _lib.on_device(x.device):
-            ws = _lib.workspace(x.device, lib.deftet_rowdot_workspace_bytes(R))
-            _lib.check(lib.deftet_sqrt_rowsum_f32(_lib.ptr(x), float(eps), _lib.ptr(out), R, x.numel() // max(R, 1), _lib.ptr(ws), ws.numel(),
-                                                  _lib.current_stream(x.device)), "deftet_sqrt_rowsum_f32")
+        _lib.call("deftet_sqrt_rowsum_f32", x.device, x, float(eps), out, R, x.numel() // max(R, 1), ws=lib.deftet_rowdot_workspace_bytes(R))
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         (x,) = ctx.saved_tensors
-        lib = _lib.load()
         g = _f32c(grad_out)
         gx = torch.empty_like(x)
         if x.numel() == 0:
             return gx, None
         R = x.shape[0]
-        with _lib.on_device(x.device):
-            _lib.check(lib.deftet_sqrt_rowsum_bwd_f32(_lib.ptr(x), ctx.eps, _lib.ptr(g), _lib.ptr(gx), R, x.numel() // max(R, 1),
-                                                      _lib.current_stream(x.device)), "deftet_sqrt_rowsum_bwd_f32")
+        _lib.call("deftet_sqrt_rowsum_bwd_f32", x.device, x, ctx.eps, g, gx, R, x.numel() // max(R, 1))
         return gx, None
 
 
@@ -829,84 +774,66 @@ def _i32_tets(tet_list, device):
     return t.to(device=device, dtype=torch.int32).contiguous()
 
 
-def _builder_ws(lib, dev, n_point, n_tet):
-    return _lib.workspace(dev, lib.deftet_builder_workspace_bytes(int(n_point), int(n_tet)))
+def _builder_bytes(n_point, n_tet):
+    return _lib.load().deftet_builder_workspace_bytes(int(n_point), int(n_tet))
 
 
 def tet_adj_share(tet_list, n_point, device):
     """int32 rows [2*n_shared, 3] = [t0,t1,f0],[t1,t0,f1] in ascending face-key order
     (utils/lib/tet_adj_share/run.cpp:40-97)."""
-    lib = _lib.load()
     dev = torch.device(device)
     tet = _i32_tets(tet_list, dev)
     _lib.require_gpu(tet)
     T = tet.shape[0]
     out = torch.empty(max(T * 8, 1), 3, dtype=torch.int32, device=dev)
     n = torch.zeros(1, dtype=torch.int32, device=dev)
-    with _lib.on_device(dev):
-        ws = _builder_ws(lib, dev, n_point, T)
-        _lib.check(lib.deftet_tet_adj_share_i32(_lib.ptr(tet), _lib.ptr(out), _lib.ptr(n), int(n_point), T, _lib.ptr(ws),
-                                                ws.numel(), _lib.current_stream(dev)), "deftet_tet_adj_share_i32")
+    _lib.call("deftet_tet_adj_share_i32", dev, tet, out, n, int(n_point), T, ws=_builder_bytes(n_point, T))
     return out[: int(n.item()) * 2]
 
 
 def tet_face_adj(tet_list, n_point, device, wrap32=True):
     """int32 rows [n,2] = [fa,fb] (utils/lib/tet_face_adj/run.cpp:18-92); two-phase: count, then fill."""
-    lib = _lib.load()
     dev = torch.device(device)
     tet = _i32_tets(tet_list, dev)
     _lib.require_gpu(tet)
     T = tet.shape[0]
     n = torch.zeros(1, dtype=torch.int64, device=dev)
-    with _lib.on_device(dev):
-        ws = _builder_ws(lib, dev, n_point, T)
-        st = _lib.current_stream(dev)
-        _lib.check(lib.deftet_tet_face_adj_i32(_lib.ptr(tet), None, 0, _lib.ptr(n), int(n_point), T, int(wrap32),
-                                               _lib.ptr(ws), ws.numel(), st), "deftet_tet_face_adj_i32(count)")
-        cnt = int(n.item())
-        out = torch.empty(max(cnt, 1), 2, dtype=torch.int32, device=dev)
-        _lib.check(lib.deftet_tet_face_adj_i32(_lib.ptr(tet), _lib.ptr(out), cnt, _lib.ptr(n), int(n_point), T, int(wrap32),
-                                               _lib.ptr(ws), ws.numel(), st), "deftet_tet_face_adj_i32(fill)")
+    nbytes = _builder_bytes(n_point, T)
+    _lib.call("deftet_tet_face_adj_i32", dev, tet, None, 0, n, int(n_point), T, int(wrap32), ws=nbytes, what="deftet_tet_face_adj_i32(count)")
+    cnt = int(n.item())
+    out = torch.empty(max(cnt, 1), 2, dtype=torch.int32, device=dev)
+    _lib.call("deftet_tet_face_adj_i32", dev, tet, out, cnt, n, int(n_point), T, int(wrap32), ws=nbytes, what="deftet_tet_face_adj_i32(fill)")
     return out[:cnt]
 
 
 def tet_point_adj(tet_list, n_point, device):
     """int32 [n,2] unique directed vertex pairs sorted by (a,b) (utils/lib/tet_point_adj/run.cpp:20-56)."""
-    lib = _lib.load()
     dev = torch.device(device)
     tet = _i32_tets(tet_list, dev)
     _lib.require_gpu(tet)
     T = tet.shape[0]
     out = torch.empty(max(T * 12, 1), 2, dtype=torch.int32, device=dev)
     n = torch.zeros(1, dtype=torch.int32, device=dev)
-    with _lib.on_device(dev):
-        ws = _builder_ws(lib, dev, n_point, T)
-        _lib.check(lib.deftet_tet_point_adj_i32(_lib.ptr(tet), _lib.ptr(out), _lib.ptr(n), int(n_point), T, _lib.ptr(ws),
-                                                ws.numel(), _lib.current_stream(dev)), "deftet_tet_point_adj_i32")
+    _lib.call("deftet_tet_point_adj_i32", dev, tet, out, n, int(n_point), T, ws=_builder_bytes(n_point, T))
     return out[: int(n.item())]
 
 
 def colaps_v(points_nx3):
     """(map_array int32 [N], inverse_idx int32 [k]) — utils/lib/colaps_v/run.cpp:39-59."""
     _lib.require_gpu(points_nx3)
-    lib = _lib.load()
     pts = _f32c(points_nx3)
     N = pts.shape[0]
     dev = pts.device
     m = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
     inv = torch.empty(max(N, 1), dtype=torch.int32, device=dev)
     n = torch.zeros(1, dtype=torch.int32, device=dev)
-    with _lib.on_device(dev):
-        ws = _builder_ws(lib, dev, N, 0)
-        _lib.check(lib.deftet_colaps_v_f32(_lib.ptr(pts), _lib.ptr(m), _lib.ptr(inv), _lib.ptr(n), N, _lib.ptr(ws), ws.numel(),
-                                           _lib.current_stream(dev)), "deftet_colaps_v_f32")
+    _lib.call("deftet_colaps_v_f32", dev, pts, m, inv, n, N, ws=_builder_bytes(N, 0))
     return m[:N], inv[: int(n.item())]
 
 
 def tet_to_face(tet_list, n_point, device, with_boundary=False):
     """(face_fx3, tetidx_fx2, tetfaceidx_fx2, boundary_fx3) int64, first-seen order —
     utils/tet_utils.py:208-256 / prepare_for_wz.py:49-104; raises on non-manifold input."""
-    lib = _lib.load()
     dev = torch.device(device)
     tet = _i32_tets(tet_list, dev)
     _lib.require_gpu(tet)
@@ -917,11 +844,7 @@ def tet_to_face(tet_list, n_point, device, with_boundary=False):
     tf2 = torch.empty(cap, 2, dtype=torch.int64, device=dev)
     b3 = torch.empty(cap, 3, dtype=torch.int64, device=dev)
     counts = torch.zeros(3, dtype=torch.int32, device=dev)
-    with _lib.on_device(dev):
-        ws = _builder_ws(lib, dev, n_point, T)
-        _lib.check(lib.deftet_tet_to_face_i32(_lib.ptr(tet), _lib.ptr(f3), _lib.ptr(t2), _lib.ptr(tf2), _lib.ptr(b3),
-                                              _lib.ptr(counts), int(n_point), T, int(with_boundary), _lib.ptr(ws), ws.numel(),
-                                              _lib.current_stream(dev)), "deftet_tet_to_face_i32")
+    _lib.call("deftet_tet_to_face_i32", dev, tet, f3, t2, tf2, b3, counts, int(n_point), T, int(with_boundary), ws=_builder_bytes(n_point, T))
     nf, nb, nm = (int(x) for x in counts.tolist())
     return f3[:nf], t2[:nf], tf2[:nf], b3[:nb], nm
 
@@ -939,10 +862,7 @@ def tet_neighbours(tet_list, n_point, device, want_face_owners=False):
     T = int(torch.as_tensor(tet_list).shape[0])
     nbr = torch.empty(T, 4, dtype=torch.int64, device=dev)
     owners = torch.empty(T * 4, 2, dtype=torch.int64, device=dev) if want_face_owners else None
-    with _lib.on_device(dev):
-        ws = _lib.workspace(dev, lib.deftet_tet_neighbours_workspace_bytes(T))
-        _lib.check(lib.deftet_tet_neighbours_i64(_lib.ptr(t2), _lib.ptr(tf2), int(t2.shape[0]), T, _lib.ptr(nbr), _lib.ptr(owners),
-                                                 _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)), "deftet_tet_neighbours_i64")
+    _lib.call("deftet_tet_neighbours_i64", dev, t2, tf2, int(t2.shape[0]), T, nbr, owners, ws=lib.deftet_tet_neighbours_workspace_bytes(T))
     return (nbr, owners) if want_face_owners else nbr
 
 
@@ -955,11 +875,8 @@ def face_edge_adj(face_fx3x3, n_max_nei=30, brute=False):
     face = _f32c(face_fx3x3)
     F = face.shape[0]
     adj = torch.full((F, n_max_nei), -1.0, device=face.device, dtype=torch.float32)    # utils.py:47
-    with _lib.on_device(face.device):
-        ws = None if brute else _lib.workspace(face.device, lib.deftet_face_edge_adj_workspace_bytes(F))
-        _lib.check(lib.deftet_face_edge_adj_f32(_lib.ptr(face), _lib.ptr(adj), F, n_max_nei, _lib.ptr(ws),
-                                                ws.numel() if ws is not None else 0, _lib.current_stream(face.device)),
-                   "deftet_face_edge_adj_f32")
+    _lib.call("deftet_face_edge_adj_f32", face.device, face, adj, F, n_max_nei,
+              ws=None if brute else lib.deftet_face_edge_adj_workspace_bytes(F))
     return adj
 
 
@@ -968,23 +885,18 @@ def host_ints(values, device, i32=False, i64=False, f32=False):
     (int32, int64, float32).  The values travel in a kernel's argument block (deftet_put_host_ints): no copy from pageable
     host memory — torch.tensor(list, device=...) blocks the Python thread until the stream has drained — and one launch for
     all dtypes."""
-    import ctypes
     vals = [int(v) for v in values]
     n = len(vals)
     outs = [torch.empty(n, device=device, dtype=dt) if want else None
             for want, dt in ((i32, torch.int32), (i64, torch.int64), (f32, torch.float32))]
     if n and any(o is not None for o in outs):
-        lib = _lib.load()
-        with _lib.on_device(torch.device(device)):
-            _lib.check(lib.deftet_put_host_ints((ctypes.c_longlong * n)(*vals), n, _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2]),
-                                                _lib.current_stream(torch.device(device))), "deftet_put_host_ints")
+        _lib.call("deftet_put_host_ints", torch.device(device), (ctypes.c_longlong * n)(*vals), n, *outs)
     got = tuple(o for o in outs if o is not None)
     return got[0] if len(got) == 1 else got
 
 
 def _host_counts(counts, B, hi, what):
-    import ctypes
-    c = [int(x) for x in counts]
+    c =[int(x) for x in counts]
     if len(c) != B or any(x < 0 or x > hi for x in c):
         raise RuntimeError("%s: need %d counts in [0, %d], got %s" % (what, B, hi, c))
     return (ctypes.c_int * B)(*c)
@@ -999,11 +911,8 @@ def face_edge_adj_ragged(face_bxfx3x3, n_face, n_max_nei=30, brute=False):
     B, F = face.shape[0], face.shape[1]
     cnt = _host_counts(n_face, B, F, "face_edge_adj_ragged")
     adj = torch.full((B, F, n_max_nei), -1.0, device=face.device, dtype=torch.float32)
-    with _lib.on_device(face.device):
-        ws = None if brute else _lib.workspace(face.device, lib.deftet_face_edge_adj_ragged_workspace_bytes(B, F))
-        _lib.check(lib.deftet_face_edge_adj_ragged_f32(_lib.ptr(face), _lib.ptr(adj), B, F, cnt, n_max_nei, _lib.ptr(ws),
-                                                       ws.numel() if ws is not None else 0, _lib.current_stream(face.device)),
-                   "deftet_face_edge_adj_ragged_f32")
+    _lib.call("deftet_face_edge_adj_ragged_f32", face.device, face, adj, B, F, cnt, n_max_nei,
+              ws=None if brute else lib.deftet_face_edge_adj_ragged_workspace_bytes(B, F))
     return adj
 
 
@@ -1015,11 +924,7 @@ def nn_index_ragged(queries_bxnx3, points_bxmx3, n_query, brute=False):
     B, N, M = q.shape[0], q.shape[1], p.shape[1]
     cnt = _host_counts(n_query, B, N, "nn_index_ragged")
     out = torch.zeros(B, N, device=q.device, dtype=torch.int32)
-    with _lib.on_device(q.device):
-        ws = None if brute else _lib.workspace(q.device, lib.deftet_nn_index_workspace_bytes(B, N, M))
-        _lib.check(lib.deftet_nn_index_ragged_f32(_lib.ptr(q), _lib.ptr(p), _lib.ptr(out), B, N, M, cnt, _lib.ptr(ws),
-                                                  ws.numel() if ws is not None else 0, _lib.current_stream(q.device)),
-                   "deftet_nn_index_ragged_f32")
+    _lib.call("deftet_nn_index_ragged_f32", q.device, q, p, out, B, N, M, cnt, ws=None if brute else lib.deftet_nn_index_workspace_bytes(B, N, M))
     return out
 
 
@@ -1029,22 +934,17 @@ class _ChamferToCloud(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tri, gt, counts, per_face, generator, uv=None):
-        lib = _lib.load()
         B, F, M, K = tri.shape[0], tri.shape[1], gt.shape[1], int(per_face)
         dev = tri.device
         # uv (optional, tests): the two uniform numbers per sample drawn by the caller instead of here
         r = torch.rand(2, B, F, K, device=dev, generator=generator) if uv is None else _f32c(uv).reshape(2, B, F, K)
         samples = torch.empty(B, F * K, 3, device=dev, dtype=torch.float32)
-        st = _lib.current_stream(dev)
-        with _lib.on_device(dev):
-            _lib.check(lib.deftet_face_samples_f32(_lib.ptr(tri), _lib.ptr(r), _lib.ptr(samples), B, F, K, st), "deftet_face_samples_f32")
+        _lib.call("deftet_face_samples_f32", dev, tri, r, samples, B, F, K)
         n_valid = [int(c) * K for c in counts]
         idx = nn_index_ragged(samples, gt, n_valid)
         nv = host_ints(n_valid, dev, i32=True)                        # (not torch.tensor(..., device=dev): that copy blocks until the stream drains)
         d = torch.empty(B, F * K, device=dev, dtype=torch.float32)
-        with _lib.on_device(dev):
-            _lib.check(lib.deftet_chamfer_fwd_f32(_lib.ptr(samples), _lib.ptr(gt), _lib.ptr(idx), _lib.ptr(nv), _lib.ptr(d), B, F * K, M, st),
-                       "deftet_chamfer_fwd_f32")
+        _lib.call("deftet_chamfer_fwd_f32", dev, samples, gt, idx, nv, d, B, F * K, M)
         ctx.save_for_backward(samples, gt, idx, nv, d, r)
         ctx.dims = (B, F, K, M)
         return rowdot(d)
@@ -1053,13 +953,9 @@ class _ChamferToCloud(torch.autograd.Function):
     def backward(ctx, grad_sum):
         samples, gt, idx, nv, d, r = ctx.saved_tensors
         B, F, K, M = ctx.dims
-        lib = _lib.load()
         g = _f32c(grad_sum)
         grad_tri = torch.empty(B, F, 3, 3, device=samples.device, dtype=torch.float32)
-        with _lib.on_device(samples.device):
-            _lib.check(lib.deftet_chamfer_bwd_f32(_lib.ptr(samples), _lib.ptr(gt), _lib.ptr(idx), _lib.ptr(nv), _lib.ptr(d), _lib.ptr(r),
-                                                  _lib.ptr(g), _lib.ptr(grad_tri), B, F, K, M, _lib.current_stream(samples.device)),
-                       "deftet_chamfer_bwd_f32")
+        _lib.call("deftet_chamfer_bwd_f32", samples.device, samples, gt, idx, nv, d, r, g, grad_tri, B, F, K, M)
         return grad_tri, None, None, None, None, None
 
 
@@ -1078,29 +974,21 @@ def chamfer_to_cloud(tri_bxfx3x3, gt_bxmx3, counts, per_face=20, generator=None,
 class _NormalConsistency(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tri, adj, n_face):
-        lib = _lib.load()
         B, F, K = tri.shape[0], tri.shape[1], adj.shape[2]
         loss = torch.empty(B, device=tri.device, dtype=torch.float32)
         nrm = torch.empty(B, F, 3, device=tri.device, dtype=torch.float32)
         cnt = torch.empty(B, device=tri.device, dtype=torch.float32)
-        with _lib.on_device(tri.device):
-            _lib.check(lib.deftet_normal_consistency_fwd_f32(_lib.ptr(tri), _lib.ptr(adj), _lib.ptr(n_face), _lib.ptr(loss), _lib.ptr(nrm),
-                                                             _lib.ptr(cnt), B, F, K, _lib.current_stream(tri.device)),
-                       "deftet_normal_consistency_fwd_f32")
+        _lib.call("deftet_normal_consistency_fwd_f32", tri.device, tri, adj, n_face, loss, nrm, cnt, B, F, K)
         ctx.save_for_backward(tri, adj, n_face, nrm, cnt)
         return loss
 
     @staticmethod
     def backward(ctx, g):
         tri, adj, n_face, nrm, cnt = ctx.saved_tensors
-        lib = _lib.load()
         B, F, K = tri.shape[0], tri.shape[1], adj.shape[2]
         gtri = torch.empty_like(tri)
         acc = torch.empty(B, F, 3, device=tri.device, dtype=torch.float32)
-        with _lib.on_device(tri.device):
-            _lib.check(lib.deftet_normal_consistency_bwd_f32(_lib.ptr(tri), _lib.ptr(adj), _lib.ptr(n_face), _lib.ptr(nrm), _lib.ptr(cnt),
-                                                             _lib.ptr(_f32c(g)), _lib.ptr(gtri), _lib.ptr(acc), B, F, K,
-                                                             _lib.current_stream(tri.device)), "deftet_normal_consistency_bwd_f32")
+        _lib.call("deftet_normal_consistency_bwd_f32", tri.device, tri, adj, n_face, nrm, cnt, _f32c(g), gtri, acc, B, F, K)
         return gtri, None, None
 
 
@@ -1125,12 +1013,8 @@ def tri_dist_fwd(pts_bxpx3, face_bxfx3x3, n_face_b, brute=False, want_order=Fals
     order = None
     if want_order and not brute and face.shape[1] > 0 and B * P > 0:
         order = torch.empty(B, P, device=pts.device, dtype=torch.int32)
-    with _lib.on_device(pts.device):
-        ws = None if brute else _lib.workspace(pts.device, lib.deftet_tri_dist_workspace_bytes(B, P, face.shape[1]))
-        _lib.check(lib.deftet_tri_dist_fwd_order_f32(_lib.ptr(pts), _lib.ptr(face), _lib.ptr(nfb), _lib.ptr(d), _lib.ptr(f),
-                                                     _lib.ptr(order), B, P, face.shape[1], _lib.ptr(ws),
-                                                     ws.numel() if ws is not None else 0, _lib.current_stream(pts.device)),
-                   "deftet_tri_dist_fwd_order_f32")
+    _lib.call("deftet_tri_dist_fwd_order_f32", pts.device, pts, face, nfb, d, f, order, B, P, face.shape[1],
+              ws=None if brute else lib.deftet_tri_dist_workspace_bytes(B, P, face.shape[1]))
     return (d, f, order) if want_order else (d, f)
 
 
@@ -1138,18 +1022,13 @@ def tri_dist_bwd(pts_bxpx3, face_bxfx3x3, closest_f, dl_dd, deterministic=False,
     """dL/dface f32 [B,F,3,3] — tet_analytic_distance_back.cu:591-715.  order: the forward's point order (see
     tri_dist_fwd); with it the atomic path adds up a wavefront's contributions per distinct face first."""
     _lib.require_gpu(pts_bxpx3, face_bxfx3x3, closest_f, dl_dd)
-    lib = _lib.load()
     pts, face, cf, g = _f32c(pts_bxpx3), _f32c(face_bxfx3x3), _f32c(closest_f), _f32c(dl_dd)
     B, P, F = pts.shape[0], pts.shape[1], face.shape[1]
     out = torch.zeros(B, F, 3, 3, device=pts.device, dtype=torch.float32)               # utils.py:65
-    with _lib.on_device(pts.device):
-        if order is not None and not deterministic:
-            _lib.check(lib.deftet_tri_dist_bwd_order_f32(_lib.ptr(pts), _lib.ptr(face), _lib.ptr(cf), _lib.ptr(g),
-                                                         _lib.ptr(order.contiguous()), _lib.ptr(out), B, P, F,
-                                                         _lib.current_stream(pts.device)), "deftet_tri_dist_bwd_order_f32")
-        else:
-            _lib.check(lib.deftet_tri_dist_bwd_f32(_lib.ptr(pts), _lib.ptr(face), _lib.ptr(cf), _lib.ptr(g), _lib.ptr(out), B, P, F,
-                                                   int(deterministic), _lib.current_stream(pts.device)), "deftet_tri_dist_bwd_f32")
+    if order is not None and not deterministic:
+        _lib.call("deftet_tri_dist_bwd_order_f32", pts.device, pts, face, cf, g, order.contiguous(), out, B, P, F)
+    else:
+        _lib.call("deftet_tri_dist_bwd_f32", pts.device, pts, face, cf, g, out, B, P, F, int(deterministic))
     return out
 
 
@@ -1161,11 +1040,7 @@ def nn_index(queries_bxnx3, points_bxmx3, brute=False):
     q, p = _f32c(queries_bxnx3), _f32c(points_bxmx3)
     B, N, M = q.shape[0], q.shape[1], p.shape[1]
     out = torch.zeros(B, N, device=q.device, dtype=torch.int32)                         # nearest_neighbor.py:32-33
-    with _lib.on_device(q.device):
-        ws = None if brute else _lib.workspace(q.device, lib.deftet_nn_index_workspace_bytes(B, N, M))
-        _lib.check(lib.deftet_nn_index_f32(_lib.ptr(q), _lib.ptr(p), _lib.ptr(out), B, N, M, _lib.ptr(ws),
-                                           ws.numel() if ws is not None else 0, _lib.current_stream(q.device)),
-                   "deftet_nn_index_f32")
+    _lib.call("deftet_nn_index_f32", q.device, q, p, out, B, N, M, ws=None if brute else lib.deftet_nn_index_workspace_bytes(B, N, M))
     return out
 
 
@@ -1184,10 +1059,7 @@ def check_sign(verts_bxvx3, faces_fx3, points_bxnx3, brute=False, return_count=F
     cnt = torch.empty(B, N, device=dev, dtype=torch.int32) if return_count else None
     bad = torch.zeros(1, device=dev, dtype=torch.int32)
     algo = 1 if brute else 0
-    with _lib.on_device(dev):
-        ws = _lib.workspace(dev, lib.deftet_check_sign_workspace_bytes(B, F, algo))
-        _lib.check(lib.deftet_check_sign_f32(_lib.ptr(v), _lib.ptr(f), _lib.ptr(p), _lib.ptr(out), _lib.ptr(cnt), _lib.ptr(bad), B, V, F, N,
-                                             algo, _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)), "deftet_check_sign_f32")
+    _lib.call("deftet_check_sign_f32", dev, v, f, p, out, cnt, bad, B, V, F, N, algo, ws=lib.deftet_check_sign_workspace_bytes(B, F, algo))
     if check and int(bad.item()):
         raise IndexError("check_sign: face index outside [0, %d)" % V)
     inside = out.view(torch.bool)                            # 0 / 1 bytes: a reinterpretation, not a conversion launch
@@ -1215,11 +1087,8 @@ def check_sign_ragged(verts_list, faces_list, points_bxnx3, brute=False, return_
     bad = torch.zeros(1, device=dev, dtype=torch.int32)
     algo = 1 if brute else 0
     ftot, fmax = int(sum(f_cnt)), int(max(f_cnt) if f_cnt else 0)
-    with _lib.on_device(dev):
-        ws = _lib.workspace(dev, lib.deftet_check_sign_ragged_workspace_bytes(B, ftot, fmax, algo))
-        _lib.check(lib.deftet_check_sign_ragged_f32(_lib.ptr(v_cat), _lib.ptr(v_off), _lib.ptr(f_cat), _lib.ptr(f_off), _lib.ptr(p),
-                                                    _lib.ptr(out), _lib.ptr(cnt), _lib.ptr(bad), B, ftot, fmax, N, algo, _lib.ptr(ws),
-                                                    ws.numel(), _lib.current_stream(dev)), "deftet_check_sign_ragged_f32")
+    _lib.call("deftet_check_sign_ragged_f32", dev, v_cat, v_off, f_cat, f_off, p, out, cnt, bad, B, ftot, fmax, N, algo,
+              ws=lib.deftet_check_sign_ragged_workspace_bytes(B, ftot, fmax, algo))
     if check and int(bad.item()):
         raise IndexError("check_sign_ragged: face index outside its mesh")
     inside = out.view(torch.bool)                            # 0 / 1 bytes: a reinterpretation, not a conversion launch
@@ -1240,11 +1109,8 @@ def _winding_call(name, v, v_off, f, f_off, p, B, V, ftot, fmax, algo, beta, che
     N, dev, a = p.shape[1], p.device, WINDING_ALGOS[algo]
     out = torch.empty(B, N, device=dev, dtype=torch.float32)
     bad = torch.zeros(4, device=dev, dtype=torch.int32)
-    with _lib.on_device(dev):
-        ws = _lib.workspace(dev, lib.deftet_winding_number_workspace_bytes(B, ftot, fmax, N, a))
-        _lib.check(lib.deftet_winding_number_f32(_lib.ptr(v), _lib.ptr(v_off), _lib.ptr(f), _lib.ptr(f_off), _lib.ptr(p), _lib.ptr(out),
-                                                 _lib.ptr(bad), B, V, ftot, fmax, N, a, beta, _lib.ptr(ws), ws.numel(),
-                                                 _lib.current_stream(dev)), "deftet_winding_number_f32")
+    _lib.call("deftet_winding_number_f32", dev, v, v_off, f, f_off, p, out, bad, B, V, ftot, fmax, N, a, beta,
+              ws=lib.deftet_winding_number_workspace_bytes(B, ftot, fmax, N, a))
     if check:
         n_idx, n_corner, n_point = bad[:3].tolist()
         if n_idx:
@@ -1319,16 +1185,12 @@ def tet_edges(tet_tx4, n_point):
     """(edges [E,2] int64 — unique (min,max) rows in lexicographic order, tet_edge [T,6] int64):
     generate_edge + generate_tet_edge_idx of prepare_for_wz.py:184-236."""
     _lib.require_gpu(tet_tx4)
-    lib = _lib.load()
     tet = _i64_tets(tet_tx4)
     T, dev = tet.shape[0], tet.device
     edges = torch.empty(max(6 * T, 1), 2, device=dev, dtype=torch.int64)
     tet_edge = torch.empty(T, 6, device=dev, dtype=torch.int64)
     cnt = torch.zeros(2, device=dev, dtype=torch.int32)
-    with _lib.on_device(dev):
-        ws = _builder_ws(lib, dev, n_point, T)
-        _lib.check(lib.deftet_tet_edges_i64(_lib.ptr(tet), _lib.ptr(edges), _lib.ptr(tet_edge), _lib.ptr(cnt), _lib.ptr(cnt[1:]),
-                                            int(n_point), T, _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)), "deftet_tet_edges_i64")
+    _lib.call("deftet_tet_edges_i64", dev, tet, edges, tet_edge, cnt, cnt[1:], int(n_point), T, ws=_builder_bytes(n_point, T))
     n, bad = cnt.tolist()
     if bad:
         raise IndexError("tet_edges: vertex index outside [0, %d)" % n_point)
@@ -1338,7 +1200,6 @@ def tet_edges(tet_tx4, n_point):
 def subdivide(tet_tx4, points_px3, feat_pxk, subdiv_sig=None):
     """(points_new [P+E,3], feat_new [P+E,K], tet_new [T',4]): generate_subdivision, prepare_for_wz.py:255-301."""
     _lib.require_gpu(tet_tx4, points_px3, feat_pxk, subdiv_sig)
-    lib = _lib.load()
     tet, pts, feat = _i64_tets(tet_tx4), _f32c(points_px3), _f32c(feat_pxk)
     P, K, T, dev = pts.shape[0], feat.shape[1], tet.shape[0], tet.device
     if feat.shape[0] != P or pts.shape[1] != 3:
@@ -1354,11 +1215,7 @@ def subdivide(tet_tx4, points_px3, feat_pxk, subdiv_sig=None):
     fn = torch.empty(P + E, K, device=dev, dtype=torch.float32)
     tn = torch.empty(max(8 * T, 1), 4, device=dev, dtype=torch.int64)
     cnt = torch.zeros(1, device=dev, dtype=torch.int32)
-    with _lib.on_device(dev):
-        ws = _builder_ws(lib, dev, P, T)
-        _lib.check(lib.deftet_subdivide_f32(_lib.ptr(tet), _lib.ptr(tet_edge), _lib.ptr(edges), _lib.ptr(pts), _lib.ptr(feat), _lib.ptr(sig),
-                                            _lib.ptr(pn), _lib.ptr(fn), _lib.ptr(tn), _lib.ptr(cnt), P, T, E, K,
-                                            _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)), "deftet_subdivide_f32")
+    _lib.call("deftet_subdivide_f32", dev, tet, tet_edge, edges, pts, feat, sig, pn, fn, tn, cnt, P, T, E, K, ws=_builder_bytes(P, T))
     return pn, fn, tn[: int(cnt.item())]
 
 
@@ -1366,58 +1223,46 @@ def point_adj_idx(n_point, tet_tx4):
     """(pointadj_idx [P,m] int64 — ascending neighbours, -1 padded; adjsum [P,1] f32):
     generate_point_adj_idx, prepare_for_wz.py:134-146, without the dense P x P matrix."""
     _lib.require_gpu(tet_tx4)
-    lib = _lib.load()
     dev, P = tet_tx4.device, int(n_point)
     pairs = tet_point_adj(tet_tx4.to(torch.int32), P, dev)                 # sorted unique ordered pairs (A4)
     n = pairs.shape[0]
     adjsum = torch.zeros(P, 1, device=dev, dtype=torch.float32)
     mx = torch.zeros(1, device=dev, dtype=torch.int32)
-    with _lib.on_device(dev):
-        ws = _lib.workspace(dev, (P + 1) * 4 + 256)
-        args = (_lib.ptr(pairs), n, P)
-        _lib.check(lib.deftet_point_adj_table_i64(*args, None, 0, _lib.ptr(adjsum), _lib.ptr(mx), _lib.ptr(ws), ws.numel(),
-                                                  _lib.current_stream(dev)), "deftet_point_adj_table_i64")
-        m = int(mx.item())
-        table = torch.empty(P, m, device=dev, dtype=torch.int64)
-        if m > 0:
-            _lib.check(lib.deftet_point_adj_table_i64(*args, _lib.ptr(table), m, None, None, _lib.ptr(ws), ws.numel(),
-                                                      _lib.current_stream(dev)), "deftet_point_adj_table_i64")
+    nbytes = (P + 1) * 4 + 256
+    _lib.call("deftet_point_adj_table_i64", dev, pairs, n, P, None, 0, adjsum, mx, ws=nbytes)
+    m = int(mx.item())
+    table = torch.empty(P, m, device=dev, dtype=torch.int64)
+    if m > 0:
+        _lib.call("deftet_point_adj_table_i64", dev, pairs, n, P, table, m, None, None, ws=nbytes)
     return table, adjsum
 
 
 def delete_tet(tet_tx4, tet_weights_txk, thres=0.01):
     """tets whose largest weight is > thres, order kept: delete_tet, prepare_for_wz.py:171-180."""
     _lib.require_gpu(tet_tx4, tet_weights_txk)
-    lib = _lib.load()
     tet, w = _i64_tets(tet_tx4), _f32c(tet_weights_txk)
     T, dev = tet.shape[0], tet.device
     if w.dim() != 2 or w.shape[0] != T:
         raise RuntimeError("delete_tet: weights [T,k] expected")
     out = torch.empty(max(T, 1), 4, device=dev, dtype=torch.int64)
     cnt = torch.zeros(1, device=dev, dtype=torch.int32)
-    with _lib.on_device(dev):
-        ws = _builder_ws(lib, dev, 0, T)
-        _lib.check(lib.deftet_delete_tet_i64(_lib.ptr(tet), _lib.ptr(w), float(np.float32(thres)), _lib.ptr(out), _lib.ptr(cnt), T, w.shape[1],
-                                             _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)), "deftet_delete_tet_i64")
+    _lib.call("deftet_delete_tet_i64", dev, tet, w, float(np.float32(thres)), out, cnt, T, w.shape[1], ws=_builder_bytes(0, T))
     return out[: int(cnt.item())]
 
 
 def tet_neighbour_weights(tet_weights_txk, tet_neighbour_idx_tx4, neilevel=1):
     """tetweights2tetneighbourweights, diff_render/diftet_6_subdiv/3_model/deftet.py:316-331."""
     _lib.require_gpu(tet_weights_txk, tet_neighbour_idx_tx4)
-    lib = _lib.load()
     w = _f32c(tet_weights_txk)
     nei = tet_neighbour_idx_tx4.long().contiguous()
     T = w.shape[0]
     if nei.shape != (T, 4):
         raise RuntimeError("tet_neighbour_weights: neighbour index [T,4] expected")
-    with _lib.on_device(w.device):
-        for _ in range(int(neilevel)):
-            K = w.shape[1]
-            out = torch.empty(T, 4 * K, device=w.device, dtype=torch.float32)
-            _lib.check(lib.deftet_tet_neighbour_weights_f32(_lib.ptr(w), _lib.ptr(nei), _lib.ptr(out), T, K,
-                                                            _lib.current_stream(w.device)), "deftet_tet_neighbour_weights_f32")
-            w = out
+    for _ in range(int(neilevel)):
+        K = w.shape[1]
+        out = torch.empty(T, 4 * K, device=w.device, dtype=torch.float32)
+        _lib.call("deftet_tet_neighbour_weights_f32", w.device, w, nei, out, T, K)
+        w = out
     return w
 
 
@@ -1435,16 +1280,13 @@ def tet_gather(pos_bxvx3, tet_idx, check=False):
     tet_idx int [T,4] (shared) or [B,T,4].  check=True synchronises and raises on an index
     outside [0,V) like torch.gather does (otherwise such corners are NaN)."""
     _lib.require_gpu(pos_bxvx3, tet_idx)
-    lib = _lib.load()
     pos, idx = _f32c(pos_bxvx3), _idx64(tet_idx)
     B, V, T = pos.shape[0], pos.shape[1], idx.shape[1]
     if idx.shape[0] not in (1, B) or idx.shape[2] != 4 or pos.shape[2] != 3:
         raise RuntimeError("tet_gather: pos [B,V,3] and tet_idx [T,4] or [B,T,4] expected")
     out = torch.empty(B, T, 4, 3, device=pos.device, dtype=torch.float32)
     bad = torch.zeros(1, device=pos.device, dtype=torch.int32) if check else None
-    with _lib.on_device(pos.device):
-        _lib.check(lib.deftet_tet_gather_fwd_f32(_lib.ptr(pos), _lib.ptr(idx), _lib.ptr(out), _lib.ptr(bad), B, V, T, idx.shape[0],
-                                                 _lib.current_stream(pos.device)), "deftet_tet_gather_fwd_f32")
+    _lib.call("deftet_tet_gather_fwd_f32", pos.device, pos, idx, out, bad, B, V, T, idx.shape[0])
     if check and int(bad.item()):
         raise RuntimeError("tet_gather: index out of range [0, %d)" % V)
     return out
@@ -1461,10 +1303,7 @@ def tet_vertex_csr(tet_idx, n_vertex):
     offsets = torch.empty(Bi * V + 1, device=dev, dtype=torch.int32)
     slots = torch.empty(Bi * T * 4, device=dev, dtype=torch.int32)
     bad = torch.zeros(1, device=dev, dtype=torch.int32)
-    with _lib.on_device(dev):
-        ws = _lib.workspace(dev, lib.deftet_tet_vertex_csr_workspace_bytes(Bi, V, T))
-        _lib.check(lib.deftet_tet_vertex_csr_i32(_lib.ptr(idx), _lib.ptr(offsets), _lib.ptr(slots), _lib.ptr(bad), Bi, V, T,
-                                                 _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)), "deftet_tet_vertex_csr_i32")
+    _lib.call("deftet_tet_vertex_csr_i32", dev, idx, offsets, slots, bad, Bi, V, T, ws=lib.deftet_tet_vertex_csr_workspace_bytes(Bi, V, T))
     if int(bad.item()):
         raise RuntimeError("tet_vertex_csr: index out of range [0, %d)" % V)
     return offsets, slots, Bi
@@ -1474,7 +1313,6 @@ def tet_gather_bwd(grad_tet_bxtx4x3, csr, n_vertex, out=None):
     """grad_pos f32 [B,V,3] = per-vertex sum of grad_tet in ascending (tet, corner) order
     (deterministic, no atomics).  out: existing [B,V,3] tensor to ADD to."""
     _lib.require_gpu(grad_tet_bxtx4x3)
-    lib = _lib.load()
     g = _f32c(grad_tet_bxtx4x3)
     offsets, slots, Bi = csr
     B, T, V = g.shape[0], g.shape[1], int(n_vertex)
@@ -1484,9 +1322,7 @@ def tet_gather_bwd(grad_tet_bxtx4x3, csr, n_vertex, out=None):
     if acc and (out.shape != (B, V, 3) or out.dtype != torch.float32 or not out.is_contiguous()):
         raise RuntimeError("tet_gather_bwd: out must be contiguous f32 [B,V,3]")
     gp = out if acc else torch.empty(B, V, 3, device=g.device, dtype=torch.float32)
-    with _lib.on_device(g.device):
-        _lib.check(lib.deftet_tet_gather_bwd_f32(_lib.ptr(g), _lib.ptr(offsets), _lib.ptr(slots), _lib.ptr(gp), B, V, T, Bi,
-                                                 1 if acc else 0, _lib.current_stream(g.device)), "deftet_tet_gather_bwd_f32")
+    _lib.call("deftet_tet_gather_bwd_f32", g.device, g, offsets, slots, gp, B, V, T, Bi, 1 if acc else 0)
     return gp
 
 
@@ -1531,13 +1367,8 @@ class VertexAdjacency:
         vals = torch.empty(nnz, device=dev, dtype=torch.float32) if want_vals else None
         t_vals = torch.empty(nnz, device=dev, dtype=torch.float32) if want_vals else None
         bad = torch.empty(1, device=dev, dtype=torch.int32)
-        with _lib.on_device(dev):
-            ws = _lib.workspace(dev, lib.deftet_vertex_adjacency_workspace_bytes(nnz, V))
-            _lib.check(lib.deftet_vertex_adjacency_csr_i32(_lib.ptr(rows), _lib.ptr(cols), rows.element_size(), _lib.ptr(values), nnz, V,
-                                                           order, _lib.ptr(offsets), _lib.ptr(out_cols), _lib.ptr(vals),
-                                                           _lib.ptr(t_offsets), _lib.ptr(t_rows), _lib.ptr(t_vals), _lib.ptr(bad),
-                                                           _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
-                       "deftet_vertex_adjacency_csr_i32")
+        _lib.call("deftet_vertex_adjacency_csr_i32", dev, rows, cols, rows.element_size(), values, nnz, V, order, offsets, out_cols, vals,
+                  t_offsets, t_rows, t_vals, bad, ws=lib.deftet_vertex_adjacency_workspace_bytes(nnz, V))
         # (the one host sync: build time only; `checked`: the caller's own kernel has already refused indices outside [0, V))
         if not checked and int(bad.item()):
             raise RuntimeError("VertexAdjacency: vertex index out of range [0, %d)" % V)
@@ -1612,12 +1443,8 @@ class _VertexLaplacian(torch.autograd.Function):
         dev = x.device
         r = torch.empty(B, V, C, device=dev, dtype=torch.float32)
         out = torch.empty((B,) if reduction == VLAP_SHAPE else (B, V, C), device=dev, dtype=torch.float32)
-        with _lib.on_device(dev):
-            ws = _lib.workspace(dev, lib.deftet_vertex_laplacian_workspace_bytes(B, V)) if reduction == VLAP_SHAPE else None
-            _lib.check(lib.deftet_vertex_laplacian_fwd_f32(_lib.ptr(x), _lib.ptr(adj.offsets), _lib.ptr(adj.cols), _lib.ptr(adj.vals),
-                                                           _lib.ptr(adj.row_weights), adj.weighting, reduction, B, V, C, adj.nnz,
-                                                           _lib.ptr(r), _lib.ptr(out), _lib.ptr(ws), ws.numel() if ws is not None else 0,
-                                                           _lib.current_stream(dev)), "deftet_vertex_laplacian_fwd_f32")
+        _lib.call("deftet_vertex_laplacian_fwd_f32", dev, x, adj.offsets, adj.cols, adj.vals, adj.row_weights, adj.weighting, reduction,
+                  B, V, C, adj.nnz, r, out, ws=lib.deftet_vertex_laplacian_workspace_bytes(B, V) if reduction == VLAP_SHAPE else None)
         ctx.save_for_backward(r)
         ctx.adj, ctx.reduction = adj, reduction
         return out
@@ -1628,15 +1455,11 @@ class _VertexLaplacian(torch.autograd.Function):
             return None, None, None
         (r,) = ctx.saved_tensors
         adj, reduction = ctx.adj, ctx.reduction
-        lib = _lib.load()
         g = _f32c(grad_out)
         B, V, C = r.shape
         dx = torch.empty_like(r)
-        with _lib.on_device(r.device):
-            _lib.check(lib.deftet_vertex_laplacian_bwd_f32(_lib.ptr(r), _lib.ptr(g), _lib.ptr(adj.t_offsets), _lib.ptr(adj.t_rows),
-                                                           _lib.ptr(adj.t_vals), _lib.ptr(adj.row_weights), adj.weighting, reduction,
-                                                           B, V, C, adj.nnz, _lib.ptr(dx), _lib.current_stream(r.device)),
-                       "deftet_vertex_laplacian_bwd_f32")
+        _lib.call("deftet_vertex_laplacian_bwd_f32", r.device, r, g, adj.t_offsets, adj.t_rows, adj.t_vals, adj.row_weights, adj.weighting,
+                  reduction, B, V, C, adj.nnz, dx)
         return dx, None, None
 
 
@@ -1659,12 +1482,9 @@ def vertex_laplacian(x, adjacency, reduction="shape"):
 # --------------------------------------------------------------------------------- vertex aggregation
 def _vertex_aggregate(x, offsets, idx, vals, nnz):
     """out = M·x for the CSR (offsets, idx, vals): the one library call both directions make"""
-    lib = _lib.load()
     B, V, C = x.shape
     out = torch.empty(B, V, C, device=x.device, dtype=torch.float32)
-    with _lib.on_device(x.device):
-        _lib.check(lib.deftet_vertex_aggregate_f32(_lib.ptr(x), _lib.ptr(offsets), _lib.ptr(idx), _lib.ptr(vals), B, V, C, nnz,
-                                                   _lib.ptr(out), _lib.current_stream(x.device)), "deftet_vertex_aggregate_f32")
+    _lib.call("deftet_vertex_aggregate_f32", x.device, x, offsets, idx, vals, B, V, C, nnz, out)
     return out
 
 
@@ -1727,11 +1547,8 @@ def boundary_index(tet_face_fx3, tet_idx_fx2, occ_bxn, mode=1):
     dev = occ.device
     out = torch.empty(max(B * Fi, 1), 3, dtype=torch.int64, device=dev)
     offs = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-    with _lib.on_device(dev):
-        ws = _lib.workspace(dev, lib.deftet_boundary_index_workspace_bytes(B, Fi))
-        _lib.check(lib.deftet_boundary_index_i64(_lib.ptr(face), _lib.ptr(tidx), _lib.ptr(occ), _lib.ptr(out), _lib.ptr(offs),
-                                                 B, T, Fi, int(mode), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
-                   "deftet_boundary_index_i64")
+    _lib.call("deftet_boundary_index_i64", dev, face, tidx, occ, out, offs, B, T, Fi, int(mode),
+              ws=lib.deftet_boundary_index_workspace_bytes(B, Fi))
     o = offs.tolist()                                   # one sync (the reference syncs once per shape)
     return [out[o[b]:o[b + 1]] for b in range(B)]
 
@@ -1763,11 +1580,8 @@ class _TetEnergies(torch.autograd.Function):
         dev = tet.device
         out = torch.empty(B, 3, device=dev, dtype=torch.float32)
         stats = torch.empty(B, 8, device=dev, dtype=torch.float64)
-        with _lib.on_device(dev):
-            ws = _lib.workspace(dev, lib.deftet_tet_energies_workspace_bytes2(B, T))
-            _lib.check(lib.deftet_tet_energies_fwd_f32(_lib.ptr(tet), _lib.ptr(inv), _lib.ptr(out), _lib.ptr(stats), B, T,
-                                                       int(pow_v), int(pow_e), float(scale), _lib.ptr(ws), ws.numel(),
-                                                       _lib.current_stream(dev)), "deftet_tet_energies_fwd_f32")
+        _lib.call("deftet_tet_energies_fwd_f32", dev, tet, inv, out, stats, B, T, int(pow_v), int(pow_e), float(scale),
+                  ws=lib.deftet_tet_energies_workspace_bytes2(B, T))
         ctx.save_for_backward(tet, inv if inv is not None else tet.new_empty(0), stats)
         ctx.cfg = (int(pow_v), int(pow_e), float(scale), inv is not None)
         return out
@@ -1776,14 +1590,10 @@ class _TetEnergies(torch.autograd.Function):
     def backward(ctx, grad_out):
         tet, inv, stats = ctx.saved_tensors
         pow_v, pow_e, scale, has_inv = ctx.cfg
-        lib = _lib.load()
         g = _f32c(grad_out)
         B, T = tet.shape[0], tet.shape[1]
         grad_tet = torch.empty_like(tet)
-        with _lib.on_device(tet.device):
-            _lib.check(lib.deftet_tet_energies_bwd_f32(_lib.ptr(tet), _lib.ptr(inv) if has_inv else None, _lib.ptr(stats),
-                                                       _lib.ptr(g), _lib.ptr(grad_tet), B, T, pow_v, pow_e, scale,
-                                                       _lib.current_stream(tet.device)), "deftet_tet_energies_bwd_f32")
+        _lib.call("deftet_tet_energies_bwd_f32", tet.device, tet, inv if has_inv else None, stats, g, grad_tet, B, T, pow_v, pow_e, scale)
         return grad_tet, None, None, None, None
 
 
@@ -1812,7 +1622,6 @@ def tet_face_neighbours(tet_list, n_point, device):
     """TetFaceNeighbours of a tet list — row t of the i-th matrix of tet_adj_share (utils/lib/tet_adj_share/run.cpp:40-97,
     diff_render/diftet_6_subdiv/3_model/utils_tetsv.py:16-75) as one table.  Raises ValueError when a face has more than two
     owners, as both reference functions do."""
-    lib = _lib.load()
     dev = torch.device(device)
     if dev.type != "cuda" or not torch.cuda.is_available():
         raise _lib.DefTetHipError("deftet_amd operators need a GPU (got device %s); there is no CPU fallback" % dev)
@@ -1824,9 +1633,7 @@ def tet_face_neighbours(tet_list, n_point, device):
         raise ValueError("tet_face_neighbours: empty tet list")
     n64 = torch.empty(T, 4, dtype=torch.int64, device=dev)
     n32 = torch.empty(T, 4, dtype=torch.int32, device=dev)
-    with _lib.on_device(dev):
-        _lib.check(lib.deftet_tet_face_neighbours_i64(_lib.ptr(t2), _lib.ptr(tf2), int(t2.shape[0]), T, _lib.ptr(n64), _lib.ptr(n32),
-                                                      _lib.current_stream(dev)), "deftet_tet_face_neighbours_i64")
+    _lib.call("deftet_tet_face_neighbours_i64", dev, t2, tf2, int(t2.shape[0]), T, n64, n32)
     return TetFaceNeighbours(n64, n32)
 
 
@@ -1926,25 +1733,19 @@ def surface_extract(tet_bxfx4x3, occ, nbr, mode, thres=None, attr=None, vertex_w
         C = int(attr.shape[3])
     h = float(thres) if thres is not None else 0.0
     offs = torch.empty(B + 1, dtype=torch.int32, device=dev)
-    with _lib.on_device(dev):
-        st = _lib.current_stream(dev)
-        # the count pass leaves the row bases in its workspace for the fill pass: a tensor of this call, not the shared one
-        wsb = lib.deftet_surface_extract_workspace_bytes(B, T, int(w is not None))
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        _lib.check(lib.deftet_surface_extract_count_f32(_lib.ptr(occ), _lib.ptr(w), _lib.ptr(idx32), V, _lib.ptr(nbr.table32), B, T, mode,
-                                                        h, _lib.ptr(offs), _lib.ptr(ws), wsb, st), "deftet_surface_extract_count_f32")
-        o = offs.tolist()                               # the one sync (the reference syncs per shape and per local face)
-        if o[B] < 0:
-            raise RuntimeError("surface_extract: a neighbour or vertex index is out of range")
-        F = o[B]
-        face = torch.empty(F, 3, 3, dtype=torch.float32, device=dev)
-        fattr = torch.empty(F, 3, C, dtype=torch.float32, device=dev) if attr is not None else None
-        index = torch.empty(F, 2, dtype=torch.int64, device=dev) if return_index else None
-        faces = torch.empty(F, 3, dtype=torch.int64, device=dev) if return_faces else None
-        _lib.check(lib.deftet_surface_extract_fill_f32(_lib.ptr(tet), _lib.ptr(attr), C, _lib.ptr(occ) if w is None else None,
-                                                       _lib.ptr(idx32), _lib.ptr(nbr.table32), B, T, mode, h, F, _lib.ptr(face),
-                                                       _lib.ptr(fattr), _lib.ptr(index), _lib.ptr(faces), _lib.ptr(ws), wsb, st),
-                   "deftet_surface_extract_fill_f32")
+    # the count pass leaves the row bases in its workspace for the fill pass: a tensor of this call, not the shared one
+    ws = torch.empty(lib.deftet_surface_extract_workspace_bytes(B, T, int(w is not None)), dtype=torch.uint8, device=dev)
+    _lib.call("deftet_surface_extract_count_f32", dev, occ, w, idx32, V, nbr.table32, B, T, mode, h, offs, ws=ws)
+    o = offs.tolist()                                   # the one sync (the reference syncs per shape and per local face)
+    if o[B] < 0:
+        raise RuntimeError("surface_extract: a neighbour or vertex index is out of range")
+    F = o[B]
+    face = torch.empty(F, 3, 3, dtype=torch.float32, device=dev)
+    fattr = torch.empty(F, 3, C, dtype=torch.float32, device=dev) if attr is not None else None
+    index = torch.empty(F, 2, dtype=torch.int64, device=dev) if return_index else None
+    faces = torch.empty(F, 3, dtype=torch.int64, device=dev) if return_faces else None
+    _lib.call("deftet_surface_extract_fill_f32", dev, tet, attr, C, occ if w is None else None, idx32, nbr.table32, B, T, mode, h, F,
+              face, fattr, index, faces, ws=ws)
 
     def split(x):
         return None if x is None else [x[o[b]:o[b + 1]] for b in range(B)]
@@ -1976,11 +1777,8 @@ def surface_weld(verts_vx3, faces_fx3, attrs=None):
     vout = torch.empty(cap, 3, dtype=torch.float32, device=dev)
     aout = torch.empty(cap, C, dtype=torch.float32, device=dev) if attrs is not None else None
     fout = torch.empty(F, 3, dtype=torch.int64, device=dev)
-    with _lib.on_device(dev):
-        ws = _lib.workspace(dev, lib.deftet_surface_weld_workspace_bytes(V))
-        _lib.check(lib.deftet_surface_weld_f32(_lib.ptr(faces), F, _lib.ptr(verts), _lib.ptr(attrs), C, V, cap, _lib.ptr(n), _lib.ptr(old),
-                                               _lib.ptr(vout), _lib.ptr(aout), _lib.ptr(fout), _lib.ptr(ws), ws.numel(),
-                                               _lib.current_stream(dev)), "deftet_surface_weld_f32")
+    _lib.call("deftet_surface_weld_f32", dev, faces, F, verts, attrs, C, V, cap, n, old, vout, aout, fout,
+              ws=lib.deftet_surface_weld_workspace_bytes(V))
     n_used, bad = n.tolist()
     if bad:
         raise RuntimeError("surface_weld: a face index is outside [0, %d)" % V)
@@ -2031,11 +1829,7 @@ def _tet_components(inside, nbr):
     dev = m.device
     parts = _components_out(B, T, dev)
     bad = torch.empty(1, dtype=torch.int32, device=dev)
-    with _lib.on_device(dev):
-        ws = _lib.workspace(dev, lib.deftet_tet_components_workspace_bytes(B, T))
-        _lib.check(lib.deftet_tet_components_u8(_lib.ptr(m), _lib.ptr(nbr.table32), B, T, _lib.ptr(parts[0]), _lib.ptr(parts[1]),
-                                                _lib.ptr(parts[2]), _lib.ptr(parts[3]), _lib.ptr(bad), _lib.ptr(ws), ws.numel(),
-                                                _lib.current_stream(dev)), "deftet_tet_components_u8")
+    _lib.call("deftet_tet_components_u8", dev, m, nbr.table32, B, T, *parts, bad, ws=lib.deftet_tet_components_workspace_bytes(B, T))
     return _components_result(parts, single), bad
 
 
@@ -2066,12 +1860,8 @@ def _occupancy_cleanup(inside, nbr, keep_largest, min_size, fill_voids, return_c
     keep = torch.empty(B, T, dtype=torch.uint8, device=dev)
     parts = _components_out(B, T, dev) if return_components else (None, None, None, None)
     bad = torch.empty(1, dtype=torch.int32, device=dev)
-    with _lib.on_device(dev):
-        ws = _lib.workspace(dev, lib.deftet_tet_components_workspace_bytes(B, T))
-        _lib.check(lib.deftet_occupancy_cleanup_u8(_lib.ptr(m), _lib.ptr(nbr.table32), B, T, int(bool(keep_largest)), int(min_size),
-                                                   int(bool(fill_voids)), _lib.ptr(keep), _lib.ptr(parts[0]), _lib.ptr(parts[1]),
-                                                   _lib.ptr(parts[2]), _lib.ptr(parts[3]), _lib.ptr(bad), _lib.ptr(ws), ws.numel(),
-                                                   _lib.current_stream(dev)), "deftet_occupancy_cleanup_u8")
+    _lib.call("deftet_occupancy_cleanup_u8", dev, m, nbr.table32, B, T, int(bool(keep_largest)), int(min_size), int(bool(fill_voids)),
+              keep, *parts, bad, ws=lib.deftet_tet_components_workspace_bytes(B, T))
     keep = keep.view(torch.bool)
     return (keep[0] if single else keep), (_components_result(parts, single) if return_components else None), bad
 
@@ -2122,10 +1912,7 @@ class TetEdges:
         offsets = torch.empty(V + 1, device=dev, dtype=torch.int32)
         slots = torch.empty(2 * E, device=dev, dtype=torch.int32)
         bad = torch.zeros(1, device=dev, dtype=torch.int32)
-        with _lib.on_device(dev):
-            ws = _lib.workspace(dev, lib.deftet_edge_vertex_csr_workspace_bytes(V, E))
-            _lib.check(lib.deftet_edge_vertex_csr_i32(_lib.ptr(edges), _lib.ptr(offsets), _lib.ptr(slots), _lib.ptr(bad), V, E,
-                                                      _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)), "deftet_edge_vertex_csr_i32")
+        _lib.call("deftet_edge_vertex_csr_i32", dev, edges, offsets, slots, bad, V, E, ws=lib.deftet_edge_vertex_csr_workspace_bytes(V, E))
         if int(bad.item()):
             raise IndexError("TetEdges: vertex index outside [0, %d)" % V)
         self.tets = tets.to(torch.int32).contiguous()
@@ -2146,26 +1933,19 @@ class _MarchingTets(torch.autograd.Function):
         C = 0 if attr is None else int(attr.shape[2])
         ev = torch.empty(B, E, dtype=torch.int32, device=dev)
         offs = torch.empty(2, B + 1, dtype=torch.int32, device=dev)
-        with _lib.on_device(dev):
-            st = _lib.current_stream(dev)
-            # the count pass leaves the output rows in its workspace for the fill pass: a tensor of this call, not the shared one
-            wsb = lib.deftet_marching_tets_workspace_bytes(B, T, E)
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            _lib.check(lib.deftet_marching_tets_count_f32(_lib.ptr(field), _lib.ptr(top.edges), _lib.ptr(top.tets), B, V, T, E, iso,
-                                                          _lib.ptr(ev), _lib.ptr(offs), _lib.ptr(ws), wsb, st),
-                       "deftet_marching_tets_count_f32")
-            o = offs.tolist()                           # the one sync
-            Nv, Nf = o[0][B], o[1][B]
-            verts = torch.empty(Nv, 3, dtype=torch.float32, device=dev)
-            vattr = torch.empty(Nv, C, dtype=torch.float32, device=dev) if C else None
-            faces = torch.empty(Nf, 3, dtype=torch.int64, device=dev)
-            edge_id = torch.empty(Nv, dtype=torch.int64, device=dev) if return_index else None
-            t = torch.empty(Nv, dtype=torch.float32, device=dev) if return_index else None
-            tet_id = torch.empty(Nf, dtype=torch.int64, device=dev) if return_index else None
-            _lib.check(lib.deftet_marching_tets_fill_f32(_lib.ptr(pos), _lib.ptr(field), _lib.ptr(attr), C, _lib.ptr(top.edges),
-                                                         _lib.ptr(top.tets), _lib.ptr(top.tet_edge), _lib.ptr(ev), B, V, T, E, iso, Nv, Nf,
-                                                         _lib.ptr(verts), _lib.ptr(vattr), _lib.ptr(faces), _lib.ptr(edge_id), _lib.ptr(t),
-                                                         _lib.ptr(tet_id), _lib.ptr(ws), wsb, st), "deftet_marching_tets_fill_f32")
+        # the count pass leaves the output rows in its workspace for the fill pass: a tensor of this call, not the shared one
+        ws = torch.empty(lib.deftet_marching_tets_workspace_bytes(B, T, E), dtype=torch.uint8, device=dev)
+        _lib.call("deftet_marching_tets_count_f32", dev, field, top.edges, top.tets, B, V, T, E, iso, ev, offs, ws=ws)
+        o = offs.tolist()                               # the one sync
+        Nv, Nf = o[0][B], o[1][B]
+        verts = torch.empty(Nv, 3, dtype=torch.float32, device=dev)
+        vattr = torch.empty(Nv, C, dtype=torch.float32, device=dev) if C else None
+        faces = torch.empty(Nf, 3, dtype=torch.int64, device=dev)
+        edge_id = torch.empty(Nv, dtype=torch.int64, device=dev) if return_index else None
+        t = torch.empty(Nv, dtype=torch.float32, device=dev) if return_index else None
+        tet_id = torch.empty(Nf, dtype=torch.int64, device=dev) if return_index else None
+        _lib.call("deftet_marching_tets_fill_f32", dev, pos, field, attr, C, top.edges, top.tets, top.tet_edge, ev, B, V, T, E, iso, Nv, Nf,
+                  verts, vattr, faces, edge_id, t, tet_id, ws=ws)
         ctx.save_for_backward(pos, field, attr, ev, offs)
         ctx.topology, ctx.iso, ctx.offsets = top, iso, o
         outs = (verts, vattr, faces, edge_id, t, tet_id)
@@ -2186,16 +1966,12 @@ class _MarchingTets(torch.autograd.Function):
         if Nv == 0 or (g_verts is None and g_vattr is None):
             return (torch.zeros_like(pos) if want[0] else None, torch.zeros_like(field) if want[1] else None,
                     torch.zeros_like(attr) if want_attr else None, None, None, None)
-        lib = _lib.load()
         g_verts, g_vattr = (None if g is None else _f32c(g) for g in (g_verts, g_vattr))
         gp = torch.empty(B, V, 3, device=dev, dtype=torch.float32) if want[0] else None
         gf = torch.empty(B, V, device=dev, dtype=torch.float32) if want[1] else None
         ga = torch.empty(B, V, C, device=dev, dtype=torch.float32) if want_attr else None
-        with _lib.on_device(dev):
-            _lib.check(lib.deftet_marching_tets_bwd_f32(_lib.ptr(g_verts), _lib.ptr(g_vattr), Nv, _lib.ptr(pos), _lib.ptr(field),
-                                                        _lib.ptr(attr), C, _lib.ptr(top.edges), _lib.ptr(top.offsets), _lib.ptr(top.slots),
-                                                        _lib.ptr(ev), _lib.ptr(offs), B, V, top.n_edge, ctx.iso, _lib.ptr(gp), _lib.ptr(gf),
-                                                        _lib.ptr(ga), _lib.current_stream(dev)), "deftet_marching_tets_bwd_f32")
+        _lib.call("deftet_marching_tets_bwd_f32", dev, g_verts, g_vattr, Nv, pos, field, attr, C, top.edges, top.offsets, top.slots, ev, offs,
+                  B, V, top.n_edge, ctx.iso, gp, gf, ga)
         return gp, gf, ga, None, None, None
 
 
@@ -2260,10 +2036,7 @@ class FaceTopology:
         offsets = torch.empty(V + 1, device=dev, dtype=torch.int32)
         slots = torch.empty(3 * F, device=dev, dtype=torch.int32)
         bad = torch.zeros(1, device=dev, dtype=torch.int32)
-        with _lib.on_device(dev):
-            ws = _lib.workspace(dev, lib.deftet_face_vertex_csr_workspace_bytes(V, F))
-            _lib.check(lib.deftet_face_vertex_csr_i32(_lib.ptr(faces), _lib.ptr(offsets), _lib.ptr(slots), _lib.ptr(bad), V, F,
-                                                      _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)), "deftet_face_vertex_csr_i32")
+        _lib.call("deftet_face_vertex_csr_i32", dev, faces, offsets, slots, bad, V, F, ws=lib.deftet_face_vertex_csr_workspace_bytes(V, F))
         if int(bad.item()):
             raise RuntimeError("FaceTopology: face index out of range [0, %d)" % V)
         self.faces, self.n_vertex, self.n_face = faces, V, F
@@ -2283,7 +2056,6 @@ class _ProjectVertices(torch.autograd.Function):
     @staticmethod
     def forward(ctx, points, features, rot, cam_pos, proj, multiplier, depth):
         _lib.require_gpu(points, features, rot, cam_pos, proj)
-        lib = _lib.load()
         rot, cam_pos, proj = _f32c(rot), _f32c(cam_pos), _f32c(proj).reshape(-1)
         B = rot.shape[0]
         if rot.shape != (B, 3, 3) or cam_pos.shape != (B, 3) or proj.numel() != 3:
@@ -2297,11 +2069,8 @@ class _ProjectVertices(torch.autograd.Function):
         z = torch.empty(B, V, device=dev, dtype=torch.float32)
         xy = torch.empty(B, V, 2, device=dev, dtype=torch.float32)
         act = torch.empty(B, V, Do, device=dev, dtype=torch.float32)
-        with _lib.on_device(dev):
-            _lib.check(lib.deftet_project_vertices_fwd_f32(_lib.ptr(pos), _lib.ptr(feat), _lib.ptr(rot), _lib.ptr(cam_pos), _lib.ptr(proj),
-                                                           multiplier, int(depth), _lib.ptr(z), _lib.ptr(xy), _lib.ptr(act), B, V, D,
-                                                           pos.shape[0], feat.shape[0], _lib.current_stream(dev)),
-                       "deftet_project_vertices_fwd_f32")
+        _lib.call("deftet_project_vertices_fwd_f32", dev, pos, feat, rot, cam_pos, proj, multiplier, int(depth), z, xy, act, B, V, D,
+                  pos.shape[0], feat.shape[0])
         ctx.save_for_backward(pos, feat, rot, cam_pos, proj)   # the inputs: the backward recomputes the camera space in fp64
         ctx.args = (multiplier, bool(depth), points.shape, features.shape)
         ctx.mark_non_differentiable(z)                          # z reaches the loss through the depth channel of `act` only
@@ -2315,15 +2084,12 @@ class _ProjectVertices(torch.autograd.Function):
         want_p, want_f = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if (g_xy is None and g_act is None) or not (want_p or want_f):
             return (None,) * 7
-        lib = _lib.load()
         B, Bp, Bf, V, D, dev = rot.shape[0], pos.shape[0], feat.shape[0], pos.shape[1], feat.shape[2], pos.device
         g_xy, g_act = (None if g is None else _f32c(g) for g in (g_xy, g_act))
         gp = torch.empty(Bp, V, 3, device=dev, dtype=torch.float32) if want_p else None
         gf = torch.empty(Bf, V, D, device=dev, dtype=torch.float32) if want_f else None
-        with _lib.on_device(dev):
-            _lib.check(lib.deftet_project_vertices_bwd_f32(_lib.ptr(g_xy), _lib.ptr(g_act), _lib.ptr(pos), _lib.ptr(feat), _lib.ptr(rot),
-                                                           _lib.ptr(cam_pos), _lib.ptr(proj), multiplier, int(depth), _lib.ptr(gp), _lib.ptr(gf),
-                                                           B, V, D, Bp, Bf, _lib.current_stream(dev)), "deftet_project_vertices_bwd_f32")
+        _lib.call("deftet_project_vertices_bwd_f32", dev, g_xy, g_act, pos, feat, rot, cam_pos, proj, multiplier, int(depth), gp, gf,
+                  B, V, D, Bp, Bf)
         return (gp.reshape(pshape) if want_p else None, gf.reshape(fshape) if want_f else None, None, None, None, None, None)
 
 
@@ -2342,7 +2108,6 @@ class _FaceGather(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z, xy, act, topology):
         _lib.require_gpu(z, xy, act)
-        lib = _lib.load()
         z, xy, act = _f32c(z), _f32c(xy), _f32c(act)
         B, V = z.shape[0], topology.n_vertex
         F, Do = topology.n_face, act.shape[-1]
@@ -2352,11 +2117,8 @@ class _FaceGather(torch.autograd.Function):
         face_z = torch.empty(B, F, 3, device=dev, dtype=torch.float32)
         face_xy = torch.empty(B, F, 3, 2, device=dev, dtype=torch.float32)
         face_feat = torch.empty(B, F, 3, Do, device=dev, dtype=torch.float32)
-        with _lib.on_device(dev):
-            # (no flag: the topology checked its indices when it was built)
-            _lib.check(lib.deftet_face_gather_fwd_f32(_lib.ptr(z), _lib.ptr(xy), _lib.ptr(act), _lib.ptr(topology.faces), _lib.ptr(face_z),
-                                                      _lib.ptr(face_xy), _lib.ptr(face_feat), None, B, V, F, Do,
-                                                      _lib.current_stream(dev)), "deftet_face_gather_fwd_f32")
+        # (no flag: the topology checked its indices when it was built)
+        _lib.call("deftet_face_gather_fwd_f32", dev, z, xy, act, topology.faces, face_z, face_xy, face_feat, None, B, V, F, Do)
         ctx.topology, ctx.sizes = topology, (B, V, F, Do)
         ctx.mark_non_differentiable(face_z)
         ctx.set_materialize_grads(False)
@@ -2366,17 +2128,13 @@ class _FaceGather(torch.autograd.Function):
     def backward(ctx, _g_face_z, g_face_xy, g_face_feat):
         if g_face_xy is None and g_face_feat is None:
             return None, None, None, None
-        lib = _lib.load()
         top = ctx.topology
         B, V, F, Do = ctx.sizes
         dev = top.device
         g_face_xy, g_face_feat = (None if g is None else _f32c(g) for g in (g_face_xy, g_face_feat))
         g_xy = torch.empty(B, V, 2, device=dev, dtype=torch.float32)
         g_act = torch.empty(B, V, Do, device=dev, dtype=torch.float32)
-        with _lib.on_device(dev):
-            _lib.check(lib.deftet_face_gather_bwd_f32(_lib.ptr(g_face_xy), _lib.ptr(g_face_feat), _lib.ptr(top.offsets), _lib.ptr(top.slots),
-                                                      _lib.ptr(g_xy), _lib.ptr(g_act), B, V, F, Do, _lib.current_stream(dev)),
-                       "deftet_face_gather_bwd_f32")
+        _lib.call("deftet_face_gather_bwd_f32", dev, g_face_xy, g_face_feat, top.offsets, top.slots, g_xy, g_act, B, V, F, Do)
         return None, g_xy, g_act, None
 
 
@@ -2399,10 +2157,10 @@ def _pv_need(t, dtype, what):
     return t.contiguous()
 
 
-def _grid_workspace(lib, dev, B, N, size):
-    """the workspace of the operator whose grids have the spatial shape `size`: (R, R, R) volumes or (H, W) maps"""
-    nbytes = lib.deftet_pointvoxel_workspace_bytes(B, N, size[0]) if len(size) == 3 else lib.deftet_image_sample_workspace_bytes(B, N, *size)
-    return _lib.workspace(dev, nbytes), nbytes
+def _grid_bytes(B, N, size):
+    """the workspace bytes of the operator whose grids have the spatial shape `size`: (R, R, R) volumes or (H, W) maps"""
+    lib = _lib.load()
+    return lib.deftet_pointvoxel_workspace_bytes(B, N, size[0]) if len(size) == 3 else lib.deftet_image_sample_workspace_bytes(B, N, *size)
 
 
 def avg_voxelize_fwd(features, coords, resolution):
@@ -2410,7 +2168,6 @@ def avg_voxelize_fwd(features, coords, resolution):
     avg_voxelize_forward.  out[b,c,s] adds feat * (1.0f / cnt) over the points of voxel s in ascending point order, from 0 (the
     bits of the reference kernel run serially); a coordinate outside [0,R) gives ind = -1 and takes no part.  No atomics."""
     _lib.require_gpu(features, coords)
-    lib = _lib.load()
     features, coords = _pv_need(features, torch.float32, "avg_voxelize: features"), _pv_need(coords, torch.int32, "avg_voxelize: coords")
     R = int(resolution)
     if features.dim() != 3 or coords.dim() != 3 or coords.shape[1] != 3 or R < 1:
@@ -2422,17 +2179,13 @@ def avg_voxelize_fwd(features, coords, resolution):
     out = torch.empty(B, C, R ** 3, device=dev, dtype=torch.float32)
     ind = torch.empty(B, N, device=dev, dtype=torch.int32)
     cnt = torch.empty(B, R ** 3, device=dev, dtype=torch.int32)
-    with _lib.on_device(dev):
-        ws, nbytes = _grid_workspace(lib, dev, B, N, (R, R, R))
-        _lib.check(lib.deftet_avg_voxelize_fwd_f32(_lib.ptr(features), _lib.ptr(coords), _lib.ptr(out), _lib.ptr(ind), _lib.ptr(cnt), B, C, N, R,
-                                                   _lib.ptr(ws), nbytes, _lib.current_stream(dev)), "deftet_avg_voxelize_fwd_f32")
+    _lib.call("deftet_avg_voxelize_fwd_f32", dev, features, coords, out, ind, cnt, B, C, N, R, ws=_grid_bytes(B, N, (R, R, R)))
     return out, ind, cnt
 
 
 def avg_voxelize_bwd(grad_y, ind, cnt):
     """grad_x f32 [B,C,N] = grad_y[b,c,ind] * (1.0f / cnt[ind]) of grad_y f32 [B,C,R^3]: avg_voxelize_backward, as a gather."""
     _lib.require_gpu(grad_y, ind, cnt)
-    lib = _lib.load()
     grad_y = _pv_need(grad_y, torch.float32, "avg_voxelize_bwd: grad_y")
     ind, cnt = _pv_need(ind, torch.int32, "avg_voxelize_bwd: ind"), _pv_need(cnt, torch.int32, "avg_voxelize_bwd: cnt")
     if grad_y.dim() != 3 or ind.dim() != 2 or cnt.dim() != 2:
@@ -2443,9 +2196,7 @@ def avg_voxelize_bwd(grad_y, ind, cnt):
         raise RuntimeError("avg_voxelize_bwd: grad_y %s, ind %s, cnt %s do not agree" % (tuple(grad_y.shape), tuple(ind.shape), tuple(cnt.shape)))
     N, dev = ind.shape[1], grad_y.device
     grad_x = torch.empty(B, C, N, device=dev, dtype=torch.float32)
-    with _lib.on_device(dev):
-        _lib.check(lib.deftet_avg_voxelize_bwd_f32(_lib.ptr(grad_y), _lib.ptr(ind), _lib.ptr(cnt), _lib.ptr(grad_x), B, C, N, R,
-                                                   _lib.current_stream(dev)), "deftet_avg_voxelize_bwd_f32")
+    _lib.call("deftet_avg_voxelize_bwd_f32", dev, grad_y, ind, cnt, grad_x, B, C, N, R)
     return grad_x
 
 
@@ -2455,7 +2206,7 @@ class GridCells:
     __slots__ = ("perm", "seg", "wsorted", "isorted", "B", "N", "size")
 
 
-def _grid_cells(lib, B, N, size, dev, pos=None, pos_mode=0, inds=None, wgts=None, uv=None, border=0, align=0):
+def _grid_cells(B, N, size, dev, pos=None, pos_mode=0, inds=None, wgts=None, uv=None, border=0, align=0):
     """the cells of pos (or of the recorded inds / wgts) in volumes of shape `size`, or of uv in maps of shape `size`"""
     n_cells, corners = (size[0] ** 3, 8) if uv is None else ((size[0] + 1) * (size[1] + 1), 4)
     cells = GridCells()
@@ -2464,38 +2215,29 @@ def _grid_cells(lib, B, N, size, dev, pos=None, pos_mode=0, inds=None, wgts=None
     cells.seg = torch.empty(B * n_cells + 1, device=dev, dtype=torch.int32)
     cells.wsorted = torch.empty(corners, B * N, device=dev, dtype=torch.float32)
     cells.isorted = torch.empty(8, B * N, device=dev, dtype=torch.int32) if inds is not None else None
-    out = (_lib.ptr(cells.perm), _lib.ptr(cells.seg), _lib.ptr(cells.wsorted))
-    with _lib.on_device(dev):
-        ws, nbytes = _grid_workspace(lib, dev, B, N, size)
-        tail = (_lib.ptr(ws), nbytes, _lib.current_stream(dev))
-        if uv is not None:
-            _lib.check(lib.deftet_image_cells_f32(_lib.ptr(uv), *out, B, N, size[0], size[1], border, align, *tail), "deftet_image_cells_f32")
-        elif inds is None:
-            _lib.check(lib.deftet_voxel_cells_f32(_lib.ptr(pos), pos_mode, *out, B, N, size[0], *tail), "deftet_voxel_cells_f32")
-        else:
-            _lib.check(lib.deftet_voxel_cells_from_inds_i32(_lib.ptr(inds), _lib.ptr(wgts), *out, _lib.ptr(cells.isorted), B, N, size[0], *tail),
-                       "deftet_voxel_cells_from_inds_i32")
+    out, nbytes = (cells.perm, cells.seg, cells.wsorted), _grid_bytes(B, N, size)
+    if uv is not None:
+        _lib.call("deftet_image_cells_f32", dev, uv, *out, B, N, size[0], size[1], border, align, ws=nbytes)
+    elif inds is None:
+        _lib.call("deftet_voxel_cells_f32", dev, pos, pos_mode, *out, B, N, size[0], ws=nbytes)
+    else:
+        _lib.call("deftet_voxel_cells_from_inds_i32", dev, inds, wgts, *out, cells.isorted, B, N, size[0], ws=nbytes)
     return cells
 
 
-def _grid_bwd(lib, gout, cells, C, c_off, C_total):
+def _grid_bwd(gout, cells, C, c_off, C_total):
     """the gradient f32 [B, C, *size] of one grid from the rows [c_off, c_off + C) of gout, gathered through `cells`"""
     B, N, size, dev = cells.B, cells.N, cells.size, gout.device
     ggrid = torch.empty((B, C) + size, device=dev, dtype=torch.float32)
-    head = (_lib.ptr(gout), _lib.ptr(cells.perm), _lib.ptr(cells.seg), _lib.ptr(cells.wsorted))
-    with _lib.on_device(dev):
-        ws, nbytes = _grid_workspace(lib, dev, B, N, size)
-        tail = (N, c_off, C_total, _lib.ptr(ws), nbytes, _lib.current_stream(dev))
-        if len(size) == 3:
-            _lib.check(lib.deftet_voxel_sample_bwd_vol_f32(*head, _lib.ptr(cells.isorted), _lib.ptr(ggrid), B, C, size[0], *tail),
-                       "deftet_voxel_sample_bwd_vol_f32")
-        else:
-            _lib.check(lib.deftet_image_sample_bwd_map_f32(*head, _lib.ptr(ggrid), B, C, size[0], size[1], *tail),
-                       "deftet_image_sample_bwd_map_f32")
+    head, nbytes = (gout, cells.perm, cells.seg, cells.wsorted), _grid_bytes(B, N, size)
+    if len(size) == 3:
+        _lib.call("deftet_voxel_sample_bwd_vol_f32", dev, *head, cells.isorted, ggrid, B, C, size[0], N, c_off, C_total, ws=nbytes)
+    else:
+        _lib.call("deftet_image_sample_bwd_map_f32", dev, *head, ggrid, B, C, size[0], size[1], N, c_off, C_total, ws=nbytes)
     return ggrid
 
 
-def _grid_grads(lib, gout, grids, needs, c_off, C_total, make_cells):
+def _grid_grads(gout, grids, needs, c_off, C_total, make_cells):
     """The gradients of the grids of a list (None where `needs` says so), grid k reading its rows of gout behind those of the
     grids before it, from c_off: one sort of the points per distinct grid size (make_cells(size)), then the gather."""
     grads, cells = [], {}
@@ -2503,7 +2245,7 @@ def _grid_grads(lib, gout, grids, needs, c_off, C_total, make_cells):
         size = tuple(g.shape[2:])
         if need and size not in cells:
             cells[size] = make_cells(size)
-        grads.append(_grid_bwd(lib, gout, cells[size], g.shape[1], c_off, C_total) if need else None)
+        grads.append(_grid_bwd(gout, cells[size], g.shape[1], c_off, C_total) if need else None)
         c_off += g.shape[1]
     return grads
 
@@ -2524,7 +2266,6 @@ def _check_volumes(caller, volumes, pos):
 class _VoxelSample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pos, append_pos, pos_mode, *volumes):
-        lib = _lib.load()
         dev = pos.device
         B, N = (pos.shape[0], pos.shape[1]) if pos_mode == 0 else (pos.shape[0], pos.shape[2])
         C_feat = sum(v.shape[1] for v in volumes)
@@ -2533,9 +2274,7 @@ class _VoxelSample(torch.autograd.Function):
         c_off = 0
         with _lib.on_device(dev):
             for v in volumes:
-                _lib.check(lib.deftet_voxel_sample_fwd_f32(_lib.ptr(v), _lib.ptr(pos), _lib.ptr(out), None, None, B, v.shape[1], v.shape[-1], N,
-                                                           c_off, C_total, pos_mode, 0, _lib.current_stream(dev)),
-                           "deftet_voxel_sample_fwd_f32")
+                _lib.call("deftet_voxel_sample_fwd_f32", dev, v, pos, out, None, None, B, v.shape[1], v.shape[-1], N, c_off, C_total, pos_mode, 0)
                 c_off += v.shape[1]
         if append_pos:
             out[:, C_feat:, :].copy_(pos.transpose(1, 2) if pos_mode == 0 else pos)
@@ -2547,20 +2286,18 @@ class _VoxelSample(torch.autograd.Function):
     def backward(ctx, gout):
         pos, volumes = ctx.saved_tensors[0], ctx.saved_tensors[1:]
         append_pos, pos_mode, B, N, C_feat, C_total = ctx.args
-        lib = _lib.load()
         dev = pos.device
         gout = _f32c(gout)
-        grads = _grid_grads(lib, gout, volumes, ctx.needs_input_grad[3:], 0, C_total,
-                            lambda size: _grid_cells(lib, B, N, size, dev, pos=pos, pos_mode=pos_mode))
+        grads = _grid_grads(gout, volumes, ctx.needs_input_grad[3:], 0, C_total,
+                            lambda size: _grid_cells(B, N, size, dev, pos=pos, pos_mode=pos_mode))
         gpos = None
         if ctx.needs_input_grad[0]:
             gpos = torch.zeros_like(pos) if not volumes else torch.empty_like(pos)
             c_off = 0
             with _lib.on_device(dev):
                 for k, v in enumerate(volumes):                      # list order; channels ascending inside the kernel
-                    _lib.check(lib.deftet_voxel_sample_bwd_pos_f32(_lib.ptr(v), _lib.ptr(pos), _lib.ptr(gout), _lib.ptr(gpos), B, v.shape[1],
-                                                                   v.shape[-1], N, c_off, C_total, pos_mode, int(k > 0),
-                                                                   _lib.current_stream(dev)), "deftet_voxel_sample_bwd_pos_f32")
+                    _lib.call("deftet_voxel_sample_bwd_pos_f32", dev, v, pos, gout, gpos, B, v.shape[1], v.shape[-1], N, c_off, C_total, pos_mode,
+                              int(k > 0))
                     c_off += v.shape[1]
             if append_pos:
                 gpos += gout[:, C_feat:, :].transpose(1, 2) if pos_mode == 0 else gout[:, C_feat:, :]
@@ -2592,7 +2329,6 @@ def voxel_sample(volumes, pos, append_pos=False, voxel_units=False):
 class _ImageSample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, uv, glob, app, border, align, *maps):
-        lib = _lib.load()
         dev = uv.device
         B, N = uv.shape[0], uv.shape[1]
         G = glob.shape[1] if glob is not None else 0
@@ -2600,18 +2336,14 @@ class _ImageSample(torch.autograd.Function):
         C_total = G + sum(m.shape[1] for m in maps) + A
         out = torch.empty(B, C_total, N, device=dev, dtype=torch.float32)
         with _lib.on_device(dev):
-            st = _lib.current_stream(dev)
             c_off = G
             for k, m in enumerate(maps):                             # the first launch also writes the global and the appended rows
                 first = k == 0
-                _lib.check(lib.deftet_image_sample_fwd_f32(_lib.ptr(m), _lib.ptr(uv), _lib.ptr(glob) if first else None,
-                                                           _lib.ptr(app) if first else None, _lib.ptr(out), B, m.shape[1], m.shape[2],
-                                                           m.shape[3], N, G if first else 0, A if first else 0, c_off, C_total, border, align,
-                                                           st), "deftet_image_sample_fwd_f32")
+                _lib.call("deftet_image_sample_fwd_f32", dev, m, uv, glob if first else None, app if first else None, out, B, m.shape[1],
+                          m.shape[2], m.shape[3], N, G if first else 0, A if first else 0, c_off, C_total, border, align)
                 c_off += m.shape[1]
             if not maps and G + A > 0:
-                _lib.check(lib.deftet_image_sample_fwd_f32(None, _lib.ptr(uv), _lib.ptr(glob), _lib.ptr(app), _lib.ptr(out), B, 0, 1, 1, N, G, A,
-                                                           G, C_total, border, align, st), "deftet_image_sample_fwd_f32")
+                _lib.call("deftet_image_sample_fwd_f32", dev, None, uv, glob, app, out, B, 0, 1, 1, N, G, A, G, C_total, border, align)
         ctx.save_for_backward(uv, *maps)
         ctx.args = (border, align, B, N, G, A, C_total)
         return out
@@ -2620,27 +2352,23 @@ class _ImageSample(torch.autograd.Function):
     def backward(ctx, gout):
         uv, maps = ctx.saved_tensors[0], ctx.saved_tensors[1:]
         border, align, B, N, G, A, C_total = ctx.args
-        lib = _lib.load()
         dev = uv.device
         gout = _f32c(gout)
-        grads = _grid_grads(lib, gout, maps, ctx.needs_input_grad[5:], G, C_total,
-                            lambda size: _grid_cells(lib, B, N, size, dev, uv=uv, border=border, align=align))
+        grads = _grid_grads(gout, maps, ctx.needs_input_grad[5:], G, C_total,
+                            lambda size: _grid_cells(B, N, size, dev, uv=uv, border=border, align=align))
         guv = None
         if ctx.needs_input_grad[0]:
             guv = torch.zeros_like(uv) if not maps else torch.empty_like(uv)
             c_off = G
             with _lib.on_device(dev):
                 for k, m in enumerate(maps):                         # list order; channels ascending inside the kernel
-                    _lib.check(lib.deftet_image_sample_bwd_uv_f32(_lib.ptr(m), _lib.ptr(uv), _lib.ptr(gout), _lib.ptr(guv), B, m.shape[1],
-                                                                  m.shape[2], m.shape[3], N, c_off, C_total, border, align, int(k > 0),
-                                                                  _lib.current_stream(dev)), "deftet_image_sample_bwd_uv_f32")
+                    _lib.call("deftet_image_sample_bwd_uv_f32", dev, m, uv, gout, guv, B, m.shape[1], m.shape[2], m.shape[3], N, c_off, C_total,
+                              border, align, int(k > 0))
                     c_off += m.shape[1]
         gglob = None
         if G > 0 and ctx.needs_input_grad[1]:
             gglob = torch.empty(B, G, device=dev, dtype=torch.float32)
-            with _lib.on_device(dev):
-                _lib.check(lib.deftet_image_sample_bwd_global_f32(_lib.ptr(gout), _lib.ptr(gglob), B, G, N, C_total, _lib.current_stream(dev)),
-                           "deftet_image_sample_bwd_global_f32")
+            _lib.call("deftet_image_sample_bwd_global_f32", dev, gout, gglob, B, G, N, C_total)
         elif ctx.needs_input_grad[1]:
             gglob = torch.zeros(B, 0, device=dev, dtype=torch.float32)
         gapp = gout[:, C_total - A:, :].transpose(1, 2).contiguous() if ctx.needs_input_grad[2] else None
@@ -2702,14 +2430,10 @@ def tet_centroid_sample_bwd_pos(volumes, centroids, gout, append_pos=True):
     """gcent f32 [B,K,3]: the gradient of tet_centroid_sample's result on its centroids, one launch for the whole volume list.  The
     bits of voxel_sample's chain on the same centroids: per volume the channel sum from 0 in ascending order, the volumes added in
     list order, the position rows of gout last.  A slot with a NaN centroid gets 0."""
-    lib = _lib.load()
     B, K = centroids.shape[0], centroids.shape[1]
     gcent = torch.empty(B, K, 3, device=centroids.device, dtype=torch.float32)
-    ptrs, chans, ress, n = _tcs_volume_list(volumes)
-    with _lib.on_device(centroids.device):
-        _lib.check(lib.deftet_tet_centroid_sample_bwd_pos_f32(ptrs, chans, ress, n, _lib.ptr(centroids), _lib.ptr(gout), _lib.ptr(gcent), B, K,
-                                                              1 if append_pos else 0, _lib.current_stream(centroids.device)),
-                   "deftet_tet_centroid_sample_bwd_pos_f32")
+    _lib.call("deftet_tet_centroid_sample_bwd_pos_f32", centroids.device, *_tcs_volume_list(volumes), centroids, gout, gcent, B, K,
+              1 if append_pos else 0)
     return gcent
 
 
@@ -2727,22 +2451,14 @@ def tet_centroid_sample_bwd_vertices(gcent, csr, n_vertex, n_tet, select=None, f
         raise RuntimeError("tet_centroid_sample: out must be contiguous f32 [B,V,3]")
     dev = gcent.device
     gpos = out if acc else torch.empty(B, V, 3, device=dev, dtype=torch.float32)
-    with _lib.on_device(dev):
-        ws, nbytes = None, 0
-        if select is not None:
-            nbytes = lib.deftet_tet_centroid_sample_workspace_bytes(B, T, K)
-            ws = _lib.workspace(dev, nbytes)
-        _lib.check(lib.deftet_tet_centroid_sample_bwd_vertices_f32(_lib.ptr(gcent), _lib.ptr(offsets), _lib.ptr(slots), _lib.ptr(select),
-                                                                   int(first), _lib.ptr(gpos), B, V, T, Bi, K, 1 if acc else 0, _lib.ptr(ws),
-                                                                   nbytes, _lib.current_stream(dev)),
-                   "deftet_tet_centroid_sample_bwd_vertices_f32")
+    _lib.call("deftet_tet_centroid_sample_bwd_vertices_f32", dev, gcent, offsets, slots, select, int(first), gpos, B, V, T, Bi, K,
+              1 if acc else 0, ws=lib.deftet_tet_centroid_sample_workspace_bytes(B, T, K) if select is not None else None)
     return gpos
 
 
 class _TetCentroidSample(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pos, tet_idx, csr, select, first, K, append_pos, check, *volumes):
-        lib = _lib.load()
         dev = pos.device
         B, V, T = pos.shape[0], pos.shape[1], tet_idx.shape[1]
         C_feat = sum(v.shape[1] for v in volumes)
@@ -2750,12 +2466,8 @@ class _TetCentroidSample(torch.autograd.Function):
         out = torch.empty(B, C_total, K, device=dev, dtype=torch.float32)
         centroids = torch.empty(B, K, 3, device=dev, dtype=torch.float32)
         bad = torch.zeros(1, device=dev, dtype=torch.int32) if check else None
-        ptrs, chans, ress, n = _tcs_volume_list(volumes)
-        with _lib.on_device(dev):
-            _lib.check(lib.deftet_tet_centroid_sample_fwd_f32(ptrs, chans, ress, n, _lib.ptr(pos), _lib.ptr(tet_idx), _lib.ptr(select), first,
-                                                              _lib.ptr(out), _lib.ptr(centroids), _lib.ptr(bad), B, V, T, tet_idx.shape[0], K,
-                                                              1 if append_pos else 0, _lib.current_stream(dev)),
-                       "deftet_tet_centroid_sample_fwd_f32")
+        _lib.call("deftet_tet_centroid_sample_fwd_f32", dev, *_tcs_volume_list(volumes), pos, tet_idx, select, first, out, centroids, bad,
+                  B, V, T, tet_idx.shape[0], K, 1 if append_pos else 0)
         if check and int(bad.item()):
             raise RuntimeError("tet_centroid_sample: a chosen tet is outside [0, %d) or one of its vertices outside [0, %d)" % (T, V))
         ctx.save_for_backward(centroids, *volumes)
@@ -2768,11 +2480,9 @@ class _TetCentroidSample(torch.autograd.Function):
     def backward(ctx, gout, _gcentroids):
         centroids, volumes = ctx.saved_tensors[0], ctx.saved_tensors[1:]
         append_pos, first, B, V, T, K, C_feat, C_total = ctx.args
-        lib = _lib.load()
         dev = centroids.device
         gout = _f32c(gout)
-        grads = _grid_grads(lib, gout, volumes, ctx.needs_input_grad[8:], 0, C_total,
-                            lambda size: _grid_cells(lib, B, K, size, dev, pos=centroids))
+        grads = _grid_grads(gout, volumes, ctx.needs_input_grad[8:], 0, C_total, lambda size: _grid_cells(B, K, size, dev, pos=centroids))
         gpos = None
         if ctx.needs_input_grad[0]:
             gcent = tet_centroid_sample_bwd_pos(volumes, centroids, gout, append_pos)
@@ -2849,17 +2559,13 @@ def tet_field_sample_fwd(field, tet_idx, cond, bary, fill=0.0, bad=None):
     (v_k its vertices in tet_idx, w = bary); `fill` where cond is -1, NaN where a vertex index lies outside [0,V) (bad: an int32
     [1] tensor set to 1 then).  One launch.  The raw forward of tet_field_sample."""
     _lib.require_gpu(field, tet_idx, cond, bary, bad)
-    lib = _lib.load()
     field, idx, cond, bary = _pv_need(field, torch.float32, "tet_field_sample: field"), _idx32(tet_idx), _f32c(cond), _f32c(bary)
     B, V, C, T, Bi, Q = _tfs_sizes("tet_field_sample", field, idx, cond)
     if bary.shape != (B, Q, 4):
         raise RuntimeError("tet_field_sample: bary [B,Q,4] expected (got %s)" % (tuple(bary.shape),))
     dev = field.device
     out = torch.empty(B, Q, C, device=dev, dtype=torch.float32)
-    with _lib.on_device(dev):
-        _lib.check(lib.deftet_tet_field_sample_fwd_f32(_lib.ptr(field), _lib.ptr(idx), _lib.ptr(cond), _lib.ptr(bary), _lib.ptr(out),
-                                                       _lib.ptr(bad), float(fill), B, V, T, Bi, Q, C, _lib.current_stream(dev)),
-                   "deftet_tet_field_sample_fwd_f32")
+    _lib.call("deftet_tet_field_sample_fwd_f32", dev, field, idx, cond, bary, out, bad, float(fill), B, V, T, Bi, Q, C)
     return out
 
 
@@ -2867,17 +2573,13 @@ def tet_field_sample_bwd_w(field, tet_idx, cond, gout):
     """grad_w f32 [B,Q,4]: the gradient of tet_field_sample's result on the barycentric weights, grad_w[b,q,k] = the sum over the
     channels in ascending order of gout[b,q,c] * f(v_k,c), one fp32 accumulator from 0; 0 on a miss.  One launch."""
     _lib.require_gpu(field, tet_idx, cond, gout)
-    lib = _lib.load()
     field, idx, cond, gout = _pv_need(field, torch.float32, "tet_field_sample: field"), _idx32(tet_idx), _f32c(cond), _f32c(gout)
     B, V, C, T, Bi, Q = _tfs_sizes("tet_field_sample_bwd_w", field, idx, cond)
     if gout.shape != (B, Q, C):
         raise RuntimeError("tet_field_sample_bwd_w: gout [B,Q,C] = %s expected (got %s)" % ((B, Q, C), tuple(gout.shape)))
     dev = field.device
     gw = torch.empty(B, Q, 4, device=dev, dtype=torch.float32)
-    with _lib.on_device(dev):
-        _lib.check(lib.deftet_tet_field_sample_bwd_w_f32(_lib.ptr(field), _lib.ptr(idx), _lib.ptr(cond), _lib.ptr(gout), _lib.ptr(gw), B, V, T,
-                                                         Bi, Q, C, _lib.current_stream(dev)),
-                   "deftet_tet_field_sample_bwd_w_f32")
+    _lib.call("deftet_tet_field_sample_bwd_w_f32", dev, field, idx, cond, gout, gw, B, V, T, Bi, Q, C)
     return gw
 
 
@@ -2904,13 +2606,8 @@ def tet_field_sample_bwd_field(gout, cond, bary, csr, n_vertex, n_tet, out=None,
     acc = bool(accumulate)
     dev = gout.device
     gfield = out if out is not None else torch.empty(B, V, C, device=dev, dtype=torch.float32)
-    with _lib.on_device(dev):
-        nbytes = lib.deftet_tet_field_sample_workspace_bytes(B, T, Q)
-        ws = _lib.workspace(dev, nbytes)
-        _lib.check(lib.deftet_tet_field_sample_bwd_field_f32(_lib.ptr(gout), _lib.ptr(cond), _lib.ptr(bary), _lib.ptr(offsets), _lib.ptr(slots),
-                                                             _lib.ptr(gfield), B, V, T, Bi, Q, C, 1 if acc else 0, _lib.ptr(ws), nbytes,
-                                                             _lib.current_stream(dev)),
-                   "deftet_tet_field_sample_bwd_field_f32")
+    _lib.call("deftet_tet_field_sample_bwd_field_f32", dev, gout, cond, bary, offsets, slots, gfield, B, V, T, Bi, Q, C, 1 if acc else 0,
+              ws=lib.deftet_tet_field_sample_workspace_bytes(B, T, Q))
     return gfield
 
 
@@ -3008,7 +2705,6 @@ def trilinear_devoxelize_fwd(r, is_training, coords, features):
     d == 0, so nothing past r - 1 is read; coordinates are clamped to [0, r-1] first (the reference reads out of bounds there).
     Not training: inds and wgts are [1]-shaped zeros."""
     _lib.require_gpu(coords, features)
-    lib = _lib.load()
     coords, features = _pv_need(coords, torch.float32, "trilinear_devoxelize: coords"), _pv_need(features, torch.float32, "trilinear_devoxelize: features")
     r = int(r)
     if coords.dim() != 3 or coords.shape[1] != 3 or features.dim() != 3 or r < 1:
@@ -3023,10 +2719,8 @@ def trilinear_devoxelize_fwd(r, is_training, coords, features):
         wgts = torch.empty(B, 8, N, device=dev, dtype=torch.float32)
     else:
         inds, wgts = torch.zeros(1, device=dev, dtype=torch.int32), torch.zeros(1, device=dev, dtype=torch.float32)
-    with _lib.on_device(dev):
-        _lib.check(lib.deftet_voxel_sample_fwd_f32(_lib.ptr(features), _lib.ptr(coords), _lib.ptr(outs), _lib.ptr(inds) if is_training else None,
-                                                   _lib.ptr(wgts) if is_training else None, B, C, r, N, 0, C, 1, 1, _lib.current_stream(dev)),
-                   "deftet_voxel_sample_fwd_f32")
+    _lib.call("deftet_voxel_sample_fwd_f32", dev, features, coords, outs, inds if is_training else None, wgts if is_training else None,
+              B, C, r, N, 0, C, 1, 1)
     return outs, inds, wgts
 
 
@@ -3037,7 +2731,6 @@ def trilinear_devoxelize_bwd(grad_y, inds, wgts, r):
     inds / wgts that come from trilinear_devoxelize_fwd.  Hand-made inds without that lo / hi structure lose the other terms, and a
     non-finite grad_y does not spread through weight-0 terms as the reference's atomics would (0 * inf)."""
     _lib.require_gpu(grad_y, inds, wgts)
-    lib = _lib.load()
     grad_y, wgts = _pv_need(grad_y, torch.float32, "trilinear_devoxelize_bwd: grad_y"), _pv_need(wgts, torch.float32, "trilinear_devoxelize_bwd: wgts")
     inds, r = _pv_need(inds, torch.int32, "trilinear_devoxelize_bwd: inds"), int(r)
     if grad_y.dim() != 3 or inds.dim() != 3 or inds.shape != wgts.shape or inds.shape[1] != 8 or r < 1:
@@ -3045,8 +2738,8 @@ def trilinear_devoxelize_bwd(grad_y, inds, wgts, r):
     B, C, N = grad_y.shape
     if inds.shape[0] != B or inds.shape[2] != N:
         raise RuntimeError("trilinear_devoxelize_bwd: grad_y %s and inds %s do not agree" % (tuple(grad_y.shape), tuple(inds.shape)))
-    cells = _grid_cells(lib, B, N, (r, r, r), grad_y.device, inds=inds, wgts=wgts)
-    return _grid_bwd(lib, grad_y, cells, C, 0, C).view(B, C, r ** 3)
+    cells = _grid_cells(B, N, (r, r, r), grad_y.device, inds=inds, wgts=wgts)
+    return _grid_bwd(grad_y, cells, C, 0, C).view(B, C, r ** 3)
 
 
 # --------------------------------------------------------------------------------- ground-truth preparation
@@ -3064,11 +2757,9 @@ class VoxelBits:
 
     def unpack(self):
         """uint8 [B,R,R,R]"""
-        lib = _lib.load()
         B, R, dev = self.n_batch, self.resolution, self.device
         vox = torch.empty(B, R, R, R, device=dev, dtype=torch.uint8)
-        with _lib.on_device(dev):
-            _lib.check(lib.deftet_voxel_unpack_u8(_lib.ptr(self.words), B, R, _lib.ptr(vox), _lib.current_stream(dev)), "deftet_voxel_unpack_u8")
+        _lib.call("deftet_voxel_unpack_u8", dev, self.words, B, R, vox)
         return vox
 
 
@@ -3085,11 +2776,9 @@ def _vox_u8(vox, what):
 def voxel_pack(vox):
     """VoxelBits of a grid [B,R,R,R] (non-zero = occupied)."""
     v = _vox_u8(vox, "voxel_pack")
-    lib = _lib.load()
     B, R, dev = int(v.shape[0]), int(v.shape[1]), v.device
     words = torch.empty(B, R, R, (R + 31) // 32, device=dev, dtype=torch.int32)
-    with _lib.on_device(dev):
-        _lib.check(lib.deftet_voxel_pack_u8(_lib.ptr(v), B, R, _lib.ptr(words), _lib.current_stream(dev)), "deftet_voxel_pack_u8")
+    _lib.call("deftet_voxel_pack_u8", dev, v, B, R, words)
     return VoxelBits(words, R)
 
 
@@ -3124,11 +2813,7 @@ def mesh_voxelize(vertices, faces, resolution, origin=None, scale=None, return_b
     words = torch.empty(B, R, R, (R + 31) // 32, device=dev, dtype=torch.int32)
     vox = None if return_bits else torch.empty(B, R, R, R, device=dev, dtype=torch.uint8)
     stats = torch.empty(4, device=dev, dtype=torch.int32)
-    with _lib.on_device(dev):
-        ws = _lib.workspace(dev, lib.deftet_mesh_voxelize_workspace_bytes(B, F))
-        _lib.check(lib.deftet_mesh_voxelize_f32(_lib.ptr(v), _lib.ptr(f), _lib.ptr(origin), _lib.ptr(scale), B, V, F, R, _lib.ptr(words),
-                                                _lib.ptr(vox), _lib.ptr(stats), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
-                   "deftet_mesh_voxelize_f32")
+    _lib.call("deftet_mesh_voxelize_f32", dev, v, f, origin, scale, B, V, F, R, words, vox, stats, ws=lib.deftet_mesh_voxelize_workspace_bytes(B, F))
     return VoxelBits(words, R, stats) if return_bits else vox
 
 
@@ -3137,11 +2822,9 @@ def extract_odms(vox):
     axis d // 2, ascending for even d, descending for odd d; a map is indexed by the two other axes in ascending axis order;
     a depth is the number of empty voxels in front of the first occupied one, R for an empty ray."""
     v = vox.unpack() if isinstance(vox, VoxelBits) else _vox_u8(vox, "extract_odms")
-    lib = _lib.load()
     B, R, dev = int(v.shape[0]), int(v.shape[1]), v.device
     odms = torch.empty(B, 6, R, R, device=dev, dtype=torch.int32)
-    with _lib.on_device(dev):
-        _lib.check(lib.deftet_extract_odms_u8(_lib.ptr(v), B, R, _lib.ptr(odms), _lib.current_stream(dev)), "deftet_extract_odms_u8")
+    _lib.call("deftet_extract_odms_u8", dev, v, B, R, odms)
     return odms
 
 
@@ -3149,7 +2832,6 @@ def project_odms(odms, voxelgrids=None, votes=1):
     """uint8 [B,R,R,R]: start from a full grid (or `voxelgrids`); direction d carves the voxels in front of its depth; a voxel
     stays iff fewer than `votes` directions carve it (extract_odms' direction order)."""
     _lib.require_gpu(odms)
-    lib = _lib.load()
     if odms.dim() != 4 or odms.shape[1] != 6 or odms.shape[2] != odms.shape[3] or odms.shape[0] < 1 or odms.shape[2] < 1:
         raise RuntimeError("project_odms: odms [B,6,R,R] expected, got %s" % (tuple(odms.shape),))
     o = odms.to(torch.int32).contiguous()
@@ -3160,9 +2842,7 @@ def project_odms(odms, voxelgrids=None, votes=1):
         if tuple(vin.shape) != (B, R, R, R) or vin.device != dev:
             raise RuntimeError("project_odms: voxelgrids [%d,%d,%d,%d] on %s expected" % (B, R, R, R, dev))
     out = torch.empty(B, R, R, R, device=dev, dtype=torch.uint8)
-    with _lib.on_device(dev):
-        _lib.check(lib.deftet_project_odms_i32(_lib.ptr(o), _lib.ptr(vin), B, R, int(votes), _lib.ptr(out), _lib.current_stream(dev)),
-                   "deftet_project_odms_i32")
+    _lib.call("deftet_project_odms_i32", dev, o, vin, B, R, int(votes), out)
     return out
 
 
@@ -3173,10 +2853,7 @@ def voxel_fill(vox_or_bits):
     lib = _lib.load()
     B, R, dev = bits.n_batch, bits.resolution, bits.device
     out = torch.empty_like(bits.words)
-    with _lib.on_device(dev):
-        ws = _lib.workspace(dev, lib.deftet_voxel_fill_workspace_bytes(B, R))
-        _lib.check(lib.deftet_voxel_fill_b32(_lib.ptr(bits.words), B, R, _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
-                   "deftet_voxel_fill_b32")
+    _lib.call("deftet_voxel_fill_b32", dev, bits.words, B, R, out, ws=lib.deftet_voxel_fill_workspace_bytes(B, R))
     res = VoxelBits(out, R)
     return res if isinstance(vox_or_bits, VoxelBits) else res.unpack()
 
@@ -3197,19 +2874,14 @@ def voxel_surface_mesh(vox, iso_value=0.5):
     lib = _lib.load()
     B, R, dev = bits.n_batch, bits.resolution, bits.device
     offs = torch.empty(2 * (B + 1), device=dev, dtype=torch.int32)
-    with _lib.on_device(dev):
-        st = _lib.current_stream(dev)
-        wsb = lib.deftet_voxel_surface_workspace_bytes(B, R)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)            # the count pass leaves its tables here for the fill pass
-        _lib.check(lib.deftet_voxel_surface_count_b32(_lib.ptr(bits.words), B, R, _lib.ptr(offs), _lib.ptr(ws), wsb, st),
-                   "deftet_voxel_surface_count_b32")
-        o = offs.tolist()                                                # the one sync
-        fo, vo = o[:B + 1], o[B + 1:]
-        faces = torch.empty(fo[B], 3, device=dev, dtype=torch.int64)
-        verts = torch.empty(vo[B], 3, device=dev, dtype=torch.float32)
-        _lib.check(lib.deftet_voxel_surface_fill_b32(_lib.ptr(bits.words), B, R, fo[B], vo[B], _lib.ptr(verts) if vo[B] else None,
-                                                     _lib.ptr(faces) if fo[B] else None, _lib.ptr(ws), wsb, st),
-                   "deftet_voxel_surface_fill_b32")
+    # the count pass leaves its tables here for the fill pass
+    ws = torch.empty(lib.deftet_voxel_surface_workspace_bytes(B, R), dtype=torch.uint8, device=dev)
+    _lib.call("deftet_voxel_surface_count_b32", dev, bits.words, B, R, offs, ws=ws)
+    o = offs.tolist()                                                    # the one sync
+    fo, vo = o[:B + 1], o[B + 1:]
+    faces = torch.empty(fo[B], 3, device=dev, dtype=torch.int64)
+    verts = torch.empty(vo[B], 3, device=dev, dtype=torch.float32)
+    _lib.call("deftet_voxel_surface_fill_b32", dev, bits.words, B, R, fo[B], vo[B], verts if vo[B] else None, faces if fo[B] else None, ws=ws)
     return [verts[vo[b]:vo[b + 1]] for b in range(B)], [faces[fo[b]:fo[b + 1]] for b in range(B)]
 
 
@@ -3223,10 +2895,7 @@ def face_edges(faces_fx3, n_vertex):
     F, V, dev = int(f.shape[0]), int(n_vertex), f.device
     pairs = torch.empty(6 * F, 2, device=dev, dtype=torch.int32)
     n = torch.empty(2, device=dev, dtype=torch.int32)
-    with _lib.on_device(dev):
-        ws = _lib.workspace(dev, lib.deftet_face_edges_workspace_bytes(F))
-        _lib.check(lib.deftet_face_edges_i32(_lib.ptr(f), F, V, _lib.ptr(pairs) if F else None, _lib.ptr(n), _lib.ptr(ws), ws.numel(),
-                                             _lib.current_stream(dev)), "deftet_face_edges_i32")
+    _lib.call("deftet_face_edges_i32", dev, f, F, V, pairs if F else None, n, ws=lib.deftet_face_edges_workspace_bytes(F))
     count, bad = n.tolist()
     if bad:
         raise RuntimeError("face_edges: a face index is outside [0, %d)" % V)

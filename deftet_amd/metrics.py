@@ -40,34 +40,26 @@ def point_to_mesh_distance(points, face_vertices, n_face=None, brute=False):
     if points.dim() != 3 or points.shape[2] != 3 or face_vertices.dim() != 4 or face_vertices.shape[2:] != (3, 3) or \
             face_vertices.shape[0] != points.shape[0]:
         raise ValueError("point_to_mesh_distance: points [B,P,3] and face_vertices [B,F,3,3] expected")
-    lib = _lib.load()
     p, fv = points.detach().contiguous().float(), face_vertices.detach().contiguous().float()
     B, P, F, dev = p.shape[0], p.shape[1], fv.shape[1], p.device
     nf = _n_face_dev(n_face, B, F, dev)
     d = torch.empty(B, P, device=dev, dtype=torch.float32)
     fi = torch.empty(B, P, device=dev, dtype=torch.int64)
     dt = torch.empty(B, P, device=dev, dtype=torch.int32)
-    with _lib.on_device(dev):
-        st = _lib.current_stream(dev)
-        if brute:
-            _lib.check(lib.deftet_point_mesh_distance_scan_f32(_lib.ptr(p), _lib.ptr(fv), _lib.ptr(nf), B, P, F, _lib.ptr(d), _lib.ptr(fi),
-                                                               _lib.ptr(dt), st), "deftet_point_mesh_distance_scan_f32")
-        else:
-            ws = _lib.workspace(dev, lib.deftet_point_mesh_distance_workspace_bytes(B, P, F))
-            _lib.check(lib.deftet_point_mesh_distance_f32(_lib.ptr(p), _lib.ptr(fv), _lib.ptr(nf), B, P, F, _lib.ptr(d), _lib.ptr(fi),
-                                                          _lib.ptr(dt), _lib.ptr(ws), ws.numel(), st), "deftet_point_mesh_distance_f32")
+    if brute:
+        _lib.call("deftet_point_mesh_distance_scan_f32", dev, p, fv, nf, B, P, F, d, fi, dt)
+    else:
+        _lib.call("deftet_point_mesh_distance_f32", dev, p, fv, nf, B, P, F, d, fi, dt,
+                  ws=_lib.load().deftet_point_mesh_distance_workspace_bytes(B, P, F))
     return d, fi, dt
 
 
 def _sided(p1, p2, want_i64=True):
     idx = hip_ops.nn_index(p1, p2)                                   # A10, unchanged
-    lib = _lib.load()
     B, N, M, dev = p1.shape[0], p1.shape[1], p2.shape[1], p1.device
     d = torch.empty(B, N, device=dev, dtype=torch.float32)
     i64 = torch.empty(B, N, device=dev, dtype=torch.int64) if want_i64 else None
-    with _lib.on_device(dev):
-        _lib.check(lib.deftet_nn_distance_f32(_lib.ptr(p1), _lib.ptr(p2), _lib.ptr(idx), B, N, M, _lib.ptr(d), _lib.ptr(i64),
-                                              _lib.current_stream(dev)), "deftet_nn_distance_f32")
+    _lib.call("deftet_nn_distance_f32", dev, p1, p2, idx, B, N, M, d, i64)
     return d, i64, idx
 
 
@@ -107,11 +99,7 @@ def sample_faces(face_vertices, n_face, uniforms, areas=None):
     pts = torch.empty(B, N, 3, device=dev, dtype=torch.float32)
     ch = torch.empty(B, N, device=dev, dtype=torch.int64)
     empty = torch.empty(B, device=dev, dtype=torch.int32)
-    with _lib.on_device(dev):
-        ws = _lib.workspace(dev, lib.deftet_sample_points_workspace_bytes(B, F))
-        _lib.check(lib.deftet_sample_points_f32(_lib.ptr(fv), _lib.ptr(a), _lib.ptr(nf), _lib.ptr(u), B, F, N, _lib.ptr(pts), _lib.ptr(ch),
-                                                _lib.ptr(empty), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
-                   "deftet_sample_points_f32")
+    _lib.call("deftet_sample_points_f32", dev, fv, a, nf, u, B, F, N, pts, ch, empty, ws=lib.deftet_sample_points_workspace_bytes(B, F))
     return pts, ch, empty
 
 
@@ -146,11 +134,8 @@ def metric_block(surface_points, pred_points, dist_a=None, dist_b=None, radius=0
     db = None if dist_b is None else dist_b.contiguous().float()
     Nh = 0 if da is None else da.shape[1]
     out = torch.empty(B, 5, device=dev, dtype=torch.float32)
-    with _lib.on_device(dev):
-        ws = _lib.workspace(dev, lib.deftet_surface_metrics_workspace_bytes(B))
-        _lib.check(lib.deftet_surface_metrics_f32(_lib.ptr(s), _lib.ptr(p), _lib.ptr(idx12), _lib.ptr(idx21), _lib.ptr(da), _lib.ptr(db), B,
-                                                  N1, N2, Nh, float(radius), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                                                  _lib.current_stream(dev)), "deftet_surface_metrics_f32")
+    _lib.call("deftet_surface_metrics_f32", dev, s, p, idx12, idx21, da, db, B, N1, N2, Nh, float(radius), out,
+              ws=lib.deftet_surface_metrics_workspace_bytes(B))
     return out
 
 

@@ -35,12 +35,8 @@ class _SparseRender(Function):
         dev = pix.device
         feat = torch.empty(B, P, knum, D, device=dev, dtype=torch.float32)
         face = torch.empty(B, P, knum, device=dev, dtype=torch.int64)
-        with _lib.on_device(dev):
-            ws = _lib.workspace(dev, lib.deftet_sparse_render_workspace_bytes(B, P, F, knum))
-            _lib.check(lib.deftet_sparse_render_fwd_policy_f32(_lib.ptr(pix), _lib.ptr(rng), _lib.ptr(fz), _lib.ptr(fxy), _lib.ptr(ff),
-                                                               _lib.ptr(feat), _lib.ptr(face), _lib.ptr(None), B, P, F, D, knum, eps,
-                                                               int(policy), _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
-                       "deftet_sparse_render_fwd_policy_f32")
+        _lib.call("deftet_sparse_render_fwd_policy_f32", dev, pix, rng, fz, fxy, ff, feat, face, None, B, P, F, D, knum, eps, int(policy),
+                  ws=lib.deftet_sparse_render_workspace_bytes(B, P, F, knum))
         ctx.save_for_backward(pix, fxy, ff, face)
         ctx.eps = eps
         ctx.mark_non_differentiable(face)
@@ -61,12 +57,8 @@ class _SparseRender(Function):
         gxy = torch.empty_like(fxy)
         gff = torch.empty_like(ff)
         dev = pix.device
-        with _lib.on_device(dev):
-            ws = _lib.workspace(dev, lib.deftet_sparse_render_bwd_workspace_bytes(B, P, F, knum))
-            _lib.check(lib.deftet_sparse_render_bwd_f32(_lib.ptr(pix), _lib.ptr(fxy), _lib.ptr(ff), _lib.ptr(face), _lib.ptr(None),
-                                                        _lib.ptr(g), _lib.ptr(gxy), _lib.ptr(gff), B, P, F, D, knum, ctx.eps,
-                                                        _lib.ptr(ws), ws.numel(), _lib.current_stream(dev)),
-                       "deftet_sparse_render_bwd_f32")
+        _lib.call("deftet_sparse_render_bwd_f32", dev, pix, fxy, ff, face, None, g, gxy, gff, B, P, F, D, knum, ctx.eps,
+                  ws=lib.deftet_sparse_render_bwd_workspace_bytes(B, P, F, knum))
         return None, None, None, gxy, gff, None, None, None
 
 
@@ -91,12 +83,8 @@ class _SparseRenderComposite(Function):
         coverage = torch.empty(B, P, 1, device=dev, dtype=torch.float32)
         dep = torch.empty(B, P, 1, device=dev, dtype=torch.float32) if depth else None
         face = torch.empty(B, P, knum, device=dev, dtype=torch.int32)
-        with _lib.on_device(dev):
-            ws = _lib.workspace(dev, lib.deftet_sparse_render_composite_workspace_bytes(B, P, F, D, knum))
-            _lib.check(lib.deftet_sparse_render_composite_fwd_f32(
-                _lib.ptr(pix), _lib.ptr(rng), _lib.ptr(fz), _lib.ptr(fxy), _lib.ptr(ff), B, P, F, D, knum, eps, int(policy), int(depth),
-                background, far_depth, _lib.ptr(colour), _lib.ptr(coverage), _lib.ptr(dep), _lib.ptr(face), _lib.ptr(ws), ws.numel(),
-                _lib.current_stream(dev)), "deftet_sparse_render_composite_fwd_f32")
+        _lib.call("deftet_sparse_render_composite_fwd_f32", dev, pix, rng, fz, fxy, ff, B, P, F, D, knum, eps, int(policy), int(depth),
+                  background, far_depth, colour, coverage, dep, face, ws=lib.deftet_sparse_render_composite_workspace_bytes(B, P, F, D, knum))
         ctx.save_for_backward(pix, fxy, ff, face)              # the inputs and the int32 faces: nothing of size P * knum * D
         ctx.eps, ctx.depth, ctx.background, ctx.far_depth = eps, depth, background, far_depth
         ctx.mark_non_differentiable(face)
@@ -117,12 +105,8 @@ class _SparseRenderComposite(Function):
         gxy = torch.empty_like(fxy)
         gff = torch.empty_like(ff)
         dev = pix.device
-        with _lib.on_device(dev):
-            ws = _lib.workspace(dev, lib.deftet_sparse_render_composite_bwd_workspace_bytes(B, P, F, D, knum))
-            _lib.check(lib.deftet_sparse_render_composite_bwd_f32(
-                _lib.ptr(pix), _lib.ptr(fxy), _lib.ptr(ff), _lib.ptr(face), _lib.ptr(gc), _lib.ptr(gv), _lib.ptr(gd), B, P, F, D, knum,
-                ctx.eps, int(ctx.depth), ctx.background, ctx.far_depth, _lib.ptr(gxy), _lib.ptr(gff), _lib.ptr(ws), ws.numel(),
-                _lib.current_stream(dev)), "deftet_sparse_render_composite_bwd_f32")
+        _lib.call("deftet_sparse_render_composite_bwd_f32", dev, pix, fxy, ff, face, gc, gv, gd, B, P, F, D, knum, ctx.eps, int(ctx.depth),
+                  ctx.background, ctx.far_depth, gxy, gff, ws=lib.deftet_sparse_render_composite_bwd_workspace_bytes(B, P, F, D, knum))
         return None, None, None, gxy, gff, None, None, None, None, None, None
 
 

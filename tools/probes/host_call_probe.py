@@ -45,6 +45,9 @@ out = {
 pos = torch.zeros(1, 8, 3, device=dev)
 idx = torch.zeros(1, 4, dtype=torch.int64, device=dev)
 out["hip_ops.tet_gather (tiny: one library launch)"] = per_call(lambda: hip_ops.tet_gather(pos, idx))
+gathered = torch.empty(1, 1, 4, 3, device=dev)                     # B = 1, V = 8, T = 1, one index list
+out["_lib.call (the same launch, no checks or allocation)"] = per_call(
+    lambda: _lib.call("deftet_tet_gather_fwd_f32", dev, pos, idx, gathered, None, 1, 8, 1, 1))
 w = torch.zeros(2, 16, device=dev)
 out["hip_ops.rowdot (tiny)"] = per_call(lambda: hip_ops.rowdot(w, w, w, w))
 print(json.dumps(out))
