@@ -193,6 +193,10 @@ SIGNATURES = {
     "deftet_tet_components_workspace_bytes": (_sz, [_i, _i]),
     "deftet_tet_components_u8": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "deftet_occupancy_cleanup_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "deftet_tet_refine_workspace_bytes": (_sz, [_i, _i]),
+    "deftet_tet_refine_mark_i64": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "deftet_tet_refine_count_i64": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "deftet_tet_refine_fill_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lock = threading.Lock()

@@ -1266,6 +1266,90 @@ def tet_neighbour_weights(tet_weights_txk, tet_neighbour_idx_tx4, neilevel=1):
     return w
 
 
+# --------------------------------------------------------------------------------- conforming selective refinement
+RefinedTets = collections.namedtuple("RefinedTets", "points_new feat_new tet_new parent kind edges_split")
+_REFINE_MAX_SWEEPS = 64                                 # what one deftet_tet_refine_mark_i64 call enqueues at most
+
+
+def refine_marks(tet_edge_tx6, select, n_edge, sweeps_per_sync=4):
+    """The closed edge marks of a selective refinement: (marks int32 [E] of 0 / 1 on the device, the marks every sweep set, a
+    host list).  Every edge of a selected tet is marked; then sweeps_per_sync in-place sweeps of the face rule (two marked edges
+    of a tet's face mark the third) are enqueued per read-back until the last sweep of a group set nothing, which proves closure.
+    The result is the rule's least fixed point, the same bits whatever the schedule and the grouping.  Raises IndexError on a
+    tet_edge entry outside [0, E), RuntimeError after E + 1 sweeps that still changed something (each sets at least one mark, so
+    that cannot happen)."""
+    _lib.require_gpu(tet_edge_tx6, select)
+    te = tet_edge_tx6 if tet_edge_tx6.dtype == torch.int64 else tet_edge_tx6.long()
+    if te.dim() != 2 or te.shape[1] != 6:
+        raise RuntimeError("refine_marks: tet_edge [T,6] expected, got %s" % (tuple(te.shape),))
+    te = te.contiguous()
+    T, E, dev = int(te.shape[0]), int(n_edge), te.device
+    S = int(sweeps_per_sync)
+    if not 1 <= S <= _REFINE_MAX_SWEEPS:
+        raise ValueError("refine_marks: sweeps_per_sync=%d outside 1..%d" % (S, _REFINE_MAX_SWEEPS))
+    if select.numel() != T or select.device != dev:
+        raise RuntimeError("refine_marks: select needs one entry per tet, on %s" % dev)
+    if E < 0 or E > 6 * T:
+        raise RuntimeError("refine_marks: n_edge=%d outside [0, 6 T]" % E)
+    sel = (select if select.dtype == torch.bool else select != 0).reshape(-1).contiguous().view(torch.uint8)
+    marks = torch.empty(E, device=dev, dtype=torch.int32)
+    state = torch.empty(S + 1, device=dev, dtype=torch.int32)             # the counts of a group's sweeps, then bad
+    counts, reset = [], 1
+    while True:
+        _lib.call("deftet_tet_refine_mark_i64", dev, te, sel, T, E, reset, S, marks, state, state[S:])
+        got = state.tolist()                                              # the one read-back per group
+        if got[S]:
+            raise IndexError("refine_tets: tet_edge entry outside [0, %d)" % E)
+        counts += got[:S]
+        if got[S - 1] == 0:
+            return marks, counts
+        if sum(1 for c in counts if c) > E + 1:
+            raise RuntimeError("refine_tets: the marks did not close within n_edge + 1 sweeps")
+        reset = 0
+
+
+def refine_tets(tet_tx4, points_px3, feat_pxk, select, edges=None, tet_edge=None, sweeps_per_sync=4):
+    """Conforming selective refinement: RefinedTets(points_new f32 [P+M,3], feat_new f32 [P+M,K], tet_new int64 [T',4], parent int64
+    [T'], kind uint8 [T'], edges_split int64 [M,2]).  The tets with select [T] set are split 1 -> 8 like subdivide, and the split
+    is closed (red-green closure on edge marks, refine_marks) so that a face of the result has the owners its parent face had:
+    what tet_neighbours, surface_extract, tet_components and marching_tets assume, and what subdivide(..., subdiv_sig) does not
+    give.  M marked edges get a midpoint each, vertex P + r for marked edge number r of tet_edges' order, (x[a] + x[b]) / 2 in
+    fp32 for positions and features, its ends in edges_split[r].  Tets stay in parent order, a parent's children contiguous;
+    kind = the parent's marked edges: 0 untouched, 1 / 2 / 3 green closure tets (2, 4, 4 children), 6 a regular split (8).
+    Refining a result again is legal and conforming, but the children of green tets degrade in shape: kind tells which they are.
+    Every tet selected: subdivide's points, features and tets bit for bit; none: the input.  edges, tet_edge: tet_edges(tet, P)
+    when the caller has them already (both or neither).  Integers only, the same bits on every run; one read-back per
+    sweeps_per_sync sweeps and one for the sizes.  Raises IndexError on an index out of range, RuntimeError on wrong shapes and CPU
+    tensors (and on a pattern that is no refinement, which closed marks cannot hold)."""
+    _lib.require_gpu(tet_tx4, points_px3, feat_pxk, select, edges, tet_edge)
+    lib = _lib.load()
+    tet, pts, feat = _i64_tets(tet_tx4), _f32c(points_px3), _f32c(feat_pxk)
+    if pts.dim() != 2 or pts.shape[1] != 3 or feat.dim() != 2 or feat.shape[0] != pts.shape[0]:
+        raise RuntimeError("refine_tets: points [P,3] and features [P,K] expected")
+    P, K, T, dev = int(pts.shape[0]), int(feat.shape[1]), int(tet.shape[0]), tet.device
+    if (edges is None) != (tet_edge is None):
+        raise RuntimeError("refine_tets: edges and tet_edge come together")
+    if edges is None:
+        edges, tet_edge = tet_edges(tet, P)
+    edges, tet_edge = edges.long().contiguous(), tet_edge.long().contiguous()
+    if edges.dim() != 2 or edges.shape[1] != 2 or tuple(tet_edge.shape) != (T, 6):
+        raise RuntimeError("refine_tets: edges [E,2] and tet_edge [%d,6] expected" % T)
+    E = int(edges.shape[0])
+    marks, _counts = refine_marks(tet_edge, select, E, sweeps_per_sync)
+    # the count pass leaves the ranks and child offsets in its workspace for the fill pass: a tensor of this call, not the shared one
+    ws = torch.empty(lib.deftet_tet_refine_workspace_bytes(T, E), dtype=torch.uint8, device=dev)
+    totals = torch.empty(3, device=dev, dtype=torch.int32)
+    _lib.call("deftet_tet_refine_count_i64", dev, tet_edge, edges, marks, P, T, E, totals, ws=ws)
+    M, Tn, bad = totals.tolist()
+    if bad:
+        raise RuntimeError("refine_tets: an edge end is outside [0, %d), or the marks are not closed" % P)
+    out = RefinedTets(torch.empty(P + M, 3, device=dev, dtype=torch.float32), torch.empty(P + M, K, device=dev, dtype=torch.float32),
+                      torch.empty(Tn, 4, device=dev, dtype=torch.int64), torch.empty(Tn, device=dev, dtype=torch.int64),
+                      torch.empty(Tn, device=dev, dtype=torch.uint8), torch.empty(M, 2, device=dev, dtype=torch.int64))
+    _lib.call("deftet_tet_refine_fill_f32", dev, tet, tet_edge, edges, marks, pts, feat, P, T, E, K, M, Tn, *out, ws=ws)
+    return out
+
+
 # --------------------------------------------------------------------------------- N2 vertex <-> tet gather
 def _idx64(tet_idx):
     if tet_idx.dtype != torch.int64:
@@ -1883,6 +1967,29 @@ def cleaned_occupancy(occ, inside, keep):
     """occ with the outcome of occupancy_cleanup written into it: 0 where an inside tet was dropped, 1 where an outside tet was
     filled, occ everywhere else (all three of one shape)."""
     return torch.where(keep, torch.where(inside, occ, torch.ones_like(occ)), torch.where(inside, torch.zeros_like(occ), occ))
+
+
+def occupancy_band(inside, nbr_tx4, rings=0):
+    """bool [T]: the tets that have a face neighbour in the other state in any shape of inside [B,T] (or [T]; non-zero = inside),
+    grown by `rings` face rings — the selection refine_tets wants around a surface.  nbr_tx4 int64 [T,4] (or a TetFaceNeighbours:
+    its table); entries of -1 are ignored.  Plain torch ops on the existing neighbour table, no kernel of its own: a handful of
+    gathers over [B,T,4], on whatever device the inputs are."""
+    nbr = nbr_tx4.table if isinstance(nbr_tx4, TetFaceNeighbours) else nbr_tx4
+    if nbr.dim() != 2 or nbr.shape[1] != 4:
+        raise RuntimeError("occupancy_band: neighbour table [T,4] expected, got %s" % (tuple(nbr.shape),))
+    T = int(nbr.shape[0])
+    if inside.dim() not in (1, 2) or inside.shape[-1] != T or inside.device != nbr.device:
+        raise RuntimeError("occupancy_band: inside [B,%d] or [%d] on %s expected, got %s on %s" % (T, T, nbr.device, tuple(inside.shape), inside.device))
+    ins = inside if inside.dtype == torch.bool else inside != 0
+    ins = ins[None] if ins.dim() == 1 else ins
+    if int(rings) < 0:
+        raise ValueError("occupancy_band: rings=%d is negative" % rings)
+    has = nbr >= 0
+    to = torch.where(has, nbr, torch.zeros_like(nbr)).long()
+    band = ((ins[:, to] != ins[:, :, None]) & has[None]).any(2).any(0)
+    for _ in range(int(rings)):
+        band = band | (band[to] & has).any(1)
+    return band
 
 
 # --------------------------------------------------------------------------------- marching tetrahedra (DESIGN.md §6l)

@@ -7,6 +7,9 @@ and return values).  The reference works on numpy arrays on the host; these acce
     generate_edge_points     (:238-252)   generate_subdivision   (:255-301)
     generate_point_adj_idx   (:134-146)   delete_tet             (:171-180)
     tetweights2tetneighbourweights (3_model/deftet.py:316-331)
+
+generate_conforming_subdivision has no reference counterpart: the selective generate_subdivision with the refinement closed
+(hip_ops.refine_tets), for the operators that need every interior face to have two owners.
 """
 import numpy as np
 import torch
@@ -63,6 +66,17 @@ def generate_subdivision(tet_list_tx4, tet_points_px3, tet_feat_pxk, tet_list_su
     sig = None if tet_list_subdiv_sig is None else _in(tet_list_subdiv_sig, torch.bool)[0]
     pn, fn, tn = hip_ops.subdivide(tet, pts, feat, sig)
     return _out(pn, npy), _out(fn, npy), _out(tn, npy)
+
+
+def generate_conforming_subdivision(tet_list_tx4, tet_points_px3, tet_feat_pxk, tet_list_subdiv_sig):
+    """generate_subdivision's triple for a selective split that stays a conforming mesh: the tets with tet_list_subdiv_sig set
+    are split 1 -> 8 and their neighbours as far as the closure reaches (hip_ops.refine_tets; tets stay in parent order)."""
+    tet, npy = _in(tet_list_tx4, torch.int64)
+    pts, _ = _in(tet_points_px3, torch.float32)
+    feat, _ = _in(tet_feat_pxk, torch.float32)
+    sig, _ = _in(tet_list_subdiv_sig, torch.bool)
+    r = hip_ops.refine_tets(tet, pts, feat, sig)
+    return _out(r.points_new, npy), _out(r.feat_new, npy), _out(r.tet_new, npy)
 
 
 def generate_point_adj_idx(n_point, tet_list):

@@ -42,7 +42,9 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
-/* 370: generalised winding numbers for inside tests on open meshes — deftet_winding_number_f32, its workspace size,
+/* 380: conforming selective tet refinement (red-green closure on edge marks) — deftet_tet_refine_mark_i64, deftet_tet_refine_count_i64,
+ *      deftet_tet_refine_fill_f32 and deftet_tet_refine_workspace_bytes (tet_refine.hip).
+ * 370: generalised winding numbers for inside tests on open meshes — deftet_winding_number_f32, its workspace size,
  *      deftet_winding_number_levels, deftet_winding_number_resolve_algo (winding_number.hip).
  * 360: pixel-aligned image-feature sampling for the single-image branch — deftet_image_sample_fwd_f32, deftet_image_cells_f32,
  *      deftet_image_sample_bwd_map_f32 / _bwd_uv_f32 / _bwd_global_f32 and their workspace size (image_sample.hip).
@@ -365,6 +367,51 @@ int deftet_tet_components_u8(const uint8_t *inside_bxt, const int32_t *nbr32_tx4
 int deftet_occupancy_cleanup_u8(const uint8_t *inside_bxt, const int32_t *nbr32_tx4, int n_batch, int n_tet, int keep_largest,
                                 int min_size, int fill_voids, uint8_t *keep, int32_t *labels, int32_t *sizes, uint8_t *open,
                                 int32_t *count, int32_t *bad, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * Conforming selective refinement of a tet list (380; tet_refine.hip): refine the selected tets and close the
+ * refinement so that no split tet leaves a midpoint on an edge or face its neighbour still owns whole.  The reference's selective
+ * generate_subdivision (3_model/prepare_for_wz.py:255-301 with subdiv_sig) does leave them.  Over edges_ex2 int64 [n_edge,2] and
+ * tet_edge_tx6 int64 [n_tet,6] of deftet_tet_edges_i64 (local slots 0 ab, 1 ac, 2 ad, 3 bc, 4 bd, 5 cd), n_edge <= 6 n_tet:
+ *   marks    every edge of a selected tet; then, until nothing changes, a tet's face with two of its three edges marked gets the
+ *            third (faces as slots {0,1,3}, {0,2,4}, {1,2,5}, {3,4,5}).  The least fixed point of a monotone rule: the same set
+ *            in whatever order the rule is applied.  A closed tet has 0, 1, 2 (opposite: slots e and 5 - e), 3 (one face) or 6
+ *            marked slots: these are the only sets of slots in which no face has exactly two (all 64 checked), whatever ids
+ *            tet_edge holds.  Any other pattern means the marks are not closed and is reported in bad;
+ *   vertices marked edge number r in list order becomes vertex n_point + r = (x[a] + x[b]) / 2.0f;
+ *   tets     in parent order, the children of one parent contiguous; "v[i] = m" is the parent with corner i replaced by m, m(p,q)
+ *            the midpoint of the edge between corners p and q:
+ *              0 marks  the parent;
+ *              1 mark   edge (p,q), p < q: v[q] = m; v[p] = m;
+ *              2 marks  edges e0 < e1 with ends (p0,q0), (p1,q1): {v[q0] = m0, v[q1] = m1}; {v[q0] = m0, v[p1] = m1};
+ *                       {v[p0] = m0, v[q1] = m1}; {v[p0] = m0, v[p1] = m1};
+ *              3 marks  the face's corners p < q < r: {v[q] = m(p,q), v[r] = m(p,r)}; {v[p] = m(p,q), v[r] = m(q,r)};
+ *                       {v[p] = m(p,r), v[q] = m(q,r)}; {v[p] = m(p,q), v[q] = m(q,r), v[r] = m(p,r)};
+ *              6 marks  the eight children of deftet_subdivide_f32, in its order.
+ * Selecting every tet gives deftet_subdivide_f32's points, features and tets bit for bit; selecting none, the input.
+ *
+ * deftet_tet_refine_mark_i64: marks_e uint32 [n_edge], the caller's, one 0 / 1 word per edge.  reset != 0: the marks and *bad are
+ * zeroed and the edges of the tets with select_t uint8 [n_tet] != 0 are marked; reset == 0 continues on the marks as they are
+ * (select_t is not read).  Then n_sweeps (0..64) in-place sweeps, one tet per lane: marks only go 0 -> 1, no lane waits for
+ * another, integer atomics only.  sweep_counts int32 [n_sweeps] (device) = the marks each sweep set; a sweep that set nothing
+ * read a state nobody wrote during it, so a last count of 0 proves closure — call again while it is not 0 (every such sweep sets
+ * a mark, so n_edge + 1 sweeps always suffice).  *bad (device) = 1 for a tet_edge entry outside [0, n_edge): such a tet is skipped. */
+int deftet_tet_refine_mark_i64(const int64_t *tet_edge_tx6, const uint8_t *select_t, int n_tet, int n_edge, int reset, int n_sweeps,
+                               uint32_t *marks_e, int32_t *sweep_counts, int32_t *bad, void *stream);
+/* Count pass on closed marks: totals int32 [3] (device) = {M marked edges, T' tets of the refinement, bad}; bad = 1 for an illegal
+ * pattern, a tet_edge entry outside [0, n_edge) or a marked edge with an end outside [0, n_point) (such a tet is counted as one
+ * child: the sizes stay valid, the result is not a refinement).  Leaves the ranks and child offsets in the workspace for the fill
+ * pass: hand the same workspace, untouched, to it. */
+size_t deftet_tet_refine_workspace_bytes(int n_tet, int n_edge);
+int deftet_tet_refine_count_i64(const int64_t *tet_edge_tx6, const int64_t *edges_ex2, const uint32_t *marks_e, int n_point, int n_tet,
+                                int n_edge, int32_t *totals, void *workspace, size_t workspace_bytes, void *stream);
+/* Fill pass, n_split = M and n_tet_new = T' of the count pass: points_new f32 [n_point+M,3], feat_new f32 [n_point+M,n_feat]
+ * (n_feat = 0: not touched), tet_new int64 [T',4], parent int64 [T'], kind uint8 [T'] = the parent's number of marked slots,
+ * edges_split int64 [M,2] = the ends of the marked edges. */
+int deftet_tet_refine_fill_f32(const int64_t *tet_tx4, const int64_t *tet_edge_tx6, const int64_t *edges_ex2, const uint32_t *marks_e,
+                               const float *points, const float *feat, int n_point, int n_tet, int n_edge, int n_feat, int n_split,
+                               long long n_tet_new, float *points_new, float *feat_new, int64_t *tet_new, int64_t *parent,
+                               uint8_t *kind, int64_t *edges_split, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------
  * Marching tetrahedra on a per-vertex field (320; marching_tets.hip): a welded iso-surface mesh per shape, with
