@@ -56,7 +56,12 @@ def test_radix_sort_ignores_bits_above_the_requested_ones_and_honours_a_device_s
     assert np.array_equal(ko.cpu().numpy()[:used2], keys2[:used2][order]) and np.array_equal(vo.cpu().numpy()[:used2], order.astype(np.int32))
 
 
-@pytest.mark.parametrize("n", SIZES)
+# scans of up to 8,192 elements run in one workgroup, longer ones as tile totals, one spine workgroup of 1,024 threads and an apply
+# pass: both sides of that switch, and of the spine's second trip (more than 1,024 tiles of 2,048)
+SCAN_SIZES = SIZES + [8191, 8192, 8193, 16_384, 1024 * 2048, 1024 * 2048 + 1]
+
+
+@pytest.mark.parametrize("n", SCAN_SIZES)
 @pytest.mark.parametrize("dt", [np.int32, np.int64])
 def test_scans_equal_numpy(cuda, n, dt):
     from deftet_amd import hip_ops
