@@ -2806,6 +2806,307 @@ def tet_field_sample(field, pos_bxvx3, tet_idx, pts_bxqx3, csr=None, topology=No
     return (out, cond, bary) if return_index else out
 
 
+# ------------------------------------------------------------------------------------
+# field gradients on the tets, their energies, per-tet values to the vertices (tet_field_grad.hip)
+# ------------------------------------------------------------------------------------
+TFE_MAX_CHANNELS, _TFE_STATS = 8, 17                    # tet_field_grad.hip kTfeMaxC, kTfeStats
+_CsrAndList = collections.namedtuple("_CsrAndList", "csr tet_idx32")     # what tet_to_vertex reads of a TetTopology
+
+
+def _check_csr(caller, csr, Bi, V, T):
+    if (not isinstance(csr, (tuple, list)) or len(csr) != 3 or csr[2] != Bi or csr[1].numel() != Bi * T * 4
+            or csr[0].numel() != Bi * V + 1):
+        raise RuntimeError("%s: csr is not tet_vertex_csr(tet_idx, %d) of this tet list" % (caller, V))
+
+
+def _tfg_inputs(caller, field, pos, tet_idx, topology, max_channels=None):
+    """(field, pos, idx) contiguous — f32 [B,V,C], f32 [B,V,3], int32 [Bi,T,4] — checked against each other; the topology's own
+    int32 copy of the list when tet_idx is the list it was built from"""
+    for name, t in (("field", field), ("pos", pos), ("tet_idx", tet_idx)):
+        if not isinstance(t, torch.Tensor):
+            raise RuntimeError("%s: %s must be a tensor" % (caller, name))
+    if pos.device != field.device or tet_idx.device != field.device:
+        raise RuntimeError("%s: field, pos and tet_idx must be on one device" % caller)
+    _lib.require_gpu(field, pos, tet_idx)
+    field, pos = _pv_need(field, torch.float32, caller + ": field"), _pv_need(pos, torch.float32, caller + ": pos")
+    if tet_idx.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError("%s: tet_idx must be int32 or int64 (got %s)" % (caller, str(tet_idx.dtype).replace("torch.", "")))
+    if field.dim() != 3 or field.shape[2] < 1:
+        raise RuntimeError("%s: field [B,V,C] with a channel dimension of at least 1 expected (got %s)" % (caller, tuple(field.shape)))
+    B, V, C = field.shape
+    if max_channels is not None and C > max_channels:
+        raise _lib.DefTetHipError("%s: field [B,V,C] with 1 <= C <= %d expected, got %s (DEFTET_EINVAL)" % (caller, max_channels, tuple(field.shape)))
+    if pos.dim() != 3 or tuple(pos.shape) != (B, V, 3):
+        raise RuntimeError("%s: pos [%d,%d,3] expected (got %s)" % (caller, B, V, tuple(pos.shape)))
+    idx = getattr(topology, "tet_idx32", None)
+    if idx is None or (tet_idx is not getattr(topology, "tet_idx", None) and tet_idx is not idx):
+        idx = tet_idx
+    idx = _idx32(idx)
+    if idx.dim() != 3 or idx.shape[2] != 4 or idx.shape[0] not in (1, B):
+        raise RuntimeError("%s: tet_idx [T,4] or [B,T,4] expected (got %s)" % (caller, tuple(tet_idx.shape)))
+    return field, pos, idx
+
+
+def _tfg_csr(caller, csr, topology, idx, V):
+    if csr is None:
+        csr = getattr(topology, "csr", None)
+    if csr is not None:
+        _check_csr(caller, csr, idx.shape[0], V, idx.shape[1])
+    return csr
+
+
+def tet_field_gradient_fwd(field, pos_bxvx3, tet_idx, return_volume=False):
+    """grad f32 [B,T,C,3] (and vol f32 [B,T]): per tet the gradient of the linear interpolant of field f32 [B,V,C] over the
+    positions f32 [B,V,3], g_c = (n0 df0 + n1 df1 + n2 df2) / det in fp32 (include/deftet_hip.h), 0 with volume 0 on a dead tet
+    (det > 0 fails).  One launch.  The raw forward of tet_field_gradient."""
+    field, pos, idx = _tfg_inputs("tet_field_gradient", field, pos_bxvx3, tet_idx, None)
+    B, V, C = field.shape
+    T, dev = idx.shape[1], field.device
+    out = torch.empty(B, T, C, 3, device=dev, dtype=torch.float32)
+    vol = torch.empty(B, T, device=dev, dtype=torch.float32) if return_volume else None
+    _lib.call("deftet_tet_field_gradient_fwd_f32", dev, field, pos, idx, out, vol, B, V, T, idx.shape[0], C)
+    return (out, vol) if return_volume else out
+
+
+def tet_volumes(pos_bxvx3, tet_idx):
+    """vol f32 [B,T] = det E / 6 of every tet, 0 for a dead one: tet_field_gradient's volumes alone (no gradient), e.g. as the
+    constant weights of tet_to_vertex.  One launch."""
+    _lib.require_gpu(pos_bxvx3, tet_idx)
+    pos, idx = _pv_need(pos_bxvx3.detach(), torch.float32, "tet_volumes: pos"), _idx32(tet_idx)
+    if pos.dim() != 3 or pos.shape[2] != 3 or idx.dim() != 3 or idx.shape[2] != 4 or idx.shape[0] not in (1, pos.shape[0]):
+        raise RuntimeError("tet_volumes: pos [B,V,3] and tet_idx [T,4] or [B,T,4] expected (got %s, %s)" % (tuple(pos.shape), tuple(idx.shape)))
+    B, V, T = pos.shape[0], pos.shape[1], idx.shape[1]
+    vol = torch.empty(B, T, device=pos.device, dtype=torch.float32)
+    _lib.call("deftet_tet_field_gradient_fwd_f32", pos.device, None, pos, idx, None, vol, B, V, T, idx.shape[0], 1)
+    return vol
+
+
+def tet_field_gradient_bwd(grad_out, grad_vol, field, pos_bxvx3, tet_idx, csr, want_field=True, want_pos=True):
+    """(grad_field f32 [B,V,C] | None, grad_pos f32 [B,V,3] | None): grad_out f32 [B,T,C,3] and grad_vol f32 [B,T] (or None) of
+    tet_field_gradient_fwd taken to the vertices, per vertex one fp32 accumulator over its incidences in the CSR's order
+    (ascending 4 t + corner); no atomics, the same bits on every run.  One launch per gradient asked for."""
+    field, pos, idx = _tfg_inputs("tet_field_gradient_bwd", field, pos_bxvx3, tet_idx, None)
+    B, V, C = field.shape
+    T, dev = idx.shape[1], field.device
+    _check_csr("tet_field_gradient_bwd", csr, idx.shape[0], V, T)
+    _lib.require_gpu(grad_out, grad_vol)
+    g = _f32c(grad_out)
+    if tuple(g.shape) != (B, T, C, 3):
+        raise RuntimeError("tet_field_gradient_bwd: grad_out %s expected (got %s)" % ((B, T, C, 3), tuple(g.shape)))
+    gv = None
+    if grad_vol is not None:
+        gv = _f32c(grad_vol)
+        if tuple(gv.shape) != (B, T):
+            raise RuntimeError("tet_field_gradient_bwd: grad_vol %s expected (got %s)" % ((B, T), tuple(gv.shape)))
+    gf = torch.empty(B, V, C, device=dev, dtype=torch.float32) if want_field else None
+    gp = torch.empty(B, V, 3, device=dev, dtype=torch.float32) if want_pos else None
+    if want_field or want_pos:
+        _lib.call("deftet_tet_field_gradient_bwd_f32", dev, g, gv, field, pos, idx, csr[0], csr[1], gf, gp, B, V, T, idx.shape[0], C)
+    return gf, gp
+
+
+class _TetFieldGradient(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, field, pos, idx, csr, return_volume):
+        out, vol = tet_field_gradient_fwd(field, pos, idx, return_volume=True) if return_volume else (tet_field_gradient_fwd(field, pos, idx), None)
+        ctx.save_for_backward(field, pos)
+        ctx.idx, ctx.csr = idx, csr
+        ctx.set_materialize_grads(False)
+        return out, vol
+
+    @staticmethod
+    def backward(ctx, g_out, g_vol):
+        field, pos = ctx.saved_tensors
+        want_f, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_f or want_p):
+            return None, None, None, None, None
+        if g_out is None and g_vol is None:
+            return (torch.zeros_like(field) if want_f else None, torch.zeros_like(pos) if want_p else None, None, None, None)
+        if g_out is None:
+            g_out = field.new_zeros(field.shape[0], ctx.idx.shape[1], field.shape[2], 3)
+        csr = ctx.csr
+        if csr is None:                                              # the slow path: a sort of 4 T incidences and a host sync per backward
+            csr = tet_vertex_csr(ctx.idx, pos.shape[1])
+        gf, gp = tet_field_gradient_bwd(g_out, g_vol, field.detach(), pos.detach(), ctx.idx, csr, want_field=want_f, want_pos=want_p)
+        return gf, gp, None, None, None
+
+
+def tet_field_gradient(field, pos_bxvx3, tet_idx, csr=None, topology=None, return_volume=False):
+    """f32 [B,T,C,3]: the gradient of a per-vertex field f32 [B,V,C] (an SDF, an occupancy, features) on every tet of the mesh
+    (pos f32 [B,V,3], tet_idx int [T,4] or [B,T,4]) — it is constant on a tet: g_c = E^-1 df_c with the rows of E the edges from
+    vertex 0 and df_k = f(v_{k+1},c) - f(v0,c), in the adjugate form in fp32.  return_volume: also vol f32 [B,T] = det E / 6.
+    A tet is live iff det E > 0 in fp32 (the orientation of every grid here); a NaN, flat or inverted tet has gradient 0 and
+    volume 0 and gives nothing to a backward.  Differentiable in field and pos, also through vol: the gradient lands on the
+    vertices through `csr` = tet_vertex_csr(tet_idx, V) in its order, without float atomics (the same bits on every run).  A
+    TetTopology handed in as `topology` brings its own csr.  csr=None with a gradient asked for is the SLOW PATH: the CSR is
+    rebuilt in every backward (a sort and a host sync)."""
+    field, pos, idx = _tfg_inputs("tet_field_gradient", field, pos_bxvx3, tet_idx, topology)
+    csr = _tfg_csr("tet_field_gradient", csr, topology, idx, field.shape[1])
+    out, vol = _TetFieldGradient.apply(field, pos, idx, csr, bool(return_volume))
+    return (out, vol) if return_volume else out
+
+
+class _TetFieldEnergies(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, field, pos, idx, csr, target):
+        lib = _lib.load()
+        B, V, C = field.shape
+        T, dev = idx.shape[1], field.device
+        out = torch.empty(B, C, 2, device=dev, dtype=torch.float32)
+        stats = torch.empty(B, _TFE_STATS, device=dev, dtype=torch.float64)
+        _lib.call("deftet_tet_field_energies_fwd_f32", dev, field, pos, idx, out, stats, target, B, V, T, idx.shape[0], C,
+                  ws=lib.deftet_tet_field_energies_workspace_bytes(B))
+        ctx.save_for_backward(field, pos, stats)
+        ctx.idx, ctx.csr, ctx.target = idx, csr, target
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        field, pos, stats = ctx.saved_tensors
+        want_f, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_f or want_p):
+            return None, None, None, None, None
+        B, V, C = field.shape
+        idx, dev = ctx.idx, field.device
+        csr = ctx.csr
+        if csr is None:                                              # the slow path, as in tet_field_gradient
+            csr = tet_vertex_csr(idx, V)
+        gf = torch.empty(B, V, C, device=dev, dtype=torch.float32) if want_f else None
+        gp = torch.empty(B, V, 3, device=dev, dtype=torch.float32) if want_p else None
+        _lib.call("deftet_tet_field_energies_bwd_f32", dev, stats, _f32c(g_out), ctx.target, field, pos, idx, csr[0], csr[1], gf, gp, B, V,
+                  idx.shape[1], idx.shape[0], C)
+        return gf, gp, None, None, None
+
+
+def tet_field_energies(field, pos_bxvx3, tet_idx, csr=None, topology=None, target=1.0):
+    """f32 [B,C,2], 1 <= C <= 8: the two energies of a per-vertex field's gradient g (tet_field_gradient) over the live tets,
+    weighted by their volumes w_t, W = sum w_t:  [...,0] = sum w_t |g_c|^2 / W, the Dirichlet energy (the FEM Laplacian), and
+    [...,1] = sum w_t (|g_c| - target)^2 / W, the Eikonal term.  One pass over the tets, [B,T,C,3] never stored, the sums in
+    fp64 in one order.  Differentiable in field and pos through the saved per-shape sums and the incidence CSR (csr, topology
+    and the slow path as in tet_field_gradient), without float atomics.  Where |g| = 0 the Eikonal term's derivative is taken
+    as 0.  W = 0 (no live tet) gives 0 energies and 0 gradients."""
+    field, pos, idx = _tfg_inputs("tet_field_energies", field, pos_bxvx3, tet_idx, topology, max_channels=TFE_MAX_CHANNELS)
+    csr = _tfg_csr("tet_field_energies", csr, topology, idx, field.shape[1])
+    return _TetFieldEnergies.apply(field, pos, idx, csr, float(target))
+
+
+def _ttv_topology(tet_idx_or_csr, n_vertex):
+    """(csr, int32 idx | None) of tet_to_vertex's second argument: a TetTopology (its csr and list), a csr tuple, or a tet list"""
+    V = int(n_vertex)
+    if hasattr(tet_idx_or_csr, "csr") and hasattr(tet_idx_or_csr, "tet_idx32"):
+        return tet_idx_or_csr.csr, _idx32(tet_idx_or_csr.tet_idx32)
+    if isinstance(tet_idx_or_csr, (tuple, list)):
+        return tet_idx_or_csr, None
+    if not isinstance(tet_idx_or_csr, torch.Tensor) or tet_idx_or_csr.dtype not in (torch.int32, torch.int64):
+        raise RuntimeError("tet_to_vertex: a tet list int [T,4] or [B,T,4], a tet_vertex_csr tuple or a TetTopology expected")
+    _lib.require_gpu(tet_idx_or_csr)
+    idx = _idx32(tet_idx_or_csr)
+    if idx.dim() != 3 or idx.shape[2] != 4:
+        raise RuntimeError("tet_to_vertex: tet_idx [T,4] or [B,T,4] expected (got %s)" % (tuple(tet_idx_or_csr.shape),))
+    return tet_vertex_csr(idx, V), idx                               # the slow path: the CSR is built in this call
+
+
+def _csr_tet_list(csr, V, T):
+    """int32 [Bi,T,4] of a tet_vertex_csr: position i of the sorted incidences belongs to the vertex whose segment holds it"""
+    offsets, slots, Bi = csr
+    pos = torch.arange(slots.numel(), device=slots.device, dtype=torch.int32)
+    row = torch.bucketize(pos, offsets[1:].contiguous(), right=True)      # b V + v
+    idx = torch.empty(Bi * T * 4, device=slots.device, dtype=torch.int32)
+    idx[(row // V).long() * (4 * T) + slots.long()] = (row % V).to(torch.int32)
+    return idx.reshape(Bi, T, 4)
+
+
+def tet_to_vertex_fwd(values, weights, csr, n_vertex, fill=0.0):
+    """(out f32 [B,V,C], weight_sum f32 [B,V]): per vertex (sum w_t values[t]) / (sum w_t) over its incidences in the CSR's order,
+    one fp32 accumulator each from 0, every step rounded; `fill` where the weight sum is not > 0.  One launch."""
+    B, T, C = values.shape
+    V, dev = int(n_vertex), values.device
+    out = torch.empty(B, V, C, device=dev, dtype=torch.float32)
+    wsum = torch.empty(B, V, device=dev, dtype=torch.float32)
+    _lib.call("deftet_tet_to_vertex_fwd_f32", dev, values, weights, csr[0], csr[1], out, wsum, float(fill), B, V, T, csr[2], C)
+    return out, wsum
+
+
+def tet_to_vertex_bwd(grad_out, weight_sum, weights, tet_idx, n_tet):
+    """grad_values f32 [B,T,C] = w_t * (gout[v_0] / W_{v_0} + ... + gout[v_3] / W_{v_3}), one fp32 accumulator from 0 over the
+    corners in order, a corner whose weight sum is not > 0 left out: a gather, no reduction.  One launch."""
+    g = _f32c(grad_out)
+    B, V, C = g.shape
+    idx = _idx32(tet_idx)
+    gval = torch.empty(B, int(n_tet), C, device=g.device, dtype=torch.float32)
+    _lib.call("deftet_tet_to_vertex_bwd_f32", g.device, g, weight_sum, weights, idx, gval, B, V, int(n_tet), idx.shape[0], C)
+    return gval
+
+
+class _TetToVertex(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, values, weights, csr, idx, V, fill):
+        out, wsum = tet_to_vertex_fwd(values, weights, csr, V, fill)
+        ctx.save_for_backward(wsum, weights)
+        ctx.csr, ctx.idx, ctx.n = csr, idx, (V, values.shape[1])
+        ctx.mark_non_differentiable(wsum)
+        return out, wsum
+
+    @staticmethod
+    def backward(ctx, g_out, _g_wsum):
+        wsum, weights = ctx.saved_tensors
+        V, T = ctx.n
+        idx = ctx.idx if ctx.idx is not None else _csr_tet_list(ctx.csr, V, T)     # (a csr alone: its tet list is read back from it)
+        return tet_to_vertex_bwd(g_out, wsum, weights, idx, T), None, None, None, None, None
+
+
+def tet_to_vertex(values_bxtxc, tet_idx_or_csr, n_vertex, weights=None, fill=0.0):
+    """f32 [B,V,C]: per-tet values f32 [B,T,C] (an occupancy, tet_field_gradient's rows flattened) carried to the vertices as the
+    weighted mean over each vertex's incident tets, (sum w_t values[t]) / (sum w_t) in the incidence CSR's order (ascending
+    4 t + corner), one fp32 accumulator each from 0 with every step rounded.  weights f32 [B,T] (the tet volumes, say) are a
+    CONSTANT: they get no gradient; None = 1, the plain mean.  A vertex whose weight sum is not > 0 — no incident tet, or only
+    dead ones — gets `fill`.  tet_idx_or_csr: tet_vertex_csr(tet_idx, n_vertex) built once per list, a TetTopology, or the tet
+    list itself int [T,4] / [B,T,4] (the slow path: the CSR is built in this call, a sort and a host sync).  Differentiable in
+    values: grad[t] = w_t sum_k gout[v_k] / W_{v_k}, a gather over the four corners (with a csr alone the tet list is first read
+    back from it)."""
+    if not isinstance(values_bxtxc, torch.Tensor) or values_bxtxc.dim() != 3 or values_bxtxc.shape[2] < 1:
+        raise RuntimeError("tet_to_vertex: values [B,T,C] with a channel dimension of at least 1 expected (got %s)"
+                           % (tuple(getattr(values_bxtxc, "shape", ())),))
+    _lib.require_gpu(values_bxtxc, weights)
+    val = _pv_need(values_bxtxc, torch.float32, "tet_to_vertex: values")
+    B, T, C = val.shape
+    V = int(n_vertex)
+    csr, idx = _ttv_topology(tet_idx_or_csr, V)
+    if not isinstance(csr, (tuple, list)) or len(csr) != 3 or csr[2] not in (1, B):
+        raise RuntimeError("tet_to_vertex: csr is not tet_vertex_csr(tet_idx, %d) of this tet list" % V)
+    _check_csr("tet_to_vertex", csr, csr[2], V, T)
+    if idx is not None and tuple(idx.shape) != (csr[2], T, 4):
+        raise RuntimeError("tet_to_vertex: the tet list %s does not belong to values %s" % (tuple(idx.shape), tuple(val.shape)))
+    w = None
+    if weights is not None:
+        w = _pv_need(weights.detach(), torch.float32, "tet_to_vertex: weights")
+        if tuple(w.shape) != (B, T):
+            raise RuntimeError("tet_to_vertex: weights [%d,%d] expected (got %s)" % (B, T, tuple(w.shape)))
+    if csr[0].device != val.device or (w is not None and w.device != val.device) or (idx is not None and idx.device != val.device):
+        raise RuntimeError("tet_to_vertex: values, weights and the tet list must be on one device")
+    return _TetToVertex.apply(val, w, csr, idx, V, float(fill))[0]
+
+
+def vertex_field_gradient(field, pos_bxvx3, tet_idx, csr=None, topology=None, fill=0.0):
+    """f32 [B,V,C,3]: the field's gradient at the vertices, the volume-weighted mean of tet_field_gradient over each vertex's
+    incident tets (tet_to_vertex with the volumes as constant weights); `fill` at a vertex with no live tet.  Differentiable in
+    field and pos through the per-tet gradients."""
+    field, pos, idx = _tfg_inputs("vertex_field_gradient", field, pos_bxvx3, tet_idx, topology)
+    V = field.shape[1]
+    csr = _tfg_csr("vertex_field_gradient", csr, topology, idx, V)
+    if csr is None:
+        csr = tet_vertex_csr(idx, V)                                 # the slow path, once for both steps
+    g, vol = _TetFieldGradient.apply(field, pos, idx, csr, True)
+    B, T, C = g.shape[:3]
+    return tet_to_vertex(g.reshape(B, T, C * 3), _CsrAndList(csr, idx), V, weights=vol, fill=fill).reshape(B, V, C, 3)
+
+
+def unit_normals(grad_nx3):
+    """-g / |g| row by row, 0 where |g| = 0: the outward normal of a level set whose inside is the higher side"""
+    norm = grad_nx3.norm(dim=-1, keepdim=True)
+    return torch.where(norm > 0, -grad_nx3 / norm.clamp_min(torch.finfo(torch.float32).tiny), torch.zeros_like(grad_nx3))
+
+
 def trilinear_devoxelize_fwd(r, is_training, coords, features):
     """(outs f32 [B,C,N], inds i32 [B,8,N], wgts f32 [B,8,N]) of coords f32 [B,3,N] in voxel units and features f32 [B,C,r^3]: the
     extension's trilinear_devoxelize_forward, one fixed expression per point (the reference kernel's bits).  hi = lo where

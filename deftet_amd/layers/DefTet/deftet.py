@@ -81,6 +81,21 @@ class TetTopology:
         return hip_ops.tet_field_sample(field, vertice_pos, self.tet_idx32, pts, csr=self.csr, topology=self, fill=fill,
                                         return_index=return_index)
 
+    def field_gradient(self, field, vertice_pos, return_volume=False):
+        """hip_ops.tet_field_gradient on this tet list: the gradient of the per-vertex field [B,V,C] on every tet, [B,T,C,3] (and
+        the volumes [B,T]), differentiable in field and vertice_pos through the cached incidence CSR."""
+        return hip_ops.tet_field_gradient(field, vertice_pos, self.tet_idx32, csr=self.csr, topology=self, return_volume=return_volume)
+
+    def field_energies(self, field, vertice_pos, target=1.0):
+        """hip_ops.tet_field_energies on this tet list: [B,C,2] = the volume-weighted Dirichlet energy and Eikonal term
+        (|grad f| - target)^2 of the per-vertex field, differentiable in field and vertice_pos."""
+        return hip_ops.tet_field_energies(field, vertice_pos, self.tet_idx32, csr=self.csr, topology=self, target=target)
+
+    def to_vertices(self, values_bxtxc, weights=None, fill=0.0):
+        """hip_ops.tet_to_vertex on this tet list: per-tet values [B,T,C] as the (weighted) mean over each vertex's incident
+        tets, [B,V,C]; differentiable in the values, the weights a constant."""
+        return hip_ops.tet_to_vertex(values_bxtxc, self, self.n_vertex, weights=weights, fill=fill)
+
     def vertex_adjacency(self, normalize=True):
         """hip_ops.VertexAdjacency of this tet list (D⁻¹A with `normalize`, else A), for DefTet.laplacian_sparse; built on the
         first call per `normalize` and kept."""
@@ -246,6 +261,24 @@ class DefTet(nn.Module):
         """[B,Q,C]: field [B,V,C] interpolated at the query points with their barycentric weights in the mesh (vertice_pos,
         tetrahedron_bxfx4), 0 where no tet holds the point; the gradient reaches field, vertice_pos and the points."""
         return _topology_for(tetrahedron_bxfx4, vertice_pos.shape[1]).field_sample(field, vertice_pos, point_pos_bxpx3)
+
+    # --- the geometry-aware regularisers of a per-vertex field: volume-weighted Dirichlet energy and Eikonal term
+    def field_regularizers(self, vertice_pos, tetrahedron_bxfx4, field, target=1.0):
+        """[B,C,2] = (sum w |grad f_c|^2 / W, sum w (|grad f_c| - target)^2 / W) over the live tets, w their volumes, of the
+        per-vertex field [B,V,C] (1 <= C <= 8); the gradient reaches field and vertice_pos (hip_ops.tet_field_energies)."""
+        return _topology_for(tetrahedron_bxfx4, vertice_pos.shape[1]).field_energies(field, vertice_pos, target=target)
+
+    # --- the welded iso-surface of a per-TET occupancy: to the vertices, then marching tetrahedra
+    def iso_surface(self, vertice_pos, tetrahedron_bxfx4, pred_tet_occ, iso=0.5, volume_weighted=True):
+        """hip_ops.IsoMesh (lists of B tensors) of the per-tet occupancy pred_tet_occ [B,T] / [B,T,1]: every vertex takes the mean
+        of its incident tets' values (weighted by their volumes with volume_weighted, as constants) and hip_ops.marching_tets
+        takes the level `iso` of that per-vertex field on the tet list's edges.  Differentiable in pred_tet_occ and vertice_pos.
+        The shapes share one tet list."""
+        topo = _topology_for(tetrahedron_bxfx4, vertice_pos.shape[1])
+        occ = pred_tet_occ.reshape(pred_tet_occ.shape[0], -1, 1)
+        weights = hip_ops.tet_volumes(vertice_pos, topo.tet_idx32) if volume_weighted else None
+        field = topo.to_vertices(occ, weights=weights)
+        return hip_ops.marching_tets(vertice_pos, field.squeeze(-1), topo.edges(), iso=iso)
 
     # --- A11 (each call evaluates the fused kernel and returns its own component)
     def volume_variance(self, tet_bxfx4x3, base_area_mask=None, area_normalize=(20, 20), pow=2, center_occ=None):

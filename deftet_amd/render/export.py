@@ -53,15 +53,21 @@ def soup_color_obj_text(tet_fx3x3, tetcolor_fx3x3):
     return _format_rows("v %f %f %f %f %f %f\n" * 3 + "f %d %d %d\n", _soup_table(np.concatenate([tri, col], axis=2), 6))
 
 
-def mesh_obj_text(verts_vx3, faces_fx3, colors_vx3=None):
+def mesh_obj_text(verts_vx3, faces_fx3, colors_vx3=None, normals_vx3=None):
     """Indexed mesh: one 'v' line per vertex (with colours: six numbers) and 'f a+1 c+1 b+1' per face — the soup writers' 1,3,2
-    order, which turns the extraction's inward triangles outward."""
+    order, which turns the extraction's inward triangles outward.  With normals_vx3: one 'vn' line per vertex after the 'v'
+    lines and faces as 'f a//a c//c b//b'."""
     v = _np(verts_vx3).reshape(-1, 3).astype(np.float64)
     f = _np(faces_fx3).reshape(-1, 3).astype(np.float64) + 1
     if colors_vx3 is None:
         head = _format_rows("v %f %f %f\n", v)
     else:
         head = _format_rows("v %f %f %f %f %f %f\n", np.concatenate([v, _np(colors_vx3).reshape(-1, 3).astype(np.float64)], axis=1))
+    if normals_vx3 is not None:
+        vn = _np(normals_vx3).reshape(-1, 3).astype(np.float64)
+        if vn.shape[0] != v.shape[0]:
+            raise ValueError("%d vertices, %d normals" % (v.shape[0], vn.shape[0]))
+        return head + _format_rows("vn %f %f %f\n", vn) + _format_rows("f %d//%d %d//%d %d//%d\n", f[:, [0, 0, 2, 2, 1, 1]])
     return head + _format_rows("f %d %d %d\n", f[:, [0, 2, 1]])
 
 
@@ -71,7 +77,7 @@ def _write(path, text):
 
 
 def save_surface_objs(points_px3, feat, tet_tx4, nbr, savedir, prefix, thresholds=(0.005, 0.05, 0.15, 0.25), welded=False,
-                      iso=None, keep_largest=False, min_component=0, fill_voids=False):
+                      iso=None, keep_largest=False, min_component=0, fill_voids=False, normals=False):
     """Writes what Deftet.saveobj writes (3_model/deftet.py:533-557): for every threshold `tet-geo-<prefix>-thres-<t>.obj` and
     `tet-color-<prefix>-thres-<t>.obj`.  `feat` = (weights [P] / [P,1], colours [P,3]) as `processfunc` returns them, or one
     [P,4] tensor holding them side by side; the colours are written reversed (colorsnp_px3[:, ::-1], :513).  The per-tet
@@ -87,7 +93,9 @@ def save_surface_objs(points_px3, feat, tet_tx4, nbr, savedir, prefix, threshold
     the per-tet occupancy is then a torch maximum over the corner weights (the fused maximum, bit for bit, on finite weights),
     inside = occ > float32(2 thres) — the threshold mode's own inside test — a dropped tet gets 0, a filled one 1, and the result
     goes to surface_extract as `occ`.  With all three left at their defaults nothing of this runs.  The `mt-` files are not
-    cleaned: a per-vertex field has no per-tet mask."""
+    cleaned: a per-vertex field has no per-tet mask.  normals=True (with iso): the `mt-geo` file also carries one `vn` line per
+    vertex — the unit outward normal, minus the normalised gradient of the weights (hip_ops.vertex_field_gradient) interpolated
+    along the crossing edge, zero where that gradient is zero — and its faces read `f a//a b//b c//c`."""
     if isinstance(feat, (tuple, list)):
         weights, colours = feat
     else:
@@ -124,10 +132,16 @@ def save_surface_objs(points_px3, feat, tet_tx4, nbr, savedir, prefix, threshold
             paths.append("%s/tet-mesh-%s-thres-%.3f.obj" % (savedir, prefix, thres))
             _write(paths[-1], mesh_obj_text(v, f, c))
     if iso is not None:
-        mesh = hip_ops.marching_tets(pts, w, hip_ops.TetEdges(tet, pts.shape[0]), iso=iso, attr=col)
+        attr, vn = col, None
+        if normals:                                                   # the gradient rides along with the colours: one extraction
+            grad = hip_ops.vertex_field_gradient(w.reshape(1, -1, 1), pts[None], tet)
+            attr = torch.cat([col, grad.reshape(-1, 3)], dim=1)
+        mesh = hip_ops.marching_tets(pts, w, hip_ops.TetEdges(tet, pts.shape[0]), iso=iso, attr=attr)
         v, f, c = mesh.verts[0].detach(), mesh.faces[0][:, [0, 2, 1]], mesh.vert_attr[0].detach()     # (the writer swaps them back)
+        if normals:
+            c, vn = c[:, :3], hip_ops.unit_normals(c[:, 3:6])
         paths.append("%s/mt-geo-%s-iso-%.3f.obj" % (savedir, prefix, iso))
-        _write(paths[-1], mesh_obj_text(v, f))
+        _write(paths[-1], mesh_obj_text(v, f, normals_vx3=vn))
         paths.append("%s/mt-color-%s-iso-%.3f.obj" % (savedir, prefix, iso))
         _write(paths[-1], mesh_obj_text(v, f, c))
     return paths

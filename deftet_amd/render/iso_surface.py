@@ -25,3 +25,31 @@ def marching_tets(model, iso, processfunc, return_index=False):
     topology = model_tet_edges(model, points.shape[0], points.device)
     mesh = hip_ops.marching_tets(points, weights.reshape(1, -1), topology, iso=iso, attr=colours, return_index=return_index)
     return hip_ops.IsoMesh(*[None if x is None else x[0] for x in mesh])
+
+
+def model_tet_csr(model, n_vertex, device):
+    """(int32 tet list [1,T,4], its incidence CSR) of model.tftet_tx4, kept on the model and keyed by the tet-list object like
+    model_tet_edges."""
+    import torch
+    tets = model.tftet_tx4
+    kept = getattr(model, "_deftet_tet_csr", None)
+    if kept is None or kept[0] is not tets or kept[1] != n_vertex or kept[2].device != device:
+        idx = torch.as_tensor(tets).to(device).to(torch.int32).reshape(1, -1, 4).contiguous()
+        kept = (tets, n_vertex, idx, hip_ops.tet_vertex_csr(idx, n_vertex))
+        model._deftet_tet_csr = kept
+    return kept[2], kept[3]
+
+
+def marching_tets_normals(model, iso, processfunc):
+    """marching_tets(model, iso, processfunc) with vert_attr [Nv,3] holding the unit OUTWARD normal instead of the colours: the
+    per-vertex gradient of the weights (hip_ops.vertex_field_gradient, the volume-weighted mean of the tets' gradients)
+    interpolated along each crossing edge, normalised and negated — inside is weights > iso, so the field falls towards the
+    outside.  A zero gradient gives a zero normal.  Differentiable like marching_tets."""
+    points = model.get_point(True)
+    weights, _colours = processfunc(points, model.get_feat())
+    P, dev = points.shape[0], points.device
+    idx, csr = model_tet_csr(model, P, dev)
+    grad = hip_ops.vertex_field_gradient(weights.reshape(1, P, 1), points.reshape(1, P, 3), idx, csr=csr)
+    mesh = hip_ops.marching_tets(points, weights.reshape(1, -1), model_tet_edges(model, P, dev), iso=iso, attr=grad.reshape(1, P, 3))
+    mesh = mesh._replace(vert_attr=[hip_ops.unit_normals(a) for a in mesh.vert_attr])
+    return hip_ops.IsoMesh(*[None if x is None else x[0] for x in mesh])

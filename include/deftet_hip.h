@@ -42,6 +42,8 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
+/* 390: field gradients on the tets — deftet_tet_field_gradient_fwd_f32 / _bwd_f32, deftet_tet_field_energies_fwd_f32 / _bwd_f32 with
+ *      deftet_tet_field_energies_workspace_bytes, deftet_tet_to_vertex_fwd_f32 / _bwd_f32 (tet_field_grad.hip). */
 /* 380: conforming selective tet refinement (red-green closure on edge marks) — deftet_tet_refine_mark_i64, deftet_tet_refine_count_i64,
  *      deftet_tet_refine_fill_f32 and deftet_tet_refine_workspace_bytes (tet_refine.hip).
  * 370: generalised winding numbers for inside tests on open meshes — deftet_winding_number_f32, its workspace size,
@@ -1161,6 +1163,48 @@ int deftet_voxel_surface_fill_b32(const uint32_t *bits, int n_batch, int resolut
 size_t deftet_face_edges_workspace_bytes(int n_face);
 int deftet_face_edges_i32(const int64_t *faces, int n_face, int n_vertex, int32_t *pairs, int32_t *n_out, void *workspace,
                           size_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * Field gradients on the tets (390; tet_field_grad.hip).  field f32 [B,V,C], pos f32 [B,V,3], tet_idx int32
+ * [idx_batch,T,4] (16-byte aligned; idx_batch 1 = one list for every shape, or n_batch), offsets / slots = the incidence CSR of
+ * deftet_tet_vertex_csr_i32 for that list.  For a tet with vertices v0..v3 at x0..x3 and e0 = x1 - x0, e1 = x2 - x0, e2 = x3 - x0:
+ * n0 = e1 x e2, n1 = e2 x e0, n2 = e0 x e1, det = e0 . n0, vol = det / 6, g_c = (n0 df0 + n1 df1 + n2 df2) / det with
+ * df_k = f(v_{k+1},c) - f(v0,c).  A tet is live iff det > 0 in fp32 and its indices lie in [0,V); a dead tet has gradient 0 and
+ * volume 0 and takes part in no energy and no backward.  No float atomics: every sum has one order (the file's header), so two
+ * runs give the same bits.
+ * deftet_tet_field_gradient_fwd_f32: out f32 [B,T,C,3] = g, vol f32 [B,T] (optional).  One launch.  out NULL (field then unused):
+ *   the volumes alone.
+ * deftet_tet_field_gradient_bwd_f32: grad_out f32 [B,T,C,3] and grad_vol f32 [B,T] (optional) taken to grad_field f32 [B,V,C] and
+ *   grad_pos f32 [B,V,3] (each optional, every element written), per vertex one accumulator over its incidences in ascending
+ *   4 t + corner.  One launch each; nothing of size O(T) is stored in between.
+ * deftet_tet_field_energies_fwd_f32: 1 <= n_channel <= 8 (DEFTET_EINVAL otherwise).  With w_t = vol_t of the live tets and
+ *   W = sum w_t: out f32 [B,C,2] = (sum w_t |g_c|^2 / W, sum w_t (|g_c| - target)^2 / W), both 0 when W = 0; the sums in fp64 in
+ *   one order.  stats f64 [B,17] = (W, out[:,0] padded to 8, out[:,1] padded to 8) in fp64 is kept by the caller for the backward.
+ *   Two launches, g never stored.
+ * deftet_tet_field_energies_bwd_f32: grad_out f32 [B,C,2] taken to grad_field and grad_pos (each optional) by the same walk
+ *   of the incidence CSR; where |g_c| = 0 the derivative of the second term is taken as 0; all 0 when W = 0.
+ * deftet_tet_to_vertex_fwd_f32: values f32 [B,T,C], weights f32 [B,T] (NULL = 1): out f32 [B,V,C] = num / den with
+ *   num = sum of fl(w_t values[t,c]) and den = sum of w_t over the vertex's incidences in CSR order, one fp32 accumulator each
+ *   from 0, every step rounded; `fill` where den is not > 0.  weight_sum f32 [B,V] (required) receives den.
+ * deftet_tet_to_vertex_bwd_f32: grad_values f32 [B,T,C] = w_t * (sum over the corners k = 0..3 of grad_out[v_k,c] /
+ *   weight_sum[v_k], one accumulator from 0, a corner whose weight_sum is not > 0 left out).  No gradient on the weights. */
+int deftet_tet_field_gradient_fwd_f32(const float *field, const float *pos, const int32_t *tet_idx, float *out, float *vol, int n_batch,
+                                      int n_vertex, int n_tet, int idx_batch, int n_channel, void *stream);
+int deftet_tet_field_gradient_bwd_f32(const float *grad_out, const float *grad_vol, const float *field, const float *pos,
+                                      const int32_t *tet_idx, const int32_t *offsets, const int32_t *slots, float *grad_field,
+                                      float *grad_pos, int n_batch, int n_vertex, int n_tet, int idx_batch, int n_channel, void *stream);
+size_t deftet_tet_field_energies_workspace_bytes(int n_batch);
+int deftet_tet_field_energies_fwd_f32(const float *field, const float *pos, const int32_t *tet_idx, float *out, double *stats, float target,
+                                      int n_batch, int n_vertex, int n_tet, int idx_batch, int n_channel, void *workspace,
+                                      size_t workspace_bytes, void *stream);
+int deftet_tet_field_energies_bwd_f32(const double *stats, const float *grad_out, float target, const float *field, const float *pos,
+                                      const int32_t *tet_idx, const int32_t *offsets, const int32_t *slots, float *grad_field,
+                                      float *grad_pos, int n_batch, int n_vertex, int n_tet, int idx_batch, int n_channel, void *stream);
+int deftet_tet_to_vertex_fwd_f32(const float *values, const float *weights, const int32_t *offsets, const int32_t *slots, float *out,
+                                 float *weight_sum, float fill, int n_batch, int n_vertex, int n_tet, int idx_batch, int n_channel,
+                                 void *stream);
+int deftet_tet_to_vertex_bwd_f32(const float *grad_out, const float *weight_sum, const float *weights, const int32_t *tet_idx,
+                                 float *grad_values, int n_batch, int n_vertex, int n_tet, int idx_batch, int n_channel, void *stream);
 
 #ifdef __cplusplus
 }
