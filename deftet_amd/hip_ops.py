@@ -40,6 +40,22 @@ def _f32c(t):
     return t.contiguous().float()
 
 
+def _bad_flag(check, dev):
+    """the int32 [1] flag an entry sets on a bad index; None without check"""
+    return torch.zeros(1, device=dev, dtype=torch.int32) if check else None
+
+
+def _raise_if(bad, error, message):
+    """the one read-back of a _bad_flag (a host sync; none for None): raises error(message) when the flag is set"""
+    if bad is not None and int(bad.item()):
+        raise error(message)
+
+
+def _expected(caller, what, got):
+    """the one form of an argument error: got = the offending tensor (its shape is named), or a dtype / device / text"""
+    return RuntimeError("%s: %s expected (got %s)" % (caller, what, tuple(got.shape) if isinstance(got, torch.Tensor) else got))
+
+
 class _LRU(collections.OrderedDict):
     """At most `maxsize` entries, the least recently used dropped first (like _TOPOLOGIES in layers/DefTet/deftet.py); every
     access holds `lock`.  An entry that leaves is retire()d: the GPU may still be writing into pinned host memory it owns, and
@@ -502,22 +518,106 @@ def _idx32(tet_idx):
     return idx.contiguous()
 
 
-def _indexed_inputs(pos_bxvx3, tet_idx, pts_bxqx3, topology):
-    _lib.require_gpu(pos_bxvx3, tet_idx, pts_bxqx3)
-    pos, pts = _f32c(pos_bxvx3), _f32c(pts_bxqx3)
-    idx = getattr(topology, "tet_idx32", None)
-    if idx is None or (tet_idx is not getattr(topology, "tet_idx", None) and tet_idx is not idx):
-        idx = tet_idx
+# The tet-mesh argument contract of the vertex-indexed operators ("A tet mesh as an argument"), stated once:
+# _topology_parts reads a topology, _mesh_args checks the mesh, _check_csr decides whether a CSR fits, _resolve_csr finds the CSR
+# of a call, _csr_or_build is the slow path, _out_or_new the `out=` of the gradients that land on the vertices.
+def _topology_parts(topology):
+    """(tet_idx, tet_idx32, csr) of a TetTopology (layers/DefTet/deftet.py) or anything shaped like one, None for what it does not
+    have; the only place that reads one"""
+    return getattr(topology, "tet_idx", None), getattr(topology, "tet_idx32", None), getattr(topology, "csr", None)
+
+
+def _f32_on(caller, name, t, dev, convert):
+    """t as a contiguous f32 tensor once it is seen to be a tensor on dev (None: it names the device), float32 unless `convert`"""
+    if not isinstance(t, torch.Tensor) or (t.dtype != torch.float32 and not convert) or (dev is not None and t.device != dev):
+        raise _expected(caller, "%s as a float32 tensor%s" % (name, "" if dev is None else " on %s" % dev),
+                        "%s on %s" % (t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t).__name__)
+    return _f32c(t) if convert else t.contiguous()
+
+
+def _mesh_args(caller, pos, tet_idx, topology=None, field=None, pts=None, convert=False):
+    """(pos, idx, field, pts) of a tet mesh argument: contiguous f32 pos [B,V,3] and int32 idx [Bi,T,4] with Bi in (1, B) — the
+    topology's own tet_idx32 when tet_idx is its tet_idx or tet_idx32, else a conversion of tet_idx (int32 / int64 [T,4] or
+    [Bi,T,4]) — and, where given, contiguous f32 field [B,V,C >= 1] and pts [B,Q,3]; all checked against each other for rank, last
+    dimension, B, V, dtype and device.  pos=None with a field: the field alone names B and V.  convert: the contract of the
+    entries that came first, floats of any dtype taken to f32 and tet_idx of any dtype _idx32 converts."""
+    if not isinstance(tet_idx, torch.Tensor):
+        raise _expected(caller, "tet_idx as a tensor", type(tet_idx).__name__)
+    _lib.require_gpu(pos, tet_idx, field, pts)
+    dev = None
+    if pos is not None:
+        pos = _f32_on(caller, "pos", pos, dev, convert)
+        if pos.dim() != 3 or pos.shape[2] != 3:
+            raise _expected(caller, "pos [B,V,3]", pos)
+        dev = pos.device
+    if field is not None:
+        field = _f32_on(caller, "field", field, dev, convert)
+        if field.dim() != 3 or field.shape[2] < 1 or (pos is not None and field.shape[:2] != pos.shape[:2]):
+            raise _expected(caller, "field [B,V,C] with a channel dimension of at least 1 and the B, V of pos", field)
+    anchor = field if pos is None else pos                            # names B, V and the device
+    if anchor is None:
+        raise _expected(caller, "pos or field", None)
+    B, dev = anchor.shape[0], anchor.device
+    if pts is not None:
+        pts = _f32_on(caller, "pts", pts, dev, convert)
+        if pts.dim() != 3 or pts.shape[2] != 3 or pts.shape[0] != B:
+            raise _expected(caller, "pts [%d,Q,3]" % B, pts)
+    if not convert and tet_idx.dtype != torch.int32 and tet_idx.dtype != torch.int64:
+        raise _expected(caller, "tet_idx int32 or int64", tet_idx.dtype)
+    idx = tet_idx
+    if topology is not None:
+        own, own32, _ = _topology_parts(topology)
+        if own32 is not None and (tet_idx is own or tet_idx is own32):
+            idx = own32
     idx = _idx32(idx)
-    if pos.dim() != 3 or pos.shape[2] != 3:
-        raise RuntimeError("pos must be [B,V,3], got %s" % (tuple(pos.shape),))
-    if idx.dim() != 3 or idx.shape[2] != 4 or idx.shape[0] not in (1, pos.shape[0]):
-        raise RuntimeError("tet_idx must be [T,4] or [B,T,4] with B matching pos, got %s" % (tuple(idx.shape),))
-    if pts.dim() != 3 or pts.shape[2] != 3 or pts.shape[0] != pos.shape[0]:
-        raise RuntimeError("point_pos_bxnx3 must be [B,Q,3] with the same B, got %s" % (tuple(pts.shape),))
-    if idx.device != pos.device or pts.device != pos.device:
-        raise RuntimeError("pos, tet_idx and pts must be on one device")
-    return pos, idx, pts
+    if idx.dim() != 3 or idx.shape[2] != 4 or idx.shape[0] not in (1, B) or idx.device != dev:
+        raise _expected(caller, "tet_idx [T,4] or [%d,T,4] on %s" % (B, dev), "%s on %s" % (tuple(tet_idx.shape), idx.device))
+    return pos, idx, field, pts
+
+
+def _check_csr(caller, csr, B, V, T, idx_batch=None, dev=None):
+    """Whether csr fits a mesh of B shapes, V vertices and T tets, decided here alone: a sequence (offsets, slots, Bc) as
+    tet_vertex_csr returns it, Bc in (1, B) and equal to idx_batch (the index lists of the mesh) where the entry reads the lists
+    beside the CSR, slots of Bc * 4 T and offsets of Bc * V + 1 elements, both int32 tensors on dev (the operands' device).  The
+    C entries dereference what they are handed, so nothing that fails here reaches one."""
+    try:
+        offsets, slots, Bc = csr
+        ok = (slots.numel() == Bc * 4 * T and offsets.numel() == Bc * V + 1 and (Bc == 1 or Bc == B)
+              and (idx_batch is None or Bc == idx_batch) and offsets.dtype == torch.int32 and slots.dtype == torch.int32
+              and (dev is None or (offsets.device == dev and slots.device == dev)))
+    except (TypeError, ValueError, AttributeError):                   # not a sequence of three, or not tensors
+        ok = False
+    if not ok:
+        seen = [("%s %s on %s" % (t.dtype, tuple(t.shape), t.device)) if isinstance(t, torch.Tensor) else repr(t)
+                for t in (csr if isinstance(csr, (tuple, list)) else [csr])]
+        raise RuntimeError("%s: the CSR does not match the tet list: it is not tet_vertex_csr(tet_idx, %d) of %s list(s) of %d tets, int32%s "
+                           "(got %s)" % (caller, V, "1 or %d" % B if idx_batch is None else idx_batch, T,
+                                         "" if dev is None else " on %s" % dev, ", ".join(seen)))
+
+
+def _resolve_csr(caller, csr, topology, pos, idx):
+    """the CSR of a call that takes `csr=` / `topology=`: the given one, else the topology's, checked against the mesh (pos or a
+    field [B,V,.], idx); None when there is neither (the slow path, _csr_or_build)"""
+    if csr is None and topology is not None:
+        csr = _topology_parts(topology)[2]
+    if csr is not None:
+        _check_csr(caller, csr, pos.shape[0], pos.shape[1], idx.shape[1], idx.shape[0], pos.device)
+    return csr
+
+
+def _csr_or_build(csr, idx, V):
+    """csr, or THE SLOW PATH when there is none: tet_vertex_csr(idx, V) built on the spot — a sort of 4 T incidences and a host
+    sync, in every backward of an operator that was handed neither `csr=` nor a `topology=`"""
+    return csr if csr is not None else tet_vertex_csr(idx, V)
+
+
+def _out_or_new(caller, out, shape, dev):
+    """the result of a gradient on the vertices: `out` must be contiguous f32 [B,V,C] (`shape`) on dev; None: a fresh one"""
+    if out is None:
+        return torch.empty(*shape, device=dev, dtype=torch.float32)     # (unpacked: a shape tuple costs torch 0.8 us more)
+    if tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise _expected(caller, "out contiguous f32 %s on %s" % (tuple(shape), dev), "%s %s on %s" % (out.dtype, tuple(out.shape), out.device))
+    return out
 
 
 def point_in_tet_indexed(pos_bxvx3, tet_idx, pts_bxqx3, want_bary=False, algo=PIT_AUTO, pred_bxt=None, want_hits=False, prepared=None,
@@ -527,13 +627,13 @@ def point_in_tet_indexed(pos_bxvx3, tet_idx, pts_bxqx3, want_bary=False, algo=PI
     copy is used when `topology` is one).  Returns exactly what point_in_tet(tet_gather(pos, tet_idx), pts, ...) returns, bit
     for bit, including the hit records (either backward takes them).  An index outside [0, V) reads as a NaN corner, as in
     tet_gather; check=True synchronises and raises on one.  order="auto" without a topology keys the decision by tet_idx."""
-    pos, idx, pts = _indexed_inputs(pos_bxvx3, tet_idx, pts_bxqx3, topology)
+    pos, idx, _, pts = _mesh_args("point_in_tet_indexed", pos_bxvx3, tet_idx, topology, pts=pts_bxqx3, convert=True)
     _lib.require_gpu(pred_bxt)
     lib = _lib.load()
     B, V, T, Q, Bi = pos.shape[0], pos.shape[1], idx.shape[1], pts.shape[1], idx.shape[0]
     dev = pts.device
     key = topology if topology is not None else tet_idx
-    bad = torch.zeros(1, device=dev, dtype=torch.int32) if check else None
+    bad = _bad_flag(check, dev)
     with _lib.on_device(dev):
         cond, bary, pred, occ, hits, order, ws, box = _pit_begin("point_in_tet_indexed", lib, pts, T, want_bary, algo, pred_bxt, want_hits,
                                                                  prepared, order, query_box, query_box_misses,
@@ -544,8 +644,7 @@ def point_in_tet_indexed(pos_bxvx3, tet_idx, pts_bxqx3, want_bary=False, algo=PI
         else:
             _lib.call("deftet_point_in_tet_indexed_f32", dev, pos, idx, Bi, pts, cond, bary, pred, occ, hits, B, V, T, Q, algo, order,
                       *box, bad, ws=ws)
-    if check and int(bad.item()):
-        raise RuntimeError("point_in_tet_indexed: index out of range [0, %d)" % V)
+    _raise_if(bad, RuntimeError, "point_in_tet_indexed: index out of range [0, %d)" % V)
     return _pit_result(cond, bary, occ, hits, want_hits)
 
 
@@ -599,15 +698,10 @@ def point_in_tet_bwd(tet_bxtx4x3, pts_bxqx3, cond, grad_w, want_grad_pts=False, 
 def _to_vertices_begin(caller, csr, Bi, B, V, T, pts, want_grad_pts, grad_occ, out):
     """The checks, outputs and workspace size of the two *_bwd_to_vertices, on the queries' device (Bi: the index lists the tets
     come from, None = the CSR's).  Returns (offsets, slots, Bi, grad_pos, grad_pts, grad_occ as f32, grad_pred, workspace bytes)."""
-    offsets, slots, Bc = csr
-    if Bi is not None and Bc != Bi:
-        raise RuntimeError("%s: the CSR was built over %d index list(s), tet_idx has %d" % (caller, Bc, Bi))
-    if slots.numel() != Bc * T * 4 or offsets.numel() != Bc * V + 1:
-        raise RuntimeError("%s: CSR does not match the tets / n_vertex" % caller)
-    if out is not None and (out.shape != (B, V, 3) or out.dtype != torch.float32 or not out.is_contiguous()):
-        raise RuntimeError("%s: out must be contiguous f32 [B,V,3]" % caller)
     dev = pts.device
-    grad_pos = out if out is not None else torch.empty(B, V, 3, device=dev, dtype=torch.float32)
+    _check_csr(caller, csr, B, V, T, Bi, dev)
+    offsets, slots, Bc = csr
+    grad_pos = _out_or_new(caller, out, (B, V, 3), dev)
     grad_pts = torch.empty_like(pts) if want_grad_pts else None
     go = _f32c(grad_occ) if grad_occ is not None else None
     # (`accumulate` of the C entry covers grad_pos AND grad_pred: a fresh grad_pred must then start from zero)
@@ -635,7 +729,7 @@ def point_in_tet_indexed_bwd_to_vertices(pos, tet_idx, pts, cond, grad_w, csr, w
     """point_in_tet_bwd_to_vertices for the indexed forward: the tets are read from (pos, tet_idx) instead of a gathered tensor.
     csr = tet_vertex_csr(tet_idx, V) of the same list (same idx_batch).  Returns and `out=` as point_in_tet_bwd_to_vertices, bit
     for bit the same values on the same inputs; hits from either forward."""
-    pos, idx, pts = _indexed_inputs(pos, tet_idx, pts, None)
+    pos, idx, _, pts = _mesh_args("point_in_tet_indexed_bwd_to_vertices", pos, tet_idx, pts=pts, convert=True)
     _lib.require_gpu(cond, grad_w, grad_occ)
     cond, gw = _f32c(cond), _f32c(grad_w)
     B, V, T, Q, Bi = pos.shape[0], pos.shape[1], idx.shape[1], pts.shape[1], idx.shape[0]
@@ -1369,27 +1463,36 @@ def tet_gather(pos_bxvx3, tet_idx, check=False):
     if idx.shape[0] not in (1, B) or idx.shape[2] != 4 or pos.shape[2] != 3:
         raise RuntimeError("tet_gather: pos [B,V,3] and tet_idx [T,4] or [B,T,4] expected")
     out = torch.empty(B, T, 4, 3, device=pos.device, dtype=torch.float32)
-    bad = torch.zeros(1, device=pos.device, dtype=torch.int32) if check else None
+    bad = _bad_flag(check, pos.device)
     _lib.call("deftet_tet_gather_fwd_f32", pos.device, pos, idx, out, bad, B, V, T, idx.shape[0])
-    if check and int(bad.item()):
-        raise RuntimeError("tet_gather: index out of range [0, %d)" % V)
+    _raise_if(bad, RuntimeError, "tet_gather: index out of range [0, %d)" % V)
     return out
+
+
+def _incidence_csr(entry, bytes_entry, idx, sizes, error, message):
+    """(offsets int32 [Bi*V+1], slots int32 [Bi*corners*E]) of the elements idx (tets, edges, faces) around their vertices, slot =
+    corners * e + corner in ascending order per vertex: the one builder behind tet_vertex_csr, TetEdges and FaceTopology (their
+    entries are all vtx::incidence_csr).  sizes = (Bi | None, V, E, corners), Bi = None for an entry that takes a single list.
+    One read-back (a host sync); raises error(message % V) on an index outside [0, V)."""
+    Bi, V, E, corners = sizes
+    dims, lists = ((V, E), 1) if Bi is None else ((Bi, V, E), Bi)
+    dev = idx.device
+    offsets = torch.empty(lists * V + 1, device=dev, dtype=torch.int32)
+    slots = torch.empty(lists * E * corners, device=dev, dtype=torch.int32)
+    bad = _bad_flag(True, dev)
+    _lib.call(entry, dev, idx, offsets, slots, bad, *dims, ws=getattr(_lib.load(), bytes_entry)(*dims))
+    _raise_if(bad, error, message % V)
+    return offsets, slots
 
 
 def tet_vertex_csr(tet_idx, n_vertex):
     """(offsets int32 [Bi*V+1], slots int32 [Bi*4T], Bi): incidences (4*t+corner, ascending) per
     vertex — built once per topology for tet_gather_bwd.  Raises on an out-of-range index."""
     _lib.require_gpu(tet_idx)
-    lib = _lib.load()
     idx = _idx64(tet_idx)
     Bi, T, V = idx.shape[0], idx.shape[1], int(n_vertex)
-    dev = idx.device
-    offsets = torch.empty(Bi * V + 1, device=dev, dtype=torch.int32)
-    slots = torch.empty(Bi * T * 4, device=dev, dtype=torch.int32)
-    bad = torch.zeros(1, device=dev, dtype=torch.int32)
-    _lib.call("deftet_tet_vertex_csr_i32", dev, idx, offsets, slots, bad, Bi, V, T, ws=lib.deftet_tet_vertex_csr_workspace_bytes(Bi, V, T))
-    if int(bad.item()):
-        raise RuntimeError("tet_vertex_csr: index out of range [0, %d)" % V)
+    offsets, slots = _incidence_csr("deftet_tet_vertex_csr_i32", "deftet_tet_vertex_csr_workspace_bytes", idx, (Bi, V, T, 4),
+                                    RuntimeError, "tet_vertex_csr: index out of range [0, %d)")
     return offsets, slots, Bi
 
 
@@ -1398,14 +1501,11 @@ def tet_gather_bwd(grad_tet_bxtx4x3, csr, n_vertex, out=None):
     (deterministic, no atomics).  out: existing [B,V,3] tensor to ADD to."""
     _lib.require_gpu(grad_tet_bxtx4x3)
     g = _f32c(grad_tet_bxtx4x3)
-    offsets, slots, Bi = csr
     B, T, V = g.shape[0], g.shape[1], int(n_vertex)
-    if slots.numel() != Bi * T * 4 or offsets.numel() != Bi * V + 1:
-        raise RuntimeError("tet_gather_bwd: CSR does not match grad_tet / n_vertex")
+    _check_csr("tet_gather_bwd", csr, B, V, T, dev=g.device)
+    offsets, slots, Bi = csr
     acc = out is not None
-    if acc and (out.shape != (B, V, 3) or out.dtype != torch.float32 or not out.is_contiguous()):
-        raise RuntimeError("tet_gather_bwd: out must be contiguous f32 [B,V,3]")
-    gp = out if acc else torch.empty(B, V, 3, device=g.device, dtype=torch.float32)
+    gp = _out_or_new("tet_gather_bwd", out, (B, V, 3), g.device)
     _lib.call("deftet_tet_gather_bwd_f32", g.device, g, offsets, slots, gp, B, V, T, Bi, 1 if acc else 0)
     return gp
 
@@ -2009,19 +2109,14 @@ class TetEdges:
         if device is not None:
             tets = tets.to(device)
         _lib.require_gpu(tets)
-        lib = _lib.load()
         tets = _i64_tets(tets)
         T, V, dev = int(tets.shape[0]), int(n_vertex), tets.device
         if T == 0 or V <= 0:
             raise ValueError("TetEdges: an empty tet list or no vertices")
         edges, tet_edge = tet_edges(tets, V)                          # (IndexError on an index outside [0, V))
         E = int(edges.shape[0])
-        offsets = torch.empty(V + 1, device=dev, dtype=torch.int32)
-        slots = torch.empty(2 * E, device=dev, dtype=torch.int32)
-        bad = torch.zeros(1, device=dev, dtype=torch.int32)
-        _lib.call("deftet_edge_vertex_csr_i32", dev, edges, offsets, slots, bad, V, E, ws=lib.deftet_edge_vertex_csr_workspace_bytes(V, E))
-        if int(bad.item()):
-            raise IndexError("TetEdges: vertex index outside [0, %d)" % V)
+        offsets, slots = _incidence_csr("deftet_edge_vertex_csr_i32", "deftet_edge_vertex_csr_workspace_bytes", edges, (None, V, E, 2),
+                                        IndexError, "TetEdges: vertex index outside [0, %d)")
         self.tets = tets.to(torch.int32).contiguous()
         self.edges, self.tet_edge = edges.to(torch.int32).contiguous(), tet_edge.to(torch.int32).contiguous()
         self.offsets, self.slots = offsets, slots
@@ -2137,15 +2232,10 @@ class FaceTopology:
         _lib.require_gpu(faces)
         if faces.dim() != 2 or faces.shape[1] != 3:
             raise RuntimeError("FaceTopology: faces [F,3] expected")
-        lib = _lib.load()
         faces = faces.to(dtype=torch.int64, copy=True).contiguous()   # ours: later in-place edits of the caller's list do not reach it
         F, V, dev = faces.shape[0], int(n_vertex), faces.device
-        offsets = torch.empty(V + 1, device=dev, dtype=torch.int32)
-        slots = torch.empty(3 * F, device=dev, dtype=torch.int32)
-        bad = torch.zeros(1, device=dev, dtype=torch.int32)
-        _lib.call("deftet_face_vertex_csr_i32", dev, faces, offsets, slots, bad, V, F, ws=lib.deftet_face_vertex_csr_workspace_bytes(V, F))
-        if int(bad.item()):
-            raise RuntimeError("FaceTopology: face index out of range [0, %d)" % V)
+        offsets, slots = _incidence_csr("deftet_face_vertex_csr_i32", "deftet_face_vertex_csr_workspace_bytes", faces, (None, V, F, 3),
+                                        RuntimeError, "FaceTopology: face index out of range [0, %d)")
         self.faces, self.n_vertex, self.n_face = faces, V, F
         self.offsets, self.slots, self.device = offsets, slots, dev
 
@@ -2549,15 +2639,11 @@ def tet_centroid_sample_bwd_vertices(gcent, csr, n_vertex, n_tet, select=None, f
     that tet in ascending slot, the sum of gcent f32 [B,K,3] in one fp32 accumulator from 0).  select int32 [K] or the range from
     `first`; out: an existing contiguous f32 [B,V,3] to ADD to.  Every element is written: no memset, no atomics."""
     lib = _lib.load()
+    B, K, V, T, dev = gcent.shape[0], gcent.shape[1], int(n_vertex), int(n_tet), gcent.device
+    _check_csr("tet_centroid_sample_bwd_vertices", csr, B, V, T, dev=dev)
     offsets, slots, Bi = csr
-    B, K, V, T = gcent.shape[0], gcent.shape[1], int(n_vertex), int(n_tet)
-    if slots.numel() != Bi * T * 4 or offsets.numel() != Bi * V + 1 or Bi not in (1, B):
-        raise RuntimeError("tet_centroid_sample: the CSR does not match the tet list / n_vertex")
     acc = out is not None
-    if acc and (out.shape != (B, V, 3) or out.dtype != torch.float32 or not out.is_contiguous()):
-        raise RuntimeError("tet_centroid_sample: out must be contiguous f32 [B,V,3]")
-    dev = gcent.device
-    gpos = out if acc else torch.empty(B, V, 3, device=dev, dtype=torch.float32)
+    gpos = _out_or_new("tet_centroid_sample_bwd_vertices", out, (B, V, 3), dev)
     _lib.call("deftet_tet_centroid_sample_bwd_vertices_f32", dev, gcent, offsets, slots, select, int(first), gpos, B, V, T, Bi, K,
               1 if acc else 0, ws=lib.deftet_tet_centroid_sample_workspace_bytes(B, T, K) if select is not None else None)
     return gpos
@@ -2572,11 +2658,10 @@ class _TetCentroidSample(torch.autograd.Function):
         C_total = C_feat + (3 if append_pos else 0)
         out = torch.empty(B, C_total, K, device=dev, dtype=torch.float32)
         centroids = torch.empty(B, K, 3, device=dev, dtype=torch.float32)
-        bad = torch.zeros(1, device=dev, dtype=torch.int32) if check else None
+        bad = _bad_flag(check, dev)
         _lib.call("deftet_tet_centroid_sample_fwd_f32", dev, *_tcs_volume_list(volumes), pos, tet_idx, select, first, out, centroids, bad,
                   B, V, T, tet_idx.shape[0], K, 1 if append_pos else 0)
-        if check and int(bad.item()):
-            raise RuntimeError("tet_centroid_sample: a chosen tet is outside [0, %d) or one of its vertices outside [0, %d)" % (T, V))
+        _raise_if(bad, RuntimeError, "tet_centroid_sample: a chosen tet is outside [0, %d) or one of its vertices outside [0, %d)" % (T, V))
         ctx.save_for_backward(centroids, *volumes)
         ctx.tet_idx, ctx.csr, ctx.select = tet_idx, csr, select
         ctx.args = (bool(append_pos), first, B, V, T, K, C_feat, C_total)
@@ -2593,10 +2678,7 @@ class _TetCentroidSample(torch.autograd.Function):
         gpos = None
         if ctx.needs_input_grad[0]:
             gcent = tet_centroid_sample_bwd_pos(volumes, centroids, gout, append_pos)
-            csr = ctx.csr
-            if csr is None:                                          # the slow path: a sort of 4 T incidences and a host sync per backward
-                csr = tet_vertex_csr(ctx.tet_idx, V)
-            gpos = tet_centroid_sample_bwd_vertices(gcent, csr, V, T, select=ctx.select, first=first)
+            gpos = tet_centroid_sample_bwd_vertices(gcent, _csr_or_build(ctx.csr, ctx.tet_idx, V), V, T, select=ctx.select, first=first)
         return (gpos, None, None, None, None, None, None, None) + tuple(grads)
 
 
@@ -2610,22 +2692,14 @@ def tet_centroid_sample(volumes, pos_bxvx3, tet_idx, csr=None, select=None, firs
     in fp32; the values are voxel_sample's at that point, bit for bit.
     Differentiable in pos and in every volume, with the same bits on every run and no atomics: the volumes through voxel_sample's
     sort by cell, pos through the incidence CSR — `csr` = tet_vertex_csr(tet_idx, V), built once per tet list (TetTopology keeps
-    it).  csr=None with pos requiring grad is the SLOW PATH: the CSR is rebuilt in every backward (a sort and a host sync).
+    it).  csr=None with pos requiring grad is the slow path: the CSR is rebuilt in every backward.
     check=True synchronises and raises on a tet index outside [0,T) or a vertex index outside [0,V); otherwise such a slot's
     values are NaN and it adds nothing to the gradient of pos.  return_centroids: also the centroids f32 [B,K,3] (no gradient)."""
     volumes = list(volumes)
-    _lib.require_gpu(pos_bxvx3, tet_idx, select, *volumes)
-    pos = _pv_need(pos_bxvx3, torch.float32, "tet_centroid_sample: pos")
-    if pos.dim() != 3 or pos.shape[2] != 3:
-        raise RuntimeError("tet_centroid_sample: pos [B,V,3] expected")
+    _lib.require_gpu(select, *volumes)
+    pos, idx, _, _ = _mesh_args("tet_centroid_sample", pos_bxvx3, tet_idx)
     if len(volumes) > _TCS_MAX_VOLUMES:
         raise RuntimeError("tet_centroid_sample: at most %d volumes (got %d)" % (_TCS_MAX_VOLUMES, len(volumes)))
-    B = pos.shape[0]
-    if tet_idx.dtype not in (torch.int32, torch.int64):
-        raise RuntimeError("tet_centroid_sample: tet_idx must be int32 or int64 (got %s)" % str(tet_idx.dtype).replace("torch.", ""))
-    idx = _idx32(tet_idx)
-    if idx.dim() != 3 or idx.shape[2] != 4 or idx.shape[0] not in (1, B) or idx.device != pos.device:
-        raise RuntimeError("tet_centroid_sample: tet_idx [T,4] or [B,T,4] on the device of pos expected (got %s)" % (tuple(tet_idx.shape),))
     T = idx.shape[1]
     vols = _check_volumes("tet_centroid_sample", volumes, pos)
     first = int(first)
@@ -2640,8 +2714,8 @@ def tet_centroid_sample(volumes, pos_bxvx3, tet_idx, csr=None, select=None, firs
         K = T - first if count is None else int(count)
         if first < 0 or K < 0 or first + K > T:
             raise RuntimeError("tet_centroid_sample: the range [%d, %d) does not lie in the %d tets" % (first, first + K, T))
-    if csr is not None and (len(csr) != 3 or csr[1].numel() != csr[2] * T * 4 or csr[0].numel() != csr[2] * pos.shape[1] + 1):
-        raise RuntimeError("tet_centroid_sample: csr is not tet_vertex_csr(tet_idx, %d) of this tet list" % pos.shape[1])
+    if csr is not None:                                              # (the backward reads the CSR alone: its idx_batch need not be the list's)
+        _check_csr("tet_centroid_sample", csr, pos.shape[0], pos.shape[1], T, dev=pos.device)
     out, centroids = _TetCentroidSample.apply(pos, idx, csr, select, first, K, bool(append_pos), bool(check), *vols)
     return (out, centroids) if return_centroids else out
 
@@ -2649,27 +2723,26 @@ def tet_centroid_sample(volumes, pos_bxvx3, tet_idx, csr=None, select=None, firs
 # ------------------------------------------------------------------------------------
 # a per-vertex field at query points (tet_field_sample.hip)
 # ------------------------------------------------------------------------------------
-def _tfs_sizes(caller, field, idx, cond):
-    """(B, V, C, T, Bi, Q) of contiguous f32 field [B,V,C], int32 idx [Bi,T,4] and cond [B,Q,1] or [B,Q], checked against each other"""
-    if field.dim() != 3 or field.shape[2] < 1:
-        raise RuntimeError("%s: field [B,V,C] with a channel dimension of at least 1 expected (got %s)" % (caller, tuple(field.shape)))
+def _tfs_args(caller, field, tet_idx, cond):
+    """(field, idx, cond, (B, V, C, T, Bi, Q)) of the raw entries: _mesh_args of the field and the list, and f32 cond [B,Q,1] or [B,Q]"""
+    _lib.require_gpu(cond)
+    _, idx, field, _ = _mesh_args(caller, None, tet_idx, field=_pv_need(field, torch.float32, caller + ": field"), convert=True)
+    cond = _f32c(cond)
     B, V, C = field.shape
-    if idx.dim() != 3 or idx.shape[2] != 4 or idx.shape[0] not in (1, B):
-        raise RuntimeError("%s: tet_idx [T,4] or [B,T,4] expected (got %s)" % (caller, tuple(idx.shape)))
     if cond.dim() not in (2, 3) or cond.shape[0] != B or cond.numel() != B * cond.shape[1]:
-        raise RuntimeError("%s: cond [B,Q,1] with the B of field expected (got %s)" % (caller, tuple(cond.shape)))
-    return B, V, C, idx.shape[1], idx.shape[0], cond.shape[1]
+        raise _expected(caller, "cond [%d,Q,1]" % B, cond)
+    return field, idx, cond, (B, V, C, idx.shape[1], idx.shape[0], cond.shape[1])
 
 
 def tet_field_sample_fwd(field, tet_idx, cond, bary, fill=0.0, bad=None):
     """out f32 [B,Q,C] = ((w0 f(v0) + w1 f(v1)) + w2 f(v2)) + w3 f(v3) per channel, every step rounded, in the tet cond names
     (v_k its vertices in tet_idx, w = bary); `fill` where cond is -1, NaN where a vertex index lies outside [0,V) (bad: an int32
     [1] tensor set to 1 then).  One launch.  The raw forward of tet_field_sample."""
-    _lib.require_gpu(field, tet_idx, cond, bary, bad)
-    field, idx, cond, bary = _pv_need(field, torch.float32, "tet_field_sample: field"), _idx32(tet_idx), _f32c(cond), _f32c(bary)
-    B, V, C, T, Bi, Q = _tfs_sizes("tet_field_sample", field, idx, cond)
+    _lib.require_gpu(bary, bad)
+    field, idx, cond, (B, V, C, T, Bi, Q) = _tfs_args("tet_field_sample", field, tet_idx, cond)
+    bary = _f32c(bary)
     if bary.shape != (B, Q, 4):
-        raise RuntimeError("tet_field_sample: bary [B,Q,4] expected (got %s)" % (tuple(bary.shape),))
+        raise _expected("tet_field_sample", "bary [%d,%d,4]" % (B, Q), bary)
     dev = field.device
     out = torch.empty(B, Q, C, device=dev, dtype=torch.float32)
     _lib.call("deftet_tet_field_sample_fwd_f32", dev, field, idx, cond, bary, out, bad, float(fill), B, V, T, Bi, Q, C)
@@ -2679,11 +2752,11 @@ def tet_field_sample_fwd(field, tet_idx, cond, bary, fill=0.0, bad=None):
 def tet_field_sample_bwd_w(field, tet_idx, cond, gout):
     """grad_w f32 [B,Q,4]: the gradient of tet_field_sample's result on the barycentric weights, grad_w[b,q,k] = the sum over the
     channels in ascending order of gout[b,q,c] * f(v_k,c), one fp32 accumulator from 0; 0 on a miss.  One launch."""
-    _lib.require_gpu(field, tet_idx, cond, gout)
-    field, idx, cond, gout = _pv_need(field, torch.float32, "tet_field_sample: field"), _idx32(tet_idx), _f32c(cond), _f32c(gout)
-    B, V, C, T, Bi, Q = _tfs_sizes("tet_field_sample_bwd_w", field, idx, cond)
+    _lib.require_gpu(gout)
+    field, idx, cond, (B, V, C, T, Bi, Q) = _tfs_args("tet_field_sample_bwd_w", field, tet_idx, cond)
+    gout = _f32c(gout)
     if gout.shape != (B, Q, C):
-        raise RuntimeError("tet_field_sample_bwd_w: gout [B,Q,C] = %s expected (got %s)" % ((B, Q, C), tuple(gout.shape)))
+        raise _expected("tet_field_sample_bwd_w", "gout [%d,%d,%d]" % (B, Q, C), gout)
     dev = field.device
     gw = torch.empty(B, Q, 4, device=dev, dtype=torch.float32)
     _lib.call("deftet_tet_field_sample_bwd_w_f32", dev, field, idx, cond, gout, gw, B, V, T, Bi, Q, C)
@@ -2697,22 +2770,18 @@ def tet_field_sample_bwd_field(gout, cond, bary, csr, n_vertex, n_tet, out=None,
     _lib.require_gpu(gout, cond, bary, out)
     lib = _lib.load()
     gout, cond, bary = _f32c(gout), _f32c(cond), _f32c(bary)
-    offsets, slots, Bi = csr
     if gout.dim() != 3 or gout.shape[2] < 1:
-        raise RuntimeError("tet_field_sample_bwd_field: gout [B,Q,C] expected (got %s)" % (tuple(gout.shape),))
+        raise _expected("tet_field_sample_bwd_field", "gout [B,Q,C]", gout)
     B, Q, C = gout.shape
-    V, T = int(n_vertex), int(n_tet)
-    if slots.numel() != Bi * T * 4 or offsets.numel() != Bi * V + 1 or Bi not in (1, B):
-        raise RuntimeError("tet_field_sample_bwd_field: the CSR does not match the tet list / n_vertex")
+    V, T, dev = int(n_vertex), int(n_tet), gout.device
+    _check_csr("tet_field_sample_bwd_field", csr, B, V, T, dev=dev)
+    offsets, slots, Bi = csr
     if cond.numel() != B * Q or bary.shape != (B, Q, 4):
-        raise RuntimeError("tet_field_sample_bwd_field: cond [B,Q,1] and bary [B,Q,4] of gout %s expected" % (tuple(gout.shape),))
-    if out is not None and (out.shape != (B, V, C) or out.dtype != torch.float32 or not out.is_contiguous()):
-        raise RuntimeError("tet_field_sample_bwd_field: out must be contiguous f32 [B,V,C]")
+        raise _expected("tet_field_sample_bwd_field", "cond [%d,%d,1] and bary [%d,%d,4]" % (B, Q, B, Q), "%s and %s" % (tuple(cond.shape), tuple(bary.shape)))
     if accumulate and out is None:
         raise RuntimeError("tet_field_sample_bwd_field: accumulate needs out")
     acc = bool(accumulate)
-    dev = gout.device
-    gfield = out if out is not None else torch.empty(B, V, C, device=dev, dtype=torch.float32)
+    gfield = _out_or_new("tet_field_sample_bwd_field", out, (B, V, C), dev)
     _lib.call("deftet_tet_field_sample_bwd_field_f32", dev, gout, cond, bary, offsets, slots, gfield, B, V, T, Bi, Q, C, 1 if acc else 0,
               ws=lib.deftet_tet_field_sample_workspace_bytes(B, T, Q))
     return gfield
@@ -2725,10 +2794,9 @@ class _TetFieldSample(torch.autograd.Function):
         res = point_in_tet_indexed(pos, idx, pts, want_bary=True, want_hits=rec, order="auto", query_box="track", topology=topology,
                                    check=check)
         cond, bary, hits = res if rec else (res + (None,))
-        bad = torch.zeros(1, device=pos.device, dtype=torch.int32) if check else None
+        bad = _bad_flag(check, pos.device)
         out = tet_field_sample_fwd(field, idx, cond, bary, fill=fill, bad=bad)
-        if check and int(bad.item()):
-            raise RuntimeError("tet_field_sample: a vertex index outside [0, %d)" % pos.shape[1])
+        _raise_if(bad, RuntimeError, "tet_field_sample: a vertex index outside [0, %d)" % pos.shape[1])
         ctx.save_for_backward(field, pos, pts, cond, bary, hits)
         ctx.idx, ctx.csr = idx, csr
         ctx.mark_non_differentiable(cond, bary)
@@ -2739,9 +2807,7 @@ class _TetFieldSample(torch.autograd.Function):
         field, pos, pts, cond, bary, hits = ctx.saved_tensors
         V, T = pos.shape[1], ctx.idx.shape[1]
         gout = _f32c(gout)
-        csr = ctx.csr
-        if csr is None:                                              # the slow path: a sort of 4 T incidences and a host sync per backward
-            csr = tet_vertex_csr(ctx.idx, V)
+        csr = _csr_or_build(ctx.csr, ctx.idx, V)
         g_field = g_pos = g_pts = None
         if ctx.needs_input_grad[0]:
             g_field = tet_field_sample_bwd_field(gout, cond, bary, csr, V, T)
@@ -2761,39 +2827,13 @@ def tet_field_sample(field, pos_bxvx3, tet_idx, pts_bxqx3, csr=None, topology=No
     no tet holds it.  Per channel ((w0 f0 + w1 f1) + w2 f2) + w3 f3 in fp32, every step rounded.
     Differentiable in field, pos and pts, each gradient computed only when asked for, without float atomics: field through a sort
     of the queries by tet and the incidence CSR, in one fixed order (the same bits on every run); pos and pts through the gradient
-    on the weights and point_in_tet_indexed_bwd_to_vertices, whose order is fixed up to 2 queries per tet (bwd_uses_records).  `csr` = tet_vertex_csr(tet_idx, V), built once per tet list (a TetTopology handed in as
-    `topology` brings its own, and keys the traversal-order decision).  csr=None with a gradient asked for is the SLOW PATH: the
-    CSR is rebuilt in every backward (a sort and a host sync).  check=True synchronises and raises on a vertex index outside
-    [0,V); otherwise a row whose tet names one is NaN and its grad_w is 0.  return_index: also cond f32 [B,Q,1] and bary f32
-    [B,Q,4] (no gradient)."""
-    _lib.require_gpu(field, pos_bxvx3, tet_idx, pts_bxqx3)
-    field = _pv_need(field, torch.float32, "tet_field_sample: field")
-    pos = _pv_need(pos_bxvx3, torch.float32, "tet_field_sample: pos")
-    pts = _pv_need(pts_bxqx3, torch.float32, "tet_field_sample: pts")
-    if tet_idx.dtype not in (torch.int32, torch.int64):
-        raise RuntimeError("tet_field_sample: tet_idx must be int32 or int64 (got %s)" % str(tet_idx.dtype).replace("torch.", ""))
-    if pos.dim() != 3 or pos.shape[2] != 3:
-        raise RuntimeError("tet_field_sample: pos [B,V,3] expected (got %s)" % (tuple(pos.shape),))
-    if pts.dim() != 3 or pts.shape[2] != 3:
-        raise RuntimeError("tet_field_sample: pts [B,Q,3] expected (got %s)" % (tuple(pts.shape),))
-    if field.dim() != 3 or field.shape[2] < 1:
-        raise RuntimeError("tet_field_sample: field [B,V,C] with a channel dimension of at least 1 expected (got %s)" % (tuple(field.shape),))
-    B, V, C = field.shape
-    if pos.shape[:2] != (B, V) or pts.shape[0] != B:
-        raise RuntimeError("tet_field_sample: field %s, pos %s and pts %s differ in B or V" % (tuple(field.shape), tuple(pos.shape), tuple(pts.shape)))
-    idx = getattr(topology, "tet_idx32", None)
-    if idx is None or (tet_idx is not getattr(topology, "tet_idx", None) and tet_idx is not idx):
-        idx = tet_idx
-    idx = _idx32(idx)
-    if idx.dim() != 3 or idx.shape[2] != 4 or idx.shape[0] not in (1, B):
-        raise RuntimeError("tet_field_sample: tet_idx [T,4] or [B,T,4] expected (got %s)" % (tuple(tet_idx.shape),))
-    if pos.device != field.device or pts.device != field.device or idx.device != field.device:
-        raise RuntimeError("tet_field_sample: field, pos, tet_idx and pts must be on one device")
-    T, Q = idx.shape[1], pts.shape[1]
-    if csr is None:
-        csr = getattr(topology, "csr", None)
-    if csr is not None and (len(csr) != 3 or csr[2] != idx.shape[0] or csr[1].numel() != csr[2] * T * 4 or csr[0].numel() != csr[2] * V + 1):
-        raise RuntimeError("tet_field_sample: csr is not tet_vertex_csr(tet_idx, %d) of this tet list" % V)
+    on the weights and point_in_tet_indexed_bwd_to_vertices, whose order is fixed up to 2 queries per tet (bwd_uses_records).
+    `csr` = tet_vertex_csr(tet_idx, V), or a TetTopology as `topology` (it brings its own and keys the traversal-order decision);
+    neither, with a gradient asked for, is the slow path: the CSR is rebuilt in every backward.  check=True synchronises and raises on a vertex index outside [0,V); otherwise a row whose tet names
+    one is NaN and its grad_w is 0.  return_index: also cond f32 [B,Q,1] and bary f32 [B,Q,4] (no gradient)."""
+    pos, idx, field, pts = _mesh_args("tet_field_sample", pos_bxvx3, tet_idx, topology, field=field, pts=pts_bxqx3)
+    (B, _, C), Q = field.shape, pts.shape[1]
+    csr = _resolve_csr("tet_field_sample", csr, topology, pos, idx)
     if Q == 0:
         out, cond, bary = field.new_empty(B, 0, C), field.new_empty(B, 0, 1), field.new_empty(B, 0, 4)
     else:
@@ -2810,56 +2850,13 @@ def tet_field_sample(field, pos_bxvx3, tet_idx, pts_bxqx3, csr=None, topology=No
 # field gradients on the tets, their energies, per-tet values to the vertices (tet_field_grad.hip)
 # ------------------------------------------------------------------------------------
 TFE_MAX_CHANNELS, _TFE_STATS = 8, 17                    # tet_field_grad.hip kTfeMaxC, kTfeStats
-_CsrAndList = collections.namedtuple("_CsrAndList", "csr tet_idx32")     # what tet_to_vertex reads of a TetTopology
-
-
-def _check_csr(caller, csr, Bi, V, T):
-    if (not isinstance(csr, (tuple, list)) or len(csr) != 3 or csr[2] != Bi or csr[1].numel() != Bi * T * 4
-            or csr[0].numel() != Bi * V + 1):
-        raise RuntimeError("%s: csr is not tet_vertex_csr(tet_idx, %d) of this tet list" % (caller, V))
-
-
-def _tfg_inputs(caller, field, pos, tet_idx, topology, max_channels=None):
-    """(field, pos, idx) contiguous — f32 [B,V,C], f32 [B,V,3], int32 [Bi,T,4] — checked against each other; the topology's own
-    int32 copy of the list when tet_idx is the list it was built from"""
-    for name, t in (("field", field), ("pos", pos), ("tet_idx", tet_idx)):
-        if not isinstance(t, torch.Tensor):
-            raise RuntimeError("%s: %s must be a tensor" % (caller, name))
-    if pos.device != field.device or tet_idx.device != field.device:
-        raise RuntimeError("%s: field, pos and tet_idx must be on one device" % caller)
-    _lib.require_gpu(field, pos, tet_idx)
-    field, pos = _pv_need(field, torch.float32, caller + ": field"), _pv_need(pos, torch.float32, caller + ": pos")
-    if tet_idx.dtype not in (torch.int32, torch.int64):
-        raise RuntimeError("%s: tet_idx must be int32 or int64 (got %s)" % (caller, str(tet_idx.dtype).replace("torch.", "")))
-    if field.dim() != 3 or field.shape[2] < 1:
-        raise RuntimeError("%s: field [B,V,C] with a channel dimension of at least 1 expected (got %s)" % (caller, tuple(field.shape)))
-    B, V, C = field.shape
-    if max_channels is not None and C > max_channels:
-        raise _lib.DefTetHipError("%s: field [B,V,C] with 1 <= C <= %d expected, got %s (DEFTET_EINVAL)" % (caller, max_channels, tuple(field.shape)))
-    if pos.dim() != 3 or tuple(pos.shape) != (B, V, 3):
-        raise RuntimeError("%s: pos [%d,%d,3] expected (got %s)" % (caller, B, V, tuple(pos.shape)))
-    idx = getattr(topology, "tet_idx32", None)
-    if idx is None or (tet_idx is not getattr(topology, "tet_idx", None) and tet_idx is not idx):
-        idx = tet_idx
-    idx = _idx32(idx)
-    if idx.dim() != 3 or idx.shape[2] != 4 or idx.shape[0] not in (1, B):
-        raise RuntimeError("%s: tet_idx [T,4] or [B,T,4] expected (got %s)" % (caller, tuple(tet_idx.shape)))
-    return field, pos, idx
-
-
-def _tfg_csr(caller, csr, topology, idx, V):
-    if csr is None:
-        csr = getattr(topology, "csr", None)
-    if csr is not None:
-        _check_csr(caller, csr, idx.shape[0], V, idx.shape[1])
-    return csr
 
 
 def tet_field_gradient_fwd(field, pos_bxvx3, tet_idx, return_volume=False):
     """grad f32 [B,T,C,3] (and vol f32 [B,T]): per tet the gradient of the linear interpolant of field f32 [B,V,C] over the
     positions f32 [B,V,3], g_c = (n0 df0 + n1 df1 + n2 df2) / det in fp32 (include/deftet_hip.h), 0 with volume 0 on a dead tet
     (det > 0 fails).  One launch.  The raw forward of tet_field_gradient."""
-    field, pos, idx = _tfg_inputs("tet_field_gradient", field, pos_bxvx3, tet_idx, None)
+    pos, idx, field, _ = _mesh_args("tet_field_gradient", pos_bxvx3, tet_idx, field=field)
     B, V, C = field.shape
     T, dev = idx.shape[1], field.device
     out = torch.empty(B, T, C, 3, device=dev, dtype=torch.float32)
@@ -2871,10 +2868,7 @@ def tet_field_gradient_fwd(field, pos_bxvx3, tet_idx, return_volume=False):
 def tet_volumes(pos_bxvx3, tet_idx):
     """vol f32 [B,T] = det E / 6 of every tet, 0 for a dead one: tet_field_gradient's volumes alone (no gradient), e.g. as the
     constant weights of tet_to_vertex.  One launch."""
-    _lib.require_gpu(pos_bxvx3, tet_idx)
-    pos, idx = _pv_need(pos_bxvx3.detach(), torch.float32, "tet_volumes: pos"), _idx32(tet_idx)
-    if pos.dim() != 3 or pos.shape[2] != 3 or idx.dim() != 3 or idx.shape[2] != 4 or idx.shape[0] not in (1, pos.shape[0]):
-        raise RuntimeError("tet_volumes: pos [B,V,3] and tet_idx [T,4] or [B,T,4] expected (got %s, %s)" % (tuple(pos.shape), tuple(idx.shape)))
+    pos, idx, _, _ = _mesh_args("tet_volumes", _pv_need(pos_bxvx3.detach(), torch.float32, "tet_volumes: pos"), tet_idx, convert=True)
     B, V, T = pos.shape[0], pos.shape[1], idx.shape[1]
     vol = torch.empty(B, T, device=pos.device, dtype=torch.float32)
     _lib.call("deftet_tet_field_gradient_fwd_f32", pos.device, None, pos, idx, None, vol, B, V, T, idx.shape[0], 1)
@@ -2885,19 +2879,19 @@ def tet_field_gradient_bwd(grad_out, grad_vol, field, pos_bxvx3, tet_idx, csr, w
     """(grad_field f32 [B,V,C] | None, grad_pos f32 [B,V,3] | None): grad_out f32 [B,T,C,3] and grad_vol f32 [B,T] (or None) of
     tet_field_gradient_fwd taken to the vertices, per vertex one fp32 accumulator over its incidences in the CSR's order
     (ascending 4 t + corner); no atomics, the same bits on every run.  One launch per gradient asked for."""
-    field, pos, idx = _tfg_inputs("tet_field_gradient_bwd", field, pos_bxvx3, tet_idx, None)
+    pos, idx, field, _ = _mesh_args("tet_field_gradient_bwd", pos_bxvx3, tet_idx, field=field)
     B, V, C = field.shape
     T, dev = idx.shape[1], field.device
-    _check_csr("tet_field_gradient_bwd", csr, idx.shape[0], V, T)
+    _check_csr("tet_field_gradient_bwd", csr, B, V, T, idx.shape[0], dev)
     _lib.require_gpu(grad_out, grad_vol)
     g = _f32c(grad_out)
     if tuple(g.shape) != (B, T, C, 3):
-        raise RuntimeError("tet_field_gradient_bwd: grad_out %s expected (got %s)" % ((B, T, C, 3), tuple(g.shape)))
+        raise _expected("tet_field_gradient_bwd", "grad_out %s" % ((B, T, C, 3),), g)
     gv = None
     if grad_vol is not None:
         gv = _f32c(grad_vol)
         if tuple(gv.shape) != (B, T):
-            raise RuntimeError("tet_field_gradient_bwd: grad_vol %s expected (got %s)" % ((B, T), tuple(gv.shape)))
+            raise _expected("tet_field_gradient_bwd", "grad_vol %s" % ((B, T),), gv)
     gf = torch.empty(B, V, C, device=dev, dtype=torch.float32) if want_field else None
     gp = torch.empty(B, V, 3, device=dev, dtype=torch.float32) if want_pos else None
     if want_field or want_pos:
@@ -2924,9 +2918,7 @@ class _TetFieldGradient(torch.autograd.Function):
             return (torch.zeros_like(field) if want_f else None, torch.zeros_like(pos) if want_p else None, None, None, None)
         if g_out is None:
             g_out = field.new_zeros(field.shape[0], ctx.idx.shape[1], field.shape[2], 3)
-        csr = ctx.csr
-        if csr is None:                                              # the slow path: a sort of 4 T incidences and a host sync per backward
-            csr = tet_vertex_csr(ctx.idx, pos.shape[1])
+        csr = _csr_or_build(ctx.csr, ctx.idx, pos.shape[1])
         gf, gp = tet_field_gradient_bwd(g_out, g_vol, field.detach(), pos.detach(), ctx.idx, csr, want_field=want_f, want_pos=want_p)
         return gf, gp, None, None, None
 
@@ -2937,11 +2929,11 @@ def tet_field_gradient(field, pos_bxvx3, tet_idx, csr=None, topology=None, retur
     vertex 0 and df_k = f(v_{k+1},c) - f(v0,c), in the adjugate form in fp32.  return_volume: also vol f32 [B,T] = det E / 6.
     A tet is live iff det E > 0 in fp32 (the orientation of every grid here); a NaN, flat or inverted tet has gradient 0 and
     volume 0 and gives nothing to a backward.  Differentiable in field and pos, also through vol: the gradient lands on the
-    vertices through `csr` = tet_vertex_csr(tet_idx, V) in its order, without float atomics (the same bits on every run).  A
-    TetTopology handed in as `topology` brings its own csr.  csr=None with a gradient asked for is the SLOW PATH: the CSR is
-    rebuilt in every backward (a sort and a host sync)."""
-    field, pos, idx = _tfg_inputs("tet_field_gradient", field, pos_bxvx3, tet_idx, topology)
-    csr = _tfg_csr("tet_field_gradient", csr, topology, idx, field.shape[1])
+    vertices through the incidence CSR in its order, without float atomics (the same bits on every run).  `csr` =
+    tet_vertex_csr(tet_idx, V), or a TetTopology as `topology`; neither, with a gradient asked for, is the slow path: the CSR is
+    rebuilt in every backward."""
+    pos, idx, field, _ = _mesh_args("tet_field_gradient", pos_bxvx3, tet_idx, topology, field=field)
+    csr = _resolve_csr("tet_field_gradient", csr, topology, pos, idx)
     out, vol = _TetFieldGradient.apply(field, pos, idx, csr, bool(return_volume))
     return (out, vol) if return_volume else out
 
@@ -2968,9 +2960,7 @@ class _TetFieldEnergies(torch.autograd.Function):
             return None, None, None, None, None
         B, V, C = field.shape
         idx, dev = ctx.idx, field.device
-        csr = ctx.csr
-        if csr is None:                                              # the slow path, as in tet_field_gradient
-            csr = tet_vertex_csr(idx, V)
+        csr = _csr_or_build(ctx.csr, idx, V)
         gf = torch.empty(B, V, C, device=dev, dtype=torch.float32) if want_f else None
         gp = torch.empty(B, V, 3, device=dev, dtype=torch.float32) if want_p else None
         _lib.call("deftet_tet_field_energies_bwd_f32", dev, stats, _f32c(g_out), ctx.target, field, pos, idx, csr[0], csr[1], gf, gp, B, V,
@@ -2985,25 +2975,29 @@ def tet_field_energies(field, pos_bxvx3, tet_idx, csr=None, topology=None, targe
     fp64 in one order.  Differentiable in field and pos through the saved per-shape sums and the incidence CSR (csr, topology
     and the slow path as in tet_field_gradient), without float atomics.  Where |g| = 0 the Eikonal term's derivative is taken
     as 0.  W = 0 (no live tet) gives 0 energies and 0 gradients."""
-    field, pos, idx = _tfg_inputs("tet_field_energies", field, pos_bxvx3, tet_idx, topology, max_channels=TFE_MAX_CHANNELS)
-    csr = _tfg_csr("tet_field_energies", csr, topology, idx, field.shape[1])
+    pos, idx, field, _ = _mesh_args("tet_field_energies", pos_bxvx3, tet_idx, topology, field=field)
+    if field.shape[2] > TFE_MAX_CHANNELS:
+        raise _lib.DefTetHipError("tet_field_energies: field [B,V,C] with 1 <= C <= %d expected (got %s) (DEFTET_EINVAL)"
+                                  % (TFE_MAX_CHANNELS, tuple(field.shape)))
+    csr = _resolve_csr("tet_field_energies", csr, topology, pos, idx)
     return _TetFieldEnergies.apply(field, pos, idx, csr, float(target))
 
 
 def _ttv_topology(tet_idx_or_csr, n_vertex):
     """(csr, int32 idx | None) of tet_to_vertex's second argument: a TetTopology (its csr and list), a csr tuple, or a tet list"""
-    V = int(n_vertex)
-    if hasattr(tet_idx_or_csr, "csr") and hasattr(tet_idx_or_csr, "tet_idx32"):
-        return tet_idx_or_csr.csr, _idx32(tet_idx_or_csr.tet_idx32)
-    if isinstance(tet_idx_or_csr, (tuple, list)):
-        return tet_idx_or_csr, None
+    _, own32, csr = _topology_parts(tet_idx_or_csr)
+    if csr is not None and own32 is not None:
+        return csr, _idx32(own32)
+    if isinstance(tet_idx_or_csr, (tuple, list)):                    # a csr; or the pair (csr, int32 list) vertex_field_gradient hands in
+        return tet_idx_or_csr if len(tet_idx_or_csr) == 2 else (tet_idx_or_csr, None)
     if not isinstance(tet_idx_or_csr, torch.Tensor) or tet_idx_or_csr.dtype not in (torch.int32, torch.int64):
-        raise RuntimeError("tet_to_vertex: a tet list int [T,4] or [B,T,4], a tet_vertex_csr tuple or a TetTopology expected")
+        raise _expected("tet_to_vertex", "a tet list int32 / int64 [T,4] or [B,T,4], a tet_vertex_csr tuple or a TetTopology",
+                        getattr(tet_idx_or_csr, "dtype", type(tet_idx_or_csr).__name__))
     _lib.require_gpu(tet_idx_or_csr)
     idx = _idx32(tet_idx_or_csr)
     if idx.dim() != 3 or idx.shape[2] != 4:
-        raise RuntimeError("tet_to_vertex: tet_idx [T,4] or [B,T,4] expected (got %s)" % (tuple(tet_idx_or_csr.shape),))
-    return tet_vertex_csr(idx, V), idx                               # the slow path: the CSR is built in this call
+        raise _expected("tet_to_vertex", "tet_idx [T,4] or [B,T,4]", tet_idx_or_csr)
+    return _csr_or_build(None, idx, int(n_vertex)), idx              # the slow path, in this call
 
 
 def _csr_tet_list(csr, V, T):
@@ -3072,18 +3066,14 @@ def tet_to_vertex(values_bxtxc, tet_idx_or_csr, n_vertex, weights=None, fill=0.0
     B, T, C = val.shape
     V = int(n_vertex)
     csr, idx = _ttv_topology(tet_idx_or_csr, V)
-    if not isinstance(csr, (tuple, list)) or len(csr) != 3 or csr[2] not in (1, B):
-        raise RuntimeError("tet_to_vertex: csr is not tet_vertex_csr(tet_idx, %d) of this tet list" % V)
-    _check_csr("tet_to_vertex", csr, csr[2], V, T)
-    if idx is not None and tuple(idx.shape) != (csr[2], T, 4):
-        raise RuntimeError("tet_to_vertex: the tet list %s does not belong to values %s" % (tuple(idx.shape), tuple(val.shape)))
+    _check_csr("tet_to_vertex", csr, B, V, T, None if idx is None else idx.shape[0], val.device)
+    if idx is not None and (tuple(idx.shape) != (csr[2], T, 4) or idx.device != val.device):
+        raise _expected("tet_to_vertex", "a tet list [%d,%d,4] on %s" % (csr[2], T, val.device), "%s on %s" % (tuple(idx.shape), idx.device))
     w = None
     if weights is not None:
         w = _pv_need(weights.detach(), torch.float32, "tet_to_vertex: weights")
-        if tuple(w.shape) != (B, T):
-            raise RuntimeError("tet_to_vertex: weights [%d,%d] expected (got %s)" % (B, T, tuple(w.shape)))
-    if csr[0].device != val.device or (w is not None and w.device != val.device) or (idx is not None and idx.device != val.device):
-        raise RuntimeError("tet_to_vertex: values, weights and the tet list must be on one device")
+        if tuple(w.shape) != (B, T) or w.device != val.device:
+            raise _expected("tet_to_vertex", "weights [%d,%d] on %s" % (B, T, val.device), "%s on %s" % (tuple(w.shape), w.device))
     return _TetToVertex.apply(val, w, csr, idx, V, float(fill))[0]
 
 
@@ -3091,14 +3081,12 @@ def vertex_field_gradient(field, pos_bxvx3, tet_idx, csr=None, topology=None, fi
     """f32 [B,V,C,3]: the field's gradient at the vertices, the volume-weighted mean of tet_field_gradient over each vertex's
     incident tets (tet_to_vertex with the volumes as constant weights); `fill` at a vertex with no live tet.  Differentiable in
     field and pos through the per-tet gradients."""
-    field, pos, idx = _tfg_inputs("vertex_field_gradient", field, pos_bxvx3, tet_idx, topology)
+    pos, idx, field, _ = _mesh_args("vertex_field_gradient", pos_bxvx3, tet_idx, topology, field=field)
     V = field.shape[1]
-    csr = _tfg_csr("vertex_field_gradient", csr, topology, idx, V)
-    if csr is None:
-        csr = tet_vertex_csr(idx, V)                                 # the slow path, once for both steps
+    csr = _csr_or_build(_resolve_csr("vertex_field_gradient", csr, topology, pos, idx), idx, V)      # (once for both steps)
     g, vol = _TetFieldGradient.apply(field, pos, idx, csr, True)
     B, T, C = g.shape[:3]
-    return tet_to_vertex(g.reshape(B, T, C * 3), _CsrAndList(csr, idx), V, weights=vol, fill=fill).reshape(B, V, C, 3)
+    return tet_to_vertex(g.reshape(B, T, C * 3), (csr, idx), V, weights=vol, fill=fill).reshape(B, V, C, 3)
 
 
 def unit_normals(grad_nx3):

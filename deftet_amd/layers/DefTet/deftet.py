@@ -78,18 +78,18 @@ class TetTopology:
         """hip_ops.tet_field_sample on this tet list: the per-vertex field [B,V,C] read at the points pts [B,Q,3] with the
         barycentric weights of the tet that holds each, [B,Q,C] (`fill` outside the mesh), differentiable in field, vertice_pos and
         pts through the cached incidence CSR."""
-        return hip_ops.tet_field_sample(field, vertice_pos, self.tet_idx32, pts, csr=self.csr, topology=self, fill=fill,
+        return hip_ops.tet_field_sample(field, vertice_pos, self.tet_idx32, pts, topology=self, fill=fill,
                                         return_index=return_index)
 
     def field_gradient(self, field, vertice_pos, return_volume=False):
         """hip_ops.tet_field_gradient on this tet list: the gradient of the per-vertex field [B,V,C] on every tet, [B,T,C,3] (and
         the volumes [B,T]), differentiable in field and vertice_pos through the cached incidence CSR."""
-        return hip_ops.tet_field_gradient(field, vertice_pos, self.tet_idx32, csr=self.csr, topology=self, return_volume=return_volume)
+        return hip_ops.tet_field_gradient(field, vertice_pos, self.tet_idx32, topology=self, return_volume=return_volume)
 
     def field_energies(self, field, vertice_pos, target=1.0):
         """hip_ops.tet_field_energies on this tet list: [B,C,2] = the volume-weighted Dirichlet energy and Eikonal term
         (|grad f| - target)^2 of the per-vertex field, differentiable in field and vertice_pos."""
-        return hip_ops.tet_field_energies(field, vertice_pos, self.tet_idx32, csr=self.csr, topology=self, target=target)
+        return hip_ops.tet_field_energies(field, vertice_pos, self.tet_idx32, topology=self, target=target)
 
     def to_vertices(self, values_bxtxc, weights=None, fill=0.0):
         """hip_ops.tet_to_vertex on this tet list: per-tet values [B,T,C] as the (weighted) mean over each vertex's incident

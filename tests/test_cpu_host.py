@@ -510,3 +510,128 @@ def test_sparse_render_default_policy_is_none():
     from deftet_amd.render.deftet_sparse_render import deftet_sparse_render, NEAREST, FIRST
     assert inspect.signature(deftet_sparse_render).parameters["policy"].default is None
     assert (NEAREST, FIRST) == (0, 1)
+
+
+# ---------------------------------------------------------------------------- the tet-mesh argument contract of hip_ops
+def _kuhn_csr(idx_batch, dtype=torch.int32):
+    """(csr, tets int32 [idx_batch,48,4], V = 27, T = 48) of the 2x2x2 Kuhn grid, the CSR built in numpy: per list and vertex
+    the incidences 4 t + corner in ascending order, the offsets running on through the lists"""
+    verts, tets = grids.kuhn_grid(4)
+    V, T = verts.shape[0], tets.shape[0]
+    flat = tets.reshape(-1).astype(np.int64)
+    order = np.argsort(flat, kind="stable")
+    counts = np.bincount(flat, minlength=V)
+    offsets = np.concatenate([[0], np.cumsum(np.tile(counts, idx_batch))])
+    slots = np.tile(order, idx_batch)
+    lists = torch.from_numpy(np.tile(tets[None], (idx_batch, 1, 1)))
+    return (torch.from_numpy(offsets).to(dtype), torch.from_numpy(slots).to(dtype), idx_batch), lists, V, T
+
+
+def test_check_csr_is_the_contract():
+    from deftet_amd import hip_ops
+    chk = hip_ops._check_csr
+    cpu = torch.device("cpu")
+    for Bi in (1, 2):
+        csr, _, V, T = _kuhn_csr(Bi)
+        assert (V, T) == (27, 48) and int(csr[0][-1]) == Bi * 4 * T
+        chk("op", csr, 2, V, T)
+        chk("op", csr, 2, V, T, Bi, cpu)
+        chk("op", list(csr), 2, V, T, idx_batch=Bi)
+    csr, _, V, T = _kuhn_csr(1)
+    three = _kuhn_csr(3)[0]
+    bad = [lambda: chk("some_op", csr, 2, V, T + 1), lambda: chk("some_op", csr, 2, V, T - 1),
+           lambda: chk("some_op", csr, 2, V + 1, T), lambda: chk("some_op", csr, 2, V - 1, T),
+           lambda: chk("some_op", three, 2, V, T),                            # idx_batch 3 with B = 2
+           lambda: chk("some_op", csr, 2, V, T, 2),                           # built over 1 list, the mesh has 2
+           lambda: chk("some_op", (csr[0], csr[1].long(), 1), 2, V, T), lambda: chk("some_op", (csr[0].long(), csr[1], 1), 2, V, T),
+           lambda: chk("some_op", csr[:2], 2, V, T), lambda: chk("some_op", None, 2, V, T),
+           lambda: chk("some_op", (csr[0].tolist(), csr[1], 1), 2, V, T),
+           lambda: chk("some_op", csr, 2, V, T, 1, torch.device("meta"))]     # a CSR on another device than the operands
+    for k, fn in enumerate(bad):
+        with pytest.raises(RuntimeError, match="some_op"):
+            fn()
+            pytest.fail("case %d did not raise" % k)
+
+
+def test_mesh_args_resolve_the_list_and_check_the_mesh(monkeypatch):
+    from deftet_amd import _lib, hip_ops
+    monkeypatch.setattr(_lib, "require_gpu", lambda *tensors: None)
+    monkeypatch.setattr(_lib, "call", lambda *a, **k: pytest.fail("a launch from an argument check"))
+    mesh = hip_ops._mesh_args
+    B, C, Q = 2, 3, 5
+    csr, lists, V, T = _kuhn_csr(1)
+
+    class Topo:                                                               # what a TetTopology shows of itself
+        tet_idx = lists.long()
+        tet_idx32 = lists
+    Topo.csr = csr
+    pos, field, pts = torch.rand(B, V, 3), torch.rand(B, V, C), torch.rand(B, Q, 3)
+    for handed in (Topo.tet_idx, Topo.tet_idx32):
+        p, idx, f, q = mesh("op", pos, handed, Topo, field=field, pts=pts)
+        assert idx is Topo.tet_idx32 and p is pos and f is field and q is pts
+    other = lists.long().clone()
+    for topology in (None, Topo):
+        for handed in (other, other[0], other.int()[0], other.expand(B, -1, -1)):
+            idx = mesh("op", pos, handed, topology)[1]
+            assert idx is not Topo.tet_idx32 and idx.dtype == torch.int32 and idx.is_contiguous() and idx.dim() == 3
+            assert torch.equal(idx, handed.reshape(-1, T, 4).int())
+    assert mesh("op", pos, other, field=field)[2] is field and mesh("op", pos, other, pts=pts)[2:] == (None, pts)
+    assert mesh("op", pos.transpose(0, 1).contiguous().transpose(0, 1), other)[0].is_contiguous()
+    assert mesh("op", None, other, field=field)[0] is None                   # the raw entries: the field alone names B and V
+    p, idx, _, q = mesh("op", pos.double(), other.to(torch.int16), pts=pts.half(), convert=True)      # the first entries' contract
+    assert p.dtype == q.dtype == torch.float32 and torch.equal(p, pos) and idx.dtype == torch.int32 and torch.equal(idx, other.int())
+    bad = [lambda: mesh("some_op", pos[:, :, :2], other), lambda: mesh("some_op", pos[0], other), lambda: mesh("some_op", pos.double(), other),
+           lambda: mesh("some_op", pos, other[:, :, :3]), lambda: mesh("some_op", pos, other.float()), lambda: mesh("some_op", pos, other.to(torch.int16)),
+           lambda: mesh("some_op", pos, other.expand(3, -1, -1)),             # idx_batch 3 with B = 2
+           lambda: mesh("some_op", pos, other, field=field[:, :-1]), lambda: mesh("some_op", pos, other, field=field[:1]),
+           lambda: mesh("some_op", pos, other, field=field[:, :, :0]), lambda: mesh("some_op", pos, other, field=field[:, :, 0]),
+           lambda: mesh("some_op", pos, other, field=field.double()),
+           lambda: mesh("some_op", pos, other, pts=pts[:1]), lambda: mesh("some_op", pos, other, pts=pts[:, :, :2]),
+           lambda: mesh("some_op", pos, other, pts=pts.half()),
+           lambda: mesh("some_op", pos, other.int().to("meta")), lambda: mesh("some_op", pos, other, pts=pts.to("meta")),
+           lambda: mesh("some_op", pos, None), lambda: mesh("some_op", None, other), lambda: mesh("some_op", pos, other.tolist())]
+    for k, fn in enumerate(bad):
+        with pytest.raises(RuntimeError, match="some_op"):
+            fn()
+            pytest.fail("case %d did not raise" % k)
+    # the resolver: the given CSR first, else the topology's, checked against the mesh; None when there is neither
+    resolve = hip_ops._resolve_csr
+    mine = _kuhn_csr(1)[0]
+    assert resolve("op", mine, Topo, pos, lists) is mine and resolve("op", None, Topo, pos, lists) is csr
+    assert resolve("op", None, None, pos, lists) is None and resolve("op", None, other, pos, lists) is None
+    for wrong in (_kuhn_csr(2)[0], csr[:2], (csr[0], csr[1][:-1], 1)):
+        with pytest.raises(RuntimeError, match="some_op"):
+            resolve("some_op", wrong, Topo, pos, lists)
+    Topo.csr = _kuhn_csr(2)[0]                                               # a topology whose CSR is not this list's
+    with pytest.raises(RuntimeError, match="some_op"):
+        resolve("some_op", None, Topo, pos, lists)
+
+
+def test_csr_or_build_calls_the_bound_builder_once(monkeypatch):
+    from deftet_amd import hip_ops
+    calls = []
+    dummy = ("offsets", "slots", 1)
+    monkeypatch.setattr(hip_ops, "tet_vertex_csr", lambda *a: calls.append(a) or dummy)
+    csr, lists, V, T = _kuhn_csr(1)
+    assert hip_ops._csr_or_build(csr, lists, V) is csr and calls == []
+    assert hip_ops._csr_or_build(None, lists, V) is dummy and len(calls) == 1 and calls[0][0] is lists and calls[0][1] == V
+
+
+def test_out_or_new_and_the_bad_flag():
+    from deftet_amd import hip_ops
+    cpu = torch.device("cpu")
+    new = hip_ops._out_or_new("op", None, (2, 5, 3), cpu)
+    assert new.shape == (2, 5, 3) and new.dtype == torch.float32 and new.is_contiguous()
+    assert hip_ops._out_or_new("op", new, (2, 5, 3), cpu) is new
+    for out, shape, dev in ((new, (2, 5, 4), cpu), (new.double(), (2, 5, 3), cpu), (new.transpose(0, 1), (5, 2, 3), cpu),
+                            (new, (2, 5, 3), torch.device("meta"))):
+        with pytest.raises(RuntimeError, match="some_op"):
+            hip_ops._out_or_new("some_op", out, shape, dev)
+    assert hip_ops._bad_flag(False, cpu) is None
+    flag = hip_ops._bad_flag(True, cpu)
+    assert flag.dtype == torch.int32 and flag.tolist() == [0]
+    hip_ops._raise_if(None, IndexError, "never")
+    hip_ops._raise_if(flag, IndexError, "never")
+    flag.fill_(1)
+    with pytest.raises(IndexError, match="this one"):
+        hip_ops._raise_if(flag, IndexError, "this one")
