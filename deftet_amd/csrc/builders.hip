@@ -676,24 +676,15 @@ static NeighboursLayout neighbours_layout(int T, void *ws)
     return L;
 }
 
-#define TRY(x)                     \
-    do {                           \
-        int s_ = (x);              \
-        if (s_ != DEFTET_OK) return s_; \
-    } while (0)
-
-static int check_common(const void *tet, int n_point, int n_tet, void *ws)
+static int check_common(const void *tet, int n_point, int n_tet)
 {
     DEFTET_CHECK_ARG(n_tet >= 0 && n_point >= 0, "negative size");
     DEFTET_CHECK_ARG(n_point <= 2097151, "n_point=%d: face keys min*n^2+max*n+mid would overflow 63 bits", n_point);
     DEFTET_CHECK_ARG(n_tet <= 100000000, "n_tet too large");
     DEFTET_CHECK_ARG(n_tet == 0 || tet, "null tet_list");
     DEFTET_CHECK_ARG(n_tet == 0 || (((uintptr_t)tet & 15) == 0), "tet_list must be 16-byte aligned");
-    DEFTET_CHECK_ARG(n_tet == 0 || (ws && ((uintptr_t)ws & 255) == 0), "workspace null or not 256-byte aligned");
     return DEFTET_OK;
 }
-
-static inline dim3 grid_for(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 
 // ------------------------------------------------------------------------------------
@@ -774,20 +765,20 @@ extern "C" size_t deftet_builder_workspace_bytes(int n_point, int n_tet)
 extern "C" int deftet_tet_adj_share_i32(const int32_t *tet, int32_t *out_rows, int32_t *n_out, int n_point, int T,
                                         void *workspace, size_t wsb, void *stream_)
 {
-    TRY(check_common(tet, n_point, T, workspace));
+    DEFTET_TRY(check_common(tet, n_point, T));
     hipStream_t st = as_stream(stream_);
     DEFTET_CHECK_ARG(n_out, "null n_out");
     if (T == 0) { DEFTET_HIP(hipMemsetAsync(n_out, 0, 4, st)); return DEFTET_OK; }
     DEFTET_CHECK_ARG(out_rows, "null out_rows");
     const size_t n = (size_t)T * 4;
     const PairLayout L = share_layout(T, workspace);
-    DEFTET_CHECK_ARG(L.bytes <= wsb, "workspace too small");
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, L.bytes));
     const u64 np = (u64)n_point;
-    DEFTET_LAUNCH(k_face_keys, grid_for(n), dim3(256), st, tet, T, np, L.key, L.own, (u64 *)nullptr);
-    TRY(sort_pairs(L.sort, L.key, L.skey, L.own, L.sown, n, key_bits(np * np * np), st));
-    DEFTET_LAUNCH(k_share_flag, grid_for(n), dim3(256), st, L.skey, (int)n, L.flag);
-    TRY(ex_scan(L.scan, L.flag, L.pos, n, st));
-    DEFTET_LAUNCH(k_share_emit, grid_for(n), dim3(256), st, L.flag, L.pos, L.sown, (int)n, out_rows, n_out);
+    DEFTET_LAUNCH(k_face_keys, blocks_for(n, 256), dim3(256), st, tet, T, np, L.key, L.own, (u64 *)nullptr);
+    DEFTET_TRY(sort_pairs(L.sort, L.key, L.skey, L.own, L.sown, n, key_bits(np * np * np), st));
+    DEFTET_LAUNCH(k_share_flag, blocks_for(n, 256), dim3(256), st, L.skey, (int)n, L.flag);
+    DEFTET_TRY(ex_scan(L.scan, L.flag, L.pos, n, st));
+    DEFTET_LAUNCH(k_share_emit, blocks_for(n, 256), dim3(256), st, L.flag, L.pos, L.sown, (int)n, out_rows, n_out);
     return DEFTET_OK;
 }
 
@@ -795,24 +786,24 @@ extern "C" int deftet_tet_to_face_i32(const int32_t *tet, int64_t *face_fx3, int
                                       int64_t *boundary_fx3, int32_t *counts, int n_point, int T, int with_boundary,
                                       void *workspace, size_t wsb, void *stream_)
 {
-    TRY(check_common(tet, n_point, T, workspace));
+    DEFTET_TRY(check_common(tet, n_point, T));
     hipStream_t st = as_stream(stream_);
     DEFTET_CHECK_ARG(counts, "null counts");
     if (T == 0) { DEFTET_HIP(hipMemsetAsync(counts, 0, 12, st)); return DEFTET_OK; }
     DEFTET_CHECK_ARG(face_fx3 && tetidx_fx2 && tetfaceidx_fx2, "null output");
     const size_t n = (size_t)T * 4;
     const ToFaceLayout L = to_face_layout(T, workspace);
-    DEFTET_CHECK_ARG(L.bytes <= wsb, "workspace too small");
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, L.bytes));
     const u64 np = (u64)n_point;
-    DEFTET_LAUNCH(k_face_keys, grid_for(n), dim3(256), st, tet, T, np, L.key, L.own, (u64 *)nullptr);
-    TRY(sort_pairs(L.sort, L.key, L.skey, L.own, L.sown, n, key_bits(np * np * np), st));
+    DEFTET_LAUNCH(k_face_keys, blocks_for(n, 256), dim3(256), st, tet, T, np, L.key, L.own, (u64 *)nullptr);
+    DEFTET_TRY(sort_pairs(L.sort, L.key, L.skey, L.own, L.sown, n, key_bits(np * np * np), st));
     DEFTET_HIP(hipMemsetAsync(L.gsize, 0, n * 4, st));
-    DEFTET_LAUNCH(k_group_info, grid_for(n), dim3(256), st, L.skey, L.sown, (int)n, L.gsize, L.second);
-    DEFTET_LAUNCH(k_face_flags, grid_for(n), dim3(256), st, L.gsize, (int)n, with_boundary, L.f_in, L.f_bd, L.f_mu);
-    TRY(ex_scan(L.scan, L.f_in, L.p_in, n, st));
-    TRY(ex_scan(L.scan, L.f_bd, L.p_bd, n, st));
-    TRY(ex_scan(L.scan, L.f_mu, L.p_mu, n, st));
-    DEFTET_LAUNCH(k_face_emit, grid_for(n), dim3(256), st, tet, L.gsize, L.second, L.f_in, L.p_in, L.f_bd, L.p_bd, L.f_mu, L.p_mu, (int)n,
+    DEFTET_LAUNCH(k_group_info, blocks_for(n, 256), dim3(256), st, L.skey, L.sown, (int)n, L.gsize, L.second);
+    DEFTET_LAUNCH(k_face_flags, blocks_for(n, 256), dim3(256), st, L.gsize, (int)n, with_boundary, L.f_in, L.f_bd, L.f_mu);
+    DEFTET_TRY(ex_scan(L.scan, L.f_in, L.p_in, n, st));
+    DEFTET_TRY(ex_scan(L.scan, L.f_bd, L.p_bd, n, st));
+    DEFTET_TRY(ex_scan(L.scan, L.f_mu, L.p_mu, n, st));
+    DEFTET_LAUNCH(k_face_emit, blocks_for(n, 256), dim3(256), st, tet, L.gsize, L.second, L.f_in, L.p_in, L.f_bd, L.p_bd, L.f_mu, L.p_mu, (int)n,
                   (long long *)face_fx3, (long long *)tetidx_fx2, (long long *)tetfaceidx_fx2, (long long *)boundary_fx3,
                   counts);
     return DEFTET_OK;
@@ -828,55 +819,55 @@ extern "C" int deftet_tet_neighbours_i64(const int64_t *tetidx_fx2, const int64_
     DEFTET_CHECK_ARG(nbr_tx4, "null nbr_tx4");
     DEFTET_CHECK_ARG(n_face == 0 || (tetidx_fx2 && tetfaceidx_fx2), "null face table");
     const NeighboursLayout L = neighbours_layout(T, workspace);
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && L.bytes <= wsb, "workspace null, misaligned or too small");
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, L.bytes));
     hipStream_t st = as_stream(stream_);
     DEFTET_HIP(hipMemsetAsync(L.slotFace, 0x7F, (size_t)T * 16, st));
     DEFTET_HIP(hipMemsetAsync(L.slotNbr, 0xFF, (size_t)T * 16, st));
     if (n_face > 0)
-        DEFTET_LAUNCH(k_owner_scatter, grid_for((size_t)n_face), dim3(256), st, (const long long *)tetidx_fx2, (const long long *)tetfaceidx_fx2,
+        DEFTET_LAUNCH(k_owner_scatter, blocks_for((size_t)n_face, 256), dim3(256), st, (const long long *)tetidx_fx2, (const long long *)tetfaceidx_fx2,
                       n_face, L.slotFace, L.slotNbr, (long long *)withtet_4tx2);
-    DEFTET_LAUNCH(k_neighbour_rows, grid_for((size_t)T), dim3(256), st, L.slotFace, L.slotNbr, T, (long long *)nbr_tx4);
+    DEFTET_LAUNCH(k_neighbour_rows, blocks_for((size_t)T, 256), dim3(256), st, L.slotFace, L.slotNbr, T, (long long *)nbr_tx4);
     return DEFTET_OK;
 }
 
 extern "C" int deftet_tet_face_adj_i32(const int32_t *tet, int32_t *out_rows, long long capacity, long long *n_out,
                                        int n_point, int T, int wrap32, void *workspace, size_t wsb, void *stream_)
 {
-    TRY(check_common(tet, n_point, T, workspace));
+    DEFTET_TRY(check_common(tet, n_point, T));
     hipStream_t st = as_stream(stream_);
     DEFTET_CHECK_ARG(n_out && capacity >= 0, "null n_out / negative capacity");
     if (T == 0) { DEFTET_HIP(hipMemsetAsync(n_out, 0, 8, st)); return DEFTET_OK; }
     DEFTET_CHECK_ARG(out_rows || capacity == 0, "null out_rows");
     const size_t n = (size_t)T * 12, nf = (size_t)T * 4;
     const FaceAdjLayout L = face_adj_layout(T, workspace);
-    DEFTET_CHECK_ARG(L.bytes <= wsb, "workspace too small");
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, L.bytes));
     const u64 np = (u64)n_point;
-    DEFTET_LAUNCH(k_face_keys, grid_for(nf), dim3(256), st, tet, T, np, (u64 *)nullptr, (u32 *)nullptr, L.fkey);
-    DEFTET_LAUNCH(k_edge_keys, grid_for(n), dim3(256), st, tet, T, np, wrap32, L.key, L.ord);
-    TRY(sort_pairs(L.sort, L.key, L.skey, L.ord, L.sord, n, wrap32 ? 32 : key_bits(np * np), st));
-    DEFTET_LAUNCH(k_edge_count, grid_for(n), dim3(256), st, L.skey, L.sord, L.fkey, (int)n, L.cnt);
-    TRY(ex_scan(L.scan, L.cnt, L.pos, n, st));
-    DEFTET_LAUNCH(k_edge_emit, grid_for(n), dim3(256), st, L.skey, L.sord, L.fkey, L.cnt, L.pos, (int)n, capacity, out_rows, n_out);
+    DEFTET_LAUNCH(k_face_keys, blocks_for(nf, 256), dim3(256), st, tet, T, np, (u64 *)nullptr, (u32 *)nullptr, L.fkey);
+    DEFTET_LAUNCH(k_edge_keys, blocks_for(n, 256), dim3(256), st, tet, T, np, wrap32, L.key, L.ord);
+    DEFTET_TRY(sort_pairs(L.sort, L.key, L.skey, L.ord, L.sord, n, wrap32 ? 32 : key_bits(np * np), st));
+    DEFTET_LAUNCH(k_edge_count, blocks_for(n, 256), dim3(256), st, L.skey, L.sord, L.fkey, (int)n, L.cnt);
+    DEFTET_TRY(ex_scan(L.scan, L.cnt, L.pos, n, st));
+    DEFTET_LAUNCH(k_edge_emit, blocks_for(n, 256), dim3(256), st, L.skey, L.sord, L.fkey, L.cnt, L.pos, (int)n, capacity, out_rows, n_out);
     return DEFTET_OK;
 }
 
 extern "C" int deftet_tet_point_adj_i32(const int32_t *tet, int32_t *out_edges, int32_t *n_out, int n_point, int T,
                                         void *workspace, size_t wsb, void *stream_)
 {
-    TRY(check_common(tet, n_point, T, workspace));
+    DEFTET_TRY(check_common(tet, n_point, T));
     hipStream_t st = as_stream(stream_);
     DEFTET_CHECK_ARG(n_out, "null n_out");
     if (T == 0) { DEFTET_HIP(hipMemsetAsync(n_out, 0, 4, st)); return DEFTET_OK; }
     DEFTET_CHECK_ARG(out_edges, "null out_edges");
     const size_t n = (size_t)T * 12;
     const PointAdjLayout L = point_adj_layout(T, workspace);
-    DEFTET_CHECK_ARG(L.bytes <= wsb, "workspace too small");
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, L.bytes));
     const u64 np = (u64)n_point;
-    DEFTET_LAUNCH(k_pt_keys, grid_for(n), dim3(256), st, tet, T, np, L.key);
-    TRY(sort_keys(L.sort, L.key, L.skey, n, key_bits(np * np), st));
-    DEFTET_LAUNCH(k_unique_flag, grid_for(n), dim3(256), st, L.skey, (int)n, L.flag);
-    TRY(ex_scan(L.scan, L.flag, L.pos, n, st));
-    DEFTET_LAUNCH(k_pt_emit, grid_for(n), dim3(256), st, L.skey, L.flag, L.pos, (int)n, np, out_edges, n_out);
+    DEFTET_LAUNCH(k_pt_keys, blocks_for(n, 256), dim3(256), st, tet, T, np, L.key);
+    DEFTET_TRY(sort_keys(L.sort, L.key, L.skey, n, key_bits(np * np), st));
+    DEFTET_LAUNCH(k_unique_flag, blocks_for(n, 256), dim3(256), st, L.skey, (int)n, L.flag);
+    DEFTET_TRY(ex_scan(L.scan, L.flag, L.pos, n, st));
+    DEFTET_LAUNCH(k_pt_emit, blocks_for(n, 256), dim3(256), st, L.skey, L.flag, L.pos, (int)n, np, out_edges, n_out);
     return DEFTET_OK;
 }
 
@@ -888,55 +879,53 @@ extern "C" int deftet_colaps_v_f32(const float *pts, int32_t *map_array, int32_t
     DEFTET_CHECK_ARG(n_out, "null n_out");
     if (N == 0) { DEFTET_HIP(hipMemsetAsync(n_out, 0, 4, st)); return DEFTET_OK; }
     DEFTET_CHECK_ARG(pts && map_array && inverse_idx, "null pointer");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0, "workspace null or misaligned");
     const size_t n = (size_t)N;
     const ColapsLayout L = colaps_layout(N, workspace);
-    DEFTET_CHECK_ARG(L.bytes <= wsb, "workspace too small");
-    DEFTET_LAUNCH(k_dec_keys, grid_for(n), dim3(256), st, pts, N, L.kx, L.ky, L.kz, L.i0);
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, L.bytes));
+    DEFTET_LAUNCH(k_dec_keys, blocks_for(n, 256), dim3(256), st, pts, N, L.kx, L.ky, L.kz, L.i0);
     // LSD over the three coordinate keys (stable): z, then y, then x
-    TRY(sort_pairs(L.sort, L.kz, L.kb, L.i0, L.i1, n, 64, st));
-    DEFTET_LAUNCH(k_gather_u64, grid_for(n), dim3(256), st, L.ky, L.i1, N, L.ka);
-    TRY(sort_pairs(L.sort, L.ka, L.kb, L.i1, L.i0, n, 64, st));
-    DEFTET_LAUNCH(k_gather_u64, grid_for(n), dim3(256), st, L.kx, L.i0, N, L.ka);
-    TRY(sort_pairs(L.sort, L.ka, L.kb, L.i0, L.i1, n, 64, st));
-    DEFTET_LAUNCH(k_colaps_heads, grid_for(n), dim3(256), st, L.kx, L.ky, L.kz, L.i1, N, L.hp);
-    TRY(max_scan(L.scan, L.hp, L.hps, n, st));
-    DEFTET_LAUNCH(k_colaps_first, grid_for(n), dim3(256), st, L.hps, L.i1, N, L.first, L.isf);
-    TRY(ex_scan(L.scan, L.isf, L.nid, n, st));
-    DEFTET_LAUNCH(k_colaps_emit, grid_for(n), dim3(256), st, L.first, L.isf, L.nid, N, map_array, inverse_idx, n_out);
+    DEFTET_TRY(sort_pairs(L.sort, L.kz, L.kb, L.i0, L.i1, n, 64, st));
+    DEFTET_LAUNCH(k_gather_u64, blocks_for(n, 256), dim3(256), st, L.ky, L.i1, N, L.ka);
+    DEFTET_TRY(sort_pairs(L.sort, L.ka, L.kb, L.i1, L.i0, n, 64, st));
+    DEFTET_LAUNCH(k_gather_u64, blocks_for(n, 256), dim3(256), st, L.kx, L.i0, N, L.ka);
+    DEFTET_TRY(sort_pairs(L.sort, L.ka, L.kb, L.i0, L.i1, n, 64, st));
+    DEFTET_LAUNCH(k_colaps_heads, blocks_for(n, 256), dim3(256), st, L.kx, L.ky, L.kz, L.i1, N, L.hp);
+    DEFTET_TRY(max_scan(L.scan, L.hp, L.hps, n, st));
+    DEFTET_LAUNCH(k_colaps_first, blocks_for(n, 256), dim3(256), st, L.hps, L.i1, N, L.first, L.isf);
+    DEFTET_TRY(ex_scan(L.scan, L.isf, L.nid, n, st));
+    DEFTET_LAUNCH(k_colaps_emit, blocks_for(n, 256), dim3(256), st, L.first, L.isf, L.nid, N, map_array, inverse_idx, n_out);
     return DEFTET_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
 // N3 entry points
 // ---------------------------------------------------------------------------------------------
-static int check_i64(const void *tet, int n_point, int n_tet, void *ws)
+static int check_i64(const void *tet, int n_point, int n_tet)
 {
     DEFTET_CHECK_ARG(n_tet >= 0 && n_point >= 0, "negative size");
     DEFTET_CHECK_ARG(n_point <= 2000000000 && n_tet <= 100000000, "size too large");
     DEFTET_CHECK_ARG(n_tet == 0 || tet, "null tet list");
-    DEFTET_CHECK_ARG(n_tet == 0 || (ws && ((uintptr_t)ws & 255) == 0), "workspace null or not 256-byte aligned");
     return DEFTET_OK;
 }
 
 extern "C" int deftet_tet_edges_i64(const int64_t *tet, int64_t *edges_ex2, int64_t *tet_edge_tx6, int32_t *n_edge, int32_t *bad_flag,
                                     int n_point, int T, void *workspace, size_t wsb, void *stream_)
 {
-    TRY(check_i64(tet, n_point, T, workspace));
+    DEFTET_TRY(check_i64(tet, n_point, T));
     hipStream_t st = as_stream(stream_);
     DEFTET_CHECK_ARG(n_edge && bad_flag, "null n_edge / bad_flag");
     const PairLayout L = edges_layout(T, workspace);
-    DEFTET_CHECK_ARG(T == 0 || L.bytes <= wsb, "workspace too small");
+    if (T > 0) DEFTET_TRY(workspace_ok(__func__, workspace, wsb, L.bytes));
     DEFTET_HIP(hipMemsetAsync(bad_flag, 0, 4, st));
     if (T == 0) { DEFTET_HIP(hipMemsetAsync(n_edge, 0, 4, st)); return DEFTET_OK; }
     DEFTET_CHECK_ARG(edges_ex2 && tet_edge_tx6, "null output");
     const size_t n = (size_t)T * 6;
     const u64 np = (u64)(n_point > 0 ? n_point : 1);
-    DEFTET_LAUNCH(k_uedge_keys, grid_for(n), dim3(256), st, (const long long *)tet, T, np, L.key, L.own, bad_flag);
-    TRY(sort_pairs(L.sort, L.key, L.skey, L.own, L.sown, n, key_bits(np * np), st));
-    DEFTET_LAUNCH(k_unique_flag, grid_for(n), dim3(256), st, L.skey, (int)n, L.flag);
-    TRY(ex_scan(L.scan, L.flag, L.pos, n, st));
-    DEFTET_LAUNCH(k_uedge_emit, grid_for(n), dim3(256), st, L.skey, L.sown, L.flag, L.pos, (int)n, np, (long long *)edges_ex2,
+    DEFTET_LAUNCH(k_uedge_keys, blocks_for(n, 256), dim3(256), st, (const long long *)tet, T, np, L.key, L.own, bad_flag);
+    DEFTET_TRY(sort_pairs(L.sort, L.key, L.skey, L.own, L.sown, n, key_bits(np * np), st));
+    DEFTET_LAUNCH(k_unique_flag, blocks_for(n, 256), dim3(256), st, L.skey, (int)n, L.flag);
+    DEFTET_TRY(ex_scan(L.scan, L.flag, L.pos, n, st));
+    DEFTET_LAUNCH(k_uedge_emit, blocks_for(n, 256), dim3(256), st, L.skey, L.sown, L.flag, L.pos, (int)n, np, (long long *)edges_ex2,
                   (long long *)tet_edge_tx6, n_edge);
     return DEFTET_OK;
 }
@@ -946,28 +935,28 @@ extern "C" int deftet_subdivide_f32(const int64_t *tet, const int64_t *tet_edge_
                                     int64_t *tet_new, int32_t *n_tet_new, int n_point, int T, int n_edge, int n_feat,
                                     void *workspace, size_t wsb, void *stream_)
 {
-    TRY(check_i64(tet, n_point, T, workspace));
+    DEFTET_TRY(check_i64(tet, n_point, T));
     DEFTET_CHECK_ARG(n_edge >= 0 && n_feat >= 0, "negative size");
     DEFTET_CHECK_ARG(n_tet_new, "null n_tet_new");
     const SubdivLayout L = subdiv_layout(T, workspace);
-    DEFTET_CHECK_ARG(T == 0 || L.bytes <= wsb, "workspace too small");
+    if (T > 0) DEFTET_TRY(workspace_ok(__func__, workspace, wsb, L.bytes));
     hipStream_t st = as_stream(stream_);
     if (n_point + n_edge > 0) {
         DEFTET_CHECK_ARG(points && points_new && (n_edge == 0 || edges_ex2), "null point arrays");
-        DEFTET_LAUNCH(k_subdiv_points, grid_for((size_t)(n_point + n_edge) * 3), dim3(256), st, points, (const long long *)edges_ex2,
+        DEFTET_LAUNCH(k_subdiv_points, blocks_for((size_t)(n_point + n_edge) * 3, 256), dim3(256), st, points, (const long long *)edges_ex2,
                       n_point, n_edge, 3, points_new);
         if (n_feat > 0) {
             DEFTET_CHECK_ARG(feat && feat_new, "null feature arrays");
-            DEFTET_LAUNCH(k_subdiv_points, grid_for((size_t)(n_point + n_edge) * n_feat), dim3(256), st, feat,
+            DEFTET_LAUNCH(k_subdiv_points, blocks_for((size_t)(n_point + n_edge) * n_feat, 256), dim3(256), st, feat,
                           (const long long *)edges_ex2, n_point, n_edge, n_feat, feat_new);
         }
     }
     if (T == 0) { DEFTET_HIP(hipMemsetAsync(n_tet_new, 0, 4, st)); return DEFTET_OK; }
     DEFTET_CHECK_ARG(tet_edge_tx6 && tet_new, "null tet arrays");
-    DEFTET_LAUNCH(k_subdiv_flags, grid_for(T), dim3(256), st, subdiv_sig, T, L.keepOld, L.split);
-    TRY(ex_scan(L.scan, L.keepOld, L.posOld, (size_t)T, st));
-    TRY(ex_scan(L.scan, L.split, L.posSplit, (size_t)T, st));
-    DEFTET_LAUNCH(k_subdiv_tets, grid_for(T), dim3(256), st, (const long long *)tet, (const long long *)tet_edge_tx6, subdiv_sig,
+    DEFTET_LAUNCH(k_subdiv_flags, blocks_for(T, 256), dim3(256), st, subdiv_sig, T, L.keepOld, L.split);
+    DEFTET_TRY(ex_scan(L.scan, L.keepOld, L.posOld, (size_t)T, st));
+    DEFTET_TRY(ex_scan(L.scan, L.split, L.posSplit, (size_t)T, st));
+    DEFTET_LAUNCH(k_subdiv_tets, blocks_for(T, 256), dim3(256), st, (const long long *)tet, (const long long *)tet_edge_tx6, subdiv_sig,
                   L.posOld, L.posSplit, T, n_point, (long long *)tet_new, n_tet_new);
     return DEFTET_OK;
 }
@@ -977,17 +966,17 @@ extern "C" int deftet_point_adj_table_i64(const int32_t *pairs_nx2, int n_pairs,
 {
     DEFTET_CHECK_ARG(n_pairs >= 0 && n_point >= 0 && width >= 0, "negative size");
     DEFTET_CHECK_ARG(n_pairs == 0 || pairs_nx2, "null pairs");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && wsb >= ((size_t)n_point + 1) * 4, "workspace null, misaligned or too small");
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, ((size_t)n_point + 1) * 4));
     hipStream_t st = as_stream(stream_);
     int *rowStart = static_cast<int *>(workspace);
-    DEFTET_LAUNCH(k_adj_rowstart, grid_for((size_t)n_pairs + 1), dim3(256), st, pairs_nx2, n_pairs, n_point, rowStart);
+    DEFTET_LAUNCH(k_adj_rowstart, blocks_for((size_t)n_pairs + 1, 256), dim3(256), st, pairs_nx2, n_pairs, n_point, rowStart);
     if (width == 0) {                                             // phase A: degrees and the table width
         DEFTET_CHECK_ARG(max_degree && (n_point == 0 || adjsum_px1), "null adjsum / max_degree");
         DEFTET_HIP(hipMemsetAsync(max_degree, 0, 4, st));
-        if (n_point > 0) DEFTET_LAUNCH(k_adj_degree, grid_for(n_point), dim3(256), st, rowStart, n_point, adjsum_px1, max_degree);
+        if (n_point > 0) DEFTET_LAUNCH(k_adj_degree, blocks_for(n_point, 256), dim3(256), st, rowStart, n_point, adjsum_px1, max_degree);
     } else if (n_point > 0) {                                     // phase B: the padded table
         DEFTET_CHECK_ARG(table_pxm, "null table");
-        DEFTET_LAUNCH(k_adj_fill, grid_for((size_t)n_point * width), dim3(256), st, pairs_nx2, rowStart, n_point, width,
+        DEFTET_LAUNCH(k_adj_fill, blocks_for((size_t)n_point * width, 256), dim3(256), st, pairs_nx2, rowStart, n_point, width,
                       (long long *)table_pxm);
     }
     return DEFTET_OK;
@@ -1000,12 +989,11 @@ extern "C" int deftet_delete_tet_i64(const int64_t *tet, const float *weights_tx
     hipStream_t st = as_stream(stream_);
     if (T == 0) { DEFTET_HIP(hipMemsetAsync(n_kept, 0, 4, st)); return DEFTET_OK; }
     DEFTET_CHECK_ARG(tet && tet_kept && (K == 0 || weights_txk), "null pointer");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0, "workspace null or not 256-byte aligned");
     const DeleteLayout L = delete_layout(T, workspace);
-    DEFTET_CHECK_ARG(L.bytes <= wsb, "workspace too small");
-    DEFTET_LAUNCH(k_delete_flags, grid_for(T), dim3(256), st, weights_txk, T, K, thres, L.keep);
-    TRY(ex_scan(L.scan, L.keep, L.pos, (size_t)T, st));
-    DEFTET_LAUNCH(k_compact_tets, grid_for(T), dim3(256), st, (const long long *)tet, L.keep, L.pos, T, (long long *)tet_kept, n_kept);
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, L.bytes));
+    DEFTET_LAUNCH(k_delete_flags, blocks_for(T, 256), dim3(256), st, weights_txk, T, K, thres, L.keep);
+    DEFTET_TRY(ex_scan(L.scan, L.keep, L.pos, (size_t)T, st));
+    DEFTET_LAUNCH(k_compact_tets, blocks_for(T, 256), dim3(256), st, (const long long *)tet, L.keep, L.pos, T, (long long *)tet_kept, n_kept);
     return DEFTET_OK;
 }
 
@@ -1015,7 +1003,7 @@ extern "C" int deftet_tet_neighbour_weights_f32(const float *weights_txk, const 
     DEFTET_CHECK_ARG(T >= 0 && K >= 0, "negative size");
     if (T == 0 || K == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(weights_txk && nei_tx4 && out_tx4k, "null pointer");
-    DEFTET_LAUNCH(k_neighbour_weights, grid_for((size_t)T * 4 * K), dim3(256), as_stream(stream_), weights_txk,
+    DEFTET_LAUNCH(k_neighbour_weights, blocks_for((size_t)T * 4 * K, 256), dim3(256), as_stream(stream_), weights_txk,
                   (const long long *)nei_tx4, T, K, out_tx4k);
     return DEFTET_OK;
 }
@@ -1043,7 +1031,7 @@ extern "C" int deftet_tet_adj_share_host(int *tet_list, int *face_edge_p, int *n
     HOST_PROLOGUE(n_tet)
     DevBuf d_out, d_n;
     if (d_out.alloc((size_t)n_tet * 8 * 12) || d_n.alloc(4)) return set_error(DEFTET_ELAUNCH, "hipMalloc failed");
-    TRY(deftet_tet_adj_share_i32((const int32_t *)d_tet.p, (int32_t *)d_out.p, (int32_t *)d_n.p, n_point, n_tet, d_ws.p, wsb, nullptr));
+    DEFTET_TRY(deftet_tet_adj_share_i32((const int32_t *)d_tet.p, (int32_t *)d_out.p, (int32_t *)d_n.p, n_point, n_tet, d_ws.p, wsb, nullptr));
     DEFTET_HIP(hipDeviceSynchronize());
     DEFTET_HIP(hipMemcpy(n_face_edge_p, d_n.p, 4, hipMemcpyDeviceToHost));
     DEFTET_HIP(hipMemcpy(face_edge_p, d_out.p, (size_t)n_face_edge_p[0] * 24, hipMemcpyDeviceToHost));
@@ -1056,8 +1044,8 @@ extern "C" int deftet_tet_face_adj_host(int *tet_list, int *face_edge_p, int *n_
     const long long cap = (long long)n_tet * 4 * 50;             // interface.py:27-28
     DevBuf d_out, d_n;
     if (d_out.alloc((size_t)cap * 8) || d_n.alloc(8)) return set_error(DEFTET_ELAUNCH, "hipMalloc failed");
-    TRY(deftet_tet_face_adj_i32((const int32_t *)d_tet.p, (int32_t *)d_out.p, cap, (long long *)d_n.p, n_point, n_tet, 1,
-                                d_ws.p, wsb, nullptr));
+    DEFTET_TRY(deftet_tet_face_adj_i32((const int32_t *)d_tet.p, (int32_t *)d_out.p, cap, (long long *)d_n.p, n_point, n_tet, 1,
+                                       d_ws.p, wsb, nullptr));
     DEFTET_HIP(hipDeviceSynchronize());
     long long cnt = 0;
     DEFTET_HIP(hipMemcpy(&cnt, d_n.p, 8, hipMemcpyDeviceToHost));
@@ -1072,7 +1060,7 @@ extern "C" int deftet_tet_point_adj_host(int *tet_list, int *edge_p, int *n_edge
     HOST_PROLOGUE(n_tet)
     DevBuf d_out, d_n;
     if (d_out.alloc((size_t)n_tet * 12 * 8) || d_n.alloc(4)) return set_error(DEFTET_ELAUNCH, "hipMalloc failed");
-    TRY(deftet_tet_point_adj_i32((const int32_t *)d_tet.p, (int32_t *)d_out.p, (int32_t *)d_n.p, n_point, n_tet, d_ws.p, wsb, nullptr));
+    DEFTET_TRY(deftet_tet_point_adj_i32((const int32_t *)d_tet.p, (int32_t *)d_out.p, (int32_t *)d_n.p, n_point, n_tet, d_ws.p, wsb, nullptr));
     DEFTET_HIP(hipDeviceSynchronize());
     DEFTET_HIP(hipMemcpy(n_edge, d_n.p, 4, hipMemcpyDeviceToHost));
     DEFTET_HIP(hipMemcpy(edge_p, d_out.p, (size_t)n_edge[0] * 8, hipMemcpyDeviceToHost));
@@ -1088,7 +1076,7 @@ extern "C" int deftet_colaps_v_host(float *point_p, int *map_array_p, int *inver
         d_n.alloc(4) || d_ws.alloc(wsb))
         return set_error(DEFTET_ELAUNCH, "hipMalloc failed");
     DEFTET_HIP(hipMemcpy(d_pts.p, point_p, (size_t)n_point * 12, hipMemcpyHostToDevice));
-    TRY(deftet_colaps_v_f32((const float *)d_pts.p, (int32_t *)d_map.p, (int32_t *)d_inv.p, (int32_t *)d_n.p, n_point, d_ws.p, wsb, nullptr));
+    DEFTET_TRY(deftet_colaps_v_f32((const float *)d_pts.p, (int32_t *)d_map.p, (int32_t *)d_inv.p, (int32_t *)d_n.p, n_point, d_ws.p, wsb, nullptr));
     DEFTET_HIP(hipDeviceSynchronize());
     DEFTET_HIP(hipMemcpy(n_colaps_v_p, d_n.p, 4, hipMemcpyDeviceToHost));
     DEFTET_HIP(hipMemcpy(map_array_p, d_map.p, (size_t)n_point * 4, hipMemcpyDeviceToHost));

@@ -51,10 +51,9 @@ inline void take_sort(Arena &A, size_t n, SortBufs &s)
 // keys (already written) -> perm (the point ids b N + p in key order, stable) and seg
 inline int sort_and_segment(const SortBufs &s, int32_t *perm, int32_t *seg, size_t n, unsigned n_keys, hipStream_t st)
 {
-    const int rc = prims::radix_sort_from<unsigned, unsigned>(prims::PtrLoad<unsigned>{s.keys}, s.sorted, prims::IotaLoad{}, (unsigned *)perm,
-                                                               n, key_bits(n_keys), s.tmp, s.tmp_bytes, st);
-    if (rc != DEFTET_OK) return rc;
-    DEFTET_LAUNCH(k_pv_segments, dim3((n_keys + 1 + kPvBlock - 1) / kPvBlock), dim3(kPvBlock), st, (const unsigned *)s.sorted, (unsigned)n,
+    DEFTET_TRY(prims::radix_sort_from<unsigned, unsigned>(prims::PtrLoad<unsigned>{s.keys}, s.sorted, prims::IotaLoad{}, (unsigned *)perm,
+                                                          n, key_bits(n_keys), s.tmp, s.tmp_bytes, st));
+    DEFTET_LAUNCH(k_pv_segments, dim3(blocks_for(n_keys + 1, kPvBlock)), dim3(kPvBlock), st, (const unsigned *)s.sorted, (unsigned)n,
                   n_keys, seg);
     return DEFTET_OK;
 }
@@ -78,7 +77,6 @@ struct CellWs {
     int32_t *perm, *seg;
     float *part;
     size_t part_bytes, bytes;
-    bool fits(const void *ws, size_t ws_bytes) const { return ws && ((uintptr_t)ws & 255) == 0 && bytes <= ws_bytes; }
 };
 template <int NC>
 inline CellWs cell_layout(size_t n, size_t n_keys, size_t budget, bool own_perm_seg, bool overlay, void *ws)
@@ -174,12 +172,12 @@ inline int cell_gather_bwd(const CellWs &L, Keep keep, const float *gout, const 
     size_t fit = L.part_bytes / ((size_t)B * n_cells * NC * sizeof(float));                 // >= 1 by the layout
     if (fit > 65535) fit = 65535;
     const int c_chunk = (int)fit < C ? (int)fit : C;
-    const unsigned gCell = (unsigned)((n_cells + kPvBlock - 1) / kPvBlock);
+    const unsigned gCell = blocks_for(n_cells, kPvBlock);
     for (int c0 = 0; c0 < C; c0 += c_chunk) {
         const int cc = C - c0 < c_chunk ? C - c0 : c_chunk;
         DEFTET_LAUNCH((k_cell_partials<NC, Keep>), dim3(gCell, (unsigned)cc, (unsigned)B), dim3(kPvBlock), st, gout, perm, seg, wsorted, L.part,
                       keep, B, n_cells, N, c_off + c0, C_total, c_chunk);
-        if (int rc = from_partials((const float *)L.part, c0, c_chunk, cc)) return rc;
+        DEFTET_TRY(from_partials((const float *)L.part, c0, c_chunk, cc));
     }
     return DEFTET_OK;
 }

@@ -85,7 +85,7 @@ extern "C" int deftet_face_samples_f32(const float *tri, const float *r, float *
     if (total == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(tri && r && samples, "null pointer");
     DEFTET_CHECK_ARG(total * 3 < (1LL << 40), "too many samples");
-    DEFTET_LAUNCH(k_face_samples, dim3((unsigned)((total + 255) / 256)), dim3(256), as_stream(stream_), tri, r, samples, K, total);
+    DEFTET_LAUNCH(k_face_samples, dim3(blocks_for(total, 256)), dim3(256), as_stream(stream_), tri, r, samples, K, total);
     return DEFTET_OK;
 }
 
@@ -95,7 +95,7 @@ extern "C" int deftet_chamfer_fwd_f32(const float *samples, const float *gt, con
     DEFTET_CHECK_ARG(B >= 0 && N >= 0 && M >= 1 && B <= 65535, "bad size");
     if (B == 0 || N == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(samples && gt && idx && n_valid && d, "null pointer");
-    DEFTET_LAUNCH(k_chamfer_fwd, dim3((N + 255) / 256, B), dim3(256), as_stream(stream_), samples, gt, idx, n_valid, d, N, M);
+    DEFTET_LAUNCH(k_chamfer_fwd, dim3(blocks_for(N, 256), B), dim3(256), as_stream(stream_), samples, gt, idx, n_valid, d, N, M);
     return DEFTET_OK;
 }
 
@@ -105,7 +105,7 @@ extern "C" int deftet_chamfer_bwd_f32(const float *samples, const float *gt, con
     DEFTET_CHECK_ARG(B >= 0 && F >= 0 && K >= 1 && M >= 1 && B <= 65535, "bad size");
     if (B == 0 || F == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(samples && gt && idx && n_valid && d && r && gscale && grad_tri, "null pointer");
-    DEFTET_LAUNCH(k_chamfer_bwd, dim3((F + 255) / 256, B), dim3(256), as_stream(stream_), samples, gt, idx, n_valid, d, r, gscale, grad_tri, F, K,
+    DEFTET_LAUNCH(k_chamfer_bwd, dim3(blocks_for(F, 256), B), dim3(256), as_stream(stream_), samples, gt, idx, n_valid, d, r, gscale, grad_tri, F, K,
                   M, (long long)B * F * K);
     return DEFTET_OK;
 }

@@ -333,16 +333,15 @@ static int check_sign_run(const float *verts, const int64_t *faces, const int *v
     DEFTET_CHECK_ARG(points && inside && bad_flag, "null pointer");
     hipStream_t st = as_stream(stream_);
     DEFTET_HIP(hipMemsetAsync(bad_flag, 0, 4, st));
-    const dim3 blk(256), gn((N + 255) / 256, B);
+    const dim3 blk(256), gn(blocks_for(N, 256), B);
     if (F == 0 || nRec == 0) {                                       // no surface: everything is outside
         DEFTET_HIP(hipMemsetAsync(inside, 0, (size_t)B * N, st));
         if (count) DEFTET_HIP(hipMemsetAsync(count, 0, (size_t)B * N * 4, st));
         return DEFTET_OK;
     }
     DEFTET_CHECK_ARG(verts && faces, "null mesh");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0, "workspace null or not 256-byte aligned");
     Layout L = make_layout(B, F, nRec, algo, workspace, workspace_bytes);
-    DEFTET_CHECK_ARG(L.bytes <= workspace_bytes, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
+    DEFTET_TRY(workspace_ok("deftet_check_sign*", workspace, workspace_bytes, L.bytes));
     int pb = (F + 255) / 256;
     if (pb > kParts) pb = kParts;
     if (algo == 1) {
@@ -355,13 +354,10 @@ static int check_sign_run(const float *verts, const int64_t *faces, const int *v
     DEFTET_HIP(hipMemsetAsync(L.counters, 0, (size_t)((char *)L.cellStart - (char *)L.counters), st));   // counters, cellCount, cellFill
     DEFTET_LAUNCH(k_prep, dim3(pb, B), blk, st, verts, (const long long *)faces, V, F, L.rec, L.kind, L.box, L.part, L.counters, L.irreg,
                   bad_flag, vOff, fOff);
-    const dim3 gf((F + 255) / 256, B);
+    const dim3 gf(blocks_for(F, 256), B);
     DEFTET_LAUNCH(k_bin<0>, gf, blk, st, (const signed char *)L.kind, (const float4 *)L.box, (const float *)L.part, pb, F, L.G, L.dom,
                   L.cellCount, (const int *)nullptr, (int *)nullptr, (int *)nullptr, L.counters, L.irreg, L.kind, fOff);
-    {
-        const int rc = prims::scan<int, prims::Plus, true>(L.cellCount, L.cellStart, nc, 0, prims::Plus(), L.scanTmp, L.scanTmpBytes, st);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(prims::scan<int, prims::Plus, true>(L.cellCount, L.cellStart, nc, 0, prims::Plus(), L.scanTmp, L.scanTmpBytes, st));
     DEFTET_LAUNCH(k_bin<1>, gf, blk, st, (const signed char *)L.kind, (const float4 *)L.box, (const float *)L.part, pb, F, L.G, L.dom,
                   L.cellCount, (const int *)L.cellStart, L.cellFill, L.list, L.counters, L.irreg, L.kind, fOff);
     DEFTET_LAUNCH(k_query, gn, blk, st, points, (const float4 *)L.rec, N, F, L.G, (const float *)L.dom, (const int *)L.cellStart,

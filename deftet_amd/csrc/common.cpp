@@ -23,6 +23,12 @@ int set_error(int code, const char *fmt, ...)
     return code;
 }
 
+int workspace_refused(const char *who, const void *ws, size_t got, size_t need, size_t align)
+{
+    return set_error(DEFTET_EINVAL, "%s: workspace null, misaligned or too small: need %zu bytes, got %zu at %p (%zu-byte alignment)", who,
+                     need, got, ws, align);
+}
+
 // ---- per-kernel event timing -------------------------------------------------------
 namespace {
 struct Prof {

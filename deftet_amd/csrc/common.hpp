@@ -20,6 +20,14 @@ inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s);
         if (!(cond)) return deftet::set_error(DEFTET_EINVAL, __VA_ARGS__); \
     } while (0)
 
+// status propagation: the one way a host function hands a callee's refusal or launch error up (variadic: a template
+// argument list may bring its own commas)
+#define DEFTET_TRY(...)                                               \
+    do {                                                              \
+        const int rc_ = (__VA_ARGS__);                                \
+        if (rc_ != DEFTET_OK) return rc_;                             \
+    } while (0)
+
 #define DEFTET_HIP(call)                                                                   \
     do {                                                                                    \
         hipError_t e_ = (call);                                                             \
@@ -62,6 +70,15 @@ void prof_end(hipStream_t st);
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }   // a: a power of two
+// workgroups of `block` items that cover n items (host side: launch arguments)
+inline unsigned blocks_for(size_t n, size_t block) { return (unsigned)((n + block - 1) / block); }
+// The workspace acceptance rule ("Workspaces"): the caller's buffer is present, `align`-byte aligned and at least
+// `need` bytes long.  DEFTET_OK, or DEFTET_EINVAL with the one wording (common.cpp), which names the entry and both byte counts.
+int workspace_refused(const char *who, const void *ws, size_t got, size_t need, size_t align);
+inline int workspace_ok(const char *who, const void *ws, size_t got, size_t need, size_t align = 256)
+{
+    return ws && aligned(ws, align) && need <= got ? DEFTET_OK : workspace_refused(who, ws, got, need, align);
+}
 __device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7FC00000); }
 __device__ __forceinline__ void cross3(const float *a, const float *b, float *o)
 {

@@ -37,8 +37,6 @@ constexpr int kMaxRes = 1024;
 constexpr unsigned kMinRasterBlocks = 1024;   // four workgroups (16 waves) on each of 256 compute units
 
 static inline int words_of(int R) { return (R + 31) >> 5; }
-static inline unsigned grid_for(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
 // ---------------------------------------------------------------------------- voxelization
 // os[b] = (origin x, y, z, scale): the given ones, or the minimum of the vertices / their largest extent
 __global__ __launch_bounds__(kThreads) void k_vx_frame(const float *__restrict__ verts, int V, const float *__restrict__ origin,
@@ -508,8 +506,7 @@ static int check_grid(int B, int R)
 // the face table is int32: a shape has at most 3 R R (R + 1) lattice faces, two triangles each
 static int check_surface(int B, int R)
 {
-    const int rc = check_grid(B, R);
-    if (rc != DEFTET_OK) return rc;
+    DEFTET_TRY(check_grid(B, R));
     DEFTET_CHECK_ARG((long long)B * 6 * R * R * (R + 1) < 2147483647LL, "n_batch * 6 * resolution^2 * (resolution + 1) triangles at most do not fit 31 bits");
     return DEFTET_OK;
 }
@@ -592,10 +589,7 @@ extern "C" int deftet_mesh_voxelize_f32(const float *verts, const int64_t *faces
                                         int F, int R, uint32_t *bits, uint8_t *vox, int32_t *stats, void *workspace, size_t wsb,
                                         void *stream_)
 {
-    {
-        const int rc = check_grid(B, R);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(check_grid(B, R));
     DEFTET_CHECK_ARG(V >= 0 && F >= 0, "n_vertex=%d, n_face=%d: neither may be negative", V, F);
     DEFTET_CHECK_ARG((long long)B * F < 2147483647LL, "n_batch * n_face does not fit 31 bits");
     {
@@ -609,8 +603,7 @@ extern "C" int deftet_mesh_voxelize_f32(const float *verts, const int64_t *faces
     DEFTET_CHECK_ARG(F == 0 || (verts && faces && V > 0), "null pointer: verts / faces");
     DEFTET_CHECK_ARG(V > 0 || (origin && scale), "no vertices: origin and scale cannot be derived");
     const VoxWs S = vox_carve(workspace, B, F);
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && S.total <= wsb,
-                     "workspace null, misaligned or smaller than deftet_mesh_voxelize_workspace_bytes");
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, S.total));
     hipStream_t st = as_stream(stream_);
     const int W = words_of(R);
     const size_t nword = (size_t)B * R * R * W, n = S.n;
@@ -618,12 +611,9 @@ extern "C" int deftet_mesh_voxelize_f32(const float *verts, const int64_t *faces
     DEFTET_HIP(hipMemsetAsync(stats, 0, 16, st));
     if (F > 0) {
         DEFTET_LAUNCH(k_vx_frame, dim3(B), dim3(kThreads), st, verts, V, origin, scale, S.os);
-        DEFTET_LAUNCH(k_vx_count, dim3(grid_for(n)), dim3(kThreads), st, verts, (const long long *)faces, (const float4 *)S.os, B, V, F, R, S.tpos,
+        DEFTET_LAUNCH(k_vx_count, dim3(blocks_for(n, kThreads)), dim3(kThreads), st, verts, (const long long *)faces, (const float4 *)S.os, B, V, F, R, S.tpos,
                       (int *)stats);
-        {
-            const int rc = prims::scan<int, prims::Plus, true>(S.tpos, S.tpos, n, 0, prims::Plus(), S.tmp, S.tmp_bytes, st);
-            if (rc != DEFTET_OK) return rc;
-        }
+        DEFTET_TRY(prims::scan<int, prims::Plus, true>(S.tpos, S.tpos, n, 0, prims::Plus(), S.tmp, S.tmp_bytes, st));
         // the number of tasks stays on the device, so the grid cannot follow it: one wave per triangle, but never fewer than
         // kMinRasterBlocks workgroups (a few large triangles are many tasks; a wave without a task reads the total and leaves)
         // and never more than a full machine of waves; the waves stride over the tasks
@@ -632,55 +622,43 @@ extern "C" int deftet_mesh_voxelize_f32(const float *verts, const int64_t *faces
         DEFTET_LAUNCH(k_vx_raster, dim3(nblk), dim3(kThreads), st, verts, (const long long *)faces, (const float4 *)S.os, B, V, F, R, W,
                       (const int *)S.tpos, (unsigned *)bits, (int *)stats);
     }
-    if (vox) DEFTET_LAUNCH(k_unpack, dim3(grid_for((size_t)B * R * R * R)), dim3(kThreads), st, (const unsigned *)bits, (size_t)B * R * R * R, R, W, vox);
+    if (vox) DEFTET_LAUNCH(k_unpack, dim3(blocks_for((size_t)B * R * R * R, kThreads)), dim3(kThreads), st, (const unsigned *)bits, (size_t)B * R * R * R, R, W, vox);
     return DEFTET_OK;
 }
 
 extern "C" int deftet_voxel_pack_u8(const uint8_t *vox, int B, int R, uint32_t *bits, void *stream_)
 {
-    {
-        const int rc = check_grid(B, R);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(check_grid(B, R));
     DEFTET_CHECK_ARG(vox && bits, "null pointer: vox / bits");
     const int W = words_of(R);
     const size_t nword = (size_t)B * R * R * W;
-    DEFTET_LAUNCH(k_pack, dim3(grid_for(nword)), dim3(kThreads), as_stream(stream_), vox, nword, R, W, (unsigned *)bits);
+    DEFTET_LAUNCH(k_pack, dim3(blocks_for(nword, kThreads)), dim3(kThreads), as_stream(stream_), vox, nword, R, W, (unsigned *)bits);
     return DEFTET_OK;
 }
 
 extern "C" int deftet_voxel_unpack_u8(const uint32_t *bits, int B, int R, uint8_t *vox, void *stream_)
 {
-    {
-        const int rc = check_grid(B, R);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(check_grid(B, R));
     DEFTET_CHECK_ARG(vox && bits, "null pointer: vox / bits");
     const size_t n = (size_t)B * R * R * R;
-    DEFTET_LAUNCH(k_unpack, dim3(grid_for(n)), dim3(kThreads), as_stream(stream_), (const unsigned *)bits, n, R, words_of(R), vox);
+    DEFTET_LAUNCH(k_unpack, dim3(blocks_for(n, kThreads)), dim3(kThreads), as_stream(stream_), (const unsigned *)bits, n, R, words_of(R), vox);
     return DEFTET_OK;
 }
 
 extern "C" int deftet_extract_odms_u8(const uint8_t *vox, int B, int R, int32_t *odms, void *stream_)
 {
-    {
-        const int rc = check_grid(B, R);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(check_grid(B, R));
     DEFTET_CHECK_ARG(vox && odms, "null pointer: vox / odms");
-    DEFTET_LAUNCH(k_odm_extract, dim3(grid_for((size_t)B * 6 * R * R)), dim3(kThreads), as_stream(stream_), vox, B, R, (int *)odms);
+    DEFTET_LAUNCH(k_odm_extract, dim3(blocks_for((size_t)B * 6 * R * R, kThreads)), dim3(kThreads), as_stream(stream_), vox, B, R, (int *)odms);
     return DEFTET_OK;
 }
 
 extern "C" int deftet_project_odms_i32(const int32_t *odms, const uint8_t *vox_in, int B, int R, int votes, uint8_t *out, void *stream_)
 {
-    {
-        const int rc = check_grid(B, R);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(check_grid(B, R));
     DEFTET_CHECK_ARG(odms && out, "null pointer: odms / out");
     DEFTET_CHECK_ARG(votes >= 1 && votes <= 6, "votes=%d outside 1..6", votes);
-    DEFTET_LAUNCH(k_odm_project, dim3(grid_for((size_t)B * R * R * R)), dim3(kThreads), as_stream(stream_), (const int *)odms, vox_in, B, R, votes,
+    DEFTET_LAUNCH(k_odm_project, dim3(blocks_for((size_t)B * R * R * R, kThreads)), dim3(kThreads), as_stream(stream_), (const int *)odms, vox_in, B, R, votes,
                   out);
     return DEFTET_OK;
 }
@@ -693,18 +671,14 @@ extern "C" size_t deftet_voxel_fill_workspace_bytes(int B, int R)
 
 extern "C" int deftet_voxel_fill_b32(const uint32_t *bits, int B, int R, uint32_t *out, void *workspace, size_t wsb, void *stream_)
 {
-    {
-        const int rc = check_grid(B, R);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(check_grid(B, R));
     DEFTET_CHECK_ARG(bits && out && bits != out, "null pointer: bits / out, or out aliases bits");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && wsb >= deftet_voxel_fill_workspace_bytes(B, R),
-                     "workspace null, misaligned or smaller than deftet_voxel_fill_workspace_bytes");
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, deftet_voxel_fill_workspace_bytes(B, R)));
     hipStream_t st = as_stream(stream_);
     const int W = words_of(R);
-    DEFTET_LAUNCH(k_fill_span_k, dim3(grid_for((size_t)B * R * R)), dim3(kThreads), st, (const unsigned *)bits, (size_t)B * R * R, W, (unsigned *)out);
+    DEFTET_LAUNCH(k_fill_span_k, dim3(blocks_for((size_t)B * R * R, kThreads)), dim3(kThreads), st, (const unsigned *)bits, (size_t)B * R * R, W, (unsigned *)out);
     for (int axis = 0; axis < 2; ++axis)
-        DEFTET_LAUNCH(k_fill_span_axis, dim3(grid_for((size_t)B * R * W)), dim3(kThreads), st, (const unsigned *)bits, B, R, W, axis,
+        DEFTET_LAUNCH(k_fill_span_axis, dim3(blocks_for((size_t)B * R * W, kThreads)), dim3(kThreads), st, (const unsigned *)bits, B, R, W, axis,
                       (unsigned *)workspace, (unsigned *)out);
     return DEFTET_OK;
 }
@@ -717,23 +691,17 @@ extern "C" size_t deftet_voxel_surface_workspace_bytes(int B, int R)
 
 extern "C" int deftet_voxel_surface_count_b32(const uint32_t *bits, int B, int R, int32_t *offsets, void *workspace, size_t wsb, void *stream_)
 {
-    {
-        const int rc = check_surface(B, R);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(check_surface(B, R));
     DEFTET_CHECK_ARG(bits && offsets, "null pointer: bits / offsets");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && wsb >= deftet_voxel_surface_workspace_bytes(B, R),
-                     "workspace null, misaligned or smaller than deftet_voxel_surface_workspace_bytes");
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, deftet_voxel_surface_workspace_bytes(B, R)));
     hipStream_t st = as_stream(stream_);
     const SurfWs S = surf_carve(workspace, B, R);
     const Grid G{(const unsigned *)bits, B, R, words_of(R), words_of(R + 1)};
     const size_t nf = (size_t)B * R * R * G.W + 1, nv = (size_t)B * (R + 1) * (R + 1) * G.Wc + 1;
-    DEFTET_LAUNCH(k_sf_count_faces, dim3(grid_for(nf)), dim3(kThreads), st, G, S.fpos);
-    DEFTET_LAUNCH(k_sf_count_verts, dim3(grid_for(nv)), dim3(kThreads), st, G, S.used, S.vpos);
-    int rc = prims::scan<int, prims::Plus, true>(S.fpos, S.fpos, nf, 0, prims::Plus(), S.tmp, S.tmp_bytes, st);
-    if (rc != DEFTET_OK) return rc;
-    rc = prims::scan<int, prims::Plus, true>(S.vpos, S.vpos, nv, 0, prims::Plus(), S.tmp, S.tmp_bytes, st);
-    if (rc != DEFTET_OK) return rc;
+    DEFTET_LAUNCH(k_sf_count_faces, dim3(blocks_for(nf, kThreads)), dim3(kThreads), st, G, S.fpos);
+    DEFTET_LAUNCH(k_sf_count_verts, dim3(blocks_for(nv, kThreads)), dim3(kThreads), st, G, S.used, S.vpos);
+    DEFTET_TRY(prims::scan<int, prims::Plus, true>(S.fpos, S.fpos, nf, 0, prims::Plus(), S.tmp, S.tmp_bytes, st));
+    DEFTET_TRY(prims::scan<int, prims::Plus, true>(S.vpos, S.vpos, nv, 0, prims::Plus(), S.tmp, S.tmp_bytes, st));
     DEFTET_LAUNCH(k_sf_offsets, dim3((B + 256) / 256), dim3(256), st, (const int *)S.fpos, (const int *)S.vpos, G, (int *)offsets);
     return DEFTET_OK;
 }
@@ -741,24 +709,20 @@ extern "C" int deftet_voxel_surface_count_b32(const uint32_t *bits, int B, int R
 extern "C" int deftet_voxel_surface_fill_b32(const uint32_t *bits, int B, int R, long long cap_faces, long long cap_verts, float *verts,
                                              int64_t *faces, void *workspace, size_t wsb, void *stream_)
 {
-    {
-        const int rc = check_surface(B, R);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(check_surface(B, R));
     DEFTET_CHECK_ARG(bits, "null pointer: bits");
     DEFTET_CHECK_ARG(cap_faces >= 0 && cap_verts >= 0, "negative capacity");
     DEFTET_CHECK_ARG((cap_faces == 0 || faces) && (cap_verts == 0 || verts), "null pointer: verts / faces");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && wsb >= deftet_voxel_surface_workspace_bytes(B, R),
-                     "workspace null, misaligned or smaller than deftet_voxel_surface_workspace_bytes");
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, deftet_voxel_surface_workspace_bytes(B, R)));
     hipStream_t st = as_stream(stream_);
     const SurfWs S = surf_carve(workspace, B, R);
     const Grid G{(const unsigned *)bits, B, R, words_of(R), words_of(R + 1)};
     const size_t nf = (size_t)B * R * R * G.W, nv = (size_t)B * (R + 1) * (R + 1) * G.Wc;
     if (cap_faces > 0)
-        DEFTET_LAUNCH(k_sf_fill_faces, dim3(grid_for(nf)), dim3(kThreads), st, G, (const int *)S.fpos, (const unsigned *)S.used, (const int *)S.vpos,
+        DEFTET_LAUNCH(k_sf_fill_faces, dim3(blocks_for(nf, kThreads)), dim3(kThreads), st, G, (const int *)S.fpos, (const unsigned *)S.used, (const int *)S.vpos,
                       cap_faces, (long long *)faces);
     if (cap_verts > 0)
-        DEFTET_LAUNCH(k_sf_fill_verts, dim3(grid_for(nv)), dim3(kThreads), st, G, (const unsigned *)S.used, (const int *)S.vpos, cap_verts, verts);
+        DEFTET_LAUNCH(k_sf_fill_verts, dim3(blocks_for(nv, kThreads)), dim3(kThreads), st, G, (const unsigned *)S.used, (const int *)S.vpos, cap_verts, verts);
     return DEFTET_OK;
 }
 
@@ -776,20 +740,17 @@ extern "C" int deftet_face_edges_i32(const int64_t *faces, int F, int V, int32_t
     hipStream_t st = as_stream(stream_);
     const EdgeWs S = edge_carve(workspace, F);
     DEFTET_CHECK_ARG(F == 0 || (faces && pairs), "null pointer: faces / pairs");
-    DEFTET_CHECK_ARG(F == 0 || (workspace && ((uintptr_t)workspace & 255) == 0 && S.total <= wsb),
-                     "workspace null, misaligned or smaller than deftet_face_edges_workspace_bytes");
+    if (F > 0) DEFTET_TRY(workspace_ok(__func__, workspace, wsb, S.total));
     DEFTET_HIP(hipMemsetAsync(n_out, 0, 8, st));
     if (F == 0) return DEFTET_OK;
     const size_t n = S.n;
     int bits = 1;
     while (bits < 64 && ((unsigned long long)V * (unsigned long long)V) >> bits) ++bits;       // the sentinel V^2 must sort last
-    DEFTET_LAUNCH(k_edge_keys, dim3(grid_for(n)), dim3(kThreads), st, (const long long *)faces, (long long)n, V, S.k0, (int *)n_out);
-    int rc = prims::radix_sort_keys<unsigned long long>(S.k0, S.k1, n, bits, S.sort_tmp, S.sort_bytes, st);
-    if (rc != DEFTET_OK) return rc;
-    DEFTET_LAUNCH(k_edge_flag, dim3(grid_for(n + 1)), dim3(kThreads), st, (const unsigned long long *)S.k1, (long long)n, V, S.pos);
-    rc = prims::scan<int, prims::Plus, true>(S.pos, S.pos, n + 1, 0, prims::Plus(), S.scan_tmp, S.scan_bytes, st);
-    if (rc != DEFTET_OK) return rc;
-    DEFTET_LAUNCH(k_edge_compact, dim3(grid_for(n + 1)), dim3(kThreads), st, (const unsigned long long *)S.k1, (long long)n, V, (const int *)S.pos,
+    DEFTET_LAUNCH(k_edge_keys, dim3(blocks_for(n, kThreads)), dim3(kThreads), st, (const long long *)faces, (long long)n, V, S.k0, (int *)n_out);
+    DEFTET_TRY(prims::radix_sort_keys<unsigned long long>(S.k0, S.k1, n, bits, S.sort_tmp, S.sort_bytes, st));
+    DEFTET_LAUNCH(k_edge_flag, dim3(blocks_for(n + 1, kThreads)), dim3(kThreads), st, (const unsigned long long *)S.k1, (long long)n, V, S.pos);
+    DEFTET_TRY(prims::scan<int, prims::Plus, true>(S.pos, S.pos, n + 1, 0, prims::Plus(), S.scan_tmp, S.scan_bytes, st));
+    DEFTET_LAUNCH(k_edge_compact, dim3(blocks_for(n + 1, kThreads)), dim3(kThreads), st, (const unsigned long long *)S.k1, (long long)n, V, (const int *)S.pos,
                   (int *)pairs, (int *)n_out);
     return DEFTET_OK;
 }

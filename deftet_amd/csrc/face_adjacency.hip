@@ -383,12 +383,12 @@ extern "C" int deftet_face_edge_adj_ragged_f32(const float *face, float *adj, in
     if (!workspace || max_nei > kMaxNeiFast) {
         for (int b = 0; b < B; ++b)
             if (n_face_host[b] > 0)
-                DEFTET_LAUNCH(k_face_edge_adj, dim3((n_face_host[b] + 255) / 256), dim3(256), st, face + (size_t)b * F_max * 9,
+                DEFTET_LAUNCH(k_face_edge_adj, dim3(blocks_for(n_face_host[b], 256)), dim3(256), st, face + (size_t)b * F_max * 9,
                               adj + (size_t)b * F_max * max_nei, n_face_host[b], max_nei);
         return DEFTET_OK;
     }
     const A8Layout L = a8_layout(B, F_max, workspace);
-    DEFTET_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && L.bytes <= wsb, "workspace misaligned or too small");
+    DEFTET_TRY(workspace_ok("deftet_face_edge_adj*", workspace, wsb, L.bytes));
     const u32 mask = a8_table_mask(F_max);
     DEFTET_HIP(hipMemsetAsync(L.head, 0xFF, (size_t)B * (mask + 1) * 4, st));   // -1 = empty chain
     for (int b0 = 0; b0 < B; b0 += kA8Shapes) {
@@ -398,9 +398,9 @@ extern "C" int deftet_face_edge_adj_ragged_f32(const float *face, float *adj, in
         for (int i = 0; i < nb; ++i) { cnt.n[i] = n_face_host[b0 + i]; fmax = std::max(fmax, cnt.n[i]); }
         if (fmax == 0) continue;
         const float *fb = face + (size_t)b0 * F_max * 9;
-        DEFTET_LAUNCH(k_edge_insert, dim3((fmax * 3 + 255) / 256, nb), dim3(256), st, fb, F_max, cnt, mask, L.head + (size_t)b0 * (mask + 1),
+        DEFTET_LAUNCH(k_edge_insert, dim3(blocks_for(fmax * 3, 256), nb), dim3(256), st, fb, F_max, cnt, mask, L.head + (size_t)b0 * (mask + 1),
                       L.next + (size_t)b0 * F_max * 3);
-        DEFTET_LAUNCH(k_face_neighbors, dim3((fmax + 255) / 256, nb), dim3(256), st, fb, F_max, cnt, mask,
+        DEFTET_LAUNCH(k_face_neighbors, dim3(blocks_for(fmax, 256), nb), dim3(256), st, fb, F_max, cnt, mask,
                       (const int *)(L.head + (size_t)b0 * (mask + 1)), (const int *)(L.next + (size_t)b0 * F_max * 3),
                       adj + (size_t)b0 * F_max * max_nei, max_nei);
     }
@@ -438,8 +438,8 @@ extern "C" int deftet_normal_consistency_bwd_f32(const float *tri, const float *
     DEFTET_CHECK_ARG(tri && n_face && nrm && count && grad_loss && grad_tri && acc && (max_nei == 0 || adj), "null pointer");
     hipStream_t st = as_stream(stream_);
     DEFTET_HIP(hipMemsetAsync(acc, 0, (size_t)B * F_max * 3 * sizeof(float), st));
-    DEFTET_LAUNCH(k_normal_consistency_bwd_scatter, dim3((F_max + 255) / 256, B), dim3(256), st, adj, n_face, nrm, acc, F_max, max_nei);
-    DEFTET_LAUNCH(k_normal_consistency_bwd_final, dim3((F_max + 255) / 256, B), dim3(256), st, tri, n_face, count, grad_loss, (const float *)acc,
+    DEFTET_LAUNCH(k_normal_consistency_bwd_scatter, dim3(blocks_for(F_max, 256), B), dim3(256), st, adj, n_face, nrm, acc, F_max, max_nei);
+    DEFTET_LAUNCH(k_normal_consistency_bwd_final, dim3(blocks_for(F_max, 256), B), dim3(256), st, tri, n_face, count, grad_loss, (const float *)acc,
                   grad_tri, F_max);
     return DEFTET_OK;
 }

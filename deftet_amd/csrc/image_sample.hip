@@ -163,7 +163,7 @@ int deftet_image_sample_fwd_f32(const float *map, const float *uv, const float *
                                 int channel_offset, int n_channel_total, int border, int align_corners, void *stream)
 {
     const int B = n_batch, C = n_channel, N = n_point, H = height, W = width, G = global_features ? n_global : 0, A = append ? n_append : 0;
-    if (int rc = check_sizes(B, C, N, H, W, "image_sample")) return rc;
+    DEFTET_TRY(check_sizes(B, C, N, H, W, "image_sample"));
     DEFTET_CHECK_ARG(n_global >= 0 && n_append >= 0, "image_sample: negative row count");
     DEFTET_CHECK_ARG(channel_offset >= 0 && (long long)n_channel_total >= (long long)channel_offset + C,
                      "image_sample: channel offset + channels exceed the destination");
@@ -173,17 +173,17 @@ int deftet_image_sample_fwd_f32(const float *map, const float *uv, const float *
     if (B == 0 || N == 0 || (C == 0 && G + A == 0)) return DEFTET_OK;
     DEFTET_CHECK_ARG(out && (C == 0 || (map && uv)), "image_sample: null pointer");
     hipStream_t st = as_stream(stream);
-    const unsigned gN = (unsigned)((N + kPvBlock - 1) / kPvBlock);
+    const unsigned gN = blocks_for(N, kPvBlock);
     if (C > 0) {
         const int c_per = channels_per_thread(C, (long long)gN * B);
-        const unsigned gC = (unsigned)((C + c_per - 1) / c_per);
+        const unsigned gC = blocks_for(C, c_per);
         if (gC > 65535u) return set_error(DEFTET_ELIMIT, "image_sample: too many channel chunks");
         DEFTET_LAUNCH(k_is_fwd, dim3(gN, gC, B), dim3(kPvBlock), st, map, uv, out, C, H, W, N, channel_offset, n_channel_total, border,
                       align_corners, c_per);
     }
     if (G + A > 0) {
         const int r_per = channels_per_thread(G + A, (long long)gN * B);
-        const unsigned gR = (unsigned)((G + A + r_per - 1) / r_per);
+        const unsigned gR = blocks_for(G + A, r_per);
         if (gR > 65535u) return set_error(DEFTET_ELIMIT, "image_sample: too many row chunks");
         DEFTET_LAUNCH(k_is_rows, dim3(gN, gR, B), dim3(kPvBlock), st, global_features, append, out, G, A, N, n_channel_total, r_per);
     }
@@ -194,11 +194,10 @@ int deftet_image_cells_f32(const float *uv, int32_t *perm, int32_t *seg, float *
                            int border, int align_corners, void *workspace, size_t workspace_bytes, void *stream)
 {
     const int B = n_batch, N = n_point, H = height, W = width;
-    if (int rc = check_sizes(B, 0, N, H, W, "image_cells")) return rc;
+    DEFTET_TRY(check_sizes(B, 0, N, H, W, "image_cells"));
     DEFTET_CHECK_ARG(flags_ok(border, align_corners), "image_cells: border and align_corners are 0 or 1");
     const CellWs L = layout(B, N, H, W, workspace);
-    DEFTET_CHECK_ARG(L.fits(workspace, workspace_bytes),
-                     "image_cells: workspace null, misaligned or smaller than deftet_image_sample_workspace_bytes");
+    DEFTET_TRY(workspace_ok(__func__, workspace, workspace_bytes, L.bytes));
     if (B == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(seg, "image_cells: null pointer");
     hipStream_t st = as_stream(stream);
@@ -209,10 +208,10 @@ int deftet_image_cells_f32(const float *uv, int32_t *perm, int32_t *seg, float *
     }
     DEFTET_CHECK_ARG(uv && perm && wsorted, "image_cells: null pointer");
     const size_t n = (size_t)B * N;
-    DEFTET_LAUNCH(k_is_keys, dim3((unsigned)((N + kPvBlock - 1) / kPvBlock), B), dim3(kPvBlock), st, uv, L.s.keys, N, H, W, border, align_corners,
+    DEFTET_LAUNCH(k_is_keys, dim3(blocks_for(N, kPvBlock), B), dim3(kPvBlock), st, uv, L.s.keys, N, H, W, border, align_corners,
                   n_keys);
-    if (int rc = sort_and_segment(L.s, perm, seg, n, n_keys, st)) return rc;
-    DEFTET_LAUNCH(k_is_weights, dim3((unsigned)((n + kPvBlock - 1) / kPvBlock)), dim3(kPvBlock), st, uv, (const int32_t *)perm, wsorted, B, N, H,
+    DEFTET_TRY(sort_and_segment(L.s, perm, seg, n, n_keys, st));
+    DEFTET_LAUNCH(k_is_weights, dim3(blocks_for(n, kPvBlock)), dim3(kPvBlock), st, uv, (const int32_t *)perm, wsorted, B, N, H,
                   W, border, align_corners);
     return DEFTET_OK;
 }
@@ -222,19 +221,18 @@ int deftet_image_sample_bwd_map_f32(const float *grad_out, const int32_t *perm, 
                                     void *workspace, size_t workspace_bytes, void *stream)
 {
     const int B = n_batch, C = n_channel, N = n_point, H = height, W = width;
-    if (int rc = check_sizes(B, C, N, H, W, "image_sample_bwd_map")) return rc;
+    DEFTET_TRY(check_sizes(B, C, N, H, W, "image_sample_bwd_map"));
     DEFTET_CHECK_ARG(channel_offset >= 0 && (long long)n_channel_total >= (long long)channel_offset + C,
                      "image_sample_bwd_map: channel offset + channels exceed the source");
     const CellWs L = layout(B, N, H, W, workspace);
-    DEFTET_CHECK_ARG(L.fits(workspace, workspace_bytes),
-                     "image_sample_bwd_map: workspace null, misaligned or smaller than deftet_image_sample_workspace_bytes");
+    DEFTET_TRY(workspace_ok(__func__, workspace, workspace_bytes, L.bytes));
     if (B == 0 || C == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(seg && grad_map && (N == 0 || (grad_out && perm && wsorted)), "image_sample_bwd_map: null pointer");
     const size_t HW = (size_t)H * W;
     hipStream_t st = as_stream(stream);
     return cell_gather_bwd<4>(L, KeepEvery{}, grad_out, perm, seg, wsorted, B, cells_of(H, W), N, C, channel_offset, n_channel_total, st,
                               [&](const float *part, int c0, int c_chunk, int cc) -> int {
-                                  DEFTET_LAUNCH(k_is_map_from_partials, dim3((unsigned)(((size_t)cc * HW + kPvBlock - 1) / kPvBlock), (unsigned)B),
+                                  DEFTET_LAUNCH(k_is_map_from_partials, dim3(blocks_for((size_t)cc * HW, kPvBlock), (unsigned)B),
                                                 dim3(kPvBlock), st, part, grad_map, C, H, W, c0, c_chunk, cc);
                                   return DEFTET_OK;
                               });
@@ -245,13 +243,13 @@ int deftet_image_sample_bwd_uv_f32(const float *map, const float *uv, const floa
                                    int align_corners, int accumulate, void *stream)
 {
     const int B = n_batch, C = n_channel, N = n_point, H = height, W = width;
-    if (int rc = check_sizes(B, C, N, H, W, "image_sample_bwd_uv")) return rc;
+    DEFTET_TRY(check_sizes(B, C, N, H, W, "image_sample_bwd_uv"));
     DEFTET_CHECK_ARG(channel_offset >= 0 && (long long)n_channel_total >= (long long)channel_offset + C,
                      "image_sample_bwd_uv: channel offset + channels exceed the source");
     DEFTET_CHECK_ARG(flags_ok(border, align_corners), "image_sample_bwd_uv: border and align_corners are 0 or 1");
     if (B == 0 || N == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(uv && grad_uv && (C == 0 || (map && grad_out)), "image_sample_bwd_uv: null pointer");
-    DEFTET_LAUNCH(k_is_bwd_uv, dim3((unsigned)((N + kPvBlock - 1) / kPvBlock), B), dim3(kPvBlock), as_stream(stream), map, uv, grad_out, grad_uv,
+    DEFTET_LAUNCH(k_is_bwd_uv, dim3(blocks_for(N, kPvBlock), B), dim3(kPvBlock), as_stream(stream), map, uv, grad_out, grad_uv,
                   C, H, W, N, channel_offset, n_channel_total, border, align_corners, accumulate);
     return DEFTET_OK;
 }
@@ -265,7 +263,7 @@ int deftet_image_sample_bwd_global_f32(const float *grad_out, float *grad_global
     if (B == 0 || G == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(grad_global && (N == 0 || grad_out), "image_sample_bwd_global: null pointer");
     const int rows = B * G, per = kPvBlock / 64;
-    DEFTET_LAUNCH(k_is_rowsum, dim3((unsigned)((rows + per - 1) / per)), dim3(kPvBlock), as_stream(stream), grad_out, grad_global, rows, G, N,
+    DEFTET_LAUNCH(k_is_rowsum, dim3(blocks_for(rows, per)), dim3(kPvBlock), as_stream(stream), grad_out, grad_global, rows, G, N,
                   n_channel_total);
     return DEFTET_OK;
 }

@@ -234,8 +234,7 @@ static int check_shape(int B, int V, int T, int E, float iso, void *workspace, s
     DEFTET_CHECK_ARG((long long)B * E + 2LL * B * T < 2147483647LL && (long long)B * V < 2147483648LL,
                      "n_batch * (n_edge + 2 n_tet) or n_batch * n_vertex does not fit 31 bits");
     L = make_layout(B, T, E, workspace);
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && L.bytes <= wsb,
-                     "workspace null, misaligned or smaller than deftet_marching_tets_workspace_bytes");
+    DEFTET_TRY(workspace_ok("deftet_marching_tets*", workspace, wsb, L.bytes));
     return DEFTET_OK;
 }
 
@@ -266,22 +265,16 @@ extern "C" int deftet_marching_tets_count_f32(const float *field_bxv, const int3
                                               size_t wsb, void *stream_)
 {
     Layout L;
-    {
-        const int rc = check_shape(B, V, T, E, iso, workspace, wsb, L);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(check_shape(B, V, T, E, iso, workspace, wsb, L));
     DEFTET_CHECK_ARG(field_bxv && edges_ex2 && tet_idx_tx4 && edge_vertex_bxe && offsets_2xb1, "null pointer");
     DEFTET_CHECK_ARG(((uintptr_t)edges_ex2 & 7) == 0 && ((uintptr_t)tet_idx_tx4 & 15) == 0, "misaligned edges_ex2 / tet_idx_tx4");
     hipStream_t st = as_stream(stream_);
     const size_t n = L.n;
     const Shape s{field_bxv, (const int2 *)edges_ex2, (const int4 *)tet_idx_tx4, B, V, T, E, iso};
-    DEFTET_LAUNCH(k_mt_count, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), st, s, L.cnt);
-    {
-        const int rc = prims::scan<int, prims::Plus, true>(L.cnt, L.cnt, n, 0, prims::Plus(), L.scanTmp, L.scanTmpBytes, st);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_LAUNCH(k_mt_count, dim3(blocks_for(n, kThreads)), dim3(kThreads), st, s, L.cnt);
+    DEFTET_TRY(prims::scan<int, prims::Plus, true>(L.cnt, L.cnt, n, 0, prims::Plus(), L.scanTmp, L.scanTmpBytes, st));
     const size_t nf = (size_t)B * E > (size_t)B + 1 ? (size_t)B * E : (size_t)B + 1;
-    DEFTET_LAUNCH(k_mt_finish, dim3((unsigned)((nf + kThreads - 1) / kThreads)), dim3(kThreads), st, (const int *)L.cnt, B, T, E, edge_vertex_bxe,
+    DEFTET_LAUNCH(k_mt_finish, dim3(blocks_for(nf, kThreads)), dim3(kThreads), st, (const int *)L.cnt, B, T, E, edge_vertex_bxe,
                   offsets_2xb1);
     return DEFTET_OK;
 }
@@ -293,10 +286,7 @@ extern "C" int deftet_marching_tets_fill_f32(const float *pos_bxvx3, const float
                                              int64_t *tet_id, void *workspace, size_t wsb, void *stream_)
 {
     Layout L;
-    {
-        const int rc = check_shape(B, V, T, E, iso, workspace, wsb, L);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(check_shape(B, V, T, E, iso, workspace, wsb, L));
     DEFTET_CHECK_ARG(C >= 0 && C <= 8 && (attr_bxvxc == nullptr) == (C == 0), "n_attr=%d outside 0..8, or attr_bxvxc does not go with it", C);
     DEFTET_CHECK_ARG(n_vert >= 0 && n_face >= 0, "negative capacity");
     DEFTET_CHECK_ARG(pos_bxvx3 && field_bxv && edges_ex2 && tet_idx_tx4 && tet_edge_tx6 && edge_vertex_bxe, "null pointer");
@@ -308,7 +298,7 @@ extern "C" int deftet_marching_tets_fill_f32(const float *pos_bxvx3, const float
     const Shape s{field_bxv, (const int2 *)edges_ex2, (const int4 *)tet_idx_tx4, B, V, T, E, iso};
     const Out o{pos_bxvx3, attr_bxvxc, tet_edge_tx6, edge_vertex_bxe, verts, vert_attr, (long long *)faces, (long long *)edge_id, t,
                 (long long *)tet_id, n_vert, n_face, C};
-    DEFTET_LAUNCH(k_mt_fill, dim3((unsigned)((n - 1 + kThreads - 1) / kThreads)), dim3(kThreads), st, s, o, (const int *)L.cnt);
+    DEFTET_LAUNCH(k_mt_fill, dim3(blocks_for(n - 1, kThreads)), dim3(kThreads), st, s, o, (const int *)L.cnt);
     return DEFTET_OK;
 }
 
@@ -330,7 +320,7 @@ extern "C" int deftet_marching_tets_bwd_f32(const float *grad_verts, const float
     DEFTET_CHECK_ARG(!grad_attr || C > 0, "grad_attr without attributes");
     hipStream_t st = as_stream(stream_);
     const Shape s{field_bxv, (const int2 *)edges_ex2, nullptr, B, V, 0, E, iso};
-    const dim3 grid((V + kThreads - 1) / kThreads, B);
+    const dim3 grid(blocks_for(V, kThreads), B);
     if (C == 0)
         DEFTET_LAUNCH(k_mt_bwd<0>, grid, dim3(kThreads), st, s, pos_bxvx3, attr_bxvxc, C, csr_offsets, csr_slots, edge_vertex_bxe, offsets_2xb1,
                       grad_verts, grad_vert_attr, n_vert, grad_pos, grad_field, grad_attr);

@@ -607,8 +607,7 @@ extern "C" int deftet_point_mesh_distance_f32(const float *pts, const float *fac
 {
     const int rc = pm_check(pts, face, n_face, B, P, F, dist, face_idx, dist_type);
     if (rc != DEFTET_OK || B == 0 || P == 0) return rc;
-    DEFTET_CHECK_ARG(workspace && aligned(workspace, 256) && workspace_bytes >= deftet_point_mesh_distance_workspace_bytes(B, P, F),
-                     "workspace null, misaligned or too small");
+    DEFTET_TRY(workspace_ok(__func__, workspace, workspace_bytes, deftet_point_mesh_distance_workspace_bytes(B, P, F)));
     hipStream_t st = as_stream(stream_);
     met::PMSlices s;
     met::pm_layout(B, F, workspace, &s);
@@ -621,13 +620,13 @@ extern "C" int deftet_point_mesh_distance_f32(const float *pts, const float *fac
     DEFTET_LAUNCH(met::k_pm_stats, dim3(met::kPParts, B), dim3(256), st, fc, nf, F, s.part);
     DEFTET_LAUNCH(met::k_pm_grid, dim3(B), dim3(64), st, s.part, s.grids);
     if (F > 0) {
-        const dim3 fg((F + 255) / 256, B);
+        const dim3 fg(blocks_for(F, 256), B);
         DEFTET_LAUNCH(met::k_pm_bin, fg, dim3(256), st, fc, nf, F, s.grids, 0, s.count, s.start, s.fill, s.list, s.wide, s.nWide);
         const int src = deftet_scan(s.count, s.start, (long long)nc, 4, 0, s.scan_ws, s.scan_bytes, stream_);
         if (src != DEFTET_OK) return src;
         DEFTET_LAUNCH(met::k_pm_bin, fg, dim3(256), st, fc, nf, F, s.grids, 1, s.count, s.start, s.fill, s.list, s.wide, s.nWide);
     }
-    DEFTET_LAUNCH(met::k_pm_query, dim3((P + 255) / 256, B), dim3(256), st, pts, fc, P, F, s.grids, s.count, s.start, s.list, s.wide,
+    DEFTET_LAUNCH(met::k_pm_query, dim3(blocks_for(P, 256), B), dim3(256), st, pts, fc, P, F, s.grids, s.count, s.start, s.list, s.wide,
                   s.nWide, dist, (long long *)face_idx, (int *)dist_type);
     return DEFTET_OK;
 }
@@ -637,7 +636,7 @@ extern "C" int deftet_point_mesh_distance_scan_f32(const float *pts, const float
 {
     const int rc = pm_check(pts, face, n_face, B, P, F, dist, face_idx, dist_type);
     if (rc != DEFTET_OK || B == 0 || P == 0) return rc;
-    DEFTET_LAUNCH(met::k_pm_scan, dim3((P + 255) / 256, B), dim3(256), as_stream(stream_), pts, F > 0 ? face : pts, (const int *)n_face, P,
+    DEFTET_LAUNCH(met::k_pm_scan, dim3(blocks_for(P, 256), B), dim3(256), as_stream(stream_), pts, F > 0 ? face : pts, (const int *)n_face, P,
                   F, dist, (long long *)face_idx, (int *)dist_type);
     return DEFTET_OK;
 }
@@ -658,20 +657,20 @@ extern "C" int deftet_sample_points_f32(const float *face, const float *areas, c
                          aligned(points, 4) && aligned(face_choice, 8) && aligned(empty_flag, 4),
                      "misaligned pointer");
     const met::SampLayout L = met::samp_layout(B, F, workspace);
-    DEFTET_CHECK_ARG(workspace && aligned(workspace, 256) && L.bytes <= workspace_bytes, "workspace null, misaligned or too small");
+    DEFTET_TRY(workspace_ok(__func__, workspace, workspace_bytes, L.bytes));
     hipStream_t st = as_stream(stream_);
     const size_t n = (size_t)B * F;
     DEFTET_HIP(hipMemsetAsync(empty_flag, 0, (size_t)B * 4, st));
     DEFTET_HIP(hipMemsetAsync(L.amax, 0, (size_t)B * 4, st));
     if (F > 0) {
-        const dim3 fg((F + 255) / 256, B);
+        const dim3 fg(blocks_for(F, 256), B);
         DEFTET_LAUNCH(met::k_samp_area, fg, dim3(256), st, face, areas, (const int *)n_face, F, L.a, L.amax);
         DEFTET_LAUNCH(met::k_samp_quant, fg, dim3(256), st, L.a, L.amax, F, L.cum);
         const int src = deftet_scan(L.cum, L.cum, (long long)n, 8, 1, L.scan_ws, L.scan_bytes, stream_);
         if (src != DEFTET_OK) return src;
     }
     if (N > 0)
-        DEFTET_LAUNCH(met::k_samp_points, dim3((N + 255) / 256, B), dim3(256), st, F > 0 ? face : uniforms, L.cum, uniforms, F, N, points,
+        DEFTET_LAUNCH(met::k_samp_points, dim3(blocks_for(N, 256), B), dim3(256), st, F > 0 ? face : uniforms, L.cum, uniforms, F, N, points,
                       (long long *)face_choice, (int *)empty_flag);
     return DEFTET_OK;
 }
@@ -685,7 +684,7 @@ extern "C" int deftet_nn_distance_f32(const float *queries, const float *points,
     DEFTET_CHECK_ARG(aligned(queries, 4) && aligned(points, 4) && aligned(idx, 4) && aligned(dist, 4) &&
                          aligned(idx64, 8),
                      "misaligned pointer");
-    DEFTET_LAUNCH(met::k_nn_dist, dim3((N + 255) / 256, B), dim3(256), as_stream(stream_), queries, M > 0 ? points : queries,
+    DEFTET_LAUNCH(met::k_nn_dist, dim3(blocks_for(N, 256), B), dim3(256), as_stream(stream_), queries, M > 0 ? points : queries,
                   (const int *)idx, N, M, dist, (long long *)idx64);
     return DEFTET_OK;
 }
@@ -708,8 +707,7 @@ extern "C" int deftet_surface_metrics_f32(const float *p1, const float *p2, cons
     DEFTET_CHECK_ARG(aligned(p1, 4) && aligned(p2, 4) && aligned(idx12, 4) && aligned(idx21, 4) &&
                          aligned(dist_a, 4) && aligned(dist_b, 4) && aligned(out, 4),
                      "misaligned pointer");
-    DEFTET_CHECK_ARG(workspace && aligned(workspace, 256) && workspace_bytes >= deftet_surface_metrics_workspace_bytes(B),
-                     "workspace null, misaligned or too small");
+    DEFTET_TRY(workspace_ok(__func__, workspace, workspace_bytes, deftet_surface_metrics_workspace_bytes(B)));
     hipStream_t st = as_stream(stream_);
     float *part = static_cast<float *>(workspace);
     const int have_h = dist_a != nullptr && Nh > 0;

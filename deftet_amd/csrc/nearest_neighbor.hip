@@ -619,30 +619,27 @@ static int nn_group(const float *queries, const float *points, int32_t *result, 
     const dim3 blk(256);
     DEFTET_LAUNCH(k_nn_bbox, dim3(kNNBlocks, nS), blk, st, points, M, L.part, slice, L.cells, L.rep, L.nRep, (int)nc);
     DEFTET_LAUNCH(k_nn_grid, dim3(nS), dim3(64), st, (const float *)L.part, G, L.grid, slice);
-    DEFTET_LAUNCH(k_nn_bin, dim3((M + 255) / 256, nS), blk, st, points, M, (const NNGrid *)L.grid, L.cells, L.pcell, L.rep, slice);
+    DEFTET_LAUNCH(k_nn_bin, dim3(blocks_for(M, 256), nS), blk, st, points, M, (const NNGrid *)L.grid, L.cells, L.pcell, L.rep, slice);
     DEFTET_LAUNCH(k_scan_excl, dim3(scan_tiles(nc), nS), dim3(kScanThreads), st, (const int *)L.cells, L.start, (int)nc, slice, 0);
-    DEFTET_LAUNCH(k_nn_scatter, dim3((M + 255) / 256, nS), blk, st, points, M, (const int2 *)L.pcell, (const int *)L.start, L.sorted, slice);
-    DEFTET_LAUNCH(k_nn_query, dim3((Nst + 255) / 256, nS), blk, st, queries, N, (const NNGrid *)L.grid, (const int *)L.start,
+    DEFTET_LAUNCH(k_nn_scatter, dim3(blocks_for(M, 256), nS), blk, st, points, M, (const int2 *)L.pcell, (const int *)L.start, L.sorted, slice);
+    DEFTET_LAUNCH(k_nn_query, dim3(blocks_for(Nst, 256), nS), blk, st, queries, N, (const NNGrid *)L.grid, (const int *)L.start,
                   (const float4 *)L.sorted, (const int *)L.rep, points, M, result, L.farKey, 1u << keyBits, slice, cnt, Nst, shapeShift);
-    DEFTET_LAUNCH(k_iota, dim3((unsigned)((nAll + 255) / 256)), blk, st, L.iota, (long long)nAll);
+    DEFTET_LAUNCH(k_iota, dim3(blocks_for(nAll, 256)), blk, st, L.iota, (long long)nAll);
     int shapeBitsN = 0;
     while ((1 << shapeBitsN) < nS) ++shapeBitsN;
-    {
-        const int rc = prims::radix_sort<unsigned, unsigned>(L.farKey, L.farKeyS, L.iota, reinterpret_cast<unsigned *>(L.farList), nAll,
-                                                             keyBits + 1 + shapeBitsN, L.sortTmp, L.sortTmpBytes, st);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(prims::radix_sort<unsigned, unsigned>(L.farKey, L.farKeyS, L.iota, reinterpret_cast<unsigned *>(L.farList), nAll,
+                                                     keyBits + 1 + shapeBitsN, L.sortTmp, L.sortTmpBytes, st));
     const int Gc = (G + kNNCoarse - 1) / kNNCoarse, Gc3 = Gc * Gc * Gc, nt = std::max(Gc3, G * G + 2 * kNNBatch);
-    DEFTET_LAUNCH(k_nn_far_tables, dim3((nt + 255) / 256, nS), blk, st, (const int *)L.rep, points, Gc3, (const int *)L.start, G, L.repList, L.nRep,
+    DEFTET_LAUNCH(k_nn_far_tables, dim3(blocks_for(nt, 256), nS), blk, st, (const int *)L.rep, points, Gc3, (const int *)L.start, G, L.repList, L.nRep,
                   L.rowStart, L.sorted, slice, M);
     DEFTET_LAUNCH(k_nn_far_pad, dim3(nS), dim3(64), st, L.repList, (const int *)L.nRep, slice);
-    DEFTET_LAUNCH(k_nn_far_bound, dim3((nmax + 63) / 64, nS), dim3(kFarWaves * 64), st, queries, (const NNGrid *)L.grid, (const int *)L.start,
+    DEFTET_LAUNCH(k_nn_far_bound, dim3(blocks_for(nmax, 64), nS), dim3(kFarWaves * 64), st, queries, (const NNGrid *)L.grid, (const int *)L.start,
                   (const float4 *)L.sorted, (const float4 *)L.repList, (const int *)L.nRep, points, N, (const unsigned *)L.farKeyS,
                   (const unsigned *)L.farList, L.bound, L.nFar, 1u << keyBits, slice, M, Nst, shapeShift);
-    DEFTET_LAUNCH(k_nn_far_rows, dim3((nmax + 63) / 64, kFarSlices, nS), dim3(kFarWaves * 64), st, queries, (const NNGrid *)L.grid,
+    DEFTET_LAUNCH(k_nn_far_rows, dim3(blocks_for(nmax, 64), kFarSlices, nS), dim3(kFarWaves * 64), st, queries, (const NNGrid *)L.grid,
                   (const int *)L.start, (const float4 *)L.sorted, (const int *)L.rowStart, (const int *)L.nFar, (const unsigned *)L.farList, L.bound, slice,
                   N, Nst);
-    DEFTET_LAUNCH(k_nn_far_final, dim3((nmax + 255) / 256, nS), blk, st, (const unsigned long long *)L.bound, (const int *)L.nFar,
+    DEFTET_LAUNCH(k_nn_far_final, dim3(blocks_for(nmax, 256), nS), blk, st, (const unsigned long long *)L.bound, (const int *)L.nFar,
                   (const unsigned *)L.farList, result, slice, N, Nst);
     return DEFTET_OK;
 }
@@ -661,24 +658,22 @@ static int nn_index_impl(const float *queries, const float *points, int32_t *res
     hipStream_t st = as_stream(stream_);
     if (!workspace || M == 0) {
         if (!n_query_host) {
-            DEFTET_LAUNCH(k_nn, dim3((N + 255) / 256, B), dim3(256), st, queries, points, N, M, result);
+            DEFTET_LAUNCH(k_nn, dim3(blocks_for(N, 256), B), dim3(256), st, queries, points, N, M, result);
         } else {
             for (int b = 0; b < B; ++b)
                 if (n_query_host[b] > 0)
-                    DEFTET_LAUNCH(k_nn, dim3((n_query_host[b] + 255) / 256, 1), dim3(256), st, queries + (size_t)b * N * 3, points + (size_t)b * M * 3,
+                    DEFTET_LAUNCH(k_nn, dim3(blocks_for(n_query_host[b], 256), 1), dim3(256), st, queries + (size_t)b * N * 3, points + (size_t)b * M * 3,
                                   n_query_host[b], M, result + (size_t)b * N);
         }
         return DEFTET_OK;
     }
-    DEFTET_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && nn_layout(group_shapes(B), N, M, workspace).bytes <= wsb,
-                     "workspace misaligned or too small");
+    DEFTET_TRY(workspace_ok("deftet_nn_index*", workspace, wsb, nn_layout(group_shapes(B), N, M, workspace).bytes));
     for (int b0 = 0; b0 < B; b0 += kBatchShapes) {                   // groups of kBatchShapes shapes reuse the workspace (stream order)
         const int nS = std::min(kBatchShapes, B - b0);
         ShapeCounts cnt{};
         for (int i = 0; i < nS; ++i) cnt.n[i] = n_query_host ? n_query_host[b0 + i] : N;
-        const int rc = nn_group(queries + (size_t)b0 * N * 3, points + (size_t)b0 * M * 3, result + (size_t)b0 * N, nS, N, M, cnt, workspace,
-                                st);
-        if (rc != DEFTET_OK) return rc;
+        DEFTET_TRY(nn_group(queries + (size_t)b0 * N * 3, points + (size_t)b0 * M * 3, result + (size_t)b0 * N, nS, N, M, cnt, workspace,
+                            st));
     }
     return DEFTET_OK;
 }

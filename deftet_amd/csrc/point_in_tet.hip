@@ -3283,7 +3283,7 @@ extern "C" int deftet_point_in_tet_grid_dims(int T, int Q, int *G_yz, int *G_x)
 }
 
 static int pit_check(const float *tet, const float *pts, const float *cond, const float *bary, const float *pred, const float *occ,
-                     const int32_t *hit_buf, int B, int T, int Q, int algo, const void *workspace)
+                     const int32_t *hit_buf, int B, int T, int Q, int algo)
 {
     DEFTET_CHECK_ARG(!hit_buf || (((uintptr_t)hit_buf & 15) == 0 && algo != DEFTET_PIT_BRUTE), "hit_buf must be 16-byte aligned and needs a binned algo");
     DEFTET_CHECK_ARG((pred == nullptr) == (occ == nullptr), "pred and occ must be given together");
@@ -3298,7 +3298,6 @@ static int pit_check(const float *tet, const float *pts, const float *cond, cons
     DEFTET_CHECK_ARG(T == 0 || tet, "null tet pointer");
     DEFTET_CHECK_ARG(((uintptr_t)tet & 15) == 0, "tet must be 16-byte aligned");
     DEFTET_CHECK_ARG(!bary || ((uintptr_t)bary & 15) == 0, "bary must be 16-byte aligned");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0, "workspace null or not 256-byte aligned");
     return DEFTET_OK;
 }
 
@@ -3331,7 +3330,7 @@ static int pit_scan(const Layout &L, typename TS::Arg tet, const float *pts, flo
                     int32_t *hit_buf, int B, int T, int Q, int algo, hipStream_t st, const int32_t *order = nullptr)
 {
     const dim3 blk(256);
-    const dim3 gf((Q + 256 * PIT_FIN_QPT - 1) / (256 * PIT_FIN_QPT), B), gt((((T + 255) / 256 + 7) / 8) * 8, B);   // gt: multiple of 8 for the XCD mapping
+    const dim3 gf(blocks_for(Q, 256 * PIT_FIN_QPT), B), gt(align_up(blocks_for(T, 256), 8), B);   // gt: multiple of 8 for the XCD mapping
     int *ucount = hit_buf ? hit_buf + hit_cnt_off(B, T) : nullptr;
     if (T > 0) {
         if (algo == DEFTET_PIT_EXACT) {
@@ -3346,8 +3345,8 @@ static int pit_scan(const Layout &L, typename TS::Arg tet, const float *pts, flo
             if (spill) DEFTET_HIP(hipMemsetAsync(spill, 0, (size_t)B * Q * 24, st));
 #endif
             const dim3 bw(kWvThreads);                                                           // the wave-staged kernels' workgroup
-            const dim3 gw((((T + kWvThreads - 1) / kWvThreads + 7) / 8) * 8, B);
-            const dim3 gp(((((T + 1) / 2 + kWvThreads - 1) / kWvThreads + 7) / 8) * 8, B);       // two tets per lane
+            const dim3 gw(align_up(blocks_for(T, kWvThreads), 8), B);
+            const dim3 gp(align_up(blocks_for((T + 1) / 2, kWvThreads), 8), B);       // two tets per lane
 #define PIT_SCAN_ARGS tet, T, Q, L.gparam, L.G, L.Gx, L.table, L.cellStride, L.sortedQ, L.result, L.counters, L.irregT, (int2 *)hit_buf, pts, \
                       L.irregQ, ucount, hit_pad(B), spill, (const int *)order
             typedef TetCfg<TS, true> Ord;                                                       // walks the tets in `order`
@@ -3375,28 +3374,27 @@ static int pit_forward_checked(typename TS::Arg tet, const float *pts, float *co
                                const int32_t *order, const float *boxIn, float *boxOut, int32_t *missOut)
 {
     Layout L = make_layout(B, T, Q, algo, workspace, workspace_bytes);
-    DEFTET_CHECK_ARG(L.bytes <= workspace_bytes, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
+    DEFTET_TRY(workspace_ok("deftet_point_in_tet*", workspace, workspace_bytes, L.bytes));
     hipStream_t st = as_stream(stream_);
     if (algo == DEFTET_PIT_BRUTE) {
-        const dim3 blk(256), gq((Q + 255) / 256, B);
+        const dim3 blk(256), gq(blocks_for(Q, 256), B);
         if (T > 0) {
             long long n = (long long)B * T;
-            DEFTET_LAUNCH(k_prep_records<TS>, dim3((unsigned)((n + 255) / 256)), blk, st, tet, n, L.rec, T);
+            DEFTET_LAUNCH(k_prep_records<TS>, dim3(blocks_for(n, 256)), blk, st, tet, n, L.rec, T);
         }
         DEFTET_LAUNCH(k_brute, gq, blk, st, L.rec, pts, T, Q, L.result);
         DEFTET_LAUNCH(k_finalize<TS>, dim3((Q + 256 * PIT_FIN_QPT - 1) / (256 * PIT_FIN_QPT), B), blk, st, tet, pts, T, Q, L.result, cond, bary, pred, occ, (const int2 *)nullptr, (int *)nullptr,
                       (int *)nullptr, (const int *)nullptr, L.irregT, 0, pin_shapes(Q), (const float *)nullptr);
         return DEFTET_OK;
     }
-    const int rc = pit_prepare(L, pts, B, Q, st, boxIn, boxOut, missOut);
-    if (rc != DEFTET_OK) return rc;
+    DEFTET_TRY(pit_prepare(L, pts, B, Q, st, boxIn, boxOut, missOut));
     return pit_scan<TS>(L, tet, pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo, st, order);
 }
 static int pit_forward(const float *tet, const float *pts, float *cond, float *bary, const float *pred, float *occ, int32_t *hit_buf,
                        int B, int T, int Q, int algo, void *workspace, size_t workspace_bytes, void *stream_, const int32_t *order,
                        const float *boxIn = nullptr, float *boxOut = nullptr, int32_t *missOut = nullptr)
 {
-    int rc = pit_check(tet, pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo, workspace);
+    int rc = pit_check(tet, pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo);
     if (rc != DEFTET_OK || B == 0 || Q == 0) return rc;
     return pit_forward_checked<DenseTets>(tet, pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo, workspace, workspace_bytes, stream_, order,
                                           boxIn, boxOut, missOut);
@@ -3458,9 +3456,8 @@ static int pit_prepare_entry(const float *pts, int B, int T, int Q, int algo, vo
     if (Q >= (1 << 27)) return set_error(DEFTET_ELIMIT, "n_query=%d exceeds 2^27", Q);
     if (B == 0 || Q == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(pts, "null pts pointer");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0, "workspace null or not 256-byte aligned");
     Layout L = make_layout(B, T, Q, algo, workspace, workspace_bytes);
-    DEFTET_CHECK_ARG(L.bytes <= workspace_bytes, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
+    DEFTET_TRY(workspace_ok("deftet_point_in_tet*", workspace, workspace_bytes, L.bytes));
     return pit_prepare(L, pts, B, Q, as_stream(stream_), boxIn, boxOut, missOut);
 }
 
@@ -3468,10 +3465,10 @@ static int pit_scan_entry(const float *tet, const float *pts, float *cond, float
                           int B, int T, int Q, int algo, void *workspace, size_t workspace_bytes, void *stream_, const int32_t *order)
 {
     DEFTET_CHECK_ARG(algo != DEFTET_PIT_BRUTE, "scan needs a binned algo");
-    int rc = pit_check(tet, pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo, workspace);
+    int rc = pit_check(tet, pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo);
     if (rc != DEFTET_OK || B == 0 || Q == 0) return rc;
     Layout L = make_layout(B, T, Q, algo, workspace, workspace_bytes);
-    DEFTET_CHECK_ARG(L.bytes <= workspace_bytes, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
+    DEFTET_TRY(workspace_ok("deftet_point_in_tet*", workspace, workspace_bytes, L.bytes));
     return pit_scan<DenseTets>(L, tet, pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo, as_stream(stream_), order);
 }
 
@@ -3496,9 +3493,9 @@ extern "C" int deftet_point_in_tet_scan_ex_f32(const float *tet, const float *pt
 extern "C" int deftet_point_in_tet_read_stats(const void *workspace, size_t workspace_bytes, int B, int T, int Q, int algo,
                                               int32_t *out_host, void *stream_)
 {
-    DEFTET_CHECK_ARG(workspace && out_host && B > 0 && algo != DEFTET_PIT_BRUTE, "bad argument");
+    DEFTET_CHECK_ARG(out_host && B > 0 && algo != DEFTET_PIT_BRUTE, "bad argument");
     Layout L = make_layout(B, T, Q, algo, const_cast<void *>(workspace), workspace_bytes);
-    DEFTET_CHECK_ARG(L.bytes <= workspace_bytes, "workspace too small");
+    DEFTET_TRY(workspace_ok(__func__, workspace, workspace_bytes, L.bytes, 1));
     hipStream_t st = as_stream(stream_);
     std::vector<int32_t> tmp((size_t)B * 8);
     DEFTET_HIP(hipMemcpyAsync(tmp.data(), L.counters, (size_t)B * 32, hipMemcpyDeviceToHost, st));
@@ -3620,7 +3617,7 @@ static int pit_bwd(typename TS::Arg tet, const float *pts, const float *cond, co
         DEFTET_CHECK_ARG(((uintptr_t)hit_buf & 15) == 0, "hit_buf must be 16-byte aligned");
         float *missPart = nullptr;
         if (grad_pred) {
-            DEFTET_CHECK_ARG(workspace && workspace_bytes >= (size_t)B * kMissStride * 4, "workspace needed for the miss sums (80 floats per shape)");
+            DEFTET_TRY(workspace_ok("deftet_point_in_tet_bwd*", workspace, workspace_bytes, (size_t)B * kMissStride * 4, 1));   // the miss sums, 80 floats per shape
             missPart = static_cast<float *>(workspace);
         }
         const int tblocks = (T + 255) / 256, nMissParts = tblocks < kMissParts ? tblocks : kMissParts;
@@ -3631,9 +3628,7 @@ static int pit_bwd(typename TS::Arg tet, const float *pts, const float *cond, co
                       (const int *)(hit_buf + hit_list_off(B, T)), hit_pad(B), (const int4 *)(hit_buf + hit_spill_off(B, T, Q)), pin_shapes(Q),
                       (unsigned long long *)nullptr);
     } else if (workspace) {
-        const size_t need = deftet_point_in_tet_bwd_workspace_bytes(B, T, Q);
-        DEFTET_CHECK_ARG(workspace_bytes >= need && ((uintptr_t)workspace & 255) == 0,
-                         "backward workspace too small (%zu < %zu) or misaligned", workspace_bytes, need);
+        DEFTET_TRY(workspace_ok("deftet_point_in_tet_bwd*", workspace, workspace_bytes, deftet_point_in_tet_bwd_workspace_bytes(B, T, Q)));
         char *w = static_cast<char *>(workspace);
         int *head = reinterpret_cast<int *>(w);
         int *next = reinterpret_cast<int *>(w + align_up((size_t)B * T * 4, 256));
@@ -3642,16 +3637,16 @@ static int pit_bwd(typename TS::Arg tet, const float *pts, const float *cond, co
         if (grad_pred) DEFTET_HIP(hipMemsetAsync(missSum, 0, (size_t)B * 4, st));
         DEFTET_LAUNCH(k_hit_link, dim3((Q + 256 * kLinkPer - 1) / (256 * kLinkPer), B), dim3(256), st, cond, T, Q, head, next,
                       grad_occ, missSum);
-        DEFTET_LAUNCH(k_bary_bwd_gather<TS>, dim3((T + 255) / 256, B), dim3(256), st, tet, pts, grad_w, head, next, T, Q,
+        DEFTET_LAUNCH(k_bary_bwd_gather<TS>, dim3(blocks_for(T, 256), B), dim3(256), st, tet, pts, grad_w, head, next, T, Q,
                       grad_tet, grad_pts, accumulate, grad_occ, missSum, grad_pred);
     } else {
         // no workspace: atomic scatter (slow on this chip; kept for callers that cannot provide one)
         if (!accumulate) DEFTET_HIP(hipMemsetAsync(grad_tet, 0, (size_t)B * T * 48, st));
-        DEFTET_LAUNCH(k_bary_bwd<TS>, dim3((Q + 255) / 256, B), dim3(256), st, tet, pts, cond, grad_w, T, Q, grad_tet,
+        DEFTET_LAUNCH(k_bary_bwd<TS>, dim3(blocks_for(Q, 256), B), dim3(256), st, tet, pts, cond, grad_w, T, Q, grad_tet,
                       grad_pts);
         if (grad_pred) {
             if (!accumulate) DEFTET_HIP(hipMemsetAsync(grad_pred, 0, (size_t)B * T * 4, st));
-            DEFTET_LAUNCH(k_paste_bwd, dim3((Q + 255) / 256, B), dim3(256), st, cond, grad_occ, grad_pred, T, Q);
+            DEFTET_LAUNCH(k_paste_bwd, dim3(blocks_for(Q, 256), B), dim3(256), st, cond, grad_occ, grad_pred, T, Q);
         }
     }
     return DEFTET_OK;
@@ -3702,9 +3697,8 @@ static int pit_bwd_to_vertices(typename TS::Arg tet, const float *pts, const flo
     }
     DEFTET_CHECK_ARG(!tets_null(tet) && pts && cond && grad_w && csr_offsets && csr_slots, "null pointer");
     DEFTET_CHECK_ARG(!tets_misaligned(tet) && ((uintptr_t)grad_w & 15) == 0, "tet/grad_w must be 16-byte aligned");
-    const size_t need = deftet_point_in_tet_bwd_to_vertices_workspace_bytes(B, T, Q);
-    DEFTET_CHECK_ARG(workspace && workspace_bytes >= need && ((uintptr_t)workspace & 255) == 0,
-                     "workspace null, misaligned or too small (%zu < %zu)", workspace_bytes, need);
+    DEFTET_TRY(workspace_ok("deftet_point_in_tet*_bwd_to_vertices_f32", workspace, workspace_bytes,
+                            deftet_point_in_tet_bwd_to_vertices_workspace_bytes(B, T, Q)));
     Arena A(workspace, workspace_bytes);
     float *rows = A.take<float>((size_t)B * T * 12);
     unsigned long long *rowMask = A.take<unsigned long long>((size_t)B * ((T + 63) / 64));
@@ -3726,9 +3720,8 @@ static int pit_bwd_to_vertices(typename TS::Arg tet, const float *pts, const flo
     // no records (the forward was asked for none), or the dense case where the records are not the fast path: the per-tet lists
     // into dense rows, then the dense gather
     if (accumulate) DEFTET_HIP(hipMemsetAsync(rows, 0, (size_t)B * T * 48, st));     // (the inner call's `accumulate` covers grad_pred too)
-    const int rc = pit_bwd<TS>(tet, pts, cond, grad_w, rows, grad_pts, grad_occ, grad_pred, hit_buf, B, T, Q, accumulate, inner,
-                               innerBytes, stream_);
-    if (rc != DEFTET_OK) return rc;
+    DEFTET_TRY(pit_bwd<TS>(tet, pts, cond, grad_w, rows, grad_pts, grad_occ, grad_pred, hit_buf, B, T, Q, accumulate, inner,
+                           innerBytes, stream_));
     return vtx::gather_bwd_rows(rows, nullptr, csr_offsets, csr_slots, grad_pos, B, V, T, idx_batch, accumulate, st);
 }
 extern "C" int deftet_point_in_tet_bwd_to_vertices_f32(const float *tet, const float *pts, const float *cond, const float *grad_w,
@@ -3771,7 +3764,7 @@ static int flag_bad_indices(const int32_t *tet_idx, int idx_batch, int V, int T,
 {
     const long long n = (long long)idx_batch * T;
     if (!bad_flag || n == 0) return DEFTET_OK;
-    DEFTET_LAUNCH(k_idx_check, dim3((unsigned)((n + 255) / 256)), dim3(256), st, reinterpret_cast<const int4 *>(tet_idx), n, (unsigned)V, bad_flag);
+    DEFTET_LAUNCH(k_idx_check, dim3(blocks_for(n, 256)), dim3(256), st, reinterpret_cast<const int4 *>(tet_idx), n, (unsigned)V, bad_flag);
     return DEFTET_OK;
 }
 
@@ -3781,11 +3774,10 @@ extern "C" int deftet_point_in_tet_indexed_f32(const float *pos, const int32_t *
                                                int32_t *query_box_misses, int32_t *bad_flag, void *workspace, size_t workspace_bytes,
                                                void *stream_)
 {
-    int rc = pit_check_indexed(pos, tet_idx, idx_batch, B, V, T);
-    if (rc != DEFTET_OK) return rc;
+    DEFTET_TRY(pit_check_indexed(pos, tet_idx, idx_batch, B, V, T));
     DEFTET_CHECK_ARG(!query_box_in || query_box_in != query_box_out, "query_box_in and query_box_out must not alias");
     // (pit_check's tet tests see the aligned index list)
-    rc = pit_check(reinterpret_cast<const float *>(tet_idx), pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo, workspace);
+    int rc = pit_check(reinterpret_cast<const float *>(tet_idx), pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo);
     if (rc != DEFTET_OK || B == 0) return rc;
     rc = flag_bad_indices(tet_idx, idx_batch, V, T, bad_flag, as_stream(stream_));
     if (rc != DEFTET_OK || Q == 0) return rc;
@@ -3799,15 +3791,14 @@ extern "C" int deftet_point_in_tet_indexed_scan_f32(const float *pos, const int3
                                                     int Q, int algo, const int32_t *tet_order, int32_t *bad_flag, void *workspace,
                                                     size_t workspace_bytes, void *stream_)
 {
-    int rc = pit_check_indexed(pos, tet_idx, idx_batch, B, V, T);
-    if (rc != DEFTET_OK) return rc;
+    DEFTET_TRY(pit_check_indexed(pos, tet_idx, idx_batch, B, V, T));
     DEFTET_CHECK_ARG(algo != DEFTET_PIT_BRUTE, "scan needs a binned algo");
-    rc = pit_check(reinterpret_cast<const float *>(tet_idx), pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo, workspace);
+    int rc = pit_check(reinterpret_cast<const float *>(tet_idx), pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo);
     if (rc != DEFTET_OK || B == 0) return rc;
     rc = flag_bad_indices(tet_idx, idx_batch, V, T, bad_flag, as_stream(stream_));
     if (rc != DEFTET_OK || Q == 0) return rc;
     Layout L = make_layout(B, T, Q, algo, workspace, workspace_bytes);
-    DEFTET_CHECK_ARG(L.bytes <= workspace_bytes, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
+    DEFTET_TRY(workspace_ok("deftet_point_in_tet*", workspace, workspace_bytes, L.bytes));
     return pit_scan<IndexedTets>(L, make_indexed(pos, tet_idx, idx_batch, V, T), pts, cond, bary, pred, occ, hit_buf, B, T, Q, algo,
                                  as_stream(stream_), tet_order);
 }
@@ -3818,8 +3809,7 @@ extern "C" int deftet_point_in_tet_indexed_bwd_to_vertices_f32(const float *pos,
                                                                float *grad_pos, float *grad_pts, float *grad_pred, int B, int V, int T, int Q,
                                                                int accumulate, void *workspace, size_t workspace_bytes, void *stream_)
 {
-    const int rc = pit_check_indexed(pos, tet_idx, idx_batch, B, V, T);
-    if (rc != DEFTET_OK) return rc;
+    DEFTET_TRY(pit_check_indexed(pos, tet_idx, idx_batch, B, V, T));
     return pit_bwd_to_vertices<IndexedTets>(make_indexed(pos, tet_idx, idx_batch, V, T), pts, cond, grad_w, grad_occ, hit_buf,
                                             csr_offsets, csr_slots, idx_batch, grad_pos, grad_pts, grad_pred, B, V, T, Q, accumulate, workspace,
                                             workspace_bytes, stream_);
@@ -3832,7 +3822,7 @@ extern "C" int deftet_paste_occ_fwd_f32(const float *pred, float *cond, float *o
     if (B == 0 || Q == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(T > 0, "paste_occ needs at least one tet");
     DEFTET_CHECK_ARG(pred && cond && out, "null pointer");
-    DEFTET_LAUNCH(k_paste_fwd, dim3((Q + 255) / 256, B), dim3(256), as_stream(stream_), pred, cond, out, T, Q,
+    DEFTET_LAUNCH(k_paste_fwd, dim3(blocks_for(Q, 256), B), dim3(256), as_stream(stream_), pred, cond, out, T, Q,
                        clamp_cond_inplace);
     return DEFTET_OK;
 }
@@ -3848,6 +3838,6 @@ extern "C" int deftet_paste_occ_bwd_f32(const float *cond, const float *grad_out
     }
     if (B == 0 || Q == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(T > 0 && cond && grad_out && grad_pred, "null pointer / empty tet set");
-    DEFTET_LAUNCH(k_paste_bwd, dim3((Q + 255) / 256, B), dim3(256), st, cond, grad_out, grad_pred, T, Q);
+    DEFTET_LAUNCH(k_paste_bwd, dim3(blocks_for(Q, 256), B), dim3(256), st, cond, grad_out, grad_pred, T, Q);
     return DEFTET_OK;
 }

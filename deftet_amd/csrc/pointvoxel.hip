@@ -198,7 +198,6 @@ __global__ __launch_bounds__(kPvBlock) void k_vs_bwd_pos(const float *__restrict
     }
 }
 
-constexpr const char *kWsRefused = "workspace null, misaligned or smaller than deftet_pointvoxel_workspace_bytes";
 inline int check_sizes(int B, int C, int N, int R, const char *what)
 {
     if (B < 0 || C < 0 || N < 0 || R < 1) return set_error(DEFTET_EINVAL, "%s: negative size or resolution below 1", what);
@@ -226,7 +225,7 @@ int deftet_avg_voxelize_fwd_f32(const float *feat, const int32_t *coords, float 
                                 int n_channel, int n_point, int resolution, void *workspace, size_t workspace_bytes, void *stream)
 {
     const int B = n_batch, C = n_channel, N = n_point, R = resolution;
-    if (int rc = check_sizes(B, C, N, R, "avg_voxelize")) return rc;
+    DEFTET_TRY(check_sizes(B, C, N, R, "avg_voxelize"));
     const size_t R3 = (size_t)R * R * R;
     hipStream_t st = as_stream(stream);
     if (B == 0) return DEFTET_OK;
@@ -242,13 +241,13 @@ int deftet_avg_voxelize_fwd_f32(const float *feat, const int32_t *coords, float 
     const size_t n = (size_t)B * N;
     const unsigned n_keys = (unsigned)((size_t)B * R3);
     const CellWs L = layout(B, N, R, workspace);
-    DEFTET_CHECK_ARG(L.fits(workspace, workspace_bytes), "avg_voxelize: %s", kWsRefused);
-    const unsigned gN = (unsigned)((N + kPvBlock - 1) / kPvBlock);
+    DEFTET_TRY(workspace_ok(__func__, workspace, workspace_bytes, L.bytes));
+    const unsigned gN = blocks_for(N, kPvBlock);
     DEFTET_LAUNCH(k_vox_keys, dim3(gN, B), dim3(kPvBlock), st, coords, ind, L.s.keys, N, R, n_keys);
-    if (int rc = sort_and_segment(L.s, L.perm, L.seg, n, n_keys, st)) return rc;
-    const unsigned gS = (unsigned)((R3 + kPvBlock - 1) / kPvBlock);
+    DEFTET_TRY(sort_and_segment(L.s, L.perm, L.seg, n, n_keys, st));
+    const unsigned gS = blocks_for(R3, kPvBlock);
     const int c_per = C > 0 ? channels_per_thread(C, (long long)gS * B) : 1;
-    const unsigned gC = C > 0 ? (unsigned)((C + c_per - 1) / c_per) : 1u;
+    const unsigned gC = C > 0 ? blocks_for(C, c_per) : 1u;
     if (gC > 65535u) return set_error(DEFTET_ELIMIT, "avg_voxelize: too many channel chunks");
     DEFTET_LAUNCH(k_vox_fwd, dim3(gS, gC, B), dim3(kPvBlock), st, feat, (const int32_t *)L.perm, (const int32_t *)L.seg, out, cnt, C, N, (int)R3,
                   c_per);
@@ -259,12 +258,12 @@ int deftet_avg_voxelize_bwd_f32(const float *grad_y, const int32_t *ind, const i
                                 int n_point, int resolution, void *stream)
 {
     const int B = n_batch, C = n_channel, N = n_point, R = resolution;
-    if (int rc = check_sizes(B, C, N, R, "avg_voxelize_bwd")) return rc;
+    DEFTET_TRY(check_sizes(B, C, N, R, "avg_voxelize_bwd"));
     if (B == 0 || C == 0 || N == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(grad_y && ind && cnt && grad_x, "avg_voxelize_bwd: null pointer");
-    const unsigned gN = (unsigned)((N + kPvBlock - 1) / kPvBlock);
+    const unsigned gN = blocks_for(N, kPvBlock);
     const int c_per = channels_per_thread(C, (long long)gN * B);
-    const unsigned gC = (unsigned)((C + c_per - 1) / c_per);
+    const unsigned gC = blocks_for(C, c_per);
     if (gC > 65535u) return set_error(DEFTET_ELIMIT, "avg_voxelize_bwd: too many channel chunks");
     DEFTET_LAUNCH(k_vox_bwd, dim3(gN, gC, B), dim3(kPvBlock), as_stream(stream), grad_y, ind, cnt, grad_x, C, N, R * R * R, c_per);
     return DEFTET_OK;
@@ -275,15 +274,15 @@ int deftet_voxel_sample_fwd_f32(const float *vol, const float *pos, float *out, 
                                 void *stream)
 {
     const int B = n_batch, C = n_channel, N = n_point, R = resolution;
-    if (int rc = check_sizes(B, C, N, R, "voxel_sample")) return rc;
+    DEFTET_TRY(check_sizes(B, C, N, R, "voxel_sample"));
     DEFTET_CHECK_ARG(channel_offset >= 0 && n_channel_total >= channel_offset + C, "voxel_sample: channel offset + channels exceed the destination");
     DEFTET_CHECK_ARG(pos_mode == 0 || pos_mode == 1, "voxel_sample: pos_mode 0 (pos [B,N,3]) or 1 (coords [B,3,N])");
     DEFTET_CHECK_ARG((inds == nullptr) == (wgts == nullptr), "voxel_sample: inds and wgts come together");
     if (B == 0 || N == 0 || (C == 0 && !inds)) return DEFTET_OK;
     DEFTET_CHECK_ARG(pos && (C == 0 || (vol && out)), "voxel_sample: null pointer");
-    const unsigned gN = (unsigned)((N + kPvBlock - 1) / kPvBlock);
+    const unsigned gN = blocks_for(N, kPvBlock);
     const int c_per = C > 0 ? channels_per_thread(C, (long long)gN * B) : 1;
-    const unsigned gC = C > 0 ? (unsigned)((C + c_per - 1) / c_per) : 1u;
+    const unsigned gC = C > 0 ? blocks_for(C, c_per) : 1u;
     if (gC > 65535u) return set_error(DEFTET_ELIMIT, "voxel_sample: too many channel chunks");
     DEFTET_LAUNCH(k_vs_fwd, dim3(gN, gC, B), dim3(kPvBlock), as_stream(stream), vol, pos, out, inds, wgts, C, R, N, channel_offset,
                   n_channel_total, pos_mode, legacy, c_per);
@@ -294,7 +293,7 @@ int deftet_voxel_cells_f32(const float *pos, int pos_mode, int32_t *perm, int32_
                            int resolution, void *workspace, size_t workspace_bytes, void *stream)
 {
     const int B = n_batch, N = n_point, R = resolution;
-    if (int rc = check_sizes(B, 0, N, R, "voxel_cells")) return rc;
+    DEFTET_TRY(check_sizes(B, 0, N, R, "voxel_cells"));
     DEFTET_CHECK_ARG(pos_mode == 0 || pos_mode == 1, "voxel_cells: pos_mode 0 or 1");
     if (B == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(seg, "voxel_cells: null pointer");
@@ -307,10 +306,10 @@ int deftet_voxel_cells_f32(const float *pos, int pos_mode, int32_t *perm, int32_
     DEFTET_CHECK_ARG(pos && perm && wsorted, "voxel_cells: null pointer");
     const size_t n = (size_t)B * N;
     const CellWs L = layout(B, N, R, workspace);
-    DEFTET_CHECK_ARG(L.fits(workspace, workspace_bytes), "voxel_cells: %s", kWsRefused);
-    DEFTET_LAUNCH(k_cell_keys, dim3((unsigned)((N + kPvBlock - 1) / kPvBlock), B), dim3(kPvBlock), st, pos, pos_mode, L.s.keys, N, R);
-    if (int rc = sort_and_segment(L.s, perm, seg, n, n_keys, st)) return rc;
-    DEFTET_LAUNCH(k_cell_weights, dim3((unsigned)((n + kPvBlock - 1) / kPvBlock)), dim3(kPvBlock), st, pos, pos_mode, (const int32_t *)perm,
+    DEFTET_TRY(workspace_ok(__func__, workspace, workspace_bytes, L.bytes));
+    DEFTET_LAUNCH(k_cell_keys, dim3(blocks_for(N, kPvBlock), B), dim3(kPvBlock), st, pos, pos_mode, L.s.keys, N, R);
+    DEFTET_TRY(sort_and_segment(L.s, perm, seg, n, n_keys, st));
+    DEFTET_LAUNCH(k_cell_weights, dim3(blocks_for(n, kPvBlock)), dim3(kPvBlock), st, pos, pos_mode, (const int32_t *)perm,
                   wsorted, B, N, R);
     return DEFTET_OK;
 }
@@ -320,7 +319,7 @@ int deftet_voxel_cells_from_inds_i32(const int32_t *inds, const float *wgts, int
                                      void *stream)
 {
     const int B = n_batch, N = n_point, R = resolution;
-    if (int rc = check_sizes(B, 0, N, R, "voxel_cells_from_inds")) return rc;
+    DEFTET_TRY(check_sizes(B, 0, N, R, "voxel_cells_from_inds"));
     if (B == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(seg, "voxel_cells_from_inds: null pointer");
     hipStream_t st = as_stream(stream);
@@ -333,10 +332,10 @@ int deftet_voxel_cells_from_inds_i32(const int32_t *inds, const float *wgts, int
     DEFTET_CHECK_ARG(inds && wgts && perm && wsorted && isorted, "voxel_cells_from_inds: null pointer");
     const size_t n = (size_t)B * N;
     const CellWs L = layout(B, N, R, workspace);
-    DEFTET_CHECK_ARG(L.fits(workspace, workspace_bytes), "voxel_cells_from_inds: %s", kWsRefused);
-    DEFTET_LAUNCH(k_inds_keys, dim3((unsigned)((N + kPvBlock - 1) / kPvBlock), B), dim3(kPvBlock), st, inds, L.s.keys, N, R3, n_keys);
-    if (int rc = sort_and_segment(L.s, perm, seg, n, n_keys, st)) return rc;
-    DEFTET_LAUNCH(k_inds_gather, dim3((unsigned)((n + kPvBlock - 1) / kPvBlock)), dim3(kPvBlock), st, inds, wgts, (const int32_t *)perm, wsorted,
+    DEFTET_TRY(workspace_ok(__func__, workspace, workspace_bytes, L.bytes));
+    DEFTET_LAUNCH(k_inds_keys, dim3(blocks_for(N, kPvBlock), B), dim3(kPvBlock), st, inds, L.s.keys, N, R3, n_keys);
+    DEFTET_TRY(sort_and_segment(L.s, perm, seg, n, n_keys, st));
+    DEFTET_LAUNCH(k_inds_gather, dim3(blocks_for(n, kPvBlock)), dim3(kPvBlock), st, inds, wgts, (const int32_t *)perm, wsorted,
                   isorted, B, N);
     return DEFTET_OK;
 }
@@ -346,16 +345,16 @@ int deftet_voxel_sample_bwd_vol_f32(const float *grad_out, const int32_t *perm, 
                                     int channel_offset, int n_channel_total, void *workspace, size_t workspace_bytes, void *stream)
 {
     const int B = n_batch, C = n_channel, N = n_point, R = resolution;
-    if (int rc = check_sizes(B, C, N, R, "voxel_sample_bwd_vol")) return rc;
+    DEFTET_TRY(check_sizes(B, C, N, R, "voxel_sample_bwd_vol"));
     DEFTET_CHECK_ARG(channel_offset >= 0 && n_channel_total >= channel_offset + C, "voxel_sample_bwd_vol: channel offset + channels exceed the source");
     if (B == 0 || C == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(seg && grad_vol && (N == 0 || (grad_out && perm && wsorted)), "voxel_sample_bwd_vol: null pointer");
     const CellWs L = layout(B, N, R, workspace);
-    DEFTET_CHECK_ARG(L.fits(workspace, workspace_bytes), "voxel_sample_bwd_vol: %s", kWsRefused);
+    DEFTET_TRY(workspace_ok(__func__, workspace, workspace_bytes, L.bytes));
     const int R3 = R * R * R;
     hipStream_t st = as_stream(stream);
     auto gather = [&](const float *part, int c0, int c_chunk, int cc) -> int {
-        DEFTET_LAUNCH(k_vs_vol_from_partials, dim3((unsigned)(((size_t)cc * R3 + kPvBlock - 1) / kPvBlock), (unsigned)B), dim3(kPvBlock), st, part,
+        DEFTET_LAUNCH(k_vs_vol_from_partials, dim3(blocks_for((size_t)cc * R3, kPvBlock), (unsigned)B), dim3(kPvBlock), st, part,
                       grad_vol, C, R, c0, c_chunk, cc);
         return DEFTET_OK;
     };
@@ -370,12 +369,12 @@ int deftet_voxel_sample_bwd_pos_f32(const float *vol, const float *pos, const fl
                                     void *stream)
 {
     const int B = n_batch, C = n_channel, N = n_point, R = resolution;
-    if (int rc = check_sizes(B, C, N, R, "voxel_sample_bwd_pos")) return rc;
+    DEFTET_TRY(check_sizes(B, C, N, R, "voxel_sample_bwd_pos"));
     DEFTET_CHECK_ARG(channel_offset >= 0 && n_channel_total >= channel_offset + C, "voxel_sample_bwd_pos: channel offset + channels exceed the source");
     DEFTET_CHECK_ARG(pos_mode == 0 || pos_mode == 1, "voxel_sample_bwd_pos: pos_mode 0 or 1");
     if (B == 0 || N == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(pos && grad_pos && (C == 0 || (vol && grad_out)), "voxel_sample_bwd_pos: null pointer");
-    DEFTET_LAUNCH(k_vs_bwd_pos, dim3((unsigned)((N + kPvBlock - 1) / kPvBlock), B), dim3(kPvBlock), as_stream(stream), vol, pos, grad_out,
+    DEFTET_LAUNCH(k_vs_bwd_pos, dim3(blocks_for(N, kPvBlock), B), dim3(kPvBlock), as_stream(stream), vol, pos, grad_out,
                   grad_pos, C, R, N, channel_offset, n_channel_total, pos_mode, accumulate);
     return DEFTET_OK;
 }

@@ -25,7 +25,7 @@ extern "C" int deftet_radix_sort(const void *keys_in, void *keys_out, const void
     if (n == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(keys_in && keys_out && keys_in != keys_out && (value_bytes == 0 || (values_in && values_out && values_in != values_out)),
                      "null or aliased pointer");
-    DEFTET_CHECK_ARG(workspace && wsb >= deftet_radix_sort_workspace_bytes(n, key_bytes, value_bytes), "workspace null or too small");
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, deftet_radix_sort_workspace_bytes(n, key_bytes, value_bytes), 1));
     hipStream_t st = as_stream(stream_);
     typedef unsigned u32;
     typedef unsigned long long u64;
@@ -52,7 +52,8 @@ extern "C" int deftet_scan(const void *in, void *out, long long n, int elem_byte
 {
     DEFTET_CHECK_ARG(n >= 0 && (elem_bytes == 4 || elem_bytes == 8) && kind >= 0 && kind <= 2, "bad argument");
     if (n == 0) return DEFTET_OK;
-    DEFTET_CHECK_ARG(in && out && workspace && ((uintptr_t)workspace & 15) == 0, "null or misaligned pointer");
+    DEFTET_CHECK_ARG(in && out, "null pointer");
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, deftet_scan_workspace_bytes(n, elem_bytes), 16));
     hipStream_t st = as_stream(stream_);
     const size_t N = (size_t)n;
     if (elem_bytes == 4) {

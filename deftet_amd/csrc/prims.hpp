@@ -179,7 +179,7 @@ template <typename T, typename Op, bool EXCLUSIVE>
 int scan(const T *in, T *out, size_t n, T identity, Op op, void *tmp, size_t tmp_bytes, hipStream_t st)
 {
     if (n == 0) return DEFTET_OK;
-    if (!tmp || tmp_bytes < scan_temp_bytes<T>(n)) return set_error(DEFTET_EINVAL, "scan: temporary storage too small");
+    DEFTET_TRY(workspace_ok("scan", tmp, tmp_bytes, scan_temp_bytes<T>(n), 1));
     if (n <= kScanSmall) {
         DEFTET_LAUNCH((k_scan_small<T, Op, EXCLUSIVE>), dim3(1), dim3(1024), st, in, out, n, identity, op);
         return DEFTET_OK;
@@ -453,8 +453,7 @@ int radix_sort_impl(KL kin, K *kout, VL vin, V *vout, size_t n, int bits, void *
 {
     if (n == 0) return DEFTET_OK;
     if (n > 0xFFFFFFFFull) return set_error(DEFTET_ELIMIT, "radix_sort: more than 2^32 - 1 elements");
-    if (!tmp || ((uintptr_t)tmp & 255) != 0 || tmp_bytes < radix_sort_temp_bytes<K, V>(n, HAS_V))
-        return set_error(DEFTET_EINVAL, "radix_sort: temporary storage missing, misaligned or too small");
+    DEFTET_TRY(workspace_ok("radix_sort", tmp, tmp_bytes, radix_sort_temp_bytes<K, V>(n, HAS_V)));
     const int passes = bits <= 0 ? 1 : (bits + 7) / 8;
     const unsigned nblk = (unsigned)((n + kTile - 1) / kTile);
     Arena A(tmp, tmp_bytes);

@@ -1430,50 +1430,44 @@ static int raster_hits(const float *pb, const float *rb, const float *zb, const 
     DEFTET_LAUNCH(k_pix_bbox, dim3(kBoxBlocks), dim3(256), st, pb, P, L.part);
     DEFTET_LAUNCH(k_face_stats, dim3(kBoxBlocks), dim3(256), st, xb, zb, F, L.fpart);
     DEFTET_LAUNCH(k_pix_grid, dim3(1), dim3(64), st, L.part, L.fpart, L.grid, L.zAbsMax);
-#define RAST_TRY(call)                     \
-    do {                                   \
-        const int rc_ = (call);            \
-        if (rc_ != DEFTET_OK) return rc_;  \
-    } while (0)
     const bool nearest = policy == DEFTET_RASTER_NEAREST;
     const unsigned *perm = nullptr;
     if (F > 0 && nearest) {
-        DEFTET_LAUNCH(k_face_depth_keys, dim3((F + 255) / 256), dim3(256), st, zb, F, L.pkey, L.pval);
-        RAST_TRY((prims::radix_sort<unsigned, unsigned>(L.pkey, L.skey, L.pval, L.perm, (size_t)F, 24, L.tmp, L.tmpBytes, st)));
+        DEFTET_LAUNCH(k_face_depth_keys, dim3(blocks_for(F, 256)), dim3(256), st, zb, F, L.pkey, L.pval);
+        DEFTET_TRY(prims::radix_sort<unsigned, unsigned>(L.pkey, L.skey, L.pval, L.perm, (size_t)F, 24, L.tmp, L.tmpBytes, st));
         perm = L.perm;
     }
     if (F > 0) {
-        DEFTET_LAUNCH(k_face_span, dim3((F + 255) / 256), dim3(256), st, xb, F, L.grid, eps, perm, L.span, L.isWide);
+        DEFTET_LAUNCH(k_face_span, dim3(blocks_for(F, 256)), dim3(256), st, xb, F, L.grid, eps, perm, L.span, L.isWide);
         DEFTET_HIP(hipMemsetAsync(L.span + F, 0, 4, st));
         DEFTET_HIP(hipMemsetAsync(L.isWide + F, 0, 4, st));
-        RAST_TRY((prims::scan<int, prims::Plus, true>(L.span, L.pairOff, (size_t)F + 1, 0, prims::Plus(), L.tmp, L.tmpBytes, st)));
-        RAST_TRY((prims::scan<int, prims::Plus, true>(L.isWide, L.wideOff, (size_t)F + 1, 0, prims::Plus(), L.tmp, L.tmpBytes, st)));
-        DEFTET_LAUNCH(k_face_pairs, dim3((unsigned)((L.cap + 255) / 256)), dim3(256), st, xb, F, L.grid, eps, L.pairOff, L.wideOff, L.pkey,
+        DEFTET_TRY(prims::scan<int, prims::Plus, true>(L.span, L.pairOff, (size_t)F + 1, 0, prims::Plus(), L.tmp, L.tmpBytes, st));
+        DEFTET_TRY(prims::scan<int, prims::Plus, true>(L.isWide, L.wideOff, (size_t)F + 1, 0, prims::Plus(), L.tmp, L.tmpBytes, st));
+        DEFTET_LAUNCH(k_face_pairs, dim3(blocks_for(L.cap, 256)), dim3(256), st, xb, F, L.grid, eps, L.pairOff, L.wideOff, L.pkey,
                       L.pval, L.wide, L.nWide, L.cap, perm, L.wideBox);
         // stable sort of the (tile, face) pairs by tile — of the pairs really produced (pairOff[F], known on the device
         // only): the workgroups beyond that count find nothing to do (rounds 1-2 sorted the whole F * 16 capacity)
-        RAST_TRY((prims::radix_sort<unsigned, unsigned>(L.pkey, L.skey, L.pval, L.list, (size_t)L.cap, 13, L.tmp, L.tmpBytes, st,
-                                                        (const int *)(L.pairOff + F))));
+        DEFTET_TRY(prims::radix_sort<unsigned, unsigned>(L.pkey, L.skey, L.pval, L.list, (size_t)L.cap, 13, L.tmp, L.tmpBytes, st,
+                                                         (const int *)(L.pairOff + F)));
         DEFTET_LAUNCH(k_tile_starts, dim3((L.nTiles + 256) / 256), dim3(256), st, (const unsigned *)L.skey, (const int *)(L.pairOff + F), L.nTiles,
                       L.tileStart);
     } else {
         DEFTET_HIP(hipMemsetAsync(L.tileStart, 0, ((size_t)L.nTiles + 2) * 4, st));
         DEFTET_HIP(hipMemsetAsync(L.nWide, 0, 16, st));
     }
-    DEFTET_LAUNCH(k_pix_keys, dim3((P + 255) / 256), dim3(256), st, pb, P, L.grid, L.xkey, L.xval);
-    RAST_TRY((prims::radix_sort<unsigned, unsigned>(L.xkey, L.xskey, L.xval, L.pixOrder, (size_t)P, 15, L.tmp, L.tmpBytes, st)));
-    DEFTET_LAUNCH(k_pix_chunks, dim3((L.nTiles + 2 + 255) / 256), dim3(256), st, (const unsigned *)L.xskey, P, L.nTiles, L.pixStart,
+    DEFTET_LAUNCH(k_pix_keys, dim3(blocks_for(P, 256)), dim3(256), st, pb, P, L.grid, L.xkey, L.xval);
+    DEFTET_TRY(prims::radix_sort<unsigned, unsigned>(L.xkey, L.xskey, L.xval, L.pixOrder, (size_t)P, 15, L.tmp, L.tmpBytes, st));
+    DEFTET_LAUNCH(k_pix_chunks, dim3(blocks_for(L.nTiles + 2, 256)), dim3(256), st, (const unsigned *)L.xskey, P, L.nTiles, L.pixStart,
                   L.chunkCount);
-    RAST_TRY((prims::scan<int, prims::Plus, true>(L.chunkCount, L.chunkStart, (size_t)L.nTiles + 2, 0, prims::Plus(), L.tmp, L.tmpBytes, st)));
-#undef RAST_TRY
+    DEFTET_TRY(prims::scan<int, prims::Plus, true>(L.chunkCount, L.chunkStart, (size_t)L.nTiles + 2, 0, prims::Plus(), L.tmp, L.tmpBytes, st));
     {
         const long long maxChunks = (long long)(P + 63) / 64 + L.nTiles + 1;     // every tile may end with a partial chunk
         if (nearest)
-            DEFTET_LAUNCH(k_pix_raster<true>, dim3((unsigned)((maxChunks + 3) / 4)), dim3(256), st, pb, rb, zb, xb, P, L.nTiles, L.tileStart,
+            DEFTET_LAUNCH(k_pix_raster<true>, dim3(blocks_for(maxChunks, 4)), dim3(256), st, pb, rb, zb, xb, P, L.nTiles, L.tileStart,
                           (const int *)L.list, L.wide, L.nWide, F, knum, eps, L.hits, L.nhit, (const unsigned *)L.pixOrder,
                           (const int *)L.pixStart, (const int *)L.chunkStart, (const unsigned *)L.zAbsMax, (const float4 *)L.wideBox);
         else
-            DEFTET_LAUNCH(k_pix_raster<false>, dim3((unsigned)((maxChunks + 3) / 4)), dim3(256), st, pb, rb, zb, xb, P, L.nTiles, L.tileStart,
+            DEFTET_LAUNCH(k_pix_raster<false>, dim3(blocks_for(maxChunks, 4)), dim3(256), st, pb, rb, zb, xb, P, L.nTiles, L.tileStart,
                           (const int *)L.list, L.wide, L.nWide, F, knum, eps, L.hits, L.nhit, (const unsigned *)L.pixOrder,
                           (const int *)L.pixStart, (const int *)L.chunkStart, (const unsigned *)L.zAbsMax, (const float4 *)L.wideBox);
     }
@@ -1497,18 +1491,14 @@ extern "C" int deftet_sparse_render_fwd_policy_f32(const float *pix, const float
     if (B == 0 || P == 0 || knum == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(pix && rng && out_feat && out_face && (F == 0 || (fz && fxy && feat)), "null pointer");
     DEFTET_CHECK_ARG(((uintptr_t)fxy & 7) == 0, "face_vertices_image must be 8-byte aligned");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0, "workspace null or misaligned");
     Layout L = make_layout(P, F, knum, workspace, wsb);
-    DEFTET_CHECK_ARG(L.bytes <= wsb, "workspace too small: need %zu bytes, got %zu", L.bytes, wsb);
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, L.bytes));
     hipStream_t st = as_stream(stream_);
     for (int b = 0; b < B; ++b) {
         const float *pb = pix + (size_t)b * P * 2, *rb = rng + (size_t)b * P * 2;
         const float *zb = fz + (size_t)b * F * 3, *xb = fxy + (size_t)b * F * 6, *fb = feat + (size_t)b * F * 3 * D;
-        {
-            const int rc = raster_hits(pb, rb, zb, xb, P, F, knum, eps, policy, L, st);
-            if (rc != DEFTET_OK) return rc;
-        }
-        DEFTET_LAUNCH(k_pix_emit, dim3((P + 3) / 4), dim3(256), st, L.hits, L.nhit, fb, P, D, knum,
+        DEFTET_TRY(raster_hits(pb, rb, zb, xb, P, F, knum, eps, policy, L, st));
+        DEFTET_LAUNCH(k_pix_emit, dim3(blocks_for(P, 4)), dim3(256), st, L.hits, L.nhit, fb, P, D, knum,
                       out_feat + (size_t)b * P * knum * D, (long long *)out_face + (size_t)b * P * knum,
                       out_w ? out_w + (size_t)b * P * knum * 3 : nullptr);
     }
@@ -1530,17 +1520,14 @@ template <class KeyLoad>
 static int reduce_by_face(KeyLoad keys, const float *pix, const float *fxy, const float *feat, const float *gout, float *gxy,
                           float *gfeat, long long n, int F, int D, int knum, float eps, const BwdLayout &L, hipStream_t st)
 {
-    {
-        const int rc = prims::radix_sort_from<unsigned, unsigned>(keys, L.skey, prims::IotaLoad(), L.sval, (size_t)n, L.bits, L.tmp,
-                                                                  L.tmpBytes, st);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(prims::radix_sort_from<unsigned, unsigned>(keys, L.skey, prims::IotaLoad(), L.sval, (size_t)n, L.bits, L.tmp,
+                                                          L.tmpBytes, st));
     // k_bwd_runs is written for four channels and 16-byte loads and stores; everything else takes the run-time-D kernel
     if (D == 4 && (((uintptr_t)feat | (uintptr_t)gout | (uintptr_t)gfeat) & 15) == 0)
-        DEFTET_LAUNCH(k_bwd_runs, dim3((unsigned)((n + kRunBlock - 1) / kRunBlock)), dim3(kRunWaves * 64), st, pix, fxy, feat, gout,
+        DEFTET_LAUNCH(k_bwd_runs, dim3(blocks_for(n, kRunBlock)), dim3(kRunWaves * 64), st, pix, fxy, feat, gout,
                       (const unsigned *)L.skey, (const unsigned *)L.sval, n, F, knum, eps, gxy, gfeat);
     else
-        DEFTET_LAUNCH(k_bwd_sorted, dim3((unsigned)((n + kBwdWaves * 64 - 1) / (kBwdWaves * 64))), dim3(kBwdWaves * 64), st, pix, fxy,
+        DEFTET_LAUNCH(k_bwd_sorted, dim3(blocks_for(n, kBwdWaves * 64)), dim3(kBwdWaves * 64), st, pix, fxy,
                       feat, gout, (const unsigned *)L.skey, (const unsigned *)L.sval, n, F, D, knum, eps, gxy, gfeat);
     return DEFTET_OK;
 }
@@ -1567,14 +1554,12 @@ extern "C" int deftet_sparse_render_bwd_f32(const float *pix, const float *fxy, 
     DEFTET_HIP(hipMemsetAsync(gfeat, 0, (size_t)B * F * 3 * D * sizeof(float), st));
     if (n == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(pix && face_idx && gout, "null pointer");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0, "backward workspace null or misaligned");
     BwdLayout L = make_bwd_layout(P, F, knum, workspace, wsb);
-    DEFTET_CHECK_ARG(L.bytes <= wsb, "backward workspace too small: need %zu bytes, got %zu", L.bytes, wsb);
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, L.bytes));
     for (int b = 0; b < B; ++b) {
-        const int rc = reduce_by_face(FaceKeyLoad{(const long long *)face_idx + (size_t)b * n, F}, pix + (size_t)b * P * 2,
-                                      fxy + (size_t)b * F * 6, feat + (size_t)b * F * 3 * D, gout + (size_t)b * n * D,
-                                      gxy + (size_t)b * F * 6, gfeat + (size_t)b * F * 3 * D, n, F, D, knum, eps, L, st);
-        if (rc != DEFTET_OK) return rc;
+        DEFTET_TRY(reduce_by_face(FaceKeyLoad{(const long long *)face_idx + (size_t)b * n, F}, pix + (size_t)b * P * 2,
+                                  fxy + (size_t)b * F * 6, feat + (size_t)b * F * 3 * D, gout + (size_t)b * n * D,
+                                  gxy + (size_t)b * F * 6, gfeat + (size_t)b * F * 3 * D, n, F, D, knum, eps, L, st));
     }
     return DEFTET_OK;
 }
@@ -1604,31 +1589,26 @@ extern "C" int deftet_sparse_render_composite_fwd_f32(const float *pix, const fl
                                                       float *out_coverage, float *out_depth, int32_t *out_face, void *workspace,
                                                       size_t wsb, void *stream_)
 {
-    {
-        const int rc = composite_sizes_ok(B, P, F, D, knum, depth_channel);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(composite_sizes_ok(B, P, F, D, knum, depth_channel));
     DEFTET_CHECK_ARG(policy == DEFTET_RASTER_NEAREST || policy == DEFTET_RASTER_FIRST, "unknown saturation policy %d", policy);
     if (B == 0 || P == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(pix && rng && out_colour && out_coverage && (!depth_channel || out_depth) && (knum == 0 || out_face) &&
                          (F == 0 || (fz && fxy && feat)),
                      "null pointer");
     DEFTET_CHECK_ARG(((uintptr_t)fxy & 7) == 0, "face_vertices_image must be 8-byte aligned");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0, "workspace null or misaligned");
     Layout L = make_layout(P, F, knum, workspace, wsb);
-    DEFTET_CHECK_ARG(L.bytes <= wsb, "workspace too small: need %zu bytes, got %zu", L.bytes, wsb);
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, L.bytes));
     hipStream_t st = as_stream(stream_);
     const int Dc = D - (depth_channel ? 2 : 1);
     for (int b = 0; b < B; ++b) {
         const float *pb = pix + (size_t)b * P * 2, *rb = rng + (size_t)b * P * 2;
         const float *zb = fz + (size_t)b * F * 3, *xb = fxy + (size_t)b * F * 6, *fb = feat + (size_t)b * F * 3 * D;
         if (knum > 0) {
-            const int rc = raster_hits(pb, rb, zb, xb, P, F, knum, eps, policy, L, st);
-            if (rc != DEFTET_OK) return rc;
+            DEFTET_TRY(raster_hits(pb, rb, zb, xb, P, F, knum, eps, policy, L, st));
         } else {
             DEFTET_HIP(hipMemsetAsync(L.nhit, 0, (size_t)P * sizeof(int), st));       // no slots: every pixel is background
         }
-        DEFTET_LAUNCH(k_pix_composite, dim3((P + 3) / 4), dim3(256), st, L.hits, L.nhit, fb, P, D, knum, depth_channel ? 1 : 0,
+        DEFTET_LAUNCH(k_pix_composite, dim3(blocks_for(P, 4)), dim3(256), st, L.hits, L.nhit, fb, P, D, knum, depth_channel ? 1 : 0,
                       background, far_depth, out_colour + (size_t)b * P * Dc, out_coverage + (size_t)b * P,
                       depth_channel ? out_depth + (size_t)b * P : nullptr, out_face + (size_t)b * P * knum);
     }
@@ -1666,20 +1646,16 @@ extern "C" int deftet_sparse_render_composite_bwd_f32(const float *pix, const fl
                                                       float far_depth, float *gxy, float *gfeat, void *workspace, size_t wsb,
                                                       void *stream_)
 {
-    {
-        const int rc = composite_sizes_ok(B, P, F, D, knum, depth_channel);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(composite_sizes_ok(B, P, F, D, knum, depth_channel));
     if (B == 0 || F == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(fxy && feat && gxy && gfeat, "null pointer");
     const long long n = (long long)P * knum;
     if (n > 0) {
         DEFTET_CHECK_ARG(pix && face, "null pointer");
         DEFTET_CHECK_ARG(((uintptr_t)fxy & 7) == 0 && ((uintptr_t)pix & 7) == 0, "face_vertices_image and pixel_coords must be 8-byte aligned");
-        DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0, "backward workspace null or misaligned");
     }
     CompositeBwdLayout L = make_composite_bwd_layout(P, F, D, knum, n > 0 ? workspace : nullptr, wsb);
-    DEFTET_CHECK_ARG(n == 0 || L.bytes <= wsb, "backward workspace too small: need %zu bytes, got %zu", L.bytes, wsb);
+    if (n > 0) DEFTET_TRY(workspace_ok(__func__, workspace, wsb, L.bytes));
     hipStream_t st = as_stream(stream_);
     DEFTET_HIP(hipMemsetAsync(gxy, 0, (size_t)B * F * 6 * sizeof(float), st));
     DEFTET_HIP(hipMemsetAsync(gfeat, 0, (size_t)B * F * 3 * D * sizeof(float), st));
@@ -1688,13 +1664,12 @@ extern "C" int deftet_sparse_render_composite_bwd_f32(const float *pix, const fl
     for (int b = 0; b < B; ++b) {
         const float *pb = pix + (size_t)b * P * 2, *xb = fxy + (size_t)b * F * 6, *fb = feat + (size_t)b * F * 3 * D;
         const int32_t *face_b = face + (size_t)b * n;
-        DEFTET_LAUNCH(k_pix_composite_bwd, dim3((P + 3) / 4), dim3(256), st, pb, xb, fb, (const int *)face_b,
+        DEFTET_LAUNCH(k_pix_composite_bwd, dim3(blocks_for(P, 4)), dim3(256), st, pb, xb, fb, (const int *)face_b,
                       g_colour ? g_colour + (size_t)b * P * Dc : nullptr, g_coverage ? g_coverage + (size_t)b * P : nullptr,
                       (depth_channel && g_depth) ? g_depth + (size_t)b * P : nullptr, P, F, D, knum, eps, depth_channel ? 1 : 0,
                       background, far_depth, L.gout);
-        const int rc = reduce_by_face(FaceKeyLoad32{(const int *)face_b, F}, pb, xb, fb, L.gout, gxy + (size_t)b * F * 6,
-                                      gfeat + (size_t)b * F * 3 * D, n, F, D, knum, eps, L.sort, st);
-        if (rc != DEFTET_OK) return rc;
+        DEFTET_TRY(reduce_by_face(FaceKeyLoad32{(const int *)face_b, F}, pb, xb, fb, L.gout, gxy + (size_t)b * F * 6,
+                                  gfeat + (size_t)b * F * 3 * D, n, F, D, knum, eps, L.sort, st));
     }
     return DEFTET_OK;
 }

@@ -165,7 +165,7 @@ extern "C" int deftet_rowdot2_f32(const float *a, const float *b, long long n_co
     DEFTET_CHECK_ARG(n_rows >= 0 && n_cols >= 0 && n_cols2 >= 0 && n_rows <= 65535, "bad size");
     if (n_rows == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(a && out, "null pointer");
-    DEFTET_CHECK_ARG(workspace && workspace_bytes >= deftet_rowdot_workspace_bytes(n_rows), "workspace null or too small");
+    DEFTET_TRY(deftet::workspace_ok(__func__, workspace, workspace_bytes, deftet_rowdot_workspace_bytes(n_rows), 1));
     hipStream_t st = deftet::as_stream(stream_);
     float *part = static_cast<float *>(workspace);
     const int slot = n_rows <= deftet::red::kTicketRows ? deftet::ticket_slot_for_stream(st, deftet::red::kTicketSlots) : -1;
@@ -194,7 +194,7 @@ extern "C" int deftet_sqrt_rowsum_f32(const float *x, float eps, float *out, int
     DEFTET_CHECK_ARG(n_rows >= 0 && n_cols >= 0 && n_rows <= 65535, "bad size");
     if (n_rows == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(x && out, "null pointer");
-    DEFTET_CHECK_ARG(workspace && workspace_bytes >= deftet_rowdot_workspace_bytes(n_rows), "workspace null or too small");
+    DEFTET_TRY(deftet::workspace_ok(__func__, workspace, workspace_bytes, deftet_rowdot_workspace_bytes(n_rows), 1));
     hipStream_t st = deftet::as_stream(stream_);
     float *part = static_cast<float *>(workspace);
     const int slot = n_rows <= deftet::red::kTicketRows ? deftet::ticket_slot_for_stream(st, deftet::red::kTicketSlots) : -1;

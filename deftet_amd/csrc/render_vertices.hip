@@ -210,10 +210,10 @@ extern "C" int deftet_project_vertices_fwd_f32(const float *pos, const float *fe
                                                const float *proj, float multiplier, int depth_channel, float *z, float *xy, float *act,
                                                int B, int V, int D, int pos_batch, int feat_batch, void *stream_)
 {
-    if (const int rc = check_project_sizes(B, V, D, pos_batch, feat_batch)) return rc;
+    DEFTET_TRY(check_project_sizes(B, V, D, pos_batch, feat_batch));
     if (B == 0 || V == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(pos && feat && rot && cam_pos && proj && z && xy && act, "null pointer");
-    DEFTET_LAUNCH(rv::k_project_fwd, dim3((V + 255) / 256, B), dim3(256), as_stream(stream_), pos, feat, rot, cam_pos, proj, multiplier,
+    DEFTET_LAUNCH(rv::k_project_fwd, dim3(blocks_for(V, 256), B), dim3(256), as_stream(stream_), pos, feat, rot, cam_pos, proj, multiplier,
                   depth_channel ? 1 : 0, z, xy, act, V, D, pos_batch, feat_batch);
     return DEFTET_OK;
 }
@@ -223,10 +223,10 @@ extern "C" int deftet_project_vertices_bwd_f32(const float *g_xy, const float *g
                                                float *grad_pos, float *grad_feat, int B, int V, int D, int pos_batch, int feat_batch,
                                                void *stream_)
 {
-    if (const int rc = check_project_sizes(B, V, D, pos_batch, feat_batch)) return rc;
+    DEFTET_TRY(check_project_sizes(B, V, D, pos_batch, feat_batch));
     if (B == 0 || V == 0 || (!grad_pos && !grad_feat)) return DEFTET_OK;
     DEFTET_CHECK_ARG(pos && feat && rot && cam_pos && proj, "null pointer");
-    DEFTET_LAUNCH(rv::k_project_bwd, dim3((V + 255) / 256, B), dim3(256), as_stream(stream_), g_xy, g_act, pos, feat, rot, cam_pos, proj,
+    DEFTET_LAUNCH(rv::k_project_bwd, dim3(blocks_for(V, 256), B), dim3(256), as_stream(stream_), g_xy, g_act, pos, feat, rot, cam_pos, proj,
                   multiplier, depth_channel ? 1 : 0, grad_pos, grad_feat, B, V, D, pos_batch, feat_batch);
     return DEFTET_OK;
 }
@@ -244,12 +244,12 @@ static int check_gather_sizes(int B, int V, int F, int Do)
 extern "C" int deftet_face_gather_fwd_f32(const float *z, const float *xy, const float *act, const int64_t *face_idx, float *face_z,
                                           float *face_xy, float *face_feat, int32_t *bad_flag, int B, int V, int F, int Do, void *stream_)
 {
-    if (const int rc = check_gather_sizes(B, V, F, Do)) return rc;
+    DEFTET_TRY(check_gather_sizes(B, V, F, Do));
     if (B == 0 || F == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(face_idx && face_z && face_xy && face_feat && (V == 0 || (z && xy && act)), "null pointer");
     DEFTET_CHECK_ARG(((uintptr_t)xy & 7) == 0 && ((uintptr_t)face_xy & 7) == 0, "xy/face_xy must be 8-byte aligned");
     const long long n3 = (long long)3 * F;
-    DEFTET_LAUNCH(rv::k_face_gather_fwd, dim3((unsigned)((n3 * (2 + Do) + 255) / 256), B), dim3(256), as_stream(stream_), z, xy, act,
+    DEFTET_LAUNCH(rv::k_face_gather_fwd, dim3(blocks_for(n3 * (2 + Do), 256), B), dim3(256), as_stream(stream_), z, xy, act,
                   face_idx, face_z, face_xy, face_feat, V, n3, Do, bad_flag);
     return DEFTET_OK;
 }
@@ -257,10 +257,10 @@ extern "C" int deftet_face_gather_fwd_f32(const float *z, const float *xy, const
 extern "C" int deftet_face_gather_bwd_f32(const float *grad_face_xy, const float *grad_face_feat, const int32_t *offsets,
                                           const int32_t *slots, float *g_xy, float *g_act, int B, int V, int F, int Do, void *stream_)
 {
-    if (const int rc = check_gather_sizes(B, V, F, Do)) return rc;
+    DEFTET_TRY(check_gather_sizes(B, V, F, Do));
     if (B == 0 || V == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(offsets && g_xy && g_act && (F == 0 || slots), "null pointer");
-    const unsigned wgs = (unsigned)((((long long)V * (2 + Do) + 255) / 256 + 7) / 8 * 8);
+    const unsigned wgs = (unsigned)align_up(blocks_for((long long)V * (2 + Do), 256), 8);
     DEFTET_LAUNCH(rv::k_face_gather_bwd, dim3(wgs, B), dim3(256), as_stream(stream_), grad_face_xy, grad_face_feat, offsets, slots, g_xy,
                   g_act, V, (long long)3 * F, Do);
     return DEFTET_OK;

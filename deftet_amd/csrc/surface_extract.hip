@@ -259,7 +259,7 @@ extern "C" int deftet_tet_face_neighbours_i64(const int64_t *tetidx_fx2, const i
     if (nbr_tx4) DEFTET_HIP(hipMemsetAsync(nbr_tx4, 0xFF, (size_t)T * 32, st));
     if (nbr32_tx4) DEFTET_HIP(hipMemsetAsync(nbr32_tx4, 0xFF, (size_t)T * 16, st));
     if (n_face > 0)
-        DEFTET_LAUNCH(k_face_nbr_scatter, dim3((n_face + 255) / 256), dim3(256), st, (const long long *)tetidx_fx2,
+        DEFTET_LAUNCH(k_face_nbr_scatter, dim3(blocks_for(n_face, 256)), dim3(256), st, (const long long *)tetidx_fx2,
                       (const long long *)tetfaceidx_fx2, n_face, T, (long long *)nbr_tx4, (int *)nbr32_tx4);
     return DEFTET_OK;
 }
@@ -314,8 +314,7 @@ int check_shape(int B, int T, int mode, double htres, const void *nbr, void *wor
     DEFTET_CHECK_ARG(mode == DEFTET_SX_BINARY || htres == htres, "htres is NaN");
     DEFTET_CHECK_ARG(nbr && ((uintptr_t)nbr & 15) == 0, "null or misaligned pointer: nbr32_tx4");
     W = carve(workspace, B, T, with_w);
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && W.bytes <= wsb,
-                     "workspace null, misaligned or smaller than deftet_surface_extract_workspace_bytes");
+    DEFTET_TRY(workspace_ok("deftet_surface_extract*", workspace, wsb, W.bytes));
     return DEFTET_OK;
 }
 }  // namespace
@@ -331,10 +330,7 @@ extern "C" int deftet_surface_extract_count_f32(const float *occ_bxt, const floa
 {
     const int with_w = weights_bxv != nullptr;
     Ws W;
-    {
-        const int rc = check_shape(B, T, mode, htres, nbr32_tx4, workspace, wsb, with_w, W);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(check_shape(B, T, mode, htres, nbr32_tx4, workspace, wsb, with_w, W));
     DEFTET_CHECK_ARG(offsets, "null pointer: offsets");
     DEFTET_CHECK_ARG((occ_bxt != nullptr) != (weights_bxv != nullptr), "exactly one of occ_bxt and weights_bxv");
     DEFTET_CHECK_ARG(!with_w || (tet_idx_tx4 && ((uintptr_t)tet_idx_tx4 & 15) == 0 && V > 0),
@@ -343,13 +339,10 @@ extern "C" int deftet_surface_extract_count_f32(const float *occ_bxt, const floa
     const int nblk = sx_nblk(T);
     DEFTET_HIP(hipMemsetAsync(W.bad, 0, 4, st));
     if (with_w)
-        DEFTET_LAUNCH(k_sx_occ_max, dim3((T + 255) / 256, B), dim3(256), st, weights_bxv, (const int4 *)tet_idx_tx4, V, T, W.occ, W.bad);
+        DEFTET_LAUNCH(k_sx_occ_max, dim3(blocks_for(T, 256), B), dim3(256), st, weights_bxv, (const int4 *)tet_idx_tx4, V, T, W.occ, W.bad);
     Pred p{(const int4 *)nbr32_tx4, with_w ? W.occ : occ_bxt, T, mode, htres, (float)(htres * 2.0)};
     DEFTET_LAUNCH(k_sx_count, dim3(nblk, B), dim3(kThreads), st, p, nblk, B, W.pos, W.bad);
-    {
-        const int rc = prims::scan<int, prims::Plus, true>(W.pos, W.pos, W.n, 0, prims::Plus(), W.tmp, W.tmp_bytes, st);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(prims::scan<int, prims::Plus, true>(W.pos, W.pos, W.n, 0, prims::Plus(), W.tmp, W.tmp_bytes, st));
     DEFTET_LAUNCH(k_sx_offsets, dim3((B + 256) / 256), dim3(256), st, (const int *)W.pos, nblk, B, W.bad, with_w ? kOccFused : kOccGiven, offsets);
     return DEFTET_OK;
 }
@@ -361,10 +354,7 @@ extern "C" int deftet_surface_extract_fill_f32(const float *tet_bxtx4x3, const f
 {
     const int with_w = occ_bxt == nullptr;                             // the count pass left the fused occupancy in the workspace
     Ws W;
-    {
-        const int rc = check_shape(B, T, mode, htres, nbr32_tx4, workspace, wsb, with_w, W);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(check_shape(B, T, mode, htres, nbr32_tx4, workspace, wsb, with_w, W));
     DEFTET_CHECK_ARG(capacity >= 0, "negative capacity");
     DEFTET_CHECK_ARG(!attr_bxtx4xc || (C >= 1 && C <= 8), "n_attr=%d outside 1..8", C);
     DEFTET_CHECK_ARG(!faces || tet_idx_tx4, "null pointer: faces needs tet_idx_tx4");
@@ -400,19 +390,15 @@ extern "C" int deftet_surface_weld_f32(const int64_t *faces_fx3, long long n_fac
     DEFTET_CHECK_ARG((long long)capacity >= (n_face * 3 < (long long)V ? n_face * 3 : (long long)V),
                      "capacity=%d below min(n_vertex, 3 n_face)", capacity);
     const WeldWs W = weld_carve(workspace, V);
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && W.bytes <= wsb,
-                     "workspace null, misaligned or smaller than deftet_surface_weld_workspace_bytes");
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, W.bytes));
     const long long n = n_face * 3;
     DEFTET_HIP(hipMemsetAsync(W.flag, 0, ((size_t)V + 1) * 4, st));
     DEFTET_HIP(hipMemsetAsync(n_out, 0, 8, st));
-    DEFTET_LAUNCH(k_weld_flag, dim3((unsigned)((n + 255) / 256)), dim3(256), st, (const long long *)faces_fx3, n, V, W.flag, n_out);
-    {
-        const int rc = prims::scan<int, prims::Plus, true>(W.flag, W.flag, (size_t)V + 1, 0, prims::Plus(), W.tmp, W.tmp_bytes, st);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_LAUNCH(k_weld_flag, dim3(blocks_for(n, 256)), dim3(256), st, (const long long *)faces_fx3, n, V, W.flag, n_out);
+    DEFTET_TRY(prims::scan<int, prims::Plus, true>(W.flag, W.flag, (size_t)V + 1, 0, prims::Plus(), W.tmp, W.tmp_bytes, st));
     DEFTET_LAUNCH(k_weld_gather, dim3((V + 256) / 256), dim3(256), st, (const int *)W.flag, verts_vx3, attr_vxc, C, V, capacity,
                   (long long *)old_id, verts_out, attr_out, n_out);
-    DEFTET_LAUNCH(k_weld_remap, dim3((unsigned)((n + 255) / 256)), dim3(256), st, (const long long *)faces_fx3, n, V, (const int *)W.flag,
+    DEFTET_LAUNCH(k_weld_remap, dim3(blocks_for(n, 256)), dim3(256), st, (const long long *)faces_fx3, n, V, (const int *)W.flag,
                   (long long *)faces_out);
     return DEFTET_OK;
 }

@@ -236,13 +236,13 @@ int deftet_tet_centroid_sample_fwd_f32(const float *const *vols, const int *chan
     const int B = n_batch, V = n_vertex, T = n_tet, K = n_slot;
     TcsVolumes vv{};
     int C_feat = 0;
-    if (int rc = check_volumes(vols, channels, resolutions, n_vol, B, B > 0 && K > 0, vv, C_feat, "tet_centroid_sample")) return rc;
-    if (int rc = check_mesh(B, V, T, K, idx_batch, select, first, "tet_centroid_sample")) return rc;
+    DEFTET_TRY(check_volumes(vols, channels, resolutions, n_vol, B, B > 0 && K > 0, vv, C_feat, "tet_centroid_sample"));
+    DEFTET_TRY(check_mesh(B, V, T, K, idx_batch, select, first, "tet_centroid_sample"));
     if (B == 0 || K == 0) return DEFTET_OK;
     const int C_total = C_feat + (append_pos ? 3 : 0);
     DEFTET_CHECK_ARG(pos && tet_idx && centroids && (out || C_total == 0), "tet_centroid_sample: null pointer");
     DEFTET_CHECK_ARG(((uintptr_t)tet_idx & 15) == 0, "tet_centroid_sample: tet_idx must be 16-byte aligned");
-    const unsigned gK = (unsigned)((K + kPvBlock - 1) / kPvBlock);
+    const unsigned gK = blocks_for(K, kPvBlock);
     // channels per table row: a few thousand workgroups, and no more rows than the table holds
     int c_per = C_feat > 0 ? channels_per_thread(C_feat, (long long)gK * B) : 1;
     const int c_min = (C_feat + (kTcsMaxChunk - kTcsMaxVol) - 1) / (kTcsMaxChunk - kTcsMaxVol);
@@ -268,13 +268,13 @@ int deftet_tet_centroid_sample_bwd_pos_f32(const float *const *vols, const int *
     const int B = n_batch, K = n_slot;
     TcsVolumes vv{};
     int C_feat = 0;
-    if (int rc = check_volumes(vols, channels, resolutions, n_vol, B, B > 0 && K > 0, vv, C_feat, "tet_centroid_sample_bwd_pos")) return rc;
+    DEFTET_TRY(check_volumes(vols, channels, resolutions, n_vol, B, B > 0 && K > 0, vv, C_feat, "tet_centroid_sample_bwd_pos"));
     DEFTET_CHECK_ARG(B >= 0 && K >= 0, "tet_centroid_sample_bwd_pos: negative size");
     if (B > 65535 || (long long)B * K >= 0x7FFFFFFFll) return set_error(DEFTET_ELIMIT, "tet_centroid_sample_bwd_pos: more than 65535 shapes or B K past 31 bits");
     if (B == 0 || K == 0) return DEFTET_OK;
     const int C_total = C_feat + (append_pos ? 3 : 0);
     DEFTET_CHECK_ARG(centroids && grad_cent && (grad_out || C_total == 0), "tet_centroid_sample_bwd_pos: null pointer");
-    DEFTET_LAUNCH(k_tcs_bwd_pos, dim3((unsigned)((K + 63) / 64), (unsigned)B), dim3(64, (unsigned)(n_vol > 0 ? n_vol : 1)), as_stream(stream), vv,
+    DEFTET_LAUNCH(k_tcs_bwd_pos, dim3(blocks_for(K, 64), (unsigned)B), dim3(64, (unsigned)(n_vol > 0 ? n_vol : 1)), as_stream(stream), vv,
                   centroids, grad_out, grad_cent, K, C_feat, C_total);
     return DEFTET_OK;
 }
@@ -284,20 +284,19 @@ int deftet_tet_centroid_sample_bwd_vertices_f32(const float *grad_cent, const in
                                                 int accumulate, void *workspace, size_t workspace_bytes, void *stream)
 {
     const int B = n_batch, V = n_vertex, T = n_tet, K = n_slot;
-    if (int rc = check_mesh(B, V, T, K, idx_batch, select, first, "tet_centroid_sample_bwd_vertices")) return rc;
+    DEFTET_TRY(check_mesh(B, V, T, K, idx_batch, select, first, "tet_centroid_sample_bwd_vertices"));
     const bool sorted = select != nullptr && K > 0;
     const TcsLayout L = tcs_layout((size_t)T, (size_t)K, workspace);
-    if (sorted && (!workspace || ((uintptr_t)workspace & 255) != 0 || workspace_bytes < L.bytes))
-        return set_error(DEFTET_EINVAL, "tet_centroid_sample_bwd_vertices: workspace missing, misaligned or too small");
+    if (sorted) DEFTET_TRY(workspace_ok(__func__, workspace, workspace_bytes, L.bytes));
     if (B == 0 || V == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(offsets && grad_pos && (T == 0 || slots) && (K == 0 || grad_cent), "tet_centroid_sample_bwd_vertices: null pointer");
     hipStream_t st = as_stream(stream);
     if (sorted) {
-        DEFTET_LAUNCH(k_tcs_keys, dim3((unsigned)((K + kPvBlock - 1) / kPvBlock)), dim3(kPvBlock), st, select, L.s.keys, K, T);
-        if (int rc = sort_and_segment(L.s, L.perm, L.seg, (size_t)K, (unsigned)T, st)) return rc;
+        DEFTET_LAUNCH(k_tcs_keys, dim3(blocks_for(K, kPvBlock)), dim3(kPvBlock), st, select, L.s.keys, K, T);
+        DEFTET_TRY(sort_and_segment(L.s, L.perm, L.seg, (size_t)K, (unsigned)T, st));
     }
     // without a selection and without slots (K = 0) the walk finds no slot and writes the zeros itself
-    DEFTET_LAUNCH(k_tcs_bwd_vertices, dim3((unsigned)((V + kPvBlock - 1) / kPvBlock), (unsigned)B), dim3(kPvBlock), st, grad_cent, offsets,
+    DEFTET_LAUNCH(k_tcs_bwd_vertices, dim3(blocks_for(V, kPvBlock), (unsigned)B), dim3(kPvBlock), st, grad_cent, offsets,
                   slots, sorted ? (const int32_t *)L.seg : (const int32_t *)nullptr, sorted ? (const int32_t *)L.perm : (const int32_t *)nullptr,
                   first, grad_pos, V, K, idx_batch, accumulate);
     return DEFTET_OK;

@@ -258,8 +258,7 @@ int check_shape(const char *who, const void *inside, const void *nbr, int B, int
     DEFTET_CHECK_ARG(nbr && ((uintptr_t)nbr & 15) == 0, "%s: null or misaligned pointer: nbr32_tx4", who);
     DEFTET_CHECK_ARG(bad, "%s: null pointer: bad", who);
     W = carve(workspace, B, T);
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && W.bytes <= wsb,
-                     "%s: workspace null, misaligned or smaller than deftet_tet_components_workspace_bytes", who);
+    DEFTET_TRY(workspace_ok(who, workspace, wsb, W.bytes));
     return DEFTET_OK;
 }
 
@@ -267,7 +266,7 @@ int check_shape(const char *who, const void *inside, const void *nbr, int B, int
 int label(const unsigned char *inside, int invert, const int32_t *nbr, int B, int T, int count_bad, const Ws &W, int *labels, int *count,
           int *bad, hipStream_t st)
 {
-    const dim3 grid((T + kThreads - 1) / kThreads, B), block(kThreads);
+    const dim3 grid(blocks_for(T, kThreads), B), block(kThreads);
     DEFTET_LAUNCH(k_tc_init, grid, block, st, inside, invert, (const int4 *)nbr, T, count_bad, W.parent, W.acc, count, bad);
     DEFTET_LAUNCH(k_tc_hook, grid, block, st, inside, invert, (const int4 *)nbr, T, W.parent, bad);
     DEFTET_LAUNCH(k_tc_flatten, grid, block, st, inside, invert, (const int4 *)nbr, T, W.parent, labels, W.acc, count, bad);
@@ -277,7 +276,7 @@ int label(const unsigned char *inside, int invert, const int32_t *nbr, int B, in
 int finish(const Ws &W, int B, int T, int *sizes, unsigned char *open, hipStream_t st)
 {
     const size_t n = (size_t)B * T;
-    DEFTET_LAUNCH(k_tc_finish, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), st, (const unsigned *)W.acc, n, sizes, open);
+    DEFTET_LAUNCH(k_tc_finish, dim3(blocks_for(n, kThreads)), dim3(kThreads), st, (const unsigned *)W.acc, n, sizes, open);
     return DEFTET_OK;
 }
 }  // namespace
@@ -291,15 +290,11 @@ extern "C" int deftet_tet_components_u8(const uint8_t *inside_bxt, const int32_t
                                         uint8_t *open, int32_t *count, int32_t *bad, void *workspace, size_t wsb, void *stream_)
 {
     Ws W;
-    {
-        const int rc = check_shape("tet_components", inside_bxt, nbr32_tx4, B, T, bad, workspace, wsb, W);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(check_shape("tet_components", inside_bxt, nbr32_tx4, B, T, bad, workspace, wsb, W));
     DEFTET_CHECK_ARG(labels && sizes && open && count, "tet_components: null pointer: labels / sizes / open / count");
     hipStream_t st = as_stream(stream_);
     DEFTET_HIP(hipMemsetAsync(bad, 0, 4, st));
-    int rc = label(inside_bxt, 0, nbr32_tx4, B, T, 1, W, labels, count, bad, st);
-    if (rc != DEFTET_OK) return rc;
+    DEFTET_TRY(label(inside_bxt, 0, nbr32_tx4, B, T, 1, W, labels, count, bad, st));
     return finish(W, B, T, sizes, open, st);
 }
 
@@ -308,29 +303,23 @@ extern "C" int deftet_occupancy_cleanup_u8(const uint8_t *inside_bxt, const int3
                                            int32_t *bad, void *workspace, size_t wsb, void *stream_)
 {
     Ws W;
-    {
-        const int rc = check_shape("occupancy_cleanup", inside_bxt, nbr32_tx4, B, T, bad, workspace, wsb, W);
-        if (rc != DEFTET_OK) return rc;
-    }
+    DEFTET_TRY(check_shape("occupancy_cleanup", inside_bxt, nbr32_tx4, B, T, bad, workspace, wsb, W));
     DEFTET_CHECK_ARG(keep, "occupancy_cleanup: null pointer: keep");
     DEFTET_CHECK_ARG(min_size >= 0, "occupancy_cleanup: min_size=%d is negative", min_size);
     DEFTET_CHECK_ARG((labels != nullptr) == (sizes != nullptr) && (labels != nullptr) == (open != nullptr) &&
                          (labels != nullptr) == (count != nullptr),
                      "occupancy_cleanup: labels, sizes, open and count go together");
     hipStream_t st = as_stream(stream_);
-    const dim3 grid((T + kThreads - 1) / kThreads, B), block(kThreads);
+    const dim3 grid(blocks_for(T, kThreads), B), block(kThreads);
     int *lab = labels ? labels : W.labels, *cnt = count ? count : W.count;
     DEFTET_HIP(hipMemsetAsync(bad, 0, 4, st));
     const uint8_t *mask = inside_bxt;
-    int rc;
     if (fill_voids) {
-        rc = label(inside_bxt, 1, nbr32_tx4, B, T, 1, W, lab, cnt, bad, st);
-        if (rc != DEFTET_OK) return rc;
+        DEFTET_TRY(label(inside_bxt, 1, nbr32_tx4, B, T, 1, W, lab, cnt, bad, st));
         DEFTET_LAUNCH(k_tc_fill, grid, block, st, inside_bxt, (const int *)lab, (const unsigned *)W.acc, T, W.mask);
         mask = W.mask;
     }
-    rc = label(mask, 0, nbr32_tx4, B, T, !fill_voids, W, lab, cnt, bad, st);
-    if (rc != DEFTET_OK) return rc;
+    DEFTET_TRY(label(mask, 0, nbr32_tx4, B, T, !fill_voids, W, lab, cnt, bad, st));
     if (keep_largest) {
         DEFTET_HIP(hipMemsetAsync(W.best, 0, (size_t)B * 8, st));
         DEFTET_LAUNCH(k_tc_best, grid, block, st, (const int *)lab, (const unsigned *)W.acc, T, min_size, W.best);

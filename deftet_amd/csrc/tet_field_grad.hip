@@ -360,8 +360,6 @@ int tfg_check(int B, int V, int T, int C, int idx_batch, const char *what)
     return DEFTET_OK;
 }
 
-inline unsigned tfg_groups(long long n) { return (unsigned)((n + kTfgBlock - 1) / kTfgBlock); }
-
 }  // namespace
 }  // namespace deftet
 
@@ -373,12 +371,12 @@ int deftet_tet_field_gradient_fwd_f32(const float *field, const float *pos, cons
                                       int n_vertex, int n_tet, int idx_batch, int n_channel, void *stream)
 {
     const int B = n_batch, V = n_vertex, T = n_tet, C = n_channel;
-    if (int rc = tfg_check(B, V, T, C, idx_batch, "tet_field_gradient")) return rc;
+    DEFTET_TRY(tfg_check(B, V, T, C, idx_batch, "tet_field_gradient"));
     if (B == 0 || T == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(tet_idx && (out || vol) && (((field || !out) && pos) || V == 0), "tet_field_gradient: null pointer");
     DEFTET_CHECK_ARG(((uintptr_t)tet_idx & 15) == 0, "tet_field_gradient: tet_idx must be 16-byte aligned");
     const int lanes = out ? C : 1;                                    // per tet
-    DEFTET_LAUNCH(k_tfg_fwd, dim3(tfg_groups((long long)T * lanes), (unsigned)B), dim3(kTfgBlock), as_stream(stream), field, pos, tet_idx,
+    DEFTET_LAUNCH(k_tfg_fwd, dim3(blocks_for((long long)T * lanes, kTfgBlock), (unsigned)B), dim3(kTfgBlock), as_stream(stream), field, pos, tet_idx,
                   out, vol, V, T, lanes, idx_batch);
     return DEFTET_OK;
 }
@@ -388,16 +386,16 @@ int deftet_tet_field_gradient_bwd_f32(const float *grad_out, const float *grad_v
                                       float *grad_pos, int n_batch, int n_vertex, int n_tet, int idx_batch, int n_channel, void *stream)
 {
     const int B = n_batch, V = n_vertex, T = n_tet, C = n_channel;
-    if (int rc = tfg_check(B, V, T, C, idx_batch, "tet_field_gradient_bwd")) return rc;
+    DEFTET_TRY(tfg_check(B, V, T, C, idx_batch, "tet_field_gradient_bwd"));
     if (B == 0 || V == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(field && pos && offsets && (T == 0 || (tet_idx && slots && grad_out)), "tet_field_gradient_bwd: null pointer");
     DEFTET_CHECK_ARG(((uintptr_t)tet_idx & 15) == 0, "tet_field_gradient_bwd: tet_idx must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
     if (grad_field)
-        DEFTET_LAUNCH(k_tfg_bwd_field, dim3(tfg_groups((long long)V * C), (unsigned)B), dim3(kTfgBlock), st, grad_out, grad_vol, field, pos,
+        DEFTET_LAUNCH(k_tfg_bwd_field, dim3(blocks_for((long long)V * C, kTfgBlock), (unsigned)B), dim3(kTfgBlock), st, grad_out, grad_vol, field, pos,
                       tet_idx, offsets, slots, grad_field, V, T, C, idx_batch);
     if (grad_pos)
-        DEFTET_LAUNCH(k_tfg_bwd_pos, dim3(tfg_groups(V), (unsigned)B), dim3(kTfgBlock), st, grad_out, grad_vol, field, pos, tet_idx, offsets,
+        DEFTET_LAUNCH(k_tfg_bwd_pos, dim3(blocks_for(V, kTfgBlock), (unsigned)B), dim3(kTfgBlock), st, grad_out, grad_vol, field, pos, tet_idx, offsets,
                       slots, grad_pos, V, T, C, idx_batch);
     return DEFTET_OK;
 }
@@ -414,11 +412,10 @@ int deftet_tet_field_energies_fwd_f32(const float *field, const float *pos, cons
     const int B = n_batch, V = n_vertex, T = n_tet, C = n_channel;
     if (C < 1 || C > kTfeMaxC)
         return set_error(DEFTET_EINVAL, "tet_field_energies: between 1 and %d channels expected (got %d)", kTfeMaxC, C);
-    if (int rc = tfg_check(B, V, T, C, idx_batch, "tet_field_energies")) return rc;
+    DEFTET_TRY(tfg_check(B, V, T, C, idx_batch, "tet_field_energies"));
     const TfeLayout L = tfe_layout((size_t)B, workspace);
-    if (B > 0 && (!workspace || ((uintptr_t)workspace & 255) != 0 || workspace_bytes < L.bytes))
-        return set_error(DEFTET_EINVAL, "tet_field_energies: workspace missing, misaligned or too small");
     if (B == 0) return DEFTET_OK;
+    DEFTET_TRY(workspace_ok(__func__, workspace, workspace_bytes, L.bytes));
     DEFTET_CHECK_ARG(out && stats && (T == 0 || tet_idx) && ((field && pos) || V == 0 || T == 0), "tet_field_energies: null pointer");
     DEFTET_CHECK_ARG(((uintptr_t)tet_idx & 15) == 0, "tet_field_energies: tet_idx must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
@@ -434,16 +431,16 @@ int deftet_tet_field_energies_bwd_f32(const double *stats, const float *grad_out
     const int B = n_batch, V = n_vertex, T = n_tet, C = n_channel;
     if (C < 1 || C > kTfeMaxC)
         return set_error(DEFTET_EINVAL, "tet_field_energies_bwd: between 1 and %d channels expected (got %d)", kTfeMaxC, C);
-    if (int rc = tfg_check(B, V, T, C, idx_batch, "tet_field_energies_bwd")) return rc;
+    DEFTET_TRY(tfg_check(B, V, T, C, idx_batch, "tet_field_energies_bwd"));
     if (B == 0 || V == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(stats && grad_out && field && pos && offsets && (T == 0 || (tet_idx && slots)), "tet_field_energies_bwd: null pointer");
     DEFTET_CHECK_ARG(((uintptr_t)tet_idx & 15) == 0, "tet_field_energies_bwd: tet_idx must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
     if (grad_field)
-        DEFTET_LAUNCH(k_tfe_bwd_field, dim3(tfg_groups((long long)V * C), (unsigned)B), dim3(kTfgBlock), st, stats, grad_out, target, field,
+        DEFTET_LAUNCH(k_tfe_bwd_field, dim3(blocks_for((long long)V * C, kTfgBlock), (unsigned)B), dim3(kTfgBlock), st, stats, grad_out, target, field,
                       pos, tet_idx, offsets, slots, grad_field, V, T, C, idx_batch);
     if (grad_pos)
-        DEFTET_LAUNCH(k_tfe_bwd_pos, dim3(tfg_groups(V), (unsigned)B), dim3(kTfgBlock), st, stats, grad_out, target, field, pos, tet_idx,
+        DEFTET_LAUNCH(k_tfe_bwd_pos, dim3(blocks_for(V, kTfgBlock), (unsigned)B), dim3(kTfgBlock), st, stats, grad_out, target, field, pos, tet_idx,
                       offsets, slots, grad_pos, V, T, C, idx_batch);
     return DEFTET_OK;
 }
@@ -453,10 +450,10 @@ int deftet_tet_to_vertex_fwd_f32(const float *values, const float *weights, cons
                                  void *stream)
 {
     const int B = n_batch, V = n_vertex, T = n_tet, C = n_channel;
-    if (int rc = tfg_check(B, V, T, C, idx_batch, "tet_to_vertex")) return rc;
+    DEFTET_TRY(tfg_check(B, V, T, C, idx_batch, "tet_to_vertex"));
     if (B == 0 || V == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(offsets && out && weight_sum && (T == 0 || (values && slots)), "tet_to_vertex: null pointer");
-    DEFTET_LAUNCH(k_ttv_fwd, dim3(tfg_groups((long long)V * C), (unsigned)B), dim3(kTfgBlock), as_stream(stream), values, weights, offsets,
+    DEFTET_LAUNCH(k_ttv_fwd, dim3(blocks_for((long long)V * C, kTfgBlock), (unsigned)B), dim3(kTfgBlock), as_stream(stream), values, weights, offsets,
                   slots, out, weight_sum, fill, V, T, C, idx_batch);
     return DEFTET_OK;
 }
@@ -465,11 +462,11 @@ int deftet_tet_to_vertex_bwd_f32(const float *grad_out, const float *weight_sum,
                                  float *grad_values, int n_batch, int n_vertex, int n_tet, int idx_batch, int n_channel, void *stream)
 {
     const int B = n_batch, V = n_vertex, T = n_tet, C = n_channel;
-    if (int rc = tfg_check(B, V, T, C, idx_batch, "tet_to_vertex_bwd")) return rc;
+    DEFTET_TRY(tfg_check(B, V, T, C, idx_batch, "tet_to_vertex_bwd"));
     if (B == 0 || T == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(tet_idx && grad_values && ((grad_out && weight_sum) || V == 0), "tet_to_vertex_bwd: null pointer");
     DEFTET_CHECK_ARG(((uintptr_t)tet_idx & 15) == 0, "tet_to_vertex_bwd: tet_idx must be 16-byte aligned");
-    DEFTET_LAUNCH(k_ttv_bwd, dim3(tfg_groups((long long)T * C), (unsigned)B), dim3(kTfgBlock), as_stream(stream), grad_out, weight_sum,
+    DEFTET_LAUNCH(k_ttv_bwd, dim3(blocks_for((long long)T * C, kTfgBlock), (unsigned)B), dim3(kTfgBlock), as_stream(stream), grad_out, weight_sum,
                   weights, tet_idx, grad_values, V, T, C, idx_batch);
     return DEFTET_OK;
 }

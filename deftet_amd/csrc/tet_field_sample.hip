@@ -181,8 +181,6 @@ int tfs_check(int B, int V, int T, int Q, int C, int idx_batch, const char *what
     return DEFTET_OK;
 }
 
-inline unsigned tfs_groups(long long n) { return (unsigned)((n + kPvBlock - 1) / kPvBlock); }
-
 }  // namespace
 }  // namespace deftet
 
@@ -201,19 +199,19 @@ int deftet_tet_field_sample_fwd_f32(const float *field, const int32_t *tet_idx, 
                                     int n_channel, void *stream)
 {
     const int B = n_batch, V = n_vertex, T = n_tet, Q = n_query, C = n_channel;
-    if (int rc = tfs_check(B, V, T, Q, C, idx_batch, "tet_field_sample")) return rc;
+    DEFTET_TRY(tfs_check(B, V, T, Q, C, idx_batch, "tet_field_sample"));
     if (B == 0 || Q == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(cond && bary && out && (field || V == 0) && (tet_idx || T == 0), "tet_field_sample: null pointer");
     DEFTET_CHECK_ARG((((uintptr_t)tet_idx | (uintptr_t)bary) & 15) == 0, "tet_field_sample: tet_idx and bary must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
     if (C > kTfsNarrow) {
-        DEFTET_LAUNCH(k_tfs_fwd_wide, dim3(tfs_groups((long long)Q * C), (unsigned)B), dim3(kPvBlock), st, field, tet_idx, cond, bary, out,
+        DEFTET_LAUNCH(k_tfs_fwd_wide, dim3(blocks_for((long long)Q * C, kPvBlock), (unsigned)B), dim3(kPvBlock), st, field, tet_idx, cond, bary, out,
                       bad_flag, fill, V, T, Q, C, idx_batch);
     } else if (C == 4 && (((uintptr_t)field | (uintptr_t)out) & 15) == 0) {
-        DEFTET_LAUNCH(k_tfs_fwd<true>, dim3(tfs_groups(Q), (unsigned)B), dim3(kPvBlock), st, field, tet_idx, cond, bary, out, bad_flag, fill, V,
+        DEFTET_LAUNCH(k_tfs_fwd<true>, dim3(blocks_for(Q, kPvBlock), (unsigned)B), dim3(kPvBlock), st, field, tet_idx, cond, bary, out, bad_flag, fill, V,
                       T, Q, C, idx_batch);
     } else {
-        DEFTET_LAUNCH(k_tfs_fwd<false>, dim3(tfs_groups(Q), (unsigned)B), dim3(kPvBlock), st, field, tet_idx, cond, bary, out, bad_flag, fill, V,
+        DEFTET_LAUNCH(k_tfs_fwd<false>, dim3(blocks_for(Q, kPvBlock), (unsigned)B), dim3(kPvBlock), st, field, tet_idx, cond, bary, out, bad_flag, fill, V,
                       T, Q, C, idx_batch);
     }
     return DEFTET_OK;
@@ -223,11 +221,11 @@ int deftet_tet_field_sample_bwd_w_f32(const float *field, const int32_t *tet_idx
                                       int n_batch, int n_vertex, int n_tet, int idx_batch, int n_query, int n_channel, void *stream)
 {
     const int B = n_batch, V = n_vertex, T = n_tet, Q = n_query, C = n_channel;
-    if (int rc = tfs_check(B, V, T, Q, C, idx_batch, "tet_field_sample_bwd_w")) return rc;
+    DEFTET_TRY(tfs_check(B, V, T, Q, C, idx_batch, "tet_field_sample_bwd_w"));
     if (B == 0 || Q == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(cond && grad_out && grad_w && (field || V == 0) && (tet_idx || T == 0), "tet_field_sample_bwd_w: null pointer");
     DEFTET_CHECK_ARG(((uintptr_t)tet_idx & 15) == 0, "tet_field_sample_bwd_w: tet_idx must be 16-byte aligned");
-    DEFTET_LAUNCH(k_tfs_bwd_w, dim3(tfs_groups((long long)Q * 4), (unsigned)B), dim3(kPvBlock), as_stream(stream), field, tet_idx, cond,
+    DEFTET_LAUNCH(k_tfs_bwd_w, dim3(blocks_for((long long)Q * 4, kPvBlock), (unsigned)B), dim3(kPvBlock), as_stream(stream), field, tet_idx, cond,
                   grad_out, grad_w, V, T, Q, C, idx_batch);
     return DEFTET_OK;
 }
@@ -237,21 +235,20 @@ int deftet_tet_field_sample_bwd_field_f32(const float *grad_out, const float *co
                                           int n_query, int n_channel, int accumulate, void *workspace, size_t workspace_bytes, void *stream)
 {
     const int B = n_batch, V = n_vertex, T = n_tet, Q = n_query, C = n_channel;
-    if (int rc = tfs_check(B, V, T, Q, C, idx_batch, "tet_field_sample_bwd_field")) return rc;
+    DEFTET_TRY(tfs_check(B, V, T, Q, C, idx_batch, "tet_field_sample_bwd_field"));
     const bool sorted = B > 0 && Q > 0;
     const TfsLayout L = tfs_layout((size_t)B, (size_t)T, (size_t)Q, workspace);
-    if (sorted && (!workspace || ((uintptr_t)workspace & 255) != 0 || workspace_bytes < L.bytes))
-        return set_error(DEFTET_EINVAL, "tet_field_sample_bwd_field: workspace missing, misaligned or too small");
+    if (sorted) DEFTET_TRY(workspace_ok(__func__, workspace, workspace_bytes, L.bytes));
     if (B == 0 || V == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(offsets && grad_field && (T == 0 || slots) && (Q == 0 || (grad_out && cond && bary)),
                      "tet_field_sample_bwd_field: null pointer");
     hipStream_t st = as_stream(stream);
     if (sorted) {
         const long long n = (long long)B * Q;
-        DEFTET_LAUNCH(k_tfs_keys, dim3(tfs_groups(n)), dim3(kPvBlock), st, cond, L.s.keys, n, Q, T);
-        if (int rc = sort_and_segment(L.s, L.perm, L.seg, (size_t)n, (unsigned)((long long)B * ((long long)T + 1)), st)) return rc;
+        DEFTET_LAUNCH(k_tfs_keys, dim3(blocks_for(n, kPvBlock)), dim3(kPvBlock), st, cond, L.s.keys, n, Q, T);
+        DEFTET_TRY(sort_and_segment(L.s, L.perm, L.seg, (size_t)n, (unsigned)((long long)B * ((long long)T + 1)), st));
     }
-    DEFTET_LAUNCH(k_tfs_bwd_field, dim3(tfs_groups((long long)V * C), (unsigned)B), dim3(kPvBlock), st, grad_out, bary, offsets, slots,
+    DEFTET_LAUNCH(k_tfs_bwd_field, dim3(blocks_for((long long)V * C, kPvBlock), (unsigned)B), dim3(kPvBlock), st, grad_out, bary, offsets, slots,
                   sorted ? (const int32_t *)L.seg : (const int32_t *)nullptr, sorted ? (const int32_t *)L.perm : (const int32_t *)nullptr,
                   grad_field, V, T, C, idx_batch, accumulate);
     return DEFTET_OK;

@@ -417,14 +417,11 @@ extern "C" int deftet_boundary_index_i64(const int64_t *face_fx3, const int64_t 
     if (B == 0 || Fi == 0) { DEFTET_HIP(hipMemsetAsync(offsets, 0, ((size_t)B + 1) * 4, st)); return DEFTET_OK; }
     DEFTET_CHECK_ARG(face_fx3 && tetidx_fx2 && occ_bxt && out_rows, "null pointer");
     const BndLayout L = bnd_layout(B, Fi, workspace);
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && L.bytes <= wsb, "workspace null, misaligned or too small");
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, L.bytes));
     const size_t n = (size_t)B * Fi;
-    DEFTET_LAUNCH(k_bnd_flag, dim3((Fi + 255) / 256, B), dim3(256), st, (const long long *)tetidx_fx2, occ_bxt, T, Fi, mode, L.flag);
-    {
-        const int rc = prims::scan<int, prims::Plus, true>(L.flag, L.pos, n, 0, prims::Plus(), L.scanTmp, L.scanTmpBytes, st);
-        if (rc != DEFTET_OK) return rc;
-    }
-    DEFTET_LAUNCH(k_bnd_emit, dim3((Fi + 255) / 256, B), dim3(256), st, (const long long *)face_fx3, (const long long *)tetidx_fx2,
+    DEFTET_LAUNCH(k_bnd_flag, dim3(blocks_for(Fi, 256), B), dim3(256), st, (const long long *)tetidx_fx2, occ_bxt, T, Fi, mode, L.flag);
+    DEFTET_TRY(prims::scan<int, prims::Plus, true>(L.flag, L.pos, n, 0, prims::Plus(), L.scanTmp, L.scanTmpBytes, st));
+    DEFTET_LAUNCH(k_bnd_emit, dim3(blocks_for(Fi, 256), B), dim3(256), st, (const long long *)face_fx3, (const long long *)tetidx_fx2,
                   occ_bxt, L.flag, L.pos, T, Fi, B, mode, (long long *)out_rows, offsets);
     return DEFTET_OK;
 }
@@ -440,8 +437,7 @@ extern "C" int deftet_tet_energies_fwd_f32(const float *tet, const float *inv_v,
     if (B == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(tet && out && stats && ((uintptr_t)tet & 15) == 0, "null or misaligned pointer");
     const EnergyLayout L = energy_layout(B, T, workspace);
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && L.bytes <= wsb,
-                     "workspace null, misaligned or smaller than deftet_tet_energies_workspace_bytes2(B, T)");
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, L.bytes));
     hipStream_t st = as_stream(stream_);
     // B <= kETicketShapes: two launches, each pass finishes its own reduction on the counters of this stream's slot
     const int slot = B <= kETicketShapes ? ticket_slot_for_stream(st, kETicketSlots) : -1;
@@ -463,10 +459,10 @@ extern "C" int deftet_tet_energies_bwd_f32(const float *tet, const float *inv_v,
     DEFTET_CHECK_ARG(tet && stats && grad_out && grad_tet && ((uintptr_t)tet & 15) == 0 && ((uintptr_t)grad_tet & 15) == 0,
                      "null or misaligned pointer");
     if (pow_v == 4 && pow_e == 4)
-        DEFTET_LAUNCH(k_energy_bwd<true>, dim3((T + 255) / 256, B), dim3(256), as_stream(stream_), tet, inv_v, T, scale, pow_v, pow_e,
+        DEFTET_LAUNCH(k_energy_bwd<true>, dim3(blocks_for(T, 256), B), dim3(256), as_stream(stream_), tet, inv_v, T, scale, pow_v, pow_e,
                       stats, grad_out, grad_tet);
     else
-        DEFTET_LAUNCH(k_energy_bwd<false>, dim3((T + 255) / 256, B), dim3(256), as_stream(stream_), tet, inv_v, T, scale, pow_v, pow_e,
+        DEFTET_LAUNCH(k_energy_bwd<false>, dim3(blocks_for(T, 256), B), dim3(256), as_stream(stream_), tet, inv_v, T, scale, pow_v, pow_e,
                       stats, grad_out, grad_tet);
     return DEFTET_OK;
 }

@@ -301,9 +301,8 @@ extern "C" int deftet_tet_spatial_order_f32(const float *tet, int n_tet, int32_t
     if (breaks) DEFTET_HIP(hipMemsetAsync(breaks, 0, 8, st));
     if (n_tet == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(tet && order_out && ((uintptr_t)tet & 15) == 0, "null or misaligned pointer");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0, "workspace null or not 256-byte aligned");
     Layout L = make_layout(n_tet, workspace, workspace_bytes);
-    DEFTET_CHECK_ARG(L.bytes <= workspace_bytes, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
+    DEFTET_TRY(workspace_ok(__func__, workspace, workspace_bytes, L.bytes));
     const int nblk = (n_tet + 255) / 256;
     DEFTET_LAUNCH(k_order_stats, dim3(kStatBlocks), dim3(256), st, tet, n_tet, L.part);
     DEFTET_HIP(hipMemsetAsync(L.hist, 0, (size_t)2 * kFine * 4, st));
@@ -311,10 +310,9 @@ extern "C" int deftet_tet_spatial_order_f32(const float *tet, int n_tet, int32_t
     DEFTET_LAUNCH(k_order_lut, dim3(1), dim3(64), st, (const float *)L.part, (const unsigned *)L.hist, L.lut);
     DEFTET_LAUNCH(k_order_keys, dim3(nblk), dim3(256), st, tet, n_tet, (const float *)L.part, (const unsigned short *)L.lut, L.key);
     // stable: tets with equal keys keep their original order
-    int rc = prims::radix_sort_from<unsigned, unsigned>(prims::PtrLoad<unsigned>{L.key}, L.skey, prims::IotaLoad{},
-                                                        reinterpret_cast<unsigned *>(order_out), (size_t)n_tet,
-                                                        2 * kColBits + kZBits, L.sortTmp, L.sortBytes, st);
-    if (rc != DEFTET_OK) return rc;
+    DEFTET_TRY(prims::radix_sort_from<unsigned, unsigned>(prims::PtrLoad<unsigned>{L.key}, L.skey, prims::IotaLoad{},
+                                                          reinterpret_cast<unsigned *>(order_out), (size_t)n_tet,
+                                                          2 * kColBits + kZBits, L.sortTmp, L.sortBytes, st));
     if (breaks) DEFTET_LAUNCH(k_order_breaks, dim3(nblk), dim3(256), st, (const unsigned *)L.key, (const unsigned *)L.skey, n_tet, breaks);
     return DEFTET_OK;
 }
@@ -339,7 +337,7 @@ extern "C" int deftet_tet_order_coherence_f32(const float *tet, int n_tet, const
     }
     DEFTET_CHECK_ARG(tet && ((uintptr_t)tet & 15) == 0, "null or misaligned pointer");
     const FarLayout L = far_layout(workspace);
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0 && L.bytes <= workspace_bytes, "workspace null, misaligned or too small");
+    DEFTET_TRY(workspace_ok(__func__, workspace, workspace_bytes, L.bytes));
     DEFTET_LAUNCH(k_order_stats, dim3(kStatBlocks), dim3(256), st, tet, n_tet, L.part);
     DEFTET_LAUNCH(k_order_far, dim3(kFarBlocks), dim3(256), st, tet, n_tet, (const int *)order, (const float *)L.part, L.blockFar);
     DEFTET_LAUNCH(k_order_far_sum, dim3(1), dim3(kFarBlocks), st, (const int *)L.blockFar, n_tet, out2);

@@ -290,20 +290,11 @@ static int ex_scan(const Layout &L, const int *in, int *out, size_t n, hipStream
     return prims::scan<int, prims::Plus, true>(in, out, n, 0, prims::Plus(), L.scan, L.scan_bytes, st);
 }
 
-static inline dim3 grid_for(size_t n) { return dim3((unsigned)((n + kThreads - 1) / kThreads)); }
-
 static int check_sizes(const char *who, int T, int E)
 {
     DEFTET_CHECK_ARG(T >= 0 && E >= 0, "%s: negative size", who);
     DEFTET_CHECK_ARG(T <= 100000000, "%s: n_tet=%d too large (8 n_tet children must fit 31 bits)", who, T);
     DEFTET_CHECK_ARG((long long)E <= 6LL * T, "%s: n_edge=%d is more than 6 n_tet", who, E);
-    return DEFTET_OK;
-}
-
-static int check_workspace(const char *who, const Layout &L, void *ws, size_t wsb)
-{
-    DEFTET_CHECK_ARG(ws && ((uintptr_t)ws & 255) == 0, "%s: workspace null or not 256-byte aligned", who);
-    DEFTET_CHECK_ARG(L.bytes <= wsb, "%s: workspace too small (deftet_tet_refine_workspace_bytes)", who);
     return DEFTET_OK;
 }
 
@@ -313,12 +304,6 @@ static int check_workspace(const char *who, const Layout &L, void *ws, size_t ws
 using namespace deftet;
 using namespace deftet::refine;
 
-#define TRY(x)                     \
-    do {                           \
-        int s_ = (x);              \
-        if (s_ != DEFTET_OK) return s_; \
-    } while (0)
-
 extern "C" size_t deftet_tet_refine_workspace_bytes(int n_tet, int n_edge)
 {
     return layout(n_tet > 0 ? n_tet : 0, n_edge > 0 ? n_edge : 0, nullptr).bytes;
@@ -327,7 +312,7 @@ extern "C" size_t deftet_tet_refine_workspace_bytes(int n_tet, int n_edge)
 extern "C" int deftet_tet_refine_mark_i64(const int64_t *tet_edge_tx6, const uint8_t *select_t, int T, int E, int reset, int n_sweeps,
                                           uint32_t *marks_e, int32_t *sweep_counts, int32_t *bad, void *stream_)
 {
-    TRY(check_sizes("tet_refine_mark", T, E));
+    DEFTET_TRY(check_sizes("tet_refine_mark", T, E));
     DEFTET_CHECK_ARG(n_sweeps >= 0 && n_sweeps <= kMaxSweeps, "tet_refine_mark: n_sweeps=%d outside 0..%d", n_sweeps, kMaxSweeps);
     DEFTET_CHECK_ARG(bad && (n_sweeps == 0 || sweep_counts), "tet_refine_mark: null pointer: sweep_counts / bad");
     DEFTET_CHECK_ARG(E == 0 || marks_e, "tet_refine_mark: null pointer: marks");
@@ -337,33 +322,33 @@ extern "C" int deftet_tet_refine_mark_i64(const int64_t *tet_edge_tx6, const uin
     if (reset) {
         DEFTET_HIP(hipMemsetAsync(bad, 0, 4, st));
         if (E) DEFTET_HIP(hipMemsetAsync(marks_e, 0, (size_t)E * 4, st));
-        if (T) DEFTET_LAUNCH(k_refine_init, grid_for(T), dim3(kThreads), st, (const long long *)tet_edge_tx6, select_t, T, E, marks_e, bad);
+        if (T) DEFTET_LAUNCH(k_refine_init, blocks_for(T, kThreads), dim3(kThreads), st, (const long long *)tet_edge_tx6, select_t, T, E, marks_e, bad);
     }
     if (T == 0 || E == 0) return DEFTET_OK;
     for (int s = 0; s < n_sweeps; ++s)
-        DEFTET_LAUNCH(k_refine_sweep, grid_for(T), dim3(kThreads), st, (const long long *)tet_edge_tx6, T, E, marks_e, sweep_counts + s);
+        DEFTET_LAUNCH(k_refine_sweep, blocks_for(T, kThreads), dim3(kThreads), st, (const long long *)tet_edge_tx6, T, E, marks_e, sweep_counts + s);
     return DEFTET_OK;
 }
 
 extern "C" int deftet_tet_refine_count_i64(const int64_t *tet_edge_tx6, const int64_t *edges_ex2, const uint32_t *marks_e, int n_point, int T,
                                            int E, int32_t *totals, void *workspace, size_t wsb, void *stream_)
 {
-    TRY(check_sizes("tet_refine_count", T, E));
+    DEFTET_TRY(check_sizes("tet_refine_count", T, E));
     DEFTET_CHECK_ARG(n_point >= 0, "tet_refine_count: negative size");
     DEFTET_CHECK_ARG(totals, "tet_refine_count: null pointer: totals");
     DEFTET_CHECK_ARG(T == 0 || tet_edge_tx6, "tet_refine_count: null pointer: tet_edge");
     DEFTET_CHECK_ARG(E == 0 || (edges_ex2 && marks_e), "tet_refine_count: null pointer: edges / marks");
     const Layout L = layout(T, E, workspace);
-    TRY(check_workspace("tet_refine_count", L, workspace, wsb));
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, L.bytes));
     hipStream_t st = as_stream(stream_);
     DEFTET_HIP(hipMemsetAsync(totals, 0, 12, st));
     if (E) {
-        DEFTET_LAUNCH(k_refine_edge_check, grid_for(E), dim3(kThreads), st, (const long long *)edges_ex2, marks_e, E, n_point, totals + 2);
-        TRY(ex_scan(L, (const int *)marks_e, L.rank, (size_t)E, st));
+        DEFTET_LAUNCH(k_refine_edge_check, blocks_for(E, kThreads), dim3(kThreads), st, (const long long *)edges_ex2, marks_e, E, n_point, totals + 2);
+        DEFTET_TRY(ex_scan(L, (const int *)marks_e, L.rank, (size_t)E, st));
     }
     if (T) {
-        DEFTET_LAUNCH(k_refine_children, grid_for(T), dim3(kThreads), st, (const long long *)tet_edge_tx6, marks_e, T, E, L.n_child, totals + 2);
-        TRY(ex_scan(L, L.n_child, L.child_pos, (size_t)T, st));
+        DEFTET_LAUNCH(k_refine_children, blocks_for(T, kThreads), dim3(kThreads), st, (const long long *)tet_edge_tx6, marks_e, T, E, L.n_child, totals + 2);
+        DEFTET_TRY(ex_scan(L, L.n_child, L.child_pos, (size_t)T, st));
     }
     DEFTET_LAUNCH(k_refine_totals, dim3(1), dim3(64), st, marks_e, (const int *)L.rank, E, (const int *)L.n_child, (const int *)L.child_pos, T, totals);
     return DEFTET_OK;
@@ -374,7 +359,7 @@ extern "C" int deftet_tet_refine_fill_f32(const int64_t *tet_tx4, const int64_t 
                                           long long n_tet_new, float *points_new, float *feat_new, int64_t *tet_new, int64_t *parent,
                                           uint8_t *kind, int64_t *edges_split, void *workspace, size_t wsb, void *stream_)
 {
-    TRY(check_sizes("tet_refine_fill", T, E));
+    DEFTET_TRY(check_sizes("tet_refine_fill", T, E));
     DEFTET_CHECK_ARG(n_point >= 0 && n_feat >= 0 && n_split >= 0 && n_tet_new >= 0, "tet_refine_fill: negative size");
     DEFTET_CHECK_ARG(n_split <= E && n_tet_new <= 8LL * T, "tet_refine_fill: n_split / n_tet_new are not a count pass's totals");
     DEFTET_CHECK_ARG(T == 0 || (tet_tx4 && tet_edge_tx6), "tet_refine_fill: null pointer: tet / tet_edge");
@@ -384,7 +369,7 @@ extern "C" int deftet_tet_refine_fill_f32(const int64_t *tet_tx4, const int64_t 
     DEFTET_CHECK_ARG(n_tet_new == 0 || (tet_new && parent && kind), "tet_refine_fill: null pointer: tet_new / parent / kind");
     DEFTET_CHECK_ARG(n_split == 0 || edges_split, "tet_refine_fill: null pointer: edges_split");
     const Layout L = layout(T, E, workspace);
-    TRY(check_workspace("tet_refine_fill", L, workspace, wsb));
+    DEFTET_TRY(workspace_ok(__func__, workspace, wsb, L.bytes));
     hipStream_t st = as_stream(stream_);
     const float *src[2] = {points, feat};
     float *dst[2] = {points_new, feat_new};
@@ -393,16 +378,16 @@ extern "C" int deftet_tet_refine_fill_f32(const int64_t *tet_tx4, const int64_t 
         const int K = width[k];
         if (K == 0) continue;
         if (n_point)
-            DEFTET_LAUNCH(k_refine_copy, grid_for((size_t)n_point * K), dim3(kThreads), st, src[k], (long long)n_point * K, dst[k]);
+            DEFTET_LAUNCH(k_refine_copy, blocks_for((size_t)n_point * K, kThreads), dim3(kThreads), st, src[k], (long long)n_point * K, dst[k]);
         if (n_split)
-            DEFTET_LAUNCH(k_refine_midpoints, grid_for((size_t)E * K), dim3(kThreads), st, src[k], (const long long *)edges_ex2, marks_e,
+            DEFTET_LAUNCH(k_refine_midpoints, blocks_for((size_t)E * K, kThreads), dim3(kThreads), st, src[k], (const long long *)edges_ex2, marks_e,
                           (const int *)L.rank, n_point, E, K, n_split, dst[k]);
     }
     if (n_split)
-        DEFTET_LAUNCH(k_refine_split, grid_for(E), dim3(kThreads), st, (const long long *)edges_ex2, marks_e, (const int *)L.rank, E, n_split,
+        DEFTET_LAUNCH(k_refine_split, blocks_for(E, kThreads), dim3(kThreads), st, (const long long *)edges_ex2, marks_e, (const int *)L.rank, E, n_split,
                       (long long *)edges_split);
     if (T && n_tet_new)
-        DEFTET_LAUNCH(k_refine_tets, grid_for(T), dim3(kThreads), st, (const long long *)tet_tx4, (const long long *)tet_edge_tx6, marks_e,
+        DEFTET_LAUNCH(k_refine_tets, blocks_for(T, kThreads), dim3(kThreads), st, (const long long *)tet_tx4, (const long long *)tet_edge_tx6, marks_e,
                       (const int *)L.rank, (const int *)L.child_pos, T, E, n_point, n_tet_new, (long long *)tet_new, (long long *)parent, kind);
     return DEFTET_OK;
 }

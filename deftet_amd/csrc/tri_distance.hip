@@ -1236,16 +1236,16 @@ static int tri_dist_group(const float *pts, const float *face, const float *nfb,
     DEFTET_LAUNCH(k_tri_face_stats, dim3(kTParts, nS), blk, st, face, nfb, L.part, slice, Fmax, L.cnt, L.fill, L.counters, L.rep, (int)nc, kTGc * kTGc * kTGc,
                   L.pcount);
     DEFTET_LAUNCH(k_tri_grid, dim3(nS), dim3(64), st, (const float *)L.part, L.grid, slice);
-    DEFTET_LAUNCH(k_tri_face_bin, dim3((Fmax + 255) / 256, nS), blk, st, face, nfb, (const TGrid *)L.grid, 0, L.cnt, (const int *)L.start, L.fill, L.list, L.wide,
+    DEFTET_LAUNCH(k_tri_face_bin, dim3(blocks_for(Fmax, 256), nS), blk, st, face, nfb, (const TGrid *)L.grid, 0, L.cnt, (const int *)L.start, L.fill, L.list, L.wide,
                   L.counters, L.rep, slice, Fmax, L.sph, L.frange);
     DEFTET_LAUNCH(k_scan_excl, dim3(scan_tiles(nc), nS), dim3(kScanThreads), st, (const int *)L.cnt, L.start, (int)nc, slice, 0);
-    DEFTET_LAUNCH(k_tri_face_bin, dim3((Fmax + 255) / 256, nS), blk, st, face, nfb, (const TGrid *)L.grid, 1, L.cnt, (const int *)L.start, L.fill, L.list, L.wide,
+    DEFTET_LAUNCH(k_tri_face_bin, dim3(blocks_for(Fmax, 256), nS), blk, st, face, nfb, (const TGrid *)L.grid, 1, L.cnt, (const int *)L.start, L.fill, L.list, L.wide,
                   L.counters, L.rep, slice, Fmax, L.sph, L.frange);
-    DEFTET_LAUNCH(k_tri_point_keys, dim3((P + 255) / 256, nS), blk, st, pts, P, (const TGrid *)L.grid, L.pcount, L.prank, slice);
+    DEFTET_LAUNCH(k_tri_point_keys, dim3(blocks_for(P, 256), nS), blk, st, pts, P, (const TGrid *)L.grid, L.pcount, L.prank, slice);
     DEFTET_LAUNCH(k_scan_excl, dim3(scan_tiles(nc), nS), dim3(kScanThreads), st, (const int *)L.pcount, L.pstart, (int)nc, slice, 0);
-    DEFTET_LAUNCH(k_tri_point_scatter, dim3((P + 255) / 256, nS), blk, st, P, (const int2 *)L.prank, (const int *)L.pstart, order, pskey, slice);
+    DEFTET_LAUNCH(k_tri_point_scatter, dim3(blocks_for(P, 256), nS), blk, st, P, (const int2 *)L.prank, (const int *)L.pstart, order, pskey, slice);
     if (order_out) DEFTET_HIP(hipMemcpyAsync(order_out, order, nAll * 4, hipMemcpyDeviceToDevice, st));   // for the grouped backward
-    DEFTET_LAUNCH(k_tri_chunks, dim3((kTRows + 1 + 255) / 256, nS), blk, st, (const int *)L.pstart, L.ptStart, L.chunkCount, slice);
+    DEFTET_LAUNCH(k_tri_chunks, dim3(blocks_for(kTRows + 1, 256), nS), blk, st, (const int *)L.pstart, L.ptStart, L.chunkCount, slice);
     DEFTET_LAUNCH(k_scan_excl, dim3(scan_tiles(kTRows + 1), nS), dim3(kScanThreads), st, (const int *)L.chunkCount, L.chunkStart, kTRows + 1, slice, 0);
     {
         const long long maxChunks = (long long)(P + 63) / 64 + (long long)kTRows;
@@ -1256,13 +1256,13 @@ static int tri_dist_group(const float *pts, const float *face, const float *nfb,
     }
     // the far path (counters: [0] wide faces, [1] far points)
     DEFTET_LAUNCH(k_scan_excl, dim3(scan_tiles(P), nS), dim3(kScanThreads), st, (const int *)L.farFlag, L.farOff, P, slice, 0);
-    DEFTET_LAUNCH(k_tri_compact, dim3((P + 255) / 256, nS), blk, st, (const int *)L.farFlag, (const int *)L.farOff, (const unsigned *)order, P, L.farList,
+    DEFTET_LAUNCH(k_tri_compact, dim3(blocks_for(P, 256), nS), blk, st, (const int *)L.farFlag, (const int *)L.farOff, (const unsigned *)order, P, L.farList,
                   L.counters + 1, slice);
-    DEFTET_LAUNCH(k_tri_far_bound, dim3((P + 63) / 64, nS), dim3(kTriWaves * 64), st, pts, face, (const TGrid *)L.grid, (const int *)L.wide,
+    DEFTET_LAUNCH(k_tri_far_bound, dim3(blocks_for(P, 64), nS), dim3(kTriWaves * 64), st, pts, face, (const TGrid *)L.grid, (const int *)L.wide,
                   (const int *)L.counters, (const int *)L.rep, (const int *)L.farList, (const int *)(L.counters + 1), L.bound, slice, P, Fmax);
-    DEFTET_LAUNCH(k_tri_far_rows, dim3((P + 63) / 64, kTriSlices, nS), dim3(kTriWaves * 64), st, pts, face, nfb, (const TGrid *)L.grid,
+    DEFTET_LAUNCH(k_tri_far_rows, dim3(blocks_for(P, 64), kTriSlices, nS), dim3(kTriWaves * 64), st, pts, face, nfb, (const TGrid *)L.grid,
                   (const int *)L.start, (const int *)L.list, (const int *)L.farList, (const int *)(L.counters + 1), L.bound, slice, P, Fmax);
-    DEFTET_LAUNCH(k_tri_far_final, dim3((P + 255) / 256, nS), blk, st, (const unsigned long long *)L.bound, (const int *)(L.counters + 1),
+    DEFTET_LAUNCH(k_tri_far_final, dim3(blocks_for(P, 256), nS), blk, st, (const unsigned long long *)L.bound, (const int *)(L.counters + 1),
                   (const int *)L.farList, cd, cf, slice, P);
     return DEFTET_OK;
 }
@@ -1281,18 +1281,16 @@ extern "C" int deftet_tri_dist_fwd_order_f32(const float *pts, const float *face
     hipStream_t st = as_stream(stream_);
     if (!workspace || Fmax == 0) {
         DEFTET_CHECK_ARG(!order_out, "the point order is only produced by the grid search (workspace and faces needed)");
-        DEFTET_LAUNCH(k_tri_dist_fwd, dim3((P + 255) / 256, B), dim3(256), st, pts, face, n_face_b, closest_d, closest_f, P, Fmax);
+        DEFTET_LAUNCH(k_tri_dist_fwd, dim3(blocks_for(P, 256), B), dim3(256), st, pts, face, n_face_b, closest_d, closest_f, P, Fmax);
         return DEFTET_OK;
     }
-    DEFTET_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && tri_layout(group_shapes(B), P, Fmax, workspace).bytes <= wsb,
-                     "workspace misaligned or too small");
+    DEFTET_TRY(workspace_ok("deftet_tri_dist_fwd*", workspace, wsb, tri_layout(group_shapes(B), P, Fmax, workspace).bytes));
     DEFTET_CHECK_ARG((long long)Fmax * kTMaxCells < 2147483647LL && (long long)P * 3 < 2147483647LL, "too many faces / points");
     for (int b0 = 0; b0 < B; b0 += kBatchShapes) {                   // groups of kBatchShapes shapes reuse the workspace (stream order)
         const int nS = std::min(kBatchShapes, B - b0);
-        const int rc = tri_dist_group(pts + (size_t)b0 * P * 3, face + (size_t)b0 * Fmax * 9, n_face_b + b0, closest_d + (size_t)b0 * P,
-                                      closest_f + (size_t)b0 * P, nS, P, Fmax, workspace, st,
-                                      order_out ? order_out + (size_t)b0 * P : nullptr);
-        if (rc != DEFTET_OK) return rc;
+        DEFTET_TRY(tri_dist_group(pts + (size_t)b0 * P * 3, face + (size_t)b0 * Fmax * 9, n_face_b + b0, closest_d + (size_t)b0 * P,
+                                  closest_f + (size_t)b0 * P, nS, P, Fmax, workspace, st,
+                                  order_out ? order_out + (size_t)b0 * P : nullptr));
     }
     return DEFTET_OK;
 }
@@ -1311,7 +1309,7 @@ extern "C" int deftet_tri_dist_bwd_order_f32(const float *pts, const float *face
     DEFTET_CHECK_ARG(B >= 0 && P >= 0 && F >= 0 && B <= 65535, "bad size");
     if (B == 0 || P == 0 || F == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(pts && face && closest_f && dl_dd && dldface && order, "null pointer");
-    DEFTET_LAUNCH(k_tri_dist_bwd_grouped, dim3((P + 255) / 256, B), dim3(256), as_stream(stream_), pts, face, closest_f, dl_dd, order, dldface,
+    DEFTET_LAUNCH(k_tri_dist_bwd_grouped, dim3(blocks_for(P, 256), B), dim3(256), as_stream(stream_), pts, face, closest_f, dl_dd, order, dldface,
                   P, F);
     return DEFTET_OK;
 }
@@ -1320,12 +1318,9 @@ extern "C" int deftet_tri_dist_bwd_order_f32(const float *pts, const float *face
 static int tri_dist_bwd_sorted(const float *pts, const float *face, const float *closest_f, const float *dl_dd, float *dldface, long long n,
                                int P, int F, unsigned long long *key, unsigned long long *skey, void *tmp, size_t tmpBytes, hipStream_t st)
 {
-    DEFTET_LAUNCH(k_bwd_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), st, closest_f, n, P, F, key);
-    {
-        const int rc = prims::radix_sort_keys<unsigned long long>(key, skey, (size_t)n, 64, tmp, tmpBytes, st);
-        if (rc != DEFTET_OK) return rc;
-    }
-    DEFTET_LAUNCH(k_tri_dist_bwd_sorted, dim3((unsigned)((n + 255) / 256)), dim3(256), st, pts, face, dl_dd, skey, n, P, F, dldface);
+    DEFTET_LAUNCH(k_bwd_keys, dim3(blocks_for(n, 256)), dim3(256), st, closest_f, n, P, F, key);
+    DEFTET_TRY(prims::radix_sort_keys<unsigned long long>(key, skey, (size_t)n, 64, tmp, tmpBytes, st));
+    DEFTET_LAUNCH(k_tri_dist_bwd_sorted, dim3(blocks_for(n, 256)), dim3(256), st, pts, face, dl_dd, skey, n, P, F, dldface);
     return DEFTET_OK;
 }
 
@@ -1337,7 +1332,7 @@ extern "C" int deftet_tri_dist_bwd_f32(const float *pts, const float *face, cons
     DEFTET_CHECK_ARG(pts && face && closest_f && dl_dd && dldface, "null pointer");
     hipStream_t st = as_stream(stream_);
     if (!deterministic) {
-        DEFTET_LAUNCH(k_tri_dist_bwd_atomic, dim3((P + 255) / 256, B), dim3(256), st, pts, face, closest_f, dl_dd, dldface, P, F);
+        DEFTET_LAUNCH(k_tri_dist_bwd_atomic, dim3(blocks_for(P, 256), B), dim3(256), st, pts, face, closest_f, dl_dd, dldface, P, F);
         return DEFTET_OK;
     }
     // deterministic mode allocates its own scratch (stream-ordered), it is a test/debug path

@@ -97,7 +97,7 @@ int launch(hipStream_t st, const float *x, const int *offsets, const int *idx, c
 {
     const long long rowsPerBlock = 4 * (64 / LPR);
     const long long blocks = ((long long)V + rowsPerBlock - 1) / rowsPerBlock;
-    const dim3 grid((unsigned)((blocks + 7) / 8 * 8), (unsigned)B);
+    const dim3 grid((unsigned)(blocks_for(blocks, 8) * 8), (unsigned)B);
     DEFTET_LAUNCH((k_vagg<VEC, LPR>), grid, dim3(256), st, x, offsets, idx, vals, V, C, out);
     return DEFTET_OK;
 }

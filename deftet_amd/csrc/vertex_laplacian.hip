@@ -190,7 +190,7 @@ inline int bit_length(unsigned v)
     return n;
 }
 
-inline unsigned grid_x(int V) { return (unsigned)((((V + 255) / 256) + 7) / 8 * 8); }
+inline unsigned grid_x(int V) { return (unsigned)align_up(blocks_for(V, 256), 8); }
 
 inline size_t sort_tmp_bytes(size_t n) { return prims::radix_sort_temp_bytes<u64, unsigned>(n); }
 
@@ -219,13 +219,12 @@ int build_csr(const I *rows, const I *cols, const float *vals, int nnz, int V, i
               float *out_vals, int32_t *t_offsets, int32_t *t_rows, float *t_vals, int32_t *bad, const CsrLayout &L, hipStream_t st)
 {
     const int mb = bit_length((unsigned)V);                  // 2^mb > V: an all-ones major part is never a vertex
-    const unsigned gk = (unsigned)((nnz + 255) / 256), gf = (unsigned)((nnz + 256) / 256);
+    const unsigned gk = blocks_for(nnz, 256), gf = blocks_for(nnz + 1, 256);
     for (int t = 0; t < 2; ++t) {
         const int minorBits = t == 0 && order == DEFTET_VADJ_ROW_INPUT ? 0 : mb;
         DEFTET_LAUNCH((k_vadj_keys<I>), dim3(gk), dim3(256), st, rows, cols, nnz, V, t, minorBits, L.key, bad);
-        const int rc = prims::radix_sort_from<u64, unsigned>(prims::PtrLoad<u64>{L.key}, L.skey, prims::IotaLoad{}, L.perm, (size_t)nnz,
-                                                             mb + minorBits, L.sortTmp, L.sortTmpBytes, st);
-        if (rc != DEFTET_OK) return rc;
+        DEFTET_TRY(prims::radix_sort_from<u64, unsigned>(prims::PtrLoad<u64>{L.key}, L.skey, prims::IotaLoad{}, L.perm, (size_t)nnz,
+                                                         mb + minorBits, L.sortTmp, L.sortTmpBytes, st));
         if (t == 0)
             DEFTET_LAUNCH((k_vadj_fill<I>), dim3(gf), dim3(256), st, (const u64 *)L.skey, (const unsigned *)L.perm, nnz, V, minorBits, cols, vals,
                           out_cols, out_vals, offsets);
@@ -284,8 +283,7 @@ extern "C" int deftet_vertex_adjacency_csr_i32(const void *row_idx, const void *
                          aligned(t_offsets, 4) && aligned(t_rows, 4) && aligned(t_vals, 4) && aligned(bad_flag, 4),
                      "outputs and values must be 4-byte aligned");
     const vlap::CsrLayout L = vlap::csr_layout(nnz, workspace);
-    DEFTET_CHECK_ARG(nnz == 0 || (workspace && aligned(workspace, 256) && L.bytes <= workspace_bytes),
-                     "workspace null, misaligned or too small");
+    if (nnz > 0) DEFTET_TRY(workspace_ok(__func__, workspace, workspace_bytes, L.bytes));
     hipStream_t st = as_stream(stream_);
     DEFTET_HIP(hipMemsetAsync(bad_flag, 0, 4, st));
     if (nnz == 0) {
@@ -329,14 +327,11 @@ extern "C" int deftet_vertex_laplacian_fwd_f32(const float *x, const int32_t *of
                                                int n_chan, int nnz, float *r, float *out, void *workspace, size_t workspace_bytes,
                                                void *stream_)
 {
-    const int rc = vlap_check(weighting, reduction, n_batch, n_vertex, n_chan, nnz, offsets, cols, vals, row_weights);
-    if (rc != DEFTET_OK) return rc;
+    DEFTET_TRY(vlap_check(weighting, reduction, n_batch, n_vertex, n_chan, nnz, offsets, cols, vals, row_weights));
     const bool shape = reduction == DEFTET_VLAP_SHAPE, rowdiv = weighting == DEFTET_VLAP_ROW_DIVISOR;
     DEFTET_CHECK_ARG(out && (n_vertex == 0 || (x && r)), "null pointer");
     DEFTET_CHECK_ARG(aligned(x, 4) && aligned(r, 4) && aligned(out, 4), "x, r and out must be 4-byte aligned");
-    DEFTET_CHECK_ARG(!shape || (workspace && aligned(workspace, 256) &&
-                                workspace_bytes >= deftet_vertex_laplacian_workspace_bytes(n_batch, n_vertex)),
-                     "workspace null, misaligned or too small");
+    if (shape) DEFTET_TRY(workspace_ok(__func__, workspace, workspace_bytes, deftet_vertex_laplacian_workspace_bytes(n_batch, n_vertex)));
     if (n_batch == 0) return DEFTET_OK;
     hipStream_t st = as_stream(stream_);
     if (n_vertex == 0) {
@@ -350,7 +345,7 @@ extern "C" int deftet_vertex_laplacian_fwd_f32(const float *x, const int32_t *of
     if (n_chan <= 4) s = vlap::launch_fwd<4>(rowdiv, shape, grid, st, x, offsets, cols, vals, row_weights, n_vertex, n_chan, r, out, part);
     else if (n_chan <= 8) s = vlap::launch_fwd<8>(rowdiv, shape, grid, st, x, offsets, cols, vals, row_weights, n_vertex, n_chan, r, out, part);
     else s = vlap::launch_fwd<16>(rowdiv, shape, grid, st, x, offsets, cols, vals, row_weights, n_vertex, n_chan, r, out, part);
-    if (s != DEFTET_OK) return s;
+    DEFTET_TRY(s);
     if (shape) DEFTET_LAUNCH(vlap::k_vlap_final, dim3(n_batch), dim3(256), st, (const float *)part, (int)gx, out);
     return DEFTET_OK;
 }
@@ -359,8 +354,7 @@ extern "C" int deftet_vertex_laplacian_bwd_f32(const float *r, const float *grad
                                                const float *t_vals, const float *row_weights, int weighting, int reduction, int n_batch,
                                                int n_vertex, int n_chan, int nnz, float *grad_x, void *stream_)
 {
-    const int rc = vlap_check(weighting, reduction, n_batch, n_vertex, n_chan, nnz, t_offsets, t_rows, t_vals, row_weights);
-    if (rc != DEFTET_OK) return rc;
+    DEFTET_TRY(vlap_check(weighting, reduction, n_batch, n_vertex, n_chan, nnz, t_offsets, t_rows, t_vals, row_weights));
     const bool shape = reduction == DEFTET_VLAP_SHAPE, rowdiv = weighting == DEFTET_VLAP_ROW_DIVISOR;
     DEFTET_CHECK_ARG(grad_out && (n_vertex == 0 || (r && grad_x)), "null pointer");
     DEFTET_CHECK_ARG(aligned(r, 4) && aligned(grad_out, 4) && aligned(grad_x, 4),

@@ -151,7 +151,7 @@ extern "C" int deftet_tet_gather_fwd_f32(const float *pos, const int64_t *tet_id
     if (B == 0 || T == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(pos && tet_idx && out, "null pointer");
     DEFTET_CHECK_ARG(((uintptr_t)tet_idx & 15) == 0 && ((uintptr_t)out & 15) == 0, "tet_idx/out must be 16-byte aligned");
-    DEFTET_LAUNCH(vtx::k_gather_fwd, dim3((T + 255) / 256, B), dim3(256), as_stream(stream_), pos, tet_idx, out, V, T, idx_batch, bad_flag);
+    DEFTET_LAUNCH(vtx::k_gather_fwd, dim3(blocks_for(T, 256), B), dim3(256), as_stream(stream_), pos, tet_idx, out, V, T, idx_batch, bad_flag);
     return DEFTET_OK;
 }
 
@@ -190,19 +190,17 @@ int deftet::vtx::incidence_csr(const int64_t *idx, int32_t *offsets, int32_t *sl
     DEFTET_CHECK_ARG(offsets && bad_flag && (E == 0 || (idx && slots)), "null pointer");
     const long long n = (long long)idx_batch * E * corners, nKeys = (long long)idx_batch * V;
     const CsrLayout L = csr_layout((size_t)n, workspace);
-    DEFTET_CHECK_ARG(n == 0 || (workspace && L.bytes <= workspace_bytes && ((uintptr_t)workspace & 255) == 0),
-                     "workspace null, misaligned or too small");
+    if (n > 0) DEFTET_TRY(workspace_ok("deftet_*_vertex_csr_i32", workspace, workspace_bytes, L.bytes));
     DEFTET_HIP(hipMemsetAsync(bad_flag, 0, 4, st));
     if (n == 0) {
         DEFTET_HIP(hipMemsetAsync(offsets, 0, (size_t)(nKeys + 1) * 4, st));
         return DEFTET_OK;
     }
-    const unsigned gb = (unsigned)((n + 255) / 256);
+    const unsigned gb = blocks_for(n, 256);
     DEFTET_LAUNCH(vtx::k_csr_keys, dim3(gb), dim3(256), st, idx, n, (long long)E * corners, V, L.key, L.val, bad_flag);
     // all 32 L.key bits: invalid incidences carry the L.key 0xFFFFFFFF and must sort behind every vertex
-    const int rc = prims::radix_sort<unsigned, unsigned>(L.key, L.skey, L.val, reinterpret_cast<unsigned *>(slots), (size_t)n, 32, L.sortTmp, L.sortTmpBytes, st);
-    if (rc != DEFTET_OK) return rc;
-    DEFTET_LAUNCH(vtx::k_csr_offsets, dim3((unsigned)((n + 256) / 256)), dim3(256), st, L.skey, n, nKeys, offsets);
+    DEFTET_TRY(prims::radix_sort<unsigned, unsigned>(L.key, L.skey, L.val, reinterpret_cast<unsigned *>(slots), (size_t)n, 32, L.sortTmp, L.sortTmpBytes, st));
+    DEFTET_LAUNCH(vtx::k_csr_offsets, dim3(blocks_for(n + 1, 256)), dim3(256), st, L.skey, n, nKeys, offsets);
     return DEFTET_OK;
 }
 
@@ -225,7 +223,7 @@ int deftet::vtx::gather_bwd_rows(const float *rows, const unsigned long long *ro
     DEFTET_CHECK_ARG(B <= 65535, "n_batch=%d exceeds 65535", B);
     if (B == 0 || V == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(offsets && grad_pos && (T == 0 || (rows && slots)), "null pointer");
-    const dim3 grid((((V + 63) / 64 + 7) / 8) * 8, B);
+    const dim3 grid(align_up(blocks_for(V, 64), 8), B);
     if (rowMask) DEFTET_LAUNCH(vtx::k_gather_bwd<true>, grid, dim3(256), st, rows, offsets, slots, grad_pos, V, (long long)T * 4, idx_batch, accumulate, rowMask);
     else DEFTET_LAUNCH(vtx::k_gather_bwd<false>, grid, dim3(256), st, rows, offsets, slots, grad_pos, V, (long long)T * 4, idx_batch, accumulate, rowMask);
     return DEFTET_OK;

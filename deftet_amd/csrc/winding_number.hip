@@ -484,17 +484,16 @@ extern "C" int deftet_winding_number_f32(const float *verts, const int32_t *vert
     if (B == 0 || N == 0) return DEFTET_OK;
     DEFTET_CHECK_ARG(points && winding && bad_counts, "null pointer");
     hipStream_t st = as_stream(stream_);
-    const dim3 blk(256), gn((N + 255) / 256, B);
+    const dim3 blk(256), gn(blocks_for(N, 256), B);
     if (F == 0 || nRec == 0) {
         DEFTET_HIP(hipMemsetAsync(bad_counts, 0, 16, st));
-        DEFTET_LAUNCH(k_wn_empty, dim3((unsigned)(((long long)B * N + 255) / 256)), blk, st, points, (long long)B * N, winding, bad_counts);
+        DEFTET_LAUNCH(k_wn_empty, dim3(blocks_for((long long)B * N, 256)), blk, st, points, (long long)B * N, winding, bad_counts);
         return DEFTET_OK;
     }
     DEFTET_CHECK_ARG(verts && faces, "null mesh");
-    DEFTET_CHECK_ARG(workspace && ((uintptr_t)workspace & 255) == 0, "workspace null or misaligned (256 bytes)");
     algo = resolve(algo, F, (long long)B * N);
     Layout L = make_layout(B, F, nRec, N, algo, workspace, workspace_bytes);
-    DEFTET_CHECK_ARG(L.bytes <= workspace_bytes, "workspace too small: need %zu bytes, got %zu", L.bytes, workspace_bytes);
+    DEFTET_TRY(workspace_ok(__func__, workspace, workspace_bytes, L.bytes));
     DEFTET_CHECK_ARG(algo == 1 || (unsigned long long)B * L.nLeafMax < 0x7FFFFFFFull, "too many leaves in the batch");
     DEFTET_HIP(hipMemsetAsync(bad_counts, 0, 16, st));
     DEFTET_HIP(hipMemsetAsync(L.shapeBad, 0, (size_t)B * 4, st));
@@ -508,22 +507,18 @@ extern "C" int deftet_winding_number_f32(const float *verts, const int32_t *vert
     }
     const float b = beta != 0.f ? beta : kBetaDefault;
     DEFTET_LAUNCH(k_wn_dom, dim3(B), dim3(64), st, (const float *)L.part, pb, F, L.Lmax, face_offsets, L.dom, L.lvl);
-    DEFTET_LAUNCH(k_wn_face_keys, dim3((F + 255) / 256, B), blk, st, (const float4 *)L.rec, F, face_offsets, (const float *)L.dom,
+    DEFTET_LAUNCH(k_wn_face_keys, dim3(blocks_for(F, 256), B), blk, st, (const float4 *)L.rec, F, face_offsets, (const float *)L.dom,
                   (const int *)L.lvl, L.nLeafMax, L.fs.keys);
-    {
-        const int rc = sort_and_segment(L.fs, L.fperm, L.seg, (size_t)nRec, (unsigned)B * L.nLeafMax, st);
-        if (rc != DEFTET_OK) return rc;
-    }
-    DEFTET_LAUNCH(k_wn_gather, dim3((unsigned)((nRec + 255) / 256)), blk, st, (const float4 *)L.rec, (const int32_t *)L.fperm, nRec, L.srec);
-    DEFTET_LAUNCH(k_wn_leaves, dim3((L.nLeafMax + 255) / 256, B), blk, st, (const float4 *)L.srec, (const int32_t *)L.seg, (const int *)L.lvl,
+    DEFTET_TRY(sort_and_segment(L.fs, L.fperm, L.seg, (size_t)nRec, (unsigned)B * L.nLeafMax, st));
+    DEFTET_LAUNCH(k_wn_gather, dim3(blocks_for(nRec, 256)), blk, st, (const float4 *)L.rec, (const int32_t *)L.fperm, nRec, L.srec);
+    DEFTET_LAUNCH(k_wn_leaves, dim3(blocks_for(L.nLeafMax, 256), B), blk, st, (const float4 *)L.srec, (const int32_t *)L.seg, (const int *)L.lvl,
                   L.nLeafMax, L.nNodeMax, L.nodes);
     for (int l = L.Lmax - 1; l >= 0; --l)
-        DEFTET_LAUNCH(k_wn_up, dim3(((1u << (3 * l)) + 255) / 256, B), blk, st, l, (const int *)L.lvl, L.nNodeMax, L.nodes);
+        DEFTET_LAUNCH(k_wn_up, dim3(blocks_for((1u << (3 * l)), 256), B), blk, st, l, (const int *)L.lvl, L.nNodeMax, L.nodes);
     if (algo == 2) {
         DEFTET_LAUNCH(k_wn_point_keys, gn, blk, st, points, N, (const float *)L.dom, (const int *)L.lvl, L.nLeafMax, L.ps.keys);
-        const int rc = prims::radix_sort_from<unsigned, unsigned>(prims::PtrLoad<unsigned>{L.ps.keys}, L.ps.sorted, prims::IotaLoad{}, L.pperm,
-                                                                   (size_t)B * N, key_bits((unsigned)B * L.nLeafMax), L.ps.tmp, L.ps.tmp_bytes, st);
-        if (rc != DEFTET_OK) return rc;
+        DEFTET_TRY(prims::radix_sort_from<unsigned, unsigned>(prims::PtrLoad<unsigned>{L.ps.keys}, L.ps.sorted, prims::IotaLoad{}, L.pperm,
+                                                              (size_t)B * N, key_bits((unsigned)B * L.nLeafMax), L.ps.tmp, L.ps.tmp_bytes, st));
         DEFTET_LAUNCH(k_wn_query<true>, gn, blk, st, points, (const float4 *)L.srec, (const float4 *)L.nodes, (const int32_t *)L.seg,
                       (const int *)L.lvl, (const int *)L.shapeBad, (const unsigned *)L.pperm, N, L.nLeafMax, L.nNodeMax, b * b, winding, bad_counts);
     } else {

@@ -13,7 +13,13 @@
  *     shape/device checks (check_condition_tet.cpp:19-25) become DEFTET_EINVAL;
  *   - kernels are enqueued on `stream` and NOT synchronised (the reference launches on
  *     the default stream and does not synchronise either); the `_host` builder variants
- *     are synchronous because they return data in host memory, exactly like run.so.
+ *     are synchronous because they return data in host memory, exactly like run.so;
+ *   - THE WORKSPACE CONTRACT: an entry point with a `workspace` takes a device buffer that is not NULL, 256-byte
+ *     aligned and at least its *_workspace_bytes(...) long, and refuses any other with DEFTET_EINVAL; the
+ *     message names the entry point, the bytes needed and the bytes given.  The exceptions are stated where
+ *     they apply: NULL selects the brute-force path of deftet_tri_dist_fwd*, deftet_nn_index* and
+ *     deftet_face_edge_adj*; deftet_rowdot*, deftet_sqrt_rowsum_f32 and deftet_radix_sort ask for no alignment,
+ *     deftet_scan for 16 bytes; a path of an entry that uses no workspace does not look at it.
  *
  * Paths in comments are relative to the reference checkout.
  */
@@ -898,7 +904,7 @@ int deftet_surface_metrics_f32(const float *p1_bxn1x3, const float *p2_bxn2x3, c
  *
  * deftet_face_vertex_csr_i32: face_idx int64 [F,3] -> offsets int32 [V+1], slots int32 [3F] holding 3*f+corner in ascending order
  * per vertex; *bad_flag (device int32, required) = 1 when an index is outside [0,V).  The 3-corner twin of
- * deftet_tet_vertex_csr_i32 (the same code); workspace 256-byte aligned.
+ * deftet_tet_vertex_csr_i32 (the same code).
  *
  * deftet_project_vertices_fwd_f32: pos f32 [pos_batch,V,3], feat f32 [feat_batch,V,D] (each batch 1 = shared by all views, or B),
  * rot f32 [B,3,3], cam_pos f32 [B,3], proj f32 [3] (device) -> z f32 [B,V], xy f32 [B,V,2], act f32 [B,V,Do]:
@@ -935,8 +941,8 @@ int deftet_face_gather_bwd_f32(const float *grad_face_xy, const float *grad_face
 
 /* The point-voxel operators between the point-cloud encoder and the tet grid (pointvoxel.hip).  No float atomics:
  * both scatters are gathers over a stable sort of the points (by voxel, by cell), so every sum has ONE order and two runs agree
- * bit for bit.  Workspace (256-byte aligned): deftet_pointvoxel_workspace_bytes(B, N, R) is the size of the one layout the four
- * entries with a workspace carve; each refuses a null, misaligned or smaller one with DEFTET_EINVAL.
+ * bit for bit.  deftet_pointvoxel_workspace_bytes(B, N, R) is the size of the one layout the four entries with a workspace carve
+ * (the workspace contract at the top).
  *
  * deftet_avg_voxelize_fwd_f32 (vox.cu avg_voxelize): feat f32 [B,C,N], coords i32 [B,3,N] -> out f32 [B,C,R^3], ind i32 [B,N] =
  * x R^2 + y R + z, cnt i32 [B,R^3].  out[b,c,s] = 0 + feat[b,c,i] * (1.0f / (float)cnt[s]) over the points of voxel s in ascending
@@ -1017,9 +1023,9 @@ int deftet_voxel_sample_bwd_pos_f32(const float *vol, const float *pos, const fl
  *   a coordinate the clamp holds (ix <= 0 or ix >= W - 1, a NaN included); the right-hand cell at an integer ix.
  * deftet_image_sample_bwd_global_f32: grad_global[b,g] = sum_n grad_out[b,g,n] of the first n_global rows of grad_out f32
  *   [B,C_total,N]: one wave per row, lane l adds n = l, l + 64, ... from 0, then the butterfly (offsets 32 .. 1).
- * Workspace (256-byte aligned): deftet_image_sample_workspace_bytes(B, N, H, W) is the size of the one layout deftet_image_cells_f32
- * and deftet_image_sample_bwd_map_f32 carve (the sort's arrays, then the partials); both refuse a smaller one with DEFTET_EINVAL
- * before any device call.  The other entries need no workspace. */
+ * deftet_image_sample_workspace_bytes(B, N, H, W) is the size of the one layout deftet_image_cells_f32 and
+ * deftet_image_sample_bwd_map_f32 carve (the sort's arrays, then the partials; the workspace contract at the top).  The other
+ * entries need no workspace. */
 size_t deftet_image_sample_workspace_bytes(int n_batch, int n_point, int height, int width);
 int deftet_image_sample_fwd_f32(const float *map, const float *uv, const float *global_features, const float *append, float *out,
                                 int n_batch, int n_channel, int height, int width, int n_point, int n_global, int n_append,
@@ -1058,7 +1064,7 @@ int deftet_image_sample_bwd_global_f32(const float *grad_out, float *grad_global
  *   ascending) and, per incidence, over the slots that chose tet t in ascending slot.  Every element of grad_pos is written; a
  *   vertex none of whose tets was chosen gets 0 (or keeps its value with accumulate).  A tet that lists a vertex twice counts
  *   twice, a tet chosen n times counts n times, a select entry outside [0,T) counts nowhere.  With select the slots are grouped
- *   by a stable radix sort in the workspace (256-byte aligned, deftet_tet_centroid_sample_workspace_bytes(B, T, n_slot)); without
+ *   by a stable radix sort in the workspace (deftet_tet_centroid_sample_workspace_bytes(B, T, n_slot)); without
  *   it no workspace is needed. */
 size_t deftet_tet_centroid_sample_workspace_bytes(int n_batch, int n_tet, int n_slot);
 int deftet_tet_centroid_sample_fwd_f32(const float *const *vols, const int *channels, const int *resolutions, int n_vol, const float *pos,
@@ -1092,8 +1098,8 @@ int deftet_tet_centroid_sample_bwd_vertices_f32(const float *grad_cent, const in
  *   4 t + corner ascending) and, per incidence (t, k), over the queries q of shape b with cond == t in ascending q, of the
  *   rounded product bary[b,q,k] * grad_out[b,q,c].  Every element of grad_field is written; a vertex none of whose tets was hit
  *   gets 0 (or keeps its value with accumulate); a tet that lists a vertex twice counts twice.  The per-tet query lists come from
- *   a stable radix sort of the keys b (T + 1) + t (misses at t = T) with the queries as values, in the workspace (256-byte
- *   aligned, deftet_tet_field_sample_workspace_bytes(B, T, Q)); without a query no workspace is needed.  A vertex runs as long
+ *   a stable radix sort of the keys b (T + 1) + t (misses at t = T) with the queries as values, in the workspace
+ *   (deftet_tet_field_sample_workspace_bytes(B, T, Q)); without a query no workspace is needed.  A vertex runs as long
  *   as the lists of its tets: load skew is accepted. */
 size_t deftet_tet_field_sample_workspace_bytes(int n_batch, int n_tet, int n_query);
 int deftet_tet_field_sample_fwd_f32(const float *field, const int32_t *tet_idx, const float *cond, const float *bary, float *out,
@@ -1108,7 +1114,7 @@ int deftet_tet_field_sample_bwd_field_f32(const float *grad_out, const float *co
 /* Ground-truth preparation (310; dataprep.hip): what dataloader.py:24-61 (MakeSurfaceMesh) does with Kaolin's
  * trianglemeshes_to_voxelgrids, extract_odms, project_odms, voxelgrids_to_trianglemeshes and adjacency_matrix.  PARITY UNPINNED:
  * Kaolin's arithmetic cannot be read or run next to this library; the rules below are this library's own.  Forward only.
- * Workspaces 256-byte aligned.  Every output is bit-reproducible (integer atomicOr / atomicAdd only, stable sorts, scans).
+ * Every output is bit-reproducible (integer atomicOr / atomicAdd only, stable sorts, scans).
  *
  * The bit grid: uint32 [B,R,R,W], W = ceil(R / 32); bit k % 32 of word k / 32 of row (i, j) is voxel (i, j, k); pad bits are 0.
  * 1 <= R <= 1024.

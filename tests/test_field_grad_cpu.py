@@ -126,7 +126,7 @@ def test_energies_workspace_is_the_layout_and_one_byte_short_is_refused(lib, B):
     args = lambda ws, n: (P, P, P, None, P, 1.0, B, 27, 48, 1, 3, ws, n, None)
     for ws, n in ((None, got), (P, got - 1), (ctypes.c_void_p(P.value + 16), got)):
         assert lib.deftet_tet_field_energies_fwd_f32(*args(ws, n)) == EINVAL
-        assert b"workspace missing, misaligned or too small" in lib.deftet_last_error()
+        assert b"workspace null, misaligned or too small: need %d bytes" % got in lib.deftet_last_error()
     assert lib.deftet_tet_field_energies_fwd_f32(*args(P, got)) == EINVAL and b"null pointer" in lib.deftet_last_error()
     assert lib.deftet_tet_field_energies_workspace_bytes(-1) == 0
 

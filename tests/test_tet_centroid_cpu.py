@@ -86,7 +86,7 @@ def test_bad_arguments_are_refused_by_name(lib):
     need = lib.deftet_tet_centroid_sample_workspace_bytes(1, 20, 5)
     for ws, nbytes in ((None, need), (P, need - 1), (ctypes.c_void_p(P.value + 16), need)):
         assert bvert(P, P, P, P, 0, P, 1, 10, 20, 1, 5, 0, ws, nbytes, None) == EINVAL
-        assert b"workspace missing, misaligned or too small" in lib.deftet_last_error()
+        assert b"workspace null, misaligned or too small: need %d bytes" % need in lib.deftet_last_error()
     # null pointers and a tet list batch that is neither 1 nor B
     assert fwd(ptrs(1), ints(3), ints(8), 1, None, None, None, 0, None, None, None, 1, 10, 20, 1, 5, 1, None) == EINVAL
     assert b"null" in lib.deftet_last_error()

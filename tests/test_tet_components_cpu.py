@@ -196,7 +196,7 @@ def test_bad_arguments_are_refused_by_name(lib):
                      (dict(inside=None), b"null pointer: inside_bxt"), (dict(nbr=None), b"nbr32_tx4"), (dict(nbr=off), b"misaligned pointer: nbr32_tx4"),
                      (dict(bad=None), b"null pointer: bad"), (dict(ws=None), b"workspace null"),
                      (dict(ws=ctypes.c_void_p(P.value + 16)), b"misaligned"),
-                     (dict(nbytes=lib.deftet_tet_components_workspace_bytes(2, 20) - 1), b"smaller than deftet_tet_components_workspace_bytes")):
+                     (dict(nbytes=lib.deftet_tet_components_workspace_bytes(2, 20) - 1), b"too small: need %d bytes" % lib.deftet_tet_components_workspace_bytes(2, 20))):
         rc, msg = both(**kw)
         assert rc == EINVAL and text in msg, (kw, msg)
     for k in range(4):                                                  # each of the four outputs by itself

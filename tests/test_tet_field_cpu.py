@@ -145,7 +145,7 @@ def test_bad_arguments_are_refused_by_name(lib):
     need = lib.deftet_tet_field_sample_workspace_bytes(1, 20, 5)
     for ws, nbytes in ((None, need), (P, need - 1), (ctypes.c_void_p(P.value + 16), need)):
         assert bf(P, P, P, P, P, P, 1, 10, 20, 1, 5, 4, 0, ws, nbytes, None) == EINVAL
-        assert b"workspace missing, misaligned or too small" in lib.deftet_last_error()
+        assert b"workspace null, misaligned or too small: need %d bytes" % need in lib.deftet_last_error()
     # sizes past what the indices hold
     assert fwd(P, P, P, P, P, None, 0.0, 1, 10, 1 << 24, 1, 5, 4, None) == -4 and b"2^24" in lib.deftet_last_error()
     assert fwd(P, P, P, P, P, None, 0.0, 70000, 10, 20, 1, 5, 4, None) == -4 and b"65535" in lib.deftet_last_error()

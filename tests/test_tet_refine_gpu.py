@@ -155,7 +155,7 @@ def test_bad_input(cuda):
     need = lib.deftet_tet_refine_workspace_bytes(T, E)
     ws = torch.empty(need, dtype=torch.uint8, device=cuda)
     args = (dev(cuda, tet_edge), dev(cuda, edges), marks, Pn, T, E, totals)
-    with pytest.raises(_lib.DefTetHipError, match="workspace too small"):
+    with pytest.raises(_lib.DefTetHipError, match="workspace null, misaligned or too small: need %d bytes, got %d" % (need, need - 1)):
         _lib.call("deftet_tet_refine_count_i64", cuda, *args, ws=ws[:need - 1])
     _lib.call("deftet_tet_refine_count_i64", cuda, *args, ws=ws)
     assert totals.tolist() == [int(want.marks.sum()), len(want.tet_new), 0]

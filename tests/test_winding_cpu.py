@@ -71,7 +71,7 @@ def test_workspace_is_the_layout_and_one_byte_short_is_refused(lib, B, F, N):
     assert size(B, B * F, F, 2 * N + 4096, FAST) > want[FAST] and size(B, B * F, F, 2 * N + 4096, EXACT) == want[EXACT]
     assert size(B, B * F, F, N, AUTO) == want[lib.deftet_winding_number_resolve_algo(AUTO, F, B * N)]
     for a, w in want.items():
-        assert _call(lib, B=B, F=F, N=N, algo=a, ws_bytes=w - 1) == EINVAL and b"workspace too small" in lib.deftet_last_error()
+        assert _call(lib, B=B, F=F, N=N, algo=a, ws_bytes=w - 1) == EINVAL and b"workspace null, misaligned or too small: need %d bytes" % w in lib.deftet_last_error()
         assert _call(lib, B=B, F=F, N=N, algo=a, ws_bytes=w, verts=None) == EINVAL and b"null mesh" in lib.deftet_last_error()
         assert _call(lib, B=B, F=F, N=N, algo=a, ws_bytes=w, ws=None) == EINVAL and b"workspace" in lib.deftet_last_error()
         assert _call(lib, B=B, F=F, N=N, algo=a, ws_bytes=w, ws=ctypes.c_void_p(P.value + 16)) == EINVAL and b"misaligned" in lib.deftet_last_error()
