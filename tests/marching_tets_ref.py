@@ -7,6 +7,11 @@ One shape at a time, in float32 and in the kernel's operation order, with this f
     marching_tets(pos, field, tets, ...)    Mesh(verts, faces, vert_attr, edge_id, t, tet_id) of one shape
     grads32(...)                            the backward's formulas in float32
     marching_tets_torch(...)                the same vertices in torch (float64 when its inputs are), for autograd
+    grads64(...)                            the gradients by float64 autograd
+    grads64_terms(...), entry_bound(...)    the same by the closed formulas, with the absolute sum of every entry's terms, and
+                                            the per-entry bound of a double accumulation rounded once
+    forward64(...)                          t, vertices and attributes in float64 with their float32 bounds
+    same_rows_nan_aware(a, b)               bit equality that takes any NaN for any NaN
     closed_and_oriented(faces, n_vert)      the watertightness check of the tests
 """
 import collections
@@ -118,7 +123,7 @@ def grads64(pos, field, edges, iso, g_verts, attr=None, g_attr=None):
     """the same gradients by float64 autograd through marching_tets_torch: (grad_pos, grad_field, grad_attr) as float64 numpy.
     The inside test runs on the float32 field against the float32 iso, like the operator's."""
     import torch
-    f32 = torch.from_numpy(np.asarray(field, np.float32))
+    f32 = torch.from_numpy(np.array(field, np.float32))
     p = torch.from_numpy(np.asarray(pos, np.float64)).requires_grad_(True)
     f = f32.double().requires_grad_(True)
     a = None if attr is None else torch.from_numpy(np.asarray(attr, np.float64)).requires_grad_(True)
@@ -131,6 +136,84 @@ def grads64(pos, field, edges, iso, g_verts, attr=None, g_attr=None):
     grads = torch.autograd.grad(loss, (p, f) if a is None else (p, f, a), allow_unused=True)
     out = [np.zeros(x.shape) if g is None else g.numpy() for g, x in zip(grads, (p, f, a))]
     return out[0], out[1], (out[2] if a is not None else None)
+
+
+def grads64_terms(pos, field, edges, iso, g_verts, attr=None, g_attr=None, skip=None):
+    """The same gradients by the closed formulas of DESIGN.md §6l, term by term in float64 from the float32 inputs widened and
+    float(float32(iso)); the inside test runs in float32 like the operator's.  ((grad_pos, grad_field, grad_attr), (S_pos, S_field,
+    S_attr)): S holds, entry by entry, the sum of the absolute values of the terms that were added into it — (1-t) g and t g for
+    grad_pos and grad_attr, |dt/df| sum_k |g_k (x_max - x_min)_k| over position and attribute components for grad_field.  The rows
+    of g_verts / g_attr are the crossing edges in ascending id, ALL of them; `skip` (bool [E]) leaves edges out of the sums."""
+    field = np.asarray(field, np.float32)
+    _inside, cross = _crossings(field, edges, iso)
+    e = np.nonzero(cross)[0]
+    keep = np.ones(e.size, bool) if skip is None else ~np.asarray(skip, bool)[e]
+    e = e[keep]
+    lo, hi = edges[e, 0], edges[e, 1]
+    pos, f, iso64 = np.asarray(pos, np.float32).astype(np.float64), field.astype(np.float64), float(np.float32(iso))
+    d = f[hi] - f[lo]
+    t = (iso64 - f[lo]) / d
+    dt_lo, dt_hi = (iso64 - f[hi]) / (d * d), -(iso64 - f[lo]) / (d * d)
+    absdot = np.zeros(e.size)
+
+    def spread(x, g):
+        """the two weighted sums of g into a zero array like x, their absolute sums, and this part of sum_k g_k (x_max - x_min)_k"""
+        g = np.asarray(g, np.float32).astype(np.float64)[keep]
+        out, S = np.zeros(x.shape), np.zeros(x.shape)
+        for ends, w in ((lo, 1.0 - t), (hi, t)):
+            np.add.at(out, ends, w[:, None] * g)
+            np.add.at(S, ends, np.abs(w[:, None] * g))
+        prod = g * (x[hi] - x[lo])
+        absdot[:] += np.abs(prod).sum(1)
+        return out, S, prod.sum(1)
+    gp, Sp, dot = spread(pos, g_verts)
+    ga = Sa = None
+    if attr is not None:
+        ga, Sa, dot_a = spread(np.asarray(attr, np.float32).astype(np.float64), g_attr)
+        dot = dot + dot_a
+    gf, Sf = np.zeros(f.shape), np.zeros(f.shape)
+    for ends, dt in ((lo, dt_lo), (hi, dt_hi)):
+        np.add.at(gf, ends, dt * dot)
+        np.add.at(Sf, ends, np.abs(dt) * absdot)
+    return (gp, gf, ga), (Sp, Sf, Sa)
+
+
+def entry_bound(want, S):
+    """|kernel - want| entry by entry for a kernel that works and sums in double and rounds once: 2^-24 |want| for
+    the one rounding to float32, 2^-40 S for a double sum in another order than numpy's (about 28 terms at 2^-53 each is 2^-48 S:
+    a factor 2^8 to spare, and 2^16 under what one float32 intermediate leaves), 2^-149 for a float32-subnormal result"""
+    return 2.0 ** -24 * np.abs(want) + 2.0 ** -40 * S + 2.0 ** -149
+
+
+U32 = 2.0 ** -24
+
+
+def forward64(pos, field, edges, iso, attr=None):
+    """(t, verts, vert_attr) of the crossing edges in float64 from the float32 inputs, each with its float32 bound:
+    4u |t| — the roundings of iso - f_min, f_max - f_min and the quotient, one u for the second order; 6u (|x_min| + |x_max|) per
+    component — 3u from t, u each for the difference, the product (5u on t (x_max - x_min), at most |x_min| + |x_max| for t in
+    [0,1]) and the sum.  u = 2^-24.  -> ((t, bound), (verts, bound), (vert_attr, bound) | None)"""
+    field = np.asarray(field, np.float32)
+    _inside, cross = _crossings(field, edges, iso)
+    e = np.nonzero(cross)[0]
+    lo, hi = edges[e, 0], edges[e, 1]
+    f = field.astype(np.float64)
+    t = (float(np.float32(iso)) - f[lo]) / (f[hi] - f[lo])
+
+    def lerp(x):
+        x = np.asarray(x, np.float32).astype(np.float64)
+        return x[lo] + t[:, None] * (x[hi] - x[lo]), 6 * U32 * (np.abs(x[lo]) + np.abs(x[hi]))
+    return (t, 4 * U32 * np.abs(t)), lerp(pos), (None if attr is None else lerp(attr))
+
+
+def same_rows_nan_aware(a, b):
+    """equal shapes and dtypes, NaN exactly where the other side has NaN (any payload, either sign), equal BYTES everywhere else"""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype or a.dtype != np.float32:
+        return False
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    na, nb = np.isnan(a), np.isnan(b)
+    return bool((na == nb).all() and (a.view(np.uint32)[~na] == b.view(np.uint32)[~na]).all())
 
 
 def closed_and_oriented(faces, n_vert):
