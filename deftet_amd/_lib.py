@@ -204,6 +204,11 @@ SIGNATURES = {
     "deftet_tet_field_energies_bwd_f32": (_i, [_vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "deftet_tet_to_vertex_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _vp]),
     "deftet_tet_to_vertex_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "deftet_tet_iso_fraction_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),
+    "deftet_tet_iso_fraction_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),
+    "deftet_tet_iso_measures_workspace_bytes": (_sz, [_i]),
+    "deftet_tet_iso_measures_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "deftet_tet_iso_measures_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),
 }
 
 _lock = threading.Lock()

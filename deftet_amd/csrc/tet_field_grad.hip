@@ -16,6 +16,7 @@
 //                out = num / den; back: gval[t,c] = w_t * (sum over the corners 0..3 of gout[v_k,c] / den[v_k], from 0)
 // G_c is the gradient arriving on g_c: read from memory (tet_field_gradient) or formed from the energies' saved sums.
 #include "common.hpp"
+#include "tet_frame.hpp"                                             // tet_frame: the tet's adjugate rows, det and whether it is live
 #include "wave.hpp"
 
 namespace deftet {
@@ -25,31 +26,6 @@ constexpr int kTfgBlock = 256;
 constexpr int kTfeMaxC = 8;                                          // channels of the energies (as marching_tets' attr)
 constexpr int kTfeParts = 64;                                        // workgroups per shape of the energy pass: one partial per lane of k_tfe_final
 constexpr int kTfeStats = 1 + 2 * kTfeMaxC;                          // W, then S0_c / W, then S1_c / W
-
-// the tet at row `trow` of the index list over the positions p of its shape: the adjugate rows n, det; false for a dead tet
-__device__ __forceinline__ bool tfg_tet(const float *__restrict__ p, const int32_t *__restrict__ tet_idx, size_t trow, int V, int vi[4],
-                                        float n[3][3], float &det)
-{
-    const int4 q = *reinterpret_cast<const int4 *>(tet_idx + trow * 4);
-    vi[0] = q.x; vi[1] = q.y; vi[2] = q.z; vi[3] = q.w;
-    det = 0.0f;
-    if ((unsigned)q.x >= (unsigned)V || (unsigned)q.y >= (unsigned)V || (unsigned)q.z >= (unsigned)V || (unsigned)q.w >= (unsigned)V)
-        return false;
-    float x[4][3], e[3][3];
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) x[k][a] = p[(size_t)vi[k] * 3 + a];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) e[k][a] = x[k + 1][a] - x[0][a];
-    cross3(e[1], e[2], n[0]);
-    cross3(e[2], e[0], n[1]);
-    cross3(e[0], e[1], n[2]);
-    det = dot3(e[0], n[0]);
-    return det > 0.0f;                                                // (a NaN is not)
-}
 
 // g_c of a live tet; f points at channel c of vertex 0 of the shape's field
 __device__ __forceinline__ void tfg_grad(const float *__restrict__ f, int C, const int vi[4], const float n[3][3], float det, float g[3])
@@ -78,7 +54,7 @@ __global__ __launch_bounds__(kTfgBlock) void k_tfg_fwd(const float *__restrict__
     const int t = (int)(e / C), c = (int)(e - (long long)t * C);
     int vi[4];
     float n[3][3], det, g[3] = {0.0f, 0.0f, 0.0f};
-    const bool live = tfg_tet(pos + (size_t)b * V * 3, tet_idx, (idx_batch > 1 ? (size_t)b * T : 0) + t, V, vi, n, det);
+    const bool live = tet_frame(pos + (size_t)b * V * 3, tet_idx, (idx_batch > 1 ? (size_t)b * T : 0) + t, V, vi, n, det);
     if (out) {                                                        // (without it: the volumes alone)
         if (live) tfg_grad(field + (size_t)b * V * C + c, C, vi, n, det, g);
         float *o = out + (((size_t)b * T + t) * C + c) * 3;
@@ -144,7 +120,7 @@ __device__ __forceinline__ void tfg_bwd_field(const Up up, const float *__restri
         if ((unsigned)t >= (unsigned)T) continue;
         int vi[4];
         float n[3][3], det, g[3], G[3], m[3], gv = 0.0f;
-        if (!tfg_tet(p, tet_idx, tbase + t, V, vi, n, det)) continue;
+        if (!tet_frame(p, tet_idx, tbase + t, V, vi, n, det)) continue;
         tfg_grad(f, C, vi, n, det, g);
         up.on_grad(t, c, g, det, G, gv);
         tfg_corner(n, k, m);
@@ -170,7 +146,7 @@ __device__ __forceinline__ void tfg_bwd_pos(const Up up, const float *__restrict
         if ((unsigned)t >= (unsigned)T) continue;
         int vi[4];
         float n[3][3], det, m[3];
-        if (!tfg_tet(p, tet_idx, tbase + t, V, vi, n, det)) continue;
+        if (!tet_frame(p, tet_idx, tbase + t, V, vi, n, det)) continue;
         tfg_corner(n, k, m);
         float r[3] = {0.0f, 0.0f, 0.0f}, gv = up.on_vol(t);
         for (int c = 0; c < C; ++c) {
@@ -238,7 +214,7 @@ __global__ __launch_bounds__(kTfgBlock) void k_tfe_pass(const float *__restrict_
     for (int t = blockIdx.x * kTfgBlock + threadIdx.x; t < T; t += kTfeParts * kTfgBlock) {
         int vi[4];
         float n[3][3], det;
-        if (!tfg_tet(p, tet_idx, tbase + t, V, vi, n, det)) continue;
+        if (!tet_frame(p, tet_idx, tbase + t, V, vi, n, det)) continue;
         const double w = (double)(det / 6.0f);
         acc[0] += w;
 #pragma unroll

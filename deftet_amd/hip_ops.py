@@ -3095,6 +3095,167 @@ def unit_normals(grad_nx3):
     return torch.where(norm > 0, -grad_nx3 / norm.clamp_min(torch.finfo(torch.float32).tiny), torch.zeros_like(grad_nx3))
 
 
+# ------------------------------------------------------------------------------------
+# iso-solid measures on the tets: inside fraction, area, volume, intersection (tet_iso_measure.hip)
+# ------------------------------------------------------------------------------------
+def _tim_args(caller, field, pos, tet_idx, iso, topology=None):
+    """(field [B,V], pos, idx, iso) of the iso measures: the tet-mesh argument contract with a field [B,V] or [B,V,1] and a
+    finite float32 level, all decided before any C entry is reached"""
+    iso = float(iso)
+    with np.errstate(over="ignore"):
+        finite = np.isfinite(np.float32(iso))
+    if not finite:
+        raise _lib.DefTetHipError("%s: iso = %r is not a finite float32 (DEFTET_EINVAL)" % (caller, iso))
+    if isinstance(field, torch.Tensor) and field.dim() == 2:
+        field = field[:, :, None]
+    pos, idx, field, _ = _mesh_args(caller, pos, tet_idx, topology, field=field)
+    if pos is None or field.shape[2] != 1:
+        raise _expected(caller, "pos [B,V,3] and field [B,V] or [B,V,1]", field)
+    return field.reshape(field.shape[0], field.shape[1]), pos, idx, iso
+
+
+def _tim_grad(caller, g, B, T, dev):
+    """an upstream gradient f32 [B,T] of the iso measures, or None"""
+    if g is None:
+        return None
+    _lib.require_gpu(g)
+    g = _f32c(g)
+    if tuple(g.shape) != (B, T) or g.device != dev:
+        raise _expected(caller, "a gradient [%d,%d] on %s" % (B, T, dev), "%s on %s" % (tuple(g.shape), g.device))
+    return g
+
+
+def tet_iso_fraction_fwd(field, pos_bxvx3, tet_idx, iso=0.0, return_area=False, return_volume=False):
+    """(frac f32 [B,T], area f32 [B,T] | None, vol f32 [B,T] | None): per tet the share of its volume with field > iso, the area
+    of the iso polygon in it and its volume (the bits of tet_volumes on every live tet, 0 on a dead one).  One launch.  The raw
+    forward of tet_iso_fraction."""
+    field, pos, idx, iso = _tim_args("tet_iso_fraction", field, pos_bxvx3, tet_idx, iso)
+    B, V = field.shape
+    T, dev = idx.shape[1], field.device
+    frac = torch.empty(B, T, device=dev, dtype=torch.float32)
+    area = torch.empty(B, T, device=dev, dtype=torch.float32) if return_area else None
+    vol = torch.empty(B, T, device=dev, dtype=torch.float32) if return_volume else None
+    _lib.call("deftet_tet_iso_fraction_fwd_f32", dev, field, pos, idx, frac, area, vol, iso, B, V, T, idx.shape[0])
+    return frac, area, vol
+
+
+def tet_iso_fraction_bwd(grad_frac, grad_area, grad_vol, field, pos_bxvx3, tet_idx, csr, iso=0.0, want_field=True, want_pos=True):
+    """(grad_field f32 [B,V] | None, grad_pos f32 [B,V,3] | None): grad_frac, grad_area, grad_vol f32 [B,T] (each or None) of
+    tet_iso_fraction_fwd taken to the vertices, per vertex one fp64 accumulator per output over its incidences in the CSR's order
+    (ascending 4 t + corner), rounded once; no atomics, the same bits on every run.  One launch."""
+    field, pos, idx, iso = _tim_args("tet_iso_fraction_bwd", field, pos_bxvx3, tet_idx, iso)
+    B, V = field.shape
+    T, dev = idx.shape[1], field.device
+    _check_csr("tet_iso_fraction_bwd", csr, B, V, T, idx.shape[0], dev)
+    g = [_tim_grad("tet_iso_fraction_bwd", x, B, T, dev) for x in (grad_frac, grad_area, grad_vol)]
+    gf = torch.empty(B, V, device=dev, dtype=torch.float32) if want_field else None
+    gp = torch.empty(B, V, 3, device=dev, dtype=torch.float32) if want_pos else None
+    if want_field or want_pos:
+        _lib.call("deftet_tet_iso_fraction_bwd_f32", dev, g[0], g[1], g[2], field, pos, idx, csr[0], csr[1], gf, gp, iso, B, V, T, idx.shape[0])
+    return gf, gp
+
+
+class _TetIsoFraction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, field, pos, idx, csr, iso, return_area, return_volume):
+        frac, area, vol = tet_iso_fraction_fwd(field, pos, idx, iso, return_area, return_volume)
+        ctx.save_for_backward(field, pos)
+        ctx.idx, ctx.csr, ctx.iso = idx, csr, iso
+        ctx.set_materialize_grads(False)
+        return frac, area, vol
+
+    @staticmethod
+    def backward(ctx, g_frac, g_area, g_vol):
+        field, pos = ctx.saved_tensors
+        want_f, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_f or want_p):
+            return (None,) * 7
+        if g_frac is None and g_area is None and g_vol is None:
+            return (torch.zeros_like(field) if want_f else None, torch.zeros_like(pos) if want_p else None) + (None,) * 5
+        csr = _csr_or_build(ctx.csr, ctx.idx, pos.shape[1])
+        gf, gp = tet_iso_fraction_bwd(g_frac, g_area, g_vol, field.detach(), pos.detach(), ctx.idx, csr, ctx.iso, want_field=want_f,
+                                      want_pos=want_p)
+        return (gf, gp) + (None,) * 5
+
+
+def tet_iso_fraction(field, pos_bxvx3, tet_idx, iso=0.0, csr=None, topology=None, return_area=False, return_volume=False):
+    """frac f32 [B,T] (then area f32 [B,T] with return_area, then vol f32 [B,T] with return_volume): the share of every tet of
+    the mesh (pos f32 [B,V,3], tet_idx int [T,4] or [B,T,4]) that lies inside the solid {field > iso} of the per-vertex field f32
+    [B,V] or [B,V,1] — a soft per-tet occupancy in [0,1], exactly 0 or 1 off the surface, usable wherever a predicted per-tet
+    occupancy is — the area of the iso polygon in the tet, and the tet's volume.  It is the solid marching_tets bounds: a corner
+    is inside iff field > iso in fp32 (strict), the cuts sit at the same parameters.  The field is linear on a tet, so the
+    fraction is a closed form in the four corner values (a small tet, its complement, or a wedge); computed in double from the
+    fp32 inputs and rounded once.  A tet is live iff it is live to tet_field_gradient (det E > 0 in fp32) and its four corner
+    values are finite; a dead tet has fraction, area and volume 0 and gives nothing to a backward.  (marching_tets differs on
+    purpose: there a NaN corner is outside and faces are emitted.)  Differentiable in field and pos — frac in field alone, vol
+    in pos alone, area in both — through the incidence CSR in its order with one fp64 accumulator per vertex and no float
+    atomics (the same bits on every run); on a kink the derivative of the case the predicate picks.  `csr`, `topology` and the
+    slow path as in tet_field_gradient."""
+    field, pos, idx, iso = _tim_args("tet_iso_fraction", field, pos_bxvx3, tet_idx, iso, topology)
+    csr = _resolve_csr("tet_iso_fraction", csr, topology, pos, idx)
+    frac, area, vol = _TetIsoFraction.apply(field, pos, idx, csr, iso, bool(return_area), bool(return_volume))
+    out = (frac,) + ((area,) if return_area else ()) + ((vol,) if return_volume else ())
+    return out if len(out) > 1 else frac
+
+
+class _TetIsoMeasures(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, field, pos, idx, csr, iso, weights):
+        lib = _lib.load()
+        B, V = field.shape
+        T, dev = idx.shape[1], field.device
+        out = torch.empty(B, 5, device=dev, dtype=torch.float32)
+        _lib.call("deftet_tet_iso_measures_fwd_f32", dev, field, pos, idx, weights, out, iso, B, V, T, idx.shape[0],
+                  ws=lib.deftet_tet_iso_measures_workspace_bytes(B))
+        ctx.save_for_backward(field, pos, weights)
+        ctx.idx, ctx.csr, ctx.iso = idx, csr, iso
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        field, pos, weights = ctx.saved_tensors
+        want_f, want_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_f or want_p):
+            return (None,) * 6
+        B, V = field.shape
+        idx, dev = ctx.idx, field.device
+        csr = _csr_or_build(ctx.csr, idx, V)
+        gf = torch.empty(B, V, device=dev, dtype=torch.float32) if want_f else None
+        gp = torch.empty(B, V, 3, device=dev, dtype=torch.float32) if want_p else None
+        _lib.call("deftet_tet_iso_measures_bwd_f32", dev, _f32c(g_out), weights, field, pos, idx, csr[0], csr[1], gf, gp, ctx.iso, B, V,
+                  idx.shape[1], idx.shape[0])
+        return (gf, gp) + (None,) * 4
+
+
+def tet_iso_measures(field, pos_bxvx3, tet_idx, iso=0.0, weights=None, csr=None, topology=None):
+    """f32 [B,5]: per shape the totals of tet_iso_fraction over the live tets —
+        [:,0] = sum frac vol     the volume enclosed by the level set (inside the mesh)
+        [:,1] = sum area         the area of the iso surface
+        [:,2] = sum w frac vol   its intersection with the per-tet occupancy w
+        [:,3] = sum w vol        the volume of that occupancy
+        [:,4] = sum vol          the live volume
+    weights f32 [B,T] is a ground-truth occupancy per tet, a CONSTANT (no gradient); None = 1.  vol is det E / 6 in double from
+    the fp32 positions; the sums run in fp64 in one order and are rounded once.  iso_iou(measures) is the volumetric IoU.
+    Differentiable in field and pos from the five upstream scalars alone (no [B,T] tensor in either direction), through the
+    incidence CSR without float atomics; `csr`, `topology` and the slow path as in tet_field_gradient."""
+    field, pos, idx, iso = _tim_args("tet_iso_measures", field, pos_bxvx3, tet_idx, iso, topology)
+    w = None
+    if weights is not None:
+        w = _f32_on("tet_iso_measures", "weights", weights, field.device, False).detach()
+        if tuple(w.shape) != (field.shape[0], idx.shape[1]):
+            raise _expected("tet_iso_measures", "weights [%d,%d]" % (field.shape[0], idx.shape[1]), w)
+    csr = _resolve_csr("tet_iso_measures", csr, topology, pos, idx)
+    return _TetIsoMeasures.apply(field, pos, idx, csr, iso, w)
+
+
+def iso_iou(measures):
+    """[B]: the volumetric IoU of the field's solid with the occupancy, I / (V_in + W - I) on the columns of tet_iso_measures,
+    0 where the union is 0.  Plain torch: differentiable through the measures."""
+    v_in, inter, w = measures[..., 0], measures[..., 2], measures[..., 3]
+    union = v_in + w - inter
+    return torch.where(union > 0, inter / torch.where(union > 0, union, torch.ones_like(union)), torch.zeros_like(union))
+
+
 def trilinear_devoxelize_fwd(r, is_training, coords, features):
     """(outs f32 [B,C,N], inds i32 [B,8,N], wgts f32 [B,8,N]) of coords f32 [B,3,N] in voxel units and features f32 [B,C,r^3]: the
     extension's trilinear_devoxelize_forward, one fixed expression per point (the reference kernel's bits).  hi = lo where

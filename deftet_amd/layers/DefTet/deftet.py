@@ -91,6 +91,17 @@ class TetTopology:
         (|grad f| - target)^2 of the per-vertex field, differentiable in field and vertice_pos."""
         return hip_ops.tet_field_energies(field, vertice_pos, self.tet_idx32, topology=self, target=target)
 
+    def iso_fraction(self, field, vertice_pos, iso=0.0, return_area=False, return_volume=False):
+        """hip_ops.tet_iso_fraction on this tet list: per tet the share of its volume inside {field > iso} of the per-vertex field
+        [B,V] / [B,V,1], [B,T] (then the iso polygon's area, then the volume), differentiable in field and vertice_pos."""
+        return hip_ops.tet_iso_fraction(field, vertice_pos, self.tet_idx32, iso=iso, topology=self, return_area=return_area,
+                                        return_volume=return_volume)
+
+    def iso_measures(self, field, vertice_pos, iso=0.0, weights=None):
+        """hip_ops.tet_iso_measures on this tet list: [B,5] = (enclosed volume, surface area, intersection with the per-tet
+        occupancy `weights`, that occupancy's volume, live volume), differentiable in field and vertice_pos."""
+        return hip_ops.tet_iso_measures(field, vertice_pos, self.tet_idx32, iso=iso, weights=weights, topology=self)
+
     def to_vertices(self, values_bxtxc, weights=None, fill=0.0):
         """hip_ops.tet_to_vertex on this tet list: per-tet values [B,T,C] as the (weighted) mean over each vertex's incident
         tets, [B,V,C]; differentiable in the values, the weights a constant."""
@@ -267,6 +278,25 @@ class DefTet(nn.Module):
         """[B,C,2] = (sum w |grad f_c|^2 / W, sum w (|grad f_c| - target)^2 / W) over the live tets, w their volumes, of the
         per-vertex field [B,V,C] (1 <= C <= 8); the gradient reaches field and vertice_pos (hip_ops.tet_field_energies)."""
         return _topology_for(tetrahedron_bxfx4, vertice_pos.shape[1]).field_energies(field, vertice_pos, target=target)
+
+    # --- the solid {field > iso} of a per-vertex field, measured per tet and per shape (hip_ops.tet_iso_fraction / tet_iso_measures)
+    def field_measures(self, vertice_pos, tetrahedron_bxfx4, field, iso=0.0, gt_occ_bxt=None):
+        """[B,5] = (enclosed volume, iso-surface area, intersection with gt_occ_bxt, volume of gt_occ_bxt, live volume) of the
+        per-vertex field [B,V] / [B,V,1]; gt_occ_bxt [B,T] / [B,T,1] is a constant (None = 1).  The gradient reaches field and
+        vertice_pos: the area as a minimal-surface regulariser, the volume as a prior."""
+        w = None if gt_occ_bxt is None else gt_occ_bxt.detach().reshape(gt_occ_bxt.shape[0], -1).float().contiguous()
+        return _topology_for(tetrahedron_bxfx4, vertice_pos.shape[1]).iso_measures(field, vertice_pos, iso=iso, weights=w)
+
+    def field_occupancy(self, vertice_pos, tetrahedron_bxfx4, field, iso=0.0):
+        """[B,T] in [0,1]: the exact share of every tet inside {field > iso} — the per-tet occupancy of a per-vertex field, usable
+        wherever pred_tet_occ is (the BCE against center_occ, paste_occ, get_boundary_index after a threshold); its gradient sees
+        where in the tet the surface is."""
+        return _topology_for(tetrahedron_bxfx4, vertice_pos.shape[1]).iso_fraction(field, vertice_pos, iso=iso)
+
+    def field_iou(self, vertice_pos, tetrahedron_bxfx4, field, gt_occ_bxt, iso=0.0):
+        """[B]: the exact volumetric IoU of {field > iso} with the per-tet ground-truth occupancy gt_occ_bxt [B,T] / [B,T,1]
+        (validate_iou's quantity, without sampling points); differentiable in field and vertice_pos."""
+        return hip_ops.iso_iou(self.field_measures(vertice_pos, tetrahedron_bxfx4, field, iso=iso, gt_occ_bxt=gt_occ_bxt))
 
     # --- the welded iso-surface of a per-TET occupancy: to the vertices, then marching tetrahedra
     def iso_surface(self, vertice_pos, tetrahedron_bxfx4, pred_tet_occ, iso=0.5, volume_weighted=True):

@@ -48,6 +48,8 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
+/* 400: iso-solid measures on the tets — deftet_tet_iso_fraction_fwd_f32 / _bwd_f32, deftet_tet_iso_measures_fwd_f32 / _bwd_f32 with
+ *      deftet_tet_iso_measures_workspace_bytes (tet_iso_measure.hip). */
 /* 390: field gradients on the tets — deftet_tet_field_gradient_fwd_f32 / _bwd_f32, deftet_tet_field_energies_fwd_f32 / _bwd_f32 with
  *      deftet_tet_field_energies_workspace_bytes, deftet_tet_to_vertex_fwd_f32 / _bwd_f32 (tet_field_grad.hip). */
 /* 380: conforming selective tet refinement (red-green closure on edge marks) — deftet_tet_refine_mark_i64, deftet_tet_refine_count_i64,
@@ -1211,6 +1213,38 @@ int deftet_tet_to_vertex_fwd_f32(const float *values, const float *weights, cons
                                  void *stream);
 int deftet_tet_to_vertex_bwd_f32(const float *grad_out, const float *weight_sum, const float *weights, const int32_t *tet_idx,
                                  float *grad_values, int n_batch, int n_vertex, int n_tet, int idx_batch, int n_channel, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * Iso-solid measures on the tets (400; tet_iso_measure.hip).  field f32 [B,V], pos, tet_idx, offsets / slots as
+ * for the field gradients above; iso a finite f32 (DEFTET_EINVAL otherwise).  A corner is inside iff field > iso (fp32, strict:
+ * the predicate of deftet_marching_tets_*).  A tet is live iff it is live to deftet_tet_field_gradient_fwd_f32 (det > 0 in fp32,
+ * indices in [0,V)) AND its four corner values are finite; a dead tet has fraction 0, area 0, volume 0 and takes part in no
+ * sum and no backward (marching tetrahedra differ here on purpose: there a NaN corner is outside and faces are emitted).
+ * Per live tet, in double from the fp32 inputs and rounded once: frac = the share of the tet's volume with field > iso (the
+ * field is linear on the tet), area = the area of the iso polygon in the tet; the closed forms stand in the file's header.
+ * deftet_tet_iso_fraction_fwd_f32: frac f32 [B,T], area f32 [B,T] (optional), vol f32 [B,T] (optional, the bits of
+ *   deftet_tet_field_gradient_fwd_f32's volumes).  One launch.
+ * deftet_tet_iso_fraction_bwd_f32: grad_frac, grad_area, grad_vol f32 [B,T] (each optional) taken to grad_field f32 [B,V] and
+ *   grad_pos f32 [B,V,3] (each optional, every element written): per vertex one fp64 accumulator per output over its incidences
+ *   in ascending 4 t + corner, the tet's case recomputed per incidence, rounded once.  frac does not depend on pos, vol not on
+ *   field.  On a kink (a corner on the level) the derivative of the case the predicate picks.  One launch.
+ * deftet_tet_iso_measures_fwd_f32: out f32 [B,5] = (sum frac vol, sum area, sum w frac vol, sum w vol, sum vol) over the live
+ *   tets, weights w f32 [B,T] (NULL = 1), vol = det / 6 in double; the sums in fp64 in one order, rounded once.  Two launches.
+ * deftet_tet_iso_measures_bwd_f32: grad_out f32 [B,5] taken to grad_field and grad_pos by the same walk; the weights are a
+ *   constant.  Nothing of size O(T) is stored between forward and backward. */
+int deftet_tet_iso_fraction_fwd_f32(const float *field, const float *pos, const int32_t *tet_idx, float *frac, float *area, float *vol,
+                                    float iso, int n_batch, int n_vertex, int n_tet, int idx_batch, void *stream);
+int deftet_tet_iso_fraction_bwd_f32(const float *grad_frac, const float *grad_area, const float *grad_vol, const float *field,
+                                    const float *pos, const int32_t *tet_idx, const int32_t *offsets, const int32_t *slots,
+                                    float *grad_field, float *grad_pos, float iso, int n_batch, int n_vertex, int n_tet, int idx_batch,
+                                    void *stream);
+size_t deftet_tet_iso_measures_workspace_bytes(int n_batch);
+int deftet_tet_iso_measures_fwd_f32(const float *field, const float *pos, const int32_t *tet_idx, const float *weights, float *out, float iso,
+                                    int n_batch, int n_vertex, int n_tet, int idx_batch, void *workspace, size_t workspace_bytes,
+                                    void *stream);
+int deftet_tet_iso_measures_bwd_f32(const float *grad_out, const float *weights, const float *field, const float *pos, const int32_t *tet_idx,
+                                    const int32_t *offsets, const int32_t *slots, float *grad_field, float *grad_pos, float iso, int n_batch,
+                                    int n_vertex, int n_tet, int idx_batch, void *stream);
 
 #ifdef __cplusplus
 }
