@@ -209,6 +209,12 @@ SIGNATURES = {
     "deftet_tet_iso_measures_workspace_bytes": (_sz, [_i]),
     "deftet_tet_iso_measures_fwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp, _sz, _vp]),
     "deftet_tet_iso_measures_bwd_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp]),
+    "deftet_loop_topology_workspace_bytes": (_sz, [_i, _i]),
+    "deftet_loop_topology_count_i64": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "deftet_loop_topology_fill_i64": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "deftet_loop_subdivide_fwd_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "deftet_loop_subdivide_bwd_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp,
+                                           _vp]),
 }
 
 _lock = threading.Lock()

@@ -2218,6 +2218,236 @@ def marching_tets(pos, field, topology, iso=0.0, attr=None, return_index=False):
     return IsoMesh(split(verts, 0), split(faces, 1), split(vattr, 0), split(edge_id, 0), split(t, 0), split(tet_id, 1))
 
 
+# --------------------------------------------------------------------------------- Loop subdivision
+LOOP_SUBDIVIDE, LOOP_LIMIT = 0, 1                                    # the `mode` of deftet_loop_subdivide_fwd_f32 / _bwd_f32
+
+
+class LoopTopology:
+    """The topology of a triangle list for loop_subdivide / loop_limit, built once and reused (like TetEdges / FaceTopology), all
+    integers on the GPU: `faces` int64 [F,3]; `edges` int32 [E,2], the unique undirected edges as (min,max) in lexicographic
+    order; `face_edge` int32 [F,3], the edge ids of the local edges (f0,f1), (f1,f2), (f2,f0); `edge_nface` int32 [E], the number
+    of (face, local edge) incidences; `edge_opp` int32 [E,2], the two opposite corners of an edge with exactly two incidences in
+    ascending 3*f+k, (-1,-1) otherwise — such an edge is a CREASE (boundary and non-manifold alike); `vertex_kind` uint8 [V]: 0
+    smooth (no crease edge, isolated vertices included), 1 crease (exactly two crease edges), 2 corner; `crease_nbr` int32 [V,2],
+    the far ends of a crease vertex's two crease edges in ascending edge id, -1 otherwise; the vertex -> edge-end CSR
+    `ev_offsets` int32 [V+1], `ev_slots` int32 [2E] (2*e+side) and the vertex -> face-corner CSR `fv_offsets`, `fv_slots` int32
+    [3F] (3*f+corner), both ascending per vertex; `child_faces` int64 [4F,3], rows 4f..4f+3 = (a,mab,mca), (b,mbc,mab),
+    (c,mca,mbc), (mab,mbc,mca) with m.. = V + the edge id (winding kept) — the faces of the subdivided mesh, whose V+E vertices
+    are the old ones followed by one per edge.  IndexError for an index outside [0, n_vertex); ValueError for a face that names
+    a vertex twice, for F = 0, n_vertex <= 0, V+E >= 2^31 or 4F >= 2^31.  One read-back (E and the flags; with `vertex_offsets`,
+    the ascending vertex ranges [S+1] of disjoint shapes in one list, also `edge_offsets`, the S+1 first edge ids of the shapes).
+    A snapshot of the list it was built from.  `device`: where to put a host list."""
+
+    def __init__(self, faces_fx3, n_vertex, device=None, vertex_offsets=None):
+        faces = torch.as_tensor(faces_fx3)
+        if device is not None:
+            faces = faces.to(device)
+        _lib.require_gpu(faces)
+        if faces.dim() != 2 or faces.shape[1] != 3:
+            raise RuntimeError("LoopTopology: faces [F,3] expected, got %s" % (tuple(faces.shape),))
+        faces = faces.to(dtype=torch.int64, copy=True).contiguous()   # ours: later in-place edits of the caller's list do not reach it
+        F, V, dev = int(faces.shape[0]), int(n_vertex), faces.device
+        if F == 0 or V <= 0:
+            raise ValueError("LoopTopology: an empty face list or no vertices")
+        if 4 * F >= 2 ** 31 or V >= 2 ** 31:
+            raise ValueError("LoopTopology: 4 * n_face = %d or n_vertex = %d does not fit 31 bits" % (4 * F, V))
+        lib = _lib.load()
+        S = 0 if vertex_offsets is None else len(vertex_offsets) - 1
+        voff = host_ints(vertex_offsets, dev, i32=True) if S else None
+        counts = torch.empty(3 + (S + 1 if S else 0), dtype=torch.int32, device=dev)
+        # the count pass leaves the sorted incidences in its workspace for the fill pass: a tensor of this call, not the shared one
+        ws = torch.empty(lib.deftet_loop_topology_workspace_bytes(V, F), dtype=torch.uint8, device=dev)
+        _lib.call("deftet_loop_topology_count_i64", dev, faces, F, V, voff, S, counts, ws=ws)
+        c = counts.tolist()                                              # the one sync
+        E = c[0]
+        if c[1]:
+            raise IndexError("LoopTopology: vertex index outside [0, %d)" % V)
+        if c[2]:
+            raise ValueError("LoopTopology: a face names a vertex twice")
+        if V + E >= 2 ** 31:
+            raise ValueError("LoopTopology: n_vertex + n_edge = %d does not fit 31 bits" % (V + E))
+
+        def i32(*shape):
+            return torch.empty(*shape, dtype=torch.int32, device=dev)
+        self.edges, self.face_edge, self.edge_nface, self.edge_opp = i32(E, 2), i32(F, 3), i32(E), i32(E, 2)
+        self.vertex_kind, self.crease_nbr = torch.empty(V, dtype=torch.uint8, device=dev), i32(V, 2)
+        self.ev_offsets, self.ev_slots, self.fv_offsets, self.fv_slots = i32(V + 1), i32(2 * E), i32(V + 1), i32(3 * F)
+        self.child_faces = torch.empty(4 * F, 3, dtype=torch.int64, device=dev)
+        _lib.call("deftet_loop_topology_fill_i64", dev, faces, F, V, E, self.edges, self.face_edge, self.edge_nface, self.edge_opp,
+                  self.vertex_kind, self.crease_nbr, self.ev_offsets, self.ev_slots, self.fv_offsets, self.fv_slots, self.child_faces, ws=ws)
+        self.faces, self.n_vertex, self.n_face, self.n_edge, self.n_vertex_out, self.device = faces, V, F, E, V + E, dev
+        self.edge_offsets = c[3:] if S else None
+
+
+def _loop_tables(top):
+    return (top.edges, top.edge_nface, top.edge_opp, top.vertex_kind, top.crease_nbr, top.ev_offsets, top.ev_slots)
+
+
+class _LoopSubdivide(torch.autograd.Function):
+    """(verts [B,V,3], attr [B,V,C] | None) -> (verts' [B,R,3], attr' [B,R,C] | None), R = V+E (mode 0) or V (mode 1, the limit)"""
+
+    @staticmethod
+    def forward(ctx, verts, attr, topology, mode):
+        top = topology
+        B, V, E, dev = int(verts.shape[0]), top.n_vertex, top.n_edge, verts.device
+        C = 0 if attr is None else int(attr.shape[2])
+        R = V + E if mode == LOOP_SUBDIVIDE else V
+        out = torch.empty(B, R, 3, dtype=torch.float32, device=dev)
+        oattr = torch.empty(B, R, C, dtype=torch.float32, device=dev) if C else None
+        _lib.call("deftet_loop_subdivide_fwd_f32", dev, verts, attr, C, *_loop_tables(top), B, V, E, mode, out, oattr)
+        ctx.topology, ctx.mode, ctx.shape = top, mode, (B, C)
+        ctx.set_materialize_grads(False)
+        return out, oattr
+
+    @staticmethod
+    def backward(ctx, g_verts, g_attr):
+        top, mode, (B, C) = ctx.topology, ctx.mode, ctx.shape
+        V, dev = top.n_vertex, top.device
+        want_v, want_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and C > 0
+        if not want_v:
+            g_verts = None
+        if not want_a:
+            g_attr = None
+        gv = ga = None
+        if g_verts is not None or g_attr is not None:
+            g_verts, g_attr = (None if g is None else _f32c(g) for g in (g_verts, g_attr))
+            gv = torch.empty(B, V, 3, dtype=torch.float32, device=dev) if g_verts is not None else None
+            ga = torch.empty(B, V, C, dtype=torch.float32, device=dev) if g_attr is not None else None
+            _lib.call("deftet_loop_subdivide_bwd_f32", dev, g_verts, g_attr, C, *_loop_tables(top), top.face_edge, top.fv_offsets,
+                      top.fv_slots, B, V, top.n_edge, top.n_face, mode, gv, ga)
+        if want_v and gv is None:
+            gv = torch.zeros(B, V, 3, dtype=torch.float32, device=dev)
+        if want_a and ga is None:
+            ga = torch.zeros(B, V, C, dtype=torch.float32, device=dev)
+        return gv, ga, None, None
+
+
+def _loop_apply(caller, verts, topology, attr, mode):
+    if not isinstance(topology, LoopTopology):
+        raise TypeError("%s: topology must be a hip_ops.LoopTopology (built once per face list)" % caller)
+    if attr is not None and (attr.dim() not in (2, 3) or not 1 <= int(attr.shape[-1]) <= 8):
+        raise _lib.DefTetHipError("%s: attr [B,V,C] with 1 <= C <= 8 expected, got %s (DEFTET_EINVAL)" % (caller, tuple(attr.shape)))
+    _lib.require_gpu(verts, attr)
+    V = topology.n_vertex
+    p = _f32c(verts)
+    single = p.dim() == 2
+    if single:
+        p = p[None]
+    if p.dim() != 3 or tuple(p.shape[1:]) != (V, 3) or p.device != topology.device:
+        raise RuntimeError("%s: verts [B,%d,3] or [%d,3] on %s expected, got %s" % (caller, V, V, topology.device, tuple(verts.shape)))
+    B = int(p.shape[0])
+    a = None
+    if attr is not None:
+        a = _f32c(attr)
+        if a.numel() != B * V * int(a.shape[-1]) or a.device != p.device:
+            raise RuntimeError("%s: attr [%d,%d,C] on %s expected, got %s" % (caller, B, V, p.device, tuple(attr.shape)))
+        a = a.reshape(B, V, int(a.shape[-1]))
+    out, oattr = _LoopSubdivide.apply(p, a, topology, mode)
+    if single and verts.dim() == 2:
+        out, oattr = out[0], None if oattr is None else oattr[0]
+    return out, oattr
+
+
+def loop_subdivide(verts, topology, attr=None):
+    """One level of Loop subdivision: (verts' f32 [B,V+E,3], attr' f32 [B,V+E,C] | None) from verts f32 [B,V,3] (or [V,3]: the
+    results then come without the batch axis) and attr f32 [B,V,C], 1 <= C <= 8, on a LoopTopology.  Rows 0..V-1 are the
+    repositioned old vertices, row V+e is the vertex of edge e; the faces of the result are topology.child_faces.  Warren's
+    weights: an interior edge (a,b) with opposite corners (c,d) gives 3/8 (a+b) + 1/8 (c+d), a crease edge 1/2 (a+b); a smooth
+    vertex of valence n moves to (1 - n beta) v + beta sum of its neighbours, beta = 3/16 for n = 3 and 3/(8n) otherwise, a
+    crease vertex to 3/4 v + 1/8 (its two crease neighbours), a corner stays.  Attributes take the same weights.  Every sum in
+    fp32 in one order (own term, then the edge-end slots ascending); differentiable by the transpose, one gather per old vertex
+    over both CSRs: no atomics, the same bits on every run, for every batch size."""
+    return _loop_apply("loop_subdivide", verts, topology, attr, LOOP_SUBDIVIDE)
+
+
+def loop_limit(verts, topology, attr=None):
+    """The limit positions of the Loop surface at the vertices: (f32 [B,V,3], attr [B,V,C] | None).  Smooth: (1 - n gamma) v +
+    gamma sum of the neighbours, gamma = 1 / (n + 3/(8 beta)) (1/12 at n = 6, 1/5 at n = 3); crease: 2/3 v + 1/6 (the two crease
+    neighbours); corner: v.  Differentiable like loop_subdivide."""
+    return _loop_apply("loop_limit", verts, topology, attr, LOOP_LIMIT)
+
+
+def loop_subdivide_mesh(verts, faces, attr=None, levels=1, limit=False):
+    """`levels` rounds of loop_subdivide on one mesh (a batch [B,V,3] shares the faces): (verts, faces int64, attr | None).  One
+    LoopTopology (one read-back) per level; limit=True projects the last level's vertices to their limit positions."""
+    levels = operator.index(levels)
+    if levels < 0:
+        raise ValueError("loop_subdivide_mesh: levels = %d is negative" % levels)
+    _lib.require_gpu(verts, faces, attr)
+    top = None
+    for _ in range(levels):
+        top = LoopTopology(faces, int(verts.shape[-2]))
+        verts, attr = loop_subdivide(verts, top, attr)
+        faces = top.child_faces
+    if limit:
+        verts, attr = loop_limit(verts, LoopTopology(faces, int(verts.shape[-2])), attr)
+    return verts, faces, attr
+
+
+def loop_subdivide_list(verts_list, faces_list, attr_list=None, levels=1, limit=False):
+    """loop_subdivide_mesh for a ragged list of shapes (what marching_tets returns): (list of verts, list of faces, list of attr |
+    None), each shape's result bit for bit that of its own call.  The shapes are concatenated into one disjoint mesh with offset
+    indices: one topology build, one launch sequence and one read-back per level for the whole list.  Edges sort by (min,max) and
+    the shapes occupy ascending index ranges, so a shape's rows are two contiguous runs — its old vertices, its edge vertices —
+    and its faces are renumbered to local indices.  A shape without faces comes back as it is."""
+    levels = operator.index(levels)
+    if levels < 0:
+        raise ValueError("loop_subdivide_list: levels = %d is negative" % levels)
+    n = len(verts_list)
+    if len(faces_list) != n or (attr_list is not None and len(attr_list) != n):
+        raise RuntimeError("loop_subdivide_list: %d verts, %d faces%s" % (n, len(faces_list), "" if attr_list is None else ", %d attrs" % len(attr_list)))
+    verts_list, faces_list = list(verts_list), [f.long() for f in faces_list]
+    attr_list = None if attr_list is None else list(attr_list)
+    live = [i for i in range(n) if int(faces_list[i].shape[0]) > 0]
+    if not live or (levels == 0 and not limit):
+        return verts_list, faces_list, attr_list
+    _lib.require_gpu(*[verts_list[i] for i in live])
+    dev = verts_list[live[0]].device
+    vs, fs = [verts_list[i] for i in live], [faces_list[i] for i in live]
+    ats = None if attr_list is None else [attr_list[i] for i in live]
+
+    def offsets(counts):
+        out = [0]
+        for c in counts:
+            out.append(out[-1] + c)
+        return out
+
+    def per_element(values, counts):
+        """values[s] repeated counts[s] times, int64 on the device (no read-back: the total is known on the host)"""
+        return torch.repeat_interleave(host_ints(values, dev, i64=True), host_ints(counts, dev, i64=True), output_size=sum(counts))
+
+    for level in range(levels + (1 if limit else 0)):
+        nv, nf = [int(v.shape[0]) for v in vs], [int(f.shape[0]) for f in fs]
+        voff, foff = offsets(nv), offsets(nf)
+        V = voff[-1]
+        # one disjoint mesh: shape s on the vertex range voff[s] .. voff[s+1]
+        v, f = torch.cat(vs, 0), torch.cat(fs, 0) + per_element(voff[:-1], nf)[:, None]
+        a = None if ats is None else torch.cat(ats, 0)
+        top = LoopTopology(f, V, vertex_offsets=voff)
+        if level == levels:                                                   # the limit projection of the last level
+            v, a = loop_limit(v, top, a)
+            vs = [v[voff[s]:voff[s + 1]] for s in range(len(vs))]
+            ats = None if a is None else [a[voff[s]:voff[s + 1]] for s in range(len(vs))]
+            break
+        v, a = loop_subdivide(v, top, a)
+        eoff = top.edge_offsets
+        ne = [y - x for x, y in zip(eoff, eoff[1:])]
+        # row r of the fine mesh -> its index inside its shape: an old vertex r - voff[s], an edge vertex nv[s] + (r - V - eoff[s])
+        first = torch.cat([per_element(voff[:-1], nv), per_element([V + eoff[s] - nv[s] for s in range(len(vs))], ne)])
+        local = (torch.arange(V + top.n_edge, device=dev) - first)[top.child_faces]
+
+        def rows_of(x, s):
+            return torch.cat([x[voff[s]:voff[s + 1]], x[V + eoff[s]:V + eoff[s + 1]]], 0)
+        ats = None if a is None else [rows_of(a, s) for s in range(len(vs))]
+        vs = [rows_of(v, s) for s in range(len(vs))]
+        fs = [local[4 * foff[s]:4 * foff[s + 1]] for s in range(len(fs))]
+    for k, i in enumerate(live):
+        verts_list[i], faces_list[i] = vs[k], fs[k]
+        if attr_list is not None:
+            attr_list[i] = ats[k]
+    return verts_list, faces_list, attr_list
+
+
 # --------------------------------------------------------------------------------- rendering from the vertices (DESIGN.md section 6h)
 class FaceTopology:
     """A face list for face_gather, built once and reused (like TetTopology / VertexAdjacency): `faces` int64 [F,3] on the GPU

@@ -299,16 +299,24 @@ class DefTet(nn.Module):
         return hip_ops.iso_iou(self.field_measures(vertice_pos, tetrahedron_bxfx4, field, iso=iso, gt_occ_bxt=gt_occ_bxt))
 
     # --- the welded iso-surface of a per-TET occupancy: to the vertices, then marching tetrahedra
-    def iso_surface(self, vertice_pos, tetrahedron_bxfx4, pred_tet_occ, iso=0.5, volume_weighted=True):
+    def iso_surface(self, vertice_pos, tetrahedron_bxfx4, pred_tet_occ, iso=0.5, volume_weighted=True, subdivide=0):
         """hip_ops.IsoMesh (lists of B tensors) of the per-tet occupancy pred_tet_occ [B,T] / [B,T,1]: every vertex takes the mean
         of its incident tets' values (weighted by their volumes with volume_weighted, as constants) and hip_ops.marching_tets
         takes the level `iso` of that per-vertex field on the tet list's edges.  Differentiable in pred_tet_occ and vertice_pos.
-        The shapes share one tet list."""
+        The shapes share one tet list.  subdivide = n > 0: every shape's mesh after n rounds of Loop subdivision
+        (hip_ops.loop_subdivide_list: one topology build and one read-back per round for the whole batch), verts and faces only."""
+        levels = int(subdivide)
+        if levels < 0:
+            raise ValueError("iso_surface: subdivide = %d is negative" % levels)
         topo = _topology_for(tetrahedron_bxfx4, vertice_pos.shape[1])
         occ = pred_tet_occ.reshape(pred_tet_occ.shape[0], -1, 1)
         weights = hip_ops.tet_volumes(vertice_pos, topo.tet_idx32) if volume_weighted else None
         field = topo.to_vertices(occ, weights=weights)
-        return hip_ops.marching_tets(vertice_pos, field.squeeze(-1), topo.edges(), iso=iso)
+        mesh = hip_ops.marching_tets(vertice_pos, field.squeeze(-1), topo.edges(), iso=iso)
+        if levels:
+            verts, faces, _attr = hip_ops.loop_subdivide_list(mesh.verts, mesh.faces, None, levels=levels)
+            mesh = hip_ops.IsoMesh(verts, faces, None, None, None, None)
+        return mesh
 
     # --- A11 (each call evaluates the fused kernel and returns its own component)
     def volume_variance(self, tet_bxfx4x3, base_area_mask=None, area_normalize=(20, 20), pow=2, center_occ=None):

@@ -77,7 +77,7 @@ def _write(path, text):
 
 
 def save_surface_objs(points_px3, feat, tet_tx4, nbr, savedir, prefix, thresholds=(0.005, 0.05, 0.15, 0.25), welded=False,
-                      iso=None, keep_largest=False, min_component=0, fill_voids=False, normals=False):
+                      iso=None, keep_largest=False, min_component=0, fill_voids=False, normals=False, subdivide=0):
     """Writes what Deftet.saveobj writes (3_model/deftet.py:533-557): for every threshold `tet-geo-<prefix>-thres-<t>.obj` and
     `tet-color-<prefix>-thres-<t>.obj`.  `feat` = (weights [P] / [P,1], colours [P,3]) as `processfunc` returns them, or one
     [P,4] tensor holding them side by side; the colours are written reversed (colorsnp_px3[:, ::-1], :513).  The per-tet
@@ -95,7 +95,12 @@ def save_surface_objs(points_px3, feat, tet_tx4, nbr, savedir, prefix, threshold
     goes to surface_extract as `occ`.  With all three left at their defaults nothing of this runs.  The `mt-` files are not
     cleaned: a per-vertex field has no per-tet mask.  normals=True (with iso): the `mt-geo` file also carries one `vn` line per
     vertex — the unit outward normal, minus the normalised gradient of the weights (hip_ops.vertex_field_gradient) interpolated
-    along the crossing edge, zero where that gradient is zero — and its faces read `f a//a b//b c//c`."""
+    along the crossing edge, zero where that gradient is zero — and its faces read `f a//a b//b c//c`.  subdivide = n > 0 (with
+    iso): the `mt-` files hold the mesh after n rounds of Loop subdivision (hip_ops.loop_subdivide_mesh), colours and normals
+    weighted like the positions, the normals normalised again; with 0 nothing of it runs."""
+    levels = int(subdivide)
+    if levels < 0:
+        raise ValueError("save_surface_objs: subdivide = %d is negative" % levels)
     if isinstance(feat, (tuple, list)):
         weights, colours = feat
     else:
@@ -137,7 +142,14 @@ def save_surface_objs(points_px3, feat, tet_tx4, nbr, savedir, prefix, threshold
             grad = hip_ops.vertex_field_gradient(w.reshape(1, -1, 1), pts[None], tet)
             attr = torch.cat([col, grad.reshape(-1, 3)], dim=1)
         mesh = hip_ops.marching_tets(pts, w, hip_ops.TetEdges(tet, pts.shape[0]), iso=iso, attr=attr)
-        v, f, c = mesh.verts[0].detach(), mesh.faces[0][:, [0, 2, 1]], mesh.vert_attr[0].detach()     # (the writer swaps them back)
+        v, f, c = mesh.verts[0].detach(), mesh.faces[0], mesh.vert_attr[0].detach()
+        if levels and f.shape[0]:
+            if normals:                                               # unit normals go in, and are normalised again below
+                c = torch.cat([c[:, :3], hip_ops.unit_normals(c[:, 3:6])], dim=1)
+            v, f, c = hip_ops.loop_subdivide_mesh(v, f, c, levels=levels)
+            if normals:                                               # (unit_normals below negates: these are normals already)
+                c = torch.cat([c[:, :3], -c[:, 3:6]], dim=1)
+        f = f[:, [0, 2, 1]]                                           # (the writer swaps them back)
         if normals:
             c, vn = c[:, :3], hip_ops.unit_normals(c[:, 3:6])
         paths.append("%s/mt-geo-%s-iso-%.3f.obj" % (savedir, prefix, iso))

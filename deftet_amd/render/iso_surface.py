@@ -15,16 +15,37 @@ def model_tet_edges(model, n_vertex, device):
     return kept[1]
 
 
-def marching_tets(model, iso, processfunc, return_index=False):
+def _subdivided(mesh, levels, normals=False):
+    """the one-shape IsoMesh `mesh` after `levels` rounds of Loop subdivision (hip_ops.loop_subdivide_mesh): verts, faces and
+    vert_attr of the fine mesh; normals: vert_attr holds directions, normalised again after the weighting"""
+    verts, faces, attr = hip_ops.loop_subdivide_mesh(mesh.verts, mesh.faces, mesh.vert_attr, levels=levels)
+    if normals:
+        attr = hip_ops.unit_normals(-attr)                            # (unit_normals negates: these are normals already)
+    return hip_ops.IsoMesh(verts, faces, attr, None, None, None)
+
+
+def _levels(subdivide, return_index=False):
+    levels = int(subdivide)
+    if levels < 0:
+        raise ValueError("subdivide = %d is negative" % levels)
+    if levels and return_index:
+        raise ValueError("return_index describes the coarse mesh: its edge ids do not describe a subdivided one (subdivide = %d)" % levels)
+    return levels
+
+
+def marching_tets(model, iso, processfunc, return_index=False, subdivide=0):
     """hip_ops.IsoMesh of a reference-shaped `model` (get_point(True), get_feat(), tftet_tx4) at the level `iso` of the
     per-vertex weights: (weights [P,1], colours [P,C]) = processfunc(points, features) as in saveobj (:509-510).  The fields are
     tensors of the one shape, not lists: verts [Nv,3], faces int64 [Nf,3], vert_attr [Nv,C] = the colours at the vertices.
-    Differentiable in whatever points, weights and colours depend on."""
+    Differentiable in whatever points, weights and colours depend on.  subdivide = n > 0: the mesh after n rounds of Loop
+    subdivision (4^n times the faces; the colours take the positions' weights); not with return_index (ValueError)."""
+    levels = _levels(subdivide, return_index)
     points = model.get_point(True)
     weights, colours = processfunc(points, model.get_feat())
     topology = model_tet_edges(model, points.shape[0], points.device)
     mesh = hip_ops.marching_tets(points, weights.reshape(1, -1), topology, iso=iso, attr=colours, return_index=return_index)
-    return hip_ops.IsoMesh(*[None if x is None else x[0] for x in mesh])
+    mesh = hip_ops.IsoMesh(*[None if x is None else x[0] for x in mesh])
+    return _subdivided(mesh, levels) if levels and mesh.faces.shape[0] else mesh
 
 
 def model_tet_csr(model, n_vertex, device):
@@ -40,11 +61,13 @@ def model_tet_csr(model, n_vertex, device):
     return kept[2], kept[3]
 
 
-def marching_tets_normals(model, iso, processfunc):
+def marching_tets_normals(model, iso, processfunc, subdivide=0):
     """marching_tets(model, iso, processfunc) with vert_attr [Nv,3] holding the unit OUTWARD normal instead of the colours: the
     per-vertex gradient of the weights (hip_ops.vertex_field_gradient, the volume-weighted mean of the tets' gradients)
     interpolated along each crossing edge, normalised and negated — inside is weights > iso, so the field falls towards the
-    outside.  A zero gradient gives a zero normal.  Differentiable like marching_tets."""
+    outside.  A zero gradient gives a zero normal.  Differentiable like marching_tets.  subdivide = n > 0: n rounds of Loop
+    subdivision, the normals weighted like the positions and normalised again."""
+    levels = _levels(subdivide)
     points = model.get_point(True)
     weights, _colours = processfunc(points, model.get_feat())
     P, dev = points.shape[0], points.device
@@ -52,4 +75,5 @@ def marching_tets_normals(model, iso, processfunc):
     grad = hip_ops.vertex_field_gradient(weights.reshape(1, P, 1), points.reshape(1, P, 3), idx, csr=csr)
     mesh = hip_ops.marching_tets(points, weights.reshape(1, -1), model_tet_edges(model, P, dev), iso=iso, attr=grad.reshape(1, P, 3))
     mesh = mesh._replace(vert_attr=[hip_ops.unit_normals(a) for a in mesh.vert_attr])
-    return hip_ops.IsoMesh(*[None if x is None else x[0] for x in mesh])
+    mesh = hip_ops.IsoMesh(*[None if x is None else x[0] for x in mesh])
+    return _subdivided(mesh, levels, normals=True) if levels and mesh.faces.shape[0] else mesh

@@ -48,6 +48,8 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
+/* 410: Loop subdivision of triangle surfaces — deftet_loop_topology_count_i64, deftet_loop_topology_fill_i64 with
+ *      deftet_loop_topology_workspace_bytes, deftet_loop_subdivide_fwd_f32 / _bwd_f32 (loop_subdivide.hip). */
 /* 400: iso-solid measures on the tets — deftet_tet_iso_fraction_fwd_f32 / _bwd_f32, deftet_tet_iso_measures_fwd_f32 / _bwd_f32 with
  *      deftet_tet_iso_measures_workspace_bytes (tet_iso_measure.hip). */
 /* 390: field gradients on the tets — deftet_tet_field_gradient_fwd_f32 / _bwd_f32, deftet_tet_field_energies_fwd_f32 / _bwd_f32 with
@@ -1245,6 +1247,45 @@ int deftet_tet_iso_measures_fwd_f32(const float *field, const float *pos, const 
 int deftet_tet_iso_measures_bwd_f32(const float *grad_out, const float *weights, const float *field, const float *pos, const int32_t *tet_idx,
                                     const int32_t *offsets, const int32_t *slots, float *grad_field, float *grad_pos, float iso, int n_batch,
                                     int n_vertex, int n_tet, int idx_batch, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * Loop subdivision of triangle surfaces (410; loop_subdivide.hip).  faces int64 [F,3] over V vertices.  An
+ * edge with a number of (face, local edge) incidences other than 2 is a crease; a vertex with no crease edge is smooth (kind 0),
+ * with exactly two a crease vertex (kind 1), otherwise a corner (kind 2).  The rules and the orders of every fp32 sum stand in
+ * the file's header; no float atomics anywhere, so two runs, two batch sizes and two launch shapes give the same bits.
+ * deftet_loop_topology_count_i64: sorts the keys min V + max of the 3 F incidences 3 f + k (local edges (f0,f1), (f1,f2), (f2,f0))
+ *   and leaves the runs in the workspace for the fill entry.  counts i32 [3] = (n_edge, 1 if an index lies outside [0,V), 1 if a
+ *   face names a vertex twice); with shape_offsets i32 [n_shape + 1] (ascending vertex ranges of disjoint shapes; NULL and 0
+ *   otherwise) counts has 3 + n_shape + 1 entries, the further ones the first edge id of every shape and n_edge.
+ *   n_face > 0, n_vertex > 0, 4 n_face < 2^31 (DEFTET_EINVAL otherwise).
+ * deftet_loop_topology_fill_i64: with n_edge as read back (n_vertex + n_edge < 2^31) and the SAME workspace: edges i32 [E,2]
+ *   (min,max) ascending, face_edge i32 [F,3], edge_nface i32 [E], edge_opp i32 [E,2] (the opposite corners of the two incidences in
+ *   ascending 3 f + k; -1 -1 for a crease), vertex_kind u8 [V], crease_nbr i32 [V,2] (kind 1: the far ends of the two crease
+ *   edges in ascending edge id; -1 otherwise), the CSRs of deftet_edge_vertex_csr_i32 over the edges (ev_offsets i32 [V+1],
+ *   ev_slots i32 [2E]) and of deftet_face_vertex_csr_i32 over the faces (fv_offsets i32 [V+1], fv_slots i32 [3F]), child_faces
+ *   int64 [4F,3]: (a,mab,mca), (b,mbc,mab), (c,mca,mbc), (mab,mbc,mca) with m.. = V + the edge id.
+ * deftet_loop_subdivide_fwd_f32: verts f32 [B,V,3], attr f32 [B,V,C] (0 <= C <= 8; NULL with C = 0).  mode 0 = subdivide:
+ *   out_verts f32 [B,V+E,3], out_attr f32 [B,V+E,C], rows 0..V-1 the old vertices, row V + e the vertex of edge e; mode 1 =
+ *   limit positions: [B,V,..].  One launch, one lane per output row.
+ * deftet_loop_subdivide_bwd_f32: the transpose.  grad_out_verts / grad_out_attr (each optional, shaped as the forward's outputs)
+ *   taken to grad_verts f32 [B,V,3] / grad_attr f32 [B,V,C] (present exactly where its source is; every element written).  One
+ *   launch, one lane per old vertex over both CSRs. */
+size_t deftet_loop_topology_workspace_bytes(int n_vertex, int n_face);
+int deftet_loop_topology_count_i64(const int64_t *faces, int n_face, int n_vertex, const int32_t *shape_offsets, int n_shape,
+                                   int32_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+int deftet_loop_topology_fill_i64(const int64_t *faces, int n_face, int n_vertex, int n_edge, int32_t *edges, int32_t *face_edge,
+                                  int32_t *edge_nface, int32_t *edge_opp, uint8_t *vertex_kind, int32_t *crease_nbr,
+                                  int32_t *ev_offsets, int32_t *ev_slots, int32_t *fv_offsets, int32_t *fv_slots, int64_t *child_faces,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+int deftet_loop_subdivide_fwd_f32(const float *verts, const float *attr, int n_attr, const int32_t *edges, const int32_t *edge_nface,
+                                  const int32_t *edge_opp, const uint8_t *vertex_kind, const int32_t *crease_nbr,
+                                  const int32_t *ev_offsets, const int32_t *ev_slots, int n_batch, int n_vertex, int n_edge, int mode,
+                                  float *out_verts, float *out_attr, void *stream);
+int deftet_loop_subdivide_bwd_f32(const float *grad_out_verts, const float *grad_out_attr, int n_attr, const int32_t *edges,
+                                  const int32_t *edge_nface, const int32_t *edge_opp, const uint8_t *vertex_kind,
+                                  const int32_t *crease_nbr, const int32_t *ev_offsets, const int32_t *ev_slots,
+                                  const int32_t *face_edge, const int32_t *fv_offsets, const int32_t *fv_slots, int n_batch,
+                                  int n_vertex, int n_edge, int n_face, int mode, float *grad_verts, float *grad_attr, void *stream);
 
 #ifdef __cplusplus
 }
