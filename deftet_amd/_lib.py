@@ -215,6 +215,13 @@ SIGNATURES = {
     "deftet_loop_subdivide_fwd_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "deftet_loop_subdivide_bwd_f32": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp,
                                            _vp]),
+    "deftet_mesh_components_workspace_bytes": (_sz, [_i, _i, _i]),
+    "deftet_mesh_components_i64": (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "deftet_mesh_cleanup_count_i64": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, C.c_double, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _vp, _vp, _vp, _sz, _vp]),
+    "deftet_mesh_cleanup_fill_i64": (_i, [_vp, _i, _i, _vp, _vp, _i, _ll, _ll, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "deftet_mesh_gather_fwd_f32": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "deftet_mesh_gather_bwd_f32": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
 }
 
 _lock = threading.Lock()

@@ -130,7 +130,7 @@ extern "C" int deftet_profile_read(double *total_ms, long long *count)
     return DEFTET_OK;
 }
 
-extern "C" int deftet_version(void) { return 410; }   // 410: Loop subdivision of triangle surfaces: topology, operator, limit positions and their transpose (loop_subdivide.hip); 400: iso-solid measures on the tets: inside fraction, area, volume, intersection (tet_iso_measure.hip); 390: field gradients on the tets, their energies and tet-to-vertex means (tet_field_grad.hip); 380: conforming selective tet refinement (tet_refine.hip); 370: generalised winding numbers (winding_number.hip); 360: pixel-aligned image-feature sampling (image_sample.hip); 350: connected tet components and the occupancy clean-up (tet_components.hip); 340: per-vertex field sampling at located query points (tet_field_sample.hip); 330: tet-centroid feature sampling (tet_centroid_sample.hip); 320: marching tetrahedra (marching_tets.hip); 310: the ground-truth preparation entry points (dataprep.hip); 300: the wide-channel vertex aggregation (vertex_aggregate.hip); 290: the point-voxel entry points (pointvoxel.hip); 280: the render-from-vertices entry points (render_vertices.hip); 270: the surface extraction entry points; 260: the evaluation metrics entry points; 250: the vertex Laplacian entry points; 240: the fused rasterize-and-composite entry points; 230: the indexed point-in-tet entry points; 221: round 6, second half (8-byte hit records, deftet_point_in_tet_bwd_to_vertices_f32, deftet_put_host_ints); 220: round 6 (deftet_tet_order_coherence_f32); 210: round 5 (the *_ex_* entry points, tet order, query box + misses)
+extern "C" int deftet_version(void) { return 420; }   // 420: connected components of a triangle list, their measures, the mesh clean-up and its gather (mesh_components.hip); 410: Loop subdivision of triangle surfaces: topology, operator, limit positions and their transpose (loop_subdivide.hip); 400: iso-solid measures on the tets: inside fraction, area, volume, intersection (tet_iso_measure.hip); 390: field gradients on the tets, their energies and tet-to-vertex means (tet_field_grad.hip); 380: conforming selective tet refinement (tet_refine.hip); 370: generalised winding numbers (winding_number.hip); 360: pixel-aligned image-feature sampling (image_sample.hip); 350: connected tet components and the occupancy clean-up (tet_components.hip); 340: per-vertex field sampling at located query points (tet_field_sample.hip); 330: tet-centroid feature sampling (tet_centroid_sample.hip); 320: marching tetrahedra (marching_tets.hip); 310: the ground-truth preparation entry points (dataprep.hip); 300: the wide-channel vertex aggregation (vertex_aggregate.hip); 290: the point-voxel entry points (pointvoxel.hip); 280: the render-from-vertices entry points (render_vertices.hip); 270: the surface extraction entry points; 260: the evaluation metrics entry points; 250: the vertex Laplacian entry points; 240: the fused rasterize-and-composite entry points; 230: the indexed point-in-tet entry points; 221: round 6, second half (8-byte hit records, deftet_point_in_tet_bwd_to_vertices_f32, deftet_put_host_ints); 220: round 6 (deftet_tet_order_coherence_f32); 210: round 5 (the *_ex_* entry points, tet order, query box + misses)
 
 extern "C" const char *deftet_last_error(void) { return deftet::err_buf(); }
 

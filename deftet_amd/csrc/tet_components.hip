@@ -28,6 +28,7 @@
 // largest surviving component, the smaller label among equals: a 64-bit max of size << 32 | ~label), k_tc_keep.
 // Every loop has a trip bound in the code; a chain that breaks the invariant or a loop that runs out is counted in `bad`.
 #include "common.hpp"
+#include "union_find.hpp"
 #include "wave.hpp"
 
 namespace deftet {
@@ -36,39 +37,8 @@ namespace tc {
 constexpr int kThreads = 256;
 constexpr unsigned kOpenBit = 0x80000000u, kSizeMask = 0x7FFFFFFFu;
 
-__device__ __forceinline__ int pload(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// root of x with every visited node shortened to its grandparent; -1 (and one count in bad) when the chain does not descend
-__device__ __forceinline__ int find_root(int *par, int x, int *bad)
-{
-    const int limit = x;                                               // a descending chain from x has at most x links
-    int p = pload(par + x);
-    for (int step = 0; p != x; ++step) {
-        if ((unsigned)p > (unsigned)x || step > limit) { atomicAdd(bad, 1); return -1; }  // (p in [0, x) from here on)
-        const int gp = pload(par + p);
-        if (gp != p && (unsigned)gp < (unsigned)p)
-            __hip_atomic_fetch_min(par + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = p;
-        p = gp;
-    }
-    return x;
-}
-
-// a failure re-reads the roots: they only ever move down, so ra + rb falls with every trip and 2 T + 2 trips cannot be used up
-__device__ __forceinline__ void unite(int *par, int a, int b, int trips, int *bad)
-{
-    for (int k = 0; k < trips; ++k) {
-        int ra = find_root(par, a, bad), rb = find_root(par, b, bad);
-        if (ra < 0 || rb < 0 || ra == rb) return;
-        if (ra > rb) { const int s = ra; ra = rb; rb = s; }
-        int expect = rb;
-        if (__hip_atomic_compare_exchange_strong(par + rb, &expect, ra, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-            return;
-        a = ra;
-        b = rb;
-    }
-    atomicAdd(bad, 1);
-}
+using uf::find_root;                                                  // union_find.hpp: the invariant, the hook, the shortening
+using uf::unite;
 
 __device__ __forceinline__ bool is_in(const unsigned char *in, int t, int invert) { return (in[t] != 0) != (invert != 0); }
 

@@ -2448,6 +2448,290 @@ def loop_subdivide_list(verts_list, faces_list, attr_list=None, levels=1, limit=
     return verts_list, faces_list, attr_list
 
 
+# --------------------------------------------------------------------------------- components of a triangle surface, its clean-up
+MESH_EDGE, MESH_VERTEX = 0, 1                                        # the `connectivity` of deftet_mesh_components_i64
+MESH_BY_FACES, MESH_BY_AREA = 0, 1                                   # the `largest_by` of deftet_mesh_cleanup_count_i64
+_MESH_CONNECTIVITY = {"edge": MESH_EDGE, "vertex": MESH_VERTEX}
+_MESH_LARGEST_BY = {"faces": MESH_BY_FACES, "area": MESH_BY_AREA}
+
+
+class MeshComponents(collections.namedtuple("MeshComponents", "labels count n_face area volume boundary_edges nonmanifold_edges "
+                                                              "misoriented_edges")):
+    """The connected components of a triangle list (mesh_components), all on the device: labels int32 [F], the smallest face
+    index of every face's component; count int32 [S], components per shape; and at the label's index, 0 elsewhere: n_face,
+    boundary_edges, nonmanifold_edges, misoriented_edges int32 [F], area and volume float64 [F] (None without verts)."""
+    __slots__ = ()
+
+    @property
+    def closed(self):
+        """bool [F], at the label's index: the component has no boundary, non-manifold or misoriented edge"""
+        return (self.n_face > 0) & (self.boundary_edges == 0) & (self.nonmanifold_edges == 0) & (self.misoriented_edges == 0)
+
+
+CleanMesh = collections.namedtuple("CleanMesh", "verts faces attr vertex_map face_map components")
+
+
+def _mesh_choice(caller, what, value, table):
+    if value not in table:
+        raise ValueError("%s: %s = %r is none of %s" % (caller, what, value, ", ".join(repr(k) for k in table)))
+    return table[value]
+
+
+def _surface_mesh_args(caller, faces, n_vertex, verts, face_offsets, vertex_offsets):
+    """(faces int64 [F,3] contiguous, verts f32 [V,3] | None, F, V, face offsets, vertex offsets: host lists of S + 1 entries)"""
+    if not isinstance(faces, torch.Tensor):
+        raise _expected(caller, "faces: an integer tensor [F,3]", type(faces).__name__)
+    _lib.require_gpu(faces, verts)
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype not in (torch.int64, torch.int32):
+        raise _expected(caller, "faces int64 [F,3]", "%s %s" % (faces.dtype, tuple(faces.shape)))
+    F, V = int(faces.shape[0]), int(n_vertex)
+    if 3 * F >= 2 ** 31 or V >= 2 ** 31:
+        raise ValueError("%s: 3 * n_face = %d or n_vertex = %d does not fit 31 bits" % (caller, 3 * F, V))
+    if V < 0 or (F > 0 and V == 0):
+        raise ValueError("%s: n_vertex = %d with %d faces" % (caller, V, F))
+    if verts is not None and (verts.dim() != 2 or tuple(verts.shape) != (V, 3) or verts.dtype != torch.float32 or verts.device != faces.device):
+        raise _expected(caller, "verts float32 [%d,3] on %s" % (V, faces.device), "%s %s on %s" % (verts.dtype, tuple(verts.shape), verts.device))
+    if (face_offsets is None) != (vertex_offsets is None):
+        raise ValueError("%s: face_offsets and vertex_offsets go together" % caller)
+    foff = [0, F] if face_offsets is None else [int(x) for x in face_offsets]
+    voff = [0, V] if vertex_offsets is None else [int(x) for x in vertex_offsets]
+    for name, off, end in (("face_offsets", foff, F), ("vertex_offsets", voff, V)):
+        if len(off) < 2 or len(off) != len(foff) or off[0] != 0 or off[-1] != end or any(y < x for x, y in zip(off, off[1:])):
+            raise ValueError("%s: %s must ascend from 0 to %d with one entry per shape and one more, got %s" % (caller, name, end, off))
+    return faces.to(torch.int64).contiguous(), (None if verts is None else verts.contiguous()), F, V, foff, voff
+
+
+def _mesh_raise(caller, flags, V):
+    """the flags of the labelling, read back: out of range, a vertex named twice, a broken union-find"""
+    if flags[0]:
+        raise IndexError("%s: vertex index outside [0, %d)" % (caller, V))
+    if flags[1]:
+        raise ValueError("%s: a face names a vertex twice" % caller)
+    if flags[2]:
+        raise RuntimeError("%s: the union-find met a broken chain or ran out of its trip bound (%d times)" % (caller, flags[2]))
+
+
+def _mesh_components_out(F, S, dev, measures):
+    def i32(n):
+        return torch.empty(n, dtype=torch.int32, device=dev)
+
+    def f64():
+        return torch.empty(F, dtype=torch.float64, device=dev) if measures else None
+    # in the order of the C entries: labels, n_face, boundary, non-manifold, misoriented, area, volume, count
+    return [i32(F), i32(F), i32(F), i32(F), i32(F), f64(), f64(), torch.zeros(S, dtype=torch.int32, device=dev) if F == 0 else i32(S)]
+
+
+def _mesh_components_result(parts):
+    labels, n_face, bnd, nm, mis, area, volume, count = parts
+    return MeshComponents(labels, count, n_face, area, volume, bnd, nm, mis)
+
+
+def mesh_components(faces, n_vertex, verts=None, connectivity="edge", check=True, face_offsets=None, vertex_offsets=None):
+    """Connected components of a triangle list: MeshComponents(labels, count, n_face, area, volume, boundary_edges,
+    nonmanifold_edges, misoriented_edges), all on the device.  faces int64 [F,3] over n_vertex vertices (F = 0 gives empty
+    results).  connectivity "edge": two faces are connected when they share an undirected vertex pair, whatever the number of
+    faces that meet on it (the three faces of a book are one piece, a bow-tie is two); "vertex": when they share a vertex (the
+    bow-tie is one).  labels int32 [F] = the SMALLEST face index of the component, so the result does not depend on the
+    schedule.  At the label's index, 0 elsewhere: n_face; boundary_edges (edges with one incidence), nonmanifold_edges (more
+    than two), misoriented_edges (two incidences running the same direction); with verts float32 [V,3] also area = sum 1/2
+    |(b-a) x (c-a)| and volume = sum a . (b x c) / 6 as float64, every term in double from the widened positions and summed in
+    an order that depends on the component's own ascending face list only (no float atomics: the same bits on every run, next
+    to whatever other components).  `closed` = the three edge counts are 0.  count int32 [S] = components per shape:
+    face_offsets / vertex_offsets (S + 1 ascending host integers each) describe S disjoint shapes in one list, as
+    loop_subdivide_list concatenates them; one shape without them.
+    Nothing of the results is read back.  The flags are (twelve bytes, check=True): IndexError for an index outside
+    [0, n_vertex) — such a corner is counted and never followed —, ValueError for a face that names a vertex twice,
+    RuntimeError for a broken union-find.  ValueError for 3 F >= 2^31 or n_vertex >= 2^31."""
+    caller = "mesh_components"
+    conn = _mesh_choice(caller, "connectivity", connectivity, _MESH_CONNECTIVITY)
+    f, v, F, V, foff, _voff = _surface_mesh_args(caller, faces, n_vertex, verts, face_offsets, vertex_offsets)
+    S, dev = len(foff) - 1, f.device
+    parts = _mesh_components_out(F, S, dev, v is not None)
+    if F == 0:
+        return _mesh_components_result(parts)
+    lib = _lib.load()
+    flags = torch.empty(3, dtype=torch.int32, device=dev)
+    _lib.call("deftet_mesh_components_i64", dev, f, F, V, v, host_ints(foff, dev, i32=True), S, conn, *parts, flags,
+              ws=lib.deftet_mesh_components_workspace_bytes(V, F, S))
+    if check:
+        _mesh_raise(caller, flags.tolist(), V)
+    return _mesh_components_result(parts)
+
+
+class _MeshGather(torch.autograd.Function):
+    """(verts [V,3], attr [V,C] | None) -> their rows at vertex_map [V'] (ascending, injective)"""
+
+    @staticmethod
+    def forward(ctx, verts, attr, vertex_map):
+        V, Vk, dev = int(verts.shape[0]), int(vertex_map.shape[0]), verts.device
+        C = 0 if attr is None else int(attr.shape[1])
+        out = torch.empty(Vk, 3, dtype=torch.float32, device=dev)
+        oattr = torch.empty(Vk, C, dtype=torch.float32, device=dev) if C else None
+        _lib.call("deftet_mesh_gather_fwd_f32", dev, verts, attr, C, vertex_map, V, Vk, out, oattr)
+        ctx.save_for_backward(vertex_map)
+        ctx.shape = (V, C)
+        ctx.set_materialize_grads(False)
+        return out, oattr
+
+    @staticmethod
+    def backward(ctx, g_verts, g_attr):
+        (vertex_map,) = ctx.saved_tensors
+        V, C = ctx.shape
+        Vk, dev = int(vertex_map.shape[0]), vertex_map.device
+        want_v, want_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1] and C > 0
+        if not want_v:
+            g_verts = None
+        if not want_a:
+            g_attr = None
+        gv = ga = None
+        if g_verts is not None or g_attr is not None:
+            g_verts, g_attr = (None if g is None else _f32c(g) for g in (g_verts, g_attr))
+            gv = torch.empty(V, 3, dtype=torch.float32, device=dev) if g_verts is not None else None
+            ga = torch.empty(V, C, dtype=torch.float32, device=dev) if g_attr is not None else None
+            _lib.call("deftet_mesh_gather_bwd_f32", dev, g_verts, g_attr, C, vertex_map, V, Vk, gv, ga)
+        if want_v and gv is None:
+            gv = torch.zeros(V, 3, dtype=torch.float32, device=dev)
+        if want_a and ga is None:
+            ga = torch.zeros(V, C, dtype=torch.float32, device=dev)
+        return gv, ga, None
+
+
+def _mesh_cleanup_flat(caller, verts, faces, attr, face_offsets, vertex_offsets, keep_largest, min_faces, min_area, drop_voids, largest_by,
+                       connectivity, return_components):
+    """the clean-up of one face list of S disjoint shapes: (verts', faces' numbered inside their shapes, attr', vertex_map,
+    face_map — old indices of the whole list —, MeshComponents | None, kept-face offsets, kept-vertex offsets: host lists)"""
+    conn = _mesh_choice(caller, "connectivity", connectivity, _MESH_CONNECTIVITY)
+    by = _mesh_choice(caller, "largest_by", largest_by, _MESH_LARGEST_BY)
+    min_faces, min_area = operator.index(min_faces), float(min_area)
+    if min_faces < 0 or not min_area >= 0.0:
+        raise ValueError("%s: min_faces = %d or min_area = %r is negative" % (caller, min_faces, min_area))
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 2:
+        raise _expected(caller, "verts float32 [V,3]", verts if isinstance(verts, torch.Tensor) else type(verts).__name__)
+    _lib.require_gpu(verts, attr)
+    f, v, F, V, foff, voff = _surface_mesh_args(caller, faces, int(verts.shape[0]), verts, face_offsets, vertex_offsets)
+    S, dev = len(foff) - 1, f.device
+    a = None
+    if attr is not None:
+        if attr.dim() != 2 or int(attr.shape[0]) != V or not 1 <= int(attr.shape[1]) <= 8 or attr.dtype != torch.float32 or attr.device != dev:
+            raise _expected(caller, "attr float32 [%d,C] with 1 <= C <= 8 on %s" % (V, dev), "%s %s on %s" % (attr.dtype, tuple(attr.shape), attr.device))
+        a = attr.contiguous()
+    if F == 0:                                                                # nothing to label: the mesh comes back as it is
+        comps = _mesh_components_result(_mesh_components_out(0, S, dev, True)) if return_components else None
+        every = torch.arange(V, dtype=torch.int64, device=dev)
+        return v, f, a, every, torch.empty(0, dtype=torch.int64, device=dev), comps, [0] * (S + 1), list(voff)
+    lib = _lib.load()
+    measures = bool(drop_voids) or min_area > 0.0 or (bool(keep_largest) and by == MESH_BY_AREA) or bool(return_components)
+    parts = _mesh_components_out(F, S, dev, measures)
+    counts = torch.empty(3 + 2 * (S + 1), dtype=torch.int32, device=dev)
+    foff_d, voff_d = host_ints(foff, dev, i32=True), host_ints(voff, dev, i32=True)
+    # the count pass leaves its scans in the workspace for the fill pass: a tensor of this call, not the shared one
+    ws = torch.empty(lib.deftet_mesh_components_workspace_bytes(V, F, S), dtype=torch.uint8, device=dev)
+    _lib.call("deftet_mesh_cleanup_count_i64", dev, f, F, V, v if measures else None, foff_d, voff_d, S, conn, int(bool(keep_largest)),
+              min_faces, min_area, int(bool(drop_voids)), by, *parts, counts, ws=ws)
+    c = counts.tolist()                                                       # the one read-back: flags and offsets
+    _mesh_raise(caller, c[:3], V)
+    fo, vo = c[3:3 + S + 1], c[3 + S + 1:]
+    Fk, Vk = fo[-1], vo[-1]
+    faces_out = torch.empty(Fk, 3, dtype=torch.int64, device=dev)
+    vertex_map = torch.empty(Vk, dtype=torch.int64, device=dev)
+    face_map = torch.empty(Fk, dtype=torch.int64, device=dev)
+    if Fk:
+        _lib.call("deftet_mesh_cleanup_fill_i64", dev, f, F, V, foff_d, voff_d, S, Fk, Vk, faces_out, vertex_map, face_map, ws=ws)
+        v_out, a_out = _MeshGather.apply(v, a, vertex_map)
+    else:
+        v_out, a_out = v[:0], None if a is None else a[:0]
+    return v_out, faces_out, a_out, vertex_map, face_map, (_mesh_components_result(parts) if return_components else None), fo, vo
+
+
+def mesh_cleanup(verts, faces, attr=None, keep_largest=False, min_faces=0, min_area=0.0, drop_voids=False, largest_by="faces",
+                 connectivity="edge", return_components=False):
+    """Cleans a triangle surface on the device and compacts it: CleanMesh(verts, faces, attr, vertex_map, face_map, components).
+    verts float32 [V,3], faces int64 [F,3], attr float32 [V,C] (1 <= C <= 8) or None.  One device sequence in this order, nothing
+    read back in between: the faces are labelled and measured (mesh_components); drop_voids drops every CLOSED component with
+    volume < 0 — marching_tets orients normals from inside to outside, so the shell of an enclosed cavity encloses negative
+    volume; min_faces = m > 0 drops the components with fewer than m faces; min_area = a > 0 those with area < a;
+    keep_largest keeps, of what is left, the component with the most faces (largest_by="faces", integers only) or the largest
+    area (largest_by="area"), the smaller label among equals; an empty mesh stays empty.  drop_voids alone leaves a floater
+    INSIDE a cavity in place: with its cavity gone it becomes a shell inside the solid, which keep_largest or min_faces removes.
+    Kept faces stay in ascending old index and are renumbered; vertices that no kept face references are dropped, the others
+    stay in ascending old index: the ascending edge-id and tet-id orders of marching_tets survive.  vertex_map int64 [V'] and
+    face_map int64 [F'] hold the old indices; verts' = verts[vertex_map] and attr' = attr[vertex_map] come from one launch and
+    are differentiable (the backward copies the gradient rows to the kept vertices and writes zeros everywhere else: no atomic,
+    no sum).  components (return_components=True): the MeshComponents of the input list, the labelling the selection was made
+    on.  One read-back per call: the counts together with the flags (IndexError / ValueError / RuntimeError as in
+    mesh_components).  A mesh without faces comes back as it is."""
+    v, f, a, vmap, fmap, comps, _fo, _vo = _mesh_cleanup_flat("mesh_cleanup", verts, faces, attr, None, None, keep_largest, min_faces, min_area,
+                                                             drop_voids, largest_by, connectivity, return_components)
+    return CleanMesh(v, f, a, vmap, fmap, comps)
+
+
+def mesh_cleanup_list(mesh_or_verts, faces_list=None, attr_list=None, keep_largest=False, min_faces=0, min_area=0.0, drop_voids=False,
+                      largest_by="faces", connectivity="edge", return_maps=False):
+    """mesh_cleanup for a ragged list of shapes: an IsoMesh as marching_tets returns it, or lists of verts, faces and (optionally)
+    attrs.  The shapes are concatenated into one disjoint mesh with offset indices: one launch sequence and ONE read-back for
+    the whole batch; then they are cut back out, every shape bit for bit what its own mesh_cleanup call gives (a component's
+    sums depend on its own face list only).  Returns an IsoMesh of lists; edge_id, t and tet_id of the input, where present,
+    are indexed through the maps.  return_maps=True: (IsoMesh, list of vertex_map, list of face_map), local to the shapes.
+    Shapes with no faces pass through unchanged."""
+    caller = "mesh_cleanup_list"
+    if isinstance(mesh_or_verts, IsoMesh):
+        if faces_list is not None or attr_list is not None:
+            raise RuntimeError("%s: an IsoMesh brings its own faces and attributes" % caller)
+        verts_list, faces_list, attr_list, edge_id, t, tet_id = mesh_or_verts
+    else:
+        verts_list, edge_id, t, tet_id = mesh_or_verts, None, None, None
+    if faces_list is None:
+        raise RuntimeError("%s: lists of verts and faces (or an IsoMesh) expected" % caller)
+    n = len(verts_list)
+    for name, other in (("faces", faces_list), ("attrs", attr_list), ("edge_id", edge_id), ("t", t), ("tet_id", tet_id)):
+        if other is not None and len(other) != n:
+            raise RuntimeError("%s: %d verts, %d %s" % (caller, n, len(other), name))
+    # checked before any shape is skipped: a wrong option is wrong for an empty batch as well
+    _mesh_choice(caller, "connectivity", connectivity, _MESH_CONNECTIVITY)
+    _mesh_choice(caller, "largest_by", largest_by, _MESH_LARGEST_BY)
+    verts_out, faces_out = list(verts_list), list(faces_list)
+    attr_out = None if attr_list is None else list(attr_list)
+    edge_out, t_out, tet_out = (None if x is None else list(x) for x in (edge_id, t, tet_id))
+    live = [i for i in range(n) if int(faces_list[i].shape[0]) > 0]
+    vmaps = [None] * n
+    fmaps = [None] * n
+    if live:
+        nv, nf = [int(verts_list[i].shape[0]) for i in live], [int(faces_list[i].shape[0]) for i in live]
+        voff, foff = [0], [0]
+        for x, y in zip(nv, nf):
+            voff.append(voff[-1] + x)
+            foff.append(foff[-1] + y)
+        _lib.require_gpu(*[verts_list[i] for i in live])
+        dev = verts_list[live[0]].device
+        first = torch.repeat_interleave(host_ints(voff[:-1], dev, i64=True), host_ints(nf, dev, i64=True), output_size=foff[-1])
+        v = torch.cat([verts_list[i] for i in live], 0)
+        f = torch.cat([faces_list[i].long() for i in live], 0) + first[:, None]
+        a = None if attr_list is None else torch.cat([attr_list[i] for i in live], 0)
+        v2, f2, a2, vmap, fmap, _comps, fo, vo = _mesh_cleanup_flat(caller, v, f, a, foff, voff, keep_largest, min_faces, min_area, drop_voids,
+                                                                    largest_by, connectivity, False)
+        for s, i in enumerate(live):
+            vs, fs = slice(vo[s], vo[s + 1]), slice(fo[s], fo[s + 1])
+            verts_out[i], faces_out[i] = v2[vs], f2[fs]
+            if attr_out is not None:
+                attr_out[i] = a2[vs]
+            vmaps[i], fmaps[i] = vmap[vs] - voff[s], fmap[fs] - foff[s]
+            if edge_out is not None:
+                edge_out[i] = edge_id[i][vmaps[i]]
+            if t_out is not None:
+                t_out[i] = t[i][vmaps[i]]
+            if tet_out is not None:
+                tet_out[i] = tet_id[i][fmaps[i]]
+    out = IsoMesh(verts_out, faces_out, attr_out, edge_out, t_out, tet_out)
+    if not return_maps:
+        return out
+    for i in range(n):
+        if vmaps[i] is None:                                                  # a shape without faces: as it is
+            dev = verts_list[i].device
+            vmaps[i] = torch.arange(int(verts_list[i].shape[0]), dtype=torch.int64, device=dev)
+            fmaps[i] = torch.empty(0, dtype=torch.int64, device=dev)
+    return out, vmaps, fmaps
+
+
 # --------------------------------------------------------------------------------- rendering from the vertices (DESIGN.md section 6h)
 class FaceTopology:
     """A face list for face_gather, built once and reused (like TetTopology / VertexAdjacency): `faces` int64 [F,3] on the GPU

@@ -299,12 +299,16 @@ class DefTet(nn.Module):
         return hip_ops.iso_iou(self.field_measures(vertice_pos, tetrahedron_bxfx4, field, iso=iso, gt_occ_bxt=gt_occ_bxt))
 
     # --- the welded iso-surface of a per-TET occupancy: to the vertices, then marching tetrahedra
-    def iso_surface(self, vertice_pos, tetrahedron_bxfx4, pred_tet_occ, iso=0.5, volume_weighted=True, subdivide=0):
+    def iso_surface(self, vertice_pos, tetrahedron_bxfx4, pred_tet_occ, iso=0.5, volume_weighted=True, subdivide=0, keep_largest=False, min_faces=0,
+                    drop_voids=False):
         """hip_ops.IsoMesh (lists of B tensors) of the per-tet occupancy pred_tet_occ [B,T] / [B,T,1]: every vertex takes the mean
         of its incident tets' values (weighted by their volumes with volume_weighted, as constants) and hip_ops.marching_tets
         takes the level `iso` of that per-vertex field on the tet list's edges.  Differentiable in pred_tet_occ and vertice_pos.
         The shapes share one tet list.  subdivide = n > 0: every shape's mesh after n rounds of Loop subdivision
-        (hip_ops.loop_subdivide_list: one topology build and one read-back per round for the whole batch), verts and faces only."""
+        (hip_ops.loop_subdivide_list: one topology build and one read-back per round for the whole batch), verts and faces only.
+        keep_largest / min_faces / drop_voids clean every shape's mesh on the device BEFORE the subdivision (hip_ops.mesh_cleanup_list:
+        cavity shells and floaters dropped, one launch sequence and one read-back for the whole batch); with all three left at
+        their defaults nothing of it runs."""
         levels = int(subdivide)
         if levels < 0:
             raise ValueError("iso_surface: subdivide = %d is negative" % levels)
@@ -313,6 +317,8 @@ class DefTet(nn.Module):
         weights = hip_ops.tet_volumes(vertice_pos, topo.tet_idx32) if volume_weighted else None
         field = topo.to_vertices(occ, weights=weights)
         mesh = hip_ops.marching_tets(vertice_pos, field.squeeze(-1), topo.edges(), iso=iso)
+        if bool(keep_largest) or int(min_faces) > 0 or bool(drop_voids):
+            mesh = hip_ops.mesh_cleanup_list(mesh, keep_largest=keep_largest, min_faces=min_faces, drop_voids=drop_voids)
         if levels:
             verts, faces, _attr = hip_ops.loop_subdivide_list(mesh.verts, mesh.faces, None, levels=levels)
             mesh = hip_ops.IsoMesh(verts, faces, None, None, None, None)

@@ -77,7 +77,8 @@ def _write(path, text):
 
 
 def save_surface_objs(points_px3, feat, tet_tx4, nbr, savedir, prefix, thresholds=(0.005, 0.05, 0.15, 0.25), welded=False,
-                      iso=None, keep_largest=False, min_component=0, fill_voids=False, normals=False, subdivide=0):
+                      iso=None, keep_largest=False, min_component=0, fill_voids=False, normals=False, subdivide=0,
+                      iso_keep_largest=False, iso_min_faces=0, iso_drop_voids=False):
     """Writes what Deftet.saveobj writes (3_model/deftet.py:533-557): for every threshold `tet-geo-<prefix>-thres-<t>.obj` and
     `tet-color-<prefix>-thres-<t>.obj`.  `feat` = (weights [P] / [P,1], colours [P,3]) as `processfunc` returns them, or one
     [P,4] tensor holding them side by side; the colours are written reversed (colorsnp_px3[:, ::-1], :513).  The per-tet
@@ -93,11 +94,16 @@ def save_surface_objs(points_px3, feat, tet_tx4, nbr, savedir, prefix, threshold
     the per-tet occupancy is then a torch maximum over the corner weights (the fused maximum, bit for bit, on finite weights),
     inside = occ > float32(2 thres) — the threshold mode's own inside test — a dropped tet gets 0, a filled one 1, and the result
     goes to surface_extract as `occ`.  With all three left at their defaults nothing of this runs.  The `mt-` files are not
-    cleaned: a per-vertex field has no per-tet mask.  normals=True (with iso): the `mt-geo` file also carries one `vn` line per
+    cleaned: a per-vertex field has no per-tet mask (by these three, that is: iso_keep_largest / iso_min_faces / iso_drop_voids below
+    clean them as a mesh).  normals=True (with iso): the `mt-geo` file also carries one `vn` line per
     vertex — the unit outward normal, minus the normalised gradient of the weights (hip_ops.vertex_field_gradient) interpolated
     along the crossing edge, zero where that gradient is zero — and its faces read `f a//a b//b c//c`.  subdivide = n > 0 (with
     iso): the `mt-` files hold the mesh after n rounds of Loop subdivision (hip_ops.loop_subdivide_mesh), colours and normals
-    weighted like the positions, the normals normalised again; with 0 nothing of it runs."""
+    weighted like the positions, the normals normalised again; with 0 nothing of it runs.
+    iso_keep_largest / iso_min_faces / iso_drop_voids (with iso) are the way to clean the `mt-` files: the marching-tetrahedra
+    mesh goes through hip_ops.mesh_cleanup on the device before the subdivision — cavity shells (closed components of negative
+    volume) and floaters dropped, the mesh compacted, colours and normals carried along.  They leave the `tet-` files alone, as
+    keep_largest / min_component / fill_voids leave the `mt-` files; with all three left at their defaults nothing of it runs."""
     levels = int(subdivide)
     if levels < 0:
         raise ValueError("save_surface_objs: subdivide = %d is negative" % levels)
@@ -143,6 +149,9 @@ def save_surface_objs(points_px3, feat, tet_tx4, nbr, savedir, prefix, threshold
             attr = torch.cat([col, grad.reshape(-1, 3)], dim=1)
         mesh = hip_ops.marching_tets(pts, w, hip_ops.TetEdges(tet, pts.shape[0]), iso=iso, attr=attr)
         v, f, c = mesh.verts[0].detach(), mesh.faces[0], mesh.vert_attr[0].detach()
+        if (bool(iso_keep_largest) or int(iso_min_faces) > 0 or bool(iso_drop_voids)) and f.shape[0]:
+            clean = hip_ops.mesh_cleanup(v, f, c, keep_largest=iso_keep_largest, min_faces=iso_min_faces, drop_voids=iso_drop_voids)
+            v, f, c = clean.verts, clean.faces, clean.attr
         if levels and f.shape[0]:
             if normals:                                               # unit normals go in, and are normalised again below
                 c = torch.cat([c[:, :3], hip_ops.unit_normals(c[:, 3:6])], dim=1)

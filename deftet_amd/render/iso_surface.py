@@ -33,18 +33,31 @@ def _levels(subdivide, return_index=False):
     return levels
 
 
-def marching_tets(model, iso, processfunc, return_index=False, subdivide=0):
+def _cleaned(mesh, keep_largest, min_faces, drop_voids):
+    """the one-shape IsoMesh `mesh` after hip_ops.mesh_cleanup; with every option off, or without faces, `mesh` itself"""
+    if not (bool(keep_largest) or int(min_faces) > 0 or bool(drop_voids)) or not mesh.faces.shape[0]:
+        return mesh
+    clean = hip_ops.mesh_cleanup(mesh.verts, mesh.faces, mesh.vert_attr, keep_largest=keep_largest, min_faces=min_faces, drop_voids=drop_voids)
+    edge_id, t, tet_id = (None if x is None else x[m] for x, m in ((mesh.edge_id, clean.vertex_map), (mesh.t, clean.vertex_map),
+                                                                   (mesh.tet_id, clean.face_map)))
+    return hip_ops.IsoMesh(clean.verts, clean.faces, clean.attr, edge_id, t, tet_id)
+
+
+def marching_tets(model, iso, processfunc, return_index=False, subdivide=0, keep_largest=False, min_faces=0, drop_voids=False):
     """hip_ops.IsoMesh of a reference-shaped `model` (get_point(True), get_feat(), tftet_tx4) at the level `iso` of the
     per-vertex weights: (weights [P,1], colours [P,C]) = processfunc(points, features) as in saveobj (:509-510).  The fields are
     tensors of the one shape, not lists: verts [Nv,3], faces int64 [Nf,3], vert_attr [Nv,C] = the colours at the vertices.
     Differentiable in whatever points, weights and colours depend on.  subdivide = n > 0: the mesh after n rounds of Loop
-    subdivision (4^n times the faces; the colours take the positions' weights); not with return_index (ValueError)."""
+    subdivision (4^n times the faces; the colours take the positions' weights); not with return_index (ValueError).
+    keep_largest / min_faces / drop_voids clean the mesh on the device BEFORE the subdivision (hip_ops.mesh_cleanup: cavity shells
+    and floaters dropped, the mesh compacted, still differentiable); with return_index the rows of edge_id, t and tet_id are
+    those of the kept vertices and faces.  With all three left at their defaults nothing of it runs."""
     levels = _levels(subdivide, return_index)
     points = model.get_point(True)
     weights, colours = processfunc(points, model.get_feat())
     topology = model_tet_edges(model, points.shape[0], points.device)
     mesh = hip_ops.marching_tets(points, weights.reshape(1, -1), topology, iso=iso, attr=colours, return_index=return_index)
-    mesh = hip_ops.IsoMesh(*[None if x is None else x[0] for x in mesh])
+    mesh = _cleaned(hip_ops.IsoMesh(*[None if x is None else x[0] for x in mesh]), keep_largest, min_faces, drop_voids)
     return _subdivided(mesh, levels) if levels and mesh.faces.shape[0] else mesh
 
 
@@ -61,12 +74,13 @@ def model_tet_csr(model, n_vertex, device):
     return kept[2], kept[3]
 
 
-def marching_tets_normals(model, iso, processfunc, subdivide=0):
+def marching_tets_normals(model, iso, processfunc, subdivide=0, keep_largest=False, min_faces=0, drop_voids=False):
     """marching_tets(model, iso, processfunc) with vert_attr [Nv,3] holding the unit OUTWARD normal instead of the colours: the
     per-vertex gradient of the weights (hip_ops.vertex_field_gradient, the volume-weighted mean of the tets' gradients)
     interpolated along each crossing edge, normalised and negated — inside is weights > iso, so the field falls towards the
     outside.  A zero gradient gives a zero normal.  Differentiable like marching_tets.  subdivide = n > 0: n rounds of Loop
-    subdivision, the normals weighted like the positions and normalised again."""
+    subdivision, the normals weighted like the positions and normalised again.  keep_largest / min_faces / drop_voids: the
+    clean-up of marching_tets, before the subdivision."""
     levels = _levels(subdivide)
     points = model.get_point(True)
     weights, _colours = processfunc(points, model.get_feat())
@@ -75,5 +89,5 @@ def marching_tets_normals(model, iso, processfunc, subdivide=0):
     grad = hip_ops.vertex_field_gradient(weights.reshape(1, P, 1), points.reshape(1, P, 3), idx, csr=csr)
     mesh = hip_ops.marching_tets(points, weights.reshape(1, -1), model_tet_edges(model, P, dev), iso=iso, attr=grad.reshape(1, P, 3))
     mesh = mesh._replace(vert_attr=[hip_ops.unit_normals(a) for a in mesh.vert_attr])
-    mesh = hip_ops.IsoMesh(*[None if x is None else x[0] for x in mesh])
+    mesh = _cleaned(hip_ops.IsoMesh(*[None if x is None else x[0] for x in mesh]), keep_largest, min_faces, drop_voids)
     return _subdivided(mesh, levels, normals=True) if levels and mesh.faces.shape[0] else mesh

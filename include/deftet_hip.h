@@ -48,6 +48,9 @@ extern "C" {
 #define DEFTET_PIT_WAVE 4    /* a wave stages the candidates of its 64 tets in LDS, filter-only per-tet setup (k_tet_scan_wave) */
 #define DEFTET_PIT_PAIR 5    /* the same with two tets per lane: a wave stages once for 128 tets (k_tet_scan_pair; measured slower, never AUTO) */
 
+/* 420: connected components of a triangle list, their measures and the mesh clean-up — deftet_mesh_components_i64,
+ *      deftet_mesh_cleanup_count_i64, deftet_mesh_cleanup_fill_i64 with deftet_mesh_components_workspace_bytes,
+ *      deftet_mesh_gather_fwd_f32 / _bwd_f32 (mesh_components.hip). */
 /* 410: Loop subdivision of triangle surfaces — deftet_loop_topology_count_i64, deftet_loop_topology_fill_i64 with
  *      deftet_loop_topology_workspace_bytes, deftet_loop_subdivide_fwd_f32 / _bwd_f32 (loop_subdivide.hip). */
 /* 400: iso-solid measures on the tets — deftet_tet_iso_fraction_fwd_f32 / _bwd_f32, deftet_tet_iso_measures_fwd_f32 / _bwd_f32 with
@@ -1286,6 +1289,50 @@ int deftet_loop_subdivide_bwd_f32(const float *grad_out_verts, const float *grad
                                   const int32_t *crease_nbr, const int32_t *ev_offsets, const int32_t *ev_slots,
                                   const int32_t *face_edge, const int32_t *fv_offsets, const int32_t *fv_slots, int n_batch,
                                   int n_vertex, int n_edge, int n_face, int mode, float *grad_verts, float *grad_attr, void *stream);
+
+/* ---------------------------------------------------------------------------------
+ * Connected components of a triangle list, their measures and the mesh clean-up (420; mesh_components.hip).
+ * faces int64 [F,3] over V vertices; n_shape >= 1 disjoint shapes in one list, face_offsets / vertex_offsets i32 [n_shape + 1]
+ * their ascending ranges (one shape: (0, F) and (0, V)).  connectivity 0 = "edge": two faces are connected when they share an
+ * undirected vertex pair, whatever the number of faces on it; 1 = "vertex": when they share a vertex.  The label of a
+ * component is its smallest face index; every per-component result stands at the label's index and is 0 elsewhere.
+ * n_face > 0, n_vertex > 0, 3 n_face < 2^31 (DEFTET_EINVAL otherwise).  Integers wherever integers suffice and no float atomic:
+ * the same bits on every run.
+ * deftet_mesh_components_i64: labels i32 [F]; n_face, boundary_edges (edges with one incidence), nonmanifold_edges (more than
+ *   two), misoriented_edges (two incidences running the same direction) i32 [F]; count i32 [n_shape] components per shape;
+ *   with verts f32 [V,3] also area f64 [F] = sum 1/2 |(b-a) x (c-a)| and volume f64 [F] = sum a . (b x c) / 6, in double from the
+ *   widened positions, summed in an order that depends on the component's own ascending face list only (chunks of 256 from
+ *   the component's start, a fixed tree inside a chunk, the chunk sums in ascending order); area and volume NULL without verts.
+ *   flags i32 [3] = (corners outside [0,V), incidences that name one vertex twice, broken union-find chains or exhausted trip
+ *   bounds); such corners are never followed.
+ * deftet_mesh_cleanup_count_i64: the same, then on the device in this order: drop_voids drops every closed component (its
+ *   three edge counts 0) with volume < 0; min_faces = m > 0 drops components with fewer faces; min_area = a > 0 those with
+ *   area < a; keep_largest keeps per shape the survivor with the most faces (largest_by 0) or the largest area (1), the smaller
+ *   label among equals.  drop_voids, min_area and largest_by 1 need verts.  counts i32 [3 + 2 (n_shape + 1)]: the flags, then the
+ *   kept faces before every shape and their total, then the kept vertices (those a kept face references) likewise — the one
+ *   read-back.  The scans stay in the workspace for the fill entry.
+ * deftet_mesh_cleanup_fill_i64: with the totals as read back and the SAME workspace: faces_out int64 [F',3] in ascending old
+ *   index, numbered from its shape's first kept vertex; vertex_map int64 [V'] and face_map int64 [F'], the old indices, ascending.
+ * deftet_mesh_gather_fwd_f32: out_verts[r] = verts[vertex_map[r]], out_attr[r] = attr[vertex_map[r]] (0 <= C <= 8; NULL with
+ *   C = 0); one launch.  deftet_mesh_gather_bwd_f32: the transpose for an injective ascending map — grad rows copied to the kept
+ *   vertices, zeros everywhere else, every element written; each output present exactly where its source is; one launch. */
+size_t deftet_mesh_components_workspace_bytes(int n_vertex, int n_face, int n_shape);
+int deftet_mesh_components_i64(const int64_t *faces, int n_face, int n_vertex, const float *verts, const int32_t *face_offsets, int n_shape,
+                               int connectivity, int32_t *labels, int32_t *n_face_out, int32_t *boundary_edges,
+                               int32_t *nonmanifold_edges, int32_t *misoriented_edges, double *area, double *volume, int32_t *count,
+                               int32_t *flags, void *workspace, size_t workspace_bytes, void *stream);
+int deftet_mesh_cleanup_count_i64(const int64_t *faces, int n_face, int n_vertex, const float *verts, const int32_t *face_offsets,
+                                  const int32_t *vertex_offsets, int n_shape, int connectivity, int keep_largest, int min_faces,
+                                  double min_area, int drop_voids, int largest_by, int32_t *labels, int32_t *n_face_out,
+                                  int32_t *boundary_edges, int32_t *nonmanifold_edges, int32_t *misoriented_edges, double *area,
+                                  double *volume, int32_t *count, int32_t *counts, void *workspace, size_t workspace_bytes, void *stream);
+int deftet_mesh_cleanup_fill_i64(const int64_t *faces, int n_face, int n_vertex, const int32_t *face_offsets, const int32_t *vertex_offsets,
+                                 int n_shape, long long n_face_out, long long n_vertex_out, int64_t *faces_out, int64_t *vertex_map,
+                                 int64_t *face_map, void *workspace, size_t workspace_bytes, void *stream);
+int deftet_mesh_gather_fwd_f32(const float *verts, const float *attr, int n_attr, const int64_t *vertex_map, int n_vertex, int n_vertex_out,
+                               float *out_verts, float *out_attr, void *stream);
+int deftet_mesh_gather_bwd_f32(const float *grad_out_verts, const float *grad_out_attr, int n_attr, const int64_t *vertex_map, int n_vertex,
+                               int n_vertex_out, float *grad_verts, float *grad_attr, void *stream);
 
 #ifdef __cplusplus
 }
